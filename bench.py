@@ -12,16 +12,21 @@ trajectory b on stream b.  The timed steps are the reference's own workload mix:
 solve_steps (one Rocketland.solve_problem, rocketland.jl:432-443) the batch is put back to create_initial
 on the device (scvx_batch_reset: straight-line guess + linearisation, enqueued on the same stream and
 inside the timed region, not counted as a step), so rejection runs do not pile up beyond what solve_problem sees.
-Timed region: `--warmup` untimed steps, the batch put back to create_initial, then WHOLE solve_problem periods -- `--steps`
-rounded up to a multiple of imax-1 = 14 (the JSON line carries both `steps`, what was timed, and `steps_requested`): the cost of a
-step varies 10x along a period (cold solves early, one-iteration warm solves after rejected steps), so only whole periods
-starting at position 0 give a figure that does not depend on the window (`--no-reset` / `--exact-steps` time exactly `--steps`).
+Timed region: `--warmup` untimed steps, the batch put back to create_initial, then exactly `--steps` solve_steps from position 0 of
+a solve_problem (`steps` in the JSON line).  The cost of a step varies 10x along a period (cold solves early, one-iteration warm solves
+after rejected steps), so only whole periods give a figure that does not depend on the window: the default `--steps 14` is one
+period, and `--whole-periods` rounds `--steps` up to a multiple of imax-1 = 14 (`steps_requested` then keeps what was asked).
+`--exact-steps` starts the timed region where the warm-up left off instead of at position 0.
+A plain run prints the headline and what the timed region itself recorded.  `--full` adds every other figure: the K1 roofline
+launches and sweeps, the parity runs against the oracle, the solver variants, the 3-DoF initialiser, the CPU baseline and, at N > 1,
+the weak-scaling run.  `--dump-outputs DIR` writes the arrays the timed path left after its last step as DIR/<name>.npy (float64).
 Scaling: at N = 1 the batch is 8192.  At N > 1 the default is BASELINE configs[3] as written -- STRONG scaling of the global batch
-8192 (1024 per GPU at N = 8) -- with the weak figure (8192 per GPU) timed beside it in the same line (`weak_scaling`);
+8192 (1024 per GPU at N = 8) -- and with `--full` the weak figure (8192 per GPU) is timed beside it in the same line (`weak_scaling`);
 `--batch b` alone = weak scaling only, `--global-batch G` = strong scaling only.
 Arithmetic: fp64 throughout.
 
-Launch:  python bench.py --gpus N --steps K --warmup W      (N > 1 without WORLD_SIZE in the environment: this process starts N
+Launch:  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                             (N > 1 without WORLD_SIZE in the environment: this process starts N
                                                              rank processes itself, before anything touches the GPU, and
                                                              forwards rank 0's line)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -39,7 +44,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK = 8.0e12  # B/s, MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters)
+HBM_PEAK = 8.0e12  # B/s, MI355X HBM3E spec (AMD's public MI355X chip-level parameters)
 
 
 def k1_alg_bytes(K, n_u=3, s=8):
@@ -359,9 +364,56 @@ def k4_traffic_model(tstats, launches):
             "source": "profiles/%s: %s" % (os.path.basename(f), m.get("source", ""))}
 
 
+def roofline_k1(cache, batch, torch, K, B, nu, npts, prof, nprof):
+    """`roofline_k1` of --full: priced on FULL launches (every trajectory linearised) -- K1 alone, 5 back-to-back launches at the
+    default npts on the batch's trajectories, HIP events on the stream it runs on -- beside the in-step mean of the timed region."""
+    k1_step_ms = prof["linearize"] / max(nprof, 1)   # in the step: launches skip the trajectories whose step was rejected
+    k1_full, _ = k1_by_npts(cache, batch, torch, K, B, npts, sweep=(npts,), with_f32=False)
+    k1_ms = k1_full[str(npts)]["ms"]
+    alg = k1_alg_bytes(K, nu) * B
+    achieved = alg / (k1_ms * 1e-3) if k1_ms > 0 else 0.0
+    traffic = k1_measured_traffic(B)
+    k1_flops = K1_FLOP_PER_SEG_SUBSTEP * K * npts * B
+    return {
+        "kernel": "scvx::linearize_pcp_kernel (K1, the discretisation kernel SURVEY 8d names; linearize_pc_kernel at npts <= 2; 2 % of the step)",
+        "bound": "fp64" if npts >= 3 else "hbm",
+        "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK, "traffic": traffic["bytes"] if traffic else None,
+        "traffic_source": traffic["source"] if traffic else None,
+        "traffic_per_launch_of_the_mix": ({"bytes": traffic.get("mix_bytes"), "source": traffic.get("mix_source"),
+                                           "note": "newest PMC passes over the bench mix: in-step launches skip rejected trajectories"}
+                                          if traffic and traffic.get("mix_bytes") else None),
+        "alg_bytes_per_launch": alg, "avg_launch_ms": k1_ms, "avg_ms_in_step": k1_step_ms,
+        "fp64_frac": (k1_flops / (k1_ms * 1e-3) / FP64_VECTOR_PEAK) if k1_ms > 0 else None,
+        "note": "avg_launch_ms = full launches (all trajectories); inside a step K1 skips trajectories whose step was rejected "
+                "(avg_ms_in_step).  K1 at rk4_npts=%d is FP64-FMA-bound, not HBM-bound (SURVEY 8d): fp64_frac = sparse flop count "
+                "(12 kflop per segment per substep) / 78.6 TFLOP/s vector peak; traffic from PMC in profiles/" % npts,
+    }
+
+
 SOCP_ALG_BYTES = 137 * 1024  # SURVEY.md 8d: K4 reads the linearisation and the iterate, writes the solution (per trajectory)
 FP64_VECTOR_PEAK = 78.6e12    # FLOP/s, AMD's public MI355X figure (SURVEY F8: not in the microarchitecture guide)
 K1_FLOP_PER_SEG_SUBSTEP = 12.0e3  # sparse count of the variational RK4 substep (DESIGN.md kernel table)
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20261016     # the fixed sample of trajectories kept when the whole batch does not fit
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (leading axis = trajectory) as out_dir/<name>.npy in float64.  When the batch does not fit
+    in DUMP_MAX_BYTES, the same fixed, seeded sample of trajectories is kept in every array, and its indices go to sample_index.npy."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_traj = sum(8 * a[0].size for a in arrays.values())
+    keep = np.arange(n)
+    if per_traj * n > DUMP_MAX_BYTES - 4096:                      # room for the .npy headers
+        m = (DUMP_MAX_BYTES - 4096) // (per_traj + 8)             # each kept trajectory: its rows + its index
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        arrays["sample_index"] = keep
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if name == "sample_index" else a[keep], dtype=np.float64))
 
 
 def self_launch(n):
@@ -415,13 +467,20 @@ def main():
     ap.add_argument("--config5", action="store_true", help="BASELINE configs[4] as named: 6-DoF + aero tables + the fin extension "
                     "(control_dim = 5, a BUILD-DEFINED model: the reference only sketches it in comments), K = 100, seed 20261005; NOT the headline workload")
     ap.add_argument("--no-reset", action="store_true", help="do not return to create_initial every imax-1 steps")
-    ap.add_argument("--exact-steps", action="store_true", help="time exactly --steps solve_steps instead of whole solve_problem periods")
+    ap.add_argument("--exact-steps", action="store_true", help="start the timed region where the warm-up left off, not at position 0 of a solve_problem")
+    ap.add_argument("--whole-periods", action="store_true", help="round --steps up to whole solve_problem periods (imax-1 = 14 steps)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: K1 roofline launches and sweeps, parity runs "
+                    "against the oracle, solver variants, the 3-DoF initialiser, the CPU baseline, the weak figure at N > 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the timed path left after its last step as "
+                    "DIR/<name>.npy (float64, a fixed sample of trajectories when the batch exceeds 64 MB)")
     ap.add_argument("--tol", type=float, default=0.0, help="solver tolerance of the headline run (default: the library's 1e-8)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traj-check", action="store_true", help="skip the B=1 full-solve parity figure (profiling runs)")
     ap.add_argument("--no-k1-sweep", action="store_true", help="skip the K1-by-npts leg (profiling runs)")
     ap.add_argument("--dump-gathered", default=None, help="rank 0 saves the gathered trajectory records [world*B][(K+1)*(14+NU)+1] as .npy (tests)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     explicit_batch = bool(args.batch)
     if not args.batch:
         args.batch = 32768 if args.config5 else 8192
@@ -472,9 +531,10 @@ def main():
         p = sp.base_prob_scaled
     K = p.K
     # N = 1: the batch.  N > 1: BASELINE configs[3] as written = STRONG scaling of the global batch (8192 -> 1024 per GPU at N = 8) is
-    # the headline, and the weak figure (--batch per GPU) is timed beside it; an explicit --batch / --global-batch picks one mode.
-    both_modes = world > 1 and not args.global_batch and not explicit_batch and not args.config5
-    if args.global_batch or both_modes:
+    # the headline, and with --full the weak figure (--batch per GPU) is timed beside it; an explicit --batch / --global-batch picks one mode.
+    default_strong = world > 1 and not args.global_batch and not explicit_batch and not args.config5
+    both_modes = default_strong and args.full
+    if args.global_batch or default_strong:
         scaling, total = "strong", (args.global_batch or args.batch)
     else:
         scaling, total = "weak", args.batch
@@ -504,8 +564,9 @@ def main():
         torch.cuda.synchronize()
 
     period = max(p.imax - 1, 1)
-    # whole solve_problem periods from position 0 (see the module docstring)
-    whole = not args.no_reset and not args.exact_steps
+    # exactly --steps from position 0; whole solve_problem periods only when asked for (see the module docstring)
+    at_zero = not args.no_reset and not args.exact_steps
+    whole = at_zero and args.whole_periods
     steps = ((args.steps + period - 1) // period) * period if whole else args.steps
 
     def timed_steps(bt, on_timed_start=None):
@@ -516,7 +577,7 @@ def main():
                 bt.reset()
             bt.solve_step_async()
             cnt += 1
-        if whole and cnt:
+        if at_zero and cnt:
             bt.reset()               # the timed region starts at position 0 of a solve_problem
             cnt = 0
         barrier()
@@ -542,7 +603,7 @@ def main():
     batch.set_profiling(False)
     tstats = batch.step_stats(reset=True)   # what the timed region executed (rank 0's shard)
     st_f, act_f, _ = batch.flags()
-    rec64 = batch.trajectory_record() if world == 1 and not args.no_traj_check else None   # for the f32_linearization leg
+    rec64 = batch.trajectory_record() if args.full and world == 1 and not args.no_traj_check else None   # for the f32_linearization leg
     done = B * steps  # every trajectory is stepped by every solve_step (failed ones are reported below, not hidden)
 
     # final trajectories: the only exchange step of the path -- one all-gather over RCCL
@@ -581,6 +642,18 @@ def main():
         elapsed, done_all = mc.reduce_clock(elapsed, done, dist, dev)
     else:
         done_all = done
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step: the trajectories (all of them, gathered, at N > 1) and, at N = 1,
+        # the per-trajectory scalars and flags of the batch
+        if dist is not None:
+            rec = gathered_arr.reshape(-1, gathered_arr.shape[-1]).cpu().numpy()
+            nx, nuk = (K + 1) * 14, (K + 1) * p.nu
+            outs = {"x": rec[:, :nx].reshape(-1, K + 1, 14), "u": rec[:, nx:nx + nuk].reshape(-1, K + 1, p.nu), "sigma": rec[:, -1]}
+        else:
+            x_o, u_o, s_o = batch.trajectory()
+            rk_o, cost_o, it_o = batch.scalars()
+            outs = {"x": x_o, "u": u_o, "sigma": s_o, "trust_radius": rk_o, "cost": cost_o, "iteration": it_o, "status": st_f, "active": act_f}
+        dump_outputs(args.dump_outputs, outs)
     weak = None
     if both_modes:
         # the weak-scaling figure beside the strong headline: `--batch` trajectories on EVERY GPU, same timed region, same clock rule
@@ -597,17 +670,8 @@ def main():
 
     if rank == 0:
         st, its, merit, pobj = batch.solver_stats()
-        k1_step_ms = prof["linearize"] / max(nprof, 1)   # in the step: launches skip the trajectories whose step was rejected
-        # `roofline_k1` is priced on FULL launches (every trajectory linearised): K1 alone, 5 back-to-back launches at the
-        # default npts on the batch's trajectories, HIP events on the stream it runs on
-        k1_full, _ = k1_by_npts(cache, batch, torch, K, B, args.npts, sweep=(args.npts,), with_f32=False)
-        k1_ms = k1_full[str(args.npts)]["ms"]
         k4_ms = prof["socp"] / max(nprof, 1)
-        alg = k1_alg_bytes(K, p.nu) * B
-        achieved = alg / (k1_ms * 1e-3) if k1_ms > 0 else 0.0
-        traffic = k1_measured_traffic(B)
         k4t = k4_traffic_model(tstats, nprof) if B == 8192 and K == 50 and p.nu == 3 else None
-        k1_flops = K1_FLOP_PER_SEG_SUBSTEP * K * args.npts * B
         # K4's algorithmic bytes per trajectory: the linearisation + the iterate in, the solution out = 137 KB at K = 50, NU = 3
         socp_alg = SOCP_ALG_BYTES if (K == 50 and p.nu == 3) else k1_alg_bytes(K, p.nu) + 8 * ((K + 1) * (14 + p.nu) + 1 + 14 * K)
         line = {
@@ -663,21 +727,6 @@ def main():
                 "parallelism": f"batch-sharded x{world}, {scaling} scaling", "traj_iters_timed": done_all, "all_gather_shape": gathered,
                 "all_gather": gather_how,
             },
-            "roofline_k1": {
-                "kernel": "scvx::linearize_pcp_kernel (K1, the discretisation kernel SURVEY 8d names; linearize_pc_kernel at npts <= 2; 2 % of the step)",
-                "bound": "fp64" if args.npts >= 3 else "hbm",
-                "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK, "traffic": traffic["bytes"] if traffic else None,
-                "traffic_source": traffic["source"] if traffic else None,
-                "traffic_per_launch_of_the_mix": ({"bytes": traffic.get("mix_bytes"), "source": traffic.get("mix_source"),
-                                                   "note": "newest PMC passes over the bench mix: in-step launches skip rejected trajectories"}
-                                                  if traffic and traffic.get("mix_bytes") else None),
-                "alg_bytes_per_launch": alg, "avg_launch_ms": k1_ms, "avg_ms_in_step": k1_step_ms,
-                "fp64_frac": (k1_flops / (k1_ms * 1e-3) / FP64_VECTOR_PEAK) if k1_ms > 0 else None,
-                "note": "avg_launch_ms = full launches (all trajectories); inside a step K1 skips trajectories whose step was rejected "
-                        "(avg_ms_in_step).  K1 at rk4_npts=%d is FP64-FMA-bound, not HBM-bound (SURVEY 8d): fp64_frac = sparse flop count "
-                        "(12 kflop per segment per substep) / 78.6 TFLOP/s vector peak; traffic from PMC in profiles/" % args.npts,
-            },
             "kernel_ms_per_step": {k: v / max(nprof, 1) for k, v in prof.items()},
             "timed_region": {
                 "solve_step_indices": [first_timed, first_timed + steps - 1],
@@ -719,14 +768,16 @@ def main():
                                        "failed_frac": float(np.mean((st != 0) & (st != 4))), "merit_max": float(np.max(merit)),
                                        "frozen_trajectories": int(np.sum(act_f == 0))},
         }
-        if world == 1 and not args.no_k1_sweep:
+        if args.full:
+            line["roofline_k1"] = roofline_k1(cache, batch, torch, K, B, p.nu, args.npts, prof, nprof)
+        if args.full and world == 1 and not args.no_k1_sweep:
             line["roofline_k1_by_npts"], line["roofline_k1_f32_by_npts"] = k1_by_npts(cache, batch, torch, K, B, args.npts)
         if weak is not None:
             line["weak_scaling"] = dict(weak, note="the same timed region with --batch trajectories on EVERY GPU (the headline `value` of an N > 1 "
                                         "run is the STRONG scaling of the global batch, BASELINE configs[3] as written)")
-        if world == 1 and not args.no_k1_sweep and not args.aero:
+        if args.full and world == 1 and not args.no_k1_sweep and not args.aero:
             line["k1_error_vs_dop853_by_npts"] = k1_error_by_npts(IntegratorCache, p)
-        if world == 1 and not args.no_traj_check and not args.aero:
+        if args.full and world == 1 and not args.no_traj_check and not args.aero:
             # device and oracle at the SAME solver tolerance (the headline's: 1e-8 unless --tol); rounds 1-4 compared the device at 1e-8
             # with the oracle at its own default 1e-9
             line["traj_linf_vs_oracle"] = traj_linf_vs_oracle(IntegratorCache, ScvxBatch, p, args.npts, tol=(args.tol if args.tol > 0 else 1e-8))
@@ -734,7 +785,7 @@ def main():
             line["traj_linf_vs_oracle_default_tols"] = traj_linf_vs_oracle(IntegratorCache, ScvxBatch, p, args.npts)
             if args.tol <= 0 and not args.config5:
                 line["traj_linf_vs_oracle_batch32"] = traj_linf_vs_oracle_batch32(cache, ScvxBatch, B, shard.ic, args.seed)
-        if world == 1 and not args.no_traj_check:
+        if args.full and world == 1 and not args.no_traj_check:
             # NOT the headline: the same loop (a) with every solve started cold, as the reference's solver does, and (b) with
             # scvx_solver_opts.reuse_inactive_tr (a conic solve whose optimum is provably unchanged after a rejected step is
             # skipped).  Reported beside `value`, never instead of it.
@@ -785,9 +836,9 @@ def main():
                                                   "rejected step the conic solve is skipped when the optimum just found lies strictly "
                                                   "inside the halved radius (it is then the new optimum too); every solve_step still runs "
                                                   "its propagation, trust-region test and re-linearisation")
-        if world == 1 and not args.no_traj_check and not args.aero:
+        if args.full and world == 1 and not args.no_traj_check and not args.aero:
             line["k0_threedof_init"] = k0_threedof(B, args.seed)
-        if not args.no_cpu_baseline and world == 1 and not args.aero:  # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.aero:  # reported on rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(args.npts, args.seed, period)
         print(json.dumps(line), flush=True)
     if dist is not None:

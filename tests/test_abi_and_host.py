@@ -303,10 +303,38 @@ def test_bench_gpus_n_launches_its_own_ranks_and_fails_with_them():
 
 
 def test_bench_rounds_the_timed_steps_to_whole_solve_problem_periods():
-    """ADVICE r3 / VERDICT r3 item 3: the timed region is whole periods of imax - 1 = 14 solve_steps (the source states the rule once)."""
+    """ADVICE r3 / VERDICT r3 item 3: with --whole-periods the timed region is whole periods of imax - 1 = 14 solve_steps (the source states
+    the rule once); without it, exactly --steps are timed."""
     import os
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")).read()
     assert "steps = ((args.steps + period - 1) // period) * period if whole else args.steps" in src
+    assert "whole = at_zero and args.whole_periods" in src
     period = 14
     for asked, timed in ((1, 14), (14, 14), (15, 28), (20, 28), (28, 28)):
         assert ((asked + period - 1) // period) * period == timed
+
+
+def test_bench_dump_outputs_keeps_float64_under_the_cap_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; a batch that fits is written whole, one that does not is cut
+    to the same seeded sample of trajectories in every array (indices in sample_index.npy), and the files stay under the cap."""
+    import bench
+    rng = np.random.default_rng(0)
+    n = 300
+    arrays = {"x": rng.normal(size=(n, 4, 3)), "sigma": rng.normal(size=n), "status": rng.integers(0, 4, n).astype(np.int32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, v)
+    assert not (tmp_path / "whole" / "sample_index.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 8 * 15 * 100)     # room for 100 trajectories of 14 values + their index
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    keep = idx.astype(np.int64)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "a" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, v[keep])
+        assert np.array_equal(a, np.load(tmp_path / "b" / (k + ".npy")))    # the same sample every time
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES

@@ -148,17 +148,10 @@ _REF_SIGNATURES = {
 def test_julia_install_defines_the_references_own_signatures():
     """ScvxAMD.install!() adds methods to Dynamics / Rocketland with the reference's exact argument lists,
     so the recipe of rocketland.jl:26-32 runs unedited.  Parsed, not executed (no Julia in the image); the expected argument
-    lists are checked against /root/reference when it is present (this container), and held above otherwise."""
+    lists are held above, as the reference's lines cited there state them."""
     import re
     jl = open(os.path.join(ROOT, "julia", "ScvxAMD.jl")).read()
     body = jl[jl.index("function install!()"):]
     found = dict(re.findall(r"^\s+function (\(::Type\{IntegratorCache\}\)|\w+)\(([^)]*)\)\s*$", body, flags=re.M))
     assert found == _REF_SIGNATURES, found
     assert "@eval HOST.Dynamics" in body and "@eval HOST.Rocketland" in body
-    ref = "/root/reference"
-    if os.path.isdir(ref):
-        src = {f: open(os.path.join(ref, f)).read() for f in ("dynamics.jl", "rocketland.jl")}
-        for name, args in _REF_SIGNATURES.items():
-            fn = "dynamics.jl" if name in ("make_dynamics_module", "(::Type{IntegratorCache})", "predict_state", "linearize_dynamics") else "rocketland.jl"
-            want = args if name != "solve_problem" else args.replace("cache::IntegratorCache", "cache::LinearCache")
-            assert ("function " + name + "(" + want + ")") in src[fn], (name, fn)

@@ -965,11 +965,54 @@ def test_two_rank_bench_on_one_gpu_matches_the_single_process_run(tmp_path):
     assert np.array_equal(a, b)
 
 
+def test_plain_bench_times_exactly_the_steps_asked_and_dumps_what_the_timed_path_computed(tmp_path):
+    """`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` without --full: three timed steps (not rounded to a period), the
+    headline fields and nothing that takes a run of its own; DIR holds the batch the timed path left after its last step, equal to the
+    same sequence driven here (one warm-up step, back to create_initial, three steps)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from successiveconvexification_amd import montecarlo as mc, sample_problems as sp
+    from successiveconvexification_amd.batch import ScvxBatch
+    from successiveconvexification_amd.dynamics import IntegratorCache
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, seed, out = 512, 20261004, tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["steps_requested"] == 3 and line["timed_region"]["indices_within_solve_problem"] == [0, 1, 2]
+    assert line["unit"] == "traj-iter/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and "SCvx" in line["metric"]
+    assert line["value"] > 0 and abs(line["value"] - B / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for k in ("roofline_k1", "roofline_k1_by_npts", "traj_linf_vs_oracle", "cold_start_only", "k0_threedof_init", "cpu_baseline"):
+        assert k not in line, k
+
+    c = IntegratorCache(sp.base_prob_scaled, npts=10)
+    b = ScvxBatch(c, B).init(mc.Shard(sp.base_prob_scaled, B, seed).ic)
+    b.solve_step_async()
+    b.reset()
+    for _ in range(3):
+        b.solve_step_async()
+    x, u, s = b.trajectory()
+    rk, cost, it = b.scalars()
+    st, act, _ = b.flags()
+    want = {"x": x, "u": u, "sigma": s, "trust_radius": rk, "cost": cost, "iteration": it, "status": st, "active": act}
+    assert sorted(f.name for f in out.iterdir()) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        a = np.load(out / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == v.shape, k
+        np.testing.assert_allclose(a, v, rtol=0, atol=1e-12, err_msg=k)
+    b.close(); c.close()
+
+
 def test_bench_gpus_2_from_a_plain_shell_launches_its_own_ranks():
     """`bench.py --gpus 2` with no WORLD_SIZE in the environment.  The parent starts the two rank processes itself
     (it never touches the GPU), they rendezvous on 127.0.0.1 over gloo and share this box's one card; rank 0's ONE line comes back
     through the parent: n_gpus 2, the headline = STRONG scaling of the global batch 8192 (BASELINE configs[3] as written: 4096 per
-    rank here), the weak figure (8192 per rank) beside it, whole solve_problem periods timed."""
+    rank here), with --full the weak figure (8192 per rank) beside it, with --whole-periods whole solve_problem periods timed."""
     import json
     import os
     import subprocess
@@ -977,8 +1020,8 @@ def test_bench_gpus_2_from_a_plain_shell_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["SCVX_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-traj-check", "--no-k1-sweep"], env=env, capture_output=True, text=True, timeout=1200, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--whole-periods",
+                        "--no-cpu-baseline", "--no-traj-check", "--no-k1-sweep"], env=env, capture_output=True, text=True, timeout=1200, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

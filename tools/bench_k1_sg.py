@@ -3,7 +3,7 @@ import os, sys, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for sg in ("0", "1"):
     env = dict(os.environ, SCVX_K1_SG=sg)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-traj-check"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-traj-check"],
                          env=env, capture_output=True, text=True).stdout.strip().splitlines()[-1]
     import json
     d = json.loads(out)["roofline_k1_by_npts"]

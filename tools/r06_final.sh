@@ -4,11 +4,11 @@ O=gpurun_out/r06; mkdir -p $O
 timeout -k 10 900 bash tools/final_profiles.sh r06 > $O/final_profiles.log 2>&1 || { tail -30 $O/final_profiles.log; exit 1; }
 tail -3 $O/final_profiles.log
 echo progress: profiles done
-timeout -k 10 600 python bench.py > $O/bench_B8192_final.json 2> $O/bench_B8192_final.err
+timeout -k 10 600 python bench.py --full > $O/bench_B8192_final.json 2> $O/bench_B8192_final.err
 echo progress: bench done
-timeout -k 10 300 python bench.py --aero --batch 256 > $O/bench_aero_B256.json 2> $O/bench_aero_B256.err
+timeout -k 10 300 python bench.py --full --aero --batch 256 > $O/bench_aero_B256.json 2> $O/bench_aero_B256.err
 echo progress: aero done
-timeout -k 10 900 python bench.py --config5 > $O/bench_config5.json 2> $O/bench_config5.err
+timeout -k 10 900 python bench.py --full --config5 > $O/bench_config5.json 2> $O/bench_config5.err
 echo progress: config5 done
 timeout -k 10 400 python tools/bsweep_mix.py > $O/bsweep_final.md 2>&1
 timeout -k 10 200 python tools/cold_step_latency.py > $O/cold_latency_final.md 2>&1
