@@ -24,8 +24,9 @@
  * added to the aerodynamic force (:66) and its torque cross(rFB, ff) to the body torque (:69), and the cone
  * |u[4:5]| <= finmxf at every node (rocketland.jl:203-209).  Three choices the comments leave open, stated so that configs[4]
  * numbers are not read as matching a reference model that does not exist:
- *   (1) the commented expression at dynamics.jl:69 is `cross(info.rFB, ff) + bdy_trq`; only Jinv * (rFB x ff) is enabled here, the
- *       aerodynamic body torque bdy_trq stays dropped exactly as in the live NU = 3 model (dynamics.jl:69,93);
+ *   (1) the commented expression at dynamics.jl:69 is `cross(info.rFB, ff) + bdy_trq`; the fin flag enables Jinv * (rFB x ff); the
+ *       aerodynamic body torque bdy_trq is the separate opt-in SCVX_MODEL_AERO_TORQUE below (default: dropped, as in the live
+ *       model, dynamics.jl:69,93), and the two combine freely;
  *   (2) rFB is a body-frame arm and ff = u4 fd1 + u5 fd2 is built from inertial-frame vectors: the cross product mixes the two
  *       frames as the comment does -- kept as written, not "fixed";
  *   (3) the linearised thrust lower bound (rocketland.jl:199-201) uses |u[1:3]|, the thrust part of the control; the reference's
@@ -76,6 +77,25 @@ extern "C" {
 #define SCVX_MODEL_DPMAX 1
 /* model_flags: the fin extension described at the top of this file (control_dim = 5).  Needs finmxf > 0. */
 #define SCVX_MODEL_FINS 2
+/* model_flags: the aerodynamic body torque.  The reference loads a torque table next to drag and lift (aerodynamics.jl:17-21), its
+ * symbolic aero_force returns the torque bdy_trq (aerodynamics.jl:60-77), and dx_static comments it out (dynamics.jl:69, 93-94).
+ * With this bit the rate equation becomes
+ *     wdot = Jinv (rTB x u [+ rFB x ff with FINS] + tau_aero - w x J w),
+ *     tau_aero = T(c, M) * length_scalar * force_scalar * (v x bv),   bv = C(q) e1,
+ * where c = clamp(bv.v / (M sos), -1, 1) (0 at M <= 0) and M = |v| / sos are the arguments of the drag and lift tables and T is the
+ * torque table under the same cubic B-spline, axes and Flat() extrapolation.  Three properties of the model, kept as written:
+ *   (1) the direction is NOT normalised: the symbolic aero_force returns trq * ifnz.(trqd / |trqd|, trqd) and ifnz(val, nz) = nz, so
+ *       each component is (v x bv)_i (aerodynamics.jl:67-68,76; its Jacobian rule (0, 1), dynamics.jl:205-207, makes the reference's
+ *       derivative that of T (v x bv)).  The numeric aero_force (:38-57, normalised, drag-only at |cos| >= 0.95) is never evaluated by
+ *       the loop; the host mirror aerodynamics.aero_force keeps that numeric form.  The term is smooth and vanishes at v || bv and v = 0;
+ *   (2) v x bv is an inertial-frame vector added to the body-frame torque sum, as the comment at dynamics.jl:69 does (the same frame
+ *       mix as fin choice (2));
+ *   (3) rTB and rFB lie on the body x axis, so no control produces a body-x torque: the x component of tau_aero is absorbed by the
+ *       virtual control nu.  On the sample problem the term is a small perturbation (|Jinv tau| <~ 0.05 about roll, <~ 2e-3 about
+ *       pitch and yaw, against up to 3.3 from the thrust).
+ * Valid only with aero_kind == 1 (scvx_ctx_create returns SCVX_ERR_ARG otherwise, and for any model_flags bit outside
+ * DPMAX | FINS | AERO_TORQUE); scvx_set_aero_table then needs trq != NULL.  Bit clear: today's model, bit for bit. */
+#define SCVX_MODEL_AERO_TORQUE 4
 
 /* Flat image of DescentProblem (master.jl:17-71) + the aero scalars of AtmosphericData (master.jl:10-16).
  * Angles in degrees exactly as the reference stores them.  jB is column-major 3x3. */
@@ -94,7 +114,7 @@ typedef struct scvx_problem {
     double finmxf; /* fin extension: bound of |u[4:5]| (rocketland.jl:205 pins it to 0.01 in the commented code); read only with SCVX_MODEL_FINS */
     int32_t K, imax;
     int32_t aero_kind; /* 0 = ExoatmosphericData, 1 = AtmosphericData */
-    int32_t model_flags; /* SCVX_MODEL_* bits: constraints the reference sketches but never wired up; 0 = the reference's model */
+    int32_t model_flags; /* SCVX_MODEL_* bits: model terms and constraints the reference sketches but never wired up; 0 = the reference's model */
 } scvx_problem;
 
 /* Tunables of the batched conic solver that replaces MOI.optimize! (rocketland.jl:271): a structure-
@@ -160,7 +180,8 @@ int scvx_synchronize(scvx_ctx *ctx);
 int scvx_set_nsub(scvx_ctx *ctx, int nsub);
 int scvx_get_nsub(const scvx_ctx *ctx);
 /* Aerodynamics.load_aerodata tables (aerodynamics.jl:11-28): three n_aoa x n_mach grids, cos(AoA)
- * fastest, on axes aoa0 + i*daoa, mach0 + j*dmach.  Host pointers; prefiltered on the host, uploaded. */
+ * fastest, on axes aoa0 + i*daoa, mach0 + j*dmach.  Host pointers; prefiltered on the host, uploaded.  trq is read only with
+ * SCVX_MODEL_AERO_TORQUE (then it must not be NULL); otherwise it may be NULL. */
 int scvx_set_aero_table(scvx_ctx *ctx, const double *drag, const double *lift, const double *trq,
                         int n_aoa, int n_mach, double aoa0, double daoa, double mach0, double dmach);
 

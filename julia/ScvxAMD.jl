@@ -34,11 +34,13 @@ end
 const MODEL_DPMAX = 1   # SCVX_MODEL_DPMAX: enforce 1/2 rho |v|^2 <= dpMax (fields master.jl:27,30; a todo at rocketland.jl:211)
 const MODEL_FINS = 2    # SCVX_MODEL_FINS: the fin extension, control_dim = 5 -- the model the reference sketches in comments
                         # (dynamics.jl:60-69, rocketland.jl:203-209) and include/scvx.h defines; LinPoint.control then has 5 entries
+const MODEL_AERO_TORQUE = 4   # SCVX_MODEL_AERO_TORQUE: the aerodynamic body torque T(c, M) (v x bv) the reference comments out
+                              # (dynamics.jl:69); AtmosphericData only, and the `trq` table of `tables` then reaches the dynamics
 
 t3(v) = (Float64(v[1]), Float64(v[2]), Float64(v[3]))
 t4(v) = (Float64(v[1]), Float64(v[2]), Float64(v[3]), Float64(v[4]))
 
-function CProblem(p::DescentProblem; model_flags::Integer=0, finmxf::Real=0.01)   # model_flags: MODEL_DPMAX | MODEL_FINS
+function CProblem(p::DescentProblem; model_flags::Integer=0, finmxf::Real=0.01)   # model_flags: MODEL_DPMAX | MODEL_FINS | MODEL_AERO_TORQUE
     aero = p.aero isa AtmosphericData
     CProblem(p.g, p.mdry, p.mwet, p.Tmin, p.Tmax, p.deltaMax, p.thetaMax, p.gammaGs, p.omMax, p.dpMax,
              Tuple(Float64.(vec(p.jB))), p.alpha, p.rho, p.sos, t3(p.rTB), t3(p.rFB), t3(p.rIi), t3(p.rIf), t3(p.vIi), t3(p.vIf),
@@ -290,7 +292,10 @@ allgather_trajectories!(b::Batch, out_dev::Ptr{Cdouble}) =
 # reaches the HIP path.  The reference's IntegratorCache (master.jl:113-120) has untyped fields: the device Cache rides in
 # `sim_prob`.  ProblemIteration.model is a ProblemModel of MOI handles (master.jl:96-111): a placeholder is built whose untyped
 # `debug` field carries the device Batch.  An AtmosphericData problem needs its raw tables once: ScvxAMD.TABLES[] = (drag, lift, trq).
+# The build's model extensions reach the installed methods through ScvxAMD.MODEL_FLAGS[] (default 0, the reference's model), e.g.
+# MODEL_FLAGS[] = MODEL_AERO_TORQUE to add the aerodynamic body torque of an AtmosphericData problem.
 const TABLES = Ref{Any}(nothing)
+const MODEL_FLAGS = Ref{Int}(0)
 const HOST = parentmodule(@__MODULE__)     # where master.jl included Dynamics / Rocketland / FirstRound
 device_cache(c::IntegratorCache) = c.sim_prob::Cache
 device_batch(it::ProblemIteration) = it.model.debug::Batch
@@ -311,7 +316,7 @@ function install!()
             return nothing
         end
         function (::Type{IntegratorCache})(prob::DescentProblem, info::ProbInfo, lin_mod)
-            dc = $(@__MODULE__).Cache(prob; tables=$(@__MODULE__).TABLES[])
+            dc = $(@__MODULE__).Cache(prob; tables=$(@__MODULE__).TABLES[], model_flags=$(@__MODULE__).MODEL_FLAGS[])
             return IntegratorCache(dc, nothing, nothing, nothing, nothing, info)
         end
         function predict_state(initial_state, uk, up, sigma, dt, pinfo, cache)

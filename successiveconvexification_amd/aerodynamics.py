@@ -10,7 +10,8 @@ scvx_set_aero_table when the table is uploaded.
                                      evaluates the aerodynamic force outside the optimiser (aero/TestFlight.jl-style analysis, plots) --
                                      drag only when |bv . vel / |vel|| >= 0.95, otherwise drag + lift and the aerodynamic torque.
                                      Host-side, for analysis; the SCvx loop uses the symbolic method's form (aerodynamics.jl:60-77)
-                                     inside the kernels, where tau_aero is dropped exactly as dynamics.jl:69 drops it.
+                                     inside the kernels, where tau_aero is dropped exactly as dynamics.jl:69 drops it unless
+                                     SCVX_MODEL_AERO_TORQUE adds the symbolic form T (v x bv), un-normalised (include/scvx.h).
 """
 from dataclasses import replace
 import numpy as np

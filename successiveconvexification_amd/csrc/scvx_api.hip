@@ -58,6 +58,10 @@ void fill_dyn(const scvx_problem& p, scvx::DynParams& d) {
     d.aoa0 = d.inv_daoa = d.mach0 = d.inv_dmach = 0.0;
     d.force_scalar = p.force_scalar;
     d.cdrag = d.clift = nullptr;
+    // aerodynamic body torque (SCVX_MODEL_AERO_TORQUE): T(c, M) * length_scalar * force_scalar * (v x bv)
+    d.trq = (p.model_flags & SCVX_MODEL_AERO_TORQUE) ? 1 : 0;
+    d.trq_scalar = p.length_scalar * p.force_scalar;
+    d.ctrq = nullptr;
 }
 
 // Cubic(Line(OnGrid())) prefilter along one axis of length n (aerodynamics.jl:19-21): solves
@@ -126,6 +130,9 @@ int scvx_ctx_create(const scvx_problem* p, int device, scvx_ctx** out) {
     *out = nullptr;
     if (p->K < 1) return SCVX_ERR_ARG;
     if ((p->model_flags & SCVX_MODEL_FINS) && !(p->finmxf > 0.0)) return SCVX_ERR_ARG;   // the fin cone needs its bound
+    // a bit this library does not know would select a model it does not run
+    if (p->model_flags & ~(SCVX_MODEL_DPMAX | SCVX_MODEL_FINS | SCVX_MODEL_AERO_TORQUE)) return SCVX_ERR_ARG;
+    if ((p->model_flags & SCVX_MODEL_AERO_TORQUE) && p->aero_kind != 1) return SCVX_ERR_ARG;   // the torque table is aerodynamic data
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev) return SCVX_ERR_HIP;
     scvx_ctx* ctx = new (std::nothrow) scvx_ctx();
@@ -153,6 +160,7 @@ void scvx_ctx_destroy(scvx_ctx* ctx) {
     scvx::td_cache_free(ctx);
     if (ctx->d_cdrag) (void)hipFree(ctx->d_cdrag);
     if (ctx->d_clift) (void)hipFree(ctx->d_clift);
+    if (ctx->d_ctrq) (void)hipFree(ctx->d_ctrq);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -204,20 +212,28 @@ int scvx_get_nsub(const scvx_ctx* ctx) { return ctx ? ctx->nsub : SCVX_ERR_ARG; 
 
 int scvx_set_aero_table(scvx_ctx* ctx, const double* drag, const double* lift, const double* trq, int n_aoa,
                         int n_mach, double aoa0, double daoa, double mach0, double dmach) {
-    (void)trq;  // the torque table is loaded by the reference and never reaches the dynamics (dynamics.jl:69)
+    // the torque table reaches the dynamics only with SCVX_MODEL_AERO_TORQUE (the reference's dynamics.jl:69 drops it)
     if (!ctx || !drag || !lift || n_aoa < 4 || n_mach < 4 || !(daoa > 0) || !(dmach > 0))
         return fail(ctx, SCVX_ERR_ARG, "bad aero table");
+    if (ctx->dyn.trq && !trq) return fail(ctx, SCVX_ERR_ARG, "SCVX_MODEL_AERO_TORQUE needs the torque table");
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<double> cd = prefilter_table(drag, n_aoa, n_mach);
     std::vector<double> cl = prefilter_table(lift, n_aoa, n_mach);
     const size_t bytes = cd.size() * sizeof(double);
     if (ctx->d_cdrag) (void)hipFree(ctx->d_cdrag);
     if (ctx->d_clift) (void)hipFree(ctx->d_clift);
-    ctx->d_cdrag = ctx->d_clift = nullptr;
+    if (ctx->d_ctrq) (void)hipFree(ctx->d_ctrq);
+    ctx->d_cdrag = ctx->d_clift = ctx->d_ctrq = nullptr;
+    ctx->dyn.aero = 0;
     SCVX_HIP(ctx, hipMalloc(&ctx->d_cdrag, bytes));
     SCVX_HIP(ctx, hipMalloc(&ctx->d_clift, bytes));
     SCVX_HIP(ctx, hipMemcpy(ctx->d_cdrag, cd.data(), bytes, hipMemcpyHostToDevice));
     SCVX_HIP(ctx, hipMemcpy(ctx->d_clift, cl.data(), bytes, hipMemcpyHostToDevice));
+    if (ctx->dyn.trq) {
+        std::vector<double> ct = prefilter_table(trq, n_aoa, n_mach);
+        SCVX_HIP(ctx, hipMalloc(&ctx->d_ctrq, bytes));
+        SCVX_HIP(ctx, hipMemcpy(ctx->d_ctrq, ct.data(), bytes, hipMemcpyHostToDevice));
+    }
     scvx::DynParams& d = ctx->dyn;
     d.aero = 1;
     d.n_aoa = n_aoa;
@@ -229,6 +245,7 @@ int scvx_set_aero_table(scvx_ctx* ctx, const double* drag, const double* lift, c
     d.force_scalar = ctx->prob.force_scalar;
     d.cdrag = ctx->d_cdrag;
     d.clift = ctx->d_clift;
+    d.ctrq = ctx->d_ctrq;
     return SCVX_OK;
 }
 

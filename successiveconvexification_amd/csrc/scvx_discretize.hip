@@ -218,10 +218,10 @@ __device__ double g_k1prof[2 * 16];
 #else
 #define K1_BAR() lds_barrier()
 #endif
-template <bool AERO, bool FIN, typename R>
+template <bool AERO, bool FIN, bool TRQ, typename R>
 __device__ __forceinline__ void column_deriv_rec_any(const DynP<R>& p, const R* rec, int stride, const R* c, const R* wc, R gsel,
                                                      R sigma, R* dc) {
-    column_deriv_rec_pieces<AERO, FIN, R>(p, rec, stride, c, wc, gsel, sigma, dc);
+    column_deriv_rec_pieces<AERO, FIN, TRQ, R>(p, rec, stride, c, wc, gsel, sigma, dc);
 }
 constexpr int PC_GROUP = 4;              // stages published per barrier (one RK4 substep)
 // SG (stage-granular, the default): one barrier per RK stage and the producer one STAGE ahead (2-slot ring) instead of
@@ -229,9 +229,10 @@ constexpr int PC_GROUP = 4;              // stages published per barrier (one RK
 // npts = 1 the substep-granular form does not overlap at all), which outweighs the 4x barrier count at every npts.
 // O = element type of the derivative tiles in HBM: R, or float under double arithmetic (scvx_batch_set_linearization_f32:
 // the conic solve reads them as float; rounded once, at the store)
-template <bool AERO, bool SG, typename R, typename O = R, bool FIN = false>
+// TRQ: the aerodynamic body torque (SCVX_MODEL_AERO_TORQUE; AERO only) -- a wider record without fins, the same one with them.
+template <bool AERO, bool SG, typename R, typename O = R, bool FIN = false, bool TRQ = false>
 __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pc_kernel(
-    DynP<R> p, long nseg, int K, const R* __restrict__ x, const R* __restrict__ u,
+    DynPK<R, TRQ> p, long nseg, int K, const R* __restrict__ x, const R* __restrict__ u,
     const R* __restrict__ sigma, R dt, int nsub, R* __restrict__ endpoint,
     O* __restrict__ deriv, const int* __restrict__ skip) {
     constexpr int LPS = K1Map<AERO, FIN>::LPS, SPW = K1Map<AERO, FIN>::SPW;
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pc_kernel(
     constexpr int NC = PC_WAVES - 1;
     if (block_unchanged(skip, (long)blockIdx.x * (NC * SPW), NC * SPW, nseg, K)) return;
     constexpr int NS = NC * SPW;               // segments per block
-    constexpr int NR = StageRec<AERO, FIN>::N;
+    constexpr int NR = StageRec<AERO, FIN, TRQ>::N;
     constexpr int RING = SG ? 2 : 2 * PC_GROUP;   // stage records in flight: the producer runs one stage / one substep ahead
     constexpr int RING_D = RING * NR * NS, TILE_D = NC * SPW * DSZ;
     // one LDS slab: the coefficient ring during the integration, the output tiles afterwards
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pc_kernel(
 #pragma unroll
                     for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
                     struct { R g[14]; } st;
-                    stage_eval_publish<AERO, FIN>(p, xt, uu, st.g, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + l, NS, live);
+                    stage_eval_publish<AERO, FIN, TRQ>(p, xt, uu, st.g, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + l, NS, live);
                     const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
                     const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
 #pragma unroll
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pc_kernel(
 #pragma unroll
             for (int j = 0; j < NU; j++) wc[j] = ec[j] * wk;
             R dc[14];
-            column_deriv_rec_any<AERO, FIN>(p, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + ls, NS, ct, wc, gsel, sig, dc);
+            column_deriv_rec_any<AERO, FIN, TRQ>(p, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + ls, NS, ct, wc, gsel, sig, dc);
             const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
             const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
 #pragma unroll
@@ -387,9 +388,9 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pc_kernel(
 #ifndef SCVX_K1_NB_EXO
 #define SCVX_K1_NB_EXO 1   // MEASURED AND OFF: 2 = 2.81 -> 6.16 ms at npts 10 (200 spilled VGPRs: profiles/r06_k1_exo_nb2.md)
 #endif
-template <bool AERO, typename R, typename O = R, bool FIN = false, int NB = 1>
+template <bool AERO, typename R, typename O = R, bool FIN = false, int NB = 1, bool TRQ = false>
 __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp_kernel(
-    DynP<R> p, long nseg, int K, const R* __restrict__ x, const R* __restrict__ u,
+    DynPK<R, TRQ> p, long nseg, int K, const R* __restrict__ x, const R* __restrict__ u,
     const R* __restrict__ sigma, R dt, int nsub, R* __restrict__ endpoint,
     O* __restrict__ deriv, const int* __restrict__ skip) {
     constexpr int LPS = K1Map<AERO, FIN>::LPS, SPW = K1Map<AERO, FIN>::SPW;
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp_kernel(
     constexpr int NC = PC_WAVES - 1;
     constexpr int NS = NC * SPW * NB;          // segments per group
     static_assert(NS <= 64, "one producer lane per segment");
-    constexpr int NR = StageRec<AERO, FIN>::N;
+    constexpr int NR = StageRec<AERO, FIN, TRQ>::N;
     constexpr int RING = SG ? 2 : 2 * PC_GROUP;   // stage records in flight: the producer runs one stage / one substep ahead
     constexpr int RING_D = RING * NR * NS, TILE_D = NC * SPW * DSZ;
     // PERSISTENT block: it walks the groups of NS segments blockIdx.x, blockIdx.x + gridDim.x, ...  The output tiles of a
@@ -472,7 +473,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp_kernel(
 #pragma unroll
                         for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
                         struct { R g[14]; } st;
-                        stage_eval_publish<AERO, FIN>(p, xt, uu, st.g, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + l, NS, live);
+                        stage_eval_publish<AERO, FIN, TRQ>(p, xt, uu, st.g, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + l, NS, live);
                         const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
                         const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
 #pragma unroll
@@ -555,7 +556,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp_kernel(
 #pragma unroll
                 for (int bb = 0; bb < NB; bb++) {
                     R dc[14];
-                    column_deriv_rec_any<AERO, FIN>(p, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + ls[bb], NS, ct[bb], wc, gsel, sig[bb], dc);
+                    column_deriv_rec_any<AERO, FIN, TRQ>(p, lds + (SG ? (stg & 1) : (s & 1) * PC_GROUP + stg) * NR * NS + ls[bb], NS, ct[bb], wc, gsel, sig[bb], dc);
 #pragma unroll
                     for (int i = 0; i < 14; i++) {
                         ca[bb][i] = fma(wacc, dc[i], ca[bb][i]);
@@ -627,9 +628,9 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp_kernel(
 #define SCVX_K1_NB 2
 #endif
 template <bool AERO> struct K1Split { static constexpr int NB = AERO ? SCVX_K1_NB : 1; };
-template <bool AERO, typename R, typename O = R, bool FIN = false>
+template <bool AERO, typename R, typename O = R, bool FIN = false, bool TRQ = false>
 __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp2_kernel(
-    DynP<R> p, long nseg, int K, const R* __restrict__ x, const R* __restrict__ u,
+    DynPK<R, TRQ> p, long nseg, int K, const R* __restrict__ x, const R* __restrict__ u,
     const R* __restrict__ sigma, R dt, int nsub, R* __restrict__ endpoint,
     O* __restrict__ deriv, const int* __restrict__ skip) {
     static_assert(AERO || FIN, "the exo producer is not the bottleneck");
@@ -640,7 +641,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp2_kernel(
     constexpr int NC = PC_WAVES - 2;
     constexpr int NB = K1Split<AERO>::NB;
     constexpr int NS = NC * SPW * NB;          // segments per group
-    constexpr int NR = StageRec<AERO, FIN>::N, NH = HandRec<FIN>::N;
+    constexpr int NR = StageRec<AERO, FIN, TRQ>::N, NH = HandRec<FIN, TRQ>::N;
     constexpr int RING_D = 3 * NR * NS, HAND_D = 2 * NH * NS, TILE_D = NC * SPW * DSZ;
     __shared__ __attribute__((aligned(16))) R lds[RING_D + HAND_D + TILE_D];
     R* const hand = lds + RING_D;
@@ -701,7 +702,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp2_kernel(
 #pragma unroll
                     for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
                     struct { R g[14]; } st;
-                    stage_state_publish<AERO, FIN>(p, xt, uu, st.g, lds + slot * NR * NS + l, NS, live, hand + hs * NH * NS + l, NS);
+                    stage_state_publish<AERO, FIN, TRQ>(p, xt, uu, st.g, lds + slot * NR * NS + l, NS, live, hand + hs * NH * NS + l, NS);
                     const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
                     const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
 #pragma unroll
@@ -743,7 +744,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp2_kernel(
             int slot = 0, hs = 0;
             K1_BAR();   // stage 0 has been handed over
             for (int n = 0; n < T; n++) {
-                stage_cols_publish<AERO, FIN>(p, hand + hs * NH * NS + l, NS, lds + slot * NR * NS + l, NS, live);
+                stage_cols_publish<AERO, FIN, TRQ>(p, hand + hs * NH * NS + l, NS, lds + slot * NR * NS + l, NS, live);
                 slot = slot == 2 ? 0 : slot + 1;
                 hs ^= 1;
                 K1_BAR();
@@ -811,7 +812,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp2_kernel(
 #pragma unroll
                 for (int bb = 0; bb < NB; bb++) {
                     R dc[14];
-                    column_deriv_rec_any<AERO, FIN>(p, lds + slot * NR * NS + ls[bb], NS, ct[bb], wc, gsel, sig[bb], dc);
+                    column_deriv_rec_any<AERO, FIN, TRQ>(p, lds + slot * NR * NS + ls[bb], NS, ct[bb], wc, gsel, sig[bb], dc);
 #pragma unroll
                     for (int i = 0; i < 14; i++) {
                         ca[bb][i] = fma(wacc, dc[i], ca[bb][i]);
@@ -858,8 +859,8 @@ __global__ __launch_bounds__(64 * PC_WAVES) void linearize_pcp2_kernel(
 #endif
 }
 
-template <bool AERO, typename R, bool FIN = false>
-__global__ __launch_bounds__(256) void propagate_kernel(DynP<R> p, long nseg, int K, const R* __restrict__ x,
+template <bool AERO, typename R, bool FIN = false, bool TRQ = false>
+__global__ __launch_bounds__(256) void propagate_kernel(DynPK<R, TRQ> p, long nseg, int K, const R* __restrict__ x,
                                                         const R* __restrict__ u,
                                                         const R* __restrict__ sigma, R dt, int nsub,
                                                         R* __restrict__ xnext) {
@@ -894,7 +895,7 @@ __global__ __launch_bounds__(256) void propagate_kernel(DynP<R> p, long nseg, in
 #pragma unroll
             for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
             R g[14];
-            rhs_only<AERO, FIN>(p, xt, uu, g);
+            rhs_only<AERO, FIN, TRQ>(p, xt, uu, g);
             const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
             const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
 #pragma unroll
@@ -936,8 +937,9 @@ hipError_t launch_linearize_t(const scvx_ctx* ctx, int B, int K, const R* x, con
     const long nseg = (long)B * K;
     if (nseg == 0) return hipSuccess;
     const bool fin = ctx->dyn.fin != 0;
+    const bool trq = ctx->dyn.trq != 0;   // aerodynamic torque: routed like the fin model (never the column-per-lane kernel)
     if constexpr (std::is_same<R, O>::value)
-        if (ctx->k1_variant == 0 && !fin) return launch_linearize_simple<R>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, st, skip);
+        if (ctx->k1_variant == 0 && !fin && !trq) return launch_linearize_simple<R>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, st, skip);
     // aero / fin models from 3 substeps up: the producer's stage split over two wavefronts (linearize_pcp2_kernel), six consumer wavefronts
     const bool split = SCVX_K1_SPLIT != 0 && (fin || ctx->dyn.aero) && ctx->k1_sg != 0 && (ctx->k1_persist < 0 ? ctx->nsub >= 3 : ctx->k1_persist != 0);
     const bool exo_nb = !fin && !ctx->dyn.aero && ctx->k1_sg != 0 && (ctx->k1_persist < 0 ? ctx->nsub >= 3 : ctx->k1_persist != 0);   // the exo persistent kernel with SCVX_K1_NB_EXO batches
@@ -950,11 +952,23 @@ hipError_t launch_linearize_t(const scvx_ctx* ctx, int B, int K, const R* x, con
     const long cap = (long)(ctx->num_cus > 0 ? ctx->num_cus : 256) * PC_BLOCKS_PER_CU;   // persistent blocks, one per CU (LDS and VGPRs allow no more)
     // persistent kernel from 3 substeps up (measured, B = 8192 fp64: npts 10 3.21 -> 2.95 ms; npts 1: 0.59 -> 0.67, npts 2:
     // 0.87 -> 0.90 -- a group is latency-bound there, pipeline fill + epilogue); SCVX_K1_PERSIST = 0 / 1 forces
-    const bool persist = (sg || fin) && (ctx->k1_persist < 0 ? ctx->nsub >= 3 : ctx->k1_persist != 0);
+    const bool persist = (sg || fin || trq) && (ctx->k1_persist < 0 ? ctx->nsub >= 3 : ctx->k1_persist != 0);
     const unsigned grid = (unsigned)(!persist || ngrp < cap ? ngrp : cap);
     const dim3 g(grid), blk(64 * PC_WAVES);
     const DynP<R> dp(ctx->dyn);
-    if (split) {
+    if (trq) {   // aero (+ fins) with the torque: split producer, else the stage-granular pipeline (persistent from 3 substeps up)
+        const DynPT<R> dpt(ctx->dyn);
+        if (split) {
+            if (fin) hipLaunchKernelGGL((linearize_pcp2_kernel<true, R, O, true, true>), g, blk, 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
+            else hipLaunchKernelGGL((linearize_pcp2_kernel<true, R, O, false, true>), g, blk, 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
+        } else if (persist) {
+            if (fin) hipLaunchKernelGGL((linearize_pcp_kernel<true, R, O, true, 1, true>), g, blk, 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
+            else hipLaunchKernelGGL((linearize_pcp_kernel<true, R, O, false, 1, true>), g, blk, 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
+        } else {
+            if (fin) hipLaunchKernelGGL((linearize_pc_kernel<true, true, R, O, true, true>), g, blk, 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
+            else hipLaunchKernelGGL((linearize_pc_kernel<true, true, R, O, false, true>), g, blk, 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
+        }
+    } else if (split) {
         if (fin) {
             if (ctx->dyn.aero) hipLaunchKernelGGL((linearize_pcp2_kernel<true, R, O, true>), g, blk, 0, st, dp, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
             else hipLaunchKernelGGL((linearize_pcp2_kernel<false, R, O, true>), g, blk, 0, st, dp, nseg, K, x, u, sigma, dt, ctx->nsub, endpoint, deriv, skip);
@@ -997,7 +1011,7 @@ hipError_t launch_linearize_f32(const scvx_ctx* ctx, int B, int K, const float* 
                                 float dt, float* endpoint, float* deriv, hipStream_t st) {
     // measured at B = 8192 (profiles/r02_k1.md): up to two substeps the column-per-lane form wins in float (0.37 vs 0.43 ms
     // at npts 1: the producer/consumer pipeline pays a barrier per RK stage), beyond that the producer/consumer form does
-    if (ctx->nsub <= 2 && ctx->k1_variant != 0 && !ctx->dyn.fin) return launch_linearize_simple<float>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, st);
+    if (ctx->nsub <= 2 && ctx->k1_variant != 0 && !ctx->dyn.fin && !ctx->dyn.trq) return launch_linearize_simple<float>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, st);
     return launch_linearize_t<float>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, st);
 }
 
@@ -1008,7 +1022,11 @@ hipError_t launch_propagate_t(const scvx_ctx* ctx, int B, int K, const R* x, con
     if (nseg == 0) return hipSuccess;
     const unsigned grid = (unsigned)((nseg + 255) / 256);
     const DynP<R> dp(ctx->dyn);
-    if (ctx->dyn.fin) {
+    if (ctx->dyn.trq) {
+        const DynPT<R> dpt(ctx->dyn);
+        if (ctx->dyn.fin) hipLaunchKernelGGL((propagate_kernel<true, R, true, true>), dim3(grid), dim3(256), 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, xnext);
+        else hipLaunchKernelGGL((propagate_kernel<true, R, false, true>), dim3(grid), dim3(256), 0, st, dpt, nseg, K, x, u, sigma, dt, ctx->nsub, xnext);
+    } else if (ctx->dyn.fin) {
         if (ctx->dyn.aero) hipLaunchKernelGGL((propagate_kernel<true, R, true>), dim3(grid), dim3(256), 0, st, dp, nseg, K, x, u, sigma, dt, ctx->nsub, xnext);
         else hipLaunchKernelGGL((propagate_kernel<false, R, true>), dim3(grid), dim3(256), 0, st, dp, nseg, K, x, u, sigma, dt, ctx->nsub, xnext);
     } else if (ctx->dyn.aero)

@@ -8,6 +8,9 @@
 //   fin force (FIN = true)    the commented expressions of dynamics.jl:60-63, 66, 69: fd1 = normalize((C e2) x v),
 //                             fd2 = fd1 x v, ff = u[4] fd1 + u[5] fd2 added to the aerodynamic force, torque rFB x ff
 //                             (build-defined model; control_dim = 5)
+//   aerodynamic torque (TRQ)  the symbolic aero_force's bdy_trq (aerodynamics.jl:60-77), commented out at dynamics.jl:69:
+//                             tau = T(c, M) * length_scalar * force_scalar * (v x bv), un-normalised, added to the body torque
+//                             sum as it stands (SCVX_MODEL_AERO_TORQUE, include/scvx.h)
 // The reference obtains Jacobians by forward-mode AD over generated code (dynamics.jl:245-256); here
 // they are written out analytically and applied column-wise: a lane never forms the 14x14 matrix, it
 // applies the ~48 structural non-zeros of df/dx directly to the sensitivity column it owns.
@@ -30,6 +33,9 @@ struct DynParams {
     double aoa0, inv_daoa, mach0, inv_dmach, force_scalar;
     const double* cdrag;  // prefiltered coefficients, (n_mach+2) x (n_aoa+2), aoa fastest
     const double* clift;
+    int trq;             // 1: aerodynamic body torque (SCVX_MODEL_AERO_TORQUE; needs aero)
+    double trq_scalar;   // length_scalar * force_scalar
+    const double* ctrq;  // prefiltered torque table, same layout as cdrag
 };
 
 // The device functions below are templates on the arithmetic type R: double is the reference precision (and what the
@@ -54,6 +60,18 @@ struct DynP {
         for (int i = 0; i < 3; i++) rTB[i] = (R)p.rTB[i];
     }
 };
+
+// DynP of the aerodynamic-torque instantiations (TRQ): the torque constants ride in a wider kernel argument of their own, so that
+// every torque-free kernel keeps exactly its argument block.  Device code reaches them through trq_of(p), only under TRQ.
+template <typename R>
+struct DynPT : DynP<R> {
+    R trq_scalar;         // length_scalar * force_scalar
+    const double* ctrq;   // prefiltered torque table
+    __host__ __device__ __forceinline__ explicit DynPT(const DynParams& p) : DynP<R>(p), trq_scalar((R)p.trq_scalar), ctrq(p.ctrq) {}
+};
+template <typename R, bool TRQ> using DynPK = typename std::conditional<TRQ, DynPT<R>, DynP<R>>::type;
+template <typename R>
+__device__ __forceinline__ const DynPT<R>& trq_of(const DynP<R>& p) { return static_cast<const DynPT<R>&>(p); }
 
 // Everything one RK stage needs about the state trajectory, evaluated once per stage per lane.
 template <bool AERO, typename R = double, bool FIN = false>
@@ -137,9 +155,10 @@ __device__ __forceinline__ void bspline_weights(R t, int n, int& i0, R w[4], R d
     i0 = i;
 }
 
-// drag and lift tables at (aoa, mach): value, d/daoa, d/dmach each; Flat() extrapolation.
-template <typename R>
-__device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R td[3], R tl[3]) {
+// drag and lift tables at (aoa, mach): value, d/daoa, d/dmach each; Flat() extrapolation.  TRQ: the torque table too, from the
+// same spline weights (one more 4x4 coefficient gather).
+template <typename R, bool TRQ = false>
+__device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R td[3], R tl[3], R tt[3] = nullptr) {
     const int na = p.n_aoa, nm = p.n_mach;
     R ta = (aoa - p.aoa0) * p.inv_daoa, tm = (mach - p.mach0) * p.inv_dmach;
     bool fa = false, fm = false;
@@ -152,12 +171,12 @@ __device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R t
     bspline_weights(ta, na, ia, wa, dwa);
     bspline_weights(tm, nm, im, wm, dwm);
     const int lda = na + 2;
-    R vd = 0, vda = 0, vdm = 0, vl = 0, vla = 0, vlm = 0;
+    R vd = 0, vda = 0, vdm = 0, vl = 0, vla = 0, vlm = 0, vt = 0, vta = 0, vtm = 0;
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         const double* rd = p.cdrag + (size_t)(im + b) * lda + ia;
         const double* rl = p.clift + (size_t)(im + b) * lda + ia;
-        R sd = 0, sda = 0, sl = 0, sla = 0;
+        R sd = 0, sda = 0, sl = 0, sla = 0, st = 0, sta = 0;
 #pragma unroll
         for (int a = 0; a < 4; a++) {
             const R cd = (R)rd[a], cl = (R)rl[a];
@@ -165,6 +184,11 @@ __device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R t
             sda = fma(dwa[a], cd, sda);
             sl = fma(wa[a], cl, sl);
             sla = fma(dwa[a], cl, sla);
+            if constexpr (TRQ) {
+                const R ct = (R)trq_of(p).ctrq[(size_t)(im + b) * lda + ia + a];
+                st = fma(wa[a], ct, st);
+                sta = fma(dwa[a], ct, sta);
+            }
         }
         vd = fma(wm[b], sd, vd);
         vda = fma(wm[b], sda, vda);
@@ -172,6 +196,11 @@ __device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R t
         vl = fma(wm[b], sl, vl);
         vla = fma(wm[b], sla, vla);
         vlm = fma(dwm[b], sl, vlm);
+        if (TRQ) {
+            vt = fma(wm[b], st, vt);
+            vta = fma(wm[b], sta, vta);
+            vtm = fma(dwm[b], st, vtm);
+        }
     }
     td[0] = vd;
     td[1] = fa ? R(0.0) : vda * p.inv_daoa;
@@ -179,13 +208,20 @@ __device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R t
     tl[0] = vl;
     tl[1] = fa ? R(0.0) : vla * p.inv_daoa;
     tl[2] = fm ? R(0.0) : vlm * p.inv_dmach;
+    if (TRQ) {
+        tt[0] = vt;
+        tt[1] = fa ? R(0.0) : vta * p.inv_daoa;
+        tt[2] = fm ? R(0.0) : vtm * p.inv_dmach;
+    }
 }
 
-// F[3] and (JAC) dF/d(q0..q3, v1..v3) as 3x7 row-major.
-template <bool JAC, typename R>
+// F[3] and (JAC) dF/d(q0..q3, v1..v3) as 3x7 row-major.  TRQ (value only): the aerodynamic torque tau[3] as well.
+template <bool JAC, typename R, bool TRQ = false>
 __device__ __forceinline__ void aero_force(const DynP<R>& p, const R* q, const R* v, const R* C,
-                                           R F[3], R dF[21]) {
+                                           R F[3], R dF[21], R tau[3] = nullptr) {
+    static_assert(!(JAC && TRQ), "the torque Jacobian lives in the producer's column form (trq_col)");
     F[0] = F[1] = F[2] = R(0.0);
+    if (TRQ) tau[0] = tau[1] = tau[2] = R(0.0);
     if (JAC) {
 #pragma unroll
         for (int i = 0; i < 21; i++) dF[i] = R(0.0);
@@ -201,10 +237,16 @@ __device__ __forceinline__ void aero_force(const DynP<R>& p, const R* q, const R
     bool clamped = false;
     if (arg < -R(1.0)) { arg = -R(1.0); clamped = true; }
     if (arg > R(1.0)) { arg = R(1.0); clamped = true; }
-    R td[3], tl[3];
-    aero_tables(p, arg, mach, td, tl);
+    R td[3], tl[3], tt[3];
+    aero_tables<R, TRQ>(p, arg, mach, td, tl, tt);
     const R fs = p.force_scalar;
     const R drag = td[0] * fs, lift = tl[0] * fs;
+    if constexpr (TRQ) {   // T (v x bv), un-normalised (the symbolic aero_force's ifnz, aerodynamics.jl:67-68,76)
+        const R tq = tt[0] * trq_of(p).trq_scalar;
+        tau[0] = tq * (v[1] * bv[2] - v[2] * bv[1]);
+        tau[1] = tq * (v[2] * bv[0] - v[0] * bv[2]);
+        tau[2] = tq * (v[0] * bv[1] - v[1] * bv[0]);
+    }
     // liftd = (bv x v) x v = c v - |v|^2 bv
     R ld[3];
 #pragma unroll
@@ -283,14 +325,15 @@ __device__ __forceinline__ void dcm(const R* q, R* C) {
 }
 
 // RHS only (K2 propagate and the state part of K1).
-template <bool AERO, bool FIN = false, typename R>
+template <bool AERO, bool FIN = false, bool TRQ = false, typename R>
 __device__ __forceinline__ void rhs_only(const DynP<R>& p, const R* x, const R* u, R* g) {
+    static_assert(AERO || !TRQ, "the aerodynamic torque needs the aerodynamic model");
     const R* v = x + 4;
     const R* q = x + 7;
     const R* w = x + 11;
-    R C[9], F[3] = {R(0.0), R(0.0), R(0.0)}, ff[3] = {R(0.0), R(0.0), R(0.0)};
+    R C[9], F[3] = {R(0.0), R(0.0), R(0.0)}, ff[3] = {R(0.0), R(0.0), R(0.0)}, tau[3];
     dcm(q, C);
-    if (AERO) aero_force<false, R>(p, q, v, C, F, nullptr);
+    if (AERO) aero_force<false, R, TRQ>(p, q, v, C, F, nullptr, tau);
     if (FIN) {
         R fd1[3], fd2[3];
         fin_dirs<false, R>(q, v, C, fd1, fd2, nullptr, nullptr);
@@ -317,6 +360,7 @@ __device__ __forceinline__ void rhs_only(const DynP<R>& p, const R* x, const R* 
     for (int i = 0; i < 3; i++) {
         g[11 + i] = p.Jinv[3 * i] * t[0] + p.Jinv[3 * i + 1] * t[1] + p.Jinv[3 * i + 2] * t[2];
         if (FIN) g[11 + i] += p.JrF[3 * i] * ff[0] + p.JrF[3 * i + 1] * ff[1] + p.JrF[3 * i + 2] * ff[2];   // Jinv (rFB x ff)
+        if (TRQ) g[11 + i] += p.Jinv[3 * i] * tau[0] + p.Jinv[3 * i + 1] * tau[1] + p.Jinv[3 * i + 2] * tau[2];   // Jinv tau_aero
     }
 }
 
@@ -471,7 +515,13 @@ __device__ __forceinline__ void column_deriv(const DynP<R>& p, const Stage<AERO,
 // Coefficient record of one RK stage of one segment (NCOEF doubles, stored [field][segment] in LDS):
 //   g[14] | C[9] | invm | am[3] | Dq[12] | Mw[9] | q[4] | w[3] | ku[3] = -alpha u/|u| | (aero / fins) Dv[9]
 //   | (fins) fd1[3] fd2[3] Wq[12] Wv[9] Gf1[3] Gf2[3]
-template <bool AERO, bool FIN = false> struct StageRec { static constexpr int N = FIN ? 100 : (AERO ? 67 : 58); };
+//   | (aero torque without fins) Wq[12] Wv[9]
+// Wq / Wv = d wdot / d q, d v through the fin torque Jinv (rFB x ff) and / or the aerodynamic torque Jinv tau: with fins and torque both
+// contributions share the fin model's two blocks, so only the aero + torque record grows (67 -> 88).
+template <bool AERO, bool FIN = false, bool TRQ = false> struct StageRec {
+    static constexpr int N = FIN ? 100 : (AERO ? (TRQ ? 88 : 67) : 58);
+    static constexpr int oWq = FIN ? 73 : 67, oWv = FIN ? 85 : 79;
+};
 
 // ---- column-wise force derivatives for the producer ----
 // The producer needs d F / d (q0..q3, v1..v3) only to fold it, column by column, into the record's Dq / Dv (and Wq / Wv) entries.
@@ -483,8 +533,14 @@ struct AeroPrep {
     R F[3], bv[3], l[3];
     R ivn, vn2, c, iln, drag, lift, fs_td1, fs_td2, fs_tl1, fs_tl2, isos;
 };
+// the aerodynamic torque's column-independent part: tq = T trq_scalar and its derivatives along (c, M), times trq_scalar
 template <typename R>
-__device__ __forceinline__ void aero_prep(const DynP<R>& p, const R* v, const R* C, AeroPrep<R>& A) {
+struct TrqPrep {
+    R tq, ts_t1, ts_t2;
+};
+template <typename R, bool TRQ = false>
+__device__ __forceinline__ void aero_prep(const DynP<R>& p, const R* v, const R* C, AeroPrep<R>& A, TrqPrep<R>* Tp = nullptr) {
+    if constexpr (TRQ) Tp->tq = Tp->ts_t1 = Tp->ts_t2 = R(0.0);
     A.F[0] = A.F[1] = A.F[2] = R(0.0);
     A.bv[0] = C[0]; A.bv[1] = C[3]; A.bv[2] = C[6];
     A.vn2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
@@ -502,10 +558,14 @@ __device__ __forceinline__ void aero_prep(const DynP<R>& p, const R* v, const R*
     R arg = A.c / (mach * p.sos);
     if (arg < -R(1.0)) { arg = -R(1.0); A.clamped = true; }
     if (arg > R(1.0)) { arg = R(1.0); A.clamped = true; }
-    R td[3], tl[3];
-    aero_tables(p, arg, mach, td, tl);
+    R td[3], tl[3], tt[3];
+    aero_tables<R, TRQ>(p, arg, mach, td, tl, tt);
     const R fs = p.force_scalar;
     A.drag = td[0] * fs; A.lift = tl[0] * fs;
+    if constexpr (TRQ) {
+        const R ts = trq_of(p).trq_scalar;
+        Tp->tq = tt[0] * ts; Tp->ts_t1 = tt[1] * ts; Tp->ts_t2 = tt[2] * ts;
+    }
     A.fs_td1 = fs * td[1]; A.fs_td2 = fs * td[2]; A.fs_tl1 = fs * tl[1]; A.fs_tl2 = fs * tl[2];
     R ld[3];
 #pragma unroll
@@ -556,6 +616,48 @@ __device__ __forceinline__ void aero_col(const R* q, const R* v, const AeroPrep<
         const R proj = A.l[0] * dld[0] + A.l[1] * dld[1] + A.l[2] * dld[2];
 #pragma unroll
         for (int i = 0; i < 3; i++) d[i] += dlift * A.l[i] + A.lift * (dld[i] - A.l[i] * proj) * A.iln;
+    }
+}
+// tau = tq (v x bv) (aerodynamics.jl:67-68,76 with ifnz: un-normalised), in the frame mix of dynamics.jl:69
+template <typename R>
+__device__ __forceinline__ void trq_value(const R* v, const AeroPrep<R>& A, const TrqPrep<R>& Tp, R tau[3]) {
+    tau[0] = Tp.tq * (v[1] * A.bv[2] - v[2] * A.bv[1]);
+    tau[1] = Tp.tq * (v[2] * A.bv[0] - v[0] * A.bv[2]);
+    tau[2] = Tp.tq * (v[0] * A.bv[1] - v[1] * A.bv[0]);
+}
+// column j (0..3: q0..q3, 4..6: v1..v3) of d tau / d (q, v): d tq (v x bv) + tq (v x d bv) for q, + tq (e_j x bv) for v; d tq through
+// c = clamp(bv.v / |v|) and M = |v| / sos exactly as the drag and lift columns (aero_col).  Zero at v = 0, like the force.
+template <int J, typename R>
+__device__ __forceinline__ void trq_col(const R* q, const R* v, const AeroPrep<R>& A, const TrqPrep<R>& Tp, R d[3]) {
+    d[0] = d[1] = d[2] = R(0.0);
+    if (!A.on) return;
+    R dbv[3] = {R(0.0), R(0.0), R(0.0)};
+    if (J == 0) { dbv[1] = R(2.0) * q[3]; dbv[2] = -R(2.0) * q[2]; }
+    if (J == 1) { dbv[1] = R(2.0) * q[2]; dbv[2] = R(2.0) * q[3]; }
+    if (J == 2) { dbv[0] = -R(4.0) * q[2]; dbv[1] = R(2.0) * q[1]; dbv[2] = -R(2.0) * q[0]; }
+    if (J == 3) { dbv[0] = -R(4.0) * q[3]; dbv[1] = R(2.0) * q[0]; dbv[2] = R(2.0) * q[1]; }
+    const R ivn = A.ivn;
+    R darg, dmach;
+    if (J < 4) {
+        const R dc = dbv[0] * v[0] + dbv[1] * v[1] + dbv[2] * v[2];
+        darg = A.clamped ? R(0.0) : dc * ivn;
+        dmach = R(0.0);
+    } else {
+        darg = A.clamped ? R(0.0) : (A.bv[J - 4] * ivn - A.c * v[J - 4] * ivn * ivn * ivn);
+        dmach = v[J - 4] * ivn * A.isos;
+    }
+    const R dtq = Tp.ts_t1 * darg + Tp.ts_t2 * dmach;
+    d[0] = dtq * (v[1] * A.bv[2] - v[2] * A.bv[1]);
+    d[1] = dtq * (v[2] * A.bv[0] - v[0] * A.bv[2]);
+    d[2] = dtq * (v[0] * A.bv[1] - v[1] * A.bv[0]);
+    if (J < 4) {   // + tq (v x d bv)
+        d[0] += Tp.tq * (v[1] * dbv[2] - v[2] * dbv[1]);
+        d[1] += Tp.tq * (v[2] * dbv[0] - v[0] * dbv[2]);
+        d[2] += Tp.tq * (v[0] * dbv[1] - v[1] * dbv[0]);
+    } else {       // + tq (e_j x bv)
+        if (J == 4) { d[1] -= Tp.tq * A.bv[2]; d[2] += Tp.tq * A.bv[1]; }
+        if (J == 5) { d[0] += Tp.tq * A.bv[2]; d[2] -= Tp.tq * A.bv[0]; }
+        if (J == 6) { d[0] -= Tp.tq * A.bv[1]; d[1] += Tp.tq * A.bv[0]; }
     }
 }
 template <typename R>
@@ -613,10 +715,11 @@ __device__ __forceinline__ void fin_col(const R* q, const R* v, const FinPrep<R>
 // state until the publish at the end; here a group is stored to LDS right after it is computed, the force derivatives are
 // produced one column at a time, and only g[14] survives, which the state update needs.)  Record layout: StageRec.
 // `live` = this lane owns a segment of the group.
-template <bool AERO, bool FIN, typename R>
+template <bool AERO, bool FIN, bool TRQ = false, typename R>
 __device__ __forceinline__ void stage_eval_publish(const DynP<R>& p, const R* x, const R* u, R* g, R* rec, int stride, bool live) {
+    static_assert(AERO || !TRQ, "the aerodynamic torque needs the aerodynamic model");
     constexpr int oC = 14, oInvm = 23, oAm = 24, oDq = 27, oMw = 39, oQ = 48, oW = 52, oKu = 55, oDv = 58;
-    constexpr int oF1 = 67, oF2 = 70, oWq = 73, oWv = 85, oG1 = 94, oG2 = 97;
+    constexpr int oF1 = 67, oF2 = 70, oWq = StageRec<AERO, FIN, TRQ>::oWq, oWv = StageRec<AERO, FIN, TRQ>::oWv, oG1 = 94, oG2 = 97;
     const R* v = x + 4;
     const R* q = x + 7;
     const R* w = x + 11;
@@ -629,13 +732,15 @@ __device__ __forceinline__ void stage_eval_publish(const DynP<R>& p, const R* x,
     PUT(oInvm, invm);
     const R q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
     const R u1 = u[0], u2 = u[1], u3 = u[2];
-    R F[3] = {R(0.0), R(0.0), R(0.0)}, ff[3] = {R(0.0), R(0.0), R(0.0)};
+    R F[3] = {R(0.0), R(0.0), R(0.0)}, ff[3] = {R(0.0), R(0.0), R(0.0)}, tau[3] = {R(0.0), R(0.0), R(0.0)};
     AeroPrep<R> A;
     FinPrep<R> Fp;
+    TrqPrep<R> Tp;
     if (AERO) {
-        aero_prep(p, v, C, A);
+        aero_prep<R, TRQ>(p, v, C, A, &Tp);
 #pragma unroll
         for (int i = 0; i < 3; i++) F[i] = A.F[i];
+        if (TRQ) trq_value(v, A, Tp, tau);
     }
     if (FIN) {
         fin_prep(v, C, Fp);
@@ -654,13 +759,24 @@ __device__ __forceinline__ void stage_eval_publish(const DynP<R>& p, const R* x,
         constexpr int J = decltype(Jt)::value;
         R d[3] = {R(0.0), R(0.0), R(0.0)};
         if (AERO) aero_col<J>(q, v, A, d);
+        R wt[3] = {R(0.0), R(0.0), R(0.0)};   // column J of Wq | Wv
         if (FIN) {
             R df[3];
             fin_col<J>(q, v, Fp, u[3], u[4], df);
 #pragma unroll
             for (int i = 0; i < 3; i++) {
                 d[i] += df[i];
-                PUT((J < 4 ? oWq + 4 * i + J : oWv + 3 * i + (J - 4)), p.JrF[3 * i] * df[0] + p.JrF[3 * i + 1] * df[1] + p.JrF[3 * i + 2] * df[2]);
+                wt[i] = p.JrF[3 * i] * df[0] + p.JrF[3 * i + 1] * df[1] + p.JrF[3 * i + 2] * df[2];
+                if (!TRQ) PUT((J < 4 ? oWq + 4 * i + J : oWv + 3 * i + (J - 4)), wt[i]);
+            }
+        }
+        if (TRQ) {   // the aerodynamic torque's column shares the block: Jinv d tau (+ the fin torque's)
+            R dt[3];
+            trq_col<J>(q, v, A, Tp, dt);
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                wt[i] += p.Jinv[3 * i] * dt[0] + p.Jinv[3 * i + 1] * dt[1] + p.Jinv[3 * i + 2] * dt[2];
+                PUT((J < 4 ? oWq + 4 * i + J : oWv + 3 * i + (J - 4)), wt[i]);
             }
         }
         if (J < 4) {
@@ -705,6 +821,7 @@ __device__ __forceinline__ void stage_eval_publish(const DynP<R>& p, const R* x,
         for (int i = 0; i < 3; i++) {
             g[11 + i] = p.Jinv[3 * i] * t[0] + p.Jinv[3 * i + 1] * t[1] + p.Jinv[3 * i + 2] * t[2];
             if (FIN) g[11 + i] += p.JrF[3 * i] * ff[0] + p.JrF[3 * i + 1] * ff[1] + p.JrF[3 * i + 2] * ff[2];
+            if (TRQ) g[11 + i] += p.Jinv[3 * i] * tau[0] + p.Jinv[3 * i + 1] * tau[1] + p.Jinv[3 * i + 2] * tau[2];
         }
         // T = [w]x J - [Jw]x ; Mw = -Jinv T
         R T[9];
@@ -744,14 +861,16 @@ __device__ __forceinline__ void stage_eval_publish(const DynP<R>& p, const R* x,
 // prepared aerodynamic / fin quantities: HandRec) to wavefront P1, which one stage later produces the DERIVATIVE part of the
 // same record: the seven columns of d(C u + F)/d(q, v) / m, the fin torque columns and the rate Jacobian.  Same arithmetic as
 // stage_eval_publish, statement for statement.
-template <bool FIN> struct HandRec {
+template <bool FIN, bool TRQ = false> struct HandRec {
     // q 0..3 | v 4..6 | w 7..9 | u 10..14 | invm 15 | flags 16 | ivn vn2 c iln drag lift 17..22 | fs_td1 fs_td2 fs_tl1 fs_tl2 23..26 |
-    // bv 27..29 | l 30..32 | fin: fd1 33..35 | b2 36..38 | inn 39
-    static constexpr int N = FIN ? 40 : 33;
+    // bv 27..29 | l 30..32 | fin: fd1 33..35 | b2 36..38 | inn 39 | torque: tq ts_t1 ts_t2 at oT..oT+2
+    static constexpr int oT = FIN ? 40 : 33;
+    static constexpr int N = oT + (TRQ ? 3 : 0);
 };
-template <bool AERO, bool FIN, typename R>
+template <bool AERO, bool FIN, bool TRQ = false, typename R>
 __device__ __forceinline__ void stage_state_publish(const DynP<R>& p, const R* x, const R* u, R* g, R* rec, int stride, bool live,
                                                     R* hand, int hstride) {
+    static_assert(AERO || !TRQ, "the aerodynamic torque needs the aerodynamic model");
     constexpr int oC = 14, oInvm = 23, oAm = 24, oQ = 48, oW = 52, oKu = 55;
     constexpr int oF1 = 67, oF2 = 70, oG1 = 94, oG2 = 97;
     const R* v = x + 4;
@@ -767,14 +886,20 @@ __device__ __forceinline__ void stage_state_publish(const DynP<R>& p, const R* x
     PUT(oInvm, invm);
     const R q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
     const R u1 = u[0], u2 = u[1], u3 = u[2];
-    R F[3] = {R(0.0), R(0.0), R(0.0)}, ff[3] = {R(0.0), R(0.0), R(0.0)};
+    R F[3] = {R(0.0), R(0.0), R(0.0)}, ff[3] = {R(0.0), R(0.0), R(0.0)}, tau[3] = {R(0.0), R(0.0), R(0.0)};
     AeroPrep<R> A;
     FinPrep<R> Fp;
+    TrqPrep<R> Tp;
     int flags = 0;
     if (AERO) {
-        aero_prep(p, v, C, A);
+        aero_prep<R, TRQ>(p, v, C, A, &Tp);
 #pragma unroll
         for (int i = 0; i < 3; i++) F[i] = A.F[i];
+        if (TRQ) {
+            trq_value(v, A, Tp, tau);
+            constexpr int oT = HandRec<FIN, TRQ>::oT;
+            HPUT(oT, Tp.tq); HPUT(oT + 1, Tp.ts_t1); HPUT(oT + 2, Tp.ts_t2);
+        }
         flags |= (A.on ? 1 : 0) | (A.clamped ? 2 : 0) | (A.has_lift ? 4 : 0);
         HPUT(17, A.ivn); HPUT(18, A.vn2); HPUT(19, A.c); HPUT(20, A.iln); HPUT(21, A.drag); HPUT(22, A.lift);
         HPUT(23, A.fs_td1); HPUT(24, A.fs_td2); HPUT(25, A.fs_tl1); HPUT(26, A.fs_tl2);
@@ -828,6 +953,7 @@ __device__ __forceinline__ void stage_state_publish(const DynP<R>& p, const R* x
         for (int i = 0; i < 3; i++) {
             g[11 + i] = p.Jinv[3 * i] * t[0] + p.Jinv[3 * i + 1] * t[1] + p.Jinv[3 * i + 2] * t[2];
             if (FIN) g[11 + i] += p.JrF[3 * i] * ff[0] + p.JrF[3 * i + 1] * ff[1] + p.JrF[3 * i + 2] * ff[2];
+            if (TRQ) g[11 + i] += p.Jinv[3 * i] * tau[0] + p.Jinv[3 * i + 1] * tau[1] + p.Jinv[3 * i + 2] * tau[2];
         }
     }
 #pragma unroll
@@ -842,9 +968,9 @@ __device__ __forceinline__ void stage_state_publish(const DynP<R>& p, const R* x
         PUT(oKu, k * u1); PUT(oKu + 1, k * u2); PUT(oKu + 2, k * u3);
     }
 }
-template <bool AERO, bool FIN, typename R>
+template <bool AERO, bool FIN, bool TRQ = false, typename R>
 __device__ __forceinline__ void stage_cols_publish(const DynP<R>& p, const R* hand, int hstride, R* rec, int stride, bool live) {
-    constexpr int oDq = 27, oMw = 39, oDv = 58, oWq = 73, oWv = 85;
+    constexpr int oDq = 27, oMw = 39, oDv = 58, oWq = StageRec<AERO, FIN, TRQ>::oWq, oWv = StageRec<AERO, FIN, TRQ>::oWv;
     auto PUT = [&](int i, R val) { if (live) rec[i * stride] = val; };
     auto H = [&](int i) { return hand[i * hstride]; };
     R q[4], v[3], w[3], u[5] = {R(0.0), R(0.0), R(0.0), R(0.0), R(0.0)};
@@ -860,6 +986,11 @@ __device__ __forceinline__ void stage_cols_publish(const DynP<R>& p, const R* ha
     const R u1 = u[0], u2 = u[1], u3 = u[2];
     AeroPrep<R> A;
     FinPrep<R> Fp;
+    TrqPrep<R> Tp;
+    if (TRQ) {
+        constexpr int oT = HandRec<FIN, TRQ>::oT;
+        Tp.tq = H(oT); Tp.ts_t1 = H(oT + 1); Tp.ts_t2 = H(oT + 2);
+    }
     if (AERO) {
         A.on = (flags & 1) != 0; A.clamped = (flags & 2) != 0; A.has_lift = (flags & 4) != 0;
         A.ivn = H(17); A.vn2 = H(18); A.c = H(19); A.iln = H(20); A.drag = H(21); A.lift = H(22);
@@ -878,13 +1009,24 @@ __device__ __forceinline__ void stage_cols_publish(const DynP<R>& p, const R* ha
         constexpr int J = decltype(Jt)::value;
         R d[3] = {R(0.0), R(0.0), R(0.0)};
         if (AERO) aero_col<J>(q, v, A, d);
+        R wt[3] = {R(0.0), R(0.0), R(0.0)};   // column J of Wq | Wv
         if (FIN) {
             R df[3];
             fin_col<J>(q, v, Fp, u[3], u[4], df);
 #pragma unroll
             for (int i = 0; i < 3; i++) {
                 d[i] += df[i];
-                PUT((J < 4 ? oWq + 4 * i + J : oWv + 3 * i + (J - 4)), p.JrF[3 * i] * df[0] + p.JrF[3 * i + 1] * df[1] + p.JrF[3 * i + 2] * df[2]);
+                wt[i] = p.JrF[3 * i] * df[0] + p.JrF[3 * i + 1] * df[1] + p.JrF[3 * i + 2] * df[2];
+                if (!TRQ) PUT((J < 4 ? oWq + 4 * i + J : oWv + 3 * i + (J - 4)), wt[i]);
+            }
+        }
+        if (TRQ) {   // the aerodynamic torque's column shares the block: Jinv d tau (+ the fin torque's)
+            R dt[3];
+            trq_col<J>(q, v, A, Tp, dt);
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                wt[i] += p.Jinv[3 * i] * dt[0] + p.Jinv[3 * i + 1] * dt[1] + p.Jinv[3 * i + 2] * dt[2];
+                PUT((J < 4 ? oWq + 4 * i + J : oWv + 3 * i + (J - 4)), wt[i]);
             }
         }
         if (J < 4) {
@@ -929,12 +1071,13 @@ __device__ __forceinline__ void stage_cols_publish(const DynP<R>& p, const R* ha
 // (c, its RK accumulator and stage value).  Reading the whole record in one batch (round 2's column_deriv_rec) keeps one LDS round
 // trip per stage but spilled (round 2: 97 / 240 VGPRs in the persistent kernel, exo / aero).
 // wc[NU]: FOH weights of this column's control component (NU = 5 with FIN, else 3).
-template <bool AERO, bool FIN, typename R>
+template <bool AERO, bool FIN, bool TRQ = false, typename R>
 __device__ __forceinline__ void column_deriv_rec_pieces(const DynP<R>& p, const R* rec, int stride, const R* c,
                                                         const R* wc, R gsel, R sigma, R* dc) {
     constexpr bool DV = AERO || FIN;
+    constexpr bool WB = FIN || TRQ;   // the rate rows depend on q and v (fin torque and / or aerodynamic torque)
     constexpr int oC = 14, oInvm = 23, oAm = 24, oDq = 27, oMw = 39, oQ = 48, oW = 52, oKu = 55, oDv = 58;
-    constexpr int oF1 = 67, oF2 = 70, oWq = 73, oWv = 85, oG1 = 94, oG2 = 97;
+    constexpr int oF1 = 67, oF2 = 70, oWq = StageRec<AERO, FIN, TRQ>::oWq, oWv = StageRec<AERO, FIN, TRQ>::oWv, oG1 = 94, oG2 = 97;
     auto RR = [&](int i) { return rec[i * stride]; };
     R a[14];
     {   // ---- mass, position and velocity rows ----
@@ -975,7 +1118,7 @@ __device__ __forceinline__ void column_deriv_rec_pieces(const DynP<R>& p, const 
         }
     }
     {   // ---- attitude and rate rows ----
-        R q[4], w[3], Mw[9], Wq[FIN ? 12 : 1], Wv[FIN ? 9 : 1], g1[FIN ? 3 : 1], g2[FIN ? 3 : 1];
+        R q[4], w[3], Mw[9], Wq[WB ? 12 : 1], Wv[WB ? 9 : 1], g1[FIN ? 3 : 1], g2[FIN ? 3 : 1];
 #pragma unroll
         for (int i = 0; i < 4; i++) q[i] = RR(oQ + i);
 #pragma unroll
@@ -985,6 +1128,8 @@ __device__ __forceinline__ void column_deriv_rec_pieces(const DynP<R>& p, const 
         if (FIN) {
 #pragma unroll
             for (int i = 0; i < 3; i++) { g1[i] = RR(oG1 + i); g2[i] = RR(oG2 + i); }
+        }
+        if (WB) {   // (fins: the same load order as before the torque existed)
 #pragma unroll
             for (int i = 0; i < 9; i++) Wv[i] = RR(oWv + i);
 #pragma unroll
@@ -1001,7 +1146,7 @@ __device__ __forceinline__ void column_deriv_rec_pieces(const DynP<R>& p, const 
             R t = Mw[3 * i] * cw0;
             t = fma(Mw[3 * i + 1], cw1, t);
             t = fma(Mw[3 * i + 2], cw2, t);
-            if (FIN) {
+            if (WB) {
                 t = fma(Wq[4 * i], cq0, t);
                 t = fma(Wq[4 * i + 1], cq1, t);
                 t = fma(Wq[4 * i + 2], cq2, t);

@@ -20,6 +20,7 @@ struct scvx_ctx {
     int k1_sg = 1;       // producer/consumer pipeline per RK stage (1, default) or per substep (0); SCVX_K1_SG overrides
     double* d_cdrag = nullptr;
     double* d_clift = nullptr;
+    double* d_ctrq = nullptr;   // prefiltered torque table, uploaded only with SCVX_MODEL_AERO_TORQUE
     void* comm = nullptr;   // ncclComm_t of scvx_comm_create (RCCL, bound at run time: csrc/scvx_comm.hip)
     int comm_rank = 0, comm_world = 0;
     scvx::TdCache* td = nullptr;

@@ -85,12 +85,17 @@ class DescentProblem:
     bet: float = 3.2
     sos: float = 5.0
     model_flags: int = 0   # not a reference field: 1 (SCVX_MODEL_DPMAX) enforces the dpMax / rho constraint the reference leaves as a todo;
-                           # 2 (SCVX_MODEL_FINS) enables the fin extension: control_dim = 5 (dynamics.jl:60-69 / rocketland.jl:203-209 as commented there)
+                           # 2 (SCVX_MODEL_FINS) enables the fin extension: control_dim = 5 (dynamics.jl:60-69 / rocketland.jl:203-209 as commented there);
+                           # 4 (SCVX_MODEL_AERO_TORQUE) adds the aerodynamic body torque the reference comments out (dynamics.jl:69), AtmosphericData only
     finmxf: float = 0.01   # fin extension: bound of |u[4:5]| (rocketland.jl:205)
 
     @property
     def fins(self) -> bool:
         return bool(int(self.model_flags) & 2)
+
+    @property
+    def aero_torque(self) -> bool:
+        return bool(int(self.model_flags) & 4)
 
     @property
     def nu(self) -> int:

@@ -37,7 +37,8 @@ class IntegratorCache:
         h = C.c_void_p()
         rc = self._L.scvx_ctx_create(C.byref(self._c_prob), int(device), C.byref(h))
         if rc != 0:
-            raise _lib.ScvxError(f"scvx_ctx_create failed ({rc}): is a HIP device visible? (rc -1: bad problem, e.g. fins without finmxf > 0)")
+            raise _lib.ScvxError(f"scvx_ctx_create failed ({rc}): is a HIP device visible? (rc -1: bad problem, e.g. fins without finmxf > 0, "
+                                  "the aerodynamic torque (model_flags 4) without AtmosphericData, or an unknown model_flags bit)")
         self.handle = h
         self.device = device
         self.nu = int(self._L.scvx_control_dim(h))        # 3, or 5 with the fin extension (SCVX_MODEL_FINS)

@@ -49,21 +49,27 @@ def base_prob_aero(aero_info) -> DescentProblem:
     return _base(aero_info)
 
 
-def base_prob_aero_scaled(aero_info) -> DescentProblem:
-    return normalize_problem(base_prob_aero(aero_info))
+def base_prob_aero_scaled(aero_info, torque: bool = False) -> DescentProblem:
+    """torque: the aerodynamic body torque as well (SCVX_MODEL_AERO_TORQUE, include/scvx.h; the reference comments it out,
+    dynamics.jl:69)."""
+    b = base_prob_aero(aero_info)
+    return normalize_problem(replace(b, model_flags=b.model_flags | 4) if torque else b)
 
 
-def base_prob_fin_scaled(aero_info=None, fin_table=None) -> DescentProblem:
+def base_prob_fin_scaled(aero_info=None, fin_table=None, torque: bool = False) -> DescentProblem:
     """BASELINE configs[4] "6-DoF + fin aero": the sample problem with the fin extension (control_dim = 5).  The model is
     DEFINED BY THIS BUILD from the reference's commented-out fin code (include/scvx.h).  One deliberate
     departure from normalize_problem: it scales rFB by 1/Ut (sample_problems.jl:16, harmless there because rFB is unused),
     which would put the fins 2 normalised length units = 2 km from the centre of mass; the fin torque arm is a length, so it
     is scaled by 1/Ul here like rTB.  fin_table (aerodynamics.load_fin_table of aero/fin.csv), if given, replaces the constant
-    finmxf = 0.01 of rocketland.jl:205 by the table's largest fin force at the initial Mach number (aerodynamics.fin_force_bound)."""
+    finmxf = 0.01 of rocketland.jl:205 by the table's largest fin force at the initial Mach number (aerodynamics.fin_force_bound).
+    torque: the aerodynamic body torque as well (SCVX_MODEL_AERO_TORQUE; needs aero_info)."""
     from .aerodynamics import fin_force_bound
     from .defns import AtmosphericData, ExoatmosphericData
     b = _base(aero_info if aero_info is not None else ExoatmosphericData())
-    p = normalize_problem(replace(b, model_flags=b.model_flags | 2))
+    if torque and aero_info is None:
+        raise ValueError("the aerodynamic torque needs AtmosphericData")
+    p = normalize_problem(replace(b, model_flags=b.model_flags | 2 | (4 if torque else 0)))
     p = replace(p, rFB=b.rFB * (1.0 / float(np.max(b.rIi))))
     if fin_table is not None:
         fs = p.aero.force_scalar if isinstance(p.aero, AtmosphericData) else 1.0 / (float(np.max(b.rIi)) * b.mwet / b.tf_guess**2)

@@ -1,4 +1,4 @@
-"""K1 (linearize) timing per model -- exo / aero / exo+fins / aero+fins -- and npts, across library variants.
+"""K1 (linearize) timing per model -- exo / aero / exo+fins / aero+fins / aero+trq / aero+fins+trq -- and npts, across library variants.
 HIP events through torch on the library's stream; B x K segments of random-but-physical nodes (SURVEY 8d law).
     python tools/bench_k1_models.py [--B 8192] [--K 50] lib1.so [lib2.so ...]      (paths relative to the repo root)"""
 import argparse, os, sys, ctypes as C
@@ -23,7 +23,9 @@ aero = AtmosphericData(z["drag"], z["lift"], z["torque"])
 x, u3, s = random_segments(model.base_prob_scaled(), B, K, 20261006)
 fin = 0.01 * np.random.default_rng(7).uniform(-0.7, 0.7, (B, K + 1, 2))
 models = {"exo": (sp.base_prob_scaled, u3), "aero": (sp.base_prob_aero_scaled(aero), u3),
-          "exo+fins": (sp.base_prob_fin_scaled(), np.concatenate([u3, fin], -1)), "aero+fins": (sp.base_prob_fin_scaled(aero), np.concatenate([u3, fin], -1))}
+          "exo+fins": (sp.base_prob_fin_scaled(), np.concatenate([u3, fin], -1)), "aero+fins": (sp.base_prob_fin_scaled(aero), np.concatenate([u3, fin], -1)),
+          # the aerodynamic body torque (SCVX_MODEL_AERO_TORQUE)
+          "aero+trq": (sp.base_prob_aero_scaled(aero, torque=True), u3), "aero+fins+trq": (sp.base_prob_fin_scaled(aero, torque=True), np.concatenate([u3, fin], -1))}
 ts = torch.cuda.Stream()
 torch.cuda.set_stream(ts)
 print("| library | model | npts | ms | GB/s (algorithmic) | of 8 TB/s |")
