@@ -6,6 +6,7 @@
  *
  *   Dynamics.linearize_dynamics   dynamics.jl:321-334  ->  scvx_linearize_f64[_host]
  *   Dynamics.predict_state        dynamics.jl:315-317  ->  scvx_propagate_f64[_host]
+ *   (no counterpart: open-loop flight + path audit)    ->  scvx_flight_check_f64[_host], scvx_batch_flight_check
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -197,6 +198,49 @@ int scvx_propagate_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const d
 int scvx_propagate_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u,
                             const double *sigma, double dt, double *xnext);
 
+/* ---- flight check: open-loop rollout of a plan and audit of its path constraints between the nodes ----------------
+ * scvx_solve imposes every path constraint of build_model (rocketland.jl:136-209) AT THE NODES only, and its dynamic-feasibility
+ * evidence is the virtual control.  This call flies a plan (x, u, sigma) with the integrator of scvx_propagate_f64 (RK4,
+ * first-order-hold control, `nsub` substeps per segment -- an argument of the call, independent of scvx_set_nsub, so a plan made
+ * with 10 substeps can be flown with 40) and reports, per trajectory, SCVX_FLIGHT_NREP doubles:
+ *   SCVX_FLIGHT_SHOOT  single shooting: the end of segment k starts segment k+1 -- the flight of the plan from x[0];
+ *   SCVX_FLIGHT_PLAN   the state restarts at the planned x[k] at every node -- the plan itself, audited between its nodes; its
+ *                      GAP is the largest scvx_propagate_f64 defect.
+ * The path functions are evaluated at the nsub + 1 substep boundaries s = 0..nsub of every segment (control
+ * u_k (1 - s/nsub) + u_{k+1} s/nsub; RK stage points are not sampled) and the report keeps their maxima over all samples from
+ * node 0 to node K (the SOCP leaves node 0 or node K out of some rows; the report does not).  g <= 0 means satisfied; the
+ * problem's own normalised units; state constraints on the FLOWN state.  A non-finite state makes the trajectory's GAP, MISS_*,
+ * state G_* and QNORM NaN; it cannot disturb another trajectory.
+ * G_TMIN > 0 between two nodes that sit on the bound with different thrust directions belongs to the reference's formulation
+ * (the non-convex lower bound is linearised at the nodes, rocketland.jl:199-201, and the control is a first-order hold whose
+ * chord passes inside the sphere), not to the solver. */
+#define SCVX_FLIGHT_SHOOT 0
+#define SCVX_FLIGHT_PLAN 1
+#define SCVX_FLIGHT_NREP 16
+#define SCVX_FLIGHT_GAP 0       /* max over nodes k = 1..K of |x_fly[k] - x[k]|_inf                                  */
+#define SCVX_FLIGHT_MISS_R 1    /* |r - rIf|_2 at the flown final node                                              */
+#define SCVX_FLIGHT_MISS_V 2    /* |v - vIf|_2                                                                      */
+#define SCVX_FLIGHT_MISS_Q 3    /* |q - qBIf|_2                                                                     */
+#define SCVX_FLIGHT_MISS_W 4    /* |w - wBf|_2                                                                      */
+#define SCVX_FLIGHT_MASS_END 5  /* flown final mass                                                                 */
+#define SCVX_FLIGHT_G_MASS 6    /* max of mdry - m                                             (rocketland.jl:137) */
+#define SCVX_FLIGHT_G_GLIDE 7   /* max of tan(gammaGs) |r[2:3]| - r[1]                                  (:142-148) */
+#define SCVX_FLIGHT_G_TILT 8    /* max of |q[3:4]| - sqrt((1 - cos thetaMax) / 2)                       (:155-160) */
+#define SCVX_FLIGHT_G_RATE 9    /* max of |w| - omMax                                                   (:163-167) */
+#define SCVX_FLIGHT_G_TMAX 10   /* max of |u[1:3]| - Tmax                                                   (:186) */
+#define SCVX_FLIGHT_G_TMIN 11   /* max of Tmin - |u[1:3]|: the true bound, not its linearisation        (:199-201) */
+#define SCVX_FLIGHT_G_GIMBAL 12 /* max of |u[1:3]| - u[1] / cos deltaMax                                    (:188) */
+#define SCVX_FLIGHT_G_DP 13     /* max of |v| - sqrt(2 dpMax / rho) with SCVX_MODEL_DPMAX, else -inf               */
+#define SCVX_FLIGHT_G_FIN 14    /* max of |u[4:5]| - finmxf with SCVX_MODEL_FINS, else -inf                        */
+#define SCVX_FLIGHT_QNORM 15    /* max of | |q| - 1 |                                                               */
+/* x [B][K+1][14], u [B][K+1][NU], sigma [B]; report [B][SCVX_FLIGHT_NREP]; xfly [B][K+1][14] = the flown node states
+ * (xfly[.][0] = x[.][0]), or NULL.  dt = 1 / (K + 1); K must equal the problem's.  Asynchronous on the context's stream.
+ * SCVX_ERR_ARG for nsub outside [1, 1000], an unknown mode, B < 1, K != the problem's K, a null x / u / sigma / report. */
+int scvx_flight_check_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                          int nsub, int mode, double *report_dev, double *xfly_dev);
+int scvx_flight_check_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *sigma,
+                               int nsub, int mode, double *report, double *xfly);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -306,6 +350,11 @@ int scvx_batch_set_flags(scvx_batch *b, const int32_t *status, const int32_t *ac
  * 5 infeasible: a fixed boundary value (rIi, vIi, wBi) violates the glideslope / rate / dynamic-pressure cone of node 1),
  * interior-point iterations, final merit max(pres, dres, relgap) of the returned iterate, its objective */
 int scvx_batch_get_solver_stats(scvx_batch *b, int32_t *status, int32_t *iters, double *merit, double *pobj);
+
+/* The flight check above on the batch's current accepted iterate: report [B][SCVX_FLIGHT_NREP] and xfly [B][K+1][14] (or NULL)
+ * are host arrays; nsub = 0 takes the context's.  Reads the iterate and leaves the batch untouched (trajectory, scalars, flags,
+ * linearisation, solver workspace): a solve_step after it equals the one without it bit for bit.  Synchronises. */
+int scvx_batch_flight_check(scvx_batch *b, int nsub, int mode, double *report, double *xfly);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

@@ -275,6 +275,46 @@ function solve_batch(iprob::DescentProblem, cache::Cache, ics::Matrix{Float64})
     return b, st, it, nu, dj
 end
 
+# ---- flight check (new): open-loop rollout of a plan and audit of its path constraints between the nodes ---------------------
+# include/scvx.h, "flight check".  The report is 16 x B (column-major == [B][16]); row FLIGHT_* + 1 holds that column.  g <= 0 means
+# satisfied.  G_TMIN > 0 between nodes on the bound belongs to the reference's formulation (rocketland.jl:199-201), not to the solver.
+const FLIGHT_SHOOT = 0   # SCVX_FLIGHT_SHOOT: single shooting from x[0]
+const FLIGHT_PLAN = 1    # SCVX_FLIGHT_PLAN: restart at every planned node
+const FLIGHT_NREP = 16   # SCVX_FLIGHT_NREP
+const FLIGHT_GAP = 0; const FLIGHT_MISS_R = 1; const FLIGHT_MISS_V = 2; const FLIGHT_MISS_Q = 3; const FLIGHT_MISS_W = 4
+const FLIGHT_MASS_END = 5; const FLIGHT_G_MASS = 6; const FLIGHT_G_GLIDE = 7; const FLIGHT_G_TILT = 8; const FLIGHT_G_RATE = 9
+const FLIGHT_G_TMAX = 10; const FLIGHT_G_TMIN = 11; const FLIGHT_G_GIMBAL = 12; const FLIGHT_G_DP = 13; const FLIGHT_G_FIN = 14
+const FLIGHT_QNORM = 15
+
+# the current accepted iterate of a batch: (report 16 x B, xfly 14 x (K+1) x B or nothing); nsub = 0 takes the context's
+function flight_check(b::Batch; nsub::Int=0, mode::Int=FLIGHT_SHOOT, dense::Bool=false)
+    K = b.cache.problem.K
+    report = Matrix{Float64}(undef, FLIGHT_NREP, b.B)
+    xfly = dense ? Array{Float64,3}(undef, 14, K + 1, b.B) : nothing
+    check(b.cache.ctx, ccall((:scvx_batch_flight_check, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, nsub, mode, report, dense ? pointer(xfly) : Ptr{Cdouble}(C_NULL)), "scvx_batch_flight_check")
+    return report, xfly
+end
+
+# any plans: x 14 x (K+1) x B, u NU x (K+1) x B, sigma B (host arrays)
+function flight_check(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}; nsub::Int=10,
+                      mode::Int=FLIGHT_SHOOT, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3)
+    report = Matrix{Float64}(undef, FLIGHT_NREP, B)
+    xfly = dense ? Array{Float64,3}(undef, 14, K + 1, B) : nothing
+    check(cache.ctx, ccall((:scvx_flight_check_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, sigma, nsub, mode, report, dense ? pointer(xfly) : Ptr{Cdouble}(C_NULL)), "scvx_flight_check_f64_host")
+    return report, xfly
+end
+
+# the same on device pointers (e.g. AMDGPU.jl ROCArrays), asynchronous on the context's stream; xfly_dev may be C_NULL
+flight_check_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble}, nsub::Int, mode::Int,
+                  report_dev::Ptr{Cdouble}, xfly_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_flight_check_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, sigma_dev, nsub, mode, report_dev, xfly_dev), "scvx_flight_check_f64")
+
 # multi-GPU (one Julia process per GPU): rank 0 draws the id, the host ships its 128 bytes (Distributed / MPI.jl / a file)
 unique_id() = (id = Vector{UInt8}(undef, 128); ccall((:scvx_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("RCCL unavailable"); id)
 comm_create!(c::Cache, id::Vector{UInt8}, rank::Int, world::Int) =

@@ -48,6 +48,13 @@ class ScvxThreedofOpts(C.Structure):
 
 ABI_VERSION = 4   # SCVX_ABI_VERSION of the include/scvx.h these structs and signatures were written against
 
+# scvx_flight_check_*: modes and the columns of the report [B][FLIGHT_NREP] (the SCVX_FLIGHT_* macros of include/scvx.h)
+FLIGHT_SHOOT, FLIGHT_PLAN = 0, 1
+FLIGHT_NREP = 16
+FLIGHT_COLUMNS = ("GAP", "MISS_R", "MISS_V", "MISS_Q", "MISS_W", "MASS_END", "G_MASS", "G_GLIDE", "G_TILT", "G_RATE", "G_TMAX",
+                  "G_TMIN", "G_GIMBAL", "G_DP", "G_FIN", "QNORM")
+FLIGHT_INDEX = {n: i for i, n in enumerate(FLIGHT_COLUMNS)}
+
 _vp = C.c_void_p
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
 SIGNATURES = {
@@ -68,6 +75,8 @@ SIGNATURES = {
     "scvx_linearize_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp]),
     "scvx_propagate_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp]),
     "scvx_propagate_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
+    "scvx_flight_check_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "scvx_flight_check_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),
@@ -96,6 +105,7 @@ SIGNATURES = {
     "scvx_batch_get_flags": (C.c_int, [_vp, _ip, _ip, _ip]),
     "scvx_batch_set_flags": (C.c_int, [_vp, _ip, _ip, _ip]),
     "scvx_batch_get_solver_stats": (C.c_int, [_vp, _ip, _ip, _dp, _dp]),
+    "scvx_batch_flight_check": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
     "scvx_comm_probe": (C.c_int, []),
     "scvx_comm_unique_id": (C.c_int, [_vp]),
     "scvx_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

@@ -202,6 +202,16 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_get_step_stats(self.handle, _p(o), 1 if reset else 0), "scvx_batch_get_step_stats")
         return dict(zip(("traj_steps", "solves", "ipm_iters", "warm_started", "skipped", "rejected", "failed", "converged"), o.tolist()))
 
+    def flight_check(self, nsub=None, mode="shoot", dense=False):
+        """Fly the batch's current accepted iterate open loop and audit its path constraints between the nodes
+        (scvx_batch_flight_check): a dynamics.FlightReport.  The batch is left untouched."""
+        from .dynamics import FlightReport, _flight_mode
+        rep = np.empty((self.B, _lib.FLIGHT_NREP))
+        xfly = np.empty((self.B, self.K + 1, 14)) if dense else None
+        self._chk(self._L.scvx_batch_flight_check(self.handle, int(nsub or 0), int(_flight_mode(mode)), _p(rep),
+                                                  _p(xfly) if dense else None), "scvx_batch_flight_check")
+        return FlightReport(rep, xfly, mode)
+
     def set_profiling(self, on: bool):
         self._chk(self._L.scvx_batch_set_profiling(self.handle, 1 if on else 0), "scvx_batch_set_profiling")
 

@@ -123,6 +123,21 @@ std::vector<double> prefilter_table(const double* tab, int na, int nm) {
 
 }  // namespace
 
+namespace scvx {
+int check_flight(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, int nsub, int mode, const void* report) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (B < 1) return fail(ctx, SCVX_ERR_ARG, "flight check: B >= 1 required");
+    if (K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "flight check: K must equal the problem's K");
+    if (nsub < 1 || nsub > 1000) return fail(ctx, SCVX_ERR_ARG, "flight check: nsub must be in [1,1000]");
+    if (mode != SCVX_FLIGHT_SHOOT && mode != SCVX_FLIGHT_PLAN)
+        return fail(ctx, SCVX_ERR_ARG, "flight check: unknown mode (SCVX_FLIGHT_SHOOT or SCVX_FLIGHT_PLAN)");
+    if (!x || !u || !sigma || !report) return fail(ctx, SCVX_ERR_ARG, "flight check: null buffer");
+    if (ctx->prob.aero_kind == 1 && !ctx->dyn.aero)
+        return fail(ctx, SCVX_ERR_STATE, "AtmosphericData problem: call scvx_set_aero_table first");
+    return SCVX_OK;
+}
+}  // namespace scvx
+
 extern "C" {
 
 int scvx_ctx_create(const scvx_problem* p, int device, scvx_ctx** out) {
@@ -380,6 +395,39 @@ static int disc_host(scvx_ctx* ctx, int B, int K, const double* x, const double*
         SCVX_HIP(ctx, scvx::launch_propagate(ctx, B, K, dx.p, du.p, ds.p, dt, de.p, st));
     SCVX_HIP(ctx, hipMemcpyAsync(endpoint, de.p, ne * 8, hipMemcpyDeviceToHost, st));
     if (with_deriv) SCVX_HIP(ctx, hipMemcpyAsync(deriv, dd.p, nd * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+int scvx_flight_check_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev, int nsub,
+                          int mode, double* report_dev, double* xfly_dev) {
+    int rc = scvx::check_flight(ctx, B, K, x_dev, u_dev, sigma_dev, nsub, mode, report_dev);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_flight(ctx, B, K, x_dev, u_dev, sigma_dev, nsub, mode, report_dev, xfly_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_flight_check_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, int nsub,
+                               int mode, double* report, double* xfly) {
+    int rc = scvx::check_flight(ctx, B, K, x, u, sigma, nsub, mode, report);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx);
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP;
+    DevBuf dx, du, ds, dr, df;
+    SCVX_HIP(ctx, hipMalloc(&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc(&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc(&ds.p, (size_t)B * 8));
+    SCVX_HIP(ctx, hipMalloc(&dr.p, nr * 8));
+    if (xfly) SCVX_HIP(ctx, hipMalloc(&df.p, nx * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_flight(ctx, B, K, dx.p, du.p, ds.p, nsub, mode, dr.p, df.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    if (xfly) SCVX_HIP(ctx, hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st));
     SCVX_HIP(ctx, hipStreamSynchronize(st));
     return SCVX_OK;
 }

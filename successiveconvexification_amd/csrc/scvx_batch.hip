@@ -678,6 +678,29 @@ int scvx_batch_get_trajectory(scvx_batch* b, double* traj) {
     return SCVX_OK;
 }
 
+int scvx_batch_flight_check(scvx_batch* b, int nsub, int mode, double* report, double* xfly) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (nsub == 0) nsub = ctx->nsub;
+    // b->x / u / sigma are the split views of the accepted iterate (kept current by every step); only read here
+    rc = scvx::check_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, report);
+    if (rc) return rc;
+    const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14;
+    double *dr = nullptr, *df = nullptr;
+    SCVX_HIP(ctx, hipMalloc((void**)&dr, nr * 8));
+    hipError_t e = xfly ? hipMalloc((void**)&df, nx * 8) : hipSuccess;
+    hipStream_t st = ctx->stream;
+    if (e == hipSuccess) e = scvx::launch_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, dr, df, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(report, dr, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df, nx * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(dr);
+    if (df) (void)hipFree(df);
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_flight_check: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
 int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
     int rc = check_batch(b, true);
     if (rc) return rc;

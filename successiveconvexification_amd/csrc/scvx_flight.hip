@@ -1,0 +1,185 @@
+// Flight check (scvx_flight_check_f64, include/scvx.h): the open-loop rollout of a batch of plans and the audit of their path
+// constraints between the nodes.  No counterpart in the reference, which imposes every path constraint of build_model
+// (rocketland.jl:136-209) at the nodes and never re-flies a plan.
+//
+// flight_kernel: ONE LANE PER TRAJECTORY.  The K segments of a trajectory depend on each other (single shooting), so the lane
+// walks its K x nsub RK4 substeps in order with the arithmetic of propagate_kernel (scvx_discretize.hip: rhs_only<>, first-order
+// hold from the two node values, the same fma forms, sigma scaling).  At every substep boundary s = 0..nsub of every segment it
+// evaluates the path functions and keeps their running maxima in registers; nothing but the K+1 node rows (optional) and the
+// 16-double report leaves the lane.  Blocks of one wavefront: at B = 8,192 that is 128 wavefronts over 256 CUs, each alone on
+// its SIMD -- the walk is one long dependent chain, so wavefronts are spread, not stacked.  Constants ride by value in the kernel
+// argument (scalar registers), as DynPK does; no LDS.
+#include <cmath>
+#include <limits>
+#include "scvx_internal.hpp"
+
+namespace scvx {
+
+// the constants of the path functions, formed as oracle/socp.py:99-101,188 / rocketland.jl:63-65 form them
+struct FlightK {
+    double rIf[3], vIf[3], qBIf[4], wBf[3];
+    double mdry, tggs, sqcm, omMax, Tmax, Tmin, inv_cosd, vmax, finmxf;
+    int dp;   // SCVX_MODEL_DPMAX
+};
+
+// NaN-propagating running maximum (fmax alone drops a NaN): once NaN, always NaN
+__device__ __forceinline__ double nmax(double a, double v) { return (v > a || v != v) ? v : a; }
+
+template <bool AERO, bool FIN, bool TRQ>
+__global__ __launch_bounds__(64) void flight_kernel(DynPK<double, TRQ> p, FlightK c, int B, int K, const double* __restrict__ x,
+                                                    const double* __restrict__ u, const double* __restrict__ sigma, double dt,
+                                                    int nsub, int mode, double* __restrict__ report, double* __restrict__ xfly) {
+    typedef double R;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    constexpr int NU = FIN ? 5 : 3;
+    const R* xb = x + (size_t)b * (K + 1) * 14;
+    const R* ub = u + (size_t)b * (K + 1) * NU;
+    R* xf = xfly ? xfly + (size_t)b * (K + 1) * 14 : nullptr;
+    const R sig = sigma[b];
+    const R h = dt / R(nsub);
+    const R inv_n = R(1.0) / R(nsub);
+    const R ninf = -std::numeric_limits<double>::infinity();
+    R xs[14], ukv[NU], upv[NU];
+#pragma unroll
+    for (int i = 0; i < 14; i++) xs[i] = xb[i];
+#pragma unroll
+    for (int j = 0; j < NU; j++) upv[j] = ub[j];
+    if (xf) {
+#pragma unroll
+        for (int i = 0; i < 14; i++) xf[i] = xs[i];
+    }
+    R gap = R(0.0), bad = R(0.0);   // bad: 0 while every sampled state (and every node difference) is finite, else NaN
+    R g_mass = ninf, g_glide = ninf, g_tilt = ninf, g_rate = ninf, g_tmax = ninf, g_tmin = ninf, g_gimbal = ninf, g_dp = ninf,
+      g_fin = ninf, qn = R(0.0);
+    for (int k = 0; k < K; k++) {
+#pragma unroll
+        for (int j = 0; j < NU; j++) { ukv[j] = upv[j]; upv[j] = ub[(size_t)(k + 1) * NU + j]; }
+        if (mode == SCVX_FLIGHT_PLAN && k > 0) {
+#pragma unroll
+            for (int i = 0; i < 14; i++) xs[i] = xb[(size_t)k * 14 + i];
+        }
+        for (int s = 0; s <= nsub; s++) {
+            // ---- sample: state xs, control of the hold at s / nsub (the stage-0 control of substep s) ----
+            const R lk0 = R(s) * inv_n;
+            R us[NU];
+#pragma unroll
+            for (int j = 0; j < NU; j++) us[j] = fma(ukv[j], R(1.0) - lk0, upv[j] * lk0);
+            const R un = sqrt(us[0] * us[0] + us[1] * us[1] + us[2] * us[2]);
+            g_tmax = nmax(g_tmax, un - c.Tmax);
+            g_tmin = nmax(g_tmin, c.Tmin - un);
+            g_gimbal = nmax(g_gimbal, un - us[0] * c.inv_cosd);
+            if (FIN) g_fin = nmax(g_fin, sqrt(us[3] * us[3] + us[4] * us[4]) - c.finmxf);
+            g_mass = nmax(g_mass, c.mdry - xs[0]);
+            g_glide = nmax(g_glide, c.tggs * sqrt(xs[2] * xs[2] + xs[3] * xs[3]) - xs[1]);
+            g_tilt = nmax(g_tilt, sqrt(xs[9] * xs[9] + xs[10] * xs[10]) - c.sqcm);
+            g_rate = nmax(g_rate, sqrt(xs[11] * xs[11] + xs[12] * xs[12] + xs[13] * xs[13]) - c.omMax);
+            if (c.dp) g_dp = nmax(g_dp, sqrt(xs[4] * xs[4] + xs[5] * xs[5] + xs[6] * xs[6]) - c.vmax);
+            qn = nmax(qn, fabs(sqrt(xs[7] * xs[7] + xs[8] * xs[8] + xs[9] * xs[9] + xs[10] * xs[10]) - R(1.0)));
+#pragma unroll
+            for (int i = 0; i < 14; i++) bad = fma(xs[i], R(0.0), bad);
+            if (s == nsub) break;
+            // ---- one RK4 substep, as propagate_kernel takes it ----
+            R xa[14], xt[14];
+#pragma unroll
+            for (int i = 0; i < 14; i++) {
+                xa[i] = xs[i];
+                xt[i] = xs[i];
+            }
+#pragma unroll
+            for (int stg = 0; stg < 4; stg++) {
+                const R lkp = (R(s) + (stg == 0 ? R(0.0) : (stg == 3 ? R(1.0) : R(0.5)))) * inv_n;
+                const R lkm = R(1.0) - lkp;
+                R uu[NU];
+#pragma unroll
+                for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
+                R g[14];
+                rhs_only<AERO, FIN, TRQ>(p, xt, uu, g);
+                const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
+                const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
+#pragma unroll
+                for (int i = 0; i < 14; i++) {
+                    const R dx = sig * g[i];
+                    xa[i] = fma(wacc, dx, xa[i]);
+                    if (stg < 3) xt[i] = fma(wnext, dx, xs[i]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 14; i++) xs[i] = xa[i];
+        }
+        // ---- node k + 1: the flown state against the planned one ----
+        const R* xn = xb + (size_t)(k + 1) * 14;
+#pragma unroll
+        for (int i = 0; i < 14; i++) {
+            const R d = xs[i] - xn[i];
+            gap = nmax(gap, fabs(d));
+            bad = fma(d, R(0.0), bad);
+        }
+        if (xf) {
+#pragma unroll
+            for (int i = 0; i < 14; i++) xf[(size_t)(k + 1) * 14 + i] = xs[i];
+        }
+    }
+    // xs is the flown final node (in PLAN mode: the end of the last segment)
+    R mr = R(0.0), mv = R(0.0), mq = R(0.0), mw = R(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const R dr = xs[1 + i] - c.rIf[i], dv = xs[4 + i] - c.vIf[i], dw = xs[11 + i] - c.wBf[i];
+        mr = fma(dr, dr, mr); mv = fma(dv, dv, mv); mw = fma(dw, dw, mw);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const R dq = xs[7 + i] - c.qBIf[i]; mq = fma(dq, dq, mq); }
+    R* o = report + (size_t)b * SCVX_FLIGHT_NREP;
+    o[SCVX_FLIGHT_GAP] = gap + bad;
+    o[SCVX_FLIGHT_MISS_R] = sqrt(mr) + bad;
+    o[SCVX_FLIGHT_MISS_V] = sqrt(mv) + bad;
+    o[SCVX_FLIGHT_MISS_Q] = sqrt(mq) + bad;
+    o[SCVX_FLIGHT_MISS_W] = sqrt(mw) + bad;
+    o[SCVX_FLIGHT_MASS_END] = xs[0];
+    o[SCVX_FLIGHT_G_MASS] = g_mass + bad;
+    o[SCVX_FLIGHT_G_GLIDE] = g_glide + bad;
+    o[SCVX_FLIGHT_G_TILT] = g_tilt + bad;
+    o[SCVX_FLIGHT_G_RATE] = g_rate + bad;
+    o[SCVX_FLIGHT_G_TMAX] = g_tmax;
+    o[SCVX_FLIGHT_G_TMIN] = g_tmin;
+    o[SCVX_FLIGHT_G_GIMBAL] = g_gimbal;
+    o[SCVX_FLIGHT_G_DP] = c.dp ? g_dp + bad : ninf;
+    o[SCVX_FLIGHT_G_FIN] = g_fin;
+    o[SCVX_FLIGHT_QNORM] = qn + bad;
+}
+
+hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, int nsub,
+                         int mode, double* report, double* xfly, hipStream_t st) {
+    const scvx_problem& P = ctx->prob;
+    const double d2r = M_PI / 180.0;
+    FlightK c{};
+    for (int i = 0; i < 3; i++) { c.rIf[i] = P.rIf[i]; c.vIf[i] = P.vIf[i]; c.wBf[i] = P.wBf[i]; }
+    for (int i = 0; i < 4; i++) c.qBIf[i] = P.qBIf[i];
+    c.mdry = P.mdry;
+    c.tggs = std::tan(P.gammaGs * d2r);
+    c.sqcm = std::sqrt((1.0 - std::cos(P.thetaMax * d2r)) / 2.0);
+    c.omMax = P.omMax;
+    c.Tmax = P.Tmax;
+    c.Tmin = P.Tmin;
+    c.inv_cosd = 1.0 / std::cos(P.deltaMax * d2r);
+    c.dp = (P.model_flags & SCVX_MODEL_DPMAX) ? 1 : 0;
+    c.vmax = c.dp ? std::sqrt(2.0 * P.dpMax / P.rho) : 0.0;
+    c.finmxf = P.finmxf;
+    const double dt = 1.0 / (K + 1);
+    const dim3 g((unsigned)((B + 63) / 64)), blk(64);
+    const DynP<double> dp(ctx->dyn);
+    if (ctx->dyn.trq) {
+        const DynPT<double> dpt(ctx->dyn);
+        if (ctx->dyn.fin) hipLaunchKernelGGL((flight_kernel<true, true, true>), g, blk, 0, st, dpt, c, B, K, x, u, sigma, dt, nsub, mode, report, xfly);
+        else hipLaunchKernelGGL((flight_kernel<true, false, true>), g, blk, 0, st, dpt, c, B, K, x, u, sigma, dt, nsub, mode, report, xfly);
+    } else if (ctx->dyn.fin) {
+        if (ctx->dyn.aero) hipLaunchKernelGGL((flight_kernel<true, true, false>), g, blk, 0, st, dp, c, B, K, x, u, sigma, dt, nsub, mode, report, xfly);
+        else hipLaunchKernelGGL((flight_kernel<false, true, false>), g, blk, 0, st, dp, c, B, K, x, u, sigma, dt, nsub, mode, report, xfly);
+    } else if (ctx->dyn.aero)
+        hipLaunchKernelGGL((flight_kernel<true, false, false>), g, blk, 0, st, dp, c, B, K, x, u, sigma, dt, nsub, mode, report, xfly);
+    else
+        hipLaunchKernelGGL((flight_kernel<false, false, false>), g, blk, 0, st, dp, c, B, K, x, u, sigma, dt, nsub, mode, report, xfly);
+    return hipGetLastError();
+}
+
+}  // namespace scvx

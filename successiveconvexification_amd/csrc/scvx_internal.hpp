@@ -47,6 +47,12 @@ hipError_t launch_linearize_f32(const scvx_ctx* ctx, int B, int K, const float* 
 hipError_t launch_propagate_f32(const scvx_ctx* ctx, int B, int K, const float* x, const float* u, const float* sigma,
                                 float dt, float* xnext, hipStream_t st);
 
+// Flight check (scvx_flight.hip): report[B][SCVX_FLIGHT_NREP], xfly[B][K+1][14] or nullptr; one lane per trajectory, dt = 1 / (K + 1).
+hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, int nsub,
+                         int mode, double* report, double* xfly, hipStream_t st);
+// argument checks shared by scvx_flight_check_f64[_host] and scvx_batch_flight_check (scvx_api.hip)
+int check_flight(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, int nsub, int mode, const void* report);
+
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],
 // info [B][6] = status, iters, pobj, gap, pres, dres.  threedof_to_record overwrites the trajectory records [B][(K+1)*(14+NU)+1]
 // of the trajectories whose solve is optimal with the LinPoints of initial_solve.jl:90-105.

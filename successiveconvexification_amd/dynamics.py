@@ -112,6 +112,64 @@ def propagate_batch(cache: IntegratorCache, x, u, sigma, dt):
     return e
 
 
+class FlightReport:
+    """The report of a flight check (scvx_flight_check_f64, include/scvx.h): `raw` [B][16], one named numpy view per column
+    (report.GAP, report.G_TMIN, ... -- _lib.FLIGHT_COLUMNS), `xfly` [B][K+1][14] (the flown node states) or None, and `mode`.
+    g <= 0 means satisfied, in the problem's own units.  G_TMIN > 0 between nodes that sit on the bound belongs to the reference's
+    formulation (lower bound linearised at the nodes, first-order-hold control), not to the solver."""
+
+    G_COLUMNS = tuple(n for n in _lib.FLIGHT_COLUMNS if n.startswith("G_"))
+
+    def __init__(self, raw, xfly=None, mode="shoot"):
+        self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.FLIGHT_NREP)
+        self.xfly = xfly
+        self.mode = mode
+        for name, i in _lib.FLIGHT_INDEX.items():
+            setattr(self, name, self.raw[:, i])
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    def active(self):
+        """Names of the G_* columns the model enforces (G_DP / G_FIN are -inf in every row when their flag is clear)."""
+        return tuple(n for n in self.G_COLUMNS if not np.all(np.isneginf(getattr(self, n))))
+
+    def worst(self):
+        """[B]: the largest G_* of each trajectory (NaN if any is NaN)."""
+        g = self.raw[:, [_lib.FLIGHT_INDEX[n] for n in self.G_COLUMNS]]
+        return np.where(np.isnan(g).any(axis=1), np.nan, np.max(np.nan_to_num(g, nan=-np.inf), axis=1))
+
+    def ok(self, tol=0.0):
+        """[B] bool: every active G_* <= tol (a NaN row is not ok)."""
+        return self.worst() <= tol
+
+
+def _flight_mode(mode):
+    if isinstance(mode, str):
+        if mode not in ("shoot", "plan"):
+            raise ValueError("mode must be 'shoot' or 'plan' (or SCVX_FLIGHT_SHOOT / SCVX_FLIGHT_PLAN), not %r" % (mode,))
+        return _lib.FLIGHT_SHOOT if mode == "shoot" else _lib.FLIGHT_PLAN
+    return int(mode)   # an unknown number goes to the library, which refuses it with its own message
+
+
+def flight_check_batch(cache: IntegratorCache, x, u, sigma, nsub=None, mode="shoot", dense=False) -> FlightReport:
+    """Fly the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] open loop on the device and audit the path constraints between the
+    nodes (scvx_flight_check_f64_host).  mode "shoot": single shooting from x[:, 0]; "plan": restart at every planned node.
+    nsub: RK4 substeps per segment (None = the cache's); dense: also return the flown node states."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], cache.nu) or sigma.shape != (x.shape[0],):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % cache.nu)
+    B, K1, _ = x.shape
+    rep = np.empty((B, _lib.FLIGHT_NREP))
+    xfly = np.empty((B, K1, 14)) if dense else None
+    _lib.check(cache.handle, cache._L.scvx_flight_check_f64_host(
+        cache.handle, B, K1 - 1, _p(x), _p(u), _p(sigma), int(cache.npts if nsub is None else nsub), int(_flight_mode(mode)),
+        _p(rep), _p(xfly) if dense else None), "scvx_flight_check_f64_host")
+    return FlightReport(rep, xfly, mode)
+
+
 def _pf(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 

@@ -111,3 +111,37 @@ def reduce_clock(elapsed, done, dist=None, device="cpu"):
     n = torch.tensor([float(done)], dtype=torch.float64, device=device)
     dist.all_reduce(n, op=dist.ReduceOp.SUM)
     return float(t.item()), int(n.item())
+
+
+def flight_summary(report, status, tol=0.0):
+    """What a Monte-Carlo batch has to say once it is solved and flown.  report: a dynamics.FlightReport or its raw [N][16] array
+    (e.g. gathered over ranks with scvx_allgather_f64 and flattened); status [N]: the SCvx statuses of scvx_solve.  Returns a plain
+    dict: counts by SCvx status, the number of converged plans, the share of them whose every G_* is <= tol, and min / median /
+    p99 / max of GAP, MISS_R, MISS_V, MASS_END and each G_* over the converged plans (None where there is none).  Pure numpy."""
+    from ._lib import FLIGHT_COLUMNS, FLIGHT_INDEX, FLIGHT_NREP
+    names = {0: "converged", 1: "running", 2: "rejected", 3: "solver", 4: "nonfinite", 5: "infeasible"}
+    raw = np.asarray(getattr(report, "raw", report), np.float64).reshape(-1, FLIGHT_NREP)
+    status = np.asarray(status).reshape(-1)
+    if status.shape[0] != raw.shape[0]:
+        raise ValueError("report has %d rows, status %d" % (raw.shape[0], status.shape[0]))
+    counts = {n: int(np.sum(status == c)) for c, n in names.items()}
+    counts["other"] = int(status.shape[0] - sum(counts.values()))
+    conv = raw[status == 0]
+    gcols = [n for n in FLIGHT_COLUMNS if n.startswith("G_")]
+    out = {"n": int(raw.shape[0]), "counts": counts, "converged": int(conv.shape[0]), "tol": float(tol), "stats": {}}
+    if conv.shape[0]:
+        g = conv[:, [FLIGHT_INDEX[n] for n in gcols]]
+        ok = ~np.isnan(g).any(axis=1) & (np.nan_to_num(g, nan=np.inf).max(axis=1) <= tol)
+        out["feasible_share"] = float(np.mean(ok))
+    else:
+        out["feasible_share"] = None
+    for n in ["GAP", "MISS_R", "MISS_V", "MASS_END"] + gcols:
+        c = conv[:, FLIGHT_INDEX[n]]
+        if c.shape[0] == 0:
+            out["stats"][n] = None
+        elif np.all(np.isneginf(c)):   # a constraint the model does not enforce
+            out["stats"][n] = {k: float("-inf") for k in ("min", "median", "p99", "max")}
+        else:
+            out["stats"][n] = {"min": float(np.min(c)), "median": float(np.median(c)), "p99": float(np.percentile(c, 99)),
+                               "max": float(np.max(c))}
+    return out

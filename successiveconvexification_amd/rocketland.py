@@ -5,6 +5,7 @@
     plot_solution_data(ip) / dump_solution(ip, path)              rocketland.jl:454-478 (the arrays plot_solution draws)
     solve_step(iteration, cache) -> (ProblemIteration, |nu|, dJ)  rocketland.jl:226-321
     solve_problem(iprob, cache) -> (ProblemIteration, cnu, cdel)  rocketland.jl:432-443
+    fly(iteration, cache) -> FlightReport                         (new: open-loop flight + path audit of a plan)
 The recipe of rocketland.jl:26-32 reads the same here:
     cache = IntegratorCache(prob, ProbInfo.from_problem(prob), make_dynamics_module(...))
     pi = create_initial(prob, cache); pi, cnu, cdel = solve_step(pi, cache)
@@ -50,6 +51,16 @@ def solve_problem(iprob: DescentProblem, cache: IntegratorCache):
         prob, cnu, cdel = solve_step(prob, cache)
         it += 1
     return prob, cnu, cdel
+
+
+def fly(iteration: ProblemIteration, cache: IntegratorCache = None, nsub=None, mode="shoot", dense=False):
+    """Open-loop flight of an iterate's plan (`about`, `sigma`) and the audit of its path constraints between the nodes -- what the
+    reference never does: its constraints hold at the nodes (rocketland.jl:136-209).  Returns a dynamics.FlightReport of one row."""
+    from .dynamics import flight_check_batch
+    cache = cache if cache is not None else iteration.cache
+    x = np.stack([pt.state for pt in iteration.about])[None]
+    u = np.stack([pt.control for pt in iteration.about])[None]
+    return flight_check_batch(cache, x, u, np.array([float(iteration.sigma)]), nsub=nsub, mode=mode, dense=dense)
 
 
 def run_iters(iprob: DescentProblem, niters: int, cache: IntegratorCache = None):
