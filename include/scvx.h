@@ -7,6 +7,7 @@
  *   Dynamics.linearize_dynamics   dynamics.jl:321-334  ->  scvx_linearize_f64[_host]
  *   Dynamics.predict_state        dynamics.jl:315-317  ->  scvx_propagate_f64[_host]
  *   (no counterpart: open-loop flight + path audit)    ->  scvx_flight_check_f64[_host], scvx_batch_flight_check
+ *   (no counterpart: LQR gains + closed-loop flight)   ->  scvx_track_gains_f64[_host], scvx_track_fly_f64[_host], scvx_batch_track_*
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -241,6 +242,48 @@ int scvx_flight_check_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, cons
 int scvx_flight_check_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *sigma,
                                int nsub, int mode, double *report, double *xfly);
 
+/* ---- plan tracking: time-varying LQR gains about a plan and the closed-loop flight under them ----------------------
+ * The flight check flies a plan from exactly its own x[0].  These two calls answer what happens when the vehicle is NOT there.
+ * Notation: NU = scvx_control_dim, n = 14 + NU, dx_k = x_k - xbar_k, du_k = u_k - ubar_k (bars: the plan), sigma held.  The
+ * derivative tile of segment k, column-major 14 x (14 + 2 NU + 1) = [A_k | B-_k | B+_k | Sigma_k], gives
+ *     dx_{k+1} = A_k dx_k + B-_k du_k + B+_k du_{k+1}.
+ * The control is a first-order hold, so the decision at node k is the NEXT node's control: with z_k = [dx_k; du_k] and
+ * v_k = du_{k+1},  z_{k+1} = F_k z_k + G_k v_k,  F_k = [[A_k, B-_k], [0, 0]],  G_k = [B+_k; I].  Cost, diagonal weights
+ * q[14] >= 0, r[NU] > 0, qf[14] >= 0 in the problem's normalised units:
+ *     J = sum_{k=0}^{K-1} (dx_k' Q dx_k + v_k' R v_k) + dx_K' Qf dx_K.
+ * Backward recursion from P_K = diag(Qf, 0), Qz = diag(Q, 0), k = K-1 .. 0:
+ *     S_k = R + G_k' P_{k+1} G_k,  H_k = G_k' P_{k+1} F_k,  L_k = -S_k^-1 H_k (Cholesky),
+ *     P_k = Qz + F_k' P_{k+1} F_k + H_k' L_k, symmetrised.
+ * Feedback: u_{k+1} = ubar_{k+1} + L_k [x_k - xbar_k; u_k - ubar_k], u_0 = ubar_0; z_0' P_0 z_0 is the predicted cost of an
+ * initial deviation.  The weights are the caller's choice (the quaternion and mass directions are nearly uncontrollable).
+ *
+ * gain [B][K][NU][14+NU] row-major: du_{k+1}[j] = sum_i gain[b][k][j][i] * z_k[i];  p0 [B][14+NU][14+NU] or NULL.
+ * deriv [B][K][14+2NU+1][14] as scvx_linearize_f64 writes it.  q14 / rNU / qf14 are HOST arrays in both forms.  The _f64 form
+ * is asynchronous on the context's stream.  SCVX_ERR_ARG for any r[j] <= 0, a negative or non-finite weight, B < 1,
+ * K != the problem's K, a null deriv / weight / gain. */
+int scvx_track_gains_f64(scvx_ctx *ctx, int B, int K, const double *deriv_dev, const double *q14, const double *rNU,
+                         const double *qf14, double *gain_dev, double *p0_dev);
+int scvx_track_gains_f64_host(scvx_ctx *ctx, int B, int K, const double *deriv, const double *q14, const double *rNU,
+                              const double *qf14, double *gain, double *p0);
+/* Closed-loop flight: x_fly[0] = xbar_0 + dx0, u_fly[0] = ubar_0; at every node k = 0..K-1 the feedback above forms
+ * u_fly[k+1] from the flown state and the applied control, then segment k is integrated from x_fly[k] under the hold
+ * (u_fly[k], u_fly[k+1]) with the arithmetic of the flight check.  The report is the flight check's, column for column
+ * (SCVX_FLIGHT_*): samples at every substep boundary, GAP = max over nodes 1..K of |x_fly - xbar|_inf, G_* on the flown
+ * state and the APPLIED control.  All-zero gains, dx0 = NULL, flags = 0 is the SCVX_FLIGHT_SHOOT flight check.
+ * flags: SCVX_TRACK_CLAMP rescales, after the feedback, the thrust part u[1:3] of the new node control (direction kept) so
+ * that its norm lies in [Tmin, Tmax], and with SCVX_MODEL_FINS u[4:5] so that its norm is at most finmxf.  The gimbal cone is
+ * not projected (G_GIMBAL reports it).  Without the flag the commanded control is applied as it is and G_TMAX / G_TMIN show
+ * what the law asked for.
+ * dx0 [B][14] or NULL (= 0); report [B][SCVX_FLIGHT_NREP]; xfly [B][K+1][14] or NULL; ufly [B][K+1][NU] or NULL.
+ * SCVX_ERR_ARG for nsub outside [1, 1000], unknown flag bits, B < 1, K != the problem's K, a null x / u / sigma / gain / report. */
+#define SCVX_TRACK_CLAMP 1
+int scvx_track_fly_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                       const double *gain_dev, const double *dx0_dev, int nsub, int flags, double *report_dev,
+                       double *xfly_dev, double *ufly_dev);
+int scvx_track_fly_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *sigma,
+                            const double *gain, const double *dx0, int nsub, int flags, double *report, double *xfly,
+                            double *ufly);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -355,6 +398,14 @@ int scvx_batch_get_solver_stats(scvx_batch *b, int32_t *status, int32_t *iters, 
  * are host arrays; nsub = 0 takes the context's.  Reads the iterate and leaves the batch untouched (trajectory, scalars, flags,
  * linearisation, solver workspace): a solve_step after it equals the one without it bit for bit.  Synchronises. */
 int scvx_batch_flight_check(scvx_batch *b, int nsub, int mode, double *report, double *xfly);
+
+/* Plan tracking on the batch's current accepted iterate and its own derivative tiles (float tiles are widened on load when
+ * scvx_batch_set_linearization_f32 is on): the gains, and the closed-loop flight under them from x[0] + dx0.  Host outputs;
+ * any output pointer may be NULL; nsub = 0 takes the context's.  The gains live in scratch that is allocated on first use and
+ * freed with the batch; the batch itself is left untouched, as by scvx_batch_flight_check.  Synchronises. */
+int scvx_batch_track_gains(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, double *gain, double *p0);
+int scvx_batch_track_fly(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *dx0, int nsub,
+                         int flags, double *report, double *xfly, double *ufly);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

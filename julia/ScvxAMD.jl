@@ -315,6 +315,80 @@ flight_check_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{
         (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
         cache.ctx, B, K, x_dev, u_dev, sigma_dev, nsub, mode, report_dev, xfly_dev), "scvx_flight_check_f64")
 
+# ---- plan tracking (new): time-varying LQR gains about a plan and the closed-loop flight under them ---------------------------
+# include/scvx.h, "plan tracking".  gain is n x NU x K x B (column-major == [B][K][NU][n], n = 14 + NU): du_{k+1} = gain[:, :, k, b]' * [dx_k; du_k].
+# q, r, qf: diagonal weights (scalars broadcast); 1, 1, 100 is a starting point, not tuning advice.
+const TRACK_CLAMP = 1    # SCVX_TRACK_CLAMP: rescale the commanded thrust / fin norms into their bounds
+_track_w(v, m::Int) = v isa Real ? fill(Float64(v), m) : (length(v) == m ? Vector{Float64}(v) : error("weight needs $m components"))
+
+# the gains of a batch's current accepted iterate from its own derivative tiles: (gain, p0 n x n x B or nothing)
+function track_gains(b::Batch; q=1.0, r=1.0, qf=100.0, cost::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx)); n = 14 + NU
+    gain = Array{Float64,4}(undef, n, NU, K, b.B)
+    p0 = cost ? Array{Float64,3}(undef, n, n, b.B) : nothing
+    check(b.cache.ctx, ccall((:scvx_batch_track_gains, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), gain, cost ? pointer(p0) : Ptr{Cdouble}(C_NULL)), "scvx_batch_track_gains")
+    return gain, p0
+end
+
+# closed-loop flight of a batch's current accepted iterate from x[0] + dx0 (14 x B or nothing): (report 16 x B, xfly, ufly);
+# the report's rows are the flight check's (FLIGHT_* + 1); nsub = 0 takes the context's
+function track(b::Batch; dx0::Union{Nothing,Matrix{Float64}}=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false,
+               dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    dx0 === nothing || size(dx0) == (14, b.B) || error("dx0 must be 14 x B")
+    report = Matrix{Float64}(undef, FLIGHT_NREP, b.B)
+    xfly = dense ? Array{Float64,3}(undef, 14, K + 1, b.B) : nothing
+    ufly = dense ? Array{Float64,3}(undef, NU, K + 1, b.B) : nothing
+    check(b.cache.ctx, ccall((:scvx_batch_track_fly, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), dx0 === nothing ? Ptr{Cdouble}(C_NULL) : pointer(dx0), nsub,
+        clamp ? TRACK_CLAMP : 0, report, dense ? pointer(xfly) : Ptr{Cdouble}(C_NULL), dense ? pointer(ufly) : Ptr{Cdouble}(C_NULL)),
+        "scvx_batch_track_fly")
+    return report, xfly, ufly
+end
+
+# any plans (host arrays): gains from derivative tiles 14 x (14 + 2 NU + 1) x K x B as linearisation returns them
+function track_gains(cache::Cache, deriv::Array{Float64,4}; q=1.0, r=1.0, qf=100.0, cost::Bool=false)
+    NU = (size(deriv, 2) - 15) ÷ 2; n = 14 + NU; K = size(deriv, 3); B = size(deriv, 4)
+    gain = Array{Float64,4}(undef, n, NU, K, B)
+    p0 = cost ? Array{Float64,3}(undef, n, n, B) : nothing
+    check(cache.ctx, ccall((:scvx_track_gains_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, deriv, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), gain, cost ? pointer(p0) : Ptr{Cdouble}(C_NULL)),
+        "scvx_track_gains_f64_host")
+    return gain, p0
+end
+
+# x 14 x (K+1) x B, u NU x (K+1) x B, sigma B, gain n x NU x K x B, dx0 14 x B or nothing
+function track(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, gain::Array{Float64,4};
+               dx0::Union{Nothing,Matrix{Float64}}=nothing, nsub::Int=10, clamp::Bool=false, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); NU = size(u, 1)
+    report = Matrix{Float64}(undef, FLIGHT_NREP, B)
+    xfly = dense ? Array{Float64,3}(undef, 14, K + 1, B) : nothing
+    ufly = dense ? Array{Float64,3}(undef, NU, K + 1, B) : nothing
+    check(cache.ctx, ccall((:scvx_track_fly_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, sigma, gain, dx0 === nothing ? Ptr{Cdouble}(C_NULL) : pointer(dx0), nsub, clamp ? TRACK_CLAMP : 0, report,
+        dense ? pointer(xfly) : Ptr{Cdouble}(C_NULL), dense ? pointer(ufly) : Ptr{Cdouble}(C_NULL)), "scvx_track_fly_f64_host")
+    return report, xfly, ufly
+end
+
+# the same two on device pointers (e.g. AMDGPU.jl ROCArrays), asynchronous on the context's stream; q, r, qf stay host vectors
+track_gains_dev!(cache::Cache, B::Int, K::Int, deriv_dev::Ptr{Cdouble}, q::Vector{Float64}, r::Vector{Float64}, qf::Vector{Float64},
+                 gain_dev::Ptr{Cdouble}, p0_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_track_gains_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, deriv_dev, q, r, qf, gain_dev, p0_dev), "scvx_track_gains_f64")
+track_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+           dx0_dev::Ptr{Cdouble}, nsub::Int, flags::Int, report_dev::Ptr{Cdouble}, xfly_dev::Ptr{Cdouble}, ufly_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_track_fly_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nsub, flags, report_dev, xfly_dev, ufly_dev), "scvx_track_fly_f64")
+
 # multi-GPU (one Julia process per GPU): rank 0 draws the id, the host ships its 128 bytes (Distributed / MPI.jl / a file)
 unique_id() = (id = Vector{UInt8}(undef, 128); ccall((:scvx_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("RCCL unavailable"); id)
 comm_create!(c::Cache, id::Vector{UInt8}, rank::Int, world::Int) =

@@ -54,6 +54,7 @@ FLIGHT_NREP = 16
 FLIGHT_COLUMNS = ("GAP", "MISS_R", "MISS_V", "MISS_Q", "MISS_W", "MASS_END", "G_MASS", "G_GLIDE", "G_TILT", "G_RATE", "G_TMAX",
                   "G_TMIN", "G_GIMBAL", "G_DP", "G_FIN", "QNORM")
 FLIGHT_INDEX = {n: i for i, n in enumerate(FLIGHT_COLUMNS)}
+TRACK_CLAMP = 1   # SCVX_TRACK_CLAMP: scvx_track_fly_* rescales the commanded thrust / fin norms into their bounds
 
 _vp = C.c_void_p
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
@@ -77,6 +78,10 @@ SIGNATURES = {
     "scvx_propagate_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
     "scvx_flight_check_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "scvx_flight_check_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "scvx_track_gains_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _dp, _dp, _dp, _vp, _vp]),
+    "scvx_track_gains_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_track_fly_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "scvx_track_fly_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),
@@ -106,6 +111,8 @@ SIGNATURES = {
     "scvx_batch_set_flags": (C.c_int, [_vp, _ip, _ip, _ip]),
     "scvx_batch_get_solver_stats": (C.c_int, [_vp, _ip, _ip, _dp, _dp]),
     "scvx_batch_flight_check": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
+    "scvx_batch_track_gains": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_batch_track_fly": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "scvx_comm_probe": (C.c_int, []),
     "scvx_comm_unique_id": (C.c_int, [_vp]),
     "scvx_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

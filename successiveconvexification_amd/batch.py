@@ -212,6 +212,36 @@ class ScvxBatch:
                                                   _p(xfly) if dense else None), "scvx_batch_flight_check")
         return FlightReport(rep, xfly, mode)
 
+    def track_gains(self, q=None, r=None, qf=None, cost=False):
+        """LQR gains about the batch's current accepted iterate from its own derivative tiles (scvx_batch_track_gains; weights as
+        dynamics.track_gains_batch): gain [B][K][nu][14+nu], with cost=True also p0 [B][14+nu][14+nu].  The batch is left untouched."""
+        from .dynamics import _track_weights
+        nu = self.cache.nu
+        qv, rv, qfv = _track_weights(nu, q, r, qf)
+        gain = np.empty((self.B, self.K, nu, 14 + nu))
+        p0 = np.empty((self.B, 14 + nu, 14 + nu)) if cost else None
+        self._chk(self._L.scvx_batch_track_gains(self.handle, _p(qv), _p(rv), _p(qfv), _p(gain), _p(p0) if cost else None),
+                  "scvx_batch_track_gains")
+        return (gain, p0) if cost else gain
+
+    def track(self, dx0=None, q=None, r=None, qf=None, nsub=None, clamp=False, dense=False):
+        """Fly the batch's current accepted iterate closed loop under its LQR gains from x[0] + dx0 (scvx_batch_track_fly): a
+        dynamics.FlightReport of mode "track" (dense: xfly and ufly).  The batch is left untouched."""
+        from .dynamics import FlightReport, _track_weights
+        nu = self.cache.nu
+        qv, rv, qfv = _track_weights(nu, q, r, qf)
+        if dx0 is not None:
+            dx0 = np.ascontiguousarray(dx0, np.float64)
+            if dx0.shape != (self.B, 14):
+                raise ValueError("shape mismatch: dx0 [B][14]")
+        rep = np.empty((self.B, _lib.FLIGHT_NREP))
+        xfly = np.empty((self.B, self.K + 1, 14)) if dense else None
+        ufly = np.empty((self.B, self.K + 1, nu)) if dense else None
+        self._chk(self._L.scvx_batch_track_fly(self.handle, _p(qv), _p(rv), _p(qfv), _p(dx0) if dx0 is not None else None,
+                                               int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, _p(rep),
+                                               _p(xfly) if dense else None, _p(ufly) if dense else None), "scvx_batch_track_fly")
+        return FlightReport(rep, xfly, "track", ufly)
+
     def set_profiling(self, on: bool):
         self._chk(self._L.scvx_batch_set_profiling(self.handle, 1 if on else 0), "scvx_batch_set_profiling")
 

@@ -208,6 +208,7 @@ struct scvx_batch {
     double *rk = nullptr, *cost = nullptr, *ic = nullptr, *info = nullptr, *out = nullptr, *work = nullptr;
     double *ttr = nullptr;   // trust-region norm bound at the last optimum (reuse_inactive_tr)
     double *acc = nullptr;   // scvx::ACC_N running totals (scvx_batch_get_step_stats)
+    double *track_gain = nullptr, *track_p0 = nullptr;   // scratch of scvx_batch_track_*: allocated on first use, freed with the batch
     int *k1skip = nullptr;   // per trajectory: >= SCVX_ST_REJECTED = the reference point did not change in the last step (K1 skips it)
     int *d_nlive = nullptr;  // device-side count of live trajectories (scvx_solve), mirrored asynchronously into pinned h_nlive[2]
     int *h_nlive = nullptr;
@@ -473,7 +474,8 @@ void scvx_batch_destroy(scvx_batch* b) {
     for (hipEvent_t e : b->ev_nlive) if (e) (void)hipEventDestroy(e);
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
-                    b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip};
+                    b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip,
+                    b->track_gain, b->track_p0};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -698,6 +700,68 @@ int scvx_batch_flight_check(scvx_batch* b, int nsub, int mode, double* report, d
     (void)hipFree(dr);
     if (df) (void)hipFree(df);
     if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_flight_check: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
+// The gains of the batch's current iterate into b->track_gain / b->track_p0 (enqueued on the context's stream).  The tiles in
+// b->deriv / b->deriv_f always belong to the accepted iterate: tr_update_kernel marks for K1 every trajectory whose step was
+// accepted -- the converging step included -- and a rejected or failed step leaves both the iterate and its tiles alone.
+static int enqueue_track_gains(scvx_batch* b, const double* q, const double* r, const double* qf) {
+    scvx_ctx* ctx = b->ctx;
+    int rc = scvx::check_track_weights(ctx, q, r, qf);
+    if (rc) return rc;
+    const size_t n = 14 + b->NU;
+    if (!b->track_gain) {
+        SCVX_HIP(ctx, hipMalloc((void**)&b->track_gain, (size_t)b->B * b->K * b->NU * n * 8));
+        SCVX_HIP(ctx, hipMalloc((void**)&b->track_p0, (size_t)b->B * n * n * 8));
+    }
+    if (b->deriv_f)
+        SCVX_HIP(ctx, scvx::launch_track_gains_f32(ctx, b->B, b->K, b->deriv_f, q, r, qf, b->track_gain, b->track_p0, ctx->stream));
+    else
+        SCVX_HIP(ctx, scvx::launch_track_gains(ctx, b->B, b->K, b->deriv, q, r, qf, b->track_gain, b->track_p0, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_batch_track_gains(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, double* gain, double* p0) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const size_t n = 14 + b->NU;
+    hipStream_t st = ctx->stream;
+    if (gain) SCVX_HIP(ctx, hipMemcpyAsync(gain, b->track_gain, (size_t)b->B * b->K * b->NU * n * 8, hipMemcpyDeviceToHost, st));
+    if (p0) SCVX_HIP(ctx, hipMemcpyAsync(p0, b->track_p0, (size_t)b->B * n * n * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+int scvx_batch_track_fly(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* dx0, int nsub,
+                         int flags, double* report, double* xfly, double* ufly) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (nsub == 0) nsub = ctx->nsub;
+    // every check before anything is enqueued; the outputs are optional here, so a placeholder stands in for `report`
+    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
+    if ((rc = scvx::check_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->x, nsub, flags, b->x))) return rc;
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14, nu = (size_t)b->B * (b->K + 1) * b->NU;
+    double *dr = nullptr, *df = nullptr, *dc = nullptr, *d0 = nullptr;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMalloc((void**)&dr, nr * 8);
+    if (e == hipSuccess && xfly) e = hipMalloc((void**)&df, nx * 8);
+    if (e == hipSuccess && ufly) e = hipMalloc((void**)&dc, nu * 8);
+    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0, (size_t)b->B * 14 * 8);
+    if (e == hipSuccess && dx0) e = hipMemcpyAsync(d0, dx0, (size_t)b->B * 14 * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = scvx::launch_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0, nsub, flags, dr, df, dc, st);
+    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df, nx * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && ufly) e = hipMemcpyAsync(ufly, dc, nu * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    for (double* p : {dr, df, dc, d0})
+        if (p) (void)hipFree(p);
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_fly: ") + hipGetErrorString(e));
     return SCVX_OK;
 }
 

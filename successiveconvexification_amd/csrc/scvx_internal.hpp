@@ -53,6 +53,20 @@ hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, con
 // argument checks shared by scvx_flight_check_f64[_host] and scvx_batch_flight_check (scvx_api.hip)
 int check_flight(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, int nsub, int mode, const void* report);
 
+// Plan tracking (scvx_track.hip).  Gains: one wavefront per trajectory over the derivative tiles (double, or float as
+// scvx_batch_set_linearization_f32 stores them); gain[B][K][NU][14+NU], p0[B][14+NU][14+NU] or nullptr; q / r / qf are host arrays.
+// Closed-loop flight: one lane per trajectory; dx0[B][14], xfly[B][K+1][14], ufly[B][K+1][NU] or nullptr.
+hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, const double* deriv, const double* q, const double* r, const double* qf,
+                              double* gain, double* p0, hipStream_t st);
+hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float* deriv, const double* q, const double* r,
+                                  const double* qf, double* gain, double* p0, hipStream_t st);
+hipError_t launch_track_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
+                            const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly, hipStream_t st);
+// argument checks shared by the context-level and the batch-level entry points
+int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const double* qf);
+int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
+                    const void* report);
+
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],
 // info [B][6] = status, iters, pobj, gap, pres, dres.  threedof_to_record overwrites the trajectory records [B][(K+1)*(14+NU)+1]
 // of the trajectories whose solve is optimal with the LinPoints of initial_solve.jl:90-105.

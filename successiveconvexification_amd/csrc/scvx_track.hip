@@ -1,0 +1,580 @@
+// Plan tracking (scvx_track_gains_f64 / scvx_track_fly_f64, include/scvx.h): the finite-horizon time-varying LQR about a batch of
+// plans and the closed-loop flight under it.  No counterpart in the reference, which never flies a plan.
+//
+// track_gains_kernel: ONE WAVEFRONT PER TRAJECTORY, K sequential steps of the backward Riccati recursion on the first-order-hold
+// model z_{k+1} = F_k z_k + G_k v_k, z = [dx; du], v = du_{k+1}, F = [[A, B-], [0, 0]], G = [B+; I] -- A, B-, B+ are the first
+// 14 + 2 NU columns D of the derivative tile K1 wrote.  Only the 14 x 14 block Pxx of P_{k+1} meets the tile, so one step is
+//     W = Pxx D (14 x m, m = 14 + 2 NU),  T = D' W (m x m),  Y = Pux D (NU x m)
+//     H = T[B+, AB-] + Y[:, AB-],  S = R + T[B+, B+] + Y[:, B+] + Y[:, B+]' + Puu,  L = -S^-1 H,  P = Qz + T[AB-, AB-] + H' L
+// with all operands in LDS (P, D, W, T, Y; H, L, S in W's space: 10.1 KB at NU = 3, 13.1 KB at NU = 5), the two 14-deep products W and T
+// on the FP64 matrix pipe (or one lane per output element: SCVX_TRACK_MFMA=0), everything else one lane per element, the NU x NU
+// Cholesky redundantly on the n lanes that each solve one column of L.  The tile of step k - 1 is fetched into registers (one
+// contiguous run, coalesced) while step k computes and stored to LDS behind the step's last barrier.  DS is the tiles' storage
+// type (double, or float with scvx_batch_set_linearization_f32: widened on load).
+//
+// track_fly_kernel: ONE LANE PER TRAJECTORY, the walk of flight_kernel (scvx_flight.hip: the same RK4 / first-order-hold
+// arithmetic, samples, maxima and NaN handling) with the feedback u_{k+1} = ubar_{k+1} + L_k [x_k - xbar_k; u_k - ubar_k] formed at
+// every node from the FLOWN state and the APPLIED control, an optional clamp of the commanded thrust / fin norms, and an initial
+// state offset per trajectory.  The substep is repeated here, not shared, so that flight_kernel stays bit for bit what it is.
+#include <cmath>
+#include <cstdlib>
+#include <limits>
+#include "scvx_internal.hpp"
+
+namespace scvx {
+
+struct TrackW {
+    double q[14], r[5], qf[14];
+};
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));
+
+// One 16 x 16 tile of C = A B over 14 k-slots on the FP64 matrix pipe (4 x v_mfma_f64_16x16x4_f64; fragment maps as in scvx_socp.hpp:
+// A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], C: register r of lane l is C[(l >> 4) + 4 r][l & 15]).  Operands in LDS with
+// element strides; rows >= ni of A, columns >= nj of B and k >= 14 are fed zeros -- every lane reads a clamped, valid address and the
+// value is masked afterwards.  C element (i, j) is stored at Cm[idx(i, j)] unless idx is negative.
+template <class Idx>
+__device__ __forceinline__ void track_mm16(double* Cm, Idx idx, const double* A, int sai, int sak, int ni, const double* Bm, int sbk,
+                                           int sbj, int nj, int lane) {
+    const int rc = lane & 15, kq = lane >> 4;
+    const int ia = rc < ni ? rc : ni - 1, jb = rc < nj ? rc : nj - 1;
+    v4f64 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int k = 4 * s + kq, kc = k < 14 ? k : 13;
+        const double a = A[ia * sai + kc * sak], b = Bm[kc * sbk + jb * sbj];
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64((rc < ni && k < 14) ? a : 0.0, (rc < nj && k < 14) ? b : 0.0, c, 0, 0, 0);
+    }
+    if (rc < nj) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int row = kq + 4 * r;
+            const int at = row < ni ? idx(row, rc) : -1;
+            if (at >= 0) Cm[at] = c[r];
+        }
+    }
+}
+
+// MF: the two 14-deep products W = Pxx D and T = D' W as 16 x 16 tiles on the matrix pipe (2 + 4 tiles) instead of one lane per element
+template <typename DS, int NU, bool MF>
+__global__ __launch_bounds__(64) void track_gains_kernel(TrackW w, int B, int K, const DS* __restrict__ deriv, double* __restrict__ gain,
+                                                         double* __restrict__ p0) {
+    constexpr int n = 14 + NU, m = 14 + 2 * NU, NC = m + 1, DSZ = 14 * NC, ND = 14 * m;
+    constexpr int NPRE = (ND + 63) / 64;
+    // T is kept without the block above the B+ columns (never read): rows < n with stride n, then the NU rows of B+ with stride m.
+    // H, L and S are born after W's last use and live in its space.  10,064 B at NU = 3: 16 blocks per CU, so that the 32 blocks a CU gets
+    // at B = 8,192 run in two rounds; 13,072 B at NU = 5.
+    constexpr int NT = n * n + NU * m;
+    static_assert(2 * NU * n + NU * NU <= ND, "H, L, S must fit into W");
+    __shared__ double Pl[n * n], Dl[ND], Wl[ND], Yl[NU * m], Tl[NT];
+    double *Hl = Wl, *Ll = Wl + NU * n, *Sl = Wl + 2 * NU * n;
+    auto tidx = [](int a, int c) { return a < n ? (c < n ? a * n + c : -1) : n * n + (a - n) * m + c; };
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const DS* tiles = deriv + (size_t)b * K * DSZ;
+    double* gb = gain + (size_t)b * K * NU * n;
+    // P_K = diag(Qf, 0); tile K - 1
+    for (int e = lane; e < n * n; e += 64) {
+        const int a = e / n, c = e % n;
+        Pl[e] = (a == c && a < 14) ? w.qf[a] : 0.0;
+    }
+    {
+        const DS* t = tiles + (size_t)(K - 1) * DSZ;
+        for (int e = lane; e < ND; e += 64) Dl[e] = (double)t[e];
+    }
+    __syncthreads();
+    for (int k = K - 1; k >= 0; k--) {
+        // the next step's tile, in flight while this one computes
+        DS pre[NPRE];
+        if (k > 0) {
+            const DS* t = tiles + (size_t)(k - 1) * DSZ;
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) {
+                const int e = lane + 64 * i;
+                pre[i] = e < ND ? t[e] : DS(0);
+            }
+        }
+        // W = Pxx D (P is symmetric: P[i][l] read for P[l][i], contiguous over the lanes' l), Y = Pux D
+        if (MF) {
+            for (int j0 = 0; j0 < m; j0 += 16)
+                track_mm16(Wl + j0 * 14, [](int i, int j) { return i + 14 * j; }, Pl, n, 1, 14, Dl + j0 * 14, 1, 14, m - j0 < 16 ? m - j0 : 16, lane);
+        } else {
+            for (int e = lane; e < ND; e += 64) {
+                const int l = e % 14, c = e / 14;
+                double s = 0.0;
+#pragma unroll
+                for (int i = 0; i < 14; i++) s = fma(Pl[i * n + l], Dl[c * 14 + i], s);
+                Wl[e] = s;
+            }
+        }
+        for (int e = lane; e < NU * m; e += 64) {
+            const int j = e % NU, c = e / NU;
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 14; i++) s = fma(Pl[(14 + j) * n + i], Dl[c * 14 + i], s);
+            Yl[j * m + c] = s;
+        }
+        __syncthreads();
+        // T = D' W: the [A B-] x [A B-] block and the B+ rows (the block above the B+ columns is their transpose: not formed)
+        if (MF) {
+            for (int i0 = 0; i0 < m; i0 += 16)
+                for (int j0 = 0; j0 < m; j0 += 16)
+                    track_mm16(Tl, [=](int i, int j) { return tidx(i0 + i, j0 + j); }, Dl + i0 * 14, 14, 1, m - i0 < 16 ? m - i0 : 16,
+                               Wl + j0 * 14, 1, 14, m - j0 < 16 ? m - j0 : 16, lane);
+        } else {
+            for (int e = lane; e < m * m; e += 64) {
+                const int a = e % m, c = e / m;
+                if (a < n && c >= n) continue;
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < 14; l++) s = fma(Dl[a * 14 + l], Wl[c * 14 + l], s);
+                Tl[tidx(a, c)] = s;
+            }
+        }
+        __syncthreads();
+        // H = G' P F (NU x n), S = R + G' P G (NU x NU, symmetrised)
+        for (int e = lane; e < NU * n + NU * NU; e += 64) {
+            if (e < NU * n) {
+                const int j = e / n, c = e % n;
+                Hl[e] = Tl[tidx(n + j, c)] + Yl[j * m + c];
+            } else {
+                const int j = (e - NU * n) / NU, l = (e - NU * n) % NU;
+                const double s = 0.5 * (Tl[tidx(n + j, n + l)] + Tl[tidx(n + l, n + j)]) + (Yl[j * m + n + l] + Yl[l * m + n + j]) +
+                                 Pl[(14 + j) * n + 14 + l];
+                Sl[j * NU + l] = j == l ? s + w.r[j] : s;
+            }
+        }
+        __syncthreads();
+        // L = -S^-1 H: lane c factorises S = C C' (its own copy) and solves column c
+        if (lane < n) {
+            double C[NU][NU], y[NU];
+#pragma unroll
+            for (int j = 0; j < NU; j++) {
+#pragma unroll
+                for (int i = j; i < NU; i++) {
+                    double s = Sl[i * NU + j];
+#pragma unroll
+                    for (int l = 0; l < j; l++) s = fma(-C[i][l], C[j][l], s);
+                    C[i][j] = i == j ? sqrt(s) : s / C[j][j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NU; i++) {
+                double s = Hl[i * n + lane];
+#pragma unroll
+                for (int l = 0; l < i; l++) s = fma(-C[i][l], y[l], s);
+                y[i] = s / C[i][i];
+            }
+#pragma unroll
+            for (int i = NU - 1; i >= 0; i--) {
+                double s = y[i];
+#pragma unroll
+                for (int l = i + 1; l < NU; l++) s = fma(-C[l][i], y[l], s);
+                y[i] = s / C[i][i];
+            }
+#pragma unroll
+            for (int i = 0; i < NU; i++) {
+                Ll[i * n + lane] = -y[i];
+                gb[(size_t)k * NU * n + i * n + lane] = -y[i];
+            }
+        }
+        __syncthreads();
+        // P = Qz + F' P F + H' L, symmetrised: each element from both of its triangles
+        for (int e = lane; e < n * n; e += 64) {
+            const int a = e / n, c = e % n;
+            double s1 = Tl[a * n + c], s2 = Tl[c * n + a];
+#pragma unroll
+            for (int j = 0; j < NU; j++) {
+                s1 = fma(Hl[j * n + a], Ll[j * n + c], s1);
+                s2 = fma(Hl[j * n + c], Ll[j * n + a], s2);
+            }
+            const double s = 0.5 * (s1 + s2);
+            Pl[e] = (a == c && a < 14) ? s + w.q[a] : s;
+        }
+        if (k > 0) {
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) {
+                const int e = lane + 64 * i;
+                if (e < ND) Dl[e] = (double)pre[i];
+            }
+        }
+        __syncthreads();
+    }
+    if (p0) {
+        double* o = p0 + (size_t)b * n * n;
+        for (int e = lane; e < n * n; e += 64) o[e] = Pl[e];
+    }
+}
+
+constexpr bool kTrackMfmaDefault = true;   // measured: 0.78 against 1.19 ms at B = 8,192 (exo), bit-identical gains (profiles/track.md)
+
+template <typename DS>
+static hipError_t launch_gains_t(const scvx_ctx* ctx, int B, int K, const DS* deriv, const TrackW& w, double* gain, double* p0,
+                                 hipStream_t st) {
+    // SCVX_TRACK_MFMA = 0 / 1 forces the lane-per-element / matrix-pipe form of the two 14-deep products (A/B: profiles/track.md)
+    bool mf = kTrackMfmaDefault;
+    if (const char* v = std::getenv("SCVX_TRACK_MFMA"); v && *v) mf = std::atoi(v) != 0;
+    const dim3 g((unsigned)B), blk(64);
+    if (ctx->dyn.fin) {
+        if (mf) hipLaunchKernelGGL((track_gains_kernel<DS, 5, true>), g, blk, 0, st, w, B, K, deriv, gain, p0);
+        else hipLaunchKernelGGL((track_gains_kernel<DS, 5, false>), g, blk, 0, st, w, B, K, deriv, gain, p0);
+    } else {
+        if (mf) hipLaunchKernelGGL((track_gains_kernel<DS, 3, true>), g, blk, 0, st, w, B, K, deriv, gain, p0);
+        else hipLaunchKernelGGL((track_gains_kernel<DS, 3, false>), g, blk, 0, st, w, B, K, deriv, gain, p0);
+    }
+    return hipGetLastError();
+}
+
+static TrackW pack_weights(const scvx_ctx* ctx, const double* q, const double* r, const double* qf) {
+    TrackW w{};
+    const int NU = ctx->dyn.fin ? 5 : 3;
+    for (int i = 0; i < 14; i++) { w.q[i] = q[i]; w.qf[i] = qf[i]; }
+    for (int j = 0; j < NU; j++) w.r[j] = r[j];
+    return w;
+}
+
+hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, const double* deriv, const double* q, const double* r, const double* qf,
+                              double* gain, double* p0, hipStream_t st) {
+    return launch_gains_t<double>(ctx, B, K, deriv, pack_weights(ctx, q, r, qf), gain, p0, st);
+}
+
+hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float* deriv, const double* q, const double* r,
+                                  const double* qf, double* gain, double* p0, hipStream_t st) {
+    return launch_gains_t<float>(ctx, B, K, deriv, pack_weights(ctx, q, r, qf), gain, p0, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the constants of the path functions, formed as launch_flight forms them (oracle/socp.py:99-101,188 / rocketland.jl:63-65)
+struct TrackK {
+    double rIf[3], vIf[3], qBIf[4], wBf[3];
+    double mdry, tggs, sqcm, omMax, Tmax, Tmin, inv_cosd, vmax, finmxf;
+    int dp;   // SCVX_MODEL_DPMAX
+};
+
+// NaN-propagating running maximum (fmax alone drops a NaN): once NaN, always NaN
+__device__ __forceinline__ double tmax(double a, double v) { return (v > a || v != v) ? v : a; }
+
+template <bool AERO, bool FIN, bool TRQ>
+__global__ __launch_bounds__(64) void track_fly_kernel(DynPK<double, TRQ> p, TrackK c, int B, int K, const double* __restrict__ x,
+                                                       const double* __restrict__ u, const double* __restrict__ sigma,
+                                                       const double* __restrict__ gain, const double* __restrict__ dx0, double dt,
+                                                       int nsub, int flags, double* __restrict__ report, double* __restrict__ xfly,
+                                                       double* __restrict__ ufly) {
+    typedef double R;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    constexpr int NU = FIN ? 5 : 3;
+    constexpr int n = 14 + NU;
+    const R* xb = x + (size_t)b * (K + 1) * 14;
+    const R* ub = u + (size_t)b * (K + 1) * NU;
+    const R* gb = gain + (size_t)b * K * NU * n;
+    R* xf = xfly ? xfly + (size_t)b * (K + 1) * 14 : nullptr;
+    R* uf = ufly ? ufly + (size_t)b * (K + 1) * NU : nullptr;
+    const R sig = sigma[b];
+    const R h = dt / R(nsub);
+    const R inv_n = R(1.0) / R(nsub);
+    const R ninf = -std::numeric_limits<double>::infinity();
+    const bool clamp = (flags & SCVX_TRACK_CLAMP) != 0;
+    R xs[14], ukv[NU], upv[NU];
+#pragma unroll
+    for (int i = 0; i < 14; i++) xs[i] = xb[i];
+    if (dx0) {
+#pragma unroll
+        for (int i = 0; i < 14; i++) xs[i] += dx0[(size_t)b * 14 + i];
+    }
+#pragma unroll
+    for (int j = 0; j < NU; j++) upv[j] = ub[j];
+    if (xf) {
+#pragma unroll
+        for (int i = 0; i < 14; i++) xf[i] = xs[i];
+    }
+    if (uf) {
+#pragma unroll
+        for (int j = 0; j < NU; j++) uf[j] = upv[j];
+    }
+    R gap = R(0.0), bad = R(0.0);   // bad: 0 while every sampled state (and every node difference) is finite, else NaN
+    R g_mass = ninf, g_glide = ninf, g_tilt = ninf, g_rate = ninf, g_tmax = ninf, g_tmin = ninf, g_gimbal = ninf, g_dp = ninf,
+      g_fin = ninf, qn = R(0.0);
+    for (int k = 0; k < K; k++) {
+        // ---- node k: the next node's control from the flown state and the applied control ----
+        {
+            R z[n];
+#pragma unroll
+            for (int i = 0; i < 14; i++) z[i] = xs[i] - xb[(size_t)k * 14 + i];
+#pragma unroll
+            for (int j = 0; j < NU; j++) {
+                z[14 + j] = upv[j] - ub[(size_t)k * NU + j];
+                ukv[j] = upv[j];
+            }
+            const R* g = gb + (size_t)k * NU * n;
+#pragma unroll
+            for (int j = 0; j < NU; j++) {
+                R a = ub[(size_t)(k + 1) * NU + j];
+#pragma unroll
+                for (int i = 0; i < n; i++) a = fma(g[j * n + i], z[i], a);
+                upv[j] = a;
+            }
+            if (clamp) {
+                const R un = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
+                R f = R(1.0);
+                if (un > c.Tmax) f = c.Tmax / un;
+                else if (un < c.Tmin && un > R(0.0)) f = c.Tmin / un;
+#pragma unroll
+                for (int j = 0; j < 3; j++) upv[j] *= f;
+                if (FIN) {
+                    const R fn = sqrt(upv[3] * upv[3] + upv[4] * upv[4]);
+                    const R ff = fn > c.finmxf ? c.finmxf / fn : R(1.0);
+                    upv[3] *= ff;
+                    upv[4] *= ff;
+                }
+            }
+            if (uf) {
+#pragma unroll
+                for (int j = 0; j < NU; j++) uf[(size_t)(k + 1) * NU + j] = upv[j];
+            }
+        }
+        for (int s = 0; s <= nsub; s++) {
+            // ---- sample: state xs, control of the hold at s / nsub (the stage-0 control of substep s) ----
+            const R lk0 = R(s) * inv_n;
+            R us[NU];
+#pragma unroll
+            for (int j = 0; j < NU; j++) us[j] = fma(ukv[j], R(1.0) - lk0, upv[j] * lk0);
+            const R un = sqrt(us[0] * us[0] + us[1] * us[1] + us[2] * us[2]);
+            g_tmax = tmax(g_tmax, un - c.Tmax);
+            g_tmin = tmax(g_tmin, c.Tmin - un);
+            g_gimbal = tmax(g_gimbal, un - us[0] * c.inv_cosd);
+            if (FIN) g_fin = tmax(g_fin, sqrt(us[3] * us[3] + us[4] * us[4]) - c.finmxf);
+            g_mass = tmax(g_mass, c.mdry - xs[0]);
+            g_glide = tmax(g_glide, c.tggs * sqrt(xs[2] * xs[2] + xs[3] * xs[3]) - xs[1]);
+            g_tilt = tmax(g_tilt, sqrt(xs[9] * xs[9] + xs[10] * xs[10]) - c.sqcm);
+            g_rate = tmax(g_rate, sqrt(xs[11] * xs[11] + xs[12] * xs[12] + xs[13] * xs[13]) - c.omMax);
+            if (c.dp) g_dp = tmax(g_dp, sqrt(xs[4] * xs[4] + xs[5] * xs[5] + xs[6] * xs[6]) - c.vmax);
+            qn = tmax(qn, fabs(sqrt(xs[7] * xs[7] + xs[8] * xs[8] + xs[9] * xs[9] + xs[10] * xs[10]) - R(1.0)));
+#pragma unroll
+            for (int i = 0; i < 14; i++) bad = fma(xs[i], R(0.0), bad);
+            if (s == nsub) break;
+            // ---- one RK4 substep, as propagate_kernel and flight_kernel take it ----
+            R xa[14], xt[14];
+#pragma unroll
+            for (int i = 0; i < 14; i++) {
+                xa[i] = xs[i];
+                xt[i] = xs[i];
+            }
+#pragma unroll
+            for (int stg = 0; stg < 4; stg++) {
+                const R lkp = (R(s) + (stg == 0 ? R(0.0) : (stg == 3 ? R(1.0) : R(0.5)))) * inv_n;
+                const R lkm = R(1.0) - lkp;
+                R uu[NU];
+#pragma unroll
+                for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
+                R g[14];
+                rhs_only<AERO, FIN, TRQ>(p, xt, uu, g);
+                const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
+                const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
+#pragma unroll
+                for (int i = 0; i < 14; i++) {
+                    const R dx = sig * g[i];
+                    xa[i] = fma(wacc, dx, xa[i]);
+                    if (stg < 3) xt[i] = fma(wnext, dx, xs[i]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 14; i++) xs[i] = xa[i];
+        }
+        // ---- node k + 1: the flown state against the planned one ----
+        const R* xn = xb + (size_t)(k + 1) * 14;
+#pragma unroll
+        for (int i = 0; i < 14; i++) {
+            const R d = xs[i] - xn[i];
+            gap = tmax(gap, fabs(d));
+            bad = fma(d, R(0.0), bad);
+        }
+        if (xf) {
+#pragma unroll
+            for (int i = 0; i < 14; i++) xf[(size_t)(k + 1) * 14 + i] = xs[i];
+        }
+    }
+    R mr = R(0.0), mv = R(0.0), mq = R(0.0), mw = R(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const R dr = xs[1 + i] - c.rIf[i], dv = xs[4 + i] - c.vIf[i], dw = xs[11 + i] - c.wBf[i];
+        mr = fma(dr, dr, mr); mv = fma(dv, dv, mv); mw = fma(dw, dw, mw);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const R dq = xs[7 + i] - c.qBIf[i]; mq = fma(dq, dq, mq); }
+    R* o = report + (size_t)b * SCVX_FLIGHT_NREP;
+    o[SCVX_FLIGHT_GAP] = gap + bad;
+    o[SCVX_FLIGHT_MISS_R] = sqrt(mr) + bad;
+    o[SCVX_FLIGHT_MISS_V] = sqrt(mv) + bad;
+    o[SCVX_FLIGHT_MISS_Q] = sqrt(mq) + bad;
+    o[SCVX_FLIGHT_MISS_W] = sqrt(mw) + bad;
+    o[SCVX_FLIGHT_MASS_END] = xs[0];
+    o[SCVX_FLIGHT_G_MASS] = g_mass + bad;
+    o[SCVX_FLIGHT_G_GLIDE] = g_glide + bad;
+    o[SCVX_FLIGHT_G_TILT] = g_tilt + bad;
+    o[SCVX_FLIGHT_G_RATE] = g_rate + bad;
+    o[SCVX_FLIGHT_G_TMAX] = g_tmax;
+    o[SCVX_FLIGHT_G_TMIN] = g_tmin;
+    o[SCVX_FLIGHT_G_GIMBAL] = g_gimbal;
+    o[SCVX_FLIGHT_G_DP] = c.dp ? g_dp + bad : ninf;
+    o[SCVX_FLIGHT_G_FIN] = g_fin;
+    o[SCVX_FLIGHT_QNORM] = qn + bad;
+}
+
+hipError_t launch_track_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
+                            const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly, hipStream_t st) {
+    const scvx_problem& P = ctx->prob;
+    const double d2r = M_PI / 180.0;
+    TrackK c{};
+    for (int i = 0; i < 3; i++) { c.rIf[i] = P.rIf[i]; c.vIf[i] = P.vIf[i]; c.wBf[i] = P.wBf[i]; }
+    for (int i = 0; i < 4; i++) c.qBIf[i] = P.qBIf[i];
+    c.mdry = P.mdry;
+    c.tggs = std::tan(P.gammaGs * d2r);
+    c.sqcm = std::sqrt((1.0 - std::cos(P.thetaMax * d2r)) / 2.0);
+    c.omMax = P.omMax;
+    c.Tmax = P.Tmax;
+    c.Tmin = P.Tmin;
+    c.inv_cosd = 1.0 / std::cos(P.deltaMax * d2r);
+    c.dp = (P.model_flags & SCVX_MODEL_DPMAX) ? 1 : 0;
+    c.vmax = c.dp ? std::sqrt(2.0 * P.dpMax / P.rho) : 0.0;
+    c.finmxf = P.finmxf;
+    const double dt = 1.0 / (K + 1);
+    const dim3 g((unsigned)((B + 63) / 64)), blk(64);
+    const DynP<double> dp(ctx->dyn);
+#define SCVX_TRACK_FLY(A, F, T, par) \
+    hipLaunchKernelGGL((track_fly_kernel<A, F, T>), g, blk, 0, st, par, c, B, K, x, u, sigma, gain, dx0, dt, nsub, flags, report, xfly, ufly)
+    if (ctx->dyn.trq) {
+        const DynPT<double> dpt(ctx->dyn);
+        if (ctx->dyn.fin) SCVX_TRACK_FLY(true, true, true, dpt);
+        else SCVX_TRACK_FLY(true, false, true, dpt);
+    } else if (ctx->dyn.fin) {
+        if (ctx->dyn.aero) SCVX_TRACK_FLY(true, true, false, dp);
+        else SCVX_TRACK_FLY(false, true, false, dp);
+    } else if (ctx->dyn.aero)
+        SCVX_TRACK_FLY(true, false, false, dp);
+    else
+        SCVX_TRACK_FLY(false, false, false, dp);
+#undef SCVX_TRACK_FLY
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const double* qf) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (!q || !r || !qf) return fail(ctx, SCVX_ERR_ARG, "track: null weight array (q[14], r[NU], qf[14])");
+    const int NU = ctx->dyn.fin ? 5 : 3;
+    for (int i = 0; i < 14; i++)
+        if (!(q[i] >= 0.0) || !std::isfinite(q[i]) || !(qf[i] >= 0.0) || !std::isfinite(qf[i]))
+            return fail(ctx, SCVX_ERR_ARG, "track: the weights q and qf must be finite and >= 0");
+    for (int j = 0; j < NU; j++)
+        if (!(r[j] > 0.0) || !std::isfinite(r[j])) return fail(ctx, SCVX_ERR_ARG, "track: the weights r must be finite and > 0");
+    return SCVX_OK;
+}
+
+int check_track_gains(scvx_ctx* ctx, int B, int K, const void* deriv, const double* q, const double* r, const double* qf,
+                      const void* gain) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (B < 1) return fail(ctx, SCVX_ERR_ARG, "track gains: B >= 1 required");
+    if (K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "track gains: K must equal the problem's K");
+    if (!deriv || !gain) return fail(ctx, SCVX_ERR_ARG, "track gains: null buffer");
+    return check_track_weights(ctx, q, r, qf);
+}
+
+int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
+                    const void* report) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (B < 1) return fail(ctx, SCVX_ERR_ARG, "track fly: B >= 1 required");
+    if (K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "track fly: K must equal the problem's K");
+    if (nsub < 1 || nsub > 1000) return fail(ctx, SCVX_ERR_ARG, "track fly: nsub must be in [1,1000]");
+    if (flags & ~SCVX_TRACK_CLAMP) return fail(ctx, SCVX_ERR_ARG, "track fly: unknown flags (SCVX_TRACK_CLAMP)");
+    if (!x || !u || !sigma || !gain || !report) return fail(ctx, SCVX_ERR_ARG, "track fly: null buffer");
+    if (ctx->prob.aero_kind == 1 && !ctx->dyn.aero)
+        return fail(ctx, SCVX_ERR_STATE, "AtmosphericData problem: call scvx_set_aero_table first");
+    return SCVX_OK;
+}
+
+namespace {
+struct Dev {
+    double* p = nullptr;
+    ~Dev() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+}  // namespace scvx
+
+extern "C" {
+
+int scvx_track_gains_f64(scvx_ctx* ctx, int B, int K, const double* deriv_dev, const double* q14, const double* rNU, const double* qf14,
+                         double* gain_dev, double* p0_dev) {
+    int rc = scvx::check_track_gains(ctx, B, K, deriv_dev, q14, rNU, qf14, gain_dev);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_gains(ctx, B, K, deriv_dev, q14, rNU, qf14, gain_dev, p0_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_track_gains_f64_host(scvx_ctx* ctx, int B, int K, const double* deriv, const double* q14, const double* rNU,
+                              const double* qf14, double* gain, double* p0) {
+    int rc = scvx::check_track_gains(ctx, B, K, deriv, q14, rNU, qf14, gain);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU;
+    const size_t nd = (size_t)B * K * 14 * (14 + 2 * NU + 1), ng = (size_t)B * K * NU * n, np = (size_t)B * n * n;
+    scvx::Dev dd, dg, dp;
+    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    if (p0) SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_track_gains(ctx, B, K, dd.p, q14, rNU, qf14, dg.p, dp.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(gain, dg.p, ng * 8, hipMemcpyDeviceToHost, st));
+    if (p0) SCVX_HIP(ctx, hipMemcpyAsync(p0, dp.p, np * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+int scvx_track_fly_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                       const double* gain_dev, const double* dx0_dev, int nsub, int flags, double* report_dev, double* xfly_dev,
+                       double* ufly_dev) {
+    int rc = scvx::check_track_fly(ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, nsub, flags, report_dev);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_fly(ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nsub, flags, report_dev, xfly_dev,
+                                         ufly_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_track_fly_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
+                            const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly) {
+    int rc = scvx::check_track_fly(ctx, B, K, x, u, sigma, gain, nsub, flags, report);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU;
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP,
+                 ng = (size_t)B * K * NU * n;
+    scvx::Dev dx, du, ds, dg, d0, dr, df, dc;
+    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    if (dx0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, (size_t)B * 14 * 8));
+    if (xfly) SCVX_HIP(ctx, hipMalloc((void**)&df.p, nx * 8));
+    if (ufly) SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nu * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
+    if (dx0) SCVX_HIP(ctx, hipMemcpyAsync(d0.p, dx0, (size_t)B * 14 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_track_fly(ctx, B, K, dx.p, du.p, ds.p, dg.p, d0.p, nsub, flags, dr.p, df.p, dc.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    if (xfly) SCVX_HIP(ctx, hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st));
+    if (ufly) SCVX_HIP(ctx, hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+}  // extern "C"

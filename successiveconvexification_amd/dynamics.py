@@ -120,10 +120,11 @@ class FlightReport:
 
     G_COLUMNS = tuple(n for n in _lib.FLIGHT_COLUMNS if n.startswith("G_"))
 
-    def __init__(self, raw, xfly=None, mode="shoot"):
+    def __init__(self, raw, xfly=None, mode="shoot", ufly=None):
         self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.FLIGHT_NREP)
         self.xfly = xfly
         self.mode = mode
+        self.ufly = ufly   # mode "track" with dense=True: the applied node controls [B][K+1][nu]
         for name, i in _lib.FLIGHT_INDEX.items():
             setattr(self, name, self.raw[:, i])
 
@@ -168,6 +169,70 @@ def flight_check_batch(cache: IntegratorCache, x, u, sigma, nsub=None, mode="sho
         cache.handle, B, K1 - 1, _p(x), _p(u), _p(sigma), int(cache.npts if nsub is None else nsub), int(_flight_mode(mode)),
         _p(rep), _p(xfly) if dense else None), "scvx_flight_check_f64_host")
     return FlightReport(rep, xfly, mode)
+
+
+TRACK_DEFAULT_WEIGHTS = (1.0, 1.0, 100.0)   # q, r, qf on every component: a starting point, not tuning advice
+
+
+def _track_weights(nu, q, r, qf):
+    """scalars broadcast to the weight vectors q[14], r[nu], qf[14]; None = TRACK_DEFAULT_WEIGHTS"""
+    out = []
+    for v, d, m, name in ((q, TRACK_DEFAULT_WEIGHTS[0], 14, "q"), (r, TRACK_DEFAULT_WEIGHTS[1], nu, "r"),
+                          (qf, TRACK_DEFAULT_WEIGHTS[2], 14, "qf")):
+        a = np.asarray(d if v is None else v, np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != m):
+            raise ValueError("%s must be a scalar or have %d components" % (name, m))
+        out.append(np.ascontiguousarray(np.broadcast_to(a, (m,)), np.float64))
+    return out
+
+
+def track_gains_batch(cache: IntegratorCache, deriv, q=None, r=None, qf=None, cost=False):
+    """Time-varying LQR gains about plans from their derivative tiles deriv [B*K][14+2nu+1][14] (or [B][K][...]; what
+    linearize_batch returns), on the device (scvx_track_gains_f64_host; the recursion is in include/scvx.h).  q, r, qf: diagonal
+    weights in the problem's normalised units, scalars broadcast; defaults 1, 1, 100 -- a starting point, not tuning advice (the
+    quaternion and mass directions are nearly uncontrollable).  Returns gain [B][K][nu][14+nu]: du_{k+1} = gain[b, k] @ [dx_k; du_k];
+    with cost=True also p0 [B][14+nu][14+nu]: z0' p0 z0 is the predicted cost of an initial deviation z0."""
+    nu, K = cache.nu, cache.problem.K
+    deriv = np.ascontiguousarray(deriv, np.float64)
+    if deriv.size == 0 or deriv.size % (K * 14 * (15 + 2 * nu)) or deriv.shape[-2:] != (15 + 2 * nu, 14):
+        raise ValueError("shape mismatch: deriv [B*K][%d][14] with K = %d" % (15 + 2 * nu, K))
+    B = deriv.size // (K * 14 * (15 + 2 * nu))
+    qv, rv, qfv = _track_weights(nu, q, r, qf)
+    gain = np.empty((B, K, nu, 14 + nu))
+    p0 = np.empty((B, 14 + nu, 14 + nu)) if cost else None
+    _lib.check(cache.handle, cache._L.scvx_track_gains_f64_host(cache.handle, B, K, _p(deriv), _p(qv), _p(rv), _p(qfv), _p(gain),
+                                                                _p(p0) if cost else None), "scvx_track_gains_f64_host")
+    return (gain, p0) if cost else gain
+
+
+def track_fly_batch(cache: IntegratorCache, x, u, sigma, gain, dx0=None, nsub=None, clamp=False, dense=False) -> FlightReport:
+    """Fly the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] closed loop under the gains gain [B][K][nu][14+nu] from
+    x[:, 0] + dx0 (dx0 [B][14] or None = 0) on the device (scvx_track_fly_f64_host).  The report has the flight check's 16 columns
+    (G_* on the flown state and the applied control; GAP against the planned nodes); mode "track".  clamp: rescale the commanded
+    thrust norm into [Tmin, Tmax] (and the fin norm below finmxf); off by default: a plan that rides Tmin saturates on one side at
+    most nodes and the law loses most of its authority, and without it G_TMIN / G_TMAX show what the law asked for.
+    dense: also xfly [B][K+1][14] and ufly [B][K+1][nu]."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], cache.nu) or sigma.shape != (x.shape[0],):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % cache.nu)
+    B, K1, _ = x.shape
+    if gain.shape != (B, K1 - 1, cache.nu, 14 + cache.nu):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (cache.nu, 14 + cache.nu))
+    if dx0 is not None:
+        dx0 = np.ascontiguousarray(dx0, np.float64)
+        if dx0.shape != (B, 14):
+            raise ValueError("shape mismatch: dx0 [B][14]")
+    rep = np.empty((B, _lib.FLIGHT_NREP))
+    xfly = np.empty((B, K1, 14)) if dense else None
+    ufly = np.empty((B, K1, cache.nu)) if dense else None
+    _lib.check(cache.handle, cache._L.scvx_track_fly_f64_host(
+        cache.handle, B, K1 - 1, _p(x), _p(u), _p(sigma), _p(gain), _p(dx0) if dx0 is not None else None,
+        int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, _p(rep), _p(xfly) if dense else None,
+        _p(ufly) if dense else None), "scvx_track_fly_f64_host")
+    return FlightReport(rep, xfly, "track", ufly)
 
 
 def _pf(a):

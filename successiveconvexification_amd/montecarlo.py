@@ -26,6 +26,32 @@ def disperse_ics(p, lo, hi, seed, frac=0.1):
     return ic
 
 
+def disperse_handover(x0, lo, hi, seed, frac_r=0.0, frac_v=0.0, angle=0.0, rate=0.0):
+    """State offsets dx0 [hi - lo][14] at the handover to a tracking law (ScvxBatch.track, dynamics.track_fly_batch): where the
+    vehicle really is when the plan starts at x0 ([hi - lo][14], or one [14] for all).  r and v relative per component
+    (x0 * frac * U(-1,1)), the attitude a rotation by angle * U(-1,1) radians about a uniformly random axis, expressed as
+    q (x) dq - q so that x0 + dx0 keeps a unit quaternion, rate * U(-1,1) added to each component of w, the mass untouched.
+    Trajectory b draws from Philox stream b of `seed` (its own counter word, so the draws are not those of disperse_ics): a shard
+    [lo, hi) gets exactly the rows the whole batch would."""
+    x0 = np.broadcast_to(np.asarray(x0, np.float64), (hi - lo, 14))
+    dx0 = np.zeros((hi - lo, 14))
+    for b in range(lo, hi):
+        rng = np.random.Generator(np.random.Philox(key=seed, counter=[1, 0, 0, b]))
+        un = rng.uniform(-1.0, 1.0, size=10)
+        ax = rng.standard_normal(3)
+        ax /= np.linalg.norm(ax)
+        i = b - lo
+        dx0[i, 1:4] = x0[i, 1:4] * (frac_r * un[0:3])
+        dx0[i, 4:7] = x0[i, 4:7] * (frac_v * un[3:6])
+        th = angle * un[6]
+        w, v = np.cos(0.5 * th), np.sin(0.5 * th) * ax
+        qw, qv = x0[i, 7], x0[i, 8:11]
+        dx0[i, 7] = (qw * w - qv @ v) - qw                      # Hamilton product q (x) dq, scalar first
+        dx0[i, 8:11] = (qw * v + w * qv + np.cross(qv, v)) - qv
+        dx0[i, 11:14] = rate * un[7:10]
+    return dx0
+
+
 def shard_range(total: int, rank: int, world: int):
     """Contiguous shard [lo, hi) of `total` trajectories for `rank`; sizes differ by at most one."""
     base, rem = divmod(int(total), int(world))

@@ -6,6 +6,7 @@
     solve_step(iteration, cache) -> (ProblemIteration, |nu|, dJ)  rocketland.jl:226-321
     solve_problem(iprob, cache) -> (ProblemIteration, cnu, cdel)  rocketland.jl:432-443
     fly(iteration, cache) -> FlightReport                         (new: open-loop flight + path audit of a plan)
+    track(iteration, cache, dx0) -> FlightReport                  (new: closed-loop flight under LQR gains about the plan)
 The recipe of rocketland.jl:26-32 reads the same here:
     cache = IntegratorCache(prob, ProbInfo.from_problem(prob), make_dynamics_module(...))
     pi = create_initial(prob, cache); pi, cnu, cdel = solve_step(pi, cache)
@@ -61,6 +62,21 @@ def fly(iteration: ProblemIteration, cache: IntegratorCache = None, nsub=None, m
     x = np.stack([pt.state for pt in iteration.about])[None]
     u = np.stack([pt.control for pt in iteration.about])[None]
     return flight_check_batch(cache, x, u, np.array([float(iteration.sigma)]), nsub=nsub, mode=mode, dense=dense)
+
+
+def track(iteration: ProblemIteration, cache: IntegratorCache = None, dx0=None, q=None, r=None, qf=None, nsub=None, clamp=False,
+          dense=False):
+    """Closed-loop flight of an iterate's plan from `about[0].state + dx0` (dx0 [14] or None) under the time-varying LQR gains about
+    it (dynamics.track_gains_batch on the plan's own linearisation, dynamics.track_fly_batch).  A dynamics.FlightReport of one row."""
+    from .dynamics import linearize_batch, track_fly_batch, track_gains_batch
+    cache = cache if cache is not None else iteration.cache
+    x = np.stack([pt.state for pt in iteration.about])[None]
+    u = np.stack([pt.control for pt in iteration.about])[None]
+    sigma = np.array([float(iteration.sigma)])
+    _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
+    gain = track_gains_batch(cache, deriv, q, r, qf)
+    d0 = None if dx0 is None else np.asarray(dx0, np.float64).reshape(1, 14)
+    return track_fly_batch(cache, x, u, sigma, gain, d0, nsub=nsub, clamp=clamp, dense=dense)
 
 
 def run_iters(iprob: DescentProblem, niters: int, cache: IntegratorCache = None):
