@@ -254,6 +254,16 @@ struct Consts {
 enum { LINV_SZ = 105 };
 SCVX_HD int linv_row(int i) { return i < 7 ? 15 * i : 15 * (13 - i) + (14 - i); }
 
+// a product that is rounded on its own (never contracted into a following add): where a fused pass keeps the bits of the separate
+// passes that stored the product and read it back.  (The host parity build compiles without contraction.)
+SCVX_HD double mul_rn(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+
 // compact per-node inverse of the x-block of Hb: [hm | Hr 3x3 | Hv 3x3 | hq | Hq34 2x2 | Hw 3x3] = 33 doubles
 // (Hv is a multiple of the identity unless the dynamic-pressure cone is enforced).  The u-block of a node follows:
 // 3x3 thrust block (9 doubles), and with the fin extension the 2x2 fin block (4 more): hu_size(NU).
@@ -1561,24 +1571,135 @@ struct Solver {
         SCVX_T1(0);
     }
 
-    // forward half of S_solve: t = L^-1 r (tchain is scratch; r and t distinct buffers)
-    SCVX_HD_NI void S_fwd(cgptr r, gptr t) {
+    // ---- FRONT SWEEP of a solve: tchain = L^-1 (E Hb^-1 g + sa add), E without the s column, then the forward recurrence tchain -> t ----
+    // The three node-local maps in front of a solve's forward recurrence -- Hb_inv(g -> tmpl), E_apply(tmpl -> tmpy, add, sa) and the
+    // row pass L^-1 (tmpy -> tchain) -- as ONE pass.  Row r = (k, i) of each map needs rows of nodes k and k + 1 only, so the
+    // trajectory is walked in chunks of SW_CH segments (one row per lane on the device: 4 segments = 56 rows for a wavefront) and the
+    // chunk's intermediate rows go from map to map through LDS: Hs holds Hb^-1 g of the chunk's nodes (node k in slot k % SW_NS -- the
+    // last node of a chunk is the first one of the next), Rs its rows of E Hb^-1 g + sa add.  None of the global loads of a chunk
+    // depends on an intermediate, so they are issued ahead of the arithmetic (see the pipeline below) and the hand-overs are LDS
+    // fences: the loads stay in flight across them, where each of the three passes ended in a barrier that drained them, and tmpl /
+    // tmpy are neither written nor read.  Every row's sums run in the order of the separate passes: same bits.
+    // The buffers alias the tile space of the factorisation (build_kkt / the pipelines), which is dead between factorisations: what a
+    // solve needs from it (gram, gn_pred) was copied into members, and the chain recurrences load their operands from global memory.
+    // The recurrence itself runs at the end of this routine (not in kkt_solve, which is inlined into attempt_solve at every call site:
+    // there its operand registers lengthen attempt_solve's frame, and the kernel's private segment with it).
+    static constexpr int SW_CH = Ex::kLanes >= 14 ? Ex::kLanes / 14 : 4;   // segments per chunk
+    static constexpr int SW_NS = SW_CH + 1;                                // node slots of Hs
+    static constexpr bool SW_ONE = Ex::kLanes >= 14 * SW_CH;               // a lane owns one row of a chunk: its loads live in registers
+    SCVX_HD double* sweep_lds() {
+        if constexpr (Ex::kPipelineFactor) return ex.pipe_scratch(); else return ex.scratch() + 32;
+    }
+    struct SwA { D6 hx, hu; };                       // coefficients and inputs of one x row and one u row of Hb^-1
+    struct SwB { double d[14 + 2 * NU], ad, gv; };   // row i of [A_k | B-_k | B+_k], add[r], g_nu[r]
+    struct SwC { double l[14]; };                    // row i of L_k^-1 (zero beyond the diagonal)
+    SCVX_HD D6 sw_hx_row(cgptr g, int k, int j) const {   // row j of node k: as Hb_inv
+        const int hb = j == 0 ? HX_M : j < 4 ? HX_R + 3 * (j - 1) : j < 7 ? HX_V + 3 * (j - 4) : j < 9 ? HX_Q
+                       : j < 11 ? HX_Q34 + 2 * (j - 9) : HX_W + 3 * (j - 11);
+        const int gb = j == 0 ? 0 : j < 4 ? 1 : j < 7 ? 4 : j < 9 ? j : j < 11 ? 9 : 11;
+        const int n = (j == 0 || j == 7 || j == 8) ? 1 : (j == 9 || j == 10) ? 2 : 3;
+        cgptr h = hx + (size_t)k * HX_SZ + hb; cgptr x = g + 14 * k + gb;
+        const int i1 = n > 1 ? 1 : 0, i2 = n > 2 ? 2 : 0;
+        return D6{h[0], n > 1 ? h[i1] : 0.0, n > 2 ? h[i2] : 0.0, x[0], x[i1], x[i2]};
+    }
+    SCVX_HD D6 sw_hu_row(cgptr g, int k, int c) const {
+        cgptr gu = g + L.nx;
+        if (NU == 3 || c < 3) { cgptr h = hu + HU_SZ * k + 3 * c; cgptr x = gu + NU * k; return D6{h[0], h[1], h[2], x[0], x[1], x[2]}; }
+        cgptr h = hu + HU_SZ * k + 9 + 2 * (c - 3); cgptr x = gu + NU * k + 3;
+        return D6{h[0], h[1], 0.0, x[0], x[1], 0.0};
+    }
+    SCVX_HD void sw_load_b(SwB& w, cgptr g, cgptr add, int k, int i) const {
+        dcptr Dk = D + (size_t)k * DSZ + i;
+        SCVX_UNROLL
+        for (int j = 0; j < 14 + 2 * NU; j++) w.d[j] = Dk[14 * j];
+        w.ad = add[14 * k + i];
+        w.gv = g[L.nx + L.nu_ + 14 * k + i];
+    }
+    SCVX_HD void sw_load_c(SwC& w, int k, int i) const {
+        cfptr Li = Linv + (size_t)k * LINV_SZ + linv_row(i);
+        SCVX_UNROLL
+        for (int j = 0; j < 14; j++) w.l[j] = j <= i ? (double)Li[j <= i ? j : i] : 0.0;
+    }
+    static SCVX_HD double sw_hb(const D6& w) { return w.a * w.d + w.b * w.e + w.c * w.f; }
+    // row (k, i) of E Hb^-1 g + sa add from the node slots
+    SCVX_HD double sw_erow(const SwB& w, const double* Hs, int k, int i, double hn, double sa) const {
+        const double* hk = Hs + NXU * (k % SW_NS); const double* hk1 = Hs + NXU * ((k + 1) % SW_NS);
+        double a = 0;
+        SCVX_UNROLL
+        for (int j = 0; j < 14 + NU; j++) a += w.d[j] * hk[j];
+        SCVX_UNROLL
+        for (int j = 0; j < NU; j++) a += w.d[14 + NU + j] * hk1[14 + j];
+        a += mul_rn(hn, w.gv) - hk1[i];
+        a += sa * w.ad;
+        return a;
+    }
+    static SCVX_HD double sw_lrow(const SwC& w, const double* rk_) {
+        double a = 0;
+        SCVX_UNROLL
+        for (int j = 0; j < 14; j++) a += w.l[j] * rk_[j];
+        return a;
+    }
+    SCVX_HD_NI void front_sweep(cgptr g, cgptr add, double sa, gptr t) {
         SCVX_THIS_LDS();
         SCVX_T0();
-        const int K = L.K;
-        const cfptr Linv = this->Linv;
-        const gptr tchain = this->tchain;
-        for (int e = ex.lane(); e < 14 * K; e += ex.nlanes()) {
-            const int k = e / 14, i = e - 14 * k;
-            cfptr Li = Linv + (size_t)k * LINV_SZ + linv_row(i);
-            cgptr rk_ = r + 14 * k;
-            double a = 0;
-            SCVX_UNROLL
-            for (int j = 0; j < 14; j++) a += (j <= i ? Li[j <= i ? j : i] : 0.0) * rk_[j];   // fixed trip count: the loads batch
-            tchain[e] = a;
+        const int K = L.K, nl = ex.nlanes(), ln = ex.lane();
+        const double hn = hnui;
+        const gptr tchain_ = tchain;
+        double* Hs = sweep_lds();
+        double* Rs = Hs + SW_NS * NXU;
+        for (int e = ln; e < NXU; e += nl) Hs[e] = sw_hb(e < 14 ? sw_hx_row(g, 0, e) : sw_hu_row(g, 0, e - 14));   // node 0
+        if constexpr (SW_ONE) {
+            // Software pipeline: the Hb^-1 and E rows of a chunk are requested a whole chunk ahead, its L^-1 row when the chunk starts
+            // (all three a chunk ahead would be 2 x 48 doubles per lane: more registers than a routine below attempt_solve may take
+            // without saving callee-saved ones to private memory).  Clamped indices: every lane loads from valid addresses,
+            // unpredicated (a predicated load is a branch around it).
+            auto load_ab = [&](SwA& a, SwB& b, int k0) {
+                const int ns = K - k0 < SW_CH ? K - k0 : SW_CH;
+                const int e = ln < 14 * ns ? ln : 0, eu = ln < NU * ns ? ln : 0;
+                a.hx = sw_hx_row(g, k0 + 1 + e / 14, e % 14);
+                a.hu = sw_hu_row(g, k0 + 1 + eu / NU, eu % NU);
+                sw_load_b(b, g, add, k0 + e / 14, e % 14);
+            };
+            SwA a; SwB b;
+            load_ab(a, b, 0);
+            for (int k0 = 0; k0 < K; k0 += SW_CH) {
+                const int ns = K - k0 < SW_CH ? K - k0 : SW_CH;
+                const bool on = ln < 14 * ns;
+                const int kk = on ? ln / 14 : 0, i = on ? ln - 14 * kk : 0, k = k0 + kk;
+                SwC c;
+                sw_load_c(c, k, i);
+                if (on) Hs[NXU * ((k + 1) % SW_NS) + i] = sw_hb(a.hx);
+                if (ln < NU * ns) Hs[NXU * ((k0 + 1 + ln / NU) % SW_NS) + 14 + ln % NU] = sw_hb(a.hu);
+                SwA an = a; SwB bn = b;
+                if (k0 + SW_CH < K) load_ab(an, bn, k0 + SW_CH);
+                ex.sync_lds();
+                if (on) Rs[ln] = sw_erow(b, Hs, k, i, hn, sa);
+                ex.sync_lds();
+                if (on) tchain_[14 * k + i] = sw_lrow(c, Rs + 14 * kk);
+                a = an; b = bn;
+            }
+        } else {
+            for (int k0 = 0; k0 < K; k0 += SW_CH) {
+                const int ns = K - k0 < SW_CH ? K - k0 : SW_CH;
+                for (int e = ln; e < 14 * ns; e += nl) Hs[NXU * ((k0 + 1 + e / 14) % SW_NS) + e % 14] = sw_hb(sw_hx_row(g, k0 + 1 + e / 14, e % 14));
+                for (int e = ln; e < NU * ns; e += nl) Hs[NXU * ((k0 + 1 + e / NU) % SW_NS) + 14 + e % NU] = sw_hb(sw_hu_row(g, k0 + 1 + e / NU, e % NU));
+                ex.sync_lds();
+                for (int e = ln; e < 14 * ns; e += nl) {
+                    SwB w;
+                    sw_load_b(w, g, add, k0 + e / 14, e % 14);
+                    Rs[e] = sw_erow(w, Hs, k0 + e / 14, e % 14, hn, sa);
+                }
+                ex.sync_lds();
+                for (int e = ln; e < 14 * ns; e += nl) {
+                    SwC w;
+                    sw_load_c(w, k0 + e / 14, e % 14);
+                    tchain_[14 * (k0 + e / 14) + e % 14] = sw_lrow(w, Rs + 14 * (e / 14));
+                }
+                ex.sync_lds();
+            }
         }
         ex.sync();
-        SCVX_TE(t0_, 16);
+        SCVX_TE(t0_, 14);
         SCVX_TS(tc1_);
         {
             const cgptr tz[1] = {tchain};
@@ -3271,9 +3392,7 @@ struct Solver {
             double a0, a1, a2, gn;
             if (have_band) { a0 = gram[3]; a1 = gram[7]; a2 = gram[11]; gn = gn_pred; }
             else {
-                Hb_inv(g, tmpl);
-                (void)E_apply(tmpl, tmpy, false, ryv, -rsign);
-                S_fwd(tmpy, dyv);
+                front_sweep(g, ryv, -rsign, dyv);   // dyv = t_g = L^-1 (E Hb^-1 g - rsign ryv), forward recurrence included
                 double q0 = 0, q1 = 0, q2 = 0, q3 = 0;
                 cgptr b0 = ys; cgptr b1 = ytr; cgptr b2 = ynu; cgptr wn = Wv + L.o_nu + 1; cgptr gnu = g + L.nx + L.nu_;
                 stream(0, L.ny, [&](int i) { return D6{dyv[i], b0[i], b1[i], b2[i], wn[i], gnu[i]}; },
