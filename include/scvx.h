@@ -8,6 +8,7 @@
  *   Dynamics.predict_state        dynamics.jl:315-317  ->  scvx_propagate_f64[_host]
  *   (no counterpart: open-loop flight + path audit)    ->  scvx_flight_check_f64[_host], scvx_batch_flight_check
  *   (no counterpart: LQR gains + closed-loop flight)   ->  scvx_track_gains_f64[_host], scvx_track_fly_f64[_host], scvx_batch_track_*
+ *   (no counterpart: closed-loop covariance analysis)  ->  scvx_cov_propagate_f64[_host], scvx_batch_cov
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -284,6 +285,56 @@ int scvx_track_fly_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const 
                             const double *gain, const double *dx0, int nsub, int flags, double *report, double *xfly,
                             double *ufly);
 
+/* ---- covariance analysis: the closed-loop dispersion of a tracked plan, to first order --------------------------------
+ * scvx_track_fly_f64 flies ONE displaced start per trajectory.  This call answers the statistical question -- given a handover
+ * dispersion, how large is the landing dispersion and how much thrust headroom does the tracking law need -- for every plan of a
+ * batch in one forward pass over the derivative tiles and the gains, without sampling.  Notation as above: NU = scvx_control_dim,
+ * n = 14 + NU, Sigma_k (n x n) the covariance of z_k = [x_k - xbar_k; u_k - ubar_k] under the law
+ * u_{k+1} = ubar_{k+1} + L_k z_k, u_0 = ubar_0 (exactly scvx_track_fly_f64 without SCVX_TRACK_CLAMP):
+ *     Sigma_0     = blockdiag(S0, 0)                        S0 [14][14] symmetric positive semi-definite, per trajectory
+ *     M_k         = F_k + G_k L_k                           (rows 14.. of M_k are L_k itself)
+ *     Sigma_{k+1} = M_k Sigma_k M_k' + blockdiag(diag(w), 0)   w [14] >= 0: process-noise variance added per segment (NULL = 0)
+ * symmetrised every step: Sigma_{k+1} = (T + T') / 2 with T the product as computed, each element from both of its triangles.  Only
+ * the symmetric part (S0 + S0') / 2 of S0 is used; that it is positive semi-definite is the caller's responsibility.
+ * Limits: the analysis is FIRST ORDER (linear about the plan: the derivative tiles and the gains); the covariances live at the
+ * nodes; the clamp is not modelled (N_TMIN / N_TMAX say how far the law is from needing it); w is a crude per-segment lump, not a
+ * continuous-time noise model; the 14 state coordinates are taken as they are -- the quaternion's norm direction is a coordinate
+ * like any other, as in a start x[0] + dx0.  Gimbal, dynamic-pressure and fin margins are not reported.
+ *
+ * The dispersion report, SCVX_COV_NREP doubles per trajectory (state indices: 0 mass, 1 altitude -- the glide-slope row --, 2 and 3
+ * the horizontal plane): */
+#define SCVX_COV_NREP 16
+#define SCVX_COV_SIG_M 0      /* sqrt(Sigma_K[0][0]): 1 sigma of the final mass                                            */
+#define SCVX_COV_SIG_R 1      /* sqrt(trace of the r block of Sigma_K): the 1 sigma counterpart of SCVX_FLIGHT_MISS_R      */
+#define SCVX_COV_SIG_V 2      /* the same for v                                                                            */
+#define SCVX_COV_SIG_Q 3      /* the same for q                                                                            */
+#define SCVX_COV_SIG_W 4      /* the same for w                                                                            */
+#define SCVX_COV_ELL_A 5      /* 1 sigma landing ellipse in the horizontal plane: sqrt of the larger eigenvalue of the 2 x 2 */
+#define SCVX_COV_ELL_B 6      /* block of Sigma_K at state indices 2, 3 (closed form); sqrt of the smaller one;              */
+#define SCVX_COV_ELL_ANG 7    /* angle of the major axis from the index-2 axis, in (-pi/2, pi/2]                            */
+#define SCVX_COV_SIG_PEAK 8   /* max over nodes 0..K of sqrt(trace Sigma_k[0:14][0:14])                                     */
+#define SCVX_COV_S_THRUST 9   /* max over nodes 1..K of s_T = sqrt(e' Sigma_k[uu] e), e = ubar_k[1:3] / |ubar_k[1:3]|: one  */
+                              /* standard deviation of the commanded thrust norm, to first order (a node with |ubar| = 0 is skipped) */
+#define SCVX_COV_N_MASS 10    /* margins in standard deviations to the path functions of SCVX_FLIGHT_G_MASS .. G_TMIN (same  */
+#define SCVX_COV_N_GLIDE 11   /* constants, same g <= 0 convention): with c the gradient of g in z at the planned node and   */
+#define SCVX_COV_N_TILT 12    /* s = sqrt(c' Sigma_k c),  N = min over nodes k = 1..K of -g(xbar_k, ubar_k) / s.  A node where */
+#define SCVX_COV_N_RATE 13    /* the gradient is undefined (a norm that is exactly 0, e.g. the glide slope at the landing     */
+#define SCVX_COV_N_TMAX 14    /* point) or where s == 0 is skipped; +inf when every node is skipped; negative when the plan   */
+#define SCVX_COV_N_TMIN 15    /* itself violates.                                                                            */
+/* x [B][K+1][14], u [B][K+1][NU] the plan; deriv [B][K][14+2NU+1][14] as scvx_linearize_f64 writes it; gain [B][K][NU][14+NU] as
+ * scvx_track_gains_f64 writes it; S0 [B][14][14]; w14 a HOST array or NULL in both forms; report [B][SCVX_COV_NREP].  Optional dense
+ * outputs (NULL = not wanted): sig [B][K+1][14+NU] = sqrt(diag Sigma_k), the 1 sigma corridor about the plan; covK [B][n][n] =
+ * Sigma_K; cov [B][K+1][n][n] = every Sigma_k.  A non-finite tile, gain or S0 entry makes every column of its own trajectory's
+ * report NaN (a non-finite plan value: the columns that read it) and cannot disturb another trajectory.  The _f64 form is
+ * asynchronous on the context's stream.  SCVX_ERR_ARG for B < 1, K != the problem's K, a null x / u / deriv / gain / S0 / report,
+ * a negative or non-finite w. */
+int scvx_cov_propagate_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                           const double *gain_dev, const double *S0_dev, const double *w14, double *report_dev, double *sig_dev,
+                           double *covK_dev, double *cov_dev);
+int scvx_cov_propagate_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv,
+                                const double *gain, const double *S0, const double *w14, double *report, double *sig,
+                                double *covK, double *cov);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -406,6 +457,13 @@ int scvx_batch_flight_check(scvx_batch *b, int nsub, int mode, double *report, d
 int scvx_batch_track_gains(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, double *gain, double *p0);
 int scvx_batch_track_fly(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *dx0, int nsub,
                          int flags, double *report, double *xfly, double *ufly);
+
+/* The covariance analysis above on the batch's current accepted iterate and its own derivative tiles (float tiles are widened on
+ * load), under the gains of the weights q14 / rNU / qf14 (computed into the scratch of scvx_batch_track_gains).  S0 [B][14][14],
+ * w14 [14] or NULL and every output are host arrays; report, sig, covK, cov may each be NULL.  The batch is left untouched, as by
+ * scvx_batch_flight_check.  Synchronises. */
+int scvx_batch_cov(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0, const double *w14,
+                   double *report, double *sig, double *covK, double *cov);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

@@ -389,6 +389,57 @@ track_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble
         (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         cache.ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nsub, flags, report_dev, xfly_dev, ufly_dev), "scvx_track_fly_f64")
 
+# ---- covariance analysis (new): the closed-loop dispersion of a tracked plan, to first order -----------------------------------
+# include/scvx.h, "covariance analysis".  S0 is 14 x 14 x B (only its symmetric part is used), w a scalar, 14 values or nothing;
+# the report is COV_NREP x B (rows COV_* + 1); dense outputs: sig n x (K+1) x B, covK n x n x B, cov n x n x (K+1) x B.
+const COV_NREP = 16   # SCVX_COV_NREP
+const COV_SIG_M = 0; const COV_SIG_R = 1; const COV_SIG_V = 2; const COV_SIG_Q = 3; const COV_SIG_W = 4
+const COV_ELL_A = 5; const COV_ELL_B = 6; const COV_ELL_ANG = 7; const COV_SIG_PEAK = 8; const COV_S_THRUST = 9
+const COV_N_MASS = 10; const COV_N_GLIDE = 11; const COV_N_TILT = 12; const COV_N_RATE = 13; const COV_N_TMAX = 14; const COV_N_TMIN = 15
+_cov_opt(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+
+# the current accepted iterate of a batch under its own LQR gains: (report, sig, covK, cov)
+function covariance(b::Batch, S0::Array{Float64,3}; w=nothing, q=1.0, r=1.0, qf=100.0, dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx)); n = 14 + NU
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, b.B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, b.B) : nothing
+    covK = dense ? Array{Float64,3}(undef, n, n, b.B) : nothing
+    cov = dense ? Array{Float64,4}(undef, n, n, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv check(b.cache.ctx, ccall((:scvx_batch_cov, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, _cov_opt(wv), report, _cov_opt(sig), _cov_opt(covK), _cov_opt(cov)),
+        "scvx_batch_cov")
+    return report, sig, covK, cov
+end
+
+# any plans (host arrays): x 14 x (K+1) x B, u NU x (K+1) x B, deriv 14 x (14 + 2 NU + 1) x K x B, gain n x NU x K x B, S0 14 x 14 x B
+function covariance(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                    S0::Array{Float64,3}; w=nothing, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); NU = size(u, 1); n = 14 + NU
+    size(S0) == (14, 14, B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, B) : nothing
+    covK = dense ? Array{Float64,3}(undef, n, n, B) : nothing
+    cov = dense ? Array{Float64,4}(undef, n, n, K + 1, B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv check(cache.ctx, ccall((:scvx_cov_propagate_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, _cov_opt(wv), report, _cov_opt(sig), _cov_opt(covK), _cov_opt(cov)),
+        "scvx_cov_propagate_f64_host")
+    return report, sig, covK, cov
+end
+
+# the same on device pointers (e.g. AMDGPU.jl ROCArrays), asynchronous on the context's stream; w stays a host vector (or C_NULL)
+cov_propagate_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+                   S0_dev::Ptr{Cdouble}, w::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble}, sig_dev::Ptr{Cdouble},
+                   covK_dev::Ptr{Cdouble}, cov_dev::Ptr{Cdouble}) =
+    GC.@preserve w check(cache.ctx, ccall((:scvx_cov_propagate_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), report_dev, sig_dev, covK_dev, cov_dev), "scvx_cov_propagate_f64")
+
 # multi-GPU (one Julia process per GPU): rank 0 draws the id, the host ships its 128 bytes (Distributed / MPI.jl / a file)
 unique_id() = (id = Vector{UInt8}(undef, 128); ccall((:scvx_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("RCCL unavailable"); id)
 comm_create!(c::Cache, id::Vector{UInt8}, rank::Int, world::Int) =

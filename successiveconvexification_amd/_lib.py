@@ -55,6 +55,11 @@ FLIGHT_COLUMNS = ("GAP", "MISS_R", "MISS_V", "MISS_Q", "MISS_W", "MASS_END", "G_
                   "G_TMIN", "G_GIMBAL", "G_DP", "G_FIN", "QNORM")
 FLIGHT_INDEX = {n: i for i, n in enumerate(FLIGHT_COLUMNS)}
 TRACK_CLAMP = 1   # SCVX_TRACK_CLAMP: scvx_track_fly_* rescales the commanded thrust / fin norms into their bounds
+# scvx_cov_propagate_*: the columns of the dispersion report [B][COV_NREP] (the SCVX_COV_* macros of include/scvx.h)
+COV_NREP = 16
+COV_COLUMNS = ("SIG_M", "SIG_R", "SIG_V", "SIG_Q", "SIG_W", "ELL_A", "ELL_B", "ELL_ANG", "SIG_PEAK", "S_THRUST", "N_MASS", "N_GLIDE",
+               "N_TILT", "N_RATE", "N_TMAX", "N_TMIN")
+COV_INDEX = {n: i for i, n in enumerate(COV_COLUMNS)}
 
 _vp = C.c_void_p
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
@@ -82,6 +87,8 @@ SIGNATURES = {
     "scvx_track_gains_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_track_fly_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "scvx_track_fly_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "scvx_cov_propagate_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
+    "scvx_cov_propagate_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),
@@ -113,6 +120,7 @@ SIGNATURES = {
     "scvx_batch_flight_check": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
     "scvx_batch_track_gains": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_track_fly": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "scvx_batch_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_comm_probe": (C.c_int, []),
     "scvx_comm_unique_id": (C.c_int, [_vp]),
     "scvx_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

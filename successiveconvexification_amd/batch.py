@@ -242,6 +242,25 @@ class ScvxBatch:
                                                _p(xfly) if dense else None, _p(ufly) if dense else None), "scvx_batch_track_fly")
         return FlightReport(rep, xfly, "track", ufly)
 
+    def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False):
+        """Closed-loop covariance analysis of the batch's current accepted iterate under its LQR gains (scvx_batch_cov; S0, w and
+        dense as dynamics.cov_propagate_batch, weights as track_gains): a dynamics.CovReport.  The batch is left untouched."""
+        from .dynamics import CovReport, _cov_dense, _cov_noise, _cov_s0, _track_weights
+        nu = self.cache.nu
+        n = 14 + nu
+        qv, rv, qfv = _track_weights(nu, q, r, qf)
+        s0 = _cov_s0(S0, self.B)
+        wv = _cov_noise(w)
+        want = _cov_dense(dense)
+        rep = np.empty((self.B, _lib.COV_NREP))
+        sig = np.empty((self.B, self.K + 1, n)) if "sig" in want else None
+        covK = np.empty((self.B, n, n)) if "covK" in want else None
+        cov = np.empty((self.B, self.K + 1, n, n)) if "cov" in want else None
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        self._chk(self._L.scvx_batch_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), opt(wv), _p(rep), opt(sig), opt(covK), opt(cov)),
+                  "scvx_batch_cov")
+        return CovReport(rep, sig, covK, cov)
+
     def set_profiling(self, on: bool):
         self._chk(self._L.scvx_batch_set_profiling(self.handle, 1 if on else 0), "scvx_batch_set_profiling")
 

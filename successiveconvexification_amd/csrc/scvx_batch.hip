@@ -765,6 +765,41 @@ int scvx_batch_track_fly(scvx_batch* b, const double* q14, const double* rNU, co
     return SCVX_OK;
 }
 
+int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
+                   double* report, double* sig, double* covK, double* cov) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    // every check before anything is enqueued
+    if (!S0) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
+    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const size_t n = 14 + b->NU;
+    const size_t n0 = (size_t)b->B * 196, nr = (size_t)b->B * SCVX_COV_NREP, ns = (size_t)b->B * (b->K + 1) * n, nk = (size_t)b->B * n * n,
+                 nc = (size_t)b->B * (b->K + 1) * n * n;
+    double *d0 = nullptr, *dr = nullptr, *ds = nullptr, *dk = nullptr, *dc = nullptr;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMalloc((void**)&d0, n0 * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dr, nr * 8);
+    if (e == hipSuccess && sig) e = hipMalloc((void**)&ds, ns * 8);
+    if (e == hipSuccess && covK) e = hipMalloc((void**)&dk, nk * 8);
+    if (e == hipSuccess && cov) e = hipMalloc((void**)&dc, nc * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(d0, S0, n0 * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = b->deriv_f ? scvx::launch_cov_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, d0, w14, dr, ds, dk, dc, st)
+                       : scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, d0, w14, dr, ds, dk, dc, st);
+    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && sig) e = hipMemcpyAsync(sig, ds, ns * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && covK) e = hipMemcpyAsync(covK, dk, nk * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && cov) e = hipMemcpyAsync(cov, dc, nc * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    for (double* p : {d0, dr, ds, dk, dc})
+        if (p) (void)hipFree(p);
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_cov: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
 int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
     int rc = check_batch(b, true);
     if (rc) return rc;

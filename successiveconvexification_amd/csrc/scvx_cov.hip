@@ -1,0 +1,432 @@
+// Closed-loop covariance analysis of tracked plans (scvx_cov_propagate_f64, include/scvx.h): the covariance of the augmented deviation
+// z_k = [dx_k; du_k] under the tracking law of scvx_track.hip, Sigma_{k+1} = M_k Sigma_k M_k' + diag(w, 0), M_k = F_k + G_k L_k, and the
+// per-trajectory dispersion report read off it.  No counterpart in the reference.
+//
+// cov_propagate_kernel: ONE WAVEFRONT PER TRAJECTORY, K sequential steps -- track_gains_kernel run forwards.  The rows 14.. of M_k are
+// L_k itself and only its 14 top rows meet the tile, so M is never stored as a matrix: the top rows are formed IN PLACE in the tile's
+// [A | B-] columns (Mtop = [A B-] + B+ L: the B+ columns are read, never written), the bottom rows are read from L.  One step is
+//     Mtop = [A B-] + B+ L (14 x n, NU deep),  V = M Sigma (n x n, n deep; Sigma symmetric, read by rows),
+//     T = V M' (n x n, n deep) written over Sigma,  Sigma = (T + T') / 2 + diag(w, 0): every pair from both of its triangles
+// with Sigma, the tile, L and V in LDS (7,432 B at NU = 3, 9,384 B at NU = 5: below the gains kernel's 10,080 / 13,088 B).  The two
+// n-deep products are the work.  MF = 0: one lane per output element.  MF = 1: the 16 x 16 corner of each product on the FP64
+// matrix pipe (5 x v_mfma_f64_16x16x4_f64: n = 17 / 19 pads to 20 k-slots) and the border (n^2 - 256 = 33 / 105 elements) one lane per
+// element -- two 16 x 16 tiles per side would spend three quarters of the matrix work on padding.  The tile and the gain block of step
+// k + 1 are fetched into registers while step k computes and stored to LDS behind the step's last barrier.  DS is the tiles' storage type
+// (double, or float with scvx_batch_set_linearization_f32: widened on load).
+//
+// The report is a handful of sparse quadratic forms per node: lanes 0..5 each carry one running extremum in registers (the plan values
+// of node k + 1 they need are loaded at the top of step k), lanes 6..11 read the final columns off Sigma_K.
+#include <cmath>
+#include <cstdlib>
+#include <limits>
+#include "scvx_internal.hpp"
+
+namespace scvx {
+
+// the constants of the path functions, formed as launch_flight forms them, and the process noise
+struct CovK {
+    double mdry, tggs, sqcm, omMax, Tmax, Tmin;
+    double w[14];
+};
+
+typedef double cov_v4f64 __attribute__((ext_vector_type(4)));
+
+// NaN-propagating running extrema and square root of a variance (a rounded variance of -1e-40 is 0, a NaN stays a NaN)
+__device__ __forceinline__ double cov_max(double a, double v) { return (v > a || v != v) ? v : a; }
+__device__ __forceinline__ double cov_min(double a, double v) { return (v < a || v != v) ? v : a; }
+__device__ __forceinline__ double cov_sd(double v) { return v > 0.0 ? sqrt(v) : (v != v ? v : 0.0); }
+
+// c' Sigma c for a gradient with (up to) three nonzeros c0, c1, c2 at i0, i1, i2
+__device__ __forceinline__ double cov_quad3(const double* S, int n, int i0, int i1, int i2, double c0, double c1, double c2) {
+    const double d = c0 * c0 * S[i0 * n + i0] + c1 * c1 * S[i1 * n + i1] + c2 * c2 * S[i2 * n + i2];
+    const double o = c0 * c1 * S[i0 * n + i1] + c0 * c2 * S[i0 * n + i2] + c1 * c2 * S[i1 * n + i2];
+    return d + 2.0 * o;
+}
+
+// The 16 x 16 corner C[0..15][0..15] of an n-deep product on the FP64 matrix pipe (fragment maps as track_mm16: A: lane l holds
+// A[l & 15][l >> 4], B: B[l >> 4][l & 15], C: register r of lane l is C[(l >> 4) + 4 r][l & 15]).  n >= 17, so every row and column of
+// the corner exists; k-slots >= KD are fed zeros from a clamped, valid address.
+template <int KD, class FA, class FB, class FC>
+__device__ __forceinline__ void cov_mm16(FA fa, FB fb, FC store, int lane) {
+    const int rc = lane & 15, kq = lane >> 4;
+    cov_v4f64 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < (KD + 3) / 4; s++) {
+        const int k = 4 * s + kq, kc = k < KD ? k : KD - 1;
+        const double a = fa(rc, kc), b = fb(kc, rc);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(k < KD ? a : 0.0, k < KD ? b : 0.0, c, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) store(kq + 4 * r, rc, c[r]);
+}
+
+// MF: 0 = one lane per element, 1 = the 16 x 16 corner of the two n-deep products on the matrix pipe
+template <typename DS, int NU, int MF>
+__global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
+                                                           const DS* __restrict__ deriv, const double* __restrict__ gain,
+                                                           const double* __restrict__ S0, double* __restrict__ report,
+                                                           double* __restrict__ sig, double* __restrict__ covK, double* __restrict__ cov) {
+    constexpr int n = 14 + NU, m = 14 + 2 * NU, NC = m + 1, DSZ = 14 * NC, ND = 14 * m, NL = NU * n, NN = n * n;
+    constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
+    constexpr int NBORD = NN - 256;   // elements of an n x n product outside its 16 x 16 corner
+    __shared__ double Sl[NN], Dl[ND], Ll[NL], Vl[NN], Rl[SCVX_COV_NREP + 1];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const DS* tiles = deriv + (size_t)b * K * DSZ;
+    const double* gb = gain + (size_t)b * K * NL;
+    const double* xb = x + (size_t)b * (K + 1) * 14;
+    const double* ub = u + (size_t)b * (K + 1) * NU;
+    const double* s0 = S0 + (size_t)b * 196;
+    double* covb = cov ? cov + (size_t)b * (K + 1) * NN : nullptr;
+    double* sigb = sig ? sig + (size_t)b * (K + 1) * n : nullptr;
+    const double inf = std::numeric_limits<double>::infinity();
+    // Sigma_0 = blockdiag((S0 + S0') / 2, 0); tile 0 and gain block 0
+    for (int e = lane; e < NN; e += 64) {
+        const int a = e / n, cc = e % n;
+        Sl[e] = (a < 14 && cc < 14) ? 0.5 * (s0[a * 14 + cc] + s0[cc * 14 + a]) : 0.0;
+    }
+    for (int e = lane; e < ND; e += 64) Dl[e] = (double)tiles[e];
+    for (int e = lane; e < NL; e += 64) Ll[e] = gb[e];
+    // the running columns: lane 0 SIG_PEAK (and the non-finite flag), 1 N_MASS, 2 N_GLIDE, 3 N_TILT, 4 N_RATE, 5 S_THRUST / N_TMAX / N_TMIN
+    double acc0 = lane == 0 ? 0.0 : inf, acc1 = inf, acc2 = 0.0, bad = 0.0;
+    double pv0 = 0.0, pv1 = 0.0, pv2 = 0.0;
+    __syncthreads();
+    // row a of M: the top rows sit in the tile's first n columns (column-major, stride 14), the bottom rows are L's
+    auto mrow = [&](int a, int& st) -> const double* {
+        st = a < 14 ? 14 : 1;
+        return a < 14 ? Dl + a : Ll + (a - 14) * n;
+    };
+    auto velem = [&](int a, int cc) {   // V[a][cc] = sum_l M[a][l] Sigma[cc][l]
+        int st;
+        const double* mp = mrow(a, st);
+        double s = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; l++) s = fma(mp[l * st], Sl[cc * n + l], s);
+        return s;
+    };
+    auto telem = [&](int a, int cc) {   // T[a][cc] = sum_l V[a][l] M[cc][l]
+        int st;
+        const double* mp = mrow(cc, st);
+        double s = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; l++) s = fma(Vl[a * n + l], mp[l * st], s);
+        return s;
+    };
+    auto border = [](int e, int& a, int& cc) {   // e < NBORD: rows 16.. first, then the columns 16.. of rows 0..15
+        if (e < (n - 16) * n) {
+            a = 16 + e / n;
+            cc = e % n;
+        } else {
+            e -= (n - 16) * n;
+            a = e % 16;
+            cc = 16 + e / 16;
+        }
+    };
+    // dense outputs and the running columns at node k (Sigma_k in Sl; pv*: the plan values of node k this lane's column reads)
+    auto node_out = [&](int k) {
+        if (covb)
+            for (int e = lane; e < NN; e += 64) covb[(size_t)k * NN + e] = Sl[e];
+        if (sigb && lane < n) sigb[(size_t)k * n + lane] = cov_sd(Sl[lane * n + lane]);
+        if (lane == 0) {
+            double tr = 0.0;
+#pragma unroll
+            for (int i = 0; i < 14; i++) tr += Sl[i * n + i];
+            bad = fma(tr, 0.0, bad);
+            acc0 = cov_max(acc0, cov_sd(tr));
+        } else if (k > 0 && lane < 6) {
+            if (lane == 1) {
+                const double s = cov_sd(Sl[0]);
+                if (!(s == 0.0)) acc0 = cov_min(acc0, -(c.mdry - pv0) / s);
+            } else if (lane == 5) {
+                const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
+                if (!(nr == 0.0)) {
+                    const double s = cov_sd(cov_quad3(Sl, n, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
+                    acc2 = cov_max(acc2, s);
+                    if (!(s == 0.0)) {
+                        acc0 = cov_min(acc0, -(nr - c.Tmax) / s);
+                        acc1 = cov_min(acc1, -(c.Tmin - nr) / s);
+                    }
+                }
+            } else {
+                // 2 glide: g = tggs |r[2:3]| - r[1];  3 tilt: g = |q[3:4]| - sqcm;  4 rate: g = |w| - omMax
+                const double a0 = lane == 2 ? pv1 : pv0, a1 = lane == 2 ? pv2 : pv1, a2 = lane == 4 ? pv2 : 0.0;
+                const double nr = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+                if (!(nr == 0.0)) {
+                    double g, q;
+                    if (lane == 2) {
+                        g = c.tggs * nr - pv0;
+                        q = cov_quad3(Sl, n, 1, 2, 3, -1.0, c.tggs * a0 / nr, c.tggs * a1 / nr);
+                    } else if (lane == 3) {
+                        g = nr - c.sqcm;
+                        q = cov_quad3(Sl, n, 9, 10, 10, a0 / nr, a1 / nr, 0.0);
+                    } else {
+                        g = nr - c.omMax;
+                        q = cov_quad3(Sl, n, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
+                    }
+                    const double s = cov_sd(q);
+                    if (!(s == 0.0)) acc0 = cov_min(acc0, -g / s);
+                }
+            }
+        }
+    };
+    node_out(0);
+    for (int k = 0; k < K; k++) {
+        // the next step's tile and gain block, and the plan values of node k + 1, in flight while this step computes
+        DS pre[NPRE];
+        double prel[NLPRE];
+        if (k + 1 < K) {
+            const DS* t = tiles + (size_t)(k + 1) * DSZ;
+            const double* g = gb + (size_t)(k + 1) * NL;
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) {
+                const int e = lane + 64 * i;
+                pre[i] = e < ND ? t[e] : DS(0);
+            }
+#pragma unroll
+            for (int i = 0; i < NLPRE; i++) {
+                const int e = lane + 64 * i;
+                prel[i] = e < NL ? g[e] : 0.0;
+            }
+        }
+        if (lane >= 1 && lane < 6) {
+            const double* xn = xb + (size_t)(k + 1) * 14;
+            const double* un = ub + (size_t)(k + 1) * NU;
+            const double* p = lane == 1 ? xn : lane == 2 ? xn + 1 : lane == 3 ? xn + 9 : lane == 4 ? xn + 11 : un;
+            pv0 = p[0];
+            pv1 = lane == 1 ? 0.0 : p[1];
+            pv2 = (lane == 1 || lane == 3) ? 0.0 : p[2];
+        }
+        // Mtop = [A B-] + B+ L, in place
+        for (int e = lane; e < 14 * n; e += 64) {
+            const int i = e % 14, cc = e / 14;
+            double s = Dl[e];
+#pragma unroll
+            for (int j = 0; j < NU; j++) s = fma(Dl[(n + j) * 14 + i], Ll[j * n + cc], s);
+            Dl[e] = s;
+        }
+        __syncthreads();
+        // V = M Sigma
+        if (MF) {
+            cov_mm16<n>([&](int i, int l) { int st; const double* mp = mrow(i, st); return mp[l * st]; },
+                        [&](int l, int j) { return Sl[j * n + l]; }, [&](int i, int j, double v) { Vl[i * n + j] = v; }, lane);
+            for (int e = lane; e < NBORD; e += 64) {
+                int a, cc;
+                border(e, a, cc);
+                Vl[a * n + cc] = velem(a, cc);
+            }
+        } else {
+            for (int e = lane; e < NN; e += 64) {
+                const int a = e % n, cc = e / n;
+                Vl[a * n + cc] = velem(a, cc);
+            }
+        }
+        __syncthreads();
+        // T = V M', over Sigma (no longer read)
+        if (MF) {
+            cov_mm16<n>([&](int i, int l) { return Vl[i * n + l]; },
+                        [&](int l, int j) { int st; const double* mp = mrow(j, st); return mp[l * st]; },
+                        [&](int i, int j, double v) { Sl[i * n + j] = v; }, lane);
+            for (int e = lane; e < NBORD; e += 64) {
+                int a, cc;
+                border(e, a, cc);
+                Sl[a * n + cc] = telem(a, cc);
+            }
+        } else {
+            for (int e = lane; e < NN; e += 64) {
+                const int cc = e % n, a = e / n;
+                Sl[e] = telem(a, cc);
+            }
+        }
+        __syncthreads();
+        // Sigma_{k+1} = (T + T') / 2 + diag(w, 0): one lane per pair, both triangles written with the same value
+        for (int e = lane; e < NN; e += 64) {
+            const int a = e / n, cc = e % n;
+            if (a < cc) {
+                const double s = 0.5 * (Sl[a * n + cc] + Sl[cc * n + a]);
+                Sl[a * n + cc] = s;
+                Sl[cc * n + a] = s;
+            } else if (a == cc && a < 14) {
+                Sl[e] += c.w[a];
+            }
+        }
+        if (k + 1 < K) {
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) {
+                const int e = lane + 64 * i;
+                if (e < ND) Dl[e] = (double)pre[i];
+            }
+#pragma unroll
+            for (int i = 0; i < NLPRE; i++) {
+                const int e = lane + 64 * i;
+                if (e < NL) Ll[e] = prel[i];
+            }
+        }
+        __syncthreads();
+        node_out(k + 1);
+    }
+    // the report: running columns from their lanes, the final columns off Sigma_K
+    if (covK) {
+        double* o = covK + (size_t)b * NN;
+        for (int e = lane; e < NN; e += 64) o[e] = Sl[e];
+    }
+    auto blk = [&](int i0, int i1) {
+        double t = 0.0;
+        for (int i = i0; i < i1; i++) t += Sl[i * n + i];
+        return cov_sd(t);
+    };
+    if (lane == 0) {
+        Rl[SCVX_COV_SIG_PEAK] = acc0;
+        Rl[SCVX_COV_NREP] = bad;
+    } else if (lane == 1) {
+        Rl[SCVX_COV_N_MASS] = acc0;
+    } else if (lane == 2) {
+        Rl[SCVX_COV_N_GLIDE] = acc0;
+    } else if (lane == 3) {
+        Rl[SCVX_COV_N_TILT] = acc0;
+    } else if (lane == 4) {
+        Rl[SCVX_COV_N_RATE] = acc0;
+    } else if (lane == 5) {
+        Rl[SCVX_COV_S_THRUST] = acc2;
+        Rl[SCVX_COV_N_TMAX] = acc0;
+        Rl[SCVX_COV_N_TMIN] = acc1;
+    } else if (lane == 6) {
+        Rl[SCVX_COV_SIG_M] = cov_sd(Sl[0]);
+    } else if (lane == 7) {
+        Rl[SCVX_COV_SIG_R] = blk(1, 4);
+    } else if (lane == 8) {
+        Rl[SCVX_COV_SIG_V] = blk(4, 7);
+    } else if (lane == 9) {
+        Rl[SCVX_COV_SIG_Q] = blk(7, 11);
+    } else if (lane == 10) {
+        Rl[SCVX_COV_SIG_W] = blk(11, 14);
+    } else if (lane == 11) {
+        // eigenvalues of [[a, h], [h, d]], the horizontal block of Sigma_K (state indices 2, 3), closed form
+        const double a = Sl[2 * n + 2], d = Sl[3 * n + 3], h = Sl[2 * n + 3];
+        const double mean = 0.5 * (a + d), dif = 0.5 * (a - d), rad = sqrt(dif * dif + h * h);
+        Rl[SCVX_COV_ELL_A] = cov_sd(mean + rad);
+        Rl[SCVX_COV_ELL_B] = cov_sd(mean - rad);
+        Rl[SCVX_COV_ELL_ANG] = 0.5 * atan2(2.0 * h, a - d);
+    }
+    __syncthreads();
+    if (lane < SCVX_COV_NREP) report[(size_t)b * SCVX_COV_NREP + lane] = Rl[lane] + Rl[SCVX_COV_NREP];
+}
+
+constexpr bool kCovMfmaDefault = false;   // the lane form, which the parity tests pin, until the A/B of tools/bench_cov.py is measured
+
+template <typename DS>
+static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv, const double* gain,
+                               const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
+    const scvx_problem& P = ctx->prob;
+    const double d2r = M_PI / 180.0;
+    CovK c{};
+    c.mdry = P.mdry;
+    c.tggs = std::tan(P.gammaGs * d2r);
+    c.sqcm = std::sqrt((1.0 - std::cos(P.thetaMax * d2r)) / 2.0);
+    c.omMax = P.omMax;
+    c.Tmax = P.Tmax;
+    c.Tmin = P.Tmin;
+    for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
+    // SCVX_COV_MFMA = 0 / 1 forces the lane-per-element / matrix-pipe form of the two n-deep products (A/B: tools/bench_cov.py)
+    bool mf = kCovMfmaDefault;
+    if (const char* v = std::getenv("SCVX_COV_MFMA"); v && *v) mf = std::atoi(v) != 0;
+    const dim3 g((unsigned)B), blk(64);
+#define SCVX_COV_LAUNCH(NU, MF) \
+    hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, cov)
+    if (ctx->dyn.fin) {
+        if (mf) SCVX_COV_LAUNCH(5, 1);
+        else SCVX_COV_LAUNCH(5, 0);
+    } else {
+        if (mf) SCVX_COV_LAUNCH(3, 1);
+        else SCVX_COV_LAUNCH(3, 0);
+    }
+#undef SCVX_COV_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
+    return launch_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, w, report, sig, covK, cov, st);
+}
+
+hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                          const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
+    return launch_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, w, report, sig, covK, cov, st);
+}
+
+int check_cov_noise(scvx_ctx* ctx, const double* w) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (w)
+        for (int i = 0; i < 14; i++)
+            if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
+                return fail(ctx, SCVX_ERR_ARG, "cov: the process noise w must be finite and >= 0");
+    return SCVX_OK;
+}
+
+int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
+              const double* w, const void* report) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (B < 1) return fail(ctx, SCVX_ERR_ARG, "cov: B >= 1 required");
+    if (K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "cov: K must equal the problem's K");
+    if (!x || !u || !deriv || !gain || !S0 || !report) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
+    return check_cov_noise(ctx, w);
+}
+
+namespace {
+struct CovDev {
+    double* p = nullptr;
+    ~CovDev() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+}  // namespace scvx
+
+extern "C" {
+
+int scvx_cov_propagate_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                           const double* gain_dev, const double* S0_dev, const double* w14, double* report_dev, double* sig_dev,
+                           double* covK_dev, double* cov_dev) {
+    int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev, sig_dev, covK_dev, cov_dev,
+                                   ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_cov_propagate_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                                const double* S0, const double* w14, double* report, double* sig, double* covK, double* cov) {
+    int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU;
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
+                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, ns = (size_t)B * (K + 1) * n,
+                 nk = (size_t)B * n * n, nc = (size_t)B * (K + 1) * n * n;
+    scvx::CovDev dx, du, dd, dg, d0, dr, ds, dk, dc;
+    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    if (sig) SCVX_HIP(ctx, hipMalloc((void**)&ds.p, ns * 8));
+    if (covK) SCVX_HIP(ctx, hipMalloc((void**)&dk.p, nk * 8));
+    if (cov) SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nc * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, w14, dr.p, ds.p, dk.p, dc.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    if (sig) SCVX_HIP(ctx, hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st));
+    if (covK) SCVX_HIP(ctx, hipMemcpyAsync(covK, dk.p, nk * 8, hipMemcpyDeviceToHost, st));
+    if (cov) SCVX_HIP(ctx, hipMemcpyAsync(cov, dc.p, nc * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+}  // extern "C"

@@ -67,6 +67,14 @@ int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const d
 int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
                     const void* report);
 
+// Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles (double or float) and the gains;
+// S0[B][14][14]; w: host array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.
+hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
+hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                          const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
+int check_cov_noise(scvx_ctx* ctx, const double* w);
+
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],
 // info [B][6] = status, iters, pobj, gap, pres, dres.  threedof_to_record overwrites the trajectory records [B][(K+1)*(14+NU)+1]
 // of the trajectories whose solve is optimal with the LinPoints of initial_solve.jl:90-105.

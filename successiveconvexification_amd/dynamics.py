@@ -235,6 +235,99 @@ def track_fly_batch(cache: IntegratorCache, x, u, sigma, gain, dx0=None, nsub=No
     return FlightReport(rep, xfly, "track", ufly)
 
 
+class CovReport:
+    """The dispersion report of a covariance analysis (scvx_cov_propagate_f64, include/scvx.h): `raw` [B][16], one named numpy view
+    per column (report.SIG_R, report.N_TMIN, ... -- _lib.COV_COLUMNS), and the optional dense outputs `sig` [B][K+1][14+nu] (the
+    1 sigma corridor about the plan), `covK` [B][n][n] (the final covariance) and `cov` [B][K+1][n][n], or None.  SIG_* / ELL_* /
+    S_THRUST are standard deviations in the problem's own units; N_* are margins to the path constraints in standard deviations
+    (+inf: no node had one; negative: the plan itself violates).  First order about the plan; the clamp is not modelled."""
+
+    N_COLUMNS = tuple(n for n in _lib.COV_COLUMNS if n.startswith("N_"))
+
+    def __init__(self, raw, sig=None, covK=None, cov=None):
+        self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.COV_NREP)
+        self.sig = sig
+        self.covK = covK
+        self.cov = cov
+        for name, i in _lib.COV_INDEX.items():
+            setattr(self, name, self.raw[:, i])
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    def tightest(self):
+        """[B]: the smallest N_* margin of each trajectory (NaN if any is NaN)."""
+        g = self.raw[:, [_lib.COV_INDEX[n] for n in self.N_COLUMNS]]
+        return np.where(np.isnan(g).any(axis=1), np.nan, np.min(np.nan_to_num(g, nan=np.inf), axis=1))
+
+
+def _cov_s0(S0, B):
+    """S0 as [B][14][14], one [14][14] for all, or a [14] vector of standard deviations (S0 = diag(sd^2)) -> contiguous [B][14][14]"""
+    a = np.asarray(S0, np.float64)
+    if a.shape == (14,):
+        a = np.diag(a * a)
+    if a.shape == (14, 14):
+        a = np.broadcast_to(a, (B, 14, 14))
+    if a.shape != (B, 14, 14):
+        raise ValueError("S0 must be [B][14][14], [14][14] or a [14] vector of standard deviations (B = %d)" % B)
+    return np.ascontiguousarray(a, np.float64)
+
+
+def _cov_noise(w):
+    """process-noise variances: None, a scalar or [14] -> None or a contiguous [14]"""
+    if w is None:
+        return None
+    a = np.asarray(w, np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != 14):
+        raise ValueError("w must be a scalar or have 14 components")
+    return np.ascontiguousarray(np.broadcast_to(a, (14,)), np.float64)
+
+
+def _cov_dense(dense):
+    """dense: False / True (all three) / an iterable of names out of "sig", "covK", "cov" -> the set of wanted outputs"""
+    if dense is True:
+        return {"sig", "covK", "cov"}
+    if not dense:
+        return set()
+    want = {dense} if isinstance(dense, str) else set(dense)
+    if not want <= {"sig", "covK", "cov"}:
+        raise ValueError("dense: True, False or names out of 'sig', 'covK', 'cov', not %r" % (dense,))
+    return want
+
+
+def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, dense=False) -> CovReport:
+    """Closed-loop covariance of the plans x [B][K+1][14], u [B][K+1][nu] tracked under the gains gain [B][K][nu][14+nu] (what
+    track_gains_batch returns) from the derivative tiles deriv [B][K][14+2nu+1][14] (what linearize_batch returns), on the device
+    (scvx_cov_propagate_f64_host; the recursion and its limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one
+    [14][14] for all, or a [14] vector of standard deviations; only its symmetric part is used.  w: process-noise variance added per
+    segment, a scalar or [14] (None = 0).  dense: True for sig, covK and cov, or a subset of those names."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    deriv = np.ascontiguousarray(deriv, np.float64)
+    nu = cache.nu
+    n = 14 + nu
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
+    B, K1, _ = x.shape
+    K = K1 - 1
+    if gain.shape != (B, K, nu, n):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
+    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
+        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
+    s0 = _cov_s0(S0, B)
+    wv = _cov_noise(w)
+    want = _cov_dense(dense)
+    rep = np.empty((B, _lib.COV_NREP))
+    sig = np.empty((B, K1, n)) if "sig" in want else None
+    covK = np.empty((B, n, n)) if "covK" in want else None
+    cov = np.empty((B, K1, n, n)) if "cov" in want else None
+    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    _lib.check(cache.handle, cache._L.scvx_cov_propagate_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
+                                                                  _p(rep), opt(sig), opt(covK), opt(cov)), "scvx_cov_propagate_f64_host")
+    return CovReport(rep, sig, covK, cov)
+
+
 def _pf(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 

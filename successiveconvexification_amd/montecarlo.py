@@ -52,6 +52,42 @@ def disperse_handover(x0, lo, hi, seed, frac_r=0.0, frac_v=0.0, angle=0.0, rate=
     return dx0
 
 
+def handover_factor(S0):
+    """A factor C [14][14] with C C' = the symmetric part of S0: the Cholesky factor of the coordinates S0 disperses (a coordinate
+    whose row of S0 is zero, e.g. an untouched mass, gets an exactly zero row, so its samples are exactly 0); where that block is
+    only semi-definite, the eigen factor V sqrt(max(lambda, 0)) of the whole."""
+    S = np.asarray(S0, np.float64)
+    if S.shape == (14,):
+        return np.diag(np.abs(S))
+    if S.shape != (14, 14):
+        raise ValueError("S0 must be [14][14] or a [14] vector of standard deviations")
+    S = 0.5 * (S + S.T)
+    live = np.flatnonzero(np.abs(S).max(axis=1) > 0.0)
+    Cf = np.zeros((14, 14))
+    if live.size == 0:
+        return Cf
+    try:
+        Cf[np.ix_(live, live)] = np.linalg.cholesky(S[np.ix_(live, live)])
+    except np.linalg.LinAlgError:
+        lam, V = np.linalg.eigh(S)
+        Cf = V * np.sqrt(np.maximum(lam, 0.0))[None, :]
+    return Cf
+
+
+def gaussian_handover(S0, lo, hi, seed):
+    """Gaussian state offsets dx0 [hi - lo][14] with covariance S0 ([14][14], or a [14] vector of standard deviations) at the handover
+    to a tracking law: the sampling counterpart of the covariance analysis (ScvxBatch.covariance, dynamics.cov_propagate_batch).
+    dx0 = C xi with C = handover_factor(S0) and xi standard normal; trajectory b draws from Philox stream b of `seed` with a counter
+    word of its own (the draws are neither those of disperse_ics nor of disperse_handover), so a shard [lo, hi) gets exactly the rows
+    the whole batch would."""
+    Cf = handover_factor(S0)
+    dx0 = np.zeros((hi - lo, 14))
+    for b in range(lo, hi):
+        rng = np.random.Generator(np.random.Philox(key=seed, counter=[2, 0, 0, b]))
+        dx0[b - lo] = Cf @ rng.standard_normal(14)
+    return dx0
+
+
 def shard_range(total: int, rank: int, world: int):
     """Contiguous shard [lo, hi) of `total` trajectories for `rank`; sizes differ by at most one."""
     base, rem = divmod(int(total), int(world))
@@ -167,6 +203,33 @@ def flight_summary(report, status, tol=0.0):
             out["stats"][n] = None
         elif np.all(np.isneginf(c)):   # a constraint the model does not enforce
             out["stats"][n] = {k: float("-inf") for k in ("min", "median", "p99", "max")}
+        else:
+            out["stats"][n] = {"min": float(np.min(c)), "median": float(np.median(c)), "p99": float(np.percentile(c, 99)),
+                               "max": float(np.max(c))}
+    return out
+
+
+def dispersion_summary(covreport, status):
+    """What a Monte-Carlo batch of plans has to say once its covariance analysis is done.  covreport: a dynamics.CovReport or its raw
+    [N][16] array; status [N]: the SCvx statuses of scvx_solve.  Returns a plain dict: counts by SCvx status, the number of converged
+    plans, and min / median / p99 / max of every column over the converged plans (None where there is none; a column that is +inf in
+    every converged row -- no node had that margin -- reports +inf).  Pure numpy."""
+    from ._lib import COV_COLUMNS, COV_INDEX, COV_NREP
+    names = {0: "converged", 1: "running", 2: "rejected", 3: "solver", 4: "nonfinite", 5: "infeasible"}
+    raw = np.asarray(getattr(covreport, "raw", covreport), np.float64).reshape(-1, COV_NREP)
+    status = np.asarray(status).reshape(-1)
+    if status.shape[0] != raw.shape[0]:
+        raise ValueError("report has %d rows, status %d" % (raw.shape[0], status.shape[0]))
+    counts = {n: int(np.sum(status == c)) for c, n in names.items()}
+    counts["other"] = int(status.shape[0] - sum(counts.values()))
+    conv = raw[status == 0]
+    out = {"n": int(raw.shape[0]), "counts": counts, "converged": int(conv.shape[0]), "stats": {}}
+    for n in COV_COLUMNS:
+        c = conv[:, COV_INDEX[n]]
+        if c.shape[0] == 0:
+            out["stats"][n] = None
+        elif np.all(np.isposinf(c)):
+            out["stats"][n] = {k: float("inf") for k in ("min", "median", "p99", "max")}
         else:
             out["stats"][n] = {"min": float(np.min(c)), "median": float(np.median(c)), "p99": float(np.percentile(c, 99)),
                                "max": float(np.max(c))}

@@ -7,6 +7,7 @@
     solve_problem(iprob, cache) -> (ProblemIteration, cnu, cdel)  rocketland.jl:432-443
     fly(iteration, cache) -> FlightReport                         (new: open-loop flight + path audit of a plan)
     track(iteration, cache, dx0) -> FlightReport                  (new: closed-loop flight under LQR gains about the plan)
+    covariance(iteration, cache, S0) -> CovReport                 (new: closed-loop covariance analysis of the tracked plan)
 The recipe of rocketland.jl:26-32 reads the same here:
     cache = IntegratorCache(prob, ProbInfo.from_problem(prob), make_dynamics_module(...))
     pi = create_initial(prob, cache); pi, cnu, cdel = solve_step(pi, cache)
@@ -77,6 +78,22 @@ def track(iteration: ProblemIteration, cache: IntegratorCache = None, dx0=None, 
     gain = track_gains_batch(cache, deriv, q, r, qf)
     d0 = None if dx0 is None else np.asarray(dx0, np.float64).reshape(1, 14)
     return track_fly_batch(cache, x, u, sigma, gain, d0, nsub=nsub, clamp=clamp, dense=dense)
+
+
+def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False):
+    """Closed-loop covariance analysis of an iterate's plan tracked under the time-varying LQR gains about it, from the handover
+    covariance S0 ([14][14], or a [14] vector of standard deviations) with the per-segment process noise w (dynamics.track_gains_batch
+    on the plan's own linearisation, dynamics.cov_propagate_batch).  A dynamics.CovReport of one row."""
+    from .dynamics import cov_propagate_batch, linearize_batch, track_gains_batch
+    if S0 is None:
+        raise ValueError("covariance: S0 (the handover covariance) is required")
+    cache = cache if cache is not None else iteration.cache
+    x = np.stack([pt.state for pt in iteration.about])[None]
+    u = np.stack([pt.control for pt in iteration.about])[None]
+    sigma = np.array([float(iteration.sigma)])
+    _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
+    gain = track_gains_batch(cache, deriv, q, r, qf)
+    return cov_propagate_batch(cache, x, u, deriv, gain, S0, w, dense=dense)
 
 
 def run_iters(iprob: DescentProblem, niters: int, cache: IntegratorCache = None):

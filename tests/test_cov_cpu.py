@@ -1,0 +1,277 @@
+"""Covariance analysis without a GPU: the independent reference (tests/cov_reference.py: the recursion of include/scvx.h in numpy with
+the full F, G, M) against the nonlinear closed loop of the C oracle (finite differences, and a Monte-Carlo batch with a derived
+bound), against its own longdouble form and the properties that define a covariance recursion; the three bindings (header,
+_lib.SIGNATURES, julia/ScvxAMD.jl) against each other; montecarlo.gaussian_handover / dispersion_summary; dynamics.CovReport.
+
+Data: the two plans the oracle converges on (tests/golden/oracle_flight_runs.npz), tiles from oracle.dynamics.linearize."""
+import os
+import re
+from dataclasses import replace
+
+import numpy as np
+import pytest
+
+import cov_reference as cr
+import flight_reference as fr
+import track_reference as tr
+from conftest import GOLDEN, ROOT
+
+WEIGHTS = [(1.0, 1.0, 100.0), (1.0, 1e-2, 1e4), (10.0, 1.0, 1e6)]
+_DATA = {}
+
+
+def _data():
+    """(oracle problem, dyn Params, x, u, sigma, deriv) of the golden converged plans"""
+    if not _DATA:
+        from oracle import dynamics as od, model
+        g = np.load(os.path.join(GOLDEN, "oracle_flight_runs.npz"))
+        p = replace(model.base_prob_scaled(), mdry=0.55, nuTol=1e-6, delTol=1e-3, imax=40, tf_guess=8.0)
+        par = od.Params(p)
+        x, u, s = g["x"], g["u"], g["sigma"]
+        _, d = od.linearize(par, x, u, s, 1.0 / (p.K + 1), 10)
+        _DATA["v"] = (p, par, x, u, s, d)
+    return _DATA["v"]
+
+
+def test_the_recursion_predicts_the_nonlinear_closed_loop_to_second_order():
+    """For S0 = C C' the starts x[0] +- eps C[:, j] flown through the C oracle's closed loop give sum_j d_j d_j'; against the recursion
+    (w = 0) the difference at node K falls with eps^2: error(2) / error(0.5) in [13, 20] about the nominal 16, and error(0.5) < 1e-5."""
+    from oracle import dynamics as od
+    p, par, x, u, s, d = _data()
+    fly = lambda X, U, S, L, dx0: tr.fly(od, p, X, U, S, L, dx0, 10, 0, par)[1]   # noqa: E731
+    for wi, w in enumerate(WEIGHTS):
+        L, _ = tr.gains(d, p.K, *w)
+        for b in range(2):
+            S0, C = cr.handover_s0(x[b, 0])
+            cov = cr.propagate(d[b:b + 1], p.K, L[b:b + 1], S0[None])[0]
+            err = cr.fd_errors(fly, x[b:b + 1], u[b:b + 1], s[b:b + 1], L[b:b + 1], cov, C, (2.0, 1.0, 0.5, 0.1))
+            ratio = err[2.0] / err[0.5]
+            print("weights %s plan %d: error at eps 2 / 1 / 0.5 / 0.1 = %.2e / %.2e / %.2e / %.2e, ratio(2 : 0.5) %.2f"
+                  % (w, b, err[2.0], err[1.0], err[0.5], err[0.1], ratio))
+            if wi < 2:
+                assert 13.0 <= ratio <= 20.0, (w, b, ratio)
+                assert err[0.5] < 1e-5, (w, b, err[0.5])
+
+
+@pytest.mark.parametrize("b", [0, 1])
+def test_monte_carlo_sample_covariance_within_six_standard_errors(b):
+    """N = 8,192 Gaussian starts (S0 of the check above with its factor scaled by 0.1, so that the second-order part of the flight
+    stays below the sampling error) flown through the C oracle's closed loop.  Var(S^_ij) = (S_ii S_jj + S_ij^2) / (N - 1) for Gaussian
+    samples: |S^_ij - S_ij| <= 6 sqrt(that) for EVERY entry of every node."""
+    from oracle import dynamics as od
+    from successiveconvexification_amd.montecarlo import gaussian_handover
+    p, par, x, u, s, d = _data()
+    N = 8192
+    L, _ = tr.gains(d, p.K)
+    S0, C = cr.handover_s0(x[b, 0], scale=0.1)
+    dx0 = gaussian_handover(S0, 0, N, 11)
+    sl = slice(b, b + 1)
+    _, xf, uf, _ = tr.fly(od, p, cr.rep(x[sl], N), cr.rep(u[sl], N), cr.rep(s[sl], N), cr.rep(L[sl], N), dx0, 10, 0, par)
+    cov = cr.propagate(d[sl], p.K, L[sl], S0[None])[0]
+    worst, worstK, over = cr.mc_check(xf, uf, x[b], u[b], cov)
+    print("plan %d: worst entry %.2f standard errors (%.2f at node K), %d entries over 6" % (b, worst, worstK, over))
+    assert over == 0, (worst, over)
+
+
+@pytest.mark.parametrize("w", WEIGHTS[:2])
+def test_float64_against_longdouble_symmetry_and_definiteness(w):
+    p, par, x, u, s, d = _data()
+    L, _ = tr.gains(d, p.K, *w)
+    S0 = np.stack([cr.handover_s0(x[b, 0])[0] for b in range(2)])
+    c64 = cr.propagate(d, p.K, L, S0)
+    cld = cr.propagate(d, p.K, L, S0, dtype=np.longdouble)
+    e = float(np.abs(c64 - cld).max() / np.abs(cld).max())
+    print("weights %s: float64 vs longdouble %.2e" % (w, e))
+    if np.finfo(np.longdouble).eps < np.finfo(np.float64).eps:
+        assert e < 1e-12      # K n 2^-52 = 1.9e-13 for the chained n-term products, times the room the stiffer gains need
+    assert np.array_equal(c64, np.swapaxes(c64, -1, -2))
+    lam = np.linalg.eigvalsh(c64)
+    print("smallest eigenvalue / max|Sigma| %.2e" % (lam.min() / np.abs(c64).max()))
+    assert lam.min() >= -1e-12 * np.abs(c64).max()
+
+
+def test_zero_gains_give_the_open_loop_transport_and_zero_s0_is_linear_in_w():
+    p, par, x, u, s, d = _data()
+    S0 = np.stack([cr.handover_s0(x[b, 0])[0] for b in range(2)])
+    L0 = np.zeros((2, p.K, 3, 17))
+    cov = cr.propagate(d, p.K, L0, S0)
+    Phi = cr.open_loop_phi(d, p.K)
+    want = Phi @ S0 @ np.swapaxes(Phi, 1, 2)
+    e = float(np.abs(cov[:, -1, :14, :14] - want).max() / np.abs(want).max())
+    print("zero gains: Sigma_K vs Phi S0 Phi' %.2e" % e)
+    assert e < 1e-12 and not cov[:, :, 14:, :].any() and not cov[:, :, :, 14:].any()
+    L, _ = tr.gains(d, p.K)
+    w = np.random.default_rng(1).uniform(0.0, 1e-6, 14)
+    Z = np.zeros((2, 14, 14))
+    c1, c3 = cr.propagate(d, p.K, L, Z, w), cr.propagate(d, p.K, L, Z, 3.0 * w)
+    assert c1[:, -1].any() and not c1[:, 0].any()
+    assert float(np.abs(c3[:, -1] - 3.0 * c1[:, -1]).max()) <= 1e-13 * float(np.abs(c3[:, -1]).max())
+    # and w adds to the transported S0: the recursion is affine
+    cs, cw = cr.propagate(d, p.K, L, S0), cr.propagate(d, p.K, L, S0, w)
+    assert float(np.abs(cw[:, -1] - cs[:, -1] - c1[:, -1]).max()) <= 1e-13 * float(np.abs(cw[:, -1]).max())
+    # only the symmetric part of S0 counts
+    A = np.random.default_rng(2).normal(size=(14, 14)) * 1e-7
+    assert float(np.abs(cr.propagate(d, p.K, L, S0 + (A - A.T)[None]) - cs).max()) <= 1e-14 * float(np.abs(cs).max())
+
+
+def _g_flight(p, xk, uk):
+    """the six path functions from flight_reference.report on a single sample"""
+    S, US = xk.reshape(1, 1, 1, 14), uk.reshape(1, 1, 1, -1)
+    z = np.zeros((1, 2, 14))
+    r = fr.report(p, z, S, US, z)[0]
+    return np.array([r[fr.IDX[cr.G_OF[n]]] for n in cr.MARGINS])
+
+
+def test_margin_gradients_against_central_differences_of_the_flight_reference():
+    p, par, x, u, s, d = _data()
+    h = 1e-6
+    worst = 0.0
+    for b in range(2):
+        for k in (1, 7, 23, p.K - 1):
+            xk, uk = x[b, k], u[b, k]
+            assert np.abs(cr.path_g(p, xk, uk) - _g_flight(p, xk, uk)).max() < 1e-15
+            c = cr.path_grad(p, xk, uk)
+            assert np.isfinite(c).all()
+            z = np.concatenate([xk, uk])
+            num = np.zeros_like(c)
+            for i in range(17):
+                zp, zm = z.copy(), z.copy()
+                zp[i] += h
+                zm[i] -= h
+                num[:, i] = (_g_flight(p, zp[:14], zp[14:]) - _g_flight(p, zm[:14], zm[14:])) / (2 * h)
+            worst = max(worst, float(np.abs(num - c).max()))
+    print("closed-form gradients vs central differences (h = 1e-6): %.2e" % worst)
+    assert worst < 1e-8     # O(h^2 g''') + O(eps / h) = 1e-12 + 1e-10, with room for the curvature of a norm near 1e-2
+    # a norm that is exactly zero has no gradient: the glide slope at the landing point
+    x0 = x[0, -1].copy()
+    x0[2:4] = 0.0
+    c = cr.path_grad(p, x0, u[0, -1])
+    assert np.isnan(c[1]).any() and np.isfinite(np.delete(c, 1, axis=0)).all()
+
+
+def test_report_columns():
+    p, par, x, u, s, d = _data()
+    L, _ = tr.gains(d, p.K)
+    S0 = np.stack([cr.handover_s0(x[b, 0])[0] for b in range(2)])
+    rep, cov, sig = cr.run(p, x, u, d, p.K, L, S0)
+    for b in range(2):
+        lam, V = np.linalg.eigh(cov[b, -1, 2:4, 2:4])
+        assert abs(rep[b, cr.IDX["ELL_A"]] - np.sqrt(lam[1])) <= 1e-12 * np.sqrt(lam[1])
+        assert abs(rep[b, cr.IDX["ELL_B"]] - np.sqrt(lam[0])) <= 1e-9 * np.sqrt(lam[1])
+        ang = rep[b, cr.IDX["ELL_ANG"]]
+        assert -np.pi / 2 < ang <= np.pi / 2
+        major = np.array([np.cos(ang), np.sin(ang)])
+        assert abs(abs(major @ V[:, 1]) - 1.0) < 1e-9
+        assert rep[b, cr.IDX["SIG_R"]] == np.sqrt(np.trace(cov[b, -1, 1:4, 1:4]))
+        assert rep[b, cr.IDX["SIG_PEAK"]] >= np.sqrt(np.trace(S0[b]))
+        assert np.array_equal(sig[b, :, 3], np.sqrt(cov[b, :, 3, 3]))
+    so = cr.run(p, x, u, d, p.K, np.zeros_like(L), S0)[0][:, cr.IDX["SIG_R"]]
+    print("SIG_R at the start %s, closed loop %s, open loop %s; S_THRUST %s; N_TMIN %s; N_TMAX %s; N_GLIDE %s"
+          % (np.sqrt(np.trace(S0[:, 1:4, 1:4], axis1=1, axis2=2)), rep[:, cr.IDX["SIG_R"]], so, rep[:, cr.IDX["S_THRUST"]],
+             rep[:, cr.IDX["N_TMIN"]], rep[:, cr.IDX["N_TMAX"]], rep[:, cr.IDX["N_GLIDE"]]))
+    assert np.all(rep[:, cr.IDX["SIG_R"]] < so)
+    assert np.all(rep[:, cr.IDX["S_THRUST"]] > 0) and np.isfinite(rep).all()
+    # zero gains: the commanded control never moves, so the thrust margins have no node
+    r0 = cr.run(p, x, u, d, p.K, np.zeros_like(L), S0)[0]
+    assert np.all(np.isposinf(r0[:, cr.IDX["N_TMIN"]])) and np.all(r0[:, cr.IDX["S_THRUST"]] == 0)
+    # a NaN in a tile poisons its own row only
+    dn = d.copy().reshape(2, p.K, -1, 14)
+    dn[1, 20, 3, 2] = np.nan
+    rn = cr.run(p, x, u, dn, p.K, L, S0)[0]
+    assert np.isnan(rn[1]).all() and np.array_equal(rn[0], rep[0])
+
+
+def test_header_binding_and_julia_carry_the_same_symbols():
+    from successiveconvexification_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "scvx.h")).read()
+    jl = open(os.path.join(ROOT, "julia", "ScvxAMD.jl")).read()
+    nargs = {"scvx_cov_propagate_f64": 13, "scvx_cov_propagate_f64_host": 13, "scvx_batch_cov": 10}
+    for sym, n in nargs.items():
+        m = re.search(r"\bint %s\(([^;]*?)\);" % sym, hdr, flags=re.S)
+        assert m, sym
+        assert len(m.group(1).split(",")) == n, sym
+        assert len(_lib.SIGNATURES[sym][1]) == n, sym
+        j = re.search(r"ccall\(\(:%s, LIB\), Cint,\s*\(([^)]*)\)" % sym, jl, flags=re.S)
+        assert j, sym
+        assert len([a for a in j.group(1).split(",") if a.strip()]) == n, sym
+    mac = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define SCVX_COV_([A-Z_]+) (\d+)", hdr)}
+    assert mac.pop("NREP") == 16 == _lib.COV_NREP == cr.NREP
+    assert mac == _lib.COV_INDEX == cr.IDX and _lib.COV_COLUMNS == cr.COLUMNS
+    for name, i in _lib.COV_INDEX.items():
+        assert int(re.search(r"const COV_%s = (\d+)" % name, jl).group(1)) == i
+    assert int(re.search(r"#define SCVX_ABI_VERSION (\d+)", hdr).group(1)) == 4 == _lib.ABI_VERSION
+    # outside install!(): that function's body is pinned to the reference's by test_abi_harness.py
+    assert jl.index("function covariance(b::Batch") < jl.index("function install!")
+    assert "covariance" not in jl[jl.index("function install!"):]
+
+
+def test_gaussian_handover():
+    from successiveconvexification_amd.montecarlo import gaussian_handover, handover_factor
+    p, par, x, u, s, d = _data()
+    S0, C = cr.handover_s0(x[0, 0])
+    whole = gaussian_handover(S0, 0, 12, 99)
+    assert whole.shape == (12, 14)
+    assert np.array_equal(gaussian_handover(S0, 5, 9, 99), whole[5:9])            # shards agree with the whole batch
+    assert np.array_equal(gaussian_handover(S0, 0, 12, 99), whole)                # deterministic
+    assert not np.array_equal(whole, gaussian_handover(S0, 0, 12, 100))
+    assert np.all(whole[:, 0] == 0.0) and whole[:, 1:].all()                      # the mass row of S0 is zero: exactly no mass offset
+    F = handover_factor(S0)                                                        # Cholesky of the 13 dispersed coordinates
+    assert np.abs(F @ F.T - S0).max() <= 1e-12 * np.abs(S0).max() and not F[0].any() and not F[:, 0].any()
+    v = np.zeros(14)
+    v[1:4] = 1e-3
+    Fe = handover_factor(np.outer(v, v))                                           # rank one: the eigen factor
+    assert np.abs(Fe @ Fe.T - np.outer(v, v)).max() <= 1e-12 * 1e-6
+    Sp = S0 + 1e-8 * np.eye(14)
+    Fp = handover_factor(Sp)                                                       # definite: Cholesky
+    assert np.allclose(Fp, np.tril(Fp)) and np.abs(Fp @ Fp.T - Sp).max() <= 1e-12 * np.abs(Sp).max()
+    sd = np.full(14, 2e-3)
+    assert np.array_equal(handover_factor(sd), np.diag(sd))
+    # sample covariance within six standard errors, every entry
+    N = 8192
+    z = gaussian_handover(Sp, 0, N, 3)
+    z = z - z.mean(axis=0)
+    Sh = z.T @ z / (N - 1)
+    dg = np.diag(Sp)
+    se = np.sqrt((np.outer(dg, dg) + Sp ** 2) / (N - 1))
+    print("gaussian_handover: worst entry %.2f standard errors" % (np.abs(Sh - Sp) / se).max())
+    assert np.all(np.abs(Sh - Sp) <= 6.0 * se)
+    with pytest.raises(ValueError):
+        gaussian_handover(np.zeros((3, 3)), 0, 2, 1)
+
+
+def test_dispersion_summary_and_cov_report():
+    from successiveconvexification_amd import _lib
+    from successiveconvexification_amd.dynamics import CovReport, _cov_dense, _cov_noise, _cov_s0
+    from successiveconvexification_amd.montecarlo import dispersion_summary
+    raw = np.arange(5 * 16, dtype=float).reshape(5, 16)
+    raw[:, _lib.COV_INDEX["N_RATE"]] = np.inf
+    raw[3, _lib.COV_INDEX["N_TMIN"]] = -2.0
+    r = CovReport(raw, sig=np.zeros((5, 3, 17)))
+    assert len(r) == 5 and r.covK is None and r.cov is None and r.sig.shape == (5, 3, 17)
+    for n, i in _lib.COV_INDEX.items():
+        assert np.array_equal(getattr(r, n), raw[:, i])
+    assert r.tightest()[3] == -2.0 and r.tightest()[0] == raw[0, _lib.COV_INDEX["N_MASS"]]
+    status = np.array([0, 0, 3, 0, 1])
+    sm = dispersion_summary(r, status)
+    assert sm["n"] == 5 and sm["converged"] == 3 and sm["counts"]["converged"] == 3 and sm["counts"]["solver"] == 1
+    assert sum(sm["counts"].values()) == 5
+    col = raw[[0, 1, 3], _lib.COV_INDEX["SIG_R"]]
+    assert sm["stats"]["SIG_R"] == {"min": col.min(), "median": float(np.median(col)), "p99": float(np.percentile(col, 99)), "max": col.max()}
+    assert sm["stats"]["N_TMIN"]["min"] == -2.0 and sm["stats"]["N_RATE"]["max"] == float("inf")
+    assert set(sm["stats"]) == set(_lib.COV_COLUMNS)
+    assert dispersion_summary(raw, np.ones(5, int))["stats"]["SIG_M"] is None
+    assert dispersion_summary(raw, status) == sm
+    with pytest.raises(ValueError):
+        dispersion_summary(raw, status[:4])
+    # the argument helpers of cov_propagate_batch / ScvxBatch.covariance
+    sd = np.arange(14.0)
+    assert _cov_s0(sd, 3).shape == (3, 14, 14) and np.array_equal(_cov_s0(sd, 3)[2], np.diag(sd ** 2))
+    assert np.array_equal(_cov_s0(np.eye(14), 2)[1], np.eye(14)) and _cov_s0(np.ones((2, 14, 14)), 2).flags.c_contiguous
+    with pytest.raises(ValueError):
+        _cov_s0(np.ones((3, 14, 14)), 2)
+    assert _cov_noise(None) is None and _cov_noise(2.0).tolist() == [2.0] * 14
+    with pytest.raises(ValueError):
+        _cov_noise(np.ones(3))
+    assert _cov_dense(True) == {"sig", "covK", "cov"} and _cov_dense(False) == set() and _cov_dense("sig") == {"sig"}
+    with pytest.raises(ValueError):
+        _cov_dense(["sigma"])
