@@ -689,16 +689,14 @@ int scvx_batch_flight_check(scvx_batch* b, int nsub, int mode, double* report, d
     rc = scvx::check_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, report);
     if (rc) return rc;
     const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14;
-    double *dr = nullptr, *df = nullptr;
-    SCVX_HIP(ctx, hipMalloc((void**)&dr, nr * 8));
-    hipError_t e = xfly ? hipMalloc((void**)&df, nx * 8) : hipSuccess;
+    scvx::DevBuf<double> dr, df;
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    hipError_t e = xfly ? hipMalloc((void**)&df.p, nx * 8) : hipSuccess;
     hipStream_t st = ctx->stream;
-    if (e == hipSuccess) e = scvx::launch_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, dr, df, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(report, dr, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df, nx * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = scvx::launch_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, dr.p, df.p, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dr);
-    if (df) (void)hipFree(df);
     if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_flight_check: ") + hipGetErrorString(e));
     return SCVX_OK;
 }
@@ -746,21 +744,20 @@ int scvx_batch_track_fly(scvx_batch* b, const double* q14, const double* rNU, co
     if ((rc = scvx::check_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->x, nsub, flags, b->x))) return rc;
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14, nu = (size_t)b->B * (b->K + 1) * b->NU;
-    double *dr = nullptr, *df = nullptr, *dc = nullptr, *d0 = nullptr;
+    scvx::DevBuf<double> dr, df, dc, d0;
     hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&dr, nr * 8);
-    if (e == hipSuccess && xfly) e = hipMalloc((void**)&df, nx * 8);
-    if (e == hipSuccess && ufly) e = hipMalloc((void**)&dc, nu * 8);
-    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0, (size_t)b->B * 14 * 8);
-    if (e == hipSuccess && dx0) e = hipMemcpyAsync(d0, dx0, (size_t)b->B * 14 * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = scvx::launch_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0, nsub, flags, dr, df, dc, st);
-    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df, nx * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && ufly) e = hipMemcpyAsync(ufly, dc, nu * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);
+    hipError_t e = hipMalloc((void**)&dr.p, nr * 8);
+    if (e == hipSuccess && xfly) e = hipMalloc((void**)&df.p, nx * 8);
+    if (e == hipSuccess && ufly) e = hipMalloc((void**)&dc.p, nu * 8);
+    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, (size_t)b->B * 14 * 8);
+    if (e == hipSuccess && dx0) e = hipMemcpyAsync(d0.p, dx0, (size_t)b->B * 14 * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = scvx::launch_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0.p, nsub, flags, dr.p, df.p, dc.p, st);
+    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && ufly) e = hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
     if (e == hipSuccess) e = e2;
-    for (double* p : {dr, df, dc, d0})
-        if (p) (void)hipFree(p);
     if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_fly: ") + hipGetErrorString(e));
     return SCVX_OK;
 }
@@ -777,25 +774,24 @@ int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const do
     const size_t n = 14 + b->NU;
     const size_t n0 = (size_t)b->B * 196, nr = (size_t)b->B * SCVX_COV_NREP, ns = (size_t)b->B * (b->K + 1) * n, nk = (size_t)b->B * n * n,
                  nc = (size_t)b->B * (b->K + 1) * n * n;
-    double *d0 = nullptr, *dr = nullptr, *ds = nullptr, *dk = nullptr, *dc = nullptr;
+    scvx::DevBuf<double> d0, dr, ds, dk, dc;
     hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&d0, n0 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dr, nr * 8);
-    if (e == hipSuccess && sig) e = hipMalloc((void**)&ds, ns * 8);
-    if (e == hipSuccess && covK) e = hipMalloc((void**)&dk, nk * 8);
-    if (e == hipSuccess && cov) e = hipMalloc((void**)&dc, nc * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d0, S0, n0 * 8, hipMemcpyHostToDevice, st);
+    hipError_t e = hipMalloc((void**)&d0.p, n0 * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
+    if (e == hipSuccess && sig) e = hipMalloc((void**)&ds.p, ns * 8);
+    if (e == hipSuccess && covK) e = hipMalloc((void**)&dk.p, nk * 8);
+    if (e == hipSuccess && cov) e = hipMalloc((void**)&dc.p, nc * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = b->deriv_f ? scvx::launch_cov_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, d0, w14, dr, ds, dk, dc, st)
-                       : scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, d0, w14, dr, ds, dk, dc, st);
-    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && sig) e = hipMemcpyAsync(sig, ds, ns * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && covK) e = hipMemcpyAsync(covK, dk, nk * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && cov) e = hipMemcpyAsync(cov, dc, nc * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);
+        e = b->deriv_f
+                ? scvx::launch_cov_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, d0.p, w14, dr.p, ds.p, dk.p, dc.p, st)
+                : scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, d0.p, w14, dr.p, ds.p, dk.p, dc.p, st);
+    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && sig) e = hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && covK) e = hipMemcpyAsync(covK, dk.p, nk * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && cov) e = hipMemcpyAsync(cov, dc.p, nc * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
     if (e == hipSuccess) e = e2;
-    for (double* p : {d0, dr, ds, dk, dc})
-        if (p) (void)hipFree(p);
     if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_cov: ") + hipGetErrorString(e));
     return SCVX_OK;
 }

@@ -23,7 +23,7 @@
 
 namespace scvx {
 
-// the constants of the path functions, formed as launch_flight forms them, and the process noise
+// the constants of the path functions it reads (path_constants) and the process noise
 struct CovK {
     double mdry, tggs, sqcm, omMax, Tmax, Tmin;
     double w[14];
@@ -31,9 +31,7 @@ struct CovK {
 
 typedef double cov_v4f64 __attribute__((ext_vector_type(4)));
 
-// NaN-propagating running extrema and square root of a variance (a rounded variance of -1e-40 is 0, a NaN stays a NaN)
-__device__ __forceinline__ double cov_max(double a, double v) { return (v > a || v != v) ? v : a; }
-__device__ __forceinline__ double cov_min(double a, double v) { return (v < a || v != v) ? v : a; }
+// square root of a variance (a rounded variance of -1e-40 is 0, a NaN stays a NaN)
 __device__ __forceinline__ double cov_sd(double v) { return v > 0.0 ? sqrt(v) : (v != v ? v : 0.0); }
 
 // c' Sigma c for a gradient with (up to) three nonzeros c0, c1, c2 at i0, i1, i2
@@ -132,19 +130,19 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
 #pragma unroll
             for (int i = 0; i < 14; i++) tr += Sl[i * n + i];
             bad = fma(tr, 0.0, bad);
-            acc0 = cov_max(acc0, cov_sd(tr));
+            acc0 = nan_max(acc0, cov_sd(tr));
         } else if (k > 0 && lane < 6) {
             if (lane == 1) {
                 const double s = cov_sd(Sl[0]);
-                if (!(s == 0.0)) acc0 = cov_min(acc0, -(c.mdry - pv0) / s);
+                if (!(s == 0.0)) acc0 = nan_min(acc0, -(c.mdry - pv0) / s);
             } else if (lane == 5) {
                 const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
                 if (!(nr == 0.0)) {
                     const double s = cov_sd(cov_quad3(Sl, n, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
-                    acc2 = cov_max(acc2, s);
+                    acc2 = nan_max(acc2, s);
                     if (!(s == 0.0)) {
-                        acc0 = cov_min(acc0, -(nr - c.Tmax) / s);
-                        acc1 = cov_min(acc1, -(c.Tmin - nr) / s);
+                        acc0 = nan_min(acc0, -(nr - c.Tmax) / s);
+                        acc1 = nan_min(acc1, -(c.Tmin - nr) / s);
                     }
                 }
             } else {
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
                         q = cov_quad3(Sl, n, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
                     }
                     const double s = cov_sd(q);
-                    if (!(s == 0.0)) acc0 = cov_min(acc0, -g / s);
+                    if (!(s == 0.0)) acc0 = nan_min(acc0, -g / s);
                 }
             }
         }
@@ -316,15 +314,8 @@ constexpr bool kCovMfmaDefault = false;   // the lane form, which the parity tes
 template <typename DS>
 static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv, const double* gain,
                                const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
-    const scvx_problem& P = ctx->prob;
-    const double d2r = M_PI / 180.0;
-    CovK c{};
-    c.mdry = P.mdry;
-    c.tggs = std::tan(P.gammaGs * d2r);
-    c.sqcm = std::sqrt((1.0 - std::cos(P.thetaMax * d2r)) / 2.0);
-    c.omMax = P.omMax;
-    c.Tmax = P.Tmax;
-    c.Tmin = P.Tmin;
+    const PathK pk = path_constants(ctx->prob);
+    CovK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}};
     for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
     // SCVX_COV_MFMA = 0 / 1 forces the lane-per-element / matrix-pipe form of the two n-deep products (A/B: tools/bench_cov.py)
     bool mf = kCovMfmaDefault;
@@ -371,15 +362,6 @@ int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const v
     return check_cov_noise(ctx, w);
 }
 
-namespace {
-struct CovDev {
-    double* p = nullptr;
-    ~CovDev() {
-        if (p) (void)hipFree(p);
-    }
-};
-}  // namespace
-
 }  // namespace scvx
 
 extern "C" {
@@ -404,7 +386,7 @@ int scvx_cov_propagate_f64_host(scvx_ctx* ctx, int B, int K, const double* x, co
     const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
                  ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, ns = (size_t)B * (K + 1) * n,
                  nk = (size_t)B * n * n, nc = (size_t)B * (K + 1) * n * n;
-    scvx::CovDev dx, du, dd, dg, d0, dr, ds, dk, dc;
+    scvx::DevBuf<double> dx, du, dd, dg, d0, dr, ds, dk, dc;
     SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));

@@ -47,6 +47,27 @@ hipError_t launch_linearize_f32(const scvx_ctx* ctx, int B, int K, const float* 
 hipError_t launch_propagate_f32(const scvx_ctx* ctx, int B, int K, const float* x, const float* u, const float* sigma,
                                 float dt, float* xnext, hipStream_t st);
 
+// the constants of the path functions, formed as oracle/socp.py:99-101,188 / rocketland.jl:63-65 form them (scvx_flight.hip)
+struct PathK {
+    double rIf[3], vIf[3], qBIf[4], wBf[3];
+    double mdry, tggs, sqcm, omMax, Tmax, Tmin, inv_cosd, vmax, finmxf;
+    int dp;   // SCVX_MODEL_DPMAX
+};
+PathK path_constants(const scvx_problem& P);
+
+// NaN-propagating running extrema (fmax / fmin alone drop a NaN): once NaN, always NaN
+__device__ __forceinline__ double nan_max(double a, double v) { return (v > a || v != v) ? v : a; }
+__device__ __forceinline__ double nan_min(double a, double v) { return (v < a || v != v) ? v : a; }
+
+// a device buffer of one host-side call, freed when the call returns
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
 // Flight check (scvx_flight.hip): report[B][SCVX_FLIGHT_NREP], xfly[B][K+1][14] or nullptr; one lane per trajectory, dt = 1 / (K + 1).
 hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, int nsub,
                          int mode, double* report, double* xfly, hipStream_t st);
@@ -55,7 +76,7 @@ int check_flight(scvx_ctx* ctx, int B, int K, const void* x, const void* u, cons
 
 // Plan tracking (scvx_track.hip).  Gains: one wavefront per trajectory over the derivative tiles (double, or float as
 // scvx_batch_set_linearization_f32 stores them); gain[B][K][NU][14+NU], p0[B][14+NU][14+NU] or nullptr; q / r / qf are host arrays.
-// Closed-loop flight: one lane per trajectory; dx0[B][14], xfly[B][K+1][14], ufly[B][K+1][NU] or nullptr.
+// Closed-loop flight (the flight check's kernel with TRACK set, scvx_flight.hip): dx0[B][14], xfly[B][K+1][14], ufly[B][K+1][NU] or nullptr.
 hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, const double* deriv, const double* q, const double* r, const double* qf,
                               double* gain, double* p0, hipStream_t st);
 hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float* deriv, const double* q, const double* r,

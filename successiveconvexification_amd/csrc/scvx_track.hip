@@ -12,13 +12,10 @@
 // contiguous run, coalesced) while step k computes and stored to LDS behind the step's last barrier.  DS is the tiles' storage
 // type (double, or float with scvx_batch_set_linearization_f32: widened on load).
 //
-// track_fly_kernel: ONE LANE PER TRAJECTORY, the walk of flight_kernel (scvx_flight.hip: the same RK4 / first-order-hold
-// arithmetic, samples, maxima and NaN handling) with the feedback u_{k+1} = ubar_{k+1} + L_k [x_k - xbar_k; u_k - ubar_k] formed at
-// every node from the FLOWN state and the APPLIED control, an optional clamp of the commanded thrust / fin norms, and an initial
-// state offset per trajectory.  The substep is repeated here, not shared, so that flight_kernel stays bit for bit what it is.
+// The closed-loop flight itself is the TRACK instantiation of fly_kernel (scvx_flight.hip, launch_track_fly): the walk of the flight
+// check with the feedback formed at every node.  This file keeps the gains kernel, the argument checks and the entry points.
 #include <cmath>
 #include <cstdlib>
-#include <limits>
 #include "scvx_internal.hpp"
 
 namespace scvx {
@@ -244,221 +241,6 @@ hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// the constants of the path functions, formed as launch_flight forms them (oracle/socp.py:99-101,188 / rocketland.jl:63-65)
-struct TrackK {
-    double rIf[3], vIf[3], qBIf[4], wBf[3];
-    double mdry, tggs, sqcm, omMax, Tmax, Tmin, inv_cosd, vmax, finmxf;
-    int dp;   // SCVX_MODEL_DPMAX
-};
-
-// NaN-propagating running maximum (fmax alone drops a NaN): once NaN, always NaN
-__device__ __forceinline__ double tmax(double a, double v) { return (v > a || v != v) ? v : a; }
-
-template <bool AERO, bool FIN, bool TRQ>
-__global__ __launch_bounds__(64) void track_fly_kernel(DynPK<double, TRQ> p, TrackK c, int B, int K, const double* __restrict__ x,
-                                                       const double* __restrict__ u, const double* __restrict__ sigma,
-                                                       const double* __restrict__ gain, const double* __restrict__ dx0, double dt,
-                                                       int nsub, int flags, double* __restrict__ report, double* __restrict__ xfly,
-                                                       double* __restrict__ ufly) {
-    typedef double R;
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    constexpr int NU = FIN ? 5 : 3;
-    constexpr int n = 14 + NU;
-    const R* xb = x + (size_t)b * (K + 1) * 14;
-    const R* ub = u + (size_t)b * (K + 1) * NU;
-    const R* gb = gain + (size_t)b * K * NU * n;
-    R* xf = xfly ? xfly + (size_t)b * (K + 1) * 14 : nullptr;
-    R* uf = ufly ? ufly + (size_t)b * (K + 1) * NU : nullptr;
-    const R sig = sigma[b];
-    const R h = dt / R(nsub);
-    const R inv_n = R(1.0) / R(nsub);
-    const R ninf = -std::numeric_limits<double>::infinity();
-    const bool clamp = (flags & SCVX_TRACK_CLAMP) != 0;
-    R xs[14], ukv[NU], upv[NU];
-#pragma unroll
-    for (int i = 0; i < 14; i++) xs[i] = xb[i];
-    if (dx0) {
-#pragma unroll
-        for (int i = 0; i < 14; i++) xs[i] += dx0[(size_t)b * 14 + i];
-    }
-#pragma unroll
-    for (int j = 0; j < NU; j++) upv[j] = ub[j];
-    if (xf) {
-#pragma unroll
-        for (int i = 0; i < 14; i++) xf[i] = xs[i];
-    }
-    if (uf) {
-#pragma unroll
-        for (int j = 0; j < NU; j++) uf[j] = upv[j];
-    }
-    R gap = R(0.0), bad = R(0.0);   // bad: 0 while every sampled state (and every node difference) is finite, else NaN
-    R g_mass = ninf, g_glide = ninf, g_tilt = ninf, g_rate = ninf, g_tmax = ninf, g_tmin = ninf, g_gimbal = ninf, g_dp = ninf,
-      g_fin = ninf, qn = R(0.0);
-    for (int k = 0; k < K; k++) {
-        // ---- node k: the next node's control from the flown state and the applied control ----
-        {
-            R z[n];
-#pragma unroll
-            for (int i = 0; i < 14; i++) z[i] = xs[i] - xb[(size_t)k * 14 + i];
-#pragma unroll
-            for (int j = 0; j < NU; j++) {
-                z[14 + j] = upv[j] - ub[(size_t)k * NU + j];
-                ukv[j] = upv[j];
-            }
-            const R* g = gb + (size_t)k * NU * n;
-#pragma unroll
-            for (int j = 0; j < NU; j++) {
-                R a = ub[(size_t)(k + 1) * NU + j];
-#pragma unroll
-                for (int i = 0; i < n; i++) a = fma(g[j * n + i], z[i], a);
-                upv[j] = a;
-            }
-            if (clamp) {
-                const R un = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
-                R f = R(1.0);
-                if (un > c.Tmax) f = c.Tmax / un;
-                else if (un < c.Tmin && un > R(0.0)) f = c.Tmin / un;
-#pragma unroll
-                for (int j = 0; j < 3; j++) upv[j] *= f;
-                if (FIN) {
-                    const R fn = sqrt(upv[3] * upv[3] + upv[4] * upv[4]);
-                    const R ff = fn > c.finmxf ? c.finmxf / fn : R(1.0);
-                    upv[3] *= ff;
-                    upv[4] *= ff;
-                }
-            }
-            if (uf) {
-#pragma unroll
-                for (int j = 0; j < NU; j++) uf[(size_t)(k + 1) * NU + j] = upv[j];
-            }
-        }
-        for (int s = 0; s <= nsub; s++) {
-            // ---- sample: state xs, control of the hold at s / nsub (the stage-0 control of substep s) ----
-            const R lk0 = R(s) * inv_n;
-            R us[NU];
-#pragma unroll
-            for (int j = 0; j < NU; j++) us[j] = fma(ukv[j], R(1.0) - lk0, upv[j] * lk0);
-            const R un = sqrt(us[0] * us[0] + us[1] * us[1] + us[2] * us[2]);
-            g_tmax = tmax(g_tmax, un - c.Tmax);
-            g_tmin = tmax(g_tmin, c.Tmin - un);
-            g_gimbal = tmax(g_gimbal, un - us[0] * c.inv_cosd);
-            if (FIN) g_fin = tmax(g_fin, sqrt(us[3] * us[3] + us[4] * us[4]) - c.finmxf);
-            g_mass = tmax(g_mass, c.mdry - xs[0]);
-            g_glide = tmax(g_glide, c.tggs * sqrt(xs[2] * xs[2] + xs[3] * xs[3]) - xs[1]);
-            g_tilt = tmax(g_tilt, sqrt(xs[9] * xs[9] + xs[10] * xs[10]) - c.sqcm);
-            g_rate = tmax(g_rate, sqrt(xs[11] * xs[11] + xs[12] * xs[12] + xs[13] * xs[13]) - c.omMax);
-            if (c.dp) g_dp = tmax(g_dp, sqrt(xs[4] * xs[4] + xs[5] * xs[5] + xs[6] * xs[6]) - c.vmax);
-            qn = tmax(qn, fabs(sqrt(xs[7] * xs[7] + xs[8] * xs[8] + xs[9] * xs[9] + xs[10] * xs[10]) - R(1.0)));
-#pragma unroll
-            for (int i = 0; i < 14; i++) bad = fma(xs[i], R(0.0), bad);
-            if (s == nsub) break;
-            // ---- one RK4 substep, as propagate_kernel and flight_kernel take it ----
-            R xa[14], xt[14];
-#pragma unroll
-            for (int i = 0; i < 14; i++) {
-                xa[i] = xs[i];
-                xt[i] = xs[i];
-            }
-#pragma unroll
-            for (int stg = 0; stg < 4; stg++) {
-                const R lkp = (R(s) + (stg == 0 ? R(0.0) : (stg == 3 ? R(1.0) : R(0.5)))) * inv_n;
-                const R lkm = R(1.0) - lkp;
-                R uu[NU];
-#pragma unroll
-                for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
-                R g[14];
-                rhs_only<AERO, FIN, TRQ>(p, xt, uu, g);
-                const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
-                const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
-#pragma unroll
-                for (int i = 0; i < 14; i++) {
-                    const R dx = sig * g[i];
-                    xa[i] = fma(wacc, dx, xa[i]);
-                    if (stg < 3) xt[i] = fma(wnext, dx, xs[i]);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 14; i++) xs[i] = xa[i];
-        }
-        // ---- node k + 1: the flown state against the planned one ----
-        const R* xn = xb + (size_t)(k + 1) * 14;
-#pragma unroll
-        for (int i = 0; i < 14; i++) {
-            const R d = xs[i] - xn[i];
-            gap = tmax(gap, fabs(d));
-            bad = fma(d, R(0.0), bad);
-        }
-        if (xf) {
-#pragma unroll
-            for (int i = 0; i < 14; i++) xf[(size_t)(k + 1) * 14 + i] = xs[i];
-        }
-    }
-    R mr = R(0.0), mv = R(0.0), mq = R(0.0), mw = R(0.0);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const R dr = xs[1 + i] - c.rIf[i], dv = xs[4 + i] - c.vIf[i], dw = xs[11 + i] - c.wBf[i];
-        mr = fma(dr, dr, mr); mv = fma(dv, dv, mv); mw = fma(dw, dw, mw);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const R dq = xs[7 + i] - c.qBIf[i]; mq = fma(dq, dq, mq); }
-    R* o = report + (size_t)b * SCVX_FLIGHT_NREP;
-    o[SCVX_FLIGHT_GAP] = gap + bad;
-    o[SCVX_FLIGHT_MISS_R] = sqrt(mr) + bad;
-    o[SCVX_FLIGHT_MISS_V] = sqrt(mv) + bad;
-    o[SCVX_FLIGHT_MISS_Q] = sqrt(mq) + bad;
-    o[SCVX_FLIGHT_MISS_W] = sqrt(mw) + bad;
-    o[SCVX_FLIGHT_MASS_END] = xs[0];
-    o[SCVX_FLIGHT_G_MASS] = g_mass + bad;
-    o[SCVX_FLIGHT_G_GLIDE] = g_glide + bad;
-    o[SCVX_FLIGHT_G_TILT] = g_tilt + bad;
-    o[SCVX_FLIGHT_G_RATE] = g_rate + bad;
-    o[SCVX_FLIGHT_G_TMAX] = g_tmax;
-    o[SCVX_FLIGHT_G_TMIN] = g_tmin;
-    o[SCVX_FLIGHT_G_GIMBAL] = g_gimbal;
-    o[SCVX_FLIGHT_G_DP] = c.dp ? g_dp + bad : ninf;
-    o[SCVX_FLIGHT_G_FIN] = g_fin;
-    o[SCVX_FLIGHT_QNORM] = qn + bad;
-}
-
-hipError_t launch_track_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
-                            const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly, hipStream_t st) {
-    const scvx_problem& P = ctx->prob;
-    const double d2r = M_PI / 180.0;
-    TrackK c{};
-    for (int i = 0; i < 3; i++) { c.rIf[i] = P.rIf[i]; c.vIf[i] = P.vIf[i]; c.wBf[i] = P.wBf[i]; }
-    for (int i = 0; i < 4; i++) c.qBIf[i] = P.qBIf[i];
-    c.mdry = P.mdry;
-    c.tggs = std::tan(P.gammaGs * d2r);
-    c.sqcm = std::sqrt((1.0 - std::cos(P.thetaMax * d2r)) / 2.0);
-    c.omMax = P.omMax;
-    c.Tmax = P.Tmax;
-    c.Tmin = P.Tmin;
-    c.inv_cosd = 1.0 / std::cos(P.deltaMax * d2r);
-    c.dp = (P.model_flags & SCVX_MODEL_DPMAX) ? 1 : 0;
-    c.vmax = c.dp ? std::sqrt(2.0 * P.dpMax / P.rho) : 0.0;
-    c.finmxf = P.finmxf;
-    const double dt = 1.0 / (K + 1);
-    const dim3 g((unsigned)((B + 63) / 64)), blk(64);
-    const DynP<double> dp(ctx->dyn);
-#define SCVX_TRACK_FLY(A, F, T, par) \
-    hipLaunchKernelGGL((track_fly_kernel<A, F, T>), g, blk, 0, st, par, c, B, K, x, u, sigma, gain, dx0, dt, nsub, flags, report, xfly, ufly)
-    if (ctx->dyn.trq) {
-        const DynPT<double> dpt(ctx->dyn);
-        if (ctx->dyn.fin) SCVX_TRACK_FLY(true, true, true, dpt);
-        else SCVX_TRACK_FLY(true, false, true, dpt);
-    } else if (ctx->dyn.fin) {
-        if (ctx->dyn.aero) SCVX_TRACK_FLY(true, true, false, dp);
-        else SCVX_TRACK_FLY(false, true, false, dp);
-    } else if (ctx->dyn.aero)
-        SCVX_TRACK_FLY(true, false, false, dp);
-    else
-        SCVX_TRACK_FLY(false, false, false, dp);
-#undef SCVX_TRACK_FLY
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
 int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const double* qf) {
     if (!ctx) return SCVX_ERR_ARG;
     if (!q || !r || !qf) return fail(ctx, SCVX_ERR_ARG, "track: null weight array (q[14], r[NU], qf[14])");
@@ -493,15 +275,6 @@ int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, c
     return SCVX_OK;
 }
 
-namespace {
-struct Dev {
-    double* p = nullptr;
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-};
-}  // namespace
-
 }  // namespace scvx
 
 extern "C" {
@@ -522,7 +295,7 @@ int scvx_track_gains_f64_host(scvx_ctx* ctx, int B, int K, const double* deriv, 
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     const int NU = scvx_control_dim(ctx), n = 14 + NU;
     const size_t nd = (size_t)B * K * 14 * (14 + 2 * NU + 1), ng = (size_t)B * K * NU * n, np = (size_t)B * n * n;
-    scvx::Dev dd, dg, dp;
+    scvx::DevBuf<double> dd, dg, dp;
     SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
     if (p0) SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
@@ -554,7 +327,7 @@ int scvx_track_fly_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const 
     const int NU = scvx_control_dim(ctx), n = 14 + NU;
     const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP,
                  ng = (size_t)B * K * NU * n;
-    scvx::Dev dx, du, ds, dg, d0, dr, df, dc;
+    scvx::DevBuf<double> dx, du, ds, dg, d0, dr, df, dc;
     SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
