@@ -335,6 +335,63 @@ int scvx_cov_propagate_f64_host(scvx_ctx *ctx, int B, int K, const double *x, co
                                 const double *gain, const double *S0, const double *w14, double *report, double *sig,
                                 double *covK, double *cov);
 
+/* ---- navigation-error (LQG) covariance analysis: the closed loop flown on an ESTIMATE, to first order -----------------------
+ * Everything above feeds the tracking law the true state.  A vehicle feeds it a navigation estimate xhat_k whose error is correlated
+ * from node to node, is corrected by measurements and is driven by the same disturbances that move the truth; the lump w of
+ * scvx_cov_propagate_f64 cannot express that.  This call propagates the joint covariance of truth dispersion and navigation error.
+ * Notation as above (NU, n = 14 + NU, z_k, F_k, G_k, L_k, M_k = F_k + G_k L_k; A_k = the first 14 columns of the tile), and
+ *     eps_k  = x_k - xhat_k (14)       the navigation error BEFORE the measurement at node k
+ *     zeta_k = [z_k; eps_k]            of size N = n + 14 (31, or 33 with fins)
+ *     Xi_k   = Cov(zeta_k),  Xi_0 = blockdiag(S0, 0_NU, N0): truth dispersion and navigation error independent at the handover
+ *     y_k    = H x_k + v_k             the measurement at nodes k = 0..K-1:  H [m][14], 0 <= m <= 14, Cov v = diag(rm), rm > 0;
+ *                                      H and rm are HOST arrays shared by the batch; m = 0 (H, rm NULL): inertial propagation only
+ * Per node k = 0..K-1:
+ *   1. update (skipped when m = 0):  P = Xi[eps eps],  S = H P H' + diag(rm),  Kf = P H' S^-1 (Cholesky of S),  J = I - Kf H,
+ *          Xi+ = U Xi U' + blockdiag(0_n, Kf diag(rm) Kf'),  U = blockdiag(I_n, J)        (the Joseph form: the short form
+ *          (I - Kf H) P loses positivity)
+ *   2. law:  u_{k+1} = ubar_{k+1} + L_k [(x_k - eps+_k) - xbar_k; u_k - ubar_k]        -- the law is fed the UPDATED estimate
+ *   3. time step:  Xi_{k+1} = T_k Xi+ T_k' + W,   T_k = [[M_k, -G_k L_k[:, 0:14]], [0, A_k]],   W = diag(w) in all four of the
+ *          xx, x eps, eps x and eps eps blocks: the filter propagates its estimate with the plan's model and the applied control, so
+ *          the disturbance the truth receives is exactly what the estimate misses, and the control cancels in eps to first order.
+ *          Symmetrised as above: each pair from both of its triangles.
+ * Limits: FIRST ORDER about the plan; Kf is the optimal gain for the stated model (no mismodelling study); no measurement at node K;
+ * the clamp is not modelled; the quaternion's norm direction is a coordinate like any other.  Only the symmetric parts of S0 and N0
+ * are used; that they are positive semi-definite is the caller's responsibility.
+ *
+ * report [B][SCVX_COV_NREP]: the sixteen SCVX_COV_* columns above with unchanged definitions, read off the z block of Xi.
+ * navrep [B][SCVX_NAV_NREP]: */
+#define SCVX_NAV_NREP 8
+#define SCVX_NAV_M 0       /* sqrt of the block traces of Xi_K[eps eps], the navigation error at the landing: mass,          */
+#define SCVX_NAV_R 1       /* position,                                                                                    */
+#define SCVX_NAV_V 2       /* velocity,                                                                                    */
+#define SCVX_NAV_Q 3       /* attitude,                                                                                    */
+#define SCVX_NAV_W 4       /* rate (the block layout of SCVX_COV_SIG_*)                                                    */
+#define SCVX_NAV_PEAK 5    /* max over nodes 0..K of sqrt(trace Xi_k[eps eps]) (before the update at the node)             */
+#define SCVX_NAV_EST_R 6   /* sqrt of the r / v block trace of Cov(xhat_K - xbar_K) = Sigma_xx - C - C' + P, C = Xi_K[x eps]: */
+#define SCVX_NAV_EST_V 7   /* the miss the vehicle BELIEVES it has                                                          */
+/* x, u, deriv, gain, S0, w14 as scvx_cov_propagate_f64; N0 [B][14][14]; m, H [m][14], rm [m] as above (host arrays in both forms).
+ * Optional dense outputs (NULL = not wanted): sig [B][K+1][n] and navsig [B][K+1][14] = sqrt(diag Xi_k) of the z and the eps block;
+ * kf [B][K][14][m] = the filter gains (not touched when m = 0); joint [B][K+1][N][N] = every Xi_k, before the update at its node.
+ * A non-finite tile, gain, S0 or N0 entry makes every column of its own trajectory's two reports NaN and cannot disturb another
+ * trajectory.  The _f64 form is asynchronous on the context's stream.  SCVX_ERR_ARG for everything scvx_cov_propagate_f64 refuses, a
+ * null N0 or navrep, m outside [0, 14], m > 0 with a null H or rm, an rm <= 0 or non-finite, a non-finite H. */
+int scvx_nav_cov_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                     const double *gain_dev, const double *S0_dev, const double *N0_dev, int m, const double *H, const double *rm,
+                     const double *w14, double *report_dev, double *navrep_dev, double *sig_dev, double *navsig_dev,
+                     double *kf_dev, double *joint_dev);
+int scvx_nav_cov_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv, const double *gain,
+                          const double *S0, const double *N0, int m, const double *H, const double *rm, const double *w14,
+                          double *report, double *navrep, double *sig, double *navsig, double *kf, double *joint);
+/* scvx_track_fly_f64 with the law fed an estimate: nav [B][K][14] is the error eps+_k of the estimate at node k, and the deviation
+ * is formed as z = [(x_fly - nav_k) - xbar_k; u_k - ubar_k], so an all-zero nav reproduces scvx_track_fly_f64 bit for bit.  nav must
+ * not be NULL (SCVX_ERR_ARG): without one, call scvx_track_fly_f64.  Everything else as there. */
+int scvx_track_fly_nav_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                           const double *gain_dev, const double *dx0_dev, const double *nav_dev, int nsub, int flags,
+                           double *report_dev, double *xfly_dev, double *ufly_dev);
+int scvx_track_fly_nav_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *sigma,
+                                const double *gain, const double *dx0, const double *nav, int nsub, int flags, double *report,
+                                double *xfly, double *ufly);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -464,6 +521,15 @@ int scvx_batch_track_fly(scvx_batch *b, const double *q14, const double *rNU, co
  * scvx_batch_flight_check.  Synchronises. */
 int scvx_batch_cov(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0, const double *w14,
                    double *report, double *sig, double *covK, double *cov);
+
+/* The two navigation calls above on the batch's current accepted iterate and its own derivative tiles (float tiles are widened on
+ * load), under the gains of the weights q14 / rNU / qf14.  S0, N0 [B][14][14], H, rm, w14, nav [B][K][14], dx0 and every output are
+ * host arrays; any output may be NULL.  The batch is left untouched, as by scvx_batch_flight_check.  Synchronises. */
+int scvx_batch_nav_cov(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0, const double *N0,
+                       int m, const double *H, const double *rm, const double *w14, double *report, double *navrep, double *sig,
+                       double *navsig, double *kf, double *joint);
+int scvx_batch_track_fly_nav(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *dx0,
+                             const double *nav, int nsub, int flags, double *report, double *xfly, double *ufly);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

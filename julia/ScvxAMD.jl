@@ -440,6 +440,109 @@ cov_propagate_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr
         (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), report_dev, sig_dev, covK_dev, cov_dev), "scvx_cov_propagate_f64")
 
+# ---- navigation-error (LQG) covariance analysis (new): the closed loop flown on an estimate, to first order --------------------
+# include/scvx.h, "navigation-error (LQG) covariance analysis".  S0, N0 are 14 x 14 x B; H is 14 x m (column-major == [m][14]) or
+# nothing (no measurement), rm a scalar or m variances; the reports are COV_NREP x B and NAV_NREP x B (rows NAV_* + 1); dense outputs:
+# sig n x (K+1) x B, navsig 14 x (K+1) x B, kf m x 14 x K x B, joint N x N x (K+1) x B with N = n + 14.
+const NAV_NREP = 8    # SCVX_NAV_NREP
+const NAV_M = 0; const NAV_R = 1; const NAV_V = 2; const NAV_Q = 3; const NAV_W = 4; const NAV_PEAK = 5; const NAV_EST_R = 6; const NAV_EST_V = 7
+
+function _nav_model(H, rm)
+    H === nothing && return 0, nothing, nothing
+    size(H, 1) == 14 || error("H must be 14 x m (one column per measurement)")
+    m = size(H, 2)
+    return m, Matrix{Float64}(H), _track_w(rm, m)
+end
+
+# the current accepted iterate of a batch under its own LQR gains: (report, navrep, sig, navsig, kf, joint)
+function navigation(b::Batch, S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm; w=nothing, q=1.0, r=1.0, qf=100.0, dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx)); n = 14 + NU; N = n + 14
+    (size(S0) == (14, 14, b.B) && size(N0) == (14, 14, b.B)) || error("S0 and N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    report = Matrix{Float64}(undef, COV_NREP, b.B)
+    navrep = Matrix{Float64}(undef, NAV_NREP, b.B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, b.B) : nothing
+    navsig = dense ? Array{Float64,3}(undef, 14, K + 1, b.B) : nothing
+    kf = dense && m > 0 ? Array{Float64,4}(undef, m, 14, K, b.B) : nothing
+    joint = dense ? Array{Float64,4}(undef, N, N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv check(b.cache.ctx, ccall((:scvx_batch_nav_cov, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), report, navrep,
+        _cov_opt(sig), _cov_opt(navsig), _cov_opt(kf), _cov_opt(joint)), "scvx_batch_nav_cov")
+    return report, navrep, sig, navsig, kf, joint
+end
+
+# any plans (host arrays), as covariance(cache, ...)
+function navigation(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                    S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm; w=nothing, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); NU = size(u, 1); n = 14 + NU; N = n + 14
+    (size(S0) == (14, 14, B) && size(N0) == (14, 14, B)) || error("S0 and N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    navrep = Matrix{Float64}(undef, NAV_NREP, B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, B) : nothing
+    navsig = dense ? Array{Float64,3}(undef, 14, K + 1, B) : nothing
+    kf = dense && m > 0 ? Array{Float64,4}(undef, m, 14, K, B) : nothing
+    joint = dense ? Array{Float64,4}(undef, N, N, K + 1, B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv check(cache.ctx, ccall((:scvx_nav_cov_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), report, navrep, _cov_opt(sig),
+        _cov_opt(navsig), _cov_opt(kf), _cov_opt(joint)), "scvx_nav_cov_f64_host")
+    return report, navrep, sig, navsig, kf, joint
+end
+
+# the same on device pointers, asynchronous on the context's stream; H, rm and w stay host arrays (or nothing)
+nav_cov_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+             S0_dev::Ptr{Cdouble}, N0_dev::Ptr{Cdouble}, m::Int, H::Union{Nothing,Matrix{Float64}}, rm::Union{Nothing,Vector{Float64}},
+             w::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble}, navrep_dev::Ptr{Cdouble}, sig_dev::Ptr{Cdouble},
+             navsig_dev::Ptr{Cdouble}, kf_dev::Ptr{Cdouble}, joint_dev::Ptr{Cdouble}) =
+    GC.@preserve H rm w check(cache.ctx, ccall((:scvx_nav_cov_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, _cov_opt(H), _cov_opt(rm), _cov_opt(w), report_dev, navrep_dev,
+        sig_dev, navsig_dev, kf_dev, joint_dev), "scvx_nav_cov_f64")
+
+# closed-loop flight with the law fed an estimate: nav 14 x K x B, the estimate's error at node k (zeros: track bit for bit)
+function track_nav(b::Batch, nav::Array{Float64,3}; dx0::Union{Nothing,Matrix{Float64}}=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0,
+                   clamp::Bool=false, dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    size(nav) == (14, K, b.B) || error("nav must be 14 x K x B")
+    dx0 === nothing || size(dx0) == (14, b.B) || error("dx0 must be 14 x B")
+    report = Matrix{Float64}(undef, FLIGHT_NREP, b.B)
+    xfly = dense ? Array{Float64,3}(undef, 14, K + 1, b.B) : nothing
+    ufly = dense ? Array{Float64,3}(undef, NU, K + 1, b.B) : nothing
+    check(b.cache.ctx, ccall((:scvx_batch_track_fly_nav, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), _cov_opt(dx0), nav, nsub, clamp ? TRACK_CLAMP : 0, report, _cov_opt(xfly),
+        _cov_opt(ufly)), "scvx_batch_track_fly_nav")
+    return report, xfly, ufly
+end
+
+function track_nav(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, gain::Array{Float64,4},
+                   nav::Array{Float64,3}; dx0::Union{Nothing,Matrix{Float64}}=nothing, nsub::Int=10, clamp::Bool=false, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); NU = size(u, 1)
+    size(nav) == (14, K, B) || error("nav must be 14 x K x B")
+    report = Matrix{Float64}(undef, FLIGHT_NREP, B)
+    xfly = dense ? Array{Float64,3}(undef, 14, K + 1, B) : nothing
+    ufly = dense ? Array{Float64,3}(undef, NU, K + 1, B) : nothing
+    check(cache.ctx, ccall((:scvx_track_fly_nav_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, sigma, gain, _cov_opt(dx0), nav, nsub, clamp ? TRACK_CLAMP : 0, report, _cov_opt(xfly), _cov_opt(ufly)),
+        "scvx_track_fly_nav_f64_host")
+    return report, xfly, ufly
+end
+
+track_nav_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+               dx0_dev::Ptr{Cdouble}, nav_dev::Ptr{Cdouble}, nsub::Int, flags::Int, report_dev::Ptr{Cdouble}, xfly_dev::Ptr{Cdouble},
+               ufly_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_track_fly_nav_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nav_dev, nsub, flags, report_dev, xfly_dev, ufly_dev),
+        "scvx_track_fly_nav_f64")
+
 # multi-GPU (one Julia process per GPU): rank 0 draws the id, the host ships its 128 bytes (Distributed / MPI.jl / a file)
 unique_id() = (id = Vector{UInt8}(undef, 128); ccall((:scvx_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("RCCL unavailable"); id)
 comm_create!(c::Cache, id::Vector{UInt8}, rank::Int, world::Int) =

@@ -224,9 +224,10 @@ class ScvxBatch:
                   "scvx_batch_track_gains")
         return (gain, p0) if cost else gain
 
-    def track(self, dx0=None, q=None, r=None, qf=None, nsub=None, clamp=False, dense=False):
+    def track(self, dx0=None, q=None, r=None, qf=None, nsub=None, clamp=False, dense=False, nav=None):
         """Fly the batch's current accepted iterate closed loop under its LQR gains from x[0] + dx0 (scvx_batch_track_fly): a
-        dynamics.FlightReport of mode "track" (dense: xfly and ufly).  The batch is left untouched."""
+        dynamics.FlightReport of mode "track" (dense: xfly and ufly).  nav [B][K][14]: the law is fed an estimate whose error at
+        node k is nav[:, k] (scvx_batch_track_fly_nav); None: the true state.  The batch is left untouched."""
         from .dynamics import FlightReport, _track_weights
         nu = self.cache.nu
         qv, rv, qfv = _track_weights(nu, q, r, qf)
@@ -237,6 +238,15 @@ class ScvxBatch:
         rep = np.empty((self.B, _lib.FLIGHT_NREP))
         xfly = np.empty((self.B, self.K + 1, 14)) if dense else None
         ufly = np.empty((self.B, self.K + 1, nu)) if dense else None
+        if nav is not None:
+            nav = np.ascontiguousarray(nav, np.float64)
+            if nav.shape != (self.B, self.K, 14):
+                raise ValueError("shape mismatch: nav [B][K][14]")
+            self._chk(self._L.scvx_batch_track_fly_nav(self.handle, _p(qv), _p(rv), _p(qfv), _p(dx0) if dx0 is not None else None, _p(nav),
+                                                       int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, _p(rep),
+                                                       _p(xfly) if dense else None, _p(ufly) if dense else None),
+                      "scvx_batch_track_fly_nav")
+            return FlightReport(rep, xfly, "track", ufly)
         self._chk(self._L.scvx_batch_track_fly(self.handle, _p(qv), _p(rv), _p(qfv), _p(dx0) if dx0 is not None else None,
                                                int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, _p(rep),
                                                _p(xfly) if dense else None, _p(ufly) if dense else None), "scvx_batch_track_fly")
@@ -260,6 +270,28 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), opt(wv), _p(rep), opt(sig), opt(covK), opt(cov)),
                   "scvx_batch_cov")
         return CovReport(rep, sig, covK, cov)
+
+    def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False):
+        """Navigation-error covariance analysis of the batch's current accepted iterate flown on an estimate under its LQR gains
+        (scvx_batch_nav_cov; S0, N0, H, rm, w and dense as dynamics.nav_cov_batch, weights as track_gains): a dynamics.NavReport.
+        The batch is left untouched."""
+        from .dynamics import NavReport, _cov_noise, _cov_s0, _nav_dense, _nav_model, _track_weights
+        nu = self.cache.nu
+        n = 14 + nu
+        qv, rv, qfv = _track_weights(nu, q, r, qf)
+        s0, n0 = _cov_s0(S0, self.B), _cov_s0(N0, self.B)
+        m, Hm, rmv = _nav_model(H, rm)
+        wv = _cov_noise(w)
+        want = _nav_dense(dense)
+        rep, navrep = np.empty((self.B, _lib.COV_NREP)), np.empty((self.B, _lib.NAV_NREP))
+        sig = np.empty((self.B, self.K + 1, n)) if "sig" in want else None
+        navsig = np.empty((self.B, self.K + 1, 14)) if "navsig" in want else None
+        kf = np.empty((self.B, self.K, 14, m)) if "kf" in want else None
+        joint = np.empty((self.B, self.K + 1, n + 14, n + 14)) if "joint" in want else None
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        self._chk(self._L.scvx_batch_nav_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv), _p(rep),
+                                             _p(navrep), opt(sig), opt(navsig), opt(kf), opt(joint)), "scvx_batch_nav_cov")
+        return NavReport(rep, navrep, sig, navsig, kf, joint)
 
     def set_profiling(self, on: bool):
         self._chk(self._L.scvx_batch_set_profiling(self.handle, 1 if on else 0), "scvx_batch_set_profiling")

@@ -796,6 +796,84 @@ int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const do
     return SCVX_OK;
 }
 
+int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* dx0,
+                             const double* nav, int nsub, int flags, double* report, double* xfly, double* ufly) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (nsub == 0) nsub = ctx->nsub;
+    // every check before anything is enqueued; the outputs are optional here, so a placeholder stands in for `report`
+    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
+    if ((rc = scvx::check_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->x, nsub, flags, b->x))) return rc;
+    if (!nav) return fail(ctx, SCVX_ERR_ARG, "track fly nav: null nav (without one, call scvx_batch_track_fly)");
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14, nu = (size_t)b->B * (b->K + 1) * b->NU,
+                 nv = (size_t)b->B * b->K * 14;
+    scvx::DevBuf<double> dr, df, dc, d0, dv;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMalloc((void**)&dr.p, nr * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dv.p, nv * 8);
+    if (e == hipSuccess && xfly) e = hipMalloc((void**)&df.p, nx * 8);
+    if (e == hipSuccess && ufly) e = hipMalloc((void**)&dc.p, nu * 8);
+    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, (size_t)b->B * 14 * 8);
+    if (e == hipSuccess && dx0) e = hipMemcpyAsync(d0.p, dx0, (size_t)b->B * 14 * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dv.p, nav, nv * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = scvx::launch_track_fly_nav(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0.p, dv.p, nsub, flags, dr.p, df.p, dc.p, st);
+    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && ufly) e = hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_fly_nav: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
+int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,
+                       const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
+                       double* navsig, double* kf, double* joint) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    // every check before anything is enqueued
+    if (!S0 || !N0) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (S0, N0)");
+    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
+    if ((rc = scvx::check_nav_model(ctx, m, H, rm))) return rc;
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const size_t n = 14 + b->NU, N = n + 14;
+    const size_t n0 = (size_t)b->B * 196, nr = (size_t)b->B * SCVX_COV_NREP, nn = (size_t)b->B * SCVX_NAV_NREP,
+                 ns = (size_t)b->B * (b->K + 1) * n, nv = (size_t)b->B * (b->K + 1) * 14, nk = (size_t)b->B * b->K * 14 * m,
+                 nj = (size_t)b->B * (b->K + 1) * N * N;
+    const bool wk = kf && m > 0;
+    scvx::DevBuf<double> d0, dn, dr, dq, ds, dv, dk, dj;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMalloc((void**)&d0.p, n0 * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dn.p, n0 * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dq.p, nn * 8);
+    if (e == hipSuccess && sig) e = hipMalloc((void**)&ds.p, ns * 8);
+    if (e == hipSuccess && navsig) e = hipMalloc((void**)&dv.p, nv * 8);
+    if (e == hipSuccess && wk) e = hipMalloc((void**)&dk.p, nk * 8);
+    if (e == hipSuccess && joint) e = hipMalloc((void**)&dj.p, nj * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dn.p, N0, n0 * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = b->deriv_f ? scvx::launch_nav_cov_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, d0.p, dn.p, m, H, rm, w14, dr.p,
+                                                  dq.p, ds.p, dv.p, dk.p, dj.p, st)
+                       : scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, d0.p, dn.p, m, H, rm, w14, dr.p, dq.p,
+                                              ds.p, dv.p, dk.p, dj.p, st);
+    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && navrep) e = hipMemcpyAsync(navrep, dq.p, nn * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && sig) e = hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && navsig) e = hipMemcpyAsync(navsig, dv.p, nv * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && wk) e = hipMemcpyAsync(kf, dk.p, nk * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && joint) e = hipMemcpyAsync(joint, dj.p, nj * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_nav_cov: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
 int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
     int rc = check_batch(b, true);
     if (rc) return rc;

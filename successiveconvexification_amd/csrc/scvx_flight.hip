@@ -16,6 +16,10 @@
 // an initial state offset per trajectory.  Everything else is written once, in one kernel body specialised by the constant TRACK:
 // each instantiation compiles to what a kernel of its own compiled to (profiles/fly_kernel_merge.md).  The substep is a copy of
 // propagate_kernel's, not a function shared with it: lifted into one, it is contracted and allocated differently in every kernel.
+//
+// NAV = one trailing pointer (scvx_track_fly_nav_f64): the law is fed a navigation estimate, z = [(x - nav_k) - xbar_k; u_k - ubar_k]
+// with nav [B][K][14] the estimate's error at node k.  It is a parameter PACK, empty in every other instantiation, so that those
+// keep their kernel argument and their registers exactly (profiles/nav.md).
 #include <cmath>
 #include <limits>
 #include "scvx_internal.hpp"
@@ -42,12 +46,19 @@ PathK path_constants(const scvx_problem& P) {
 
 // opt: the mode (SCVX_FLIGHT_SHOOT / PLAN) of the flight check, the flags (SCVX_TRACK_CLAMP) of the closed-loop flight;
 // gain, dx0 and ufly are read only with TRACK
-template <bool AERO, bool FIN, bool TRQ, bool TRACK>
+template <class... P>
+__device__ __forceinline__ const double* fly_nav(P... p) {
+    if constexpr (sizeof...(P) > 0) return (p, ...);
+    else return nullptr;
+}
+
+template <bool AERO, bool FIN, bool TRQ, bool TRACK, class... NAV>
 __global__ __launch_bounds__(64) void fly_kernel(DynPK<double, TRQ> p, PathK c, int B, int K, const double* __restrict__ x,
                                                  const double* __restrict__ u, const double* __restrict__ sigma,
                                                  const double* __restrict__ gain, const double* __restrict__ dx0, double dt, int nsub,
                                                  int opt, double* __restrict__ report, double* __restrict__ xfly,
-                                                 double* __restrict__ ufly) {
+                                                 double* __restrict__ ufly, NAV... nav) {
+    static_assert(sizeof...(NAV) == 0 || TRACK, "a navigation estimate feeds the tracking law");
     typedef double R;
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
@@ -88,7 +99,10 @@ __global__ __launch_bounds__(64) void fly_kernel(DynPK<double, TRQ> p, PathK c, 
             // ---- node k: the next node's control from the flown state and the applied control ----
             R z[n];
 #pragma unroll
-            for (int i = 0; i < 14; i++) z[i] = xs[i] - xb[(size_t)k * 14 + i];
+            for (int i = 0; i < 14; i++) {
+                if constexpr (sizeof...(NAV) > 0) z[i] = (xs[i] - fly_nav(nav...)[((size_t)b * K + k) * 14 + i]) - xb[(size_t)k * 14 + i];
+                else z[i] = xs[i] - xb[(size_t)k * 14 + i];
+            }
 #pragma unroll
             for (int j = 0; j < NU; j++) {
                 z[14 + j] = upv[j] - ub[(size_t)k * NU + j];
@@ -217,15 +231,17 @@ __global__ __launch_bounds__(64) void fly_kernel(DynPK<double, TRQ> p, PathK c, 
     o[SCVX_FLIGHT_QNORM] = qn + bad;
 }
 
-template <bool TRACK>
+template <bool TRACK, class... NAV>
 static hipError_t launch_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
-                             const double* dx0, int nsub, int opt, double* report, double* xfly, double* ufly, hipStream_t st) {
+                             const double* dx0, int nsub, int opt, double* report, double* xfly, double* ufly, hipStream_t st,
+                             NAV... nav) {
     const PathK c = path_constants(ctx->prob);
     const double dt = 1.0 / (K + 1);
     const dim3 g((unsigned)((B + 63) / 64)), blk(64);
     const DynP<double> dp(ctx->dyn);
 #define SCVX_FLY(A, F, T, par) \
-    hipLaunchKernelGGL((fly_kernel<A, F, T, TRACK>), g, blk, 0, st, par, c, B, K, x, u, sigma, gain, dx0, dt, nsub, opt, report, xfly, ufly)
+    hipLaunchKernelGGL((fly_kernel<A, F, T, TRACK, NAV...>), g, blk, 0, st, par, c, B, K, x, u, sigma, gain, dx0, dt, nsub, opt, report, \
+                       xfly, ufly, nav...)
     if (ctx->dyn.trq) {
         const DynPT<double> dpt(ctx->dyn);
         if (ctx->dyn.fin) SCVX_FLY(true, true, true, dpt);
@@ -249,6 +265,12 @@ hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, con
 hipError_t launch_track_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
                             const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly, hipStream_t st) {
     return launch_fly<true>(ctx, B, K, x, u, sigma, gain, dx0, nsub, flags, report, xfly, ufly, st);
+}
+
+hipError_t launch_track_fly_nav(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma,
+                                const double* gain, const double* dx0, const double* nav, int nsub, int flags, double* report,
+                                double* xfly, double* ufly, hipStream_t st) {
+    return launch_fly<true>(ctx, B, K, x, u, sigma, gain, dx0, nsub, flags, report, xfly, ufly, st, nav);
 }
 
 }  // namespace scvx

@@ -83,6 +83,10 @@ hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float
                                   const double* qf, double* gain, double* p0, hipStream_t st);
 hipError_t launch_track_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
                             const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly, hipStream_t st);
+// the same with the law fed a navigation estimate: nav[B][K][14], the estimate's error at node k (never nullptr)
+hipError_t launch_track_fly_nav(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma,
+                                const double* gain, const double* dx0, const double* nav, int nsub, int flags, double* report,
+                                double* xfly, double* ufly, hipStream_t st);
 // argument checks shared by the context-level and the batch-level entry points
 int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const double* qf);
 int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
@@ -95,6 +99,19 @@ hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const 
 hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
                           const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
 int check_cov_noise(scvx_ctx* ctx, const double* w);
+int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
+              const double* w, const void* report);
+
+// Navigation-error covariance analysis (scvx_nav.hip): cov_propagate_kernel on the joint [z; eps], N = 14 + NU + 14.  N0[B][14][14];
+// m measurements per node, H[m][14] and rm[m] host arrays (nullptr with m = 0); navrep[B][SCVX_NAV_NREP]; sig[B][K+1][n],
+// navsig[B][K+1][14], kf[B][K][14][m], joint[B][K+1][N][N] or nullptr.
+hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                          const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st);
+hipError_t launch_nav_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                              const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
+                              double* report, double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st);
+int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm);
 
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],
 // info [B][6] = status, iters, pobj, gap, pres, dres.  threedof_to_record overwrites the trajectory records [B][(K+1)*(14+NU)+1]

@@ -1,0 +1,551 @@
+// Navigation-error (LQG) covariance analysis (scvx_nav_cov_f64, include/scvx.h): the covariance Xi_k of the joint
+// zeta_k = [z_k; eps_k], z = [dx; du] the deviation of the truth from the plan under the tracking law of scvx_track.hip and
+// eps = x - xhat the error of the navigation estimate the law is fed, with a measurement update (Joseph form) and a time step per
+// node, and the two per-trajectory reports read off it.  No counterpart in the reference.
+//
+// nav_cov_kernel: ONE WAVEFRONT PER TRAJECTORY, K sequential steps -- cov_propagate_kernel (scvx_cov.hip) on the joint.  N = n + 14.
+// Neither T_k = [[M, -G Lx], [0, A]] nor U = blockdiag(I, J) is stored as a matrix:
+//     update (m > 0):  HP = H P (m x 14),  S = HP H' + diag(rm),  S = C C' (left-looking, one lane per row),  Kf' = S^-1 HP (one lane
+//                      per column),  J = I - Kf H,  Y = Xi[:, eps] J' (N x 14),  Xi[z, eps] = Y[z], Xi[eps, z] = Y[z]',
+//                      Xi[eps, eps] = J Y[eps] + Kf diag(rm) Kf'  -- the z block is not touched
+//     time step:       Mtop = [A B-] + B+ L (14 x n),  Gx = B+ Lx (14 x 14)  -- the rows 14.. of M and of G Lx are L and Lx themselves,
+//                      the eps rows of T are A;  V = T Xi (N x N),  R = V T' over Xi,  Xi = (R + R') / 2 + W: every pair from both of
+//                      its triangles, W = diag(w) in the xx, x eps, eps x and eps eps blocks
+// with Xi, V, the tile, Mtop, Gx, L and H in LDS; S, Kf' and J live in V, which the update does not otherwise need (23.5 KB at NU = 3,
+// 26.6 KB at NU = 5).  One lane per output element throughout; a row of T is one of three kinds (top, gain, eps), and the element
+// maps keep the 64 lanes of a pass in at most two of them.  The tile and the gain block of step k + 1 are fetched into registers while
+// step k computes and stored to LDS behind the step's last barrier.  DS is the tiles' storage type (double, or float with
+// scvx_batch_set_linearization_f32: widened on load).  H, rm and w ride by value in the kernel argument and are copied to LDS once.
+//
+// The dispersion report is cov_propagate_kernel's, read off the z block (lanes 0..5 the running columns, 6..11 the final ones);
+// lane 12 carries NAV_PEAK, lanes 13..19 the final columns of the navigation report.
+#include <cmath>
+#include <limits>
+#include "scvx_internal.hpp"
+
+namespace scvx {
+
+struct NavK {
+    double mdry, tggs, sqcm, omMax, Tmax, Tmin;
+    double w[14], rm[14], H[196];
+    int m;
+};
+
+// square root of a variance (a rounded variance of -1e-40 is 0, a NaN stays a NaN)
+__device__ __forceinline__ double nav_sd(double v) { return v > 0.0 ? sqrt(v) : (v != v ? v : 0.0); }
+
+// c' S c for a gradient with (up to) three nonzeros c0, c1, c2 at i0, i1, i2; S with row stride n
+__device__ __forceinline__ double nav_quad3(const double* S, int n, int i0, int i1, int i2, double c0, double c1, double c2) {
+    const double d = c0 * c0 * S[i0 * n + i0] + c1 * c1 * S[i1 * n + i1] + c2 * c2 * S[i2 * n + i2];
+    const double o = c0 * c1 * S[i0 * n + i1] + c0 * c2 * S[i0 * n + i2] + c1 * c2 * S[i1 * n + i2];
+    return d + 2.0 * o;
+}
+
+template <typename DS, int NU>
+__global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
+                                                     const DS* __restrict__ deriv, const double* __restrict__ gain,
+                                                     const double* __restrict__ S0, const double* __restrict__ N0,
+                                                     double* __restrict__ report, double* __restrict__ navrep, double* __restrict__ sig,
+                                                     double* __restrict__ navsig, double* __restrict__ kf, double* __restrict__ joint) {
+    constexpr int n = 14 + NU, N = n + 14, mt = 14 + 2 * NU, NC = mt + 1, DSZ = 14 * NC, ND = 14 * mt, NL = NU * n, NN = N * N;
+    constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
+    constexpr int NR = SCVX_COV_NREP + SCVX_NAV_NREP;
+    static_assert(N * 14 + 2 * 196 <= NN && 196 <= N * 14, "Y (S before it), J and Kf' must fit into V");
+    __shared__ double Xl[NN], Vl[NN], Dl[ND], Ml[14 * n], Gl[196], Ll[NL], Hl[196], rml[14], tl[14], Rl[NR + 2];
+    // Kl: HP, then Kf' (m x 14);  Sl: S, then its factor C, dead before Y is born in its place
+    double *Yl = Vl, *Sl = Vl, *Jl = Vl + N * 14, *Kl = Jl + 196;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const int m = c.m;
+    const DS* tiles = deriv + (size_t)b * K * DSZ;
+    const double* gb = gain + (size_t)b * K * NL;
+    const double* xb = x + (size_t)b * (K + 1) * 14;
+    const double* ub = u + (size_t)b * (K + 1) * NU;
+    const double* s0 = S0 + (size_t)b * 196;
+    const double* n0 = N0 + (size_t)b * 196;
+    double* jb = joint ? joint + (size_t)b * (K + 1) * NN : nullptr;
+    double* sigb = sig ? sig + (size_t)b * (K + 1) * n : nullptr;
+    double* nsb = navsig ? navsig + (size_t)b * (K + 1) * 14 : nullptr;
+    double* kfb = kf ? kf + (size_t)b * K * 14 * m : nullptr;
+    const double inf = std::numeric_limits<double>::infinity();
+    // Xi_0 = blockdiag((S0 + S0') / 2, 0, (N0 + N0') / 2); tile 0 and gain block 0; H and rm
+    for (int e = lane; e < NN; e += 64) {
+        const int a = e / N, cc = e % N;
+        double v = 0.0;
+        if (a < 14 && cc < 14) v = 0.5 * (s0[a * 14 + cc] + s0[cc * 14 + a]);
+        else if (a >= n && cc >= n) v = 0.5 * (n0[(a - n) * 14 + cc - n] + n0[(cc - n) * 14 + a - n]);
+        Xl[e] = v;
+    }
+    for (int e = lane; e < ND; e += 64) Dl[e] = (double)tiles[e];
+    for (int e = lane; e < NL; e += 64) Ll[e] = gb[e];
+    for (int e = lane; e < m * 14; e += 64) Hl[e] = c.H[e];
+    if (lane < 14) rml[lane] = c.rm[lane];
+    // the running columns: lane 0 SIG_PEAK (and its non-finite flag), 1 N_MASS, 2 N_GLIDE, 3 N_TILT, 4 N_RATE, 5 S_THRUST / N_TMAX /
+    // N_TMIN, 12 NAV_PEAK (and its non-finite flag)
+    double acc0 = (lane == 0 || lane == 12) ? 0.0 : inf, acc1 = inf, acc2 = 0.0, bad = 0.0;
+    double pv0 = 0.0, pv1 = 0.0, pv2 = 0.0;
+    __syncthreads();
+    // sum_l T[a][l] col(l): row a of T is [Mtop | -Gx] (a < 14), [L | -Lx] (a < n) or [0 | A] (the eps rows)
+    auto tdot = [&](int a, auto col) {
+        double s = 0.0;
+        if (a < 14) {
+#pragma unroll
+            for (int l = 0; l < n; l++) s = fma(Ml[l * 14 + a], col(l), s);
+#pragma unroll
+            for (int j = 0; j < 14; j++) s = fma(-Gl[j * 14 + a], col(n + j), s);
+        } else if (a < n) {
+            const double* lr = Ll + (a - 14) * n;
+#pragma unroll
+            for (int l = 0; l < n; l++) s = fma(lr[l], col(l), s);
+#pragma unroll
+            for (int j = 0; j < 14; j++) s = fma(-lr[j], col(n + j), s);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 14; j++) s = fma(Dl[j * 14 + a - n], col(n + j), s);
+        }
+        return s;
+    };
+    // dense outputs and the running columns at node k (the pre-update Xi_k in Xl; pv*: the plan values of node k this lane reads)
+    auto node_out = [&](int k) {
+        if (jb)
+            for (int e = lane; e < NN; e += 64) jb[(size_t)k * NN + e] = Xl[e];
+        if (sigb && lane < n) sigb[(size_t)k * n + lane] = nav_sd(Xl[lane * N + lane]);
+        if (nsb && lane >= 32 && lane < 46) nsb[(size_t)k * 14 + lane - 32] = nav_sd(Xl[(n + lane - 32) * N + n + lane - 32]);
+        if (lane == 0 || lane == 12) {
+            const int o = lane == 0 ? 0 : n;
+            double tr = 0.0;
+#pragma unroll
+            for (int i = 0; i < 14; i++) tr += Xl[(o + i) * N + o + i];
+            bad = fma(tr, 0.0, bad);
+            acc0 = nan_max(acc0, nav_sd(tr));
+        } else if (k > 0 && lane < 6) {
+            if (lane == 1) {
+                const double s = nav_sd(Xl[0]);
+                if (!(s == 0.0)) acc0 = nan_min(acc0, -(c.mdry - pv0) / s);
+            } else if (lane == 5) {
+                const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
+                if (!(nr == 0.0)) {
+                    const double s = nav_sd(nav_quad3(Xl, N, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
+                    acc2 = nan_max(acc2, s);
+                    if (!(s == 0.0)) {
+                        acc0 = nan_min(acc0, -(nr - c.Tmax) / s);
+                        acc1 = nan_min(acc1, -(c.Tmin - nr) / s);
+                    }
+                }
+            } else {
+                // 2 glide: g = tggs |r[2:3]| - r[1];  3 tilt: g = |q[3:4]| - sqcm;  4 rate: g = |w| - omMax
+                const double a0 = lane == 2 ? pv1 : pv0, a1 = lane == 2 ? pv2 : pv1, a2 = lane == 4 ? pv2 : 0.0;
+                const double nr = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+                if (!(nr == 0.0)) {
+                    double g, q;
+                    if (lane == 2) {
+                        g = c.tggs * nr - pv0;
+                        q = nav_quad3(Xl, N, 1, 2, 3, -1.0, c.tggs * a0 / nr, c.tggs * a1 / nr);
+                    } else if (lane == 3) {
+                        g = nr - c.sqcm;
+                        q = nav_quad3(Xl, N, 9, 10, 10, a0 / nr, a1 / nr, 0.0);
+                    } else {
+                        g = nr - c.omMax;
+                        q = nav_quad3(Xl, N, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
+                    }
+                    const double s = nav_sd(q);
+                    if (!(s == 0.0)) acc0 = nan_min(acc0, -g / s);
+                }
+            }
+        }
+    };
+    node_out(0);
+    for (int k = 0; k < K; k++) {
+        // the next step's tile and gain block, and the plan values of node k + 1, in flight while this step computes
+        DS pre[NPRE];
+        double prel[NLPRE];
+        if (k + 1 < K) {
+            const DS* t = tiles + (size_t)(k + 1) * DSZ;
+            const double* g = gb + (size_t)(k + 1) * NL;
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) {
+                const int e = lane + 64 * i;
+                pre[i] = e < ND ? t[e] : DS(0);
+            }
+#pragma unroll
+            for (int i = 0; i < NLPRE; i++) {
+                const int e = lane + 64 * i;
+                prel[i] = e < NL ? g[e] : 0.0;
+            }
+        }
+        if (lane >= 1 && lane < 6) {
+            const double* xn = xb + (size_t)(k + 1) * 14;
+            const double* un = ub + (size_t)(k + 1) * NU;
+            const double* p = lane == 1 ? xn : lane == 2 ? xn + 1 : lane == 3 ? xn + 9 : lane == 4 ? xn + 11 : un;
+            pv0 = p[0];
+            pv1 = lane == 1 ? 0.0 : p[1];
+            pv2 = (lane == 1 || lane == 3) ? 0.0 : p[2];
+        }
+        // Mtop = [A B-] + B+ L and Gx = B+ Lx (read by the time step; written here, behind the previous step's last barrier)
+        for (int e = lane; e < 14 * n + 196; e += 64) {
+            const bool top = e < 14 * n;
+            const int f = top ? e : e - 14 * n, i = f % 14, cc = f / 14;
+            double s = top ? Dl[f] : 0.0;
+#pragma unroll
+            for (int j = 0; j < NU; j++) s = fma(Dl[(n + j) * 14 + i], Ll[j * n + cc], s);
+            (top ? Ml : Gl)[f] = s;
+        }
+        if (m > 0) {
+            // ---- measurement update at node k, P = Xi[eps, eps] ----
+            // HP = H P (P symmetric: row c read for column c)
+            for (int e = lane; e < m * 14; e += 64) {
+                const int i = e / 14, cc = e % 14;
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < 14; l++) s = fma(Hl[i * 14 + l], Xl[(n + cc) * N + n + l], s);
+                Kl[e] = s;
+            }
+            __syncthreads();
+            // S = HP H' + diag(rm)
+            for (int e = lane; e < m * m; e += 64) {
+                const int i = e / m, j = e % m;
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < 14; l++) s = fma(Kl[i * 14 + l], Hl[j * 14 + l], s);
+                Sl[e] = i == j ? s + rml[i] : s;
+            }
+            __syncthreads();
+            // S = C C', left-looking: lane i owns row i; column j needs the finished columns < j of rows i and j
+            for (int j = 0; j < m; j++) {
+                double s = 0.0;
+                if (lane >= j && lane < m) {
+                    s = Sl[lane * m + j];
+                    for (int l = 0; l < j; l++) s = fma(-Sl[lane * m + l], Sl[j * m + l], s);
+                    tl[lane] = s;
+                }
+                __syncthreads();
+                if (lane >= j && lane < m) {
+                    const double d = sqrt(tl[j]);
+                    Sl[lane * m + j] = lane == j ? d : s / d;
+                }
+                __syncthreads();
+            }
+            // Kf' = S^-1 HP: lane cc solves column cc in place (forward, then backward)
+            if (lane < 14) {
+                for (int i = 0; i < m; i++) {
+                    double s = Kl[i * 14 + lane];
+                    for (int l = 0; l < i; l++) s = fma(-Sl[i * m + l], Kl[l * 14 + lane], s);
+                    Kl[i * 14 + lane] = s / Sl[i * m + i];
+                }
+                for (int i = m - 1; i >= 0; i--) {
+                    double s = Kl[i * 14 + lane];
+                    for (int l = i + 1; l < m; l++) s = fma(-Sl[l * m + i], Kl[l * 14 + lane], s);
+                    Kl[i * 14 + lane] = s / Sl[i * m + i];
+                }
+            }
+            __syncthreads();
+            // J = I - Kf H; the gain leaves as kf[k][14][m]
+            for (int e = lane; e < 196; e += 64) {
+                const int a = e / 14, cc = e % 14;
+                double s = 0.0;
+                for (int i = 0; i < m; i++) s = fma(Kl[i * 14 + a], Hl[i * 14 + cc], s);
+                Jl[e] = (a == cc ? 1.0 : 0.0) - s;
+            }
+            if (kfb)
+                for (int e = lane; e < 14 * m; e += 64) kfb[(size_t)k * 14 * m + e] = Kl[(e % m) * 14 + e / m];
+            __syncthreads();
+            // Y = Xi[:, eps] J' (S is dead: Y may take its place)
+            for (int e = lane; e < N * 14; e += 64) {
+                const int a = e / 14, cc = e % 14;
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < 14; l++) s = fma(Xl[a * N + n + l], Jl[cc * 14 + l], s);
+                Yl[e] = s;
+            }
+            __syncthreads();
+            // Xi[z, eps] = Y[z] and its transpose;  Xi[eps, eps] = J Y[eps] + Kf diag(rm) Kf'
+            for (int e = lane; e < N * 14; e += 64) {
+                const int a = e / 14, cc = e % 14;
+                if (a < n) {
+                    Xl[a * N + n + cc] = Yl[e];
+                    Xl[(n + cc) * N + a] = Yl[e];
+                } else {
+                    double s = 0.0;
+#pragma unroll
+                    for (int l = 0; l < 14; l++) s = fma(Jl[(a - n) * 14 + l], Yl[(n + l) * 14 + cc], s);
+                    for (int i = 0; i < m; i++) s = fma(Kl[i * 14 + a - n] * rml[i], Kl[i * 14 + cc], s);
+                    Xl[a * N + n + cc] = s;
+                }
+            }
+            __syncthreads();
+            // the eps block symmetrised: every pair from both of its triangles
+            for (int e = lane; e < 196; e += 64) {
+                const int a = e / 14, cc = e % 14;
+                if (a < cc) {
+                    const double s = 0.5 * (Xl[(n + a) * N + n + cc] + Xl[(n + cc) * N + n + a]);
+                    Xl[(n + a) * N + n + cc] = s;
+                    Xl[(n + cc) * N + n + a] = s;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- time step ----
+        // V = T Xi+ (Xi+ symmetric, read by rows): lanes run along a row of V, so a pass meets at most three rows of T
+        for (int e = lane; e < NN; e += 64) {
+            const int a = e / N, cc = e % N;
+            Vl[e] = tdot(a, [&](int l) { return Xl[cc * N + l]; });
+        }
+        __syncthreads();
+        // R = V T', over Xi (no longer read): lanes run down a column of R
+        for (int e = lane; e < NN; e += 64) {
+            const int cc = e / N, a = e % N;
+            Xl[a * N + cc] = tdot(cc, [&](int l) { return Vl[a * N + l]; });
+        }
+        __syncthreads();
+        // Xi_{k+1} = (R + R') / 2 + W: one lane per pair, both triangles written with the same value
+        for (int e = lane; e < NN; e += 64) {
+            const int a = e / N, cc = e % N;
+            if (a < cc) {
+                double s = 0.5 * (Xl[a * N + cc] + Xl[cc * N + a]);
+                if (a < 14 && cc == a + n) s += c.w[a];
+                Xl[a * N + cc] = s;
+                Xl[cc * N + a] = s;
+            } else if (a == cc) {
+                if (a < 14) Xl[e] += c.w[a];
+                else if (a >= n) Xl[e] += c.w[a - n];
+            }
+        }
+        if (k + 1 < K) {
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) {
+                const int e = lane + 64 * i;
+                if (e < ND) Dl[e] = (double)pre[i];
+            }
+#pragma unroll
+            for (int i = 0; i < NLPRE; i++) {
+                const int e = lane + 64 * i;
+                if (e < NL) Ll[e] = prel[i];
+            }
+        }
+        __syncthreads();
+        node_out(k + 1);
+    }
+    // the reports: running columns from their lanes, the final columns off Xi_K; Rl[NR], Rl[NR + 1]: the two non-finite flags
+    auto blk = [&](int o, int i0, int i1) {
+        double t = 0.0;
+        for (int i = i0; i < i1; i++) t += Xl[(o + i) * N + o + i];
+        return nav_sd(t);
+    };
+    // trace over [i0, i1) of Cov(xhat_K - xbar_K) = Sigma_xx - C - C' + P
+    auto est = [&](int i0, int i1) {
+        double t = 0.0;
+        for (int i = i0; i < i1; i++) t += Xl[i * N + i] - Xl[i * N + n + i] - Xl[(n + i) * N + i] + Xl[(n + i) * N + n + i];
+        return nav_sd(t);
+    };
+    double* Nl = Rl + SCVX_COV_NREP;
+    if (lane == 0) {
+        Rl[SCVX_COV_SIG_PEAK] = acc0;
+        Rl[NR] = bad;
+    } else if (lane == 1) {
+        Rl[SCVX_COV_N_MASS] = acc0;
+    } else if (lane == 2) {
+        Rl[SCVX_COV_N_GLIDE] = acc0;
+    } else if (lane == 3) {
+        Rl[SCVX_COV_N_TILT] = acc0;
+    } else if (lane == 4) {
+        Rl[SCVX_COV_N_RATE] = acc0;
+    } else if (lane == 5) {
+        Rl[SCVX_COV_S_THRUST] = acc2;
+        Rl[SCVX_COV_N_TMAX] = acc0;
+        Rl[SCVX_COV_N_TMIN] = acc1;
+    } else if (lane == 6) {
+        Rl[SCVX_COV_SIG_M] = nav_sd(Xl[0]);
+    } else if (lane == 7) {
+        Rl[SCVX_COV_SIG_R] = blk(0, 1, 4);
+    } else if (lane == 8) {
+        Rl[SCVX_COV_SIG_V] = blk(0, 4, 7);
+    } else if (lane == 9) {
+        Rl[SCVX_COV_SIG_Q] = blk(0, 7, 11);
+    } else if (lane == 10) {
+        Rl[SCVX_COV_SIG_W] = blk(0, 11, 14);
+    } else if (lane == 11) {
+        // eigenvalues of [[a, h], [h, d]], the horizontal block of Sigma_K (state indices 2, 3), closed form
+        const double a = Xl[2 * N + 2], d = Xl[3 * N + 3], h = Xl[2 * N + 3];
+        const double mean = 0.5 * (a + d), dif = 0.5 * (a - d), rad = sqrt(dif * dif + h * h);
+        Rl[SCVX_COV_ELL_A] = nav_sd(mean + rad);
+        Rl[SCVX_COV_ELL_B] = nav_sd(mean - rad);
+        Rl[SCVX_COV_ELL_ANG] = 0.5 * atan2(2.0 * h, a - d);
+    } else if (lane == 12) {
+        Nl[SCVX_NAV_PEAK] = acc0;
+        Rl[NR + 1] = bad;
+    } else if (lane == 13) {
+        Nl[SCVX_NAV_M] = blk(n, 0, 1);
+    } else if (lane == 14) {
+        Nl[SCVX_NAV_R] = blk(n, 1, 4);
+    } else if (lane == 15) {
+        Nl[SCVX_NAV_V] = blk(n, 4, 7);
+    } else if (lane == 16) {
+        Nl[SCVX_NAV_Q] = blk(n, 7, 11);
+    } else if (lane == 17) {
+        Nl[SCVX_NAV_W] = blk(n, 11, 14);
+    } else if (lane == 18) {
+        Nl[SCVX_NAV_EST_R] = est(1, 4);
+    } else if (lane == 19) {
+        Nl[SCVX_NAV_EST_V] = est(4, 7);
+    }
+    __syncthreads();
+    const double flag = Rl[NR] + Rl[NR + 1];
+    if (lane < SCVX_COV_NREP) report[(size_t)b * SCVX_COV_NREP + lane] = Rl[lane] + flag;
+    else if (lane < NR) navrep[(size_t)b * SCVX_NAV_NREP + lane - SCVX_COV_NREP] = Rl[lane] + flag;
+}
+
+template <typename DS>
+static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv,
+                                   const double* gain, const double* S0, const double* N0, int m, const double* H, const double* rm,
+                                   const double* w, double* report, double* navrep, double* sig, double* navsig, double* kf,
+                                   double* joint, hipStream_t st) {
+    const PathK pk = path_constants(ctx->prob);
+    NavK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}, {}, {}, m};
+    for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
+    for (int i = 0; i < m; i++) c.rm[i] = rm[i];
+    for (int i = 0; i < m * 14; i++) c.H[i] = H[i];
+    const dim3 g((unsigned)B), blk(64);
+    if (ctx->dyn.fin)
+        hipLaunchKernelGGL((nav_cov_kernel<DS, 5>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig, navsig, kf, joint);
+    else
+        hipLaunchKernelGGL((nav_cov_kernel<DS, 3>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig, navsig, kf, joint);
+    return hipGetLastError();
+}
+
+hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                          const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st) {
+    return launch_nav_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st);
+}
+
+hipError_t launch_nav_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                              const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
+                              double* report, double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st) {
+    return launch_nav_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st);
+}
+
+int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (m < 0 || m > 14) return fail(ctx, SCVX_ERR_ARG, "nav: the number of measurements m must be in [0,14]");
+    if (m > 0 && (!H || !rm)) return fail(ctx, SCVX_ERR_ARG, "nav: m > 0 needs H[m][14] and rm[m]");
+    for (int i = 0; i < m; i++)
+        if (!(rm[i] > 0.0) || !std::isfinite(rm[i])) return fail(ctx, SCVX_ERR_ARG, "nav: the measurement variances rm must be finite and > 0");
+    for (int i = 0; i < m * 14; i++)
+        if (!std::isfinite(H[i])) return fail(ctx, SCVX_ERR_ARG, "nav: the measurement matrix H must be finite");
+    return SCVX_OK;
+}
+
+int check_nav_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
+                  const void* N0, int m, const double* H, const double* rm, const double* w, const void* report, const void* navrep) {
+    int rc = check_cov(ctx, B, K, x, u, deriv, gain, S0, w, report);
+    if (rc) return rc;
+    if (!N0 || !navrep) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (N0, navrep)");
+    return check_nav_model(ctx, m, H, rm);
+}
+
+}  // namespace scvx
+
+extern "C" {
+
+int scvx_nav_cov_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                     const double* gain_dev, const double* S0_dev, const double* N0_dev, int m, const double* H, const double* rm,
+                     const double* w14, double* report_dev, double* navrep_dev, double* sig_dev, double* navsig_dev, double* kf_dev,
+                     double* joint_dev) {
+    int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev,
+                                       sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_nav_cov_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                          const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w14, double* report,
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint) {
+    int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU, N = n + 14;
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
+                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, nn = (size_t)B * SCVX_NAV_NREP,
+                 ns = (size_t)B * (K + 1) * n, nv = (size_t)B * (K + 1) * 14, nk = (size_t)B * K * 14 * m,
+                 nj = (size_t)B * (K + 1) * N * N;
+    const bool wk = kf && m > 0;
+    scvx::DevBuf<double> dx, du, dd, dg, d0, dn, dr, dq, ds, dv, dk, dj;
+    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dn.p, n0 * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dq.p, nn * 8));
+    if (sig) SCVX_HIP(ctx, hipMalloc((void**)&ds.p, ns * 8));
+    if (navsig) SCVX_HIP(ctx, hipMalloc((void**)&dv.p, nv * 8));
+    if (wk) SCVX_HIP(ctx, hipMalloc((void**)&dk.p, nk * 8));
+    if (joint) SCVX_HIP(ctx, hipMalloc((void**)&dj.p, nj * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dn.p, N0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, dn.p, m, H, rm, w14, dr.p, dq.p, ds.p, dv.p, dk.p, dj.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(navrep, dq.p, nn * 8, hipMemcpyDeviceToHost, st));
+    if (sig) SCVX_HIP(ctx, hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st));
+    if (navsig) SCVX_HIP(ctx, hipMemcpyAsync(navsig, dv.p, nv * 8, hipMemcpyDeviceToHost, st));
+    if (wk) SCVX_HIP(ctx, hipMemcpyAsync(kf, dk.p, nk * 8, hipMemcpyDeviceToHost, st));
+    if (joint) SCVX_HIP(ctx, hipMemcpyAsync(joint, dj.p, nj * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+int scvx_track_fly_nav_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                           const double* gain_dev, const double* dx0_dev, const double* nav_dev, int nsub, int flags,
+                           double* report_dev, double* xfly_dev, double* ufly_dev) {
+    int rc = scvx::check_track_fly(ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, nsub, flags, report_dev);
+    if (rc) return rc;
+    if (!nav_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "track fly nav: null nav (without one, call scvx_track_fly_f64)");
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_fly_nav(ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nav_dev, nsub, flags, report_dev,
+                                             xfly_dev, ufly_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_track_fly_nav_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
+                                const double* dx0, const double* nav, int nsub, int flags, double* report, double* xfly, double* ufly) {
+    int rc = scvx::check_track_fly(ctx, B, K, x, u, sigma, gain, nsub, flags, report);
+    if (rc) return rc;
+    if (!nav) return scvx::fail(ctx, SCVX_ERR_ARG, "track fly nav: null nav (without one, call scvx_track_fly_f64_host)");
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU;
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP,
+                 ng = (size_t)B * K * NU * n, nv = (size_t)B * K * 14;
+    scvx::DevBuf<double> dx, du, ds, dg, d0, dv, dr, df, dc;
+    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dv.p, nv * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    if (dx0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, (size_t)B * 14 * 8));
+    if (xfly) SCVX_HIP(ctx, hipMalloc((void**)&df.p, nx * 8));
+    if (ufly) SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nu * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dv.p, nav, nv * 8, hipMemcpyHostToDevice, st));
+    if (dx0) SCVX_HIP(ctx, hipMemcpyAsync(d0.p, dx0, (size_t)B * 14 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_track_fly_nav(ctx, B, K, dx.p, du.p, ds.p, dg.p, d0.p, dv.p, nsub, flags, dr.p, df.p, dc.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    if (xfly) SCVX_HIP(ctx, hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st));
+    if (ufly) SCVX_HIP(ctx, hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
+
+}  // extern "C"

@@ -205,13 +205,14 @@ def track_gains_batch(cache: IntegratorCache, deriv, q=None, r=None, qf=None, co
     return (gain, p0) if cost else gain
 
 
-def track_fly_batch(cache: IntegratorCache, x, u, sigma, gain, dx0=None, nsub=None, clamp=False, dense=False) -> FlightReport:
+def track_fly_batch(cache: IntegratorCache, x, u, sigma, gain, dx0=None, nsub=None, clamp=False, dense=False, nav=None) -> FlightReport:
     """Fly the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] closed loop under the gains gain [B][K][nu][14+nu] from
     x[:, 0] + dx0 (dx0 [B][14] or None = 0) on the device (scvx_track_fly_f64_host).  The report has the flight check's 16 columns
     (G_* on the flown state and the applied control; GAP against the planned nodes); mode "track".  clamp: rescale the commanded
     thrust norm into [Tmin, Tmax] (and the fin norm below finmxf); off by default: a plan that rides Tmin saturates on one side at
     most nodes and the law loses most of its authority, and without it G_TMIN / G_TMAX show what the law asked for.
-    dense: also xfly [B][K+1][14] and ufly [B][K+1][nu]."""
+    dense: also xfly [B][K+1][14] and ufly [B][K+1][nu].  nav [B][K][14]: the law is fed an estimate whose error at node k is
+    nav[:, k] (scvx_track_fly_nav_f64_host; zeros reproduce the flight without it bit for bit); None: the true state."""
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     sigma = np.ascontiguousarray(sigma, np.float64)
@@ -228,6 +229,15 @@ def track_fly_batch(cache: IntegratorCache, x, u, sigma, gain, dx0=None, nsub=No
     rep = np.empty((B, _lib.FLIGHT_NREP))
     xfly = np.empty((B, K1, 14)) if dense else None
     ufly = np.empty((B, K1, cache.nu)) if dense else None
+    if nav is not None:
+        nav = np.ascontiguousarray(nav, np.float64)
+        if nav.shape != (B, K1 - 1, 14):
+            raise ValueError("shape mismatch: nav [B][K][14]")
+        _lib.check(cache.handle, cache._L.scvx_track_fly_nav_f64_host(
+            cache.handle, B, K1 - 1, _p(x), _p(u), _p(sigma), _p(gain), _p(dx0) if dx0 is not None else None, _p(nav),
+            int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, _p(rep), _p(xfly) if dense else None,
+            _p(ufly) if dense else None), "scvx_track_fly_nav_f64_host")
+        return FlightReport(rep, xfly, "track", ufly)
     _lib.check(cache.handle, cache._L.scvx_track_fly_f64_host(
         cache.handle, B, K1 - 1, _p(x), _p(u), _p(sigma), _p(gain), _p(dx0) if dx0 is not None else None,
         int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, _p(rep), _p(xfly) if dense else None,
@@ -326,6 +336,89 @@ def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, d
     _lib.check(cache.handle, cache._L.scvx_cov_propagate_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
                                                                   _p(rep), opt(sig), opt(covK), opt(cov)), "scvx_cov_propagate_f64_host")
     return CovReport(rep, sig, covK, cov)
+
+
+class NavReport(CovReport):
+    """The two reports of a navigation-error covariance analysis (scvx_nav_cov_f64, include/scvx.h): everything a CovReport has (the
+    sixteen columns read off the truth-dispersion block; `covK` and `cov` are None -- ask for `joint`), plus `navraw` [B][8] with one
+    named numpy view per column (report.NAV_R, report.EST_R, ... -- _lib.NAV_COLUMNS) and the optional dense outputs `navsig`
+    [B][K+1][14] (the 1 sigma of the navigation error before the update at each node), `kf` [B][K][14][m] (the filter gains) and
+    `joint` [B][K+1][N][N], N = 14 + nu + 14 (the covariance of [z; eps] before the update at each node), or None."""
+
+    def __init__(self, raw, navraw, sig=None, navsig=None, kf=None, joint=None):
+        super().__init__(raw, sig)
+        self.navraw = np.asarray(navraw, np.float64).reshape(-1, _lib.NAV_NREP)
+        self.navsig = navsig
+        self.kf = kf
+        self.joint = joint
+        for name, i in _lib.NAV_INDEX.items():
+            setattr(self, name, self.navraw[:, i])
+
+
+def _nav_model(H, rm):
+    """the measurement model: H [m][14] (None or no rows: no measurement) and rm, a scalar or [m] variances -> (m, H, rm), contiguous"""
+    if H is None or np.size(H) == 0:
+        return 0, None, None
+    Hm = np.ascontiguousarray(H, np.float64)
+    if Hm.ndim != 2 or Hm.shape[1] != 14:
+        raise ValueError("H must be [m][14]")
+    m = Hm.shape[0]
+    if rm is None:
+        raise ValueError("rm (the measurement variances, a scalar or [m]) is needed with H")
+    r = np.asarray(rm, np.float64)
+    if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != m):
+        raise ValueError("rm must be a scalar or have %d components" % m)
+    return m, Hm, np.ascontiguousarray(np.broadcast_to(r, (m,)), np.float64)
+
+
+def _nav_dense(dense):
+    """dense: False / True (all four) / an iterable of names out of "sig", "navsig", "kf", "joint" -> the set of wanted outputs"""
+    names = {"sig", "navsig", "kf", "joint"}
+    if dense is True:
+        return names
+    if not dense:
+        return set()
+    want = {dense} if isinstance(dense, str) else set(dense)
+    if not want <= names:
+        raise ValueError("dense: True, False or names out of 'sig', 'navsig', 'kf', 'joint', not %r" % (dense,))
+    return want
+
+
+def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None, dense=False) -> NavReport:
+    """Covariance of the closed loop flown on a navigation ESTIMATE: the joint of the truth dispersion z and the navigation error eps
+    of the plans x, u tracked under `gain` from the tiles `deriv` (all as cov_propagate_batch), on the device (scvx_nav_cov_f64_host;
+    the recursion and its limits are in include/scvx.h).  S0: the handover covariance of the truth, N0: that of the navigation error
+    (each [B][14][14], one [14][14], or a [14] vector of standard deviations).  H [m][14] (montecarlo.measurement_rows) and rm (variances, a
+    scalar or [m]): the measurement taken at every node but the last; H None: inertial propagation only.  w: process-noise variance per
+    segment, which moves the truth and is missed by the estimate alike.  dense: True for sig, navsig, kf and joint, or a subset."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    deriv = np.ascontiguousarray(deriv, np.float64)
+    nu = cache.nu
+    n = 14 + nu
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
+    B, K1, _ = x.shape
+    K = K1 - 1
+    if gain.shape != (B, K, nu, n):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
+    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
+        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
+    s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
+    m, Hm, rv = _nav_model(H, rm)
+    wv = _cov_noise(w)
+    want = _nav_dense(dense)
+    rep, navrep = np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.NAV_NREP))
+    sig = np.empty((B, K1, n)) if "sig" in want else None
+    navsig = np.empty((B, K1, 14)) if "navsig" in want else None
+    kf = np.empty((B, K, 14, m)) if "kf" in want else None
+    joint = np.empty((B, K1, n + 14, n + 14)) if "joint" in want else None
+    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    _lib.check(cache.handle, cache._L.scvx_nav_cov_f64_host(
+        cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), opt(sig),
+        opt(navsig), opt(kf), opt(joint)), "scvx_nav_cov_f64_host")
+    return NavReport(rep, navrep, sig, navsig, kf, joint)
 
 
 def _pf(a):

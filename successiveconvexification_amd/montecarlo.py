@@ -88,6 +88,52 @@ def gaussian_handover(S0, lo, hi, seed):
     return dx0
 
 
+_STATE_BLOCKS = {"r": (1, 4), "v": (4, 7), "q": (7, 11), "w": (11, 14)}
+
+
+def measurement_rows(names):
+    """The measurement matrix H [m][14] of a navigation analysis (ScvxBatch.navigation, dynamics.nav_cov_batch) that observes whole
+    state blocks directly: `names` is a string or an iterable out of "r", "v", "q", "w"; the rows are identity rows in state order."""
+    names = list(names)
+    if not set(names) <= set(_STATE_BLOCKS) or len(set(names)) != len(names):
+        raise ValueError("measurement_rows: distinct names out of 'r', 'v', 'q', 'w', not %r" % (names,))
+    rows = [i for nm in ("r", "v", "q", "w") if nm in names for i in range(*_STATE_BLOCKS[nm])]
+    return np.eye(14)[rows]
+
+
+def nav_error_samples(deriv_b, kf_b, H, rm, N0, lo, hi, seed):
+    """Samples of the navigation error of ONE plan, the sampling counterpart of the navigation analysis: (fed [hi - lo][K][14], the
+    error eps+_k of the updated estimate the law is fed at node k -- the `nav` of track_fly_batch / ScvxBatch.track --, and
+    before [hi - lo][K+1][14], the error eps_k before the update), by the linear error recursion
+        eps_0 = C xi (C = handover_factor(N0)),  eps+_k = J_k eps_k - Kf_k v_k  (J = I - Kf H, v ~ N(0, diag(rm))),  eps_{k+1} = A_k eps+_k
+    with A_k the state block of the plan's tiles deriv_b [K][14+2nu+1][14] and kf_b [K][14][m] the filter gains of the analysis (H
+    None or without rows: no update).  There is NO process noise: the flyer has none, so a sampled check against the analysis is a
+    w = 0 check.  Sample b draws from Philox stream b of `seed` with a counter word of its own, so a shard [lo, hi) gets exactly the
+    rows the whole batch would."""
+    d = np.asarray(deriv_b, np.float64)
+    K = d.shape[0]
+    A = np.swapaxes(d[:, :14, :], 1, 2)                       # tiles are column-major: [k][column][row]
+    m = 0 if H is None else int(np.shape(H)[0])
+    Cf = handover_factor(N0)
+    xi = np.empty((hi - lo, 14 + K * m))                      # per sample: 14 draws for eps_0, then m per node
+    for b in range(lo, hi):
+        xi[b - lo] = np.random.Generator(np.random.Philox(key=seed, counter=[3, 0, 0, b])).standard_normal(14 + K * m)
+    if m:
+        Hm = np.asarray(H, np.float64).reshape(m, 14)
+        sr = np.sqrt(np.broadcast_to(np.asarray(rm, np.float64), (m,)))
+        kf = np.asarray(kf_b, np.float64).reshape(K, 14, m)
+    fed, before = np.zeros((hi - lo, K, 14)), np.zeros((hi - lo, K + 1, 14))
+    e = xi[:, :14] @ Cf.T
+    for k in range(K):
+        before[:, k] = e
+        if m:
+            e = e - (e @ Hm.T + sr * xi[:, 14 + k * m:14 + (k + 1) * m]) @ kf[k].T
+        fed[:, k] = e
+        e = e @ A[k].T
+    before[:, K] = e
+    return fed, before
+
+
 def shard_range(total: int, rank: int, world: int):
     """Contiguous shard [lo, hi) of `total` trajectories for `rank`; sizes differ by at most one."""
     base, rem = divmod(int(total), int(world))

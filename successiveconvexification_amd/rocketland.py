@@ -96,6 +96,24 @@ def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
     return cov_propagate_batch(cache, x, u, deriv, gain, S0, w, dense=dense)
 
 
+def navigation(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, N0=None, H=None, rm=None, w=None, q=None, r=None,
+               qf=None, dense=False):
+    """Navigation-error covariance analysis of an iterate's plan flown on an estimate under the time-varying LQR gains about it: S0 the
+    handover covariance of the truth, N0 that of the navigation error, H [m][14] and rm the measurement taken at every node but the
+    last (H None: inertial propagation only), w the per-segment process noise (dynamics.track_gains_batch on the plan's own
+    linearisation, dynamics.nav_cov_batch).  A dynamics.NavReport of one row."""
+    from .dynamics import linearize_batch, nav_cov_batch, track_gains_batch
+    if S0 is None or N0 is None:
+        raise ValueError("navigation: S0 and N0 (the handover covariances of the truth and of the navigation error) are required")
+    cache = cache if cache is not None else iteration.cache
+    x = np.stack([pt.state for pt in iteration.about])[None]
+    u = np.stack([pt.control for pt in iteration.about])[None]
+    sigma = np.array([float(iteration.sigma)])
+    _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
+    gain = track_gains_batch(cache, deriv, q, r, qf)
+    return nav_cov_batch(cache, x, u, deriv, gain, S0, N0, H, rm, w, dense=dense)
+
+
 def run_iters(iprob: DescentProblem, niters: int, cache: IntegratorCache = None):
     """rocketland.jl:420-430: niters solve_steps, keeping the position history r[3][K+1] and sigma of every iterate
     (the reference's version calls 1-argument create_initial/solve_step that do not exist at HEAD; the cache is
