@@ -334,6 +334,21 @@ int scvx_cov_propagate_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, con
 int scvx_cov_propagate_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv,
                                 const double *gain, const double *S0, const double *w14, double *report, double *sig,
                                 double *covK, double *cov);
+/* The same launch, keeping what the margins are made of: psig [B][K+1][SCVX_PSIG_N] = s = sqrt(c' Sigma_k c) of the path functions
+ * of N_MASS, N_GLIDE, N_TILT, N_RATE and of the thrust norm (N_TMAX and N_TMIN share it: s_T of SCVX_COV_S_THRUST) at every node.
+ * Node 0 is 0 and so is a node that the margin skips (undefined gradient).  A non-finite tile, gain or S0 entry makes every row of
+ * its own trajectory NaN.  Arguments up to report as scvx_cov_propagate_f64, whose outputs this call leaves bitwise unchanged;
+ * SCVX_ERR_ARG also for a null psig. */
+#define SCVX_PSIG_N 5
+#define SCVX_PSIG_MASS 0
+#define SCVX_PSIG_GLIDE 1
+#define SCVX_PSIG_TILT 2
+#define SCVX_PSIG_RATE 3
+#define SCVX_PSIG_THRUST 4
+int scvx_cov_path_sigma_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                            const double *gain_dev, const double *S0_dev, const double *w14, double *report_dev, double *psig_dev);
+int scvx_cov_path_sigma_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv,
+                                 const double *gain, const double *S0, const double *w14, double *report, double *psig);
 
 /* ---- navigation-error (LQG) covariance analysis: the closed loop flown on an ESTIMATE, to first order -----------------------
  * Everything above feeds the tracking law the true state.  A vehicle feeds it a navigation estimate xhat_k whose error is correlated
@@ -493,7 +508,9 @@ int scvx_batch_set_scalars(scvx_batch *b, const double *rk, const double *cost, 
  * The conic solver's own warm-start state is NOT part of a checkpoint: scvx_batch_set_scalars / set_flags / set_trajectory
  * drop it, so the first solve of a restored (or edited) batch starts cold.  After an ACCEPTED step that is what an
  * uninterrupted run does too (bit-identical continuation); after a REJECTED step the uninterrupted run would have
- * warm-started, so the continuation agrees to the solver tolerance, not bit for bit. */
+ * warm-started, so the continuation agrees to the solver tolerance, not bit for bit.
+ * The thrust back-offs (scvx_batch_set_thrust_margins below) ARE part of a checkpoint: scvx_batch_init clears them, so a restored
+ * batch must be given them again (scvx_batch_get_thrust_margins reads them). */
 int scvx_batch_get_flags(scvx_batch *b, int32_t *status, int32_t *active, int32_t *live);
 int scvx_batch_set_flags(scvx_batch *b, const int32_t *status, const int32_t *active, const int32_t *live);
 /* last SOCP solve, per trajectory: solver status (0 optimal: merit < tol; 4 almost optimal: numerical floor with
@@ -530,6 +547,36 @@ int scvx_batch_nav_cov(scvx_batch *b, const double *q14, const double *rNU, cons
                        double *navsig, double *kf, double *joint);
 int scvx_batch_track_fly_nav(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *dx0,
                              const double *nav, int nsub, int flags, double *report, double *xfly, double *ufly);
+
+/* ---- thrust-band back-offs and covariance-driven replanning (no counterpart in the reference) ---------------------------------
+ * Per-trajectory, per-node back-offs of the thrust band, read by the conic solve alone:
+ *     Tmin + lo_k <= |u_k[1:3]| <= Tmax - hi_k        (the lower side through its linearised row, rocketland.jl:199)
+ * the chance-constraint tightening lo_k = hi_k = n s_T(k) once the covariance analysis has the s_T(k).  Every conic solve of the batch
+ * reads them (scvx_socp_solve, scvx_solve_step, scvx_solve); the discretisation, the trust-region update, the flight check and the
+ * tracking calls keep auditing against the true Tmin / Tmax, so a margined plan shows its headroom as negative G_TMIN / G_TMAX.
+ * With no back-offs set, or with all of them zero, every result is bitwise that of a batch that never heard of them.
+ * lo, hi: host [B][K+1] each; both NULL clears.  SCVX_ERR_ARG for a negative or non-finite entry, for only one NULL pointer, and
+ * for any node with lo + hi >= Tmax - Tmin.  Setting or clearing drops the conic solver's warm-start state and the
+ * reuse_inactive_tr shortcut, as scvx_batch_set_trajectory does.  scvx_batch_init clears the back-offs; scvx_batch_reset keeps them.
+ * scvx_batch_get_thrust_margins: zeros when none are set; either pointer may be NULL. */
+int scvx_batch_set_thrust_margins(scvx_batch *b, const double *lo, const double *hi);
+int scvx_batch_get_thrust_margins(scvx_batch *b, double *lo, double *hi);
+/* The back-offs from the covariance analysis of the batch's current accepted iterate, on the device: the gains of q14 / rNU / qf14,
+ * scvx_cov_path_sigma_f64 on the batch's own tiles, then lo_k = hi_k = min(nsigma s_T(k), cap (Tmax - Tmin)) into the batch's
+ * back-off buffer.  S0 [B][14][14] and w14 [14] or NULL are host arrays; psig [B][K+1][SCVX_PSIG_N] (host, or NULL: then nothing
+ * returns to the host and the call is asynchronous on the stream).  A trajectory whose psig rows are NaN gets zero back-offs.
+ * SCVX_ERR_ARG for nsigma < 0 (or not finite), cap outside (0, 0.5), a null S0, a bad w or weight.
+ * Limits: the analysis is FIRST ORDER, and the back-offs are only as good as Sigma_k; s_T depends on the plan, so the plan that
+ * is solved under the back-offs of its predecessor has other s_T, and one round reaches about 2.5 - 3 sigma of headroom for
+ * nsigma = 3 rather than exactly n (repeat the round to tighten it). */
+int scvx_batch_thrust_margins_from_cov(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
+                                       const double *w14, double nsigma, double cap, double *psig);
+/* Start the SCvx loop again FROM THE CURRENT ITERATE: every active trajectory keeps its iterate and its tiles and gets rk = 100,
+ * cost = Inf, iter = 0 (the values of create_initial, rocketland.jl:38), status RUNNING and live = 1; failed trajectories stay
+ * frozen; the conic solver's warm-start state is dropped.  On the device, asynchronous.  The first step after it is accepted
+ * through the reference's rho = NaN branch.  A replan may land in another local optimum than a solve from the straight-line guess
+ * under the same back-offs. */
+int scvx_batch_replan(scvx_batch *b);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

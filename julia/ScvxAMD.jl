@@ -543,6 +543,83 @@ track_nav_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdo
         cache.ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nav_dev, nsub, flags, report_dev, xfly_dev, ufly_dev),
         "scvx_track_fly_nav_f64")
 
+# ---- thrust-band back-offs and covariance-driven replanning (new) ----------------------------------------------------------
+# include/scvx.h, "thrust-band back-offs".  Tmin + lo[k, b] <= |u_k| <= Tmax - hi[k, b], read by the conic solve alone; the flight
+# check and the tracking calls keep auditing against the true Tmin / Tmax.  psig is 5 x (K+1) x B (row PSIG_* + 1 holds that column).
+const PSIG_N = 5
+const PSIG_MASS = 0; const PSIG_GLIDE = 1; const PSIG_TILT = 2; const PSIG_RATE = 3; const PSIG_THRUST = 4
+
+# lo, hi: (K+1) x B each; both `nothing` clears
+function set_thrust_margins!(b::Batch, lo::Union{Nothing,Matrix{Float64}}, hi::Union{Nothing,Matrix{Float64}})
+    K = b.cache.problem.K
+    (lo === nothing) == (hi === nothing) || error("give lo and hi, or neither")
+    lo === nothing || (size(lo) == (K + 1, b.B) && size(hi) == (K + 1, b.B)) || error("lo, hi must be (K+1) x B")
+    check(b.cache.ctx, ccall((:scvx_batch_set_thrust_margins, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _cov_opt(lo), _cov_opt(hi)), "scvx_batch_set_thrust_margins")
+    return b
+end
+
+function thrust_margins(b::Batch)
+    K = b.cache.problem.K
+    lo = Matrix{Float64}(undef, K + 1, b.B); hi = Matrix{Float64}(undef, K + 1, b.B)
+    check(b.cache.ctx, ccall((:scvx_batch_get_thrust_margins, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), b.h, lo, hi),
+        "scvx_batch_get_thrust_margins")
+    return lo, hi
+end
+
+# back-offs lo = hi = min(nsigma s_T(k), cap (Tmax - Tmin)) from the covariance analysis of the current iterate, on the device;
+# psig=true also returns the 5 x (K+1) x B standard deviations of the path functions
+function thrust_margins_from_cov!(b::Batch, S0::Array{Float64,3}; nsigma::Real=3.0, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0,
+                                  psig::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    ps = psig ? Array{Float64,3}(undef, PSIG_N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv check(b.cache.ctx, ccall((:scvx_batch_thrust_margins_from_cov, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, _cov_opt(wv), Float64(nsigma), Float64(cap), _cov_opt(ps)),
+        "scvx_batch_thrust_margins_from_cov")
+    return ps
+end
+
+# start the SCvx loop again from the current iterate (rk = 100, cost = Inf, iter = 0; failed trajectories stay frozen)
+replan!(b::Batch) = (check(b.cache.ctx, ccall((:scvx_batch_replan, LIB), Cint, (Ptr{Cvoid},), b.h), "scvx_batch_replan"); b)
+
+# per round: back-offs from the covariance, replan, solve; returns (status, iters, nu, dJ, lo, hi).  First order; one round reaches
+# about 2.5 - 3 sigma of headroom for nsigma = 3; a replan may land in another local optimum than a solve from the guess
+function robustify!(b::Batch, S0::Array{Float64,3}; nsigma::Real=3.0, rounds::Int=1, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0)
+    rounds >= 1 || error("rounds >= 1")
+    st = Vector{Int32}(undef, b.B); it = Vector{Int32}(undef, b.B); nu = Vector{Float64}(undef, b.B); dj = Vector{Float64}(undef, b.B)
+    for _ in 1:rounds
+        thrust_margins_from_cov!(b, S0; nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
+        replan!(b)
+        check(b.cache.ctx, ccall((:scvx_solve, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}), b.h, st, it, nu, dj), "scvx_solve")
+    end
+    lo, hi = thrust_margins(b)
+    return st, it, nu, dj, lo, hi
+end
+
+# psig 5 x (K+1) x B of any plans (host arrays, as covariance(cache, ...)): (report, psig)
+function path_sigma(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                    S0::Array{Float64,3}; w=nothing)
+    K = size(x, 2) - 1; B = size(x, 3)
+    size(S0) == (14, 14, B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    ps = Array{Float64,3}(undef, PSIG_N, K + 1, B)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv check(cache.ctx, ccall((:scvx_cov_path_sigma_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, _cov_opt(wv), report, ps), "scvx_cov_path_sigma_f64_host")
+    return report, ps
+end
+
+path_sigma_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+                S0_dev::Ptr{Cdouble}, w::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble}, psig_dev::Ptr{Cdouble}) =
+    GC.@preserve w check(cache.ctx, ccall((:scvx_cov_path_sigma_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), report_dev, psig_dev), "scvx_cov_path_sigma_f64")
+
 # multi-GPU (one Julia process per GPU): rank 0 draws the id, the host ships its 128 bytes (Distributed / MPI.jl / a file)
 unique_id() = (id = Vector{UInt8}(undef, 128); ccall((:scvx_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("RCCL unavailable"); id)
 comm_create!(c::Cache, id::Vector{UInt8}, rank::Int, world::Int) =

@@ -60,6 +60,10 @@ COV_NREP = 16
 COV_COLUMNS = ("SIG_M", "SIG_R", "SIG_V", "SIG_Q", "SIG_W", "ELL_A", "ELL_B", "ELL_ANG", "SIG_PEAK", "S_THRUST", "N_MASS", "N_GLIDE",
                "N_TILT", "N_RATE", "N_TMAX", "N_TMIN")
 COV_INDEX = {n: i for i, n in enumerate(COV_COLUMNS)}
+# scvx_cov_path_sigma_*: the columns of psig [B][K+1][PSIG_N] (the SCVX_PSIG_* macros of include/scvx.h)
+PSIG_N = 5
+PSIG_COLUMNS = ("MASS", "GLIDE", "TILT", "RATE", "THRUST")
+PSIG_INDEX = {n: i for i, n in enumerate(PSIG_COLUMNS)}
 # scvx_nav_cov_*: the columns of the navigation report [B][NAV_NREP] (the SCVX_NAV_* macros of include/scvx.h)
 NAV_NREP = 8
 NAV_COLUMNS = ("NAV_M", "NAV_R", "NAV_V", "NAV_Q", "NAV_W", "NAV_PEAK", "EST_R", "EST_V")
@@ -93,6 +97,8 @@ SIGNATURES = {
     "scvx_track_fly_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "scvx_cov_propagate_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
     "scvx_cov_propagate_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_cov_path_sigma_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp]),
+    "scvx_cov_path_sigma_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_nav_cov_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _dp, _dp, _dp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "scvx_nav_cov_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                         _dp]),
@@ -132,6 +138,10 @@ SIGNATURES = {
     "scvx_batch_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_nav_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_track_fly_nav": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "scvx_batch_set_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
+    "scvx_batch_get_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
+    "scvx_batch_thrust_margins_from_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp]),
+    "scvx_batch_replan": (C.c_int, [_vp]),
     "scvx_comm_probe": (C.c_int, []),
     "scvx_comm_unique_id": (C.c_int, [_vp]),
     "scvx_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

@@ -271,6 +271,65 @@ class ScvxBatch:
                   "scvx_batch_cov")
         return CovReport(rep, sig, covK, cov)
 
+    def set_thrust_margins(self, lo=None, hi=None):
+        """Per-node back-offs of the thrust band for every conic solve that follows: Tmin + lo[b, k] <= |u_k| <= Tmax - hi[b, k]
+        (scvx_batch_set_thrust_margins; lo, hi [B][K+1], [K+1] for all or a scalar; both None clears).  init() clears them, reset()
+        keeps them.  The flight check and the tracking calls keep auditing against the true Tmin / Tmax."""
+        if (lo is None) != (hi is None):
+            raise ValueError("set_thrust_margins: give lo and hi, or neither (clear)")
+        if lo is None:
+            self._chk(self._L.scvx_batch_set_thrust_margins(self.handle, None, None), "scvx_batch_set_thrust_margins")
+            return self
+        a = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (self.B, self.K + 1))) for v in (lo, hi)]
+        self._chk(self._L.scvx_batch_set_thrust_margins(self.handle, _p(a[0]), _p(a[1])), "scvx_batch_set_thrust_margins")
+        return self
+
+    def thrust_margins(self):
+        """(lo, hi) [B][K+1] each: the back-offs the conic solve reads (zeros when none are set)."""
+        lo, hi = np.empty((self.B, self.K + 1)), np.empty((self.B, self.K + 1))
+        self._chk(self._L.scvx_batch_get_thrust_margins(self.handle, _p(lo), _p(hi)), "scvx_batch_get_thrust_margins")
+        return lo, hi
+
+    def _margins_from_cov(self, S0, w, q, r, qf, nsigma, cap, want_psig):
+        from .dynamics import _cov_noise, _cov_s0, _track_weights
+        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
+        s0 = _cov_s0(S0, self.B)
+        wv = _cov_noise(w)
+        psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
+        self._chk(self._L.scvx_batch_thrust_margins_from_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(wv) if wv is not None else None,
+                                                             float(nsigma), float(cap), _p(psig) if want_psig else None),
+                  "scvx_batch_thrust_margins_from_cov")
+        return psig
+
+    def path_sigma(self, S0, w=None, q=None, r=None, qf=None):
+        """psig [B][K+1][5]: per node, one standard deviation of the mass, glide-slope, tilt, rate and thrust-norm path functions
+        of the batch's current accepted iterate under its LQR gains (dynamics.cov_path_sigma_batch on the batch's own tiles).  The
+        batch's iterate, scalars and flags are left untouched and so are its thrust back-offs."""
+        from .dynamics import cov_path_sigma_batch
+        x, u, _ = self.trajectory()
+        return cov_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, w)[1]
+
+    def replan(self):
+        """Start the SCvx loop again from the current iterate (scvx_batch_replan: rk = 100, cost = Inf, iter = 0, RUNNING, live for
+        every active trajectory; failed ones stay frozen); on the device, asynchronous."""
+        self._chk(self._L.scvx_batch_replan(self.handle), "scvx_batch_replan")
+        return self
+
+    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None):
+        """Covariance-driven replanning.  Per round: the back-offs lo_k = hi_k = min(nsigma s_T(k), cap (Tmax - Tmin)) from the
+        covariance analysis of the current iterate (scvx_batch_thrust_margins_from_cov, nothing returns to the host), replan(),
+        solve().  Returns the last solve()'s (status, iters, nu_norm, dJ) plus (lo, hi).  First order, and only as good as Sigma_k;
+        s_T depends on the plan, so one round reaches about 2.5 - 3 sigma of headroom for nsigma = 3, not exactly n; a replan may
+        land in another local optimum than a solve from the straight-line guess."""
+        if int(rounds) < 1:
+            raise ValueError("robustify: rounds >= 1")
+        out = None
+        for _ in range(int(rounds)):
+            self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, False)
+            self.replan()
+            out = self.solve()
+        return out + self.thrust_margins()
+
     def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False):
         """Navigation-error covariance analysis of the batch's current accepted iterate flown on an estimate under its LQR gains
         (scvx_batch_nav_cov; S0, N0, H, rm, w and dense as dynamics.nav_cov_batch, weights as track_gains): a dynamics.NavReport.

@@ -38,8 +38,9 @@ __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_kernel(ipm::Consts C, in
                                                   const int* __restrict__ active, double* __restrict__ work,
                                                   double* __restrict__ sol, double* __restrict__ nu,
                                                   double* __restrict__ info, const int* __restrict__ step_status,
-                                                  double* __restrict__ ttr, double* __restrict__ acc) {
-    socp_body<WaveEx>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc);
+                                                  double* __restrict__ ttr, double* __restrict__ acc,
+                                                  const double* __restrict__ marg) {
+    socp_body<WaveEx>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg);
 }
 // the same solve on float derivative tiles (scvx_batch_set_linearization_f32)
 __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_lin32_kernel(ipm::Consts C, int B, size_t work_stride,
@@ -49,8 +50,9 @@ __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_lin32_kernel(ipm::Consts
                                                   const int* __restrict__ active, double* __restrict__ work,
                                                   double* __restrict__ sol, double* __restrict__ nu,
                                                   double* __restrict__ info, const int* __restrict__ step_status,
-                                                  double* __restrict__ ttr, double* __restrict__ acc) {
-    socp_body<WaveEx, float>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc);
+                                                  double* __restrict__ ttr, double* __restrict__ acc,
+                                                  const double* __restrict__ marg) {
+    socp_body<WaveEx, float>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg);
 }
 
 
@@ -178,6 +180,38 @@ __global__ void reset_scalars_kernel(int B, double* __restrict__ rk, double* __r
     for (int q = 0; q < 4; q++) info[4 * i + q] = 0.0;
 }
 
+// scvx_batch_replan: the scalars of create_initial for every ACTIVE trajectory; the iterate and its tiles stay.  A failed trajectory
+// (active = 0) keeps everything, its status included.  ttr = huge: no optimum to reuse, no warm start.
+__global__ void replan_scalars_kernel(int B, double* __restrict__ rk, double* __restrict__ cost, int* __restrict__ iter,
+                                      int* __restrict__ status, const int* __restrict__ active, int* __restrict__ live,
+                                      double* __restrict__ ttr) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B || !active[i]) return;
+    rk[i] = 100.0; cost[i] = INFINITY; iter[i] = 0; status[i] = SCVX_ST_RUNNING; live[i] = 1;
+    ttr[i] = 1.7976931348623157e308;
+}
+
+// scvx_batch_thrust_margins_from_cov: marg[b][k] = (lo, hi) = min(nsigma s_T(k), cap) from psig [B][K+1][SCVX_PSIG_N]; a
+// trajectory with a NaN anywhere in its thrust column gets zeros.  One block per trajectory.
+__global__ __launch_bounds__(64) void margins_from_psig_kernel(int B, int K, const double* __restrict__ psig, double nsigma, double cap,
+                                                               double* __restrict__ marg) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const double* p = psig + (size_t)b * (K + 1) * SCVX_PSIG_N;
+    int bad = 0;
+    for (int k = threadIdx.x; k <= K; k += 64) {
+        const double s = p[(size_t)k * SCVX_PSIG_N + SCVX_PSIG_THRUST];
+        bad |= !(s == s);
+    }
+    bad = __syncthreads_or(bad);
+    double* m = marg + (size_t)b * (K + 1) * 2;
+    for (int k = threadIdx.x; k <= K; k += 64) {
+        const double v = bad ? 0.0 : fmin(nsigma * p[(size_t)k * SCVX_PSIG_N + SCVX_PSIG_THRUST], cap);
+        m[2 * k] = v;
+        m[2 * k + 1] = v;
+    }
+}
+
 // live = active (start of a solve_problem loop); *nlive (zeroed by the caller) = how many
 __global__ void copy_flags_kernel(int B, const int* __restrict__ src, int* __restrict__ dst, int* __restrict__ nlive) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -208,6 +242,9 @@ struct scvx_batch {
     double *rk = nullptr, *cost = nullptr, *ic = nullptr, *info = nullptr, *out = nullptr, *work = nullptr;
     double *ttr = nullptr;   // trust-region norm bound at the last optimum (reuse_inactive_tr)
     double *acc = nullptr;   // scvx::ACC_N running totals (scvx_batch_get_step_stats)
+    double *marg = nullptr;   // per-node back-offs of the thrust band [B][K+1][2] = (lo, hi): read by the conic solve while marg_on
+    bool marg_on = false;     // scvx_batch_set_thrust_margins / _from_cov set it, both-NULL and scvx_batch_init clear it
+    double *cov_s0 = nullptr, *cov_rep = nullptr, *cov_psig = nullptr;   // scratch of scvx_batch_thrust_margins_from_cov: allocated on first use
     double *track_gain = nullptr, *track_p0 = nullptr;   // scratch of scvx_batch_track_*: allocated on first use, freed with the batch
     int *k1skip = nullptr;   // per trajectory: >= SCVX_ST_REJECTED = the reference point did not change in the last step (K1 skips it)
     int *d_nlive = nullptr;  // device-side count of live trajectories (scvx_solve), mirrored asynchronously into pinned h_nlive[2]
@@ -278,10 +315,10 @@ void launch_socp_block(scvx_batch* b, const int* mask) {
     constexpr int NU = 3;
     if (b->deriv_f)
         hipLaunchKernelGGL((scvx::socp_block_kernel<NW, float, NU>), dim3(b->B), dim3(64 * NW), 0, b->ctx->stream, b->C, b->B, b->work_stride,
-                           b->x, b->u, b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc);
+                           b->x, b->u, b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
     else
         hipLaunchKernelGGL((scvx::socp_block_kernel<NW, double, NU>), dim3(b->B), dim3(64 * NW), 0, b->ctx->stream, b->C, b->B, b->work_stride,
-                           b->x, b->u, b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc);
+                           b->x, b->u, b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
 }
 
 // K1 for the batch's iterate, into the derivative buffer of the batch's mode
@@ -298,16 +335,16 @@ int enqueue_socp(scvx_batch* b, const int* mask) {
     const int w = socp_waves(b->nlive_hint >= 0 && b->nlive_hint < b->B ? (b->nlive_hint > 0 ? b->nlive_hint : 1) : b->B, b->ctx->num_cus);
     if (b->NU == 5) {   // fin extension: the same three executors, instantiated for control_dim = 5 in scvx_socp_fin.hip
         scvx::SocpLaunch a{b->C, b->B, b->work_stride, b->x, b->u, b->endpoint, b->deriv, b->deriv_f, b->rk, b->ic, mask,
-                           b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->ctx->stream};
+                           b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->ctx->stream};
         scvx::launch_socp_fin(a, w);
     } else if (w == 4) launch_socp_block<4>(b, mask);
     else if (w == 2) launch_socp_block<2>(b, mask);
     else if (b->deriv_f)
         hipLaunchKernelGGL(scvx::socp_lin32_kernel, dim3(b->B), dim3(64), 0, b->ctx->stream, b->C, b->B, b->work_stride, b->x, b->u,
-                           b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc);
+                           b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
     else
         hipLaunchKernelGGL(scvx::socp_kernel, dim3(b->B), dim3(64), 0, b->ctx->stream, b->C, b->B, b->work_stride, b->x, b->u,
-                           b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc);
+                           b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
     SCVX_HIP(b->ctx, hipGetLastError());
     return SCVX_OK;
 }
@@ -450,6 +487,7 @@ int scvx_batch_create(scvx_ctx* ctx, int B, scvx_batch** out) {
     rc |= dmalloc(ctx, &b->acc, (size_t)scvx::ACC_N);
     rc |= dmalloc(ctx, &b->d_nlive, (size_t)1);
     rc |= dmalloc(ctx, &b->k1skip, nB);
+    rc |= dmalloc(ctx, &b->marg, nB * (K + 1) * 2);
     if (!rc && (hipHostMalloc((void**)&b->h_nlive, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ev_nlive[0], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ev_nlive[1], hipEventDisableTiming) != hipSuccess)) rc = SCVX_ERR_HIP;
@@ -475,7 +513,7 @@ void scvx_batch_destroy(scvx_batch* b) {
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
                     b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip,
-                    b->track_gain, b->track_p0};
+                    b->track_gain, b->track_p0, b->marg, b->cov_s0, b->cov_rep, b->cov_psig};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -551,6 +589,7 @@ int scvx_batch_init(scvx_batch* b, const double* ic) {
     SCVX_HIP(ctx, hipStreamSynchronize(st));  // host staging buffers go out of scope
     b->initialised = true;
     b->nactive_host = -1;
+    b->marg_on = false;   // a new start carries no back-offs (scvx_batch_reset keeps them)
     return SCVX_OK;
 }
 
@@ -885,6 +924,93 @@ int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
     if (rc) return rc;
     SCVX_HIP(ctx, relinearize(b, nullptr));
     SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_batch_set_thrust_margins(scvx_batch* b, const double* lo, const double* hi) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if ((lo == nullptr) != (hi == nullptr)) return fail(ctx, SCVX_ERR_ARG, "thrust margins: lo and hi must both be given, or both be NULL (clear)");
+    const size_t n = (size_t)b->B * (b->K + 1);
+    std::vector<double> m;
+    if (lo) {
+        const double band = b->C.Tmax - b->C.Tmin;
+        m.resize(2 * n);
+        for (size_t i = 0; i < n; i++) {
+            if (!(lo[i] >= 0.0) || !(hi[i] >= 0.0) || !std::isfinite(lo[i]) || !std::isfinite(hi[i]))
+                return fail(ctx, SCVX_ERR_ARG, "thrust margins: every back-off must be finite and >= 0");
+            if (!(lo[i] + hi[i] < band)) return fail(ctx, SCVX_ERR_ARG, "thrust margins: lo + hi must stay below Tmax - Tmin at every node");
+            m[2 * i] = lo[i];
+            m[2 * i + 1] = hi[i];
+        }
+        SCVX_HIP(ctx, hipMemcpyAsync(b->marg, m.data(), m.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    b->marg_on = lo != nullptr;
+    SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, ctx->stream));   // another subproblem: no optimum to reuse, no warm start
+    SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host staging buffer goes out of scope
+    return SCVX_OK;
+}
+
+int scvx_batch_get_thrust_margins(scvx_batch* b, double* lo, double* hi) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    const size_t n = (size_t)b->B * (b->K + 1);
+    std::vector<double> m(2 * n, 0.0);
+    if (b->marg_on) {
+        SCVX_HIP(ctx, hipMemcpyAsync(m.data(), b->marg, m.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (lo) lo[i] = m[2 * i];
+        if (hi) hi[i] = m[2 * i + 1];
+    }
+    return SCVX_OK;
+}
+
+int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
+                                       const double* w14, double nsigma, double cap, double* psig) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    // every check before anything is enqueued
+    if (!S0) return fail(ctx, SCVX_ERR_ARG, "thrust margins: null buffer (S0)");
+    if (!(nsigma >= 0.0) || !std::isfinite(nsigma)) return fail(ctx, SCVX_ERR_ARG, "thrust margins: nsigma must be finite and >= 0");
+    if (!(cap > 0.0 && cap < 0.5)) return fail(ctx, SCVX_ERR_ARG, "thrust margins: cap must lie in (0, 0.5), a fraction of Tmax - Tmin");
+    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
+    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
+    const size_t n0 = (size_t)b->B * 196, np = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N;
+    if (!b->cov_s0) {
+        SCVX_HIP(ctx, hipMalloc((void**)&b->cov_s0, n0 * 8));
+        SCVX_HIP(ctx, hipMalloc((void**)&b->cov_rep, (size_t)b->B * SCVX_COV_NREP * 8));
+        SCVX_HIP(ctx, hipMalloc((void**)&b->cov_psig, np * 8));
+    }
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(b->cov_s0, S0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));   // the caller's S0 is consumed when the call returns; nothing comes back
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    SCVX_HIP(ctx, b->deriv_f ? scvx::launch_cov_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st)
+                             : scvx::launch_cov_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st));
+    hipLaunchKernelGGL(scvx::margins_from_psig_kernel, dim3(b->B), dim3(64), 0, st, b->B, b->K, b->cov_psig, nsigma,
+                       cap * (b->C.Tmax - b->C.Tmin), b->marg);
+    SCVX_HIP(ctx, hipGetLastError());
+    b->marg_on = true;
+    SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, st));   // see scvx_batch_set_thrust_margins
+    if (psig) {
+        SCVX_HIP(ctx, hipMemcpyAsync(psig, b->cov_psig, np * 8, hipMemcpyDeviceToHost, st));
+        SCVX_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return SCVX_OK;
+}
+
+int scvx_batch_replan(scvx_batch* b) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    hipLaunchKernelGGL(scvx::replan_scalars_kernel, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, ctx->stream, b->B, b->rk, b->cost,
+                       b->iter, b->status, b->active, b->live, b->ttr);
+    SCVX_HIP(ctx, hipGetLastError());
     return SCVX_OK;
 }
 

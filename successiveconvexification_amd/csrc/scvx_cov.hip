@@ -59,11 +59,14 @@ __device__ __forceinline__ void cov_mm16(FA fa, FB fb, FC store, int lane) {
 }
 
 // MF: 0 = one lane per element, 1 = the 16 x 16 corner of the two n-deep products on the matrix pipe
-template <typename DS, int NU, int MF>
+// PS: 1 = also keep the per-node s = sqrt(c' Sigma_k c) of the five path functions that lanes 1..5 form for the margins
+// (scvx_cov_path_sigma_f64: psig [B][K+1][SCVX_PSIG_N]); 0 = the report alone, and nothing of it is compiled in
+template <typename DS, int NU, int MF, int PS = 0>
 __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
                                                            const DS* __restrict__ deriv, const double* __restrict__ gain,
                                                            const double* __restrict__ S0, double* __restrict__ report,
-                                                           double* __restrict__ sig, double* __restrict__ covK, double* __restrict__ cov) {
+                                                           double* __restrict__ sig, double* __restrict__ covK, double* __restrict__ cov,
+                                                           double* __restrict__ psig) {
     constexpr int n = 14 + NU, m = 14 + 2 * NU, NC = m + 1, DSZ = 14 * NC, ND = 14 * m, NL = NU * n, NN = n * n;
     constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
     constexpr int NBORD = NN - 256;   // elements of an n x n product outside its 16 x 16 corner
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
     const double* s0 = S0 + (size_t)b * 196;
     double* covb = cov ? cov + (size_t)b * (K + 1) * NN : nullptr;
     double* sigb = sig ? sig + (size_t)b * (K + 1) * n : nullptr;
+    double* psb = PS ? psig + (size_t)b * (K + 1) * SCVX_PSIG_N : nullptr;
     const double inf = std::numeric_limits<double>::infinity();
     // Sigma_0 = blockdiag((S0 + S0') / 2, 0); tile 0 and gain block 0
     for (int e = lane; e < NN; e += 64) {
@@ -132,14 +136,17 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             bad = fma(tr, 0.0, bad);
             acc0 = nan_max(acc0, cov_sd(tr));
         } else if (k > 0 && lane < 6) {
+            double sv = 0.0;   // PS: this lane's s at node k (0 where the margin skips the node)
             if (lane == 1) {
                 const double s = cov_sd(Sl[0]);
+                sv = s;
                 if (!(s == 0.0)) acc0 = nan_min(acc0, -(c.mdry - pv0) / s);
             } else if (lane == 5) {
                 const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
                 if (!(nr == 0.0)) {
                     const double s = cov_sd(cov_quad3(Sl, n, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
                     acc2 = nan_max(acc2, s);
+                    sv = s;
                     if (!(s == 0.0)) {
                         acc0 = nan_min(acc0, -(nr - c.Tmax) / s);
                         acc1 = nan_min(acc1, -(c.Tmin - nr) / s);
@@ -162,9 +169,13 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
                         q = cov_quad3(Sl, n, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
                     }
                     const double s = cov_sd(q);
+                    sv = s;
                     if (!(s == 0.0)) acc0 = nan_min(acc0, -g / s);
                 }
             }
+            if constexpr (PS != 0) psb[(size_t)k * SCVX_PSIG_N + (lane - 1)] = sv;
+        } else if (PS != 0 && lane < 6) {
+            psb[lane - 1] = 0.0;   // node 0: no margin reads it
         }
     };
     node_out(0);
@@ -307,13 +318,20 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
     }
     __syncthreads();
     if (lane < SCVX_COV_NREP) report[(size_t)b * SCVX_COV_NREP + lane] = Rl[lane] + Rl[SCVX_COV_NREP];
+    if constexpr (PS != 0) {
+        // a non-finite Sigma anywhere poisons the report; the rows of this trajectory follow it
+        const double bd = Rl[SCVX_COV_NREP];
+        if (bd != bd)
+            for (int e = lane; e < (K + 1) * SCVX_PSIG_N; e += 64) psb[e] = bd;
+    }
 }
 
 constexpr bool kCovMfmaDefault = false;   // the lane form, which the parity tests pin, until the A/B of tools/bench_cov.py is measured
 
 template <typename DS>
 static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv, const double* gain,
-                               const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
+                               const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
+                               double* psig = nullptr) {
     const PathK pk = path_constants(ctx->prob);
     CovK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}};
     for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
@@ -321,8 +339,15 @@ static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* 
     bool mf = kCovMfmaDefault;
     if (const char* v = std::getenv("SCVX_COV_MFMA"); v && *v) mf = std::atoi(v) != 0;
     const dim3 g((unsigned)B), blk(64);
-#define SCVX_COV_LAUNCH(NU, MF) \
-    hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, cov)
+#define SCVX_COV_LAUNCH(NU, MF)                                                                                                        \
+    do {                                                                                                                               \
+        if (psig)                                                                                                                      \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, \
+                               cov, psig);                                                                                             \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, \
+                               cov, psig);                                                                                             \
+    } while (0)
     if (ctx->dyn.fin) {
         if (mf) SCVX_COV_LAUNCH(5, 1);
         else SCVX_COV_LAUNCH(5, 0);
@@ -342,6 +367,17 @@ hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const 
 hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
                           const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
     return launch_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, w, report, sig, covK, cov, st);
+}
+
+// the same launch with the per-node s of the path functions kept (psig [B][K+1][SCVX_PSIG_N], not null)
+hipError_t launch_cov_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                           const double* S0, const double* w, double* report, double* psig, hipStream_t st) {
+    return launch_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, w, report, nullptr, nullptr, nullptr, st, psig);
+}
+
+hipError_t launch_cov_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                               const double* S0, const double* w, double* report, double* psig, hipStream_t st) {
+    return launch_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, w, report, nullptr, nullptr, nullptr, st, psig);
 }
 
 int check_cov_noise(scvx_ctx* ctx, const double* w) {
@@ -374,6 +410,46 @@ int scvx_cov_propagate_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, con
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev, sig_dev, covK_dev, cov_dev,
                                    ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_cov_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                            const double* gain_dev, const double* S0_dev, const double* w14, double* report_dev, double* psig_dev) {
+    int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    if (rc) return rc;
+    if (!psig_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "cov: null buffer (psig)");
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_cov_psig(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev, psig_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_cov_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                                 const double* S0, const double* w14, double* report, double* psig) {
+    int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
+    if (rc) return rc;
+    if (!psig) return scvx::fail(ctx, SCVX_ERR_ARG, "cov: null buffer (psig)");
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU;
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
+                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, np = (size_t)B * (K + 1) * SCVX_PSIG_N;
+    scvx::DevBuf<double> dx, du, dd, dg, d0, dr, dp;
+    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_cov_psig(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, w14, dr.p, dp.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(psig, dp.p, np * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
     return SCVX_OK;
 }
 

@@ -98,6 +98,11 @@ hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const 
                       const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
 hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
                           const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
+// ... with the per-node s of the five path functions kept: psig [B][K+1][SCVX_PSIG_N] (scvx_cov_path_sigma_f64)
+hipError_t launch_cov_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                           const double* S0, const double* w, double* report, double* psig, hipStream_t st);
+hipError_t launch_cov_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                               const double* S0, const double* w, double* report, double* psig, hipStream_t st);
 int check_cov_noise(scvx_ctx* ctx, const double* w);
 int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
               const double* w, const void* report);

@@ -312,6 +312,7 @@ struct Layout {
         n += (size_t)nloc * 2;           // tmpl, tmpl2
         n += (size_t)3 * (K + 1);        // uhat (thrust part of the control)
         n += (size_t)(K + 1);            // lb0
+        n += (size_t)(K + 1);            // tmx
         n += 64;                         // scalars
         n += (size_t)nv + ny + 2 * (size_t)nc + 8;   // warm-start iterate (Vw, yw, Sw, Zw) + its header
         return n;
@@ -570,7 +571,8 @@ struct Solver {
     gptr ys, ytr, ynu;   // the three border multipliers  S y = Sg, E Hb^-1 Ptr, hnui Pnu
     gptr ptl, rtr;       // ptl = Hb^-1 Ptr (local, zero on nu),  rtr = E ptl (formed only for the y-space border of the two-ended factorisation)
     gptr tmpl, tmpl2;
-    gptr uhat, lb0;
+    gptr uhat, lb0, tmx;   // lb0[k] = (Tmin + lo_k) - |ubar_k|, tmx[k] = Tmax - hi_k: the thrust band of node k less its back-offs (set_margins)
+    cgptr marg = nullptr;  // this trajectory's back-offs [K+1][2] (lo, hi), or null: none
     gptr wh, Vw, yw, Sw, Zw;   // warm-start iterate of the last solve (wh[0] = 1: valid), see SCVX_WARM_SAVE
     // per-factorisation scalars
     double h_tr[4], h_nu[4], hrk, hnui;
@@ -627,7 +629,7 @@ struct Solver {
         tchain = w; w += ny;
         ys = w; w += ny; ytr = w; w += ny; ynu = w; w += ny; rtr = w; w += ny; ptl = w; w += nloc;
         tmpl = w; w += nloc; tmpl2 = w; w += nloc;
-        uhat = w; w += 3 * (K + 1); lb0 = w; w += (K + 1);
+        uhat = w; w += 3 * (K + 1); lb0 = w; w += (K + 1); tmx = w; w += (K + 1);
         w += 64;   // scalars (unused slots kept for layout stability)
         wh = w; w += 8; Vw = w; w += nv; yw = w; w += ny; Sw = w; w += nc; Zw = w; w += nc;
     }
@@ -827,7 +829,7 @@ struct Solver {
             }
             if (k >= 1) out[L.o_mass + (k - 1)] = x[0] - af * C.mdry;
             gptr tb = out + L.o_tb + 4 * k;
-            tb[0] = af * C.Tmax; tb[1] = u[0]; tb[2] = u[1]; tb[3] = u[2];
+            tb[0] = af * tmx[k]; tb[1] = u[0]; tb[2] = u[1]; tb[3] = u[2];
             gptr tc = out + L.o_tc + 4 * k;
             tc[0] = u[0] * C.icos; tc[1] = u[0]; tc[2] = u[1]; tc[3] = u[2];
             out[L.o_lb + k] = uhat[3 * k] * du[0] + uhat[3 * k + 1] * du[1] + uhat[3 * k + 2] * du[2] - af * lb0[k];
@@ -1065,7 +1067,7 @@ struct Solver {
             cgptr du = v + L.nx + NU * k; cdptr ub = ubar + NU * k;
             double u[3];
             for (int c = 0; c < 3; c++) u[c] = af * ub[c] + du[c];
-            o[0] = tb ? af * C.Tmax : u[0] * C.icos;
+            o[0] = tb ? af * tmx[k] : u[0] * C.icos;
             o[1] = u[0]; o[2] = u[1]; o[3] = u[2];
         } else if constexpr (GRP == G_LB) {
             cgptr du = v + L.nx + NU * q;
@@ -3667,6 +3669,10 @@ struct Solver {
         ex.sync();
     }
 
+    // per-node back-offs of the thrust band for the solves that follow: m [K+1][2] = (lo_k, hi_k) >= 0, or null for none.
+    // The rows become  Tmin + lo_k <= uhat_k' u_k  and  |u_k| <= Tmax - hi_k  (read once, in solve()'s set-up).
+    SCVX_HD void set_margins(cgptr m) { marg = m; }
+
     // ---- the solve.  ic: (rIi, vIi) of this trajectory.  Outputs in V (dx, du, nu, s, ...). ----
     // warm: the previous solve in this workspace was for the same (xbar, ubar, endpoint, D) -- the step it belonged to was
     // rejected -- so its saved iterate may be used as the starting point
@@ -3687,7 +3693,9 @@ struct Solver {
             cdptr u = ubar + NU * k;   // the thrust part of the control (rocketland.jl:199 indexes control[1:3])
             const double un = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
             for (int c = 0; c < 3; c++) uhat[3 * k + c] = u[c] / un;  // rocketland.jl:199 (un = 0 -> NaN, as in the reference)
-            lb0[k] = C.Tmin - un;
+            // without back-offs both arrays hold the constants: every product below is the one formed from C.Tmin / C.Tmax
+            lb0[k] = (marg ? C.Tmin + marg[2 * k] : C.Tmin) - un;
+            tmx[k] = marg ? C.Tmax - marg[2 * k + 1] : C.Tmax;
         }
         ex.sync();
         // The ladder.  A solve that ends on its numerical floor above the tolerance (status 1 / 2 / 3) is run again from the cold

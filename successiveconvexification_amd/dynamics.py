@@ -338,6 +338,35 @@ def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, d
     return CovReport(rep, sig, covK, cov)
 
 
+def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None):
+    """What the margins of cov_propagate_batch are made of (scvx_cov_path_sigma_f64_host; same arguments): (CovReport, psig) with psig
+    [B][K+1][5] = s = sqrt(c' Sigma_k c) at every node for the path functions of the mass, glide-slope, tilt and rate margins and of the
+    thrust norm (_lib.PSIG_COLUMNS).  Node 0 and a node its margin skips are 0; a non-finite tile, gain or S0 entry makes the rows of
+    its own trajectory NaN.  psig[:, :, 4] is the s_T(k) that ScvxBatch.robustify turns into back-offs of the thrust band."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    deriv = np.ascontiguousarray(deriv, np.float64)
+    nu = cache.nu
+    n = 14 + nu
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
+    B, K1, _ = x.shape
+    K = K1 - 1
+    if gain.shape != (B, K, nu, n):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
+    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
+        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
+    s0 = _cov_s0(S0, B)
+    wv = _cov_noise(w)
+    rep = np.empty((B, _lib.COV_NREP))
+    psig = np.empty((B, K1, _lib.PSIG_N))
+    _lib.check(cache.handle, cache._L.scvx_cov_path_sigma_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0),
+                                                                   _p(wv) if wv is not None else None, _p(rep), _p(psig)),
+               "scvx_cov_path_sigma_f64_host")
+    return CovReport(rep), psig
+
+
 class NavReport(CovReport):
     """The two reports of a navigation-error covariance analysis (scvx_nav_cov_f64, include/scvx.h): everything a CovReport has (the
     sixteen columns read off the truth-dispersion block; `covK` and `cov` are None -- ask for `joint`), plus `navraw` [B][8] with one

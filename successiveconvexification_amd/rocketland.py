@@ -8,6 +8,7 @@
     fly(iteration, cache) -> FlightReport                         (new: open-loop flight + path audit of a plan)
     track(iteration, cache, dx0) -> FlightReport                  (new: closed-loop flight under LQR gains about the plan)
     covariance(iteration, cache, S0) -> CovReport                 (new: closed-loop covariance analysis of the tracked plan)
+    robustify(iteration, cache, S0) -> (ProblemIteration, lo, hi) (new: replan under thrust back-offs taken from that analysis)
 The recipe of rocketland.jl:26-32 reads the same here:
     cache = IntegratorCache(prob, ProbInfo.from_problem(prob), make_dynamics_module(...))
     pi = create_initial(prob, cache); pi, cnu, cdel = solve_step(pi, cache)
@@ -94,6 +95,21 @@ def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
     _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
     gain = track_gains_batch(cache, deriv, q, r, qf)
     return cov_propagate_batch(cache, x, u, deriv, gain, S0, w, dense=dense)
+
+
+def robustify(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None,
+              r=None, qf=None):
+    """Replan an iterate under back-offs of the thrust band taken from its own covariance analysis (ScvxBatch.robustify on the
+    iterate's device batch): Tmin + n s_T(k) <= |u_k| <= Tmax - n s_T(k).  Returns (the new ProblemIteration, lo [K+1], hi [K+1]);
+    raises like solve_step when the conic solve fails.  The limits are those of ScvxBatch.robustify."""
+    if S0 is None:
+        raise ValueError("robustify: S0 (the handover covariance) is required")
+    cache = cache if cache is not None else iteration.cache
+    batch = iteration.model
+    st, it, nu, dj, lo, hi = batch.robustify(S0, nsigma=nsigma, rounds=rounds, cap=cap, w=w, q=q, r=r, qf=qf)
+    if st[0] in (3, 4, 5):  # rocketland.jl:273-276
+        raise RuntimeError("Non-optimal result %s exiting" % {3: "SLOW_PROGRESS", 4: "NUMERICAL_ERROR", 5: "INFEASIBLE"}[int(st[0])])
+    return _snapshot(iteration.problem, cache, batch), lo[0], hi[0]
 
 
 def navigation(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, N0=None, H=None, rm=None, w=None, q=None, r=None,
