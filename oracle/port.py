@@ -42,9 +42,10 @@ def _p(a):
 
 
 def socp(p: DescentProblem, xbar, ubar, endpoint, deriv, rk, ic=None, tol=1e-8, max_iter=60, refine=6, nthreads=0, accept=0.0,
-         f32=False, work=None, warm=None, lin32=False, retries=None):
+         f32=False, work=None, warm=None, lin32=False, retries=None, marg=None):
     """Batched: xbar [B][K+1][14], ubar [B][K+1][nu], endpoint [B][K][14], deriv [B][K][14+2nu+1][14], rk [B]; nu = 3, or 5
-    when p.fins (fin extension).  Returns dict(dx, du, ds, nu, status, iters, merit, pobj)."""
+    when p.fins (fin extension).  marg: thrust-band back-offs [B][K+1][2] = (lo, hi) per node, as scvx_batch_set_thrust_margins
+    hands them to the device solve (Solver::set_margins), or None.  Returns dict(dx, du, ds, nu, status, iters, merit, pobj)."""
     xbar = np.ascontiguousarray(xbar, float)
     ubar = np.ascontiguousarray(ubar, float)
     endpoint = np.ascontiguousarray(endpoint, float)
@@ -61,7 +62,14 @@ def socp(p: DescentProblem, xbar, ubar, endpoint, deriv, rk, ic=None, tol=1e-8, 
     sol = np.zeros((B, (K + 1) * (14 + NU) + 1))
     nu = np.zeros((B, K, 14))
     info = np.zeros((B, 4))
-    if NU == 5:
+    if marg is not None:
+        marg = np.ascontiguousarray(marg, float)
+        assert marg.shape == (B, K + 1, 2) and work is None and not f32, "back-offs: [B][K+1][2], per-call workspace, double storage"
+        L = port_lib()
+        (L.scvx_port_socp_marg_fin if NU == 5 else L.scvx_port_socp_marg_lin32 if lin32 else L.scvx_port_socp_marg)(
+            C.byref(c), C.c_int(B), _p(xbar), _p(ubar), _p(endpoint), _p(deriv), _p(rk), _p(ic), _p(sol), _p(nu), _p(info),
+            C.c_int(nthreads), _p(marg))
+    elif NU == 5:
         assert not (f32 or lin32), "the fin twin is built for double storage"
         wf = np.ascontiguousarray(warm if warm is not None else np.zeros(B), np.int32)
         port_lib().scvx_port_socp_fin(C.byref(c), C.c_int(B), _p(xbar), _p(ubar), _p(endpoint), _p(deriv), _p(rk), _p(ic), _p(sol), _p(nu),

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include <omp.h>
 #include "../successiveconvexification_amd/csrc/scvx_ipm_core.hpp"
@@ -160,7 +161,7 @@ size_t scvx_port_work_doubles_nu(int K, int with_dp, int nu) {
 template <class Stor, class DStor = Stor, int NU = 3, class FStor = SCVX_FACTOR_T>
 static int port_socp(const scvx::ipm::Consts* C, int B, const double* xbar, const double* ubar, const double* endpoint,
                      const double* deriv, const double* rk, const double* ic, double* sol, double* nu, double* info,
-                     int nthreads, Stor* work_all = nullptr, const int* warm = nullptr) {
+                     int nthreads, Stor* work_all = nullptr, const int* warm = nullptr, const double* marg = nullptr) {
     const int K = C->K;
     scvx::ipm::Layout L;
     L.init(K, C->vmax > 0.0, NU);
@@ -177,6 +178,8 @@ static int port_socp(const scvx::ipm::Consts* C, int B, const double* xbar, cons
             for (size_t i = 0; i < D.size(); i++) D[i] = (DStor)deriv[(size_t)b * K * DSZ + i];
             scvx::ipm::Solver<HostEx, Stor, DStor, NU, FStor> S(ex, *C);
             Stor* wk = work_all ? work_all + (size_t)b * nw : work.data();   // persistent per-trajectory slab, as on the device
+            // per-node back-offs of the thrust band [B][K+1][2] = (lo, hi), the layout socp_body passes (double storage only)
+            if constexpr (std::is_same<Stor, double>::value) S.set_margins(marg ? marg + (size_t)b * (K + 1) * 2 : nullptr);
             scvx::ipm::Result r = S.solve(xbar + (size_t)b * (K + 1) * 14, ubar + (size_t)b * (K + 1) * NU,
                                           endpoint + (size_t)b * K * 14, D.data(), rk[b], ic + (size_t)b * 6, wk,
                                           warm && warm[b]);
@@ -196,6 +199,22 @@ int scvx_port_socp(const scvx::ipm::Consts* C, int B, const double* xbar, const 
                    const double* deriv, const double* rk, const double* ic, double* sol, double* nu, double* info,
                    int nthreads) {
     return port_socp<double>(C, B, xbar, ubar, endpoint, deriv, rk, ic, sol, nu, info, nthreads);
+}
+// thrust-band back-offs marg [B][K+1][2] = (lo, hi) per node (scvx_batch_set_thrust_margins; Solver::set_margins), or NULL for none
+int scvx_port_socp_marg(const scvx::ipm::Consts* C, int B, const double* xbar, const double* ubar, const double* endpoint,
+                        const double* deriv, const double* rk, const double* ic, double* sol, double* nu, double* info,
+                        int nthreads, const double* marg) {
+    return port_socp<double>(C, B, xbar, ubar, endpoint, deriv, rk, ic, sol, nu, info, nthreads, nullptr, nullptr, marg);
+}
+int scvx_port_socp_marg_lin32(const scvx::ipm::Consts* C, int B, const double* xbar, const double* ubar, const double* endpoint,
+                              const double* deriv, const double* rk, const double* ic, double* sol, double* nu, double* info,
+                              int nthreads, const double* marg) {
+    return port_socp<double, float>(C, B, xbar, ubar, endpoint, deriv, rk, ic, sol, nu, info, nthreads, nullptr, nullptr, marg);
+}
+int scvx_port_socp_marg_fin(const scvx::ipm::Consts* C, int B, const double* xbar, const double* ubar, const double* endpoint,
+                            const double* deriv, const double* rk, const double* ic, double* sol, double* nu, double* info,
+                            int nthreads, const double* marg) {
+    return port_socp<double, double, 5>(C, B, xbar, ubar, endpoint, deriv, rk, ic, sol, nu, info, nthreads, nullptr, nullptr, marg);
 }
 // persistent workspace [B][scvx_port_work_doubles(K)] + per-trajectory warm flags: the device's warm start of the solve that
 // follows a rejected step

@@ -1,7 +1,8 @@
 """The conic subproblem and the SCvx step on the MI355X vs the oracles.
 
 Three references, from tightest to loosest:
-  * the CPU twin of the same algorithm (oracle/scvx_port.cpp): same iteration path, 1e-6 on the minimiser,
+  * the CPU twin of the same algorithm (oracle/scvx_port.cpp): same iteration counts and 10 x the twin's build-to-build distance on the
+    sample problem (depth by depth: tests/test_gpu_k4_path.py), 1e-6 on the minimiser at other horizons,
   * the INDEPENDENT interior-point oracle on the full Rocketland.build_model form (oracle/ipm.py + oracle/socp.py):
     2e-5 on the minimiser at the default tolerance 1e-8, 5e-6 with both solvers at 1e-10, objective 1e-8 relative
     (SURVEY.md 8c asked for <= 1e-5 on trajectories; DESIGN.md "parity tolerance"),
@@ -53,19 +54,26 @@ def test_socp_matches_cpu_twin_and_oracle_ipm():
     assert np.all(st == 0), (st, merit)
     tw = port.socp(po, xb, ub, e, d, 100.0, ic)
     assert np.all(tw["status"] == 0)
-    # same algorithm on both sides: identical iteration paths (1e-11 apart, tools/diag_twin.py) unless one side reaches
-    # the numerical floor an iteration earlier — objectives then still agree to ~1e-8, the minimiser to the flatness
-    # of the optimum.  Tight on the objective, flatness-level on the minimiser.
+    # same algorithm on both sides: identical iteration paths, asserted depth by depth in tests/test_gpu_k4_path.py.  Here: the same
+    # iteration counts, and the finished solves within the full-depth bound of that test's exo K = 50 case -- 10 x the distance between
+    # the twin's own two builds (tests/golden/k4_path_yardstick.npz: dx 8.7e-10, du 9.2e-10, dsigma 3.2e-11, nu 1.0e-11), where 1e-6 stood
     K = po.K
+    import k4_path_reference as kp
+    bx, bu, bs, bn = (kp.FACTOR * kp.yardstick("exo K=50")[-1])[:4]
+    assert np.allclose([bx, bu, bs, bn], [8.7e-9, 9.2e-9, 3.2e-10, 1.0e-10], rtol=0.06)    # the bounds do not move with the file
+    print("iterations %s (twin %s); device-vs-twin x %.2e u %.2e sigma %.2e nu %.2e (bounds %.1e %.1e %.1e %.1e)"
+          % (its, tw["iters"], np.abs(x - (xb + tw["dx"])).max(), np.abs(u - (ub + tw["du"])).max(), np.abs(snew - (sg + tw["ds"])).max(),
+             np.abs(nu - tw["nu"]).max(), bx, bu, bs, bn))
+    assert np.array_equal(its, tw["iters"])
 
     def obj(dx, du, ds, nv):
         return (-dx[:, K, 0] + po.wNu * np.sqrt((nv**2).sum((1, 2))) + 0.5 * np.sqrt((dx**2).sum((1, 2)) + (du**2).sum((1, 2))) + np.abs(ds))
     og, ot = obj(x - xb, u - ub, snew - sg, nu), obj(tw["dx"], tw["du"], tw["ds"], tw["nu"])
     assert np.abs(og - ot).max() < 1e-9 * np.abs(ot).max()
-    assert np.abs(x - (xb + tw["dx"])).max() < 1e-6
-    assert np.abs(u - (ub + tw["du"])).max() < 1e-6
-    assert np.abs(snew - (sg + tw["ds"])).max() < 1e-6
-    assert np.abs(nu - tw["nu"]).max() < 1e-6
+    assert np.abs(x - (xb + tw["dx"])).max() <= bx
+    assert np.abs(u - (ub + tw["du"])).max() <= bu
+    assert np.abs(snew - (sg + tw["ds"])).max() <= bs
+    assert np.abs(nu - tw["nu"]).max() <= bn
     assert merit.max() < 1e-8 and tw["merit"].max() < 1e-8
     # independent oracle: the full build_model form solved by oracle.ipm (first trajectory only: seconds)
     it0 = oscvx.create_initial(po, 10, ic[0, :3], ic[0, 3:])
@@ -91,7 +99,13 @@ def test_socp_matches_cpu_twin_and_oracle_ipm():
 def test_both_socp_executors_agree(monkeypatch):
     """socp_kernel (one wavefront per trajectory, the large-batch form) and socp_block_kernel (four wavefronts per
     trajectory, chosen below 512 trajectories) run the same portable solver core: same iteration paths, objectives to
-    1e-7 relative (the tolerance of the twin comparison above), minimisers to the flatness of the optimum.  SCVX_K4_WAVES forces either form."""
+    1e-7 relative (the tolerance of the twin comparison above).  SCVX_K4_WAVES forces either form.  tests/test_gpu_k4_path.py holds each
+    executor to the twin's iteration counts and to 10 x the twin's build-to-build distance Y on this problem (measured: all counts equal,
+    every executor within 0.16 x that bound, profiles/k4_path_parity.md), so between themselves the executors take EQUAL iteration counts
+    (was: within 1) and sit within 2 x 10 Y of each other -- x 1.7e-8, u 1.8e-8, sigma 6.5e-10, nu 2.1e-10 -- where 2e-6 stood."""
+    import k4_path_reference as kp
+    bound = 2.0 * (kp.FACTOR * kp.yardstick("exo K=50")[-1])[:4]
+    assert np.allclose(bound, [1.74e-8, 1.84e-8, 6.5e-10, 2.06e-10], rtol=0.06)    # the bounds do not move with the file
     from oracle import model
     po = model.base_prob_scaled()
     B = 6
@@ -109,10 +123,12 @@ def test_both_socp_executors_agree(monkeypatch):
     a = res["1"]
     for waves in ("2", "4"):   # two wavefronts: the two-ended form on two wavefronts (round 6); four: two-ended on two assembly / chain pairs
         bq = res[waves]
-        assert np.abs(a[4] - bq[4]).max() <= 1, waves          # iteration counts
+        print("%s wavefronts against 1: iterations %s / %s, x %.2e u %.2e sigma %.2e nu %.2e (bounds %s)"
+              % (waves, bq[4], a[4], *[np.abs(a[i] - bq[i]).max() for i in range(4)], bound))
+        assert np.array_equal(a[4], bq[4]), waves               # iteration counts
         assert np.abs(a[5] - bq[5]).max() < 1e-8 * np.abs(a[5]).max(), waves
         for i in range(4):
-            assert np.abs(a[i] - bq[i]).max() < 2e-6, (waves, i)
+            assert np.abs(a[i] - bq[i]).max() <= bound[i], (waves, i)
 
 
 def test_solve_problem_tail_executor_matches_single_wavefront(monkeypatch):
