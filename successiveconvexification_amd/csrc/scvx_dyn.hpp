@@ -16,6 +16,7 @@
 // applies the ~48 structural non-zeros of df/dx directly to the sensitivity column it owns.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits>
 #include <type_traits>
 
 namespace scvx {
@@ -215,6 +216,14 @@ __device__ __forceinline__ void aero_tables(const DynP<R>& p, R aoa, R mach, R t
     }
 }
 
+// The lift direction c v - |v|^2 bv has length |v|^2 sin(angle of attack) and is the difference of two terms of size |v|^2.  With v
+// along the body axis the model has no lift (ifnz), but the terms cancel to their rounding residue (1e-18 with the fused
+// multiply-add, not 0), and 1 / ln turned the lift table's rounding-sized value there into a derivative of 1e-7.  A length within
+// 64 ulps of the cancelling terms is that residue: no direction, no lift.
+template <typename R>
+__device__ __forceinline__ bool lift_dir_defined(R ln, R vn2) {
+    return ln > R(64.0) * std::numeric_limits<R>::epsilon() * vn2;
+}
 // F[3] and (JAC) dF/d(q0..q3, v1..v3) as 3x7 row-major.  TRQ (value only): the aerodynamic torque tau[3] as well.
 template <bool JAC, typename R, bool TRQ = false>
 __device__ __forceinline__ void aero_force(const DynP<R>& p, const R* q, const R* v, const R* C,
@@ -252,7 +261,7 @@ __device__ __forceinline__ void aero_force(const DynP<R>& p, const R* q, const R
 #pragma unroll
     for (int i = 0; i < 3; i++) ld[i] = c * v[i] - vn2 * bv[i];
     const R ln = sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
-    const bool has_lift = ln > R(0.0);
+    const bool has_lift = lift_dir_defined(ln, vn2);
     const R iln = has_lift ? R(1.0) / ln : R(0.0);
     R l[3];
 #pragma unroll
@@ -571,7 +580,7 @@ __device__ __forceinline__ void aero_prep(const DynP<R>& p, const R* v, const R*
 #pragma unroll
     for (int i = 0; i < 3; i++) ld[i] = A.c * v[i] - A.vn2 * A.bv[i];
     const R ln = sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
-    A.has_lift = ln > R(0.0);
+    A.has_lift = lift_dir_defined(ln, A.vn2);
     A.iln = A.has_lift ? R(1.0) / ln : R(0.0);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
