@@ -578,6 +578,55 @@ int scvx_batch_thrust_margins_from_cov(scvx_batch *b, const double *q14, const d
  * under the same back-offs. */
 int scvx_batch_replan(scvx_batch *b);
 
+/* ---- path-constraint back-offs: mass, glide slope, tilt, rate (no counterpart in the reference) --------------------------------
+ * Before these, back-offs existed for the thrust band only; the covariance analysis writes the per-node 1 sigma of four more path
+ * functions (psig, SCVX_PSIG_MASS .. SCVX_PSIG_RATE), and these calls bring them back into the conic solve.  Per trajectory and node
+ * pm [B][K+1][SCVX_PMARG_N] = (mass, glide, tilt, rate), read by the conic solve alone:
+ *     m_k            >= mdry + pm[k][MASS]                      k = 1..K
+ *     |(r2, r3)_k|   <= r1_k / tan(gammaGs) - pm[k][GLIDE]      k = 0..K-1
+ *     |(q2, q3)_k|   <= sqcm - pm[k][TILT]                      k = 0..K-1      (sqcm = sqrt((1 - cos thetaMax) / 2))
+ *     |w_k|          <= omMax - pm[k][RATE]                     k = 0..K-1
+ * Every conic solve of the batch reads them; the discretisation, the trust-region update, the flight check, the tracking, covariance
+ * and navigation calls keep auditing against the true constants, so a margined plan shows its headroom at the nodes (the audit's tilt
+ * function at a node is below minus that node's back-off, and so on; a report's G_TILT is a maximum over ALL its samples, node 0 --
+ * which has no sigma and so gets no back-off from the covariance -- and the stretches between nodes included), and psig is what it
+ * was.  With none set, all of them zero, or set and cleared, every result is bitwise that of a batch that never had any (of the same
+ * build of the library: against a build from before these calls, device results agree to the solver's tolerance, not bit for bit).
+ * The entries: finite and >= 0; tilt < sqcm, rate < omMax, mass < mwet - mdry; an entry whose node has no row must be 0 (glide, tilt
+ * and rate at node K, mass at node 0), and so must glide and rate at node 0, where r and w are fixed: a back-off there either does
+ * nothing or makes the subproblem infeasible.  Tilt at node 0 is allowed (q_0 is free).  Anything else is SCVX_ERR_ARG and leaves the
+ * batch as it was.  pm is a host array; NULL clears.  Setting or clearing drops the conic solver's warm-start state and the
+ * reuse_inactive_tr shortcut, as scvx_batch_set_thrust_margins does.  scvx_batch_init clears them, scvx_batch_reset keeps them, and
+ * like the thrust ones they ARE part of a checkpoint that the caller must carry (scvx_batch_get_path_margins reads them: zeros when
+ * none are set).
+ * OUT OF SCOPE: back-offs of the gimbal cone, the dynamic-pressure cone and the fin cone (psig has no column for them), and back-offs
+ * taken from the navigation analysis (scvx_batch_nav_cov). */
+#define SCVX_PMARG_N 4
+#define SCVX_PMARG_MASS 0
+#define SCVX_PMARG_GLIDE 1
+#define SCVX_PMARG_TILT 2
+#define SCVX_PMARG_RATE 3
+int scvx_batch_set_path_margins(scvx_batch *b, const double *pm);
+int scvx_batch_get_path_margins(scvx_batch *b, double *pm);
+/* scvx_batch_thrust_margins_from_cov for any subset of the five constraints: one covariance launch on the batch's own tiles, then one
+ * small kernel that writes min(nsigma s(k), cap width_k) for the constraints selected in `which` and leaves the others as they are
+ * (a batch without path back-offs has zeros there).  Widths: Tmax - Tmin (thrust, lo_k = hi_k), mwet - mdry (mass), sqcm (tilt),
+ * omMax (rate) and max(xbar_k[1], 0) / tan(gammaGs) of the current iterate (glide: the tightened cone always contains its axis).
+ * The entries that must be 0 (above) are written as 0; a trajectory with a NaN in a selected psig column gets zeros there.
+ * The glide s(k) is that of the audit's function tan(gammaGs) |(r2, r3)_k| - r1_k (SCVX_PSIG_GLIDE), while the back-off is subtracted from
+ * r1_k / tan(gammaGs): n s(k) of back-off buys n tan(gammaGs) sigma of N_GLIDE.
+ * Arguments and refusals as scvx_batch_thrust_margins_from_cov, which is this call with which = SCVX_MARGIN_THRUST and leaves the
+ * path back-offs alone; SCVX_ERR_ARG also for which = 0 or an unknown bit.  The limits are the same: FIRST ORDER, only as good as
+ * Sigma_k, and s(k) depends on the plan. */
+#define SCVX_MARGIN_THRUST 1u
+#define SCVX_MARGIN_MASS 2u
+#define SCVX_MARGIN_GLIDE 4u
+#define SCVX_MARGIN_TILT 8u
+#define SCVX_MARGIN_RATE 16u
+#define SCVX_MARGIN_ALL 31u
+int scvx_batch_margins_from_cov(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
+                                const double *w14, double nsigma, double cap, unsigned which, double *psig);
+
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,
  * solves skipped by reuse_inactive_tr, steps REJECTED, steps that failed (SOLVER / NONFINITE / INFEASIBLE), steps that ended

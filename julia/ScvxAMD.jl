@@ -588,16 +588,59 @@ replan!(b::Batch) = (check(b.cache.ctx, ccall((:scvx_batch_replan, LIB), Cint, (
 
 # per round: back-offs from the covariance, replan, solve; returns (status, iters, nu, dJ, lo, hi).  First order; one round reaches
 # about 2.5 - 3 sigma of headroom for nsigma = 3; a replan may land in another local optimum than a solve from the guess
-function robustify!(b::Batch, S0::Array{Float64,3}; nsigma::Real=3.0, rounds::Int=1, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0)
+# which: the constraints that are tightened (MARGIN_*); with a path constraint among them path_margins(b) holds their back-offs
+function robustify!(b::Batch, S0::Array{Float64,3}; nsigma::Real=3.0, rounds::Int=1, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0,
+                    which::Integer=MARGIN_THRUST)
     rounds >= 1 || error("rounds >= 1")
     st = Vector{Int32}(undef, b.B); it = Vector{Int32}(undef, b.B); nu = Vector{Float64}(undef, b.B); dj = Vector{Float64}(undef, b.B)
     for _ in 1:rounds
-        thrust_margins_from_cov!(b, S0; nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
+        if which == MARGIN_THRUST
+            thrust_margins_from_cov!(b, S0; nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
+        else
+            margins_from_cov!(b, S0; which=which, nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
+        end
         replan!(b)
         check(b.cache.ctx, ccall((:scvx_solve, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}), b.h, st, it, nu, dj), "scvx_solve")
     end
     lo, hi = thrust_margins(b)
     return st, it, nu, dj, lo, hi
+end
+
+# ---- path-constraint back-offs: mass, glide slope, tilt, rate (new) -----------------------------------------------------------
+# include/scvx.h, "path-constraint back-offs".  pm is 4 x (K+1) x B (row PMARG_* + 1 holds that column), read by the conic solve
+# alone; `nothing` clears.  Out of scope: gimbal, dynamic-pressure and fin back-offs, and back-offs from the navigation analysis.
+const PMARG_N = 4
+const PMARG_MASS = 0; const PMARG_GLIDE = 1; const PMARG_TILT = 2; const PMARG_RATE = 3
+const MARGIN_THRUST = UInt32(1); const MARGIN_MASS = UInt32(2); const MARGIN_GLIDE = UInt32(4); const MARGIN_TILT = UInt32(8)
+const MARGIN_RATE = UInt32(16); const MARGIN_ALL = UInt32(31)
+
+function set_path_margins!(b::Batch, pm::Union{Nothing,Array{Float64,3}})
+    K = b.cache.problem.K
+    pm === nothing || size(pm) == (PMARG_N, K + 1, b.B) || error("pm must be 4 x (K+1) x B")
+    check(b.cache.ctx, ccall((:scvx_batch_set_path_margins, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), b.h, _cov_opt(pm)),
+        "scvx_batch_set_path_margins")
+    return b
+end
+
+function path_margins(b::Batch)
+    pm = Array{Float64,3}(undef, PMARG_N, b.cache.problem.K + 1, b.B)
+    check(b.cache.ctx, ccall((:scvx_batch_get_path_margins, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), b.h, pm), "scvx_batch_get_path_margins")
+    return pm
+end
+
+# min(nsigma s(k), cap width_k) for the constraints in the mask `which` (MARGIN_*), the others stay as they are
+function margins_from_cov!(b::Batch, S0::Array{Float64,3}; which::Integer=MARGIN_ALL, nsigma::Real=3.0, cap::Real=0.25, w=nothing, q=1.0,
+                           r=1.0, qf=100.0, psig::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    ps = psig ? Array{Float64,3}(undef, PSIG_N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv check(b.cache.ctx, ccall((:scvx_batch_margins_from_cov, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cuint, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, _cov_opt(wv), Float64(nsigma), Float64(cap), UInt32(which), _cov_opt(ps)),
+        "scvx_batch_margins_from_cov")
+    return ps
 end
 
 # psig 5 x (K+1) x B of any plans (host arrays, as covariance(cache, ...)): (report, psig)

@@ -64,6 +64,11 @@ COV_INDEX = {n: i for i, n in enumerate(COV_COLUMNS)}
 PSIG_N = 5
 PSIG_COLUMNS = ("MASS", "GLIDE", "TILT", "RATE", "THRUST")
 PSIG_INDEX = {n: i for i, n in enumerate(PSIG_COLUMNS)}
+# scvx_batch_set_path_margins: the columns of pm [B][K+1][PMARG_N] (SCVX_PMARG_*), and the mask of scvx_batch_margins_from_cov (SCVX_MARGIN_*)
+PMARG_N = 4
+PMARG_COLUMNS = ("MASS", "GLIDE", "TILT", "RATE")
+PMARG_INDEX = {n: i for i, n in enumerate(PMARG_COLUMNS)}
+MARGIN_BITS = {"thrust": 1, "mass": 2, "glide": 4, "tilt": 8, "rate": 16}
 # scvx_nav_cov_*: the columns of the navigation report [B][NAV_NREP] (the SCVX_NAV_* macros of include/scvx.h)
 NAV_NREP = 8
 NAV_COLUMNS = ("NAV_M", "NAV_R", "NAV_V", "NAV_Q", "NAV_W", "NAV_PEAK", "EST_R", "EST_V")
@@ -142,6 +147,9 @@ SIGNATURES = {
     "scvx_batch_get_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
     "scvx_batch_thrust_margins_from_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp]),
     "scvx_batch_replan": (C.c_int, [_vp]),
+    "scvx_batch_set_path_margins": (C.c_int, [_vp, _dp]),
+    "scvx_batch_get_path_margins": (C.c_int, [_vp, _dp]),
+    "scvx_batch_margins_from_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint, _dp]),
     "scvx_comm_probe": (C.c_int, []),
     "scvx_comm_unique_id": (C.c_int, [_vp]),
     "scvx_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

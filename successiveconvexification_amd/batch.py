@@ -290,16 +290,66 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_get_thrust_margins(self.handle, _p(lo), _p(hi)), "scvx_batch_get_thrust_margins")
         return lo, hi
 
-    def _margins_from_cov(self, S0, w, q, r, qf, nsigma, cap, want_psig):
+    def set_path_margins(self, mass=None, glide=None, tilt=None, rate=None):
+        """Per-node back-offs of four path constraints for every conic solve that follows (scvx_batch_set_path_margins):
+        m_k >= mdry + mass[b, k], |r_k[2:3]| <= r_k[1] / tan(gammaGs) - glide[b, k], |q_k[2:3]| <= sqcm - tilt[b, k] and
+        |w_k| <= omMax - rate[b, k].  Each is [B][K+1], [K+1] for all or a scalar, None for zeros; a [K+1] or scalar value is broadcast
+        and the entries that must be 0 are zeroed (glide, tilt, rate at node K; mass, glide, rate at node 0), a [B][K+1] array is
+        passed as it is.  All None clears.  init() clears them, reset() keeps them; the flight check, the tracking and the covariance
+        calls keep auditing against the true constants."""
+        vals = (mass, glide, tilt, rate)
+        if all(v is None for v in vals):
+            self._chk(self._L.scvx_batch_set_path_margins(self.handle, None), "scvx_batch_set_path_margins")
+            return self
+        pm = np.zeros((self.B, self.K + 1, _lib.PMARG_N))
+        for c, v in enumerate(vals):
+            if v is None:
+                continue
+            a = np.asarray(v, np.float64)
+            pm[:, :, c] = np.broadcast_to(a, (self.B, self.K + 1))
+            if a.ndim < 2:   # a broadcast value: the forced zeros are applied
+                pm[:, 0 if c == _lib.PMARG_INDEX["MASS"] else self.K, c] = 0.0
+                if c in (_lib.PMARG_INDEX["GLIDE"], _lib.PMARG_INDEX["RATE"]):
+                    pm[:, 0, c] = 0.0
+        self._chk(self._L.scvx_batch_set_path_margins(self.handle, _p(pm)), "scvx_batch_set_path_margins")
+        return self
+
+    def path_margins(self):
+        """pm [B][K+1][4] = (mass, glide, tilt, rate): the path back-offs the conic solve reads (zeros when none are set)."""
+        pm = np.empty((self.B, self.K + 1, _lib.PMARG_N))
+        self._chk(self._L.scvx_batch_get_path_margins(self.handle, _p(pm)), "scvx_batch_get_path_margins")
+        return pm
+
+    @staticmethod
+    def _margin_mask(constraints):
+        names = tuple(_lib.MARGIN_BITS) if isinstance(constraints, str) and constraints == "all" else constraints
+        if isinstance(names, str) or len(tuple(names)) == 0 or any(n not in _lib.MARGIN_BITS for n in names):
+            raise ValueError('constraints: a non-empty subset of %s, or "all"' % (tuple(_lib.MARGIN_BITS),))
+        mask = 0
+        for n in names:
+            mask |= _lib.MARGIN_BITS[n]
+        return mask
+
+    def _margins_from_cov(self, S0, w, q, r, qf, nsigma, cap, want_psig, mask=None):
         from .dynamics import _cov_noise, _cov_s0, _track_weights
         qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
         s0 = _cov_s0(S0, self.B)
         wv = _cov_noise(w)
         psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
+        if mask is not None:
+            self._chk(self._L.scvx_batch_margins_from_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(wv) if wv is not None else None,
+                                                          float(nsigma), float(cap), int(mask), _p(psig) if want_psig else None),
+                      "scvx_batch_margins_from_cov")
+            return psig
         self._chk(self._L.scvx_batch_thrust_margins_from_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(wv) if wv is not None else None,
                                                              float(nsigma), float(cap), _p(psig) if want_psig else None),
                   "scvx_batch_thrust_margins_from_cov")
         return psig
+
+    def margins_from_cov(self, S0, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None):
+        """The back-offs min(nsigma s(k), cap width_k) of `constraints` from the covariance analysis of the current accepted iterate
+        (scvx_batch_margins_from_cov; the others stay as they are): returns psig [B][K+1][5]."""
+        return self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
 
     def path_sigma(self, S0, w=None, q=None, r=None, qf=None):
         """psig [B][K+1][5]: per node, one standard deviation of the mass, glide-slope, tilt, rate and thrust-norm path functions
@@ -315,17 +365,22 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_replan(self.handle), "scvx_batch_replan")
         return self
 
-    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None):
+    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",)):
         """Covariance-driven replanning.  Per round: the back-offs lo_k = hi_k = min(nsigma s_T(k), cap (Tmax - Tmin)) from the
         covariance analysis of the current iterate (scvx_batch_thrust_margins_from_cov, nothing returns to the host), replan(),
         solve().  Returns the last solve()'s (status, iters, nu_norm, dJ) plus (lo, hi).  First order, and only as good as Sigma_k;
         s_T depends on the plan, so one round reaches about 2.5 - 3 sigma of headroom for nsigma = 3, not exactly n; a replan may
-        land in another local optimum than a solve from the straight-line guess."""
+        land in another local optimum than a solve from the straight-line guess.
+        constraints: which rows are tightened, any subset of ("thrust", "mass", "glide", "tilt", "rate") or "all"; the path ones
+        get min(nsigma s(k), cap width_k) with the widths of scvx_batch_margins_from_cov, and path_margins() reads them afterwards.
+        The return value is the same six for every choice; the default is the call it always was."""
         if int(rounds) < 1:
             raise ValueError("robustify: rounds >= 1")
+        mask = self._margin_mask(constraints)
+        thrust_only = mask == _lib.MARGIN_BITS["thrust"]
         out = None
         for _ in range(int(rounds)):
-            self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, False)
+            self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, False, None if thrust_only else mask)
             self.replan()
             out = self.solve()
         return out + self.thrust_margins()

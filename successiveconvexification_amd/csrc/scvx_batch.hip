@@ -39,8 +39,9 @@ __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_kernel(ipm::Consts C, in
                                                   double* __restrict__ sol, double* __restrict__ nu,
                                                   double* __restrict__ info, const int* __restrict__ step_status,
                                                   double* __restrict__ ttr, double* __restrict__ acc,
-                                                  const double* __restrict__ marg) {
-    socp_body<WaveEx>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg);
+                                                  const double* __restrict__ marg,
+                                                  const double* __restrict__ pmarg) {
+    socp_body<WaveEx>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg, pmarg);
 }
 // the same solve on float derivative tiles (scvx_batch_set_linearization_f32)
 __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_lin32_kernel(ipm::Consts C, int B, size_t work_stride,
@@ -51,8 +52,9 @@ __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_lin32_kernel(ipm::Consts
                                                   double* __restrict__ sol, double* __restrict__ nu,
                                                   double* __restrict__ info, const int* __restrict__ step_status,
                                                   double* __restrict__ ttr, double* __restrict__ acc,
-                                                  const double* __restrict__ marg) {
-    socp_body<WaveEx, float>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg);
+                                                  const double* __restrict__ marg,
+                                                  const double* __restrict__ pmarg) {
+    socp_body<WaveEx, float>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg, pmarg);
 }
 
 
@@ -191,24 +193,43 @@ __global__ void replan_scalars_kernel(int B, double* __restrict__ rk, double* __
     ttr[i] = 1.7976931348623157e308;
 }
 
-// scvx_batch_thrust_margins_from_cov: marg[b][k] = (lo, hi) = min(nsigma s_T(k), cap) from psig [B][K+1][SCVX_PSIG_N]; a
-// trajectory with a NaN anywhere in its thrust column gets zeros.  One block per trajectory.
-__global__ __launch_bounds__(64) void margins_from_psig_kernel(int B, int K, const double* __restrict__ psig, double nsigma, double cap,
-                                                               double* __restrict__ marg) {
+// scvx_batch_margins_from_cov: the back-offs min(nsigma s(k), cap width_k) of the constraints selected in `which` (SCVX_MARGIN_*)
+// from psig [B][K+1][SCVX_PSIG_N]: the thrust pair into marg [B][K+1][2], the four path ones into pmarg [B][K+1][SCVX_PMARG_N]; an
+// unselected entry keeps its value.  capw = cap times the constant widths; the glide width is that of the iterate x [B][K+1][14],
+// max(x_k[1], 0) / tan(gammaGs).  Entries whose node has no such row, and glide / rate at node 0 (r and w are fixed there), are 0.
+// A trajectory with a NaN anywhere in a selected column gets zeros.  One block per trajectory.
+struct MarginCaps { double thrust, mass, tilt, rate, cap, itan; };
+__global__ __launch_bounds__(64) void margins_from_psig_kernel(int B, int K, const double* __restrict__ psig, const double* __restrict__ x,
+                                                               double nsigma, MarginCaps capw, unsigned which, double* __restrict__ marg,
+                                                               double* __restrict__ pmarg) {
     const int b = blockIdx.x;
     if (b >= B) return;
     const double* p = psig + (size_t)b * (K + 1) * SCVX_PSIG_N;
+    const unsigned bit[SCVX_PSIG_N] = {SCVX_MARGIN_MASS, SCVX_MARGIN_GLIDE, SCVX_MARGIN_TILT, SCVX_MARGIN_RATE, SCVX_MARGIN_THRUST};
     int bad = 0;
-    for (int k = threadIdx.x; k <= K; k += 64) {
-        const double s = p[(size_t)k * SCVX_PSIG_N + SCVX_PSIG_THRUST];
-        bad |= !(s == s);
-    }
+    for (int k = threadIdx.x; k <= K; k += 64)
+        for (int c = 0; c < SCVX_PSIG_N; c++) {
+            const double s = p[(size_t)k * SCVX_PSIG_N + c];
+            bad |= (which & bit[c]) && !(s == s);
+        }
     bad = __syncthreads_or(bad);
-    double* m = marg + (size_t)b * (K + 1) * 2;
     for (int k = threadIdx.x; k <= K; k += 64) {
-        const double v = bad ? 0.0 : fmin(nsigma * p[(size_t)k * SCVX_PSIG_N + SCVX_PSIG_THRUST], cap);
-        m[2 * k] = v;
-        m[2 * k + 1] = v;
+        const double* s = p + (size_t)k * SCVX_PSIG_N;
+        if (which & SCVX_MARGIN_THRUST) {
+            double* m = marg + ((size_t)b * (K + 1) + k) * 2;
+            const double v = bad ? 0.0 : fmin(nsigma * s[SCVX_PSIG_THRUST], capw.thrust);
+            m[0] = v;
+            m[1] = v;
+        }
+        double* pm = pmarg + ((size_t)b * (K + 1) + k) * SCVX_PMARG_N;
+        const bool first = k == 0, last = k == K;
+        if (which & SCVX_MARGIN_MASS) pm[SCVX_PMARG_MASS] = bad || first ? 0.0 : fmin(nsigma * s[SCVX_PSIG_MASS], capw.mass);
+        if (which & SCVX_MARGIN_GLIDE) {
+            const double width = fmax(x[((size_t)b * (K + 1) + k) * 14 + 1], 0.0) * capw.itan;
+            pm[SCVX_PMARG_GLIDE] = bad || first || last ? 0.0 : fmin(nsigma * s[SCVX_PSIG_GLIDE], capw.cap * width);
+        }
+        if (which & SCVX_MARGIN_TILT) pm[SCVX_PMARG_TILT] = bad || last ? 0.0 : fmin(nsigma * s[SCVX_PSIG_TILT], capw.tilt);
+        if (which & SCVX_MARGIN_RATE) pm[SCVX_PMARG_RATE] = bad || first || last ? 0.0 : fmin(nsigma * s[SCVX_PSIG_RATE], capw.rate);
     }
 }
 
@@ -244,6 +265,8 @@ struct scvx_batch {
     double *acc = nullptr;   // scvx::ACC_N running totals (scvx_batch_get_step_stats)
     double *marg = nullptr;   // per-node back-offs of the thrust band [B][K+1][2] = (lo, hi): read by the conic solve while marg_on
     bool marg_on = false;     // scvx_batch_set_thrust_margins / _from_cov set it, both-NULL and scvx_batch_init clear it
+    double *pmarg = nullptr;  // per-node back-offs of the mass, glide-slope, tilt and rate rows [B][K+1][SCVX_PMARG_N]: read while pmarg_on
+    bool pmarg_on = false;    // scvx_batch_set_path_margins / scvx_batch_margins_from_cov set it, NULL and scvx_batch_init clear it
     double *cov_s0 = nullptr, *cov_rep = nullptr, *cov_psig = nullptr;   // scratch of scvx_batch_thrust_margins_from_cov: allocated on first use
     double *track_gain = nullptr, *track_p0 = nullptr;   // scratch of scvx_batch_track_*: allocated on first use, freed with the batch
     int *k1skip = nullptr;   // per trajectory: >= SCVX_ST_REJECTED = the reference point did not change in the last step (K1 skips it)
@@ -315,10 +338,10 @@ void launch_socp_block(scvx_batch* b, const int* mask) {
     constexpr int NU = 3;
     if (b->deriv_f)
         hipLaunchKernelGGL((scvx::socp_block_kernel<NW, float, NU>), dim3(b->B), dim3(64 * NW), 0, b->ctx->stream, b->C, b->B, b->work_stride,
-                           b->x, b->u, b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
+                           b->x, b->u, b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
     else
         hipLaunchKernelGGL((scvx::socp_block_kernel<NW, double, NU>), dim3(b->B), dim3(64 * NW), 0, b->ctx->stream, b->C, b->B, b->work_stride,
-                           b->x, b->u, b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
+                           b->x, b->u, b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
 }
 
 // K1 for the batch's iterate, into the derivative buffer of the batch's mode
@@ -335,16 +358,16 @@ int enqueue_socp(scvx_batch* b, const int* mask) {
     const int w = socp_waves(b->nlive_hint >= 0 && b->nlive_hint < b->B ? (b->nlive_hint > 0 ? b->nlive_hint : 1) : b->B, b->ctx->num_cus);
     if (b->NU == 5) {   // fin extension: the same three executors, instantiated for control_dim = 5 in scvx_socp_fin.hip
         scvx::SocpLaunch a{b->C, b->B, b->work_stride, b->x, b->u, b->endpoint, b->deriv, b->deriv_f, b->rk, b->ic, mask,
-                           b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->ctx->stream};
+                           b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr, b->ctx->stream};
         scvx::launch_socp_fin(a, w);
     } else if (w == 4) launch_socp_block<4>(b, mask);
     else if (w == 2) launch_socp_block<2>(b, mask);
     else if (b->deriv_f)
         hipLaunchKernelGGL(scvx::socp_lin32_kernel, dim3(b->B), dim3(64), 0, b->ctx->stream, b->C, b->B, b->work_stride, b->x, b->u,
-                           b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
+                           b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
     else
         hipLaunchKernelGGL(scvx::socp_kernel, dim3(b->B), dim3(64), 0, b->ctx->stream, b->C, b->B, b->work_stride, b->x, b->u,
-                           b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr);
+                           b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
     SCVX_HIP(b->ctx, hipGetLastError());
     return SCVX_OK;
 }
@@ -488,6 +511,7 @@ int scvx_batch_create(scvx_ctx* ctx, int B, scvx_batch** out) {
     rc |= dmalloc(ctx, &b->d_nlive, (size_t)1);
     rc |= dmalloc(ctx, &b->k1skip, nB);
     rc |= dmalloc(ctx, &b->marg, nB * (K + 1) * 2);
+    rc |= dmalloc(ctx, &b->pmarg, nB * (K + 1) * SCVX_PMARG_N);
     if (!rc && (hipHostMalloc((void**)&b->h_nlive, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ev_nlive[0], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ev_nlive[1], hipEventDisableTiming) != hipSuccess)) rc = SCVX_ERR_HIP;
@@ -513,7 +537,7 @@ void scvx_batch_destroy(scvx_batch* b) {
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
                     b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip,
-                    b->track_gain, b->track_p0, b->marg, b->cov_s0, b->cov_rep, b->cov_psig};
+                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -590,6 +614,7 @@ int scvx_batch_init(scvx_batch* b, const double* ic) {
     b->initialised = true;
     b->nactive_host = -1;
     b->marg_on = false;   // a new start carries no back-offs (scvx_batch_reset keeps them)
+    b->pmarg_on = false;
     return SCVX_OK;
 }
 
@@ -969,15 +994,64 @@ int scvx_batch_get_thrust_margins(scvx_batch* b, double* lo, double* hi) {
     return SCVX_OK;
 }
 
-int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
-                                       const double* w14, double nsigma, double cap, double* psig) {
+int scvx_batch_set_path_margins(scvx_batch* b, const double* pm) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (pm) {
+        const int K = b->K;
+        const double lim[SCVX_PMARG_N] = {b->C.mwet - b->C.mdry, INFINITY, b->C.sqcm, b->C.omMax};   // glide: its width moves with the iterate
+        for (int t = 0; t < b->B; t++)
+            for (int k = 0; k <= K; k++)
+                for (int c = 0; c < SCVX_PMARG_N; c++) {
+                    const double v = pm[((size_t)t * (K + 1) + k) * SCVX_PMARG_N + c];
+                    if (!(v >= 0.0) || !std::isfinite(v)) return fail(ctx, SCVX_ERR_ARG, "path margins: every back-off must be finite and >= 0");
+                    if (!(v < lim[c]))
+                        return fail(ctx, SCVX_ERR_ARG, "path margins: tilt < sqcm, rate < omMax and mass < mwet - mdry must hold at every node");
+                    const bool norow = c == SCVX_PMARG_MASS ? k == 0 : k == K;
+                    if (norow && v != 0.0)
+                        return fail(ctx, SCVX_ERR_ARG, "path margins: an entry without a row must be 0 (glide, tilt, rate at node K; mass at node 0)");
+                    if (k == 0 && (c == SCVX_PMARG_GLIDE || c == SCVX_PMARG_RATE) && v != 0.0)
+                        return fail(ctx, SCVX_ERR_ARG, "path margins: glide and rate at node 0 must be 0 (r and w are fixed there)");
+                }
+        SCVX_HIP(ctx, hipMemcpyAsync(b->pmarg, pm, (size_t)b->B * (K + 1) * SCVX_PMARG_N * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    b->pmarg_on = pm != nullptr;
+    SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, ctx->stream));   // see scvx_batch_set_thrust_margins
+    SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's array is consumed when the call returns
+    return SCVX_OK;
+}
+
+int scvx_batch_get_path_margins(scvx_batch* b, double* pm) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (!pm) return fail(ctx, SCVX_ERR_ARG, "path margins: null buffer (pm)");
+    const size_t n = (size_t)b->B * (b->K + 1) * SCVX_PMARG_N;
+    if (b->pmarg_on) {
+        SCVX_HIP(ctx, hipMemcpyAsync(pm, b->pmarg, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        for (size_t i = 0; i < n; i++) pm[i] = 0.0;
+    }
+    return SCVX_OK;
+}
+
+// both covariance-driven calls; thrust_call: scvx_batch_thrust_margins_from_cov, whose refusals keep their wording
+static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
+                            double nsigma, double cap, unsigned which, double* psig, bool thrust_call) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
     // every check before anything is enqueued
-    if (!S0) return fail(ctx, SCVX_ERR_ARG, "thrust margins: null buffer (S0)");
-    if (!(nsigma >= 0.0) || !std::isfinite(nsigma)) return fail(ctx, SCVX_ERR_ARG, "thrust margins: nsigma must be finite and >= 0");
-    if (!(cap > 0.0 && cap < 0.5)) return fail(ctx, SCVX_ERR_ARG, "thrust margins: cap must lie in (0, 0.5), a fraction of Tmax - Tmin");
+    const std::string who = thrust_call ? "thrust margins: " : "margins from cov: ";
+    if (!S0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (S0)");
+    if (!(nsigma >= 0.0) || !std::isfinite(nsigma)) return fail(ctx, SCVX_ERR_ARG, who + "nsigma must be finite and >= 0");
+    if (!(cap > 0.0 && cap < 0.5))
+        return fail(ctx, SCVX_ERR_ARG, who + (thrust_call ? "cap must lie in (0, 0.5), a fraction of Tmax - Tmin"
+                                                          : "cap must lie in (0, 0.5), a fraction of the constraint's width"));
+    if (which == 0u || (which & ~(unsigned)SCVX_MARGIN_ALL))
+        return fail(ctx, SCVX_ERR_ARG, "margins from cov: which must be a non-empty mask of SCVX_MARGIN_*");
     if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
     if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
     const size_t n0 = (size_t)b->B * 196, np = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N;
@@ -992,16 +1066,31 @@ int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const d
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     SCVX_HIP(ctx, b->deriv_f ? scvx::launch_cov_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st)
                              : scvx::launch_cov_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st));
-    hipLaunchKernelGGL(scvx::margins_from_psig_kernel, dim3(b->B), dim3(64), 0, st, b->B, b->K, b->cov_psig, nsigma,
-                       cap * (b->C.Tmax - b->C.Tmin), b->marg);
+    const bool path = (which & ~(unsigned)SCVX_MARGIN_THRUST) != 0u;
+    if (path && !b->pmarg_on)   // "as they are" of an unselected path constraint of a batch that has none: 0
+        SCVX_HIP(ctx, hipMemsetAsync(b->pmarg, 0, (size_t)b->B * (b->K + 1) * SCVX_PMARG_N * 8, st));
+    const scvx::MarginCaps capw{cap * (b->C.Tmax - b->C.Tmin), cap * (b->C.mwet - b->C.mdry), cap * b->C.sqcm, cap * b->C.omMax, cap, b->C.itan};
+    hipLaunchKernelGGL(scvx::margins_from_psig_kernel, dim3(b->B), dim3(64), 0, st, b->B, b->K, b->cov_psig, b->x, nsigma, capw, which, b->marg,
+                       b->pmarg);
     SCVX_HIP(ctx, hipGetLastError());
-    b->marg_on = true;
+    if (which & SCVX_MARGIN_THRUST) b->marg_on = true;
+    if (path) b->pmarg_on = true;
     SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, st));   // see scvx_batch_set_thrust_margins
     if (psig) {
         SCVX_HIP(ctx, hipMemcpyAsync(psig, b->cov_psig, np * 8, hipMemcpyDeviceToHost, st));
         SCVX_HIP(ctx, hipStreamSynchronize(st));
     }
     return SCVX_OK;
+}
+
+int scvx_batch_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
+                                const double* w14, double nsigma, double cap, unsigned which, double* psig) {
+    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false);
+}
+
+int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
+                                       const double* w14, double nsigma, double cap, double* psig) {
+    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, SCVX_MARGIN_THRUST, psig, true);
 }
 
 int scvx_batch_replan(scvx_batch* b) {

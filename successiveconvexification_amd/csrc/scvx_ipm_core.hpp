@@ -315,6 +315,7 @@ struct Layout {
         n += (size_t)(K + 1);            // tmx
         n += 64;                         // scalars
         n += (size_t)nv + ny + 2 * (size_t)nc + 8;   // warm-start iterate (Vw, yw, Sw, Zw) + its header
+        n += (size_t)4 * (K + 1);        // pth (mass floor, glide back-off, tilt bound, rate bound per node)
         return n;
     }
 };
@@ -607,6 +608,12 @@ struct Solver {
 #endif
     double cur_gate;   // max(pres, relgap) of the current iterate: refinement only pays in the endgame (dres is left out:
                        // an inaccurate solve RAISES it, and must not switch the refinement off)
+    // The members below came last and stay last: every member above keeps the place in the frame it had before them.
+    // The path constants of node k less its back-offs (set_path_margins), four per-node arrays behind one pointer, interleaved so
+    // that a node's four values sit in one 32-byte line: pth[4 k + {0, 1, 2, 3}] = mdry + mass_k, glide_k, sqcm - tilt_k, omMax - rate_k
+    gptr pth;
+    cgptr pmarg = nullptr; // this trajectory's path back-offs [K+1][4] (mass, glide, tilt, rate), or null: none
+    cdptr icp;   // solve()'s ic, read back from the frame by every attempt of the ladder rather than held in registers across them
 
     SCVX_HD Solver(Ex& e, const Consts& c) : ex(e), C(c) {
         L.init(c.K, c.vmax > 0.0, NU);
@@ -632,6 +639,7 @@ struct Solver {
         uhat = w; w += 3 * (K + 1); lb0 = w; w += (K + 1); tmx = w; w += (K + 1);
         w += 64;   // scalars (unused slots kept for layout stability)
         wh = w; w += 8; Vw = w; w += nv; yw = w; w += ny; Sw = w; w += nc; Zw = w; w += nc;
+        pth = w; w += 4 * (K + 1);   // last: every array above keeps the offset it had before the path values
     }
 
     // ---- fixed-component masks (rocketland.jl:109-115) ----
@@ -817,17 +825,17 @@ struct Solver {
             for (int c = 0; c < NU; c++) u[c] = af * ubar[NU * k + c] + du[c];
             if (k < K) {
                 gptr g = out + L.o_gs + 3 * k;
-                g[0] = x[1] * C.itan; g[1] = x[2]; g[2] = x[3];
+                g[0] = x[1] * C.itan - af * pth[4 * k + 1]; g[1] = x[2]; g[2] = x[3];
                 gptr t = out + L.o_tilt + 3 * k;
-                t[0] = af * C.sqcm; t[1] = x[9]; t[2] = x[10];
+                t[0] = af * pth[4 * k + 2]; t[1] = x[9]; t[2] = x[10];
                 gptr r = out + L.o_rate + 4 * k;
-                r[0] = af * C.omMax; r[1] = x[11]; r[2] = x[12]; r[3] = x[13];
+                r[0] = af * pth[4 * k + 3]; r[1] = x[11]; r[2] = x[12]; r[3] = x[13];
                 if (k < L.ndp) {
                     gptr d = out + L.o_dp + 4 * k;
                     d[0] = af * C.vmax; d[1] = x[4]; d[2] = x[5]; d[3] = x[6];
                 }
             }
-            if (k >= 1) out[L.o_mass + (k - 1)] = x[0] - af * C.mdry;
+            if (k >= 1) out[L.o_mass + (k - 1)] = x[0] - af * pth[4 * k];
             gptr tb = out + L.o_tb + 4 * k;
             tb[0] = af * tmx[k]; tb[1] = u[0]; tb[2] = u[1]; tb[3] = u[2];
             gptr tc = out + L.o_tc + 4 * k;
@@ -1051,16 +1059,16 @@ struct Solver {
             cgptr dx = v + 14 * k; cdptr xb = xbar + 14 * k;
             const int i1 = gs ? 2 : 9, i2 = gs ? 3 : 10;
             const double x1 = af * xb[1] + dx[1];
-            o[0] = gs ? x1 * C.itan : af * C.sqcm;
+            o[0] = gs ? x1 * C.itan - af * pth[4 * k + 1] : af * pth[4 * k + 2];
             o[1] = af * xb[i1] + dx[i1];
             o[2] = af * xb[i2] + dx[i2];
         } else if constexpr (GRP == G_RATE) {
             cgptr dx = v + 14 * q; cdptr xb = xbar + 14 * q;
-            o[0] = af * C.omMax;
+            o[0] = af * pth[4 * q + 3];
             for (int j = 0; j < 3; j++) o[1 + j] = af * xb[11 + j] + dx[11 + j];
         } else if constexpr (GRP == G_MASS) {
             const int k = q + 1;
-            o[0] = (af * xbar[14 * k] + v[14 * k]) - af * C.mdry;
+            o[0] = (af * xbar[14 * k] + v[14 * k]) - af * pth[4 * k];
         } else if constexpr (GRP == G_T4) {
             const bool tb = q <= K;
             const int k = tb ? q : q - (K + 1);
@@ -3672,13 +3680,17 @@ struct Solver {
     // per-node back-offs of the thrust band for the solves that follow: m [K+1][2] = (lo_k, hi_k) >= 0, or null for none.
     // The rows become  Tmin + lo_k <= uhat_k' u_k  and  |u_k| <= Tmax - hi_k  (read once, in solve()'s set-up).
     SCVX_HD void set_margins(cgptr m) { marg = m; }
+    // per-node back-offs of four path constraints for the solves that follow: m [K+1][4] = (mass, glide, tilt, rate) >= 0, or null.
+    // The rows become  m_k >= mdry + mass_k,  |r_k[2:3]| <= r_k[1] / tan(gammaGs) - glide_k,  |q_k[2:3]| <= sqcm - tilt_k  and
+    // |w_k| <= omMax - rate_k  (read once, in solve()'s set-up; an entry whose node has no such row is not read by any row).
+    SCVX_HD void set_path_margins(cgptr m) { pmarg = m; }
 
     // ---- the solve.  ic: (rIi, vIi) of this trajectory.  Outputs in V (dx, du, nu, s, ...). ----
     // warm: the previous solve in this workspace was for the same (xbar, ubar, endpoint, D) -- the step it belonged to was
     // rejected -- so its saved iterate may be used as the starting point
     SCVX_HD Result solve(cdptr xbar_, cdptr ubar_, cdptr endpoint_, dcptr D_,
                          double rk_, cdptr ic, gptr work, bool warm = false) {
-        xbar = xbar_; ubar = ubar_; endpoint = endpoint_; D = D_; rk = rk_;
+        xbar = xbar_; ubar = ubar_; endpoint = endpoint_; D = D_; rk = rk_; icp = ic;
         SCVX_TS(tTot_);
         carve(work);
         const int K = L.K;
@@ -3696,6 +3708,11 @@ struct Solver {
             // without back-offs both arrays hold the constants: every product below is the one formed from C.Tmin / C.Tmax
             lb0[k] = (marg ? C.Tmin + marg[2 * k] : C.Tmin) - un;
             tmx[k] = marg ? C.Tmax - marg[2 * k + 1] : C.Tmax;
+            // ... and so do the four path values of the node: mdry, 0, sqcm, omMax
+            pth[4 * k] = pmarg ? C.mdry + pmarg[4 * k] : C.mdry;
+            pth[4 * k + 1] = pmarg ? pmarg[4 * k + 1] : 0.0;
+            pth[4 * k + 2] = pmarg ? C.sqcm - pmarg[4 * k + 2] : C.sqcm;
+            pth[4 * k + 3] = pmarg ? C.omMax - pmarg[4 * k + 3] : C.omMax;
         }
         ex.sync();
         // The ladder.  A solve that ends on its numerical floor above the tolerance (status 1 / 2 / 3) is run again from the cold
@@ -3719,7 +3736,7 @@ struct Solver {
             const int a = attempt < 8 ? attempt : 7;
             p_step_frac = r_step[a]; p_init_shift = r_shift[a]; p_init_balance = r_bal[a]; p_mu_floor = r_floor[a];
             p_sigma_cube = a == 2 || a == 6;
-            res = attempt_solve(ic, warm && attempt == 0);
+            res = attempt_solve(icp, warm && attempt == 0);
             iters_all += res.iters;
             if (attempt == 0) first_warmed = res.warmed;
             if (!(res.status >= 1 && res.status <= 3) || attempt >= C.retries) { res.attempts = attempt + 1; break; }

@@ -672,7 +672,7 @@ template <class Ex, class DS = double, int NU = 3>
 __device__ __forceinline__ void socp_body(const ipm::Consts& Cin, int B, size_t work_stride, const double* x, const double* u,
                                           const double* endpoint, const DS* deriv, const double* rk, const double* ic,
                                           const int* active, double* work, double* sol, double* nu, double* info,
-                                          const int* step_status, double* ttr, double* acc, const double* marg) {
+                                          const int* step_status, double* ttr, double* acc, const double* marg, const double* pmarg) {
     const int b = blockIdx.x;
     if (b >= B) return;
     if (active && !active[b]) return;
@@ -716,6 +716,8 @@ __device__ __forceinline__ void socp_body(const ipm::Consts& Cin, int B, size_t 
     const bool warm = C.warm && step_status[b] == SCVX_ST_REJECTED && ttr[b] < 1e300;
     // per-node back-offs of the thrust band [B][K+1][2] (scvx_batch_set_thrust_margins), or null
     S.set_margins(marg ? (ipm::cgptr)(marg + (size_t)b * (K + 1) * 2) : (ipm::cgptr) nullptr);
+    // per-node back-offs of the mass, glide-slope, tilt and rate rows [B][K+1][4] (scvx_batch_set_path_margins), or null
+    S.set_path_margins(pmarg ? (ipm::cgptr)(pmarg + (size_t)b * (K + 1) * 4) : (ipm::cgptr) nullptr);
     const ipm::Result r = S.solve((ipm::cgptr)(x + (size_t)b * (K + 1) * 14), (ipm::cgptr)(u + (size_t)b * (K + 1) * NU),
                                   (ipm::cgptr)(endpoint + (size_t)b * K * 14), (typename ipm::gp<DS>::cptr)(deriv + (size_t)b * K * (14 * (14 + 2 * NU + 1))), rk[b],
                                   (ipm::cgptr)(ic + (size_t)b * 6), (ipm::gptr)(work + (size_t)b * work_stride), warm);
@@ -762,8 +764,9 @@ __global__ __launch_bounds__(64, SCVX_K4_OCC) void socp_kernel_t(ipm::Consts C, 
                                                   double* __restrict__ sol, double* __restrict__ nu,
                                                   double* __restrict__ info, const int* __restrict__ step_status,
                                                   double* __restrict__ ttr, double* __restrict__ acc,
-                                                  const double* __restrict__ marg) {
-    socp_body<WaveExT<NU>, DS, NU>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg);
+                                                  const double* __restrict__ marg,
+                                                  const double* __restrict__ pmarg) {
+    socp_body<WaveExT<NU>, DS, NU>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg, pmarg);
 }
 // NW wavefronts per trajectory (batches that cannot fill the chip with one wavefront each)
 // Compiled for 2 wavefronts per SIMD like socp_kernel (248 VGPRs, no spills; unconstrained the compiler takes 274 = one
@@ -780,8 +783,9 @@ __global__ __launch_bounds__(64 * NW, SCVX_K4_BLOCK_OCC) void socp_block_kernel(
                                                   double* __restrict__ sol, double* __restrict__ nu,
                                                   double* __restrict__ info, const int* __restrict__ step_status,
                                                   double* __restrict__ ttr, double* __restrict__ acc,
-                                                  const double* __restrict__ marg) {
-    socp_body<BlockEx<NW, NU>, DS, NU>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg);
+                                                  const double* __restrict__ marg,
+                                                  const double* __restrict__ pmarg) {
+    socp_body<BlockEx<NW, NU>, DS, NU>(C, B, work_stride, x, u, endpoint, deriv, rk, ic, active, work, sol, nu, info, step_status, ttr, acc, marg, pmarg);
 }
 
 // what a launch of the conic solve needs from the batch (scvx_batch.hip fills it; scvx_socp_fin.hip launches the NU = 5 kernels)
@@ -797,6 +801,7 @@ struct SocpLaunch {
     const int* status;
     double *ttr, *acc;
     const double* marg;        // per-node thrust back-offs [B][K+1][2], or null
+    const double* pmarg;       // per-node path back-offs [B][K+1][4] (mass, glide, tilt, rate), or null
     hipStream_t stream;
 };
 void launch_socp_fin(const SocpLaunch& a, int waves);   // scvx_socp_fin.hip

@@ -8,10 +8,10 @@ template <int NW>
 static void launch_block5(const SocpLaunch& a) {
     if (a.deriv_f)
         hipLaunchKernelGGL((socp_block_kernel<NW, float, 5>), dim3(a.B), dim3(64 * NW), 0, a.stream, a.C, a.B, a.work_stride, a.x, a.u, a.endpoint,
-                           a.deriv_f, a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg);
+                           a.deriv_f, a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg, a.pmarg);
     else
         hipLaunchKernelGGL((socp_block_kernel<NW, double, 5>), dim3(a.B), dim3(64 * NW), 0, a.stream, a.C, a.B, a.work_stride, a.x, a.u, a.endpoint,
-                           a.deriv, a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg);
+                           a.deriv, a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg, a.pmarg);
 }
 
 void launch_socp_fin(const SocpLaunch& a, int waves) {
@@ -19,10 +19,10 @@ void launch_socp_fin(const SocpLaunch& a, int waves) {
     else if (waves == 2) launch_block5<2>(a);
     else if (a.deriv_f)
         hipLaunchKernelGGL((socp_kernel_t<float, 5>), dim3(a.B), dim3(64), 0, a.stream, a.C, a.B, a.work_stride, a.x, a.u, a.endpoint, a.deriv_f,
-                           a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg);
+                           a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg, a.pmarg);
     else
         hipLaunchKernelGGL((socp_kernel_t<double, 5>), dim3(a.B), dim3(64), 0, a.stream, a.C, a.B, a.work_stride, a.x, a.u, a.endpoint, a.deriv,
-                           a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg);
+                           a.rk, a.ic, a.mask, a.work, a.sol, a.nu, a.info, a.status, a.ttr, a.acc, a.marg, a.pmarg);
 }
 
 }  // namespace scvx
