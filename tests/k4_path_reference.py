@@ -9,7 +9,12 @@ Yardstick Y(case, depth, group): the larger of
   * the distance between the twin's parity build (-O2 -ffp-contract=off) and its native build (-O3 -march=native, contraction on),
   * the distance between the parity twin and itself with every entry of deriv and endpoint multiplied by 1 + 2^-52 U(-1, 1)
     (three seeded draws),
-per group, maximised over the trajectories: dx, du, dsigma, nu by largest absolute difference, merit and pobj relative."""
+per group, maximised over the trajectories: dx, du, dsigma, nu by largest absolute difference, merit and pobj relative.
+
+ENDGAME_CASES is a second, separate table: the same comparison at iterates of runs that converge (tests/endgame_reference.py, fixture
+tests/golden/oracle_endgame_runs.npz), with the trust radius of the recorded step instead of create_initial's 100; its yardstick is
+tests/golden/k4_endgame_yardstick.npz (tests/golden/make_k4_path_yardstick.py endgame).  CASES and k4_path_yardstick.npz do not depend on it."""
+import functools
 import os
 from dataclasses import replace
 
@@ -52,8 +57,57 @@ CASES = {
 DROPPED_DEPTHS = {c: (2,) for c in ("exo K=50", "exo K=8", "exo K=9", "fins K=50", "fins K=9", "float tiles", "aero K=50")}
 
 
+# ---- the converging regime: B = 2 as pairs (step of run exo2, step of run exo3), steps 1-based, -1 = the run's last; the aero case B = 1.
+# Both sides solve at 1e-9 (the tolerance of the fixture's subproblem record: up to 26 iterations), hence the two further depths.
+ENDGAME_FIXTURE = os.path.join(GOLDEN, "k4_endgame_yardstick.npz")
+ENDGAME_DEPTHS = (1, 2, 3, 4, 6, 8, 10, 12, 16, 20, FULL)
+ENDGAME_TOL = 1e-9
+ENDGAME_CASES = {
+    "trust region binds": dict(runs=("exo2", "exo3"), steps=(9, 2)),
+    "nu at the vertex": dict(runs=("exo2", "exo3"), steps=(11, 4)),
+    "last step": dict(runs=("exo2", "exo3"), steps=(13, -1)),
+    "nu at the vertex, float tiles": dict(runs=("exo2", "exo3"), steps=(11, 4), lin32=True),
+    "aero, last step": dict(runs=("aero2",), steps=(13,)),
+}
+# the rule of DROPPED_DEPTHS, and one more: a truncated depth at which some trajectory of the twin has already finished (status 0) is
+# dropped too -- a finished solve is compared at full depth, where an iteration count one off has its own rule.  Decided on the CPU
+# (tests/test_endgame_cpu.py), never on the GPU.
+# Depth 20: the trajectories of these cases finish after 17 to 19 iterations.  Depths 4 and 6 of "last step": iterations 4 to 6 of the
+# exo3 trajectory do not improve on the third (merit 8.8188 after each).
+ENDGAME_DROPPED_DEPTHS = {"trust region binds": (20,), "nu at the vertex": (20,), "nu at the vertex, float tiles": (20,), "last step": (4, 6)}
+
+
+def spec_of(case):
+    return CASES[case] if case in CASES else ENDGAME_CASES[case]
+
+
+def all_depths(case):
+    return DEPTHS if case in CASES else ENDGAME_DEPTHS
+
+
+def tol_of(case):
+    return 1e-8 if case in CASES else ENDGAME_TOL
+
+
 def depths_of(case):
-    return tuple(n for n in DEPTHS if n not in DROPPED_DEPTHS.get(case, ()))
+    drop = DROPPED_DEPTHS.get(case, ()) if case in CASES else ENDGAME_DROPPED_DEPTHS.get(case, ())
+    return tuple(n for n in all_depths(case) if n not in drop)
+
+
+@functools.lru_cache(maxsize=None)
+def endgame_states(case):
+    """(ic [B][6], x, u, sigma, rk [B]) of an endgame case: the recorded pre-step states (read once per case; do not write to them)"""
+    import endgame_reference as er
+    g = er.load()
+    c = ENDGAME_CASES[case]
+    st = [er.state(g, r, (er.steps_of(g, r) if s < 0 else s) - 1) for r, s in zip(c["runs"], c["steps"])]
+    return (np.stack([g[r + "_ic"] for r in c["runs"]]), np.stack([s[0] for s in st]), np.stack([s[1] for s in st]), np.array([s[2] for s in st]),
+            np.array([s[3] for s in st]))
+
+
+def rk_of(case):
+    """the trust radius the case's subproblem is solved under: create_initial's 100, or the recorded steps' [B]"""
+    return 100.0 if case in CASES else endgame_states(case)[4]
 
 
 def key(case):
@@ -80,6 +134,9 @@ def _fuzz_class(cls):
 def oracle_problem(case):
     """(oracle DescentProblem, ic [B][6], back-offs [B][K+1][2] or None, nsub) of a case"""
     from oracle import model
+    if case in ENDGAME_CASES:
+        import endgame_reference as er
+        return er.oracle_problem(ENDGAME_CASES[case]["runs"][0]), endgame_states(case)[0], None, er.NSUB
     c = CASES[case]
     marg = None
     nsub = c["nsub"]
@@ -110,6 +167,9 @@ def device_problem(case):
     """the product's DescentProblem of a case (successiveconvexification_amd.sample_problems), matching oracle_problem(case)"""
     from successiveconvexification_amd import sample_problems as sp
     from successiveconvexification_amd.defns import AtmosphericData
+    if case in ENDGAME_CASES:
+        import endgame_reference as er
+        return er.device_problem(ENDGAME_CASES[case]["runs"][0])
     c = CASES[case]
     if c["model"] == "exo":
         pp = sp.base_prob_scaled
@@ -130,10 +190,15 @@ def device_problem(case):
 
 
 def cpu_inputs(case):
-    """create_initial's straight-line iterate and the ORACLE's linearisation of it: (po, ic, marg, xbar, ubar, sigma, endpoint, deriv)"""
+    """create_initial's straight-line iterate (an endgame case: the recorded iterates) and the ORACLE's linearisation of it:
+    (po, ic, marg, xbar, ubar, sigma, endpoint, deriv)"""
     from oracle import dynamics as od, model
     po, ic, marg, nsub = oracle_problem(case)
     B, K = ic.shape[0], po.K
+    if case in ENDGAME_CASES:
+        _, x, u, sg, _ = endgame_states(case)
+        e, d = od.linearize(od.Params(po), x, u, sg, 1.0 / (K + 1), nsub)
+        return po, ic, marg, x, u, sg, e, d
     x = np.zeros((B, K + 1, 14))
     u = np.zeros((B, K + 1, po.nu))
     for t in range(B):
@@ -146,7 +211,8 @@ def cpu_inputs(case):
 def run_twin(case, po, ic, marg, xb, ub, e, d, depth, **kw):
     """the twin (whichever build oracle.use_native selected) stopped after `depth` iterations, one attempt"""
     from oracle import port
-    return port.socp(po, xb, ub, e, d, 100.0, ic, max_iter=int(depth), retries=0, lin32=bool(CASES[case].get("lin32")), marg=marg, **kw)
+    return port.socp(po, xb, ub, e, d, rk_of(case), ic, tol=tol_of(case), max_iter=int(depth), retries=0, lin32=bool(spec_of(case).get("lin32")), marg=marg,
+                     **kw)
 
 
 def _rel(a, b):
@@ -189,11 +255,12 @@ def perturbed(e, d, seed):
     return e * (1.0 + EPS * rng.uniform(-1.0, 1.0, e.shape)), d * (1.0 + EPS * rng.uniform(-1.0, 1.0, d.shape))
 
 
-def measure(case, depths=DEPTHS):
+def measure(case, depths=None):
     """The yardstick of a case on this machine, from the twin alone.  Returns dict(native, perturb [depth][group], iters, status
     [depth][B], merit [depth][B], native_iters, native_status)."""
     import oracle
     oracle.use_native(False)
+    depths = all_depths(case) if depths is None else depths
     po, ic, marg, xb, ub, sg, e, d = cpu_inputs(case)
     par, per = {}, {}
     for n in depths:
@@ -213,7 +280,7 @@ def measure(case, depths=DEPTHS):
 
 
 def yardstick(case, fixture=None):
-    """Y [depth of DEPTHS][group] of a case from the committed fixture"""
-    g = np.load(FIXTURE) if fixture is None else fixture
+    """Y [depth of all_depths(case)][group] of a case from the committed fixture"""
+    g = np.load(FIXTURE if case in CASES else ENDGAME_FIXTURE) if fixture is None else fixture
     k = key(case)
     return np.maximum(g["native_" + k], g["perturb_" + k])

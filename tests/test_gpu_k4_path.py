@@ -40,114 +40,25 @@ Measured on one MI355X when the test was added (profiles/k4_path_parity.md): eve
 solves with another iteration count than the twin, worst distance / bound 0.37 (1 / 2 / 4 wavefronts: 0.22 / 0.37 / 0.33) -- the two-ended
 executors need no bound of their own.
 
+The device side of the comparison is tests/k4_path_device.py (shared with tests/test_gpu_endgame.py, which adds rules of its own for
+finished solves; none applies here).
 Every comparison prints its figures before it asserts (one markdown row per case, executor and depth: profiles/k4_path_parity.md)."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
+import k4_path_device as kd
 import k4_path_reference as kp
 
 pytestmark = pytest.mark.gpu
 
-WAVES = ("1", "2", "4")
-_RUNS = {}          # (case, waves) -> list of rows; filled once per pair
 
-
-def _set_depth(b, n):
-    from successiveconvexification_amd import _lib
-    o = _lib.ScvxSolverOpts()
-    b._L.scvx_solver_default_opts(C.byref(o))
-    o.max_iter, o.retries = int(n), 0
-    _lib.check(b.cache.handle, b._L.scvx_batch_set_solver(b.handle, C.byref(o)), "scvx_batch_set_solver")
-
-
-def _run(case, waves):
-    """every depth of one case on one executor: the device and the parity twin on the device's linearisation.  Returns rows of
-    dict(depth, dist, bound, status / iters of both sides, keep, per-trajectory distance at full depth); nothing is asserted here."""
-    if (case, waves) in _RUNS:
-        return _RUNS[(case, waves)]
-    import oracle
-    from successiveconvexification_amd.batch import ScvxBatch
-    from successiveconvexification_amd.dynamics import IntegratorCache
-    oracle.use_native(False)
-    spec = kp.CASES[case]
-    po, ic, marg, nsub = kp.oracle_problem(case)
-    pp = kp.device_problem(case)
-    B, K, NU = ic.shape[0], po.K, po.nu
-    Y = kp.yardstick(case)
-    c = IntegratorCache(pp, npts=nsub)
-    b = ScvxBatch(c, B)
-    if spec.get("lin32"):
-        b.set_linearization_f32(True)
-    b.init(ic)
-    if marg is not None:
-        b.set_thrust_margins(marg[..., 0], marg[..., 1])
-    xb, ub, sg = b.trajectory()
-    e, d = b.linearization()
-    rows = []
-    for n in kp.depths_of(case):
-        _set_depth(b, n)
-        x, u, snew, nu = b.socp_solve()
-        st, its, merit, pobj = b.solver_stats()
-        tw = kp.run_twin(case, po, ic, marg, xb, ub, e, d, n)
-        keep = tw["status"] != 5
-        dev = dict(dx=x, du=u, ds=snew, nu=nu, merit=merit, pobj=pobj)
-        ref = dict(dx=xb + tw["dx"], du=ub + tw["du"], ds=sg + tw["ds"], nu=tw["nu"], merit=tw["merit"], pobj=tw["pobj"])
-        i = kp.DEPTHS.index(n)
-        bound = np.maximum(kp.FACTOR * Y[i], kp.floor(K, NU, kp.magnitudes(tw, keep))) if n != kp.FULL else kp.FACTOR * Y[i]
-        per = np.array([kp.distance(dev, ref, np.arange(B) == t) if keep[t] else np.zeros(len(kp.GROUPS)) for t in range(B)])
-        rows.append(dict(depth=n, dist=kp.distance(dev, ref, keep), bound=bound, st=st.copy(), its=its.copy(), tst=tw["status"], tits=tw["iters"],
-                         keep=keep, per=per))
-    b.close(), c.close()
-    _RUNS[(case, waves)] = rows
-    return rows
-
-
-def _print(case, waves, r):
-    same = r["keep"] & (r["its"] == r["tits"])
-    d = r["per"][same].max(axis=0) if (r["depth"] == kp.FULL and same.any()) else r["dist"]
-    ratio = float((d / np.maximum(r["bound"], 1e-300)).max())
-    print("| %s | %s | %s | %s | %.2f | %s | %s |" % (case, waves, "full" if r["depth"] == kp.FULL else r["depth"], " | ".join("%.1e" % v for v in d), ratio,
-                                                  " ".join(str(v) for v in r["its"]), " ".join(str(v) for v in r["tits"])))
-    return ratio
-
-
-@pytest.mark.parametrize("waves", WAVES)
+@pytest.mark.parametrize("waves", kd.WAVES)
 @pytest.mark.parametrize("case", list(kp.CASES))
 def test_device_takes_the_twins_path(case, waves, monkeypatch):
     monkeypatch.setenv("SCVX_K4_WAVES", waves)
-    rows = _run(case, waves)
-    print("\n| case | wavefronts | depth | dx | du | dsigma | nu | merit | pobj | worst ratio to the bound | device iterations | twin iterations |")
-    ratios = [_print(case, waves, r) for r in rows]
-    print("%s, %s wavefront(s): worst ratio of a device / twin distance to max(10 Y, floor) %.2f" % (case, waves, max(ratios)))
-    for r in rows:
-        n, keep = r["depth"], r["keep"]
-        assert np.array_equal(r["st"] == 5, r["tst"] == 5), (n, r["st"], r["tst"])
-        if n != kp.FULL:
-            assert np.array_equal(r["st"], r["tst"]) and np.array_equal(r["its"][keep], r["tits"][keep]), (n, r["st"], r["tst"], r["its"], r["tits"])
-            assert np.all(r["dist"] <= r["bound"]), (n, r["dist"], r["bound"])
-        else:
-            assert np.all(r["st"][keep] == 0) and np.all(r["tst"][keep] == 0), (r["st"], r["tst"])
-            diff = np.abs(r["its"] - r["tits"])[keep]
-            assert diff.max(initial=0) <= 1, (r["its"], r["tits"])          # how MANY may differ: the cap below
-            for t in np.nonzero(keep)[0]:
-                if r["its"][t] == r["tits"][t]:
-                    assert np.all(r["per"][t] <= r["bound"]), (t, r["per"][t], r["bound"])
-                else:
-                    assert np.all(r["per"][t][:4] < 1e-6), (t, r["per"][t])
+    kd.check_path(case, waves)
 
 
 def test_iteration_counts_of_full_solves_equal_the_twins_within_the_cap(monkeypatch):
     """over all (case, executor, trajectory) triples: at most 5 % of the full solves take another iteration count than the twin, and
     none differs by more than 1.  A condition, not a measurement: the twin's two builds differ in 0 of 320."""
-    total = differ = worst = 0
-    for case in kp.CASES:
-        for waves in WAVES:
-            monkeypatch.setenv("SCVX_K4_WAVES", waves)
-            r = _run(case, waves)[-1]
-            assert r["depth"] == kp.FULL
-            diff = np.abs(r["its"] - r["tits"])[r["keep"]]
-            total, differ, worst = total + diff.size, differ + int((diff != 0).sum()), max(worst, int(diff.max(initial=0)))
-    print("full solves with another iteration count than the twin: %d of %d (largest difference %d)" % (differ, total, worst))
-    assert worst <= 1 and differ <= 0.05 * total, (differ, total, worst)
+    kd.check_counts(kp.CASES, monkeypatch)
