@@ -397,6 +397,19 @@ int scvx_nav_cov_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const dou
 int scvx_nav_cov_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv, const double *gain,
                           const double *S0, const double *N0, int m, const double *H, const double *rm, const double *w14,
                           double *report, double *navrep, double *sig, double *navsig, double *kf, double *joint);
+/* The same launch, keeping what the margins are made of (scvx_cov_path_sigma_f64 for the closed loop flown on an estimate): psig
+ * [B][K+1][SCVX_PSIG_N] = s = sqrt(c' Xi_k[z z] c) of the five path functions at every node -- the TRUTH block of the joint, before
+ * the update at the node (which does not touch it): the constraints bind the vehicle, not its estimate.  Same contract: node 0 is 0
+ * and so is a node that the margin skips (undefined gradient); a non-finite tile, gain, S0 or N0 entry makes every row of its own
+ * trajectory NaN, and nothing of another's.  With N0 = 0 the estimate never errs and psig is scvx_cov_path_sigma_f64's to rounding.
+ * Arguments up to navrep as scvx_nav_cov_f64, whose two reports this call leaves bitwise unchanged (max_k psig[k][THRUST] is
+ * S_THRUST); SCVX_ERR_ARG also for a null psig.  The _f64 form is asynchronous on the context's stream. */
+int scvx_nav_path_sigma_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                            const double *gain_dev, const double *S0_dev, const double *N0_dev, int m, const double *H,
+                            const double *rm, const double *w14, double *report_dev, double *navrep_dev, double *psig_dev);
+int scvx_nav_path_sigma_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv,
+                                 const double *gain, const double *S0, const double *N0, int m, const double *H, const double *rm,
+                                 const double *w14, double *report, double *navrep, double *psig);
 /* scvx_track_fly_f64 with the law fed an estimate: nav [B][K][14] is the error eps+_k of the estimate at node k, and the deviation
  * is formed as z = [(x_fly - nav_k) - xbar_k; u_k - ubar_k], so an all-zero nav reproduces scvx_track_fly_f64 bit for bit.  nav must
  * not be NULL (SCVX_ERR_ARG): without one, call scvx_track_fly_f64.  Everything else as there. */
@@ -600,7 +613,7 @@ int scvx_batch_replan(scvx_batch *b);
  * like the thrust ones they ARE part of a checkpoint that the caller must carry (scvx_batch_get_path_margins reads them: zeros when
  * none are set).
  * OUT OF SCOPE: back-offs of the gimbal cone, the dynamic-pressure cone and the fin cone (psig has no column for them), and back-offs
- * taken from the navigation analysis (scvx_batch_nav_cov). */
+ * on the constraints of the ESTIMATE.  Back-offs taken from the navigation analysis exist: scvx_batch_margins_from_nav below. */
 #define SCVX_PMARG_N 4
 #define SCVX_PMARG_MASS 0
 #define SCVX_PMARG_GLIDE 1
@@ -626,6 +639,22 @@ int scvx_batch_get_path_margins(scvx_batch *b, double *pm);
 #define SCVX_MARGIN_ALL 31u
 int scvx_batch_margins_from_cov(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
                                 const double *w14, double nsigma, double cap, unsigned which, double *psig);
+/* scvx_batch_margins_from_cov with the s(k) of the NAVIGATION analysis of the batch's current accepted iterate: the law is fed an
+ * estimate, and under navigation errors the truth disperses more than scvx_cov_path_sigma_f64 says (with N0 = S0 and position alone
+ * measured, s_T is about twice as large on the golden plans: a plan backed off 3 sigma by the covariance analysis keeps 1.3).  One
+ * navigation launch (scvx_nav_path_sigma_f64) on the batch's own tiles (double or float) and gains, then the same small kernel:
+ * the same widths and caps, the same forced zeros, zeros for a trajectory with a NaN in a selected psig column; the constraints
+ * that are not selected stay as they are (zeros on a batch that had no path back-offs).  N0 [B][14][14], H [m][14] and rm [m] are
+ * host arrays as in scvx_batch_nav_cov; everything else, psig = NULL and the dropped warm-start state included, as
+ * scvx_batch_margins_from_cov.  Every check comes before anything is enqueued: SCVX_ERR_ARG for what that call refuses and for what
+ * scvx_batch_nav_cov refuses of N0, m, H and rm, and the batch and its back-offs are then as they were.
+ * Limits: FIRST ORDER about the plan; Kf is the optimal gain for the stated model (a mismodelled filter disperses more); no
+ * measurement at node K, and no sigma at node 0 (the handover is where the plan starts: no back-off there); the glide back-off
+ * buys tan(gammaGs) times as many sigma, as above; s(k) depends on the plan, so one round reaches about 2.7 - 3 sigma of headroom
+ * under the navigation report for nsigma = 3 rather than exactly n (repeat the round to tighten it). */
+int scvx_batch_margins_from_nav(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
+                                const double *N0, int m, const double *H, const double *rm, const double *w14, double nsigma,
+                                double cap, unsigned which, double *psig);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

@@ -590,11 +590,13 @@ replan!(b::Batch) = (check(b.cache.ctx, ccall((:scvx_batch_replan, LIB), Cint, (
 # about 2.5 - 3 sigma of headroom for nsigma = 3; a replan may land in another local optimum than a solve from the guess
 # which: the constraints that are tightened (MARGIN_*); with a path constraint among them path_margins(b) holds their back-offs
 function robustify!(b::Batch, S0::Array{Float64,3}; nsigma::Real=3.0, rounds::Int=1, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0,
-                    which::Integer=MARGIN_THRUST)
+                    which::Integer=MARGIN_THRUST, nav=nothing)
     rounds >= 1 || error("rounds >= 1")
     st = Vector{Int32}(undef, b.B); it = Vector{Int32}(undef, b.B); nu = Vector{Float64}(undef, b.B); dj = Vector{Float64}(undef, b.B)
     for _ in 1:rounds
-        if which == MARGIN_THRUST
+        if nav !== nothing   # (N0, H, rm): the s(k) of the loop flown on an estimate (margins_from_nav!)
+            margins_from_nav!(b, S0, nav[1], nav[2], nav[3]; which=which, nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
+        elseif which == MARGIN_THRUST
             thrust_margins_from_cov!(b, S0; nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
         else
             margins_from_cov!(b, S0; which=which, nsigma=nsigma, cap=cap, w=w, q=q, r=r, qf=qf)
@@ -608,7 +610,7 @@ end
 
 # ---- path-constraint back-offs: mass, glide slope, tilt, rate (new) -----------------------------------------------------------
 # include/scvx.h, "path-constraint back-offs".  pm is 4 x (K+1) x B (row PMARG_* + 1 holds that column), read by the conic solve
-# alone; `nothing` clears.  Out of scope: gimbal, dynamic-pressure and fin back-offs, and back-offs from the navigation analysis.
+# alone; `nothing` clears.  Out of scope: gimbal, dynamic-pressure and fin back-offs, and back-offs on the estimate's constraints.
 const PMARG_N = 4
 const PMARG_MASS = 0; const PMARG_GLIDE = 1; const PMARG_TILT = 2; const PMARG_RATE = 3
 const MARGIN_THRUST = UInt32(1); const MARGIN_MASS = UInt32(2); const MARGIN_GLIDE = UInt32(4); const MARGIN_TILT = UInt32(8)
@@ -662,6 +664,52 @@ path_sigma_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cd
     GC.@preserve w check(cache.ctx, ccall((:scvx_cov_path_sigma_f64, LIB), Cint,
         (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), report_dev, psig_dev), "scvx_cov_path_sigma_f64")
+
+# ---- back-offs from the analysis of the loop flown on an estimate (new) --------------------------------------------------------
+# include/scvx.h, scvx_batch_margins_from_nav: margins_from_cov! with the s(k) of the closed loop fed an estimate.  N0 14 x 14 x B,
+# H and rm as navigation(b, ...) takes them.
+function margins_from_nav!(b::Batch, S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm;
+                           which::Integer=MARGIN_ALL, nsigma::Real=3.0, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0, psig::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    size(N0) == (14, 14, b.B) || error("N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    ps = psig ? Array{Float64,3}(undef, PSIG_N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv check(b.cache.ctx, ccall((:scvx_batch_margins_from_nav, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cuint, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), Float64(nsigma),
+        Float64(cap), UInt32(which), _cov_opt(ps)), "scvx_batch_margins_from_nav")
+    return ps
+end
+margins_from_nav(b::Batch, S0, N0, H, rm; kw...) = margins_from_nav!(b, S0, N0, H, rm; kw...)
+
+# psig 5 x (K+1) x B of any plans flown on an estimate (host arrays): (report, navrep, psig)
+function nav_path_sigma(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                        S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm; w=nothing)
+    K = size(x, 2) - 1; B = size(x, 3)
+    size(S0) == (14, 14, B) || error("S0 must be 14 x 14 x B")
+    size(N0) == (14, 14, B) || error("N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    navrep = Matrix{Float64}(undef, NAV_NREP, B)
+    ps = Array{Float64,3}(undef, PSIG_N, K + 1, B)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv check(cache.ctx, ccall((:scvx_nav_path_sigma_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), report, navrep, ps),
+        "scvx_nav_path_sigma_f64_host")
+    return report, navrep, ps
+end
+
+nav_path_sigma_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+                    S0_dev::Ptr{Cdouble}, N0_dev::Ptr{Cdouble}, m::Int, H::Union{Nothing,Matrix{Float64}}, rm::Union{Nothing,Vector{Float64}},
+                    w::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble}, navrep_dev::Ptr{Cdouble}, psig_dev::Ptr{Cdouble}) =
+    GC.@preserve H rm w check(cache.ctx, ccall((:scvx_nav_path_sigma_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, _cov_opt(H), _cov_opt(rm), _cov_opt(w), report_dev, navrep_dev,
+        psig_dev), "scvx_nav_path_sigma_f64")
 
 # multi-GPU (one Julia process per GPU): rank 0 draws the id, the host ships its 128 bytes (Distributed / MPI.jl / a file)
 unique_id() = (id = Vector{UInt8}(undef, 128); ccall((:scvx_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("RCCL unavailable"); id)

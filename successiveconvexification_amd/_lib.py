@@ -150,6 +150,9 @@ SIGNATURES = {
     "scvx_batch_set_path_margins": (C.c_int, [_vp, _dp]),
     "scvx_batch_get_path_margins": (C.c_int, [_vp, _dp]),
     "scvx_batch_margins_from_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint, _dp]),
+    "scvx_batch_margins_from_nav": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint, _dp]),
+    "scvx_nav_path_sigma_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _dp, _dp, _dp, _vp, _vp, _vp]),
+    "scvx_nav_path_sigma_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_comm_probe": (C.c_int, []),
     "scvx_comm_unique_id": (C.c_int, [_vp]),
     "scvx_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

@@ -351,11 +351,34 @@ class ScvxBatch:
         (scvx_batch_margins_from_cov; the others stay as they are): returns psig [B][K+1][5]."""
         return self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
 
-    def path_sigma(self, S0, w=None, q=None, r=None, qf=None):
+    def _margins_from_nav(self, S0, nav, w, q, r, qf, nsigma, cap, want_psig, mask):
+        from .dynamics import _cov_noise, _cov_s0, _nav_arg, _track_weights
+        n0, m, Hm, rmv = _nav_arg(nav, self.B)
+        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
+        s0 = _cov_s0(S0, self.B)
+        wv = _cov_noise(w)
+        psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        self._chk(self._L.scvx_batch_margins_from_nav(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv),
+                                                      float(nsigma), float(cap), int(mask), opt(psig)), "scvx_batch_margins_from_nav")
+        return psig
+
+    def margins_from_nav(self, S0, N0, H, rm, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None):
+        """margins_from_cov with the per-node s(k) of the NAVIGATION analysis of the current accepted iterate, the closed loop flown on
+        an estimate (scvx_batch_margins_from_nav; N0, H, rm as navigation()): the same widths, caps and forced zeros, the constraints
+        that are not selected stay as they are.  Returns psig [B][K+1][5], read off the truth block of the joint covariance."""
+        return self._margins_from_nav(S0, (N0, H, rm), w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
+
+    def path_sigma(self, S0, w=None, q=None, r=None, qf=None, nav=None):
         """psig [B][K+1][5]: per node, one standard deviation of the mass, glide-slope, tilt, rate and thrust-norm path functions
         of the batch's current accepted iterate under its LQR gains (dynamics.cov_path_sigma_batch on the batch's own tiles).  The
-        batch's iterate, scalars and flags are left untouched and so are its thrust back-offs."""
-        from .dynamics import cov_path_sigma_batch
+        batch's iterate, scalars and flags are left untouched and so are its thrust back-offs.  nav = (N0, H, rm): the same of the
+        navigation analysis, the law fed an estimate (dynamics.nav_path_sigma_batch)."""
+        from .dynamics import _nav_arg, cov_path_sigma_batch, nav_path_sigma_batch
+        if nav is not None:
+            n0, _, Hm, rmv = _nav_arg(nav, self.B)
+            x, u, _ = self.trajectory()
+            return nav_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, n0, Hm, rmv, w)[1]
         x, u, _ = self.trajectory()
         return cov_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, w)[1]
 
@@ -365,7 +388,7 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_replan(self.handle), "scvx_batch_replan")
         return self
 
-    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",)):
+    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",), nav=None):
         """Covariance-driven replanning.  Per round: the back-offs lo_k = hi_k = min(nsigma s_T(k), cap (Tmax - Tmin)) from the
         covariance analysis of the current iterate (scvx_batch_thrust_margins_from_cov, nothing returns to the host), replan(),
         solve().  Returns the last solve()'s (status, iters, nu_norm, dJ) plus (lo, hi).  First order, and only as good as Sigma_k;
@@ -373,12 +396,24 @@ class ScvxBatch:
         land in another local optimum than a solve from the straight-line guess.
         constraints: which rows are tightened, any subset of ("thrust", "mass", "glide", "tilt", "rate") or "all"; the path ones
         get min(nsigma s(k), cap width_k) with the widths of scvx_batch_margins_from_cov, and path_margins() reads them afterwards.
-        The return value is the same six for every choice; the default is the call it always was."""
+        The return value is the same six for every choice; the default is the call it always was.
+        nav = (N0, H, rm): the s(k) come from the navigation analysis instead (scvx_batch_margins_from_nav per round), the closed loop
+        flown on an estimate with the measurement H, rm at every node but the last; under navigation errors the covariance analysis'
+        s(k) are too small, and a plan backed off by them keeps less than it shows.  Same limits, and the filter gain is the optimal
+        one for the stated model."""
         if int(rounds) < 1:
             raise ValueError("robustify: rounds >= 1")
         mask = self._margin_mask(constraints)
         thrust_only = mask == _lib.MARGIN_BITS["thrust"]
         out = None
+        if nav is not None:
+            from .dynamics import _nav_arg
+            _nav_arg(nav, self.B)   # a malformed model is refused before the first round
+            for _ in range(int(rounds)):
+                self._margins_from_nav(S0, nav, w, q, r, qf, nsigma, cap, False, mask)
+                self.replan()
+                out = self.solve()
+            return out + self.thrust_margins()
         for _ in range(int(rounds)):
             self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, False, None if thrust_only else mask)
             self.replan()

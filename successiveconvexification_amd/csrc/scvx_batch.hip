@@ -268,6 +268,7 @@ struct scvx_batch {
     double *pmarg = nullptr;  // per-node back-offs of the mass, glide-slope, tilt and rate rows [B][K+1][SCVX_PMARG_N]: read while pmarg_on
     bool pmarg_on = false;    // scvx_batch_set_path_margins / scvx_batch_margins_from_cov set it, NULL and scvx_batch_init clear it
     double *cov_s0 = nullptr, *cov_rep = nullptr, *cov_psig = nullptr;   // scratch of scvx_batch_thrust_margins_from_cov: allocated on first use
+    double *nav_n0 = nullptr, *nav_rep = nullptr;   // scratch of scvx_batch_margins_from_nav on top of the three above: allocated on first use
     double *track_gain = nullptr, *track_p0 = nullptr;   // scratch of scvx_batch_track_*: allocated on first use, freed with the batch
     int *k1skip = nullptr;   // per trajectory: >= SCVX_ST_REJECTED = the reference point did not change in the last step (K1 skips it)
     int *d_nlive = nullptr;  // device-side count of live trajectories (scvx_solve), mirrored asynchronously into pinned h_nlive[2]
@@ -537,7 +538,7 @@ void scvx_batch_destroy(scvx_batch* b) {
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
                     b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip,
-                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig};
+                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig, b->nav_n0, b->nav_rep};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -1037,22 +1038,31 @@ int scvx_batch_get_path_margins(scvx_batch* b, double* pm) {
     return SCVX_OK;
 }
 
-// both covariance-driven calls; thrust_call: scvx_batch_thrust_margins_from_cov, whose refusals keep their wording
+// the navigation model of scvx_batch_margins_from_nav (nullptr: the covariance-driven calls)
+struct NavModel {
+    const double* N0;
+    int m;
+    const double *H, *rm;
+};
+
+// the covariance- and the navigation-driven calls; thrust_call: scvx_batch_thrust_margins_from_cov, whose refusals keep their wording
 static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
-                            double nsigma, double cap, unsigned which, double* psig, bool thrust_call) {
+                            double nsigma, double cap, unsigned which, double* psig, bool thrust_call, const NavModel* nav = nullptr) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
     // every check before anything is enqueued
-    const std::string who = thrust_call ? "thrust margins: " : "margins from cov: ";
+    const std::string who = thrust_call ? "thrust margins: " : nav ? "margins from nav: " : "margins from cov: ";
     if (!S0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (S0)");
+    if (nav && !nav->N0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (N0)");
     if (!(nsigma >= 0.0) || !std::isfinite(nsigma)) return fail(ctx, SCVX_ERR_ARG, who + "nsigma must be finite and >= 0");
     if (!(cap > 0.0 && cap < 0.5))
         return fail(ctx, SCVX_ERR_ARG, who + (thrust_call ? "cap must lie in (0, 0.5), a fraction of Tmax - Tmin"
                                                           : "cap must lie in (0, 0.5), a fraction of the constraint's width"));
     if (which == 0u || (which & ~(unsigned)SCVX_MARGIN_ALL))
-        return fail(ctx, SCVX_ERR_ARG, "margins from cov: which must be a non-empty mask of SCVX_MARGIN_*");
+        return fail(ctx, SCVX_ERR_ARG, (nav ? who : std::string("margins from cov: ")) + "which must be a non-empty mask of SCVX_MARGIN_*");
     if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
+    if (nav && (rc = scvx::check_nav_model(ctx, nav->m, nav->H, nav->rm))) return rc;
     if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
     const size_t n0 = (size_t)b->B * 196, np = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N;
     if (!b->cov_s0) {
@@ -1060,12 +1070,23 @@ static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU,
         SCVX_HIP(ctx, hipMalloc((void**)&b->cov_rep, (size_t)b->B * SCVX_COV_NREP * 8));
         SCVX_HIP(ctx, hipMalloc((void**)&b->cov_psig, np * 8));
     }
+    if (nav && !b->nav_n0) {
+        SCVX_HIP(ctx, hipMalloc((void**)&b->nav_n0, n0 * 8));
+        SCVX_HIP(ctx, hipMalloc((void**)&b->nav_rep, (size_t)b->B * SCVX_NAV_NREP * 8));
+    }
     hipStream_t st = ctx->stream;
     SCVX_HIP(ctx, hipMemcpyAsync(b->cov_s0, S0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));   // the caller's S0 is consumed when the call returns; nothing comes back
+    if (nav) SCVX_HIP(ctx, hipMemcpyAsync(b->nav_n0, nav->N0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));   // the caller's S0 (and N0) is consumed when the call returns; nothing comes back
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    SCVX_HIP(ctx, b->deriv_f ? scvx::launch_cov_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st)
-                             : scvx::launch_cov_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st));
+    if (nav)
+        SCVX_HIP(ctx, b->deriv_f ? scvx::launch_nav_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, b->nav_n0, nav->m,
+                                                             nav->H, nav->rm, w14, b->cov_rep, b->nav_rep, b->cov_psig, st)
+                                 : scvx::launch_nav_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H,
+                                                         nav->rm, w14, b->cov_rep, b->nav_rep, b->cov_psig, st));
+    else
+        SCVX_HIP(ctx, b->deriv_f ? scvx::launch_cov_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st)
+                                 : scvx::launch_cov_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st));
     const bool path = (which & ~(unsigned)SCVX_MARGIN_THRUST) != 0u;
     if (path && !b->pmarg_on)   // "as they are" of an unselected path constraint of a batch that has none: 0
         SCVX_HIP(ctx, hipMemsetAsync(b->pmarg, 0, (size_t)b->B * (b->K + 1) * SCVX_PMARG_N * 8, st));
@@ -1086,6 +1107,13 @@ static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU,
 int scvx_batch_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
                                 const double* w14, double nsigma, double cap, unsigned which, double* psig) {
     return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false);
+}
+
+int scvx_batch_margins_from_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
+                                const double* N0, int m, const double* H, const double* rm, const double* w14, double nsigma, double cap,
+                                unsigned which, double* psig) {
+    const NavModel nav{N0, m, H, rm};
+    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, &nav);
 }
 
 int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,

@@ -116,6 +116,14 @@ hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, co
 hipError_t launch_nav_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
                               const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
                               double* report, double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st);
+// ... with the per-node s of the five path functions kept, read off the truth block Xi_k[z,z]: psig [B][K+1][SCVX_PSIG_N], never nullptr
+// (scvx_nav_path_sigma_f64)
+hipError_t launch_nav_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
+                           double* navrep, double* psig, hipStream_t st);
+hipError_t launch_nav_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                               const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
+                               double* report, double* navrep, double* psig, hipStream_t st);
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm);
 
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],

@@ -18,7 +18,9 @@
 // scvx_batch_set_linearization_f32: widened on load).  H, rm and w ride by value in the kernel argument and are copied to LDS once.
 //
 // The dispersion report is cov_propagate_kernel's, read off the z block (lanes 0..5 the running columns, 6..11 the final ones);
-// lane 12 carries NAV_PEAK, lanes 13..19 the final columns of the navigation report.
+// lane 12 carries NAV_PEAK, lanes 13..19 the final columns of the navigation report.  With PS the s = sqrt(c' Xi_k[z,z] c) that lanes 1..5
+// form at every node for their margins is kept as well (scvx_nav_path_sigma_f64): the truth block before the node's update, which
+// the update does not touch -- the constraints bind the vehicle, not its estimate.
 #include <cmath>
 #include <limits>
 #include "scvx_internal.hpp"
@@ -41,12 +43,15 @@ __device__ __forceinline__ double nav_quad3(const double* S, int n, int i0, int 
     return d + 2.0 * o;
 }
 
-template <typename DS, int NU>
+// PS: 1 = also keep the per-node s of the five path functions (psig [B][K+1][SCVX_PSIG_N], lane - 1 is the column: SCVX_PSIG_MASS, GLIDE,
+// TILT, RATE, THRUST); 0 = the reports alone, and nothing of it is compiled in
+template <typename DS, int NU, int PS = 0>
 __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
                                                      const DS* __restrict__ deriv, const double* __restrict__ gain,
                                                      const double* __restrict__ S0, const double* __restrict__ N0,
                                                      double* __restrict__ report, double* __restrict__ navrep, double* __restrict__ sig,
-                                                     double* __restrict__ navsig, double* __restrict__ kf, double* __restrict__ joint) {
+                                                     double* __restrict__ navsig, double* __restrict__ kf, double* __restrict__ joint,
+                                                     double* __restrict__ psig) {
     constexpr int n = 14 + NU, N = n + 14, mt = 14 + 2 * NU, NC = mt + 1, DSZ = 14 * NC, ND = 14 * mt, NL = NU * n, NN = N * N;
     constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
     constexpr int NR = SCVX_COV_NREP + SCVX_NAV_NREP;
@@ -67,6 +72,7 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
     double* sigb = sig ? sig + (size_t)b * (K + 1) * n : nullptr;
     double* nsb = navsig ? navsig + (size_t)b * (K + 1) * 14 : nullptr;
     double* kfb = kf ? kf + (size_t)b * K * 14 * m : nullptr;
+    double* psb = PS ? psig + (size_t)b * (K + 1) * SCVX_PSIG_N : nullptr;
     const double inf = std::numeric_limits<double>::infinity();
     // Xi_0 = blockdiag((S0 + S0') / 2, 0, (N0 + N0') / 2); tile 0 and gain block 0; H and rm
     for (int e = lane; e < NN; e += 64) {
@@ -119,14 +125,17 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
             bad = fma(tr, 0.0, bad);
             acc0 = nan_max(acc0, nav_sd(tr));
         } else if (k > 0 && lane < 6) {
+            [[maybe_unused]] double sv = 0.0;   // PS: this lane's s at node k (0 where the margin skips the node: an undefined gradient)
             if (lane == 1) {
                 const double s = nav_sd(Xl[0]);
+                if constexpr (PS != 0) sv = s;
                 if (!(s == 0.0)) acc0 = nan_min(acc0, -(c.mdry - pv0) / s);
             } else if (lane == 5) {
                 const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
                 if (!(nr == 0.0)) {
                     const double s = nav_sd(nav_quad3(Xl, N, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
                     acc2 = nan_max(acc2, s);
+                    if constexpr (PS != 0) sv = s;
                     if (!(s == 0.0)) {
                         acc0 = nan_min(acc0, -(nr - c.Tmax) / s);
                         acc1 = nan_min(acc1, -(c.Tmin - nr) / s);
@@ -149,10 +158,14 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
                         q = nav_quad3(Xl, N, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
                     }
                     const double s = nav_sd(q);
+                    if constexpr (PS != 0) sv = s;
                     if (!(s == 0.0)) acc0 = nan_min(acc0, -g / s);
                 }
             }
+            if constexpr (PS != 0) psb[(size_t)k * SCVX_PSIG_N + (lane - 1)] = sv;
         }
+        if constexpr (PS != 0)
+            if (k == 0 && lane >= 1 && lane < 6) psb[lane - 1] = 0.0;   // node 0: no margin reads it
     };
     node_out(0);
     for (int k = 0; k < K; k++) {
@@ -392,23 +405,36 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
     const double flag = Rl[NR] + Rl[NR + 1];
     if (lane < SCVX_COV_NREP) report[(size_t)b * SCVX_COV_NREP + lane] = Rl[lane] + flag;
     else if (lane < NR) navrep[(size_t)b * SCVX_NAV_NREP + lane - SCVX_COV_NREP] = Rl[lane] + flag;
+    if constexpr (PS != 0) {
+        // a non-finite Xi anywhere (either flag) poisons both reports; the rows of this trajectory, and of no other, follow them
+        if (flag != flag)
+            for (int e = lane; e < (K + 1) * SCVX_PSIG_N; e += 64) psb[e] = flag;
+    }
 }
 
 template <typename DS>
 static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv,
                                    const double* gain, const double* S0, const double* N0, int m, const double* H, const double* rm,
                                    const double* w, double* report, double* navrep, double* sig, double* navsig, double* kf,
-                                   double* joint, hipStream_t st) {
+                                   double* joint, hipStream_t st, double* psig = nullptr) {
     const PathK pk = path_constants(ctx->prob);
     NavK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}, {}, {}, m};
     for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
     for (int i = 0; i < m; i++) c.rm[i] = rm[i];
     for (int i = 0; i < m * 14; i++) c.H[i] = H[i];
     const dim3 g((unsigned)B), blk(64);
-    if (ctx->dyn.fin)
-        hipLaunchKernelGGL((nav_cov_kernel<DS, 5>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig, navsig, kf, joint);
-    else
-        hipLaunchKernelGGL((nav_cov_kernel<DS, 3>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig, navsig, kf, joint);
+#define SCVX_NAV_LAUNCH(NU)                                                                                                            \
+    do {                                                                                                                               \
+        if (psig)                                                                                                                      \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig,     \
+                               navsig, kf, joint, psig);                                                                               \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 0>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig,     \
+                               navsig, kf, joint, psig);                                                                               \
+    } while (0)
+    if (ctx->dyn.fin) SCVX_NAV_LAUNCH(5);
+    else SCVX_NAV_LAUNCH(3);
+#undef SCVX_NAV_LAUNCH
     return hipGetLastError();
 }
 
@@ -422,6 +448,21 @@ hipError_t launch_nav_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x
                               const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
                               double* report, double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st) {
     return launch_nav_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st);
+}
+
+// the same launch with the per-node s of the path functions kept (psig [B][K+1][SCVX_PSIG_N], not null)
+hipError_t launch_nav_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
+                           double* navrep, double* psig, hipStream_t st) {
+    return launch_nav_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, nullptr, nullptr, nullptr, nullptr,
+                                    st, psig);
+}
+
+hipError_t launch_nav_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
+                               const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
+                               double* report, double* navrep, double* psig, hipStream_t st) {
+    return launch_nav_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, nullptr, nullptr, nullptr, nullptr,
+                                   st, psig);
 }
 
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm) {
@@ -456,6 +497,54 @@ int scvx_nav_cov_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const dou
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev,
                                        sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_nav_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                            const double* gain_dev, const double* S0_dev, const double* N0_dev, int m, const double* H, const double* rm,
+                            const double* w14, double* report_dev, double* navrep_dev, double* psig_dev) {
+    int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
+    if (rc) return rc;
+    if (!psig_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "nav: null buffer (psig)");
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_nav_psig(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev,
+                                        psig_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_nav_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                                 const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w14,
+                                 double* report, double* navrep, double* psig) {
+    int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
+    if (rc) return rc;
+    if (!psig) return scvx::fail(ctx, SCVX_ERR_ARG, "nav: null buffer (psig)");
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const int NU = scvx_control_dim(ctx), n = 14 + NU;
+    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
+                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, nn = (size_t)B * SCVX_NAV_NREP,
+                 np = (size_t)B * (K + 1) * SCVX_PSIG_N;
+    scvx::DevBuf<double> dx, du, dd, dg, d0, dn, dr, dq, dp;
+    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dn.p, n0 * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dq.p, nn * 8));
+    SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(dn.p, N0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, scvx::launch_nav_psig(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, dn.p, m, H, rm, w14, dr.p, dq.p, dp.p, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(navrep, dq.p, nn * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(psig, dp.p, np * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
     return SCVX_OK;
 }
 

@@ -450,6 +450,56 @@ def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=No
     return NavReport(rep, navrep, sig, navsig, kf, joint)
 
 
+def _nav_arg(nav, B):
+    """nav = (N0, H, rm), the navigation model of the calls that take back-offs from the navigation analysis: N0 as S0 (_cov_s0), H and
+    rm as nav_cov_batch (_nav_model), with rm finite and > 0 -> (N0 [B][14][14], m, H, rm).  ValueError before any library call."""
+    if not isinstance(nav, (tuple, list)) or len(nav) != 3:
+        raise ValueError("nav must be (N0, H, rm)")
+    N0, H, rm = nav
+    if N0 is None:
+        raise ValueError("nav: N0 (the handover covariance of the navigation error) is required")
+    n0 = _cov_s0(N0, B)
+    m, Hm, rv = _nav_model(H, rm)
+    if m > 14:
+        raise ValueError("H must have at most 14 rows")
+    if m and not (np.all(np.isfinite(rv)) and np.all(rv > 0.0)):
+        raise ValueError("rm (the measurement variances) must be finite and > 0")
+    if m and not np.all(np.isfinite(Hm)):
+        raise ValueError("H must be finite")
+    return n0, m, Hm, rv
+
+
+def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None):
+    """What the margins of nav_cov_batch are made of (scvx_nav_path_sigma_f64_host; same arguments without dense): (NavReport, psig) with
+    psig [B][K+1][5] as cov_path_sigma_batch, read off the TRUTH block of the joint covariance before the update at each node -- the
+    constraints bind the vehicle, not its estimate.  Node 0 and a node its margin skips are 0; a non-finite tile, gain, S0 or N0 entry
+    makes the rows of its own trajectory NaN.  With N0 = 0 this is cov_path_sigma_batch's psig to rounding."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    deriv = np.ascontiguousarray(deriv, np.float64)
+    nu = cache.nu
+    n = 14 + nu
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
+    B, K1, _ = x.shape
+    K = K1 - 1
+    if gain.shape != (B, K, nu, n):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
+    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
+        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
+    s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
+    m, Hm, rv = _nav_model(H, rm)
+    wv = _cov_noise(w)
+    rep, navrep = np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.NAV_NREP))
+    psig = np.empty((B, K1, _lib.PSIG_N))
+    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    _lib.check(cache.handle, cache._L.scvx_nav_path_sigma_f64_host(
+        cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), _p(psig)),
+        "scvx_nav_path_sigma_f64_host")
+    return NavReport(rep, navrep), psig
+
+
 def _pf(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 

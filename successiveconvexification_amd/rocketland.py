@@ -98,16 +98,18 @@ def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
 
 
 def robustify(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None,
-              r=None, qf=None, constraints=("thrust",)):
+              r=None, qf=None, constraints=("thrust",), nav=None):
     """Replan an iterate under back-offs of the thrust band taken from its own covariance analysis (ScvxBatch.robustify on the
     iterate's device batch): Tmin + n s_T(k) <= |u_k| <= Tmax - n s_T(k).  Returns (the new ProblemIteration, lo [K+1], hi [K+1]);
     raises like solve_step when the conic solve fails.  The limits are those of ScvxBatch.robustify.  constraints: any subset of
-    ("thrust", "mass", "glide", "tilt", "rate") or "all"; the path back-offs that were used are iteration.model.path_margins()."""
+    ("thrust", "mass", "glide", "tilt", "rate") or "all"; the path back-offs that were used are iteration.model.path_margins().
+    nav = (N0, H, rm): the back-offs come from the navigation analysis of the iterate (navigation()'s model), the law fed an estimate."""
     if S0 is None:
         raise ValueError("robustify: S0 (the handover covariance) is required")
     cache = cache if cache is not None else iteration.cache
     batch = iteration.model
-    st, it, nu, dj, lo, hi = batch.robustify(S0, nsigma=nsigma, rounds=rounds, cap=cap, w=w, q=q, r=r, qf=qf, constraints=constraints)
+    st, it, nu, dj, lo, hi = batch.robustify(S0, nsigma=nsigma, rounds=rounds, cap=cap, w=w, q=q, r=r, qf=qf, constraints=constraints,
+                                             nav=nav)
     if st[0] in (3, 4, 5):  # rocketland.jl:273-276
         raise RuntimeError("Non-optimal result %s exiting" % {3: "SLOW_PROGRESS", 4: "NUMERICAL_ERROR", 5: "INFEASIBLE"}[int(st[0])])
     return _snapshot(iteration.problem, cache, batch), lo[0], hi[0]
