@@ -3,6 +3,7 @@ oracle.socp.build with the edits of b and h, oracle.ipm, oracle.scvx.solve_step)
 test_gpu_path_margins.py.
 
     python tests/golden/make_oracle_path_margin_runs.py
+    python tests/golden/make_oracle_path_margin_runs.py --k100     # oracle_path_margin_k100.npz only: group "k100" of step 1 at K = 100
 
 Problem: the flyable variant of make_oracle_flight_runs.py with that file's dispersed starts.
 
@@ -165,5 +166,27 @@ def main():
              dropped_runs=np.array(dropped if dropped else ["none"]), **out)
 
 
+K100_KEYS = ("ic", "pm", "kinds", "x", "u", "dsig", "nu", "pobj")
+
+
+def main_k100():
+    """group "k100" alone (replace(p, K=100), the three starts of "k50"), into oracle_path_margin_k100.npz: oracle_path_margin_runs.npz
+    is neither read for its groups nor written.  About 3 minutes."""
+    import path_margin_reference as pr
+    from make_oracle_flight_runs import flyable_problem
+    from oracle import scvx
+    g = np.load(os.path.join(HERE, "oracle_flight_runs.npz"))
+    p = flyable_problem()
+    ics = np.concatenate([g["ic"], np.concatenate([p.rIi, p.vIi])[None]])
+    dropped = []
+    cases = group(pr, scvx, replace(p, K=100), ics, "k100", dropped)
+    assert not dropped and len(cases) == 3, dropped
+    np.savez(os.path.join(HERE, "oracle_path_margin_k100.npz"),
+             **{"k100_%s" % k: np.stack([np.asarray(c[k]) for c in cases]) for k in K100_KEYS})
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--k100"]:
+        main_k100()
+    else:
+        main()

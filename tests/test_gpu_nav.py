@@ -154,14 +154,11 @@ def test_angle_exclusions_stay_below_a_tenth():
     assert _ANG["left_out"] <= 0.1 * (_ANG["compared"] + _ANG["left_out"])
 
 
-@pytest.mark.parametrize("model", ["exo", "aero+fins"])
-def test_zero_navigation_error_equals_the_covariance_call(model, aero_tables):
-    """N0 = 0 on the device: the z block and the report are cov_propagate_batch's, with and without a measurement model"""
-    from successiveconvexification_amd.dynamics import IntegratorCache, cov_propagate_batch, linearize_batch, nav_cov_batch
-    pp, po, dyn, par, x, u, s = _case(model, aero_tables)
-    c = IntegratorCache(pp, npts=10)
-    K, n = po.K, 14 + c.nu
-    _, d = linearize_batch(c, x, u, s, 1.0 / (K + 1))
+def _zero_nav_equals_cov(model, c, po, x, u, d):
+    """N0 = 0 on the device (the plans x, u with the tiles d on the context c): the z block and the report are cov_propagate_batch's,
+    with and without a measurement model"""
+    from successiveconvexification_amd.dynamics import cov_propagate_batch, nav_cov_batch
+    K, n, B = po.K, 14 + c.nu, x.shape[0]
     S0 = _s0(x)
     L, _ = tr.gains(d, K)
     cov = cov_propagate_batch(c, x, u, d, L, S0, dense=True)
@@ -184,14 +181,23 @@ def test_zero_navigation_error_equals_the_covariance_call(model, aero_tables):
             assert np.array_equal(inf, np.isposinf(nav.raw[:, i]))
             if name == "ELL_ANG" or inf.all():
                 continue
-            floor = np.full(5, K * (n + 14) * EPS * float(np.abs(rld[~inf, i]).max()))
+            floor = np.full(B, K * (n + 14) * EPS * float(np.abs(rld[~inf, i]).max()))
             if name in cr.MARGINS:
-                for b in range(5):
+                for b in range(B):
                     if det[b][cr.MARGINS.index(name)] is not None:
                         _, terms, sd = det[b][cr.MARGINS.index(name)]
                         floor[b] = max(floor[b], 8.0 * EPS * terms / sd)
             bnd = np.maximum(16.0 * float(np.abs(r64[:, i] - rld[:, i])[~inf].max()), floor)
             assert np.all(np.abs(nav.raw[:, i] - cov.raw[:, i])[~inf] <= bnd[~inf]), (name, nav.raw[:, i], cov.raw[:, i], bnd)
+
+
+@pytest.mark.parametrize("model", ["exo", "aero+fins"])
+def test_zero_navigation_error_equals_the_covariance_call(model, aero_tables):
+    from successiveconvexification_amd.dynamics import IntegratorCache, linearize_batch
+    pp, po, dyn, par, x, u, s = _case(model, aero_tables)
+    c = IntegratorCache(pp, npts=10)
+    _, d = linearize_batch(c, x, u, s, 1.0 / (po.K + 1))
+    _zero_nav_equals_cov(model, c, po, x, u, d)
     c.close()
 
 

@@ -128,20 +128,33 @@ def test_path_sigma_unconverged_fin_plans_against_the_longdouble_reference(aero_
 
 @pytest.mark.parametrize("tiles", ["double", "float"])
 def test_batch_call_is_the_formula_and_the_one_shot_call_on_its_own_tiles(tiles):
+    _batch_call_is_the_formula(tiles, 50)
+
+
+@pytest.mark.parametrize("tiles", ["double", "float"])
+@pytest.mark.parametrize("K", [64, 100])
+def test_batch_call_is_the_formula_where_the_node_loop_takes_a_second_lap(K, tiles):
+    """K + 1 = 65 puts one node, K + 1 = 101 puts 37 nodes into the second lap of margins_from_psig_kernel's node-strided loop; the
+    plans are test_gpu_path_margins._plans' (a dispersed flyable batch after three solve_steps), the navigation model the fixture's
+    kind (nav_margin_reference.position_model) with N0 = S0 as in _parity"""
+    _batch_call_is_the_formula(tiles, K)
+
+
+def _batch_call_is_the_formula(tiles, K):
+    from dataclasses import replace
     from successiveconvexification_amd import _lib
-    from successiveconvexification_amd.batch import ScvxBatch
-    from successiveconvexification_amd.dynamics import IntegratorCache, nav_path_sigma_batch
-    from test_gpu_path_margins import _formula
+    from successiveconvexification_amd.dynamics import nav_path_sigma_batch
+    from test_gpu_path_margins import _capped, _formula, _plans
     import path_margin_reference as pr
-    g = np.load(os.path.join(GOLDEN, "oracle_flight_runs.npz"))
-    f = _fixture()
-    pp, po = _flyable()
-    K = pp.K
-    x, u, s = g["x"], g["u"], g["sigma"]
-    S0, N0, H, rm = f["S0"], f["N0"], f["H"], f["rm"]
-    c = IntegratorCache(pp, npts=10)
-    b = ScvxBatch(c, 2).set_linearization_f32(tiles == "float").init(g["ic"])
-    b.set_trajectory(x, u, s)
+    pp, c, b, x, u, s = _plans(K, tiles == "float")
+    po = replace(_flyable()[1], K=K)
+    if K == 50:
+        f = _fixture()
+        S0, N0, H, rm = f["S0"], f["N0"], f["H"], f["rm"]
+    else:
+        S0 = _s0(x)
+        N0 = S0.copy()
+        H, rm = nm.position_model(x[0, 0])
     state = lambda: (b.trajectory_record(),) + b.scalars() + b.flags()   # noqa: E731
     before = state()
     d = b.linearization()[1]                                    # float tiles: widened on the host
@@ -160,8 +173,19 @@ def test_batch_call_is_the_formula_and_the_one_shot_call_on_its_own_tiles(tiles)
     for name, got, want in (("thrust lo", b.thrust_margins()[0], lo), ("thrust hi", b.thrust_margins()[1], lo), ("path", b.path_margins(), pm)):
         print("%s tiles, all: %s largest %.3e, differs in %d entries" % (tiles, name, want.max(), int((got != want).sum())))
         assert np.array_equal(got, want), name
-    assert (pm[:, 1:K] > 0).all() and (lo[:, 1:] > 0).all()
-    assert (psig[:, 2:, 4] > b.path_sigma(S0)[:, 2:, 4]).all()                      # navigation errors widen s_T at every node
+    assert psig.shape == (2, K + 1, 5) and not psig[:, 0].any()
+    assert (pm[:, 1:K, [pr.MASS, pr.TILT, pr.RATE]] > 0).all() and (lo[:, 1:] > 0).all()
+    assert not pm[:, K, [pr.GLIDE, pr.TILT, pr.RATE]].any() and not pm[:, 0, [pr.MASS, pr.GLIDE, pr.RATE]].any() and not lo[:, 0].any()
+    if K == 50:          # the oracle's converged plans
+        assert (pm[:, 1:K] > 0).all() and (lo[:, 1:] > 0).all()
+        assert (psig[:, 2:, 4] > b.path_sigma(S0)[:, 2:, 4]).all()                  # navigation errors widen s_T at every node
+    # every entry capped, as it follows from the formula on the plan in use
+    pcap = b.margins_from_nav(S0, N0, H, rm, "all", nsigma=1e9, cap=0.125)
+    locap, pmcap = _formula(pp, x, pcap, 1e9, 0.125)
+    assert np.array_equal(pcap, psig) and np.array_equal(b.path_margins(), pmcap) and np.array_equal(b.thrust_margins()[0], locap)
+    _capped(pp, x, pcap, pmcap, 0.125)
+    assert np.all(locap[:, 1:] == 0.125 * (pp.Tmax - pp.Tmin))
+    assert np.array_equal(b.margins_from_nav(S0, N0, H, rm), psig)                  # ... and back to the settings of above
     # psig = NULL: nothing returns, the same back-offs
     b.set_thrust_margins(None, None).set_path_margins()
     assert b._margins_from_nav(S0, (N0, H, rm), None, None, None, None, 3.0, 0.25, False, _lib.MARGIN_BITS["thrust"] | 30) is None

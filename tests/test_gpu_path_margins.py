@@ -5,7 +5,8 @@ scvx_batch_get_path_margins, scvx_batch_margins_from_cov; include/scvx.h) agains
 Bounds, none of them taken from the device:
   * one subproblem against the independent oracle: those of test_gpu_margins.test_one_subproblem_with_backoffs_against_the_
     independent_oracle (both sides at 1e-9: 2e-5 on the minimiser, 1e-8 relative on the objective); in the oracle's solution each of
-    the four kinds is active at one node or more (asserted by the generator and by test_path_margins_cpu.py);
+    the four kinds is active at one node or more (asserted by the generator and by test_path_margins_cpu.py); group "k100" (K = 100,
+    tests/golden/oracle_path_margin_k100.npz): 4 x the CPU twin's distance from the oracle there, 4.17e-5, see the test;
   * a complete run from the straight-line guess under tilt back-offs: CONVERGED, the oracle's accept / reject sequence (13 steps,
     arrrrrrraaaaa), final mass, r and v within 1e-4 of the oracle's (test_gpu_margins.test_full_run_from_the_straight_line_guess_under_
     backoffs), the tightened tilt cone at every node within ten times the figure to which the oracle's own run resolves it (|smallest
@@ -32,8 +33,9 @@ pytestmark = pytest.mark.gpu
 KW = dict(mdry=0.55, nuTol=1e-6, delTol=1e-3, imax=40, tf_guess=8.0)
 
 
-def _fixture():
-    return np.load(os.path.join(GOLDEN, "oracle_path_margin_runs.npz"))
+def _fixture(name=None):
+    """the fixture that holds group `name`: "k100" has a file of its own"""
+    return np.load(os.path.join(GOLDEN, "oracle_path_margin_k100.npz" if name == "k100" else "oracle_path_margin_runs.npz"))
 
 
 def _s0(x):
@@ -50,18 +52,25 @@ def _problems(name):
     from successiveconvexification_amd import sample_problems as sp
     if name == "fin":
         return replace(sp.base_prob_fin_scaled(), mdry=0.55, tf_guess=8.0), replace(om.base_prob_fin_scaled(), mdry=0.55, tf_guess=8.0)
-    K = 9 if name == "k9" else 50
+    K = {"k9": 9, "k100": 100}.get(name, 50)
     return replace(sp.base_prob_scaled, K=K, **KW), replace(om.base_prob_scaled(), K=K, **KW)
 
 
-@pytest.mark.parametrize("name,waves", [(n, w) for n in ("k50", "k50f", "fin", "k9") for w in ("1", "2", "4")],
-                         ids=["%s waves%s" % (n, w) for n in ("K50", "K50 float tiles", "K50 fins", "K9") for w in "124"])
+@pytest.mark.parametrize("name,waves", [(n, w) for n in ("k50", "k50f", "fin", "k9", "k100") for w in ("1", "2", "4")],
+                         ids=["%s waves%s" % (n, w) for n in ("K50", "K50 float tiles", "K50 fins", "K9", "K100") for w in "124"])
 def test_one_subproblem_with_path_backoffs_against_the_independent_oracle(name, waves, monkeypatch):
     """scvx_socp_solve at the straight-line guess, B = 3 with different back-offs of all four kinds per trajectory, against the oracle's
-    solves of the edited SOCPs"""
+    solves of the edited SOCPs.
+
+    The bound on the minimiser is 2e-5 where the CPU twin of the conic solve (the same algorithm, tests/path_margin_port.cpp) is within
+    5e-6 of the oracle -- it is at 4e-6 on the K = 50 groups.  On group "k100" the twin is at d100 = 1.0434e-5 (start 0, in x; 1.2e-6
+    and 3.0e-6 on the other two; test_path_margins_cpu.D100, asserted there), so the device's bound at K = 100 is 4 d100 = 4.17e-5:
+    taken from the twin against the oracle on the CPU, not from a device run.  The objective keeps 1e-8 relative (the twin: 1.9e-10)."""
     from successiveconvexification_amd.batch import ScvxBatch
     from successiveconvexification_amd.dynamics import IntegratorCache
-    g = _fixture()
+    from test_path_margins_cpu import D100
+    g = _fixture(name)
+    tol = 4.0 * D100 if name == "k100" else 2e-5
     pp, po = _problems(name)
     K = pp.K
     ic, pm = g[name + "_ic"], g[name + "_pm"]
@@ -84,14 +93,14 @@ def test_one_subproblem_with_path_backoffs_against_the_independent_oracle(name, 
         obj = (-x[t, K, 0] + pp.wNu * np.linalg.norm(nu[t]) + 0.5 * np.linalg.norm(np.concatenate([(x - xb)[t].ravel(), (u - ub)[t].ravel()]))
                + abs(snew[t] - sg[t]))
         s = pr.slacks(po, x[t], pm[t])
-        print("%s waves %s trajectory %d: status %d merit %.2e its %d; device-vs-oracle x %.2e u %.2e dsigma %.2e nu %.2e; objective %.10f vs "
-              "%.10f; smallest tightened slack per kind %s; moved by the back-offs: %.2e"
-              % (name, waves, t, st[t], merit[t], its[t], ex, eu, es, en, obj, ref["pobj"][t], s.min(axis=0), np.abs(x[t] - free[0][t]).max()))
+        print("%s waves %s trajectory %d: status %d merit %.2e its %d; device-vs-oracle x %.2e u %.2e dsigma %.2e nu %.2e (bound %.2e); objective "
+              "%.10f vs %.10f; smallest tightened slack per kind %s; moved by the back-offs: %.2e"
+              % (name, waves, t, st[t], merit[t], its[t], ex, eu, es, en, tol, obj, ref["pobj"][t], s.min(axis=0), np.abs(x[t] - free[0][t]).max()))
         assert st[t] == 0 and merit[t] < 1e-9
-        assert ex < 2e-5 and eu < 2e-5 and es < 2e-5 and en < 2e-5
+        assert ex < tol and eu < tol and es < tol and en < tol, (tol, ex, eu, es, en)
         assert abs(obj - ref["pobj"][t]) < 1e-8 * abs(ref["pobj"][t])
         assert s.min() > -1e-8                                   # the tightened rows hold
-        assert (s.min(axis=0) < 2e-5).all()                      # ... and each kind binds (the oracle: < 1e-7, the minimisers agree to 2e-5)
+        assert (s.min(axis=0) < tol).all()                       # ... and each kind binds (the oracle: < 1e-7, the minimisers agree to tol)
         assert np.abs(x[t] - free[0][t]).max() > 1e-4            # the unmargined solve of the same subproblem is elsewhere
     b.close(), c.close()
 
@@ -140,13 +149,13 @@ def test_null_zero_and_cleared_backoffs_change_nothing(waves, monkeypatch):
     c.close()
 
 
-@pytest.mark.parametrize("tiles", ["double", "float"])
-def test_path_backoffs_of_one_trajectory_disturb_no_other(tiles):
+@pytest.mark.parametrize("tiles,K", [("double", 50), ("float", 50), ("double", 100)], ids=["double", "float", "double K100"])
+def test_path_backoffs_of_one_trajectory_disturb_no_other(tiles, K):
     import bench
     from successiveconvexification_amd import sample_problems as sp
     from successiveconvexification_amd.batch import ScvxBatch
     from successiveconvexification_amd.dynamics import IntegratorCache
-    p = sp.base_prob_scaled
+    p = sp.base_prob_scaled if K == 50 else replace(sp.base_prob_scaled, K=K)
     B = 4
     ic = bench.disperse_ics(p, 0, B, 20261018)
     c = IntegratorCache(p, npts=10)
@@ -165,7 +174,7 @@ def test_path_backoffs_of_one_trajectory_disturb_no_other(tiles):
         for a0, a1 in zip(r0, r1):
             assert np.array_equal(a0[others], a1[others], equal_nan=True), step
         d = float(np.abs(r0[3][1] - r1[3][1]).max())
-        print("%s tiles, step %d: trajectory 1 moved by %.3e, statuses %s / %s" % (tiles, step, d, r0[0], r1[0]))
+        print("%s tiles, K = %d, step %d: trajectory 1 moved by %.3e, statuses %s / %s" % (tiles, K, step, d, r0[0], r1[0]))
         assert d > 1e-4
     for b in (plain, marg):
         b.close()
@@ -302,16 +311,52 @@ def _formula(p, x, psig, nsigma, cap):
     return np.minimum(nsigma * psig[..., 4], cap * (p.Tmax - p.Tmin)), pm
 
 
-def test_margins_from_cov_is_the_formula_exactly():
+def _plans(K, tiles_f32=False):
+    """(problem, cache, B = 2 batch, x, u, sigma): at K = 50 the oracle's converged plans (oracle_flight_runs.npz) set into a batch; at
+    another horizon the dispersed flyable batch after three solve_steps (horizon_cases.flyable_batch)"""
     from successiveconvexification_amd.batch import ScvxBatch
     from successiveconvexification_amd.dynamics import IntegratorCache
-    g = np.load(os.path.join(GOLDEN, "oracle_flight_runs.npz"))
-    pp, po = _flyable()
-    K = pp.K
-    x, u, s = g["x"], g["u"], g["sigma"]
-    c = IntegratorCache(pp, npts=10)
-    b = ScvxBatch(c, 2).init(g["ic"])
-    b.set_trajectory(x, u, s)
+    pp = _flyable()[0]
+    if K == pp.K:
+        g = np.load(os.path.join(GOLDEN, "oracle_flight_runs.npz"))
+        c = IntegratorCache(pp, npts=10)
+        b = ScvxBatch(c, 2).set_linearization_f32(tiles_f32).init(g["ic"])
+        b.set_trajectory(g["x"], g["u"], g["sigma"])
+        return pp, c, b, g["x"], g["u"], g["sigma"]
+    import horizon_cases as hc
+    c, b = hc.flyable_batch(K, tiles_f32=tiles_f32)
+    return (replace(pp, K=K), c, b) + b.trajectory()
+
+
+def _capped(p, x, psig, pm, cap):
+    """the "every entry capped" assertions as they follow from _formula on the plan in use: wherever s > 0 and the node has such a row,
+    nsigma = 1e9 leaves the cap times the width (the glide width is that of the plan's own altitude, 0 where it is below ground)"""
+    K = p.K
+    itan, sqcm = _consts(p)
+    width = np.zeros(pm.shape)
+    width[..., pr.MASS], width[..., pr.TILT], width[..., pr.RATE] = cap * (p.mwet - p.mdry), cap * sqcm, cap * p.omMax
+    width[..., pr.GLIDE] = cap * (np.maximum(x[..., 1], 0.0) * itan)
+    has_row = np.ones(pm.shape, bool)
+    has_row[:, K, [pr.GLIDE, pr.TILT, pr.RATE]] = False
+    has_row[:, 0, [pr.MASS, pr.GLIDE, pr.RATE]] = False
+    live = has_row & (psig[..., :4] > 0)
+    assert live[:, 1:K].all() and live[:, K, pr.MASS].all()       # S0 > 0 reaches every later node: every entry that has a row is capped
+    assert np.array_equal(pm[live], width[live]) and not pm[~live].any()
+    assert not pm[:, K, [pr.GLIDE, pr.TILT, pr.RATE]].any() and not pm[:, 0].any()
+
+
+def test_margins_from_cov_is_the_formula_exactly():
+    _margins_from_cov_is_the_formula(50)
+
+
+@pytest.mark.parametrize("K", [64, 100])
+def test_margins_from_cov_is_the_formula_exactly_where_the_node_loop_takes_a_second_lap(K):
+    """K + 1 = 65 puts one node, K + 1 = 101 puts 37 nodes into the second lap of margins_from_psig_kernel's node-strided loop"""
+    _margins_from_cov_is_the_formula(K)
+
+
+def _margins_from_cov_is_the_formula(K):
+    pp, c, b, x, u, s = _plans(K)
     S0 = _s0(x)
     # every constraint, uncapped almost everywhere
     psig = b.margins_from_cov(S0, "all", nsigma=3.0, cap=0.25)
@@ -320,14 +365,20 @@ def test_margins_from_cov_is_the_formula_exactly():
     for name, got, want in (("thrust lo", b.thrust_margins()[0], lo), ("thrust hi", b.thrust_margins()[1], lo), ("path", b.path_margins(), pm)):
         print("%s: largest %.3e, differs in %d entries" % (name, want.max(), int((got != want).sum())))
         assert np.array_equal(got, want), name
-    assert (pm[:, 1:K] > 0).all() and (pm[:, 1:K, pr.TILT] < 0.25 * _consts(pp)[1]).all()
+    assert psig.shape == (2, K + 1, 5) and pm.shape == (2, K + 1, 4)
+    if K == 50:          # the oracle's converged plans: above ground and uncapped at every node
+        assert (pm[:, 1:K] > 0).all() and (pm[:, 1:K, pr.TILT] < 0.25 * _consts(pp)[1]).all()
+    assert (pm[:, 1:K, [pr.MASS, pr.TILT, pr.RATE]] > 0).all() and (lo[:, 1:] > 0).all()
     # every entry capped
     psig2 = b.margins_from_cov(S0, "all", nsigma=1e9, cap=0.125)
     lo2, pm2 = _formula(pp, x, psig2, 1e9, 0.125)
     assert np.array_equal(psig2, psig) and np.array_equal(b.path_margins(), pm2) and np.array_equal(b.thrust_margins()[1], lo2)
-    assert np.all(pm2[:, 1:K, pr.TILT] == 0.125 * _consts(pp)[1]) and np.all(pm2[:, 1:K, pr.RATE] == 0.125 * pp.omMax)
-    assert np.all(pm2[:, 1:, pr.MASS] == 0.125 * (pp.mwet - pp.mdry)) and np.all(pm2[:, 1:K, pr.GLIDE] == 0.125 * (x[:, 1:K, 1] * _consts(pp)[0]))
-    assert not pm2[:, K, [pr.GLIDE, pr.TILT, pr.RATE]].any() and not pm2[:, 0].any()
+    _capped(pp, x, psig2, pm2, 0.125)
+    assert np.all(lo2[:, 1:] == 0.125 * (pp.Tmax - pp.Tmin)) and not lo2[:, 0].any()
+    if K == 50:
+        assert np.all(pm2[:, 1:K, pr.TILT] == 0.125 * _consts(pp)[1]) and np.all(pm2[:, 1:K, pr.RATE] == 0.125 * pp.omMax)
+        assert np.all(pm2[:, 1:, pr.MASS] == 0.125 * (pp.mwet - pp.mdry)) and np.all(pm2[:, 1:K, pr.GLIDE] == 0.125 * (x[:, 1:K, 1] * _consts(pp)[0]))
+        assert not pm2[:, K, [pr.GLIDE, pr.TILT, pr.RATE]].any() and not pm2[:, 0].any()
     # an unselected constraint is left alone: tilt again at other settings, everything else as it was
     b.margins_from_cov(S0, ("tilt",), nsigma=2.0, cap=0.25)
     got = b.path_margins()
