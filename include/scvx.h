@@ -9,6 +9,7 @@
  *   (no counterpart: open-loop flight + path audit)    ->  scvx_flight_check_f64[_host], scvx_batch_flight_check
  *   (no counterpart: LQR gains + closed-loop flight)   ->  scvx_track_gains_f64[_host], scvx_track_fly_f64[_host], scvx_batch_track_*
  *   (no counterpart: closed-loop covariance analysis)  ->  scvx_cov_propagate_f64[_host], scvx_batch_cov
+ *   (no counterpart: sampled closed-loop dispersion)   ->  scvx_track_mc_f64[_host], scvx_batch_track_mc
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -420,6 +421,60 @@ int scvx_track_fly_nav_f64_host(scvx_ctx *ctx, int B, int K, const double *x, co
                                 const double *gain, const double *dx0, const double *nav, int nsub, int flags, double *report,
                                 double *xfly, double *ufly);
 
+/* ---- sampled closed-loop dispersion: S flights per plan, reduced on the device --------------------------------------------------
+ * Both covariance analyses above are FIRST ORDER about the plan and do not model the clamp.  This call is their nonlinear
+ * counterpart: it flies S samples of EVERY plan of a batch under the tracking law, optionally disturbed at every node, and returns
+ * one row of statistics per plan.  A flight is the pair (plan b, sample s); the plan, its sigma and its gains are read once per
+ * wavefront, not copied per sample as a sampled check through scvx_track_fly_f64 has to, and no dense output need leave the device.
+ * Model.  Flight (b, s) is scvx_track_fly_f64's closed loop, arithmetic included, from the start
+ *     x_fly[0] = xbar_0 + dx0,   dx0[i] = sum_j C0[b][i][j] xi0[s][j]      (fma, ascending j from 0)
+ * C0 [B][14][14] row-major: a factor of the plan's handover covariance, S0 = C0 C0'; xi0 [S][14]: standard-normal draws SHARED by
+ * all plans (common random numbers: two plans are compared on the same draws).  With eta = NULL a flight's 16 SCVX_FLIGHT_* columns
+ * are bitwise those of scvx_track_fly_f64 for the same plan, gains, flags, nsub and the dx0 this call formed.
+ * Process noise (optional): eta [S][K][14] standard-normal draws, also shared by all plans, and sw14 [14] >= 0 = sqrt(w), a HOST
+ * array.  The noise is an IMPULSE at the nodes: after segment k is integrated,
+ *     x_fly[k+1][i] = fma(sw[i], eta[s][k][i], x_fly[k+1][i])              k = 0..K-1
+ * before node k+1's gap, landing row and feedback see the state.  Its covariance is exactly the + diag(w) of
+ * scvx_cov_propagate_f64.  The s = nsub sample of segment k sees the undisturbed state, the s = 0 sample of segment k+1 the disturbed
+ * one; the last impulse (k = K-1) is followed by no sample: it enters GAP at node K, the MISS_* columns, MASS_END and the landing
+ * statistics only.  eta = NULL, or sw14 all zero, gives bitwise the undisturbed result.
+ * Per flight, besides the 16 columns: two counters over the COMMANDED node controls k = 1..K, before the clamp, of
+ * Tmin - |u[1:3]| > tol and of |u[1:3]| - Tmax > tol, and the landing deviation e = x_fly[K] - xbar_K.
+ * Reduction: on the device, deterministic (a fixed butterfly per wavefront, the wavefronts of a plan combined in order; no
+ * floating-point atomics): two calls with the same inputs give bitwise equal outputs.  mcrep [B][SCVX_MC_NREP], c = 0..15 the
+ * SCVX_FLIGHT_* columns: */
+#define SCVX_MC_NREP 48
+#define SCVX_MC_MAX 0      /* 0..15   MAX_c: the largest value of flight column c over the S flights (a NaN flight makes it NaN)     */
+#define SCVX_MC_MEAN 16    /* 16..31  MEAN_c: the mean of flight column c, ordinary IEEE arithmetic: a column that is -inf for the    */
+                           /*         model stays -inf, a NaN flight makes it NaN                                                    */
+#define SCVX_MC_P_MASS 32  /* 32..40  P_MASS .. P_FIN: the share of flights whose G_MASS .. G_FIN (flight columns 6..14) exceed tol  */
+#define SCVX_MC_P_ANY 41   /* the share of flights with any of those nine above tol (a comparison with NaN is false)                */
+#define SCVX_MC_OUT_LO 42  /* the share of the S K commanded node controls with Tmin - |u[1:3]| > tol; with SCVX_TRACK_CLAMP and      */
+#define SCVX_MC_OUT_HI 43  /* tol = 0: the share that was clamped on that side.  OUT_HI: |u[1:3]| - Tmax > tol                       */
+#define SCVX_MC_N_BAD 44   /* the number of flights whose GAP is not finite                                                         */
+#define SCVX_MC_S 45       /* S                                                                                                     */
+                           /* 46..47  0                                                                                             */
+/* Landing statistics, about the PLANNED final node (not about zero, not about the target): xmean [B][14] = the mean of e; xcov
+ * [B][14][14] = the sample covariance of e, divisor S - 1, from the accumulated sums of e and e e' (all zero for S = 1).
+ * Optional dense outputs (NULL = not wanted): flights [B][S][SCVX_FLIGHT_NREP], xland [B][S][14] = x_fly[K], dx0 [B][S][14] = the
+ * offsets the device formed.  A non-finite gain, plan or C0 entry poisons the rows of its own plan only (N_BAD = S, NaN statistics).
+ * Limits: the law is fed the TRUTH -- a navigation estimate in the sampled loop is out of scope, and `reserved` (must be NULL) keeps
+ * its place in the argument list; the draws are shared across plans, so the rows of one call are not independent experiments;
+ * quantiles are not reduced on the device -- take them from `flights`; w is the per-segment lump of the analyses, here as an impulse.
+ * x, u, sigma, gain, flags (SCVX_TRACK_CLAMP), nsub as scvx_track_fly_f64; tol >= 0.  The _f64 form takes device pointers (sw14 on
+ * the host) and is asynchronous on the context's stream; its partial sums live in a workspace that belongs to the context, so two
+ * calls on one context must not overlap on different streams.  SCVX_ERR_ARG for S < 1, B < 1 (or B > 65535), K != the problem's K,
+ * nsub outside [1, 1000], unknown flag bits, a negative or non-finite sw or tol, eta without sw, a non-NULL reserved, a null x / u /
+ * sigma / gain / C0 / xi0 / mcrep / xmean / xcov. */
+int scvx_track_mc_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                      const double *gain_dev, const double *C0_dev, const double *xi0_dev, const double *eta_dev,
+                      const double *sw14, const void *reserved, int nsub, int flags, double tol, double *mcrep_dev,
+                      double *xmean_dev, double *xcov_dev, double *flights_dev, double *xland_dev, double *dx0_dev);
+int scvx_track_mc_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                           const double *gain, const double *C0, const double *xi0, const double *eta, const double *sw14,
+                           const void *reserved, int nsub, int flags, double tol, double *mcrep, double *xmean, double *xcov,
+                           double *flights, double *xland, double *dx0);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -560,6 +615,14 @@ int scvx_batch_nav_cov(scvx_batch *b, const double *q14, const double *rNU, cons
                        double *navsig, double *kf, double *joint);
 int scvx_batch_track_fly_nav(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *dx0,
                              const double *nav, int nsub, int flags, double *report, double *xfly, double *ufly);
+
+/* The sampled dispersion above on the batch's current accepted iterate, under the gains of the weights q14 / rNU / qf14 computed
+ * from the batch's own derivative tiles (float tiles are widened on load), as scvx_batch_track_fly does.  C0 [B][14][14], xi0
+ * [S][14], eta [S][K][14] or NULL, sw14 and every output are host arrays; any output may be NULL; nsub = 0 takes the context's.  The
+ * batch is left untouched, as by scvx_batch_flight_check.  Synchronises. */
+int scvx_batch_track_mc(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                        const double *xi0, const double *eta, const double *sw14, const void *reserved, int nsub, int flags,
+                        double tol, double *mcrep, double *xmean, double *xcov, double *flights, double *xland, double *dx0);
 
 /* ---- thrust-band back-offs and covariance-driven replanning (no counterpart in the reference) ---------------------------------
  * Per-trajectory, per-node back-offs of the thrust band, read by the conic solve alone:

@@ -543,6 +543,56 @@ track_nav_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdo
         cache.ctx, B, K, x_dev, u_dev, sigma_dev, gain_dev, dx0_dev, nav_dev, nsub, flags, report_dev, xfly_dev, ufly_dev),
         "scvx_track_fly_nav_f64")
 
+# ---- sampled closed-loop dispersion (new) --------------------------------------------------------------------------------------
+# include/scvx.h, "sampled closed-loop dispersion": S flights per plan under the tracking law, reduced on the device to one row of
+# MC_NREP statistics per plan.  C0 14 x 14 x B holds every plan's factor ROW-major as the library reads it (C0[j, i, b] = C[i, j]);
+# xi0 14 x S and eta 14 x K x S (or nothing) are standard-normal draws shared by all plans; w the per-segment noise variance.
+const MC_NREP = 48
+const MC_MAX, MC_MEAN, MC_P_MASS, MC_P_ANY, MC_OUT_LO, MC_OUT_HI, MC_N_BAD, MC_S = 0, 16, 32, 41, 42, 43, 44, 45
+
+function _mc_outputs(B::Int, S::Int, dense::Bool)
+    return (Matrix{Float64}(undef, MC_NREP, B), Matrix{Float64}(undef, 14, B), Array{Float64,3}(undef, 14, 14, B),
+            dense ? Array{Float64,3}(undef, FLIGHT_NREP, S, B) : nothing, dense ? Array{Float64,3}(undef, 14, S, B) : nothing,
+            dense ? Array{Float64,3}(undef, 14, S, B) : nothing)
+end
+
+function track_mc(b::Batch, C0::Array{Float64,3}, xi0::Matrix{Float64}; eta::Union{Nothing,Array{Float64,3}}=nothing, w=nothing, q=1.0,
+                  r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false, tol::Float64=0.0, dense::Bool=false)
+    NU = control_dim(b.cache)
+    S = size(xi0, 2)
+    size(C0) == (14, 14, b.B) && size(xi0, 1) == 14 || throw(ArgumentError("C0 must be 14 x 14 x B, xi0 14 x S"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    GC.@preserve sw check(b.cache.ctx, ccall((:scvx_batch_track_mc, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, xi0, _cov_opt(eta), _cov_opt(sw), C_NULL, nsub,
+        clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0)), "scvx_batch_track_mc")
+    return mcrep, xmean, xcov, flights, xland, dx0
+end
+
+function track_mc(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, gain::Array{Float64,4},
+                  C0::Array{Float64,3}, xi0::Matrix{Float64}; eta::Union{Nothing,Array{Float64,3}}=nothing, w=nothing, nsub::Int=10,
+                  clamp::Bool=false, tol::Float64=0.0, dense::Bool=false)
+    B, K, S = size(x, 3), size(x, 2) - 1, size(xi0, 2)
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    GC.@preserve sw check(cache.ctx, ccall((:scvx_track_mc_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, xi0, _cov_opt(eta), _cov_opt(sw), C_NULL, nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep,
+        xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0)), "scvx_track_mc_f64_host")
+    return mcrep, xmean, xcov, flights, xland, dx0
+end
+
+# the same on device pointers, asynchronous on the context's stream; sw = sqrt(w) stays a host array (or nothing)
+track_mc_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+              gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble}, sw::Union{Nothing,Vector{Float64}},
+              nsub::Int, flags::Int, tol::Float64, mcrep_dev::Ptr{Cdouble}, xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble},
+              flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble}) =
+    GC.@preserve sw check(cache.ctx, ccall((:scvx_track_mc_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(sw), C_NULL, nsub, flags, tol, mcrep_dev,
+        xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev), "scvx_track_mc_f64")
+
 # ---- thrust-band back-offs and covariance-driven replanning (new) ----------------------------------------------------------
 # include/scvx.h, "thrust-band back-offs".  Tmin + lo[k, b] <= |u_k| <= Tmax - hi[k, b], read by the conic solve alone; the flight
 # check and the tracking calls keep auditing against the true Tmin / Tmax.  psig is 5 x (K+1) x B (row PSIG_* + 1 holds that column).

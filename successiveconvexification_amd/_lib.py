@@ -74,6 +74,12 @@ NAV_NREP = 8
 NAV_COLUMNS = ("NAV_M", "NAV_R", "NAV_V", "NAV_Q", "NAV_W", "NAV_PEAK", "EST_R", "EST_V")
 NAV_INDEX = {n: i for i, n in enumerate(NAV_COLUMNS)}
 
+# scvx_track_mc_*: the columns of the sampled-dispersion report [B][MC_NREP] (the SCVX_MC_* macros of include/scvx.h)
+MC_NREP = 48
+MC_COLUMNS = (tuple("MAX_" + n for n in FLIGHT_COLUMNS) + tuple("MEAN_" + n for n in FLIGHT_COLUMNS)
+              + tuple("P_" + n[2:] for n in FLIGHT_COLUMNS[6:15]) + ("P_ANY", "OUT_LO", "OUT_HI", "N_BAD", "S"))
+MC_INDEX = {n: i for i, n in enumerate(MC_COLUMNS)}
+
 _vp = C.c_void_p
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
 SIGNATURES = {
@@ -109,6 +115,10 @@ SIGNATURES = {
                                         _dp]),
     "scvx_track_fly_nav_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "scvx_track_fly_nav_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "scvx_track_mc_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp, C.c_int, C.c_int, C.c_double,
+                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    "scvx_track_mc_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int,
+                                         C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),
@@ -143,6 +153,8 @@ SIGNATURES = {
     "scvx_batch_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_nav_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_track_fly_nav": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "scvx_batch_track_mc": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp,
+                                      _dp, _dp]),
     "scvx_batch_set_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
     "scvx_batch_get_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
     "scvx_batch_thrust_margins_from_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp]),

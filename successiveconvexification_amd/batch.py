@@ -252,6 +252,22 @@ class ScvxBatch:
                                                _p(xfly) if dense else None, _p(ufly) if dense else None), "scvx_batch_track_fly")
         return FlightReport(rep, xfly, "track", ufly)
 
+    def track_mc(self, S0, samples=256, seed=0, w=None, q=None, r=None, qf=None, nsub=None, clamp=False, tol=0.0, dense=(), draws=None):
+        """Sampled closed-loop dispersion of the batch's current accepted iterate under its LQR gains: `samples` flights per plan on
+        the device, one dynamics.McReport row per plan (scvx_batch_track_mc; S0 -- a [14] vector of standard deviations, one [14][14]
+        or [B][14][14] --, seed, w, clamp, tol, dense and draws as dynamics.track_mc_batch, weights as track_gains).  The batch is left
+        untouched."""
+        from .dynamics import McReport, _mc_inputs, _mc_outputs, _track_weights
+        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
+        c0, xi0, eta, sw = _mc_inputs(S0, self.B, self.K, samples, seed, w, draws)
+        S = xi0.shape[0]
+        rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(self.B, S, dense)
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        self._chk(self._L.scvx_batch_track_mc(self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), _p(xi0), opt(eta), opt(sw), None,
+                                              int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean),
+                                              _p(xcov), opt(flights), opt(xland), opt(dx0)), "scvx_batch_track_mc")
+        return McReport(rep, xmean, xcov, flights, xland, dx0)
+
     def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False):
         """Closed-loop covariance analysis of the batch's current accepted iterate under its LQR gains (scvx_batch_cov; S0, w and
         dense as dynamics.cov_propagate_batch, weights as track_gains): a dynamics.CovReport.  The batch is left untouched."""

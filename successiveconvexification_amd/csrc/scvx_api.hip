@@ -174,6 +174,7 @@ void scvx_ctx_destroy(scvx_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)scvx_comm_destroy(ctx);
     scvx::td_cache_free(ctx);
+    scvx::mc_workspace_free(ctx);
     if (ctx->d_cdrag) (void)hipFree(ctx->d_cdrag);
     if (ctx->d_clift) (void)hipFree(ctx->d_clift);
     if (ctx->d_ctrq) (void)hipFree(ctx->d_ctrq);

@@ -894,6 +894,50 @@ int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU
     return SCVX_OK;
 }
 
+int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                        const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                        double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (nsub == 0) nsub = ctx->nsub;
+    // every check before anything is enqueued; the outputs are optional here, so a placeholder stands in for them
+    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
+    if ((rc = scvx::check_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->x, C0, xi0, eta, sw14, reserved, nsub, flags, tol, b->x,
+                                   b->x, b->x)))
+        return rc;
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const size_t nc = (size_t)b->B * 196, ni = (size_t)S * 14, ne = (size_t)S * b->K * 14, nr = (size_t)b->B * SCVX_MC_NREP,
+                 nm = (size_t)b->B * 14, nf = (size_t)b->B * S * SCVX_FLIGHT_NREP, nl = (size_t)b->B * S * 14;
+    scvx::DevBuf<double> dc, di, de, dr, dm, dv, df, dl, d0;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMalloc((void**)&dc.p, nc * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&di.p, ni * 8);
+    if (e == hipSuccess && eta) e = hipMalloc((void**)&de.p, ne * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dm.p, nm * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&dv.p, nc * 8);
+    if (e == hipSuccess && flights) e = hipMalloc((void**)&df.p, nf * 8);
+    if (e == hipSuccess && xland) e = hipMalloc((void**)&dl.p, nl * 8);
+    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, nl * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc.p, C0, nc * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && eta) e = hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p,
+                                  dm.p, dv.p, df.p, dl.p, d0.p, st);
+    if (e == hipSuccess && mcrep) e = hipMemcpyAsync(mcrep, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xmean) e = hipMemcpyAsync(xmean, dm.p, nm * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xcov) e = hipMemcpyAsync(xcov, dv.p, nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && flights) e = hipMemcpyAsync(flights, df.p, nf * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && xland) e = hipMemcpyAsync(xland, dl.p, nl * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dx0) e = hipMemcpyAsync(dx0, d0.p, nl * 8, hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
 int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,
                        const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
                        double* navsig, double* kf, double* joint) {

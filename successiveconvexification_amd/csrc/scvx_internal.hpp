@@ -24,6 +24,8 @@ struct scvx_ctx {
     void* comm = nullptr;   // ncclComm_t of scvx_comm_create (RCCL, bound at run time: csrc/scvx_comm.hip)
     int comm_rank = 0, comm_world = 0;
     scvx::TdCache* td = nullptr;
+    double* mc_ws = nullptr;     // partial rows of scvx_track_mc_f64's reduction (scvx_mc.hip), grown on demand
+    size_t mc_ws_doubles = 0;
     std::string err;
 };
 
@@ -91,6 +93,17 @@ hipError_t launch_track_fly_nav(const scvx_ctx* ctx, int B, int K, const double*
 int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const double* qf);
 int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
                     const void* report);
+
+// Sampled dispersion (scvx_mc.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan; C0[B][14][14],
+// xi0[S][14], eta[S][K][14] or nullptr, sw: host array of 14 or nullptr; mcrep[B][SCVX_MC_NREP], xmean[B][14], xcov[B][14][14];
+// flights[B][S][16], xland[B][S][14], dx0[B][S][14] or nullptr.  The partial rows live in ctx->mc_ws.
+hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
+                           const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
+                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st);
+int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain, const void* C0,
+                   const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
+                   const void* mcrep, const void* xmean, const void* xcov);
+void mc_workspace_free(scvx_ctx* ctx);
 
 // Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles (double or float) and the gains;
 // S0[B][14][14]; w: host array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.

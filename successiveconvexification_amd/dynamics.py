@@ -367,6 +367,101 @@ def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None):
     return CovReport(rep), psig
 
 
+class McReport:
+    """The report of a sampled dispersion (scvx_track_mc_f64, include/scvx.h): `raw` [B][48], one named numpy view per column
+    (report.MAX_GAP, report.MEAN_MISS_R, report.P_TMIN, report.P_ANY, report.OUT_LO, report.N_BAD, ... -- _lib.MC_COLUMNS), the landing
+    statistics `xmean` [B][14] and `xcov` [B][14][14] of x_fly[K] - xbar_K over the samples, and the optional dense outputs `flights`
+    [B][S][16], `xland` [B][S][14] and `dx0` [B][S][14], or None.  The draws are shared by all plans; quantiles come from `flights`."""
+
+    def __init__(self, raw, xmean, xcov, flights=None, xland=None, dx0=None):
+        self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.MC_NREP)
+        self.xmean, self.xcov = xmean, xcov
+        self.flights, self.xland, self.dx0 = flights, xland, dx0
+        for name, i in _lib.MC_INDEX.items():
+            setattr(self, name, self.raw[:, i])
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    def flight(self, b):
+        """The S flights of plan b as a FlightReport of S rows (needs dense "flights")."""
+        if self.flights is None:
+            raise ValueError("McReport.flight: the call was made without dense 'flights'")
+        return FlightReport(self.flights[b], None, "track")
+
+
+def _mc_dense(dense):
+    """dense: False / () / True (all three) / an iterable of names out of "flights", "xland", "dx0" -> the set of wanted outputs"""
+    if dense is True:
+        return {"flights", "xland", "dx0"}
+    if not dense:
+        return set()
+    want = {dense} if isinstance(dense, str) else set(dense)
+    if not want <= {"flights", "xland", "dx0"}:
+        raise ValueError("dense: True, False or names out of 'flights', 'xland', 'dx0', not %r" % (dense,))
+    return want
+
+
+def _mc_inputs(S0, B, K, samples, seed, w, draws):
+    """(C0 [B][14][14], xi0 [S][14], eta [S][K][14] or None, sw [14] or None) of a sampled dispersion: the factor of every plan's
+    handover covariance (montecarlo.handover_factor), the draws of montecarlo.mc_draws -- or `draws` = (xi0, eta) -- and sqrt(w)"""
+    from .montecarlo import handover_factor, mc_draws
+    s0 = _cov_s0(S0, B)
+    wv = _cov_noise(w)
+    c0 = np.ascontiguousarray(np.stack([handover_factor(s0[b]) for b in range(B)]))
+    if draws is None:
+        if int(samples) < 1:
+            raise ValueError("samples must be >= 1")
+        xi0, eta = mc_draws(int(samples), K, seed, noise=wv is not None)
+    else:
+        xi0 = np.ascontiguousarray(draws[0], np.float64)
+        eta = None if draws[1] is None else np.ascontiguousarray(draws[1], np.float64)
+        if xi0.ndim != 2 or xi0.shape[1] != 14 or xi0.shape[0] < 1 or (eta is not None and eta.shape != (xi0.shape[0], K, 14)):
+            raise ValueError("shape mismatch: draws = (xi0 [S][14], eta [S][K][14] or None)")
+    if wv is not None and np.all(wv >= 0.0):
+        sw = np.sqrt(wv)
+    else:
+        sw = wv   # None, or a bad w as it is: the library refuses it with its own message
+    return c0, xi0, eta, sw
+
+
+def _mc_outputs(B, S, dense):
+    want = _mc_dense(dense)
+    return (np.empty((B, _lib.MC_NREP)), np.empty((B, 14)), np.empty((B, 14, 14)),
+            np.empty((B, S, _lib.FLIGHT_NREP)) if "flights" in want else None, np.empty((B, S, 14)) if "xland" in want else None,
+            np.empty((B, S, 14)) if "dx0" in want else None)
+
+
+def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=0, w=None, nsub=10, clamp=False, tol=0.0, dense=(),
+                   draws=None) -> McReport:
+    """Sampled closed-loop dispersion of the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] tracked under the gains gain
+    [B][K][nu][14+nu]: `samples` flights PER PLAN on the device, reduced there to one McReport row per plan (scvx_track_mc_f64_host;
+    the model, the impulse convention and the limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one [14][14]
+    for all, or a [14] vector of standard deviations; flight (b, s) starts at x[b, 0] + handover_factor(S0[b]) @ xi0[s].  The draws
+    are montecarlo.mc_draws(samples, K, seed), shared by all plans.  w: process-noise variance per segment, a scalar or [14] (None =
+    no noise), applied as an impulse sqrt(w) * eta at every node -- the + diag(w) of cov_propagate_batch.  clamp as track_fly_batch;
+    tol: the threshold of the P_* and OUT_* columns.  dense: True, or names out of "flights", "xland", "dx0".  draws = (xi0 [S][14],
+    eta [S][K][14] or None): use these instead of mc_draws (`samples` and `seed` are then ignored)."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], cache.nu) or sigma.shape != (x.shape[0],):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % cache.nu)
+    B, K1, _ = x.shape
+    if gain.shape != (B, K1 - 1, cache.nu, 14 + cache.nu):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (cache.nu, 14 + cache.nu))
+    c0, xi0, eta, sw = _mc_inputs(S0, B, K1 - 1, samples, seed, w, draws)
+    S = xi0.shape[0]
+    rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    _lib.check(cache.handle, cache._L.scvx_track_mc_f64_host(
+        cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(sw), None,
+        int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov),
+        opt(flights), opt(xland), opt(dx0)), "scvx_track_mc_f64_host")
+    return McReport(rep, xmean, xcov, flights, xland, dx0)
+
+
 class NavReport(CovReport):
     """The two reports of a navigation-error covariance analysis (scvx_nav_cov_f64, include/scvx.h): everything a CovReport has (the
     sixteen columns read off the truth-dispersion block; `covK` and `cov` are None -- ask for `joint`), plus `navraw` [B][8] with one

@@ -88,6 +88,22 @@ def gaussian_handover(S0, lo, hi, seed):
     return dx0
 
 
+def mc_draws(samples, K, seed, noise=False, lo=0):
+    """The draws of a sampled dispersion (dynamics.track_mc_batch, ScvxBatch.track_mc): (xi0 [samples][14], eta [samples][K][14] or
+    None without `noise`), standard normal.  Sample s draws from Philox stream s of `seed` with a counter word of its own, 4 -- and in the
+    SECOND counter word, which the generator's own increments of the first never reach, so the draws share nothing with those of
+    disperse_ics, disperse_handover, gaussian_handover or nav_error_samples (words 0 to 3 in the first).  The 14 start draws come first, so
+    xi0 does not depend on `noise`, and a shard [lo, lo + samples) gets exactly the rows the whole set would."""
+    xi0 = np.empty((samples, 14))
+    eta = np.empty((samples, K, 14)) if noise else None
+    for s in range(samples):
+        rng = np.random.Generator(np.random.Philox(key=seed, counter=[0, 4, 0, lo + s]))
+        xi0[s] = rng.standard_normal(14)
+        if noise:
+            eta[s] = rng.standard_normal(K * 14).reshape(K, 14)
+    return xi0, eta
+
+
 _STATE_BLOCKS = {"r": (1, 4), "v": (4, 7), "q": (7, 11), "w": (11, 14)}
 
 
@@ -276,6 +292,38 @@ def dispersion_summary(covreport, status):
             out["stats"][n] = None
         elif np.all(np.isposinf(c)):
             out["stats"][n] = {k: float("inf") for k in ("min", "median", "p99", "max")}
+        else:
+            out["stats"][n] = {"min": float(np.min(c)), "median": float(np.median(c)), "p99": float(np.percentile(c, 99)),
+                               "max": float(np.max(c))}
+    return out
+
+
+def mc_summary(rep, status):
+    """What a batch of plans has to say once its sampled dispersion is done.  rep: a dynamics.McReport or its raw [N][48] array; status
+    [N]: the SCvx statuses of scvx_solve.  Returns a plain dict: counts by SCvx status, the number of converged plans, the samples per
+    plan, the number of converged plans with a non-finite flight, and min / median / p99 / max of every column over the converged plans
+    (None where there is none; a column that is -inf in every converged row -- a constraint the model does not enforce -- reports
+    -inf).  The statistics are over PLANS, each already reduced over its samples on the same draws.  Pure numpy."""
+    from ._lib import MC_COLUMNS, MC_INDEX, MC_NREP
+    names = {0: "converged", 1: "running", 2: "rejected", 3: "solver", 4: "nonfinite", 5: "infeasible"}
+    raw = np.asarray(getattr(rep, "raw", rep), np.float64).reshape(-1, MC_NREP)
+    status = np.asarray(status).reshape(-1)
+    if status.shape[0] != raw.shape[0]:
+        raise ValueError("report has %d rows, status %d" % (raw.shape[0], status.shape[0]))
+    counts = {n: int(np.sum(status == c)) for c, n in names.items()}
+    counts["other"] = int(status.shape[0] - sum(counts.values()))
+    conv = raw[status == 0]
+    out = {"n": int(raw.shape[0]), "counts": counts, "converged": int(conv.shape[0]),
+           "samples": int(raw[0, MC_INDEX["S"]]) if raw.shape[0] else 0,
+           "plans_with_bad_flights": int(np.sum(conv[:, MC_INDEX["N_BAD"]] != 0)), "stats": {}}
+    for n in MC_COLUMNS:
+        if n == "S":
+            continue
+        c = conv[:, MC_INDEX[n]]
+        if c.shape[0] == 0:
+            out["stats"][n] = None
+        elif np.all(np.isneginf(c)):
+            out["stats"][n] = {k: float("-inf") for k in ("min", "median", "p99", "max")}
         else:
             out["stats"][n] = {"min": float(np.min(c)), "median": float(np.median(c)), "p99": float(np.percentile(c, 99)),
                                "max": float(np.max(c))}

@@ -81,6 +81,24 @@ def track(iteration: ProblemIteration, cache: IntegratorCache = None, dx0=None, 
     return track_fly_batch(cache, x, u, sigma, gain, d0, nsub=nsub, clamp=clamp, dense=dense)
 
 
+def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, samples=256, seed=0, w=None, q=None, r=None, qf=None,
+             nsub=None, clamp=False, tol=0.0, dense=()):
+    """Sampled closed-loop dispersion of an iterate's plan tracked under the time-varying LQR gains about it: `samples` flights from
+    Gaussian starts of covariance S0 ([14][14], or a [14] vector of standard deviations), with the per-segment process noise w as an
+    impulse at the nodes (dynamics.track_gains_batch on the plan's own linearisation, dynamics.track_mc_batch).  A dynamics.McReport of
+    one row."""
+    from .dynamics import linearize_batch, track_gains_batch, track_mc_batch
+    if S0 is None:
+        raise ValueError("track_mc: S0 (the handover covariance) is required")
+    cache = cache if cache is not None else iteration.cache
+    x = np.stack([pt.state for pt in iteration.about])[None]
+    u = np.stack([pt.control for pt in iteration.about])[None]
+    sigma = np.array([float(iteration.sigma)])
+    _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
+    gain = track_gains_batch(cache, deriv, q, r, qf)
+    return track_mc_batch(cache, x, u, sigma, gain, S0, samples, seed=seed, w=w, nsub=nsub, clamp=clamp, tol=tol, dense=dense)
+
+
 def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False):
     """Closed-loop covariance analysis of an iterate's plan tracked under the time-varying LQR gains about it, from the handover
     covariance S0 ([14][14], or a [14] vector of standard deviations) with the per-segment process noise w (dynamics.track_gains_batch
