@@ -40,7 +40,13 @@
  * scvx_control_dim(ctx) returns NU.
  *
  * All pointers named *_dev are device (HBM) pointers valid on the context's device; all others are
- * host pointers.  Device entry points are asynchronous on the context's stream (scvx_set_stream);
+ * host pointers.  Device entry points are asynchronous on the context's stream (scvx_set_stream):
+ * work ordered after a call on that stream sees the call's results.  scvx_solve_step[_async] and
+ * scvx_batch_reset of a large batch run as two contiguous parts on side streams that the context owns
+ * and make the context's stream wait for them on the device, so that statement holds for them too; a
+ * part waits for the context's stream only when another call has touched the batch or the stream
+ * since its last step (after scvx_batch_trajectory_dev: at every step).  SCVX_STEP_SPLIT=1 in the
+ * environment keeps every step on the context's stream; results are the same bit for bit;
  * the *_host entry points copy in, run, copy out and synchronise.  Every function returns 0 on
  * success and a negative code on failure; scvx_last_error(ctx) then describes the failure.
  * No C++ types and no exceptions cross this boundary.
@@ -725,10 +731,13 @@ int scvx_batch_margins_from_nav(scvx_batch *b, const double *q14, const double *
  * CONVERGED}.  Synchronises the stream. */
 int scvx_batch_get_step_stats(scvx_batch *b, double *out8, int reset);
 
-/* ---- per-kernel device time of the solve_step chain (HIP events on the context's stream) ------ */
+/* ---- per-kernel device time of the solve_step chain (HIP events on the stream a step, or a part of it, runs on) ------ */
 int scvx_batch_set_profiling(scvx_batch *b, int enable);
 /* ms[5] = {socp (K4), propagate (K2), tr_update (K5), linearize (K1), glue (K3: candidate/unpack)}
- * summed over the `steps` solve_steps enqueued since the last call; synchronises and resets. */
+ * over the `steps` solve_steps enqueued since the last call; synchronises and resets.  Steps on the context's stream: the sum of
+ * each class's intervals, and the classes add up to the steps.  Steps that ran as parts on side streams: per class the length of
+ * the UNION of its intervals over all parts (socp = the time during which some conic solve was running); the parts overlap, so
+ * the classes do not add up to the steps. */
 int scvx_batch_get_profile(scvx_batch *b, double *ms, int64_t *steps);
 
 /* ---- multi-GPU: the single exchange step of the path (no counterpart in the reference) ---- */

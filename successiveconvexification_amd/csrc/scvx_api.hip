@@ -178,6 +178,8 @@ void scvx_ctx_destroy(scvx_ctx* ctx) {
     if (ctx->d_cdrag) (void)hipFree(ctx->d_cdrag);
     if (ctx->d_clift) (void)hipFree(ctx->d_clift);
     if (ctx->d_ctrq) (void)hipFree(ctx->d_ctrq);
+    for (hipStream_t s : ctx->side)   // the parts of a split step: whatever is still queued there ends first
+        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -197,12 +199,14 @@ int scvx_control_dim(const scvx_ctx* ctx) { return ctx && (ctx->prob.model_flags
 int scvx_set_stream(scvx_ctx* ctx, void* hip_stream) {
     if (!ctx) return SCVX_ERR_ARG;
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    ctx->epoch++;
     return SCVX_OK;
 }
 
 int scvx_use_null_stream(scvx_ctx* ctx) {
     if (!ctx) return SCVX_ERR_ARG;
     ctx->stream = nullptr;   // HIP's legacy default stream
+    ctx->epoch++;
     return SCVX_OK;
 }
 
@@ -222,6 +226,7 @@ int scvx_synchronize(scvx_ctx* ctx) {
 int scvx_set_nsub(scvx_ctx* ctx, int nsub) {
     if (!ctx || nsub < 1 || nsub > 1000) return fail(ctx, SCVX_ERR_ARG, "nsub must be in [1,1000]");
     ctx->nsub = nsub;
+    ctx->epoch++;
     return SCVX_OK;
 }
 
@@ -237,6 +242,9 @@ int scvx_set_aero_table(scvx_ctx* ctx, const double* drag, const double* lift, c
     std::vector<double> cd = prefilter_table(drag, n_aoa, n_mach);
     std::vector<double> cl = prefilter_table(lift, n_aoa, n_mach);
     const size_t bytes = cd.size() * sizeof(double);
+    for (hipStream_t s : ctx->side)   // a split step still queued reads the tables that go away here
+        if (s) SCVX_HIP(ctx, hipStreamSynchronize(s));
+    ctx->epoch++;
     if (ctx->d_cdrag) (void)hipFree(ctx->d_cdrag);
     if (ctx->d_clift) (void)hipFree(ctx->d_clift);
     if (ctx->d_ctrq) (void)hipFree(ctx->d_ctrq);

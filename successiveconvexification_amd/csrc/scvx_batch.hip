@@ -7,7 +7,13 @@
 //     propagate_kernel : K predict_state calls per trajectory (K2)               (:289)
 //     tr_update_kernel : jK, lK, rho test, accept / reject, radius update        (:286-313)
 //     linearize_kernel : Dynamics.linearize_dynamics on the new reference (K1)   (:318)
-// all on one stream, nothing returning to the host in between.
+// nothing returning to the host in between.  A small batch, and every scvx_solve, runs the chain on the context's stream for the
+// whole batch.  A large batch stepped by scvx_solve_step[_async] / scvx_batch_reset runs it as M contiguous parts, each on a side
+// stream of the context: trajectories never interact, so while one part drains its conic solve or runs its small kernels the other
+// still has blocks to dispatch ("Split step" below; SCVX_STEP_SPLIT = 1 turns it off, 2 - 4 force that many parts).
+// Profiling (scvx_batch_get_profile): unsplit, each class is the sum of its event intervals, and the classes add up to the step.
+// Split, each class is the length of the UNION of its intervals over all parts (socp = the time during which some conic solve was
+// running); the parts overlap, so the classes no longer add up to the step.
 //
 // The executors, the kernel body and the kernel templates of the conic solve are in scvx_socp.hpp; this file instantiates them for
 // the reference's model (control_dim = 3), scvx_socp_fin.hip for the fin extension (control_dim = 5).
@@ -16,11 +22,13 @@
 // tridiagonal Schur complement and the long dot products of the two big trust-region cones; reductions
 // are cross-lane shuffles; the 14x14 pivot tiles of the block Cholesky live in LDS.  Each trajectory's
 // working set is one contiguous slab of HBM so every strided lane loop is a coalesced access.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include <cstdio>
@@ -245,6 +253,15 @@ __global__ void copy_flags_kernel(int B, const int* __restrict__ src, int* __res
 }  // namespace scvx
 
 // ---------------------------------------------------------------------------------------------------
+// profiling marks of a batch, shared by the batch and the views of its parts: 7 events per (profiled step, part), in enqueue order
+struct scvx_step_prof {
+    std::vector<hipEvent_t> events;  // pool, reused across scvx_batch_get_profile calls
+    size_t nmarks = 0;               // marks recorded since the last scvx_batch_get_profile
+    size_t steps = 0;                // profiled steps since then
+    bool split = false;              // some of them ran as parts: the classes are unions of intervals measured from `base`
+    hipEvent_t base = nullptr;       // recorded on the context's stream when profiling is switched on and after every read
+};
+
 struct scvx_batch {
     scvx_ctx* ctx = nullptr;
     int B = 0, K = 0, nrec = 0;
@@ -282,8 +299,16 @@ struct scvx_batch {
     int nlive_hint = -1;     // trajectories scvx_solve still steps (host view, a few steps old); -1 = all: picks the conic solver's executor
     bool initialised = false;
     bool profiling = false;
-    std::vector<hipEvent_t> events;  // pool, 7 per profiled step, reused across scvx_batch_get_profile calls
-    size_t nmarks = 0;               // marks recorded since the last scvx_batch_get_profile
+    bool prof_now = false;           // the step being enqueued records marks
+    scvx_step_prof* prof = nullptr;
+    // Split step.  `dirty`: something other than a split step of this batch touched the batch or the context's stream since the last
+    // one (every entry point through check_batch, an unsplit step, another number of parts), so the parts fork from the context's
+    // stream again; while it is clear a part's consecutive steps depend on that part alone.  `pinned`: scvx_batch_trajectory_dev
+    // handed out a raw pointer, the caller may touch the batch at any time: dirty for good.
+    bool dirty = true, pinned = false;
+    unsigned long long epoch = 0;    // the context's epoch at the last split step
+    int last_parts = 1;              // parts of the last step / reset (scvx_debug_step_parts)
+    hipEvent_t ev_fork = nullptr, ev_part[SCVX_MAX_PARTS] = {nullptr, nullptr, nullptr, nullptr};   // created on first use
 };
 
 namespace {
@@ -310,9 +335,45 @@ int dmalloc(scvx_ctx* ctx, T** p, size_t n) {
     return SCVX_OK;
 }
 
-int split_views(scvx_batch* b, const double* rec, double* x, double* u, double* sigma) {
+// The per-trajectory device arrays of a batch: (member, elements per trajectory), the ONE list from which scvx_batch_create sizes its
+// allocations and part_view advances its pointers.  f(pointer member, bytes per element, elements per trajectory, optional);
+// optional = not allocated at creation (the float tiles replace `deriv` in scvx_batch_set_linearization_f32).  `acc` and `d_nlive`
+// are totals of the whole batch and the lazily allocated scratch of the analysis calls is not touched by a step: neither is here.
+template <class F>
+int for_each_slab(scvx_batch* b, F&& f) {
+    const size_t K = (size_t)b->K, NU = (size_t)b->NU, nrec = (size_t)b->nrec, dsz = (size_t)b->dsz;
+    int rc = 0;
+#define SCVX_SLAB(m, per, opt) rc |= f((void**)&b->m, sizeof(*b->m), (size_t)(per), opt)
+    SCVX_SLAB(traj, nrec, false); SCVX_SLAB(cand, nrec, false); SCVX_SLAB(traj0, nrec, false); SCVX_SLAB(sol, nrec, false);
+    SCVX_SLAB(x, (K + 1) * 14, false); SCVX_SLAB(u, (K + 1) * NU, false); SCVX_SLAB(sigma, 1, false);
+    SCVX_SLAB(cx, (K + 1) * 14, false); SCVX_SLAB(cu, (K + 1) * NU, false); SCVX_SLAB(csigma, 1, false);
+    SCVX_SLAB(endpoint, K * 14, false); SCVX_SLAB(deriv, K * dsz, false); SCVX_SLAB(deriv_f, K * dsz, true);
+    SCVX_SLAB(xprop, K * 14, false); SCVX_SLAB(nu, K * 14, false);
+    SCVX_SLAB(rk, 1, false); SCVX_SLAB(cost, 1, false); SCVX_SLAB(ic, 6, false); SCVX_SLAB(info, 4, false); SCVX_SLAB(out, 2, false);
+    SCVX_SLAB(ttr, 1, false); SCVX_SLAB(k1skip, 1, false);
+    SCVX_SLAB(marg, (K + 1) * 2, false); SCVX_SLAB(pmarg, (K + 1) * SCVX_PMARG_N, false);
+    SCVX_SLAB(work, b->work_stride, false);
+    SCVX_SLAB(iter, 1, false); SCVX_SLAB(status, 1, false); SCVX_SLAB(active, 1, false); SCVX_SLAB(live, 1, false);
+#undef SCVX_SLAB
+    return rc;
+}
+
+// Trajectories [t0, t0 + n) of `b` as a batch of their own: a shallow copy with every per-trajectory pointer advanced.  It owns nothing.
+int part_view(scvx_batch* b, int t0, int n, scvx_batch* v) {
+    *v = *b;
+    const size_t B = (size_t)b->B;
+    const int rc = for_each_slab(v, [&](void** p, size_t sz, size_t per, bool) {
+        if (t0 < 0 || n < 1 || ((size_t)t0 + (size_t)n) * per > B * per) return (int)SCVX_ERR_STATE;   // past what scvx_batch_create allocated
+        if (*p) *p = (char*)*p + (size_t)t0 * per * sz;
+        return (int)SCVX_OK;
+    });
+    v->B = n;
+    return rc ? fail(b->ctx, SCVX_ERR_STATE, "part_view: the part does not lie inside the batch") : SCVX_OK;
+}
+
+int split_views(scvx_batch* b, const double* rec, double* x, double* u, double* sigma, hipStream_t st) {
     const size_t n = (size_t)b->B * b->nrec;
-    hipLaunchKernelGGL(scvx::unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->ctx->stream, b->B, b->K, b->NU,
+    hipLaunchKernelGGL(scvx::unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->B, b->K, b->NU,
                        rec, x, u, sigma);
     SCVX_HIP(b->ctx, hipGetLastError());
     return SCVX_OK;
@@ -335,39 +396,43 @@ int socp_waves(int B, int num_cus) {
 }
 
 template <int NW>
-void launch_socp_block(scvx_batch* b, const int* mask) {
+void launch_socp_block(scvx_batch* b, const int* mask, hipStream_t st) {
     constexpr int NU = 3;
     if (b->deriv_f)
-        hipLaunchKernelGGL((scvx::socp_block_kernel<NW, float, NU>), dim3(b->B), dim3(64 * NW), 0, b->ctx->stream, b->C, b->B, b->work_stride,
+        hipLaunchKernelGGL((scvx::socp_block_kernel<NW, float, NU>), dim3(b->B), dim3(64 * NW), 0, st, b->C, b->B, b->work_stride,
                            b->x, b->u, b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
     else
-        hipLaunchKernelGGL((scvx::socp_block_kernel<NW, double, NU>), dim3(b->B), dim3(64 * NW), 0, b->ctx->stream, b->C, b->B, b->work_stride,
+        hipLaunchKernelGGL((scvx::socp_block_kernel<NW, double, NU>), dim3(b->B), dim3(64 * NW), 0, st, b->C, b->B, b->work_stride,
                            b->x, b->u, b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
 }
 
 // K1 for the batch's iterate, into the derivative buffer of the batch's mode
-hipError_t relinearize(scvx_batch* b, const int* skip) {
+hipError_t relinearize(scvx_batch* b, const int* skip, hipStream_t st) {
     const double dt = 1.0 / (b->K + 1);
     if (b->deriv_f)
-        return scvx::launch_linearize_store_f32(b->ctx, b->B, b->K, b->x, b->u, b->sigma, dt, b->endpoint, b->deriv_f, b->ctx->stream, skip);
-    return scvx::launch_linearize(b->ctx, b->B, b->K, b->x, b->u, b->sigma, dt, b->endpoint, b->deriv, b->ctx->stream, skip);
+        return scvx::launch_linearize_store_f32(b->ctx, b->B, b->K, b->x, b->u, b->sigma, dt, b->endpoint, b->deriv_f, st, skip);
+    return scvx::launch_linearize(b->ctx, b->B, b->K, b->x, b->u, b->sigma, dt, b->endpoint, b->deriv, st, skip);
 }
 
-int enqueue_socp(scvx_batch* b, const int* mask) {
-    // scvx_solve's tail: once few trajectories are still live the solve is latency-bound again, and the executors with
-    // several wavefronts per trajectory (dead blocks return at once) finish a step in half the time
-    const int w = socp_waves(b->nlive_hint >= 0 && b->nlive_hint < b->B ? (b->nlive_hint > 0 ? b->nlive_hint : 1) : b->B, b->ctx->num_cus);
+// The executor of a step: chosen ONCE from the whole batch and handed to its parts (the executors do not sum in the same order).
+// scvx_solve's tail: once few trajectories are still live the solve is latency-bound again, and the executors with
+// several wavefronts per trajectory (dead blocks return at once) finish a step in half the time
+int step_waves(const scvx_batch* b) {
+    return socp_waves(b->nlive_hint >= 0 && b->nlive_hint < b->B ? (b->nlive_hint > 0 ? b->nlive_hint : 1) : b->B, b->ctx->num_cus);
+}
+
+int enqueue_socp(scvx_batch* b, const int* mask, int w, hipStream_t st) {
     if (b->NU == 5) {   // fin extension: the same three executors, instantiated for control_dim = 5 in scvx_socp_fin.hip
         scvx::SocpLaunch a{b->C, b->B, b->work_stride, b->x, b->u, b->endpoint, b->deriv, b->deriv_f, b->rk, b->ic, mask,
-                           b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr, b->ctx->stream};
+                           b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr, st};
         scvx::launch_socp_fin(a, w);
-    } else if (w == 4) launch_socp_block<4>(b, mask);
-    else if (w == 2) launch_socp_block<2>(b, mask);
+    } else if (w == 4) launch_socp_block<4>(b, mask, st);
+    else if (w == 2) launch_socp_block<2>(b, mask, st);
     else if (b->deriv_f)
-        hipLaunchKernelGGL(scvx::socp_lin32_kernel, dim3(b->B), dim3(64), 0, b->ctx->stream, b->C, b->B, b->work_stride, b->x, b->u,
+        hipLaunchKernelGGL(scvx::socp_lin32_kernel, dim3(b->B), dim3(64), 0, st, b->C, b->B, b->work_stride, b->x, b->u,
                            b->endpoint, b->deriv_f, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
     else
-        hipLaunchKernelGGL(scvx::socp_kernel, dim3(b->B), dim3(64), 0, b->ctx->stream, b->C, b->B, b->work_stride, b->x, b->u,
+        hipLaunchKernelGGL(scvx::socp_kernel, dim3(b->B), dim3(64), 0, st, b->C, b->B, b->work_stride, b->x, b->u,
                            b->endpoint, b->deriv, b->rk, b->ic, mask, b->work, b->sol, b->nu, b->info, b->status, b->ttr, b->acc, b->marg_on ? b->marg : nullptr, b->pmarg_on ? b->pmarg : nullptr);
     SCVX_HIP(b->ctx, hipGetLastError());
     return SCVX_OK;
@@ -375,56 +440,133 @@ int enqueue_socp(scvx_batch* b, const int* mask) {
 
 constexpr size_t PROF_MAX_STEPS = 4096;   // profiled steps kept between two scvx_batch_get_profile calls
 
-int mark(scvx_batch* b) {
-    if (!b->profiling || b->nmarks >= 7 * PROF_MAX_STEPS) return SCVX_OK;
-    if (b->nmarks == b->events.size()) {
+// a step is about to be enqueued (as `parts` parts): does it record marks?
+void begin_step_profile(scvx_batch* b, int parts) {
+    scvx_step_prof* p = b->prof;
+    b->prof_now = b->profiling && p->steps < PROF_MAX_STEPS;
+    if (!b->prof_now) return;
+    p->steps++;
+    if (parts > 1) p->split = true;
+}
+
+int mark(scvx_batch* b, hipStream_t st) {
+    if (!b->prof_now) return SCVX_OK;
+    scvx_step_prof* p = b->prof;
+    if (p->nmarks == p->events.size()) {
         hipEvent_t e;
         SCVX_HIP(b->ctx, hipEventCreate(&e));
-        b->events.push_back(e);
+        p->events.push_back(e);
     }
-    SCVX_HIP(b->ctx, hipEventRecord(b->events[b->nmarks], b->ctx->stream));
-    b->nmarks++;
+    SCVX_HIP(b->ctx, hipEventRecord(p->events[p->nmarks], st));
+    p->nmarks++;
     return SCVX_OK;
 }
 
-int enqueue_step(scvx_batch* b, const int* mask) {
+// one solve_step of `b` (a batch or the view of a part) on `st` with the executor `w`
+int enqueue_step(scvx_batch* b, const int* mask, int w, hipStream_t st) {
     scvx_ctx* ctx = b->ctx;
-    hipStream_t st = ctx->stream;
     const double dt = 1.0 / (b->K + 1);
-    int rc = mark(b);
+    int rc = mark(b, st);
     if (rc) return rc;
-    rc = enqueue_socp(b, mask);
+    rc = enqueue_socp(b, mask, w, st);
     if (rc) return rc;
-    if ((rc = mark(b))) return rc;
+    if ((rc = mark(b, st))) return rc;
     const size_t n = (size_t)b->B * b->nrec;
     hipLaunchKernelGGL(scvx::candidate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->B, b->nrec, b->traj,
                        b->sol, b->cand);
     SCVX_HIP(ctx, hipGetLastError());
-    rc = split_views(b, b->cand, b->cx, b->cu, b->csigma);
+    rc = split_views(b, b->cand, b->cx, b->cu, b->csigma, st);
     if (rc) return rc;
-    if ((rc = mark(b))) return rc;
+    if ((rc = mark(b, st))) return rc;
     SCVX_HIP(ctx, scvx::launch_propagate(ctx, b->B, b->K, b->cx, b->cu, b->csigma, dt, b->xprop, st));
-    if ((rc = mark(b))) return rc;
+    if ((rc = mark(b, st))) return rc;
     hipLaunchKernelGGL(scvx::tr_update_kernel, dim3(b->B), dim3(64), 0, st, b->tr, b->B, b->cand, b->xprop, b->nu, b->info,
                        b->traj, b->rk, b->cost, b->iter, b->status, mask, b->active, b->live, b->out, b->acc, b->d_nlive, b->k1skip);
     SCVX_HIP(ctx, hipGetLastError());
-    if ((rc = mark(b))) return rc;
-    rc = split_views(b, b->traj, b->x, b->u, b->sigma);
+    if ((rc = mark(b, st))) return rc;
+    rc = split_views(b, b->traj, b->x, b->u, b->sigma, st);
     if (rc) return rc;
-    if ((rc = mark(b))) return rc;
+    if ((rc = mark(b, st))) return rc;
     // rocketland.jl:318; a rejected step returns before it (:301, about / dynam kept): those trajectories are skipped
-    SCVX_HIP(ctx, relinearize(b, b->k1skip));
-    if ((rc = mark(b))) return rc;
+    SCVX_HIP(ctx, relinearize(b, b->k1skip, st));
+    if ((rc = mark(b, st))) return rc;
     return SCVX_OK;
 }
 
-int check_batch(scvx_batch* b, bool need_init) {
+// step_call: scvx_solve_step[_async] and scvx_batch_reset, the calls that may run split; every other call leaves the batch dirty
+int check_batch(scvx_batch* b, bool need_init, bool step_call = false) {
     if (!b || !b->ctx) return SCVX_ERR_ARG;
+    if (!step_call) b->dirty = true;
     if (need_init && !b->initialised) return fail(b->ctx, SCVX_ERR_STATE, "call scvx_batch_init first");
     if (b->ctx->prob.aero_kind == 1 && !b->ctx->dyn.aero)
         return fail(b->ctx, SCVX_ERR_STATE, "AtmosphericData problem: call scvx_set_aero_table first");
     hipError_t e = hipSetDevice(b->ctx->device);
     if (e != hipSuccess) return fail(b->ctx, SCVX_ERR_HIP, "hipSetDevice failed");
+    return SCVX_OK;
+}
+
+// ---- Split step -----------------------------------------------------------------------------------------------------------------
+// Parts of the next step / reset, given the executor `w` chosen from the whole batch.  Default: 2 parts when the executor is the
+// one-wavefront form, no live-count hint is set and every part has more than 4 x CUs trajectories (below that a part would fit the
+// device at once and wants another executor): B >= 2050 on 256 CUs.  SCVX_STEP_SPLIT, read per call as SCVX_K4_WAVES is: 1 = never,
+// 2 - 4 = that many parts at any B >= M and with any executor (tests).  Parts are contiguous, the first B mod M one longer.
+int step_parts(const scvx_batch* b, int w) {
+    if (const char* v = std::getenv("SCVX_STEP_SPLIT"); v && *v) {
+        const int m = std::atoi(v);
+        if (m >= 2) return b->B >= (m > SCVX_MAX_PARTS ? SCVX_MAX_PARTS : m) ? (m > SCVX_MAX_PARTS ? SCVX_MAX_PARTS : m) : 1;
+        if (m == 1) return 1;
+    }
+    const int cus = b->ctx->num_cus > 0 ? b->ctx->num_cus : 256;
+    const int M = 2;
+    return w == 1 && b->nlive_hint < 0 && b->B / M > 4 * cus ? M : 1;
+}
+
+// body(view of the part, its stream) for each of the M parts of `b`, each on its side stream of the context; none runs on
+// ctx->stream.  Fork: a part's stream waits for what is on ctx->stream only when the batch is dirty (see scvx_batch).  Join: one
+// event per part, and ctx->stream waits for them on the device -- work ordered after the call on the context's stream sees the step,
+// the host is not blocked and the side streams are not held back.
+template <class F>
+int run_parts(scvx_batch* b, int M, F&& body) {
+    scvx_ctx* ctx = b->ctx;
+    if (!b->ev_fork) SCVX_HIP(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+    for (int m = 0; m < M; m++) {
+        if (!ctx->side[m]) SCVX_HIP(ctx, hipStreamCreateWithFlags(&ctx->side[m], hipStreamNonBlocking));
+        if (!b->ev_part[m]) SCVX_HIP(ctx, hipEventCreateWithFlags(&b->ev_part[m], hipEventDisableTiming));
+    }
+    const bool fork = b->dirty || b->pinned || b->epoch != ctx->epoch || b->last_parts != M;
+    b->dirty = true;   // until every part is enqueued and joined
+    if (fork) SCVX_HIP(ctx, hipEventRecord(b->ev_fork, ctx->stream));
+    int t0 = 0;
+    for (int m = 0; m < M; m++) {
+        const int n = b->B / M + (m < b->B % M ? 1 : 0);
+        hipStream_t st = ctx->side[m];
+        if (fork) SCVX_HIP(ctx, hipStreamWaitEvent(st, b->ev_fork, 0));
+        scvx_batch v;
+        int rc = part_view(b, t0, n, &v);
+        if (!rc) rc = body(&v, st);
+        b->prof_now = v.prof_now;
+        // also behind a failed enqueue: whatever did get onto the side stream stays ordered before the context's stream
+        const hipError_t e1 = hipEventRecord(b->ev_part[m], st);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ctx->stream, b->ev_part[m], 0) : e1;
+        if (rc) return rc;
+        SCVX_HIP(ctx, e2);
+        t0 += n;
+    }
+    b->dirty = false;
+    b->epoch = ctx->epoch;
+    b->last_parts = M;
+    return SCVX_OK;
+}
+
+int enqueue_reset(scvx_batch* b, hipStream_t st) {
+    scvx_ctx* ctx = b->ctx;
+    SCVX_HIP(ctx, hipMemcpyAsync(b->traj, b->traj0, (size_t)b->B * b->nrec * 8, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(scvx::reset_scalars_kernel, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, st, b->B, b->rk, b->cost,
+                       b->iter, b->status, b->active, b->live, b->out, b->info);
+    SCVX_HIP(ctx, hipGetLastError());
+    const int rc = split_views(b, b->traj, b->x, b->u, b->sigma, st);
+    if (rc) return rc;
+    SCVX_HIP(ctx, relinearize(b, nullptr, st));
     return SCVX_OK;
 }
 
@@ -488,40 +630,17 @@ int scvx_batch_create(scvx_ctx* ctx, int B, scvx_batch** out) {
     if (const char* v = std::getenv("SCVX_WORK_PAD"); v && *v) b->work_stride += (size_t)std::atoi(v) & ~(size_t)7;   // diagnostic: extra doubles between the slabs
     const size_t nB = (size_t)B;
     int rc = 0;
-    rc |= dmalloc(ctx, &b->traj, nB * b->nrec);
-    rc |= dmalloc(ctx, &b->cand, nB * b->nrec);
-    rc |= dmalloc(ctx, &b->traj0, nB * b->nrec);
-    rc |= dmalloc(ctx, &b->sol, nB * b->nrec);
-    rc |= dmalloc(ctx, &b->x, nB * (K + 1) * 14);
-    rc |= dmalloc(ctx, &b->u, nB * (K + 1) * b->NU);
-    rc |= dmalloc(ctx, &b->sigma, nB);
-    rc |= dmalloc(ctx, &b->cx, nB * (K + 1) * 14);
-    rc |= dmalloc(ctx, &b->cu, nB * (K + 1) * b->NU);
-    rc |= dmalloc(ctx, &b->csigma, nB);
-    rc |= dmalloc(ctx, &b->endpoint, nB * K * 14);
-    rc |= dmalloc(ctx, &b->deriv, nB * K * b->dsz);
-    rc |= dmalloc(ctx, &b->xprop, nB * K * 14);
-    rc |= dmalloc(ctx, &b->nu, nB * K * 14);
-    rc |= dmalloc(ctx, &b->rk, nB);
-    rc |= dmalloc(ctx, &b->cost, nB);
-    rc |= dmalloc(ctx, &b->ic, nB * 6);
-    rc |= dmalloc(ctx, &b->info, nB * 4);
-    rc |= dmalloc(ctx, &b->out, nB * 2);
-    rc |= dmalloc(ctx, &b->ttr, nB);
+    b->prof = new (std::nothrow) scvx_step_prof();
+    if (!b->prof) rc = SCVX_ERR_NOMEM;
+    rc |= for_each_slab(b, [&](void** p, size_t sz, size_t per, bool optional) {
+        return optional || hipMalloc(p, nB * per * sz) == hipSuccess ? (int)SCVX_OK : (int)SCVX_ERR_NOMEM;
+    });
     rc |= dmalloc(ctx, &b->acc, (size_t)scvx::ACC_N);
     rc |= dmalloc(ctx, &b->d_nlive, (size_t)1);
-    rc |= dmalloc(ctx, &b->k1skip, nB);
-    rc |= dmalloc(ctx, &b->marg, nB * (K + 1) * 2);
-    rc |= dmalloc(ctx, &b->pmarg, nB * (K + 1) * SCVX_PMARG_N);
     if (!rc && (hipHostMalloc((void**)&b->h_nlive, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ev_nlive[0], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ev_nlive[1], hipEventDisableTiming) != hipSuccess)) rc = SCVX_ERR_HIP;
     if (!rc && hipMemset(b->acc, 0, sizeof(double) * scvx::ACC_N) != hipSuccess) rc = SCVX_ERR_HIP;
-    rc |= dmalloc(ctx, &b->work, nB * b->work_stride);
-    rc |= dmalloc(ctx, &b->iter, nB);
-    rc |= dmalloc(ctx, &b->status, nB);
-    rc |= dmalloc(ctx, &b->active, nB);
-    rc |= dmalloc(ctx, &b->live, nB);
     if (rc) {
         scvx_batch_destroy(b);
         return fail(ctx, SCVX_ERR_NOMEM, "device allocation failed for the batch (" + std::to_string(nB * b->work_stride * 8 >> 20) + " MiB of solver workspace)");
@@ -533,7 +652,15 @@ int scvx_batch_create(scvx_ctx* ctx, int B, scvx_batch** out) {
 void scvx_batch_destroy(scvx_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
+    // the parts of a split step still queued on the side streams end before their arrays go (the events are the batch's own: the
+    // context may already be gone)
+    for (hipEvent_t e : b->ev_part) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
+    if (b->prof) {
+        for (hipEvent_t e : b->prof->events) (void)hipEventDestroy(e);
+        if (b->prof->base) (void)hipEventDestroy(b->prof->base);
+        delete b->prof;
+    }
     for (hipEvent_t e : b->ev_nlive) if (e) (void)hipEventDestroy(e);
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
@@ -608,9 +735,9 @@ int scvx_batch_init(scvx_batch* b, const double* ic) {
     SCVX_HIP(ctx, hipMemsetAsync(b->out, 0, (size_t)B * 16, st));
     SCVX_HIP(ctx, hipMemsetAsync(b->info, 0, (size_t)B * 32, st));
     SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)B * 8, st));   // a huge finite value: nothing to reuse yet
-    rc = split_views(b, b->traj, b->x, b->u, b->sigma);
+    rc = split_views(b, b->traj, b->x, b->u, b->sigma, st);
     if (rc) return rc;
-    SCVX_HIP(ctx, relinearize(b, nullptr));
+    SCVX_HIP(ctx, relinearize(b, nullptr, st));
     SCVX_HIP(ctx, hipStreamSynchronize(st));  // host staging buffers go out of scope
     b->initialised = true;
     b->nactive_host = -1;
@@ -637,9 +764,9 @@ int scvx_batch_init_threedof(scvx_batch* b, const double* ic, const scvx_threedo
             e = hipMemcpyAsync(b->traj0, b->traj, (size_t)B * b->nrec * 8, hipMemcpyDeviceToDevice, st);
             if (e == hipSuccess) e = hipMemcpyAsync(hinfo.data(), d_info, hinfo.size() * 8, hipMemcpyDeviceToHost, st);
         }
-        if (rc == SCVX_OK && e == hipSuccess) rc = split_views(b, b->traj, b->x, b->u, b->sigma);
+        if (rc == SCVX_OK && e == hipSuccess) rc = split_views(b, b->traj, b->x, b->u, b->sigma, st);
         if (rc == SCVX_OK && e == hipSuccess)
-            e = relinearize(b, nullptr);
+            e = relinearize(b, nullptr, st);
     }
     const hipError_t es = hipStreamSynchronize(st);
     if (d_sol) (void)hipFree(d_sol);
@@ -652,26 +779,31 @@ int scvx_batch_init_threedof(scvx_batch* b, const double* ic, const scvx_threedo
 }
 
 int scvx_batch_reset(scvx_batch* b) {
-    int rc = check_batch(b, true);
+    int rc = check_batch(b, true, true);
     if (rc) return rc;
-    scvx_ctx* ctx = b->ctx;
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(b->traj, b->traj0, (size_t)b->B * b->nrec * 8, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(scvx::reset_scalars_kernel, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, st, b->B, b->rk, b->cost,
-                       b->iter, b->status, b->active, b->live, b->out, b->info);
-    SCVX_HIP(ctx, hipGetLastError());
-    rc = split_views(b, b->traj, b->x, b->u, b->sigma);
-    if (rc) return rc;
-    SCVX_HIP(ctx, relinearize(b, nullptr));
     b->nactive_host = -1;
-    return SCVX_OK;
+    b->nlive_hint = -1;
+    const int M = step_parts(b, step_waves(b));
+    if (M > 1) return run_parts(b, M, [](scvx_batch* v, hipStream_t st) { return enqueue_reset(v, st); });
+    b->dirty = true;
+    b->last_parts = 1;
+    return enqueue_reset(b, b->ctx->stream);
 }
 
 int scvx_solve_step_async(scvx_batch* b) {
-    int rc = check_batch(b, true);
+    int rc = check_batch(b, true, true);
     if (rc) return rc;
     b->nlive_hint = b->nactive_host >= 0 && b->nactive_host < b->B ? b->nactive_host : -1;
-    rc = enqueue_step(b, b->active);
+    const int w = step_waves(b);
+    const int M = step_parts(b, w);
+    begin_step_profile(b, M);
+    if (M > 1) {
+        rc = run_parts(b, M, [w](scvx_batch* v, hipStream_t st) { return enqueue_step(v, v->active, w, st); });
+    } else {
+        b->dirty = true;   // the step runs on the context's stream: a split step after it forks from there
+        b->last_parts = 1;
+        rc = enqueue_step(b, b->active, w, b->ctx->stream);
+    }
     b->nlive_hint = -1;
     return rc;
 }
@@ -723,7 +855,8 @@ int scvx_solve(scvx_batch* b, int32_t* status, int32_t* iters, double* nu_norm, 
             if (nlive == 0) break;
             b->nlive_hint = nlive;
         }
-        rc = enqueue_step(b, b->live);
+        begin_step_profile(b, 1);
+        rc = enqueue_step(b, b->live, step_waves(b), ctx->stream);
         if (rc) { b->nlive_hint = -1; return rc; }
         SCVX_HIP(ctx, hipMemcpyAsync(&b->h_nlive[q], b->d_nlive, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         SCVX_HIP(ctx, hipEventRecord(b->ev_nlive[q], ctx->stream));
@@ -990,9 +1123,9 @@ int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
     scvx_ctx* ctx = b->ctx;
     SCVX_HIP(ctx, hipMemcpyAsync(b->traj, traj, (size_t)b->B * b->nrec * 8, hipMemcpyHostToDevice, ctx->stream));
     SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, ctx->stream));   // a new iterate: no optimum to reuse
-    rc = split_views(b, b->traj, b->x, b->u, b->sigma);
+    rc = split_views(b, b->traj, b->x, b->u, b->sigma, ctx->stream);
     if (rc) return rc;
-    SCVX_HIP(ctx, relinearize(b, nullptr));
+    SCVX_HIP(ctx, relinearize(b, nullptr, ctx->stream));
     SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SCVX_OK;
 }
@@ -1177,6 +1310,7 @@ int scvx_batch_replan(scvx_batch* b) {
 
 int scvx_batch_trajectory_dev(scvx_batch* b, double** traj_dev, int64_t* n_doubles) {
     if (!b || !traj_dev || !n_doubles) return SCVX_ERR_ARG;
+    b->pinned = true;   // the caller may read or write through the pointer at any time: every later split step forks and joins
     *traj_dev = b->traj;
     *n_doubles = (int64_t)b->B * b->nrec;
     return SCVX_OK;
@@ -1210,6 +1344,7 @@ int scvx_batch_set_linearization_f32(scvx_batch* b, int on) {
     int rc = SCVX_OK;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     if ((on != 0) == (b->deriv_f != nullptr)) return SCVX_OK;
+    b->dirty = true;
     SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t nd = (size_t)b->B * b->K * b->dsz;
     if (on) {
@@ -1222,7 +1357,7 @@ int scvx_batch_set_linearization_f32(scvx_batch* b, int on) {
         b->deriv_f = nullptr;
     }
     if (b->initialised) {
-        SCVX_HIP(ctx, relinearize(b, nullptr));
+        SCVX_HIP(ctx, relinearize(b, nullptr, ctx->stream));
         SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, ctx->stream));   // the data changed: no optimum to reuse, no warm start
         SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -1306,10 +1441,21 @@ int scvx_batch_get_step_stats(scvx_batch* b, double* out8, int reset) {
     return SCVX_OK;
 }
 
+// Diagnostic export (not part of include/scvx.h): the number of parts the batch's last solve_step / reset ran as (1 = unsplit)
+int scvx_debug_step_parts(const scvx_batch* b) { return b ? b->last_parts : SCVX_ERR_ARG; }
+
 int scvx_batch_set_profiling(scvx_batch* b, int enable) {
-    if (!b) return SCVX_ERR_ARG;
-    b->nmarks = 0;
+    int rc = check_batch(b, false);
+    if (rc) return rc;
+    scvx_step_prof* p = b->prof;
+    p->nmarks = p->steps = 0;
+    p->split = false;
     b->profiling = enable != 0;
+    b->prof_now = false;
+    if (b->profiling) {   // the origin of the split form's intervals: on the context's stream, so before every mark that follows
+        if (!p->base) SCVX_HIP(b->ctx, hipEventCreate(&p->base));
+        SCVX_HIP(b->ctx, hipEventRecord(p->base, b->ctx->stream));
+    }
     return SCVX_OK;
 }
 
@@ -1318,19 +1464,43 @@ int scvx_batch_get_profile(scvx_batch* b, double* ms, int64_t* steps) {
     if (rc) return rc;
     if (!ms || !steps) return fail(b->ctx, SCVX_ERR_ARG, "null buffer");
     scvx_ctx* ctx = b->ctx;
-    SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    scvx_step_prof* p = b->prof;
+    SCVX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // every split step has been joined into it
     for (int i = 0; i < 5; i++) ms[i] = 0.0;
-    const size_t n = b->nmarks / 7;
-    // marks per step: 0 | socp | 1 | candidate+unpack | 2 | propagate | 3 | tr_update | 4 | unpack | 5 | linearize | 6
+    const size_t n = p->nmarks / 7;   // one group of marks per (step, part)
+    // marks per group: 0 | socp | 1 | candidate+unpack | 2 | propagate | 3 | tr_update | 4 | unpack | 5 | linearize | 6
     static const int slot[6] = {0, 4, 1, 2, 4, 3};
-    for (size_t s = 0; s < n; s++)
-        for (int i = 0; i < 6; i++) {
-            float t = 0.f;
-            SCVX_HIP(ctx, hipEventElapsedTime(&t, b->events[7 * s + i], b->events[7 * s + i + 1]));
-            ms[slot[i]] += (double)t;
+    if (!p->split) {
+        for (size_t s = 0; s < n; s++)
+            for (int i = 0; i < 6; i++) {
+                float t = 0.f;
+                SCVX_HIP(ctx, hipEventElapsedTime(&t, p->events[7 * s + i], p->events[7 * s + i + 1]));
+                ms[slot[i]] += (double)t;
+            }
+    } else {
+        // the parts overlap: per class, the length of the union of its intervals, every end measured from the one base event
+        std::vector<std::pair<float, float>> iv[5];
+        for (size_t s = 0; s < n; s++) {
+            float t[7];
+            for (int i = 0; i < 7; i++) SCVX_HIP(ctx, hipEventElapsedTime(&t[i], p->base, p->events[7 * s + i]));
+            for (int i = 0; i < 6; i++) iv[slot[i]].push_back({t[i], t[i + 1]});
         }
-    *steps = (int64_t)n;
-    b->nmarks = 0;   // the events stay in the pool
+        for (int c = 0; c < 5; c++) {
+            std::sort(iv[c].begin(), iv[c].end());
+            float lo = 0.f, hi = 0.f;
+            bool open = false;
+            for (const auto& v : iv[c]) {
+                if (open && v.first <= hi) { hi = v.second > hi ? v.second : hi; continue; }
+                if (open) ms[c] += (double)hi - (double)lo;
+                lo = v.first; hi = v.second > v.first ? v.second : v.first; open = true;
+            }
+            if (open) ms[c] += (double)hi - (double)lo;
+        }
+    }
+    *steps = (int64_t)p->steps;
+    p->nmarks = p->steps = 0;   // the events stay in the pool
+    p->split = false;
+    if (b->profiling) SCVX_HIP(ctx, hipEventRecord(p->base, ctx->stream));
     return SCVX_OK;
 }
 
@@ -1380,7 +1550,7 @@ int scvx_socp_solve(scvx_batch* b, double* sol, double* nu) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
-    rc = enqueue_socp(b, b->active);
+    rc = enqueue_socp(b, b->active, step_waves(b), ctx->stream);
     if (rc) return rc;
     const size_t n = (size_t)b->B * b->nrec;
     hipLaunchKernelGGL(scvx::candidate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, b->B, b->nrec,

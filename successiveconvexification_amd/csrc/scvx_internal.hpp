@@ -7,10 +7,17 @@
 
 namespace scvx { struct TdCache; }   // device tables + workspace of the 3-DoF initialiser (scvx_threedof.hip)
 
+#define SCVX_MAX_PARTS 4   // parts a split solve_step runs as, one side stream each (scvx_batch.hip)
+
 struct scvx_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    // Side streams of the split solve_step / reset (scvx_batch.hip): non-blocking, created on first use, destroyed with the context.
+    // `epoch` counts the context-level calls that change `stream` or what a launch reads from the context (scvx_set_stream,
+    // scvx_use_null_stream, scvx_set_nsub, scvx_set_aero_table): a batch that has not seen the current value forks from `stream` again.
+    hipStream_t side[SCVX_MAX_PARTS] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned long long epoch = 0;
     scvx_problem prob{};
     scvx::DynParams dyn{};
     int nsub = 10;
