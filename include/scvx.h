@@ -464,8 +464,8 @@ int scvx_track_fly_nav_f64_host(scvx_ctx *ctx, int B, int K, const double *x, co
  * [B][14][14] = the sample covariance of e, divisor S - 1, from the accumulated sums of e and e e' (all zero for S = 1).
  * Optional dense outputs (NULL = not wanted): flights [B][S][SCVX_FLIGHT_NREP], xland [B][S][14] = x_fly[K], dx0 [B][S][14] = the
  * offsets the device formed.  A non-finite gain, plan or C0 entry poisons the rows of its own plan only (N_BAD = S, NaN statistics).
- * Limits: the law is fed the TRUTH -- a navigation estimate in the sampled loop is out of scope, and `reserved` (must be NULL) keeps
- * its place in the argument list; the draws are shared across plans, so the rows of one call are not independent experiments;
+ * Limits: the law is fed the TRUTH -- the sampled loop flown on a navigation estimate is scvx_track_mc_nav_f64 below, and `reserved`
+ * (must be NULL) keeps its place in the argument list; the draws are shared across plans, so the rows of one call are not independent experiments;
  * quantiles are not reduced on the device -- take them from `flights`; w is the per-segment lump of the analyses, here as an impulse.
  * x, u, sigma, gain, flags (SCVX_TRACK_CLAMP), nsub as scvx_track_fly_f64; tol >= 0.  The _f64 form takes device pointers (sw14 on
  * the host) and is asynchronous on the context's stream; its partial sums live in a workspace that belongs to the context, so two
@@ -480,6 +480,56 @@ int scvx_track_mc_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, 
                            const double *gain, const double *C0, const double *xi0, const double *eta, const double *sw14,
                            const void *reserved, int nsub, int flags, double tol, double *mcrep, double *xmean, double *xcov,
                            double *flights, double *xland, double *dx0);
+
+/* ---- sampled closed-loop dispersion flown on a navigation ESTIMATE ---------------------------------------------------------------
+ * scvx_track_mc_f64 feeds the law the truth; scvx_nav_cov_f64 is first order.  This call is the nonlinear, sampled counterpart of the
+ * navigation analysis: the S flights per plan of scvx_track_mc_f64 with the law fed an estimate whose error eps is generated PER FLIGHT
+ * on the device from the filter gains of the analysis, with measurement noise and with the process noise that hits the truth.
+ * Model.  Flight (b, s) is scvx_track_mc_f64's flight, statement for statement (start, impulses, clamp, samples, counters), with the
+ * law fed x_fly - eps+_k: the deviation is formed as in scvx_track_fly_nav_f64, z = [(x_fly - eps+_k) - xbar_k; u_k - ubar_k].  The
+ * error eps (14 per flight) follows the linear recursion of the analysis:
+ *     eps_0     = CN[b] xin[s]                                          (fma, ascending j from 0; CN [B][14][14] row-major, a factor
+ *                                                                        of the analysis's N0 = CN CN')
+ *     eps+_k    = eps_k - Kf[b][k] (H eps_k + sqrt(rm) (.) nud[s][k])     k = 0..K-1     (m = 0: eps+_k = eps_k)
+ *     eps_{k+1} = A_k[b] eps+_k  (+ sqrt(w) (.) eta[s][k]  when eta is given)
+ * with A_k the state block of the plan's derivative tile (deriv [B][K][14+2NU+1][14], column-major tiles: the first 14 columns), Kf
+ * [B][K][14][m] the gains scvx_nav_cov_f64 writes (`kf`), H [m][14] and rm [m] HOST arrays as there, xin [S][14] and nud [S][K][m]
+ * standard-normal draws shared by all plans like xi0 and eta.  The eta is THE SAME eta[s][k] that the truth receives as an impulse, with
+ * the same sign: the filter propagates its estimate without the disturbance, so eps receives it -- the W "in all four blocks" of
+ * scvx_nav_cov_f64.  w14 [14] >= 0 is the VARIANCE w, a host array, as the navigation call takes it (the library forms sqrt(w)), so one
+ * w feeds the gains and the flights; eta = NULL, or w14 all zero: no process noise.  With CN = 0, m = 0 and no noise every output that
+ * scvx_track_mc_f64 has is bitwise that call's; with eta = NULL a flight's 16 columns and x_fly[K] are bitwise those of
+ * scvx_track_fly_nav_f64 fed the dx0 and the eps+ (`navfed`) this call formed.
+ * Limits: the recursion for eps is LINEAR and does not depend on the flown state -- it is the analysis's error model with the truth
+ * flown nonlinearly, not an EKF re-linearised on the flown state; the gains are the analysis's gains, not recomputed per flight; there
+ * is no measurement at node K; the clamp acts on the command formed from the estimate; and the limits of scvx_track_mc_f64.
+ * Outputs.  mcrep [B][SCVX_MC_NREP], xmean [B][14], xcov [B][14][14]: exactly as scvx_track_mc_f64 defines them.  jmean [B][28] and
+ * jcov [B][28][28]: the mean and the sample covariance (divisor S - 1, zero for S = 1) of [e; eps_K], e = x_fly[K] - xbar_K, by the
+ * accumulation of xcov: xcov is bitwise jcov[:, 0:14, 0:14].  mcnav [B][SCVX_NAV_NREP], the sampled counterpart of navrep: SCVX_NAV_M ..
+ * SCVX_NAV_W the square roots of the block traces of the eps block of jcov; column 5 (where navrep has NAV_PEAK: per-node sums stay out
+ * of the reduction) is MAX_FED, */
+#define SCVX_MCNAV_MAX_FED 5 /* the largest |eps+_k|_inf fed to the law over all flights and nodes, NaN if any is NaN                  */
+/* and SCVX_NAV_EST_R, SCVX_NAV_EST_V from Sigma_xx - C - C' + P of jcov, as navrep defines them.  Optional dense outputs (NULL = not
+ * wanted): flights, xland, dx0 as scvx_track_mc_f64; navfed [B][S][K][14] = eps+_k; navK [B][S][14] = eps_K.  Without a dense output
+ * the device memory of the call is O(B S), not O(B S K).  The reduction is deterministic as there: two calls agree bit for bit.  A
+ * non-finite kf, deriv, CN, gain or plan entry poisons the rows of its own plan only (N_BAD = S, NaN statistics).
+ * The _f64 form takes device pointers (w14, H, rm on the host), is asynchronous on the context's stream and shares the workspace of
+ * scvx_track_mc_f64 (no two of these calls overlapping on different streams).  SCVX_ERR_ARG for everything scvx_track_mc_f64 and the
+ * measurement model of scvx_nav_cov_f64 refuse (m outside [0, 14], m > 0 with a null H or rm, an rm <= 0 or non-finite, a non-finite
+ * H), a negative or non-finite w14, eta without w14, a null deriv / CN / xin / jmean / jcov / mcnav, m > 0 with a null kf or nud. */
+int scvx_track_mc_nav_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                          const double *gain_dev, const double *C0_dev, const double *xi0_dev, const double *eta_dev,
+                          const double *w14, const double *deriv_dev, const double *kf_dev, const double *CN_dev,
+                          const double *xin_dev, const double *nud_dev, int m, const double *H, const double *rm, int nsub, int flags,
+                          double tol, double *mcrep_dev, double *xmean_dev, double *xcov_dev, double *jmean_dev, double *jcov_dev,
+                          double *mcnav_dev, double *flights_dev, double *xland_dev, double *dx0_dev, double *navfed_dev,
+                          double *navK_dev);
+int scvx_track_mc_nav_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                               const double *gain, const double *C0, const double *xi0, const double *eta, const double *w14,
+                               const double *deriv, const double *kf, const double *CN, const double *xin, const double *nud, int m,
+                               const double *H, const double *rm, int nsub, int flags, double tol, double *mcrep, double *xmean,
+                               double *xcov, double *jmean, double *jcov, double *mcnav, double *flights, double *xland, double *dx0,
+                               double *navfed, double *navK);
 
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
@@ -629,6 +679,18 @@ int scvx_batch_track_fly_nav(scvx_batch *b, const double *q14, const double *rNU
 int scvx_batch_track_mc(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
                         const double *xi0, const double *eta, const double *sw14, const void *reserved, int nsub, int flags,
                         double tol, double *mcrep, double *xmean, double *xcov, double *flights, double *xland, double *dx0);
+
+/* scvx_track_mc_nav_f64 on the batch's current accepted iterate, its own derivative tiles (float tiles are widened on load) and the
+ * gains of the weights q14 / rNU / qf14.  N0 [B][14][14] is the handover covariance of the navigation error and CN [B][14][14] a factor
+ * of it (N0 = CN CN'; the caller's responsibility): the call first runs the navigation launch on the device with N0, H, rm and w14 (and
+ * S0 = 0: the filter gains do not depend on it) to obtain Kf, then the flights.  C0, xi0, eta, w14, xin, nud, H, rm and every output are
+ * host arrays; any output may be NULL; nsub = 0 takes the context's.  The batch is left untouched, as by scvx_batch_flight_check.
+ * Synchronises.  SCVX_ERR_ARG as scvx_track_mc_nav_f64, and for a null N0. */
+int scvx_batch_track_mc_nav(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                            const double *xi0, const double *eta, const double *w14, const double *N0, const double *CN,
+                            const double *xin, const double *nud, int m, const double *H, const double *rm, int nsub, int flags,
+                            double tol, double *mcrep, double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav,
+                            double *flights, double *xland, double *dx0, double *navfed, double *navK);
 
 /* ---- thrust-band back-offs and covariance-driven replanning (no counterpart in the reference) ---------------------------------
  * Per-trajectory, per-node back-offs of the thrust band, read by the conic solve alone:

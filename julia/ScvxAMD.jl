@@ -593,6 +593,74 @@ track_mc_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::
         cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(sw), C_NULL, nsub, flags, tol, mcrep_dev,
         xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev), "scvx_track_mc_f64")
 
+# ---- sampled closed-loop dispersion flown on a navigation estimate (new) ----------------------------------------------------
+# include/scvx.h, "sampled closed-loop dispersion flown on a navigation ESTIMATE": track_mc with the law fed x_fly - eps+_k, the error
+# eps generated per flight on the device.  Besides track_mc's arguments: N0 14 x 14 x B (batch form: the filter gains come from it), CN
+# 14 x 14 x B its factors stored ROW-major like C0, xin 14 x S and nud m x K x S (or nothing with H === nothing) standard-normal draws,
+# H 14 x m and rm as navigation(); kf m x 14 x K x B the gains navigation(...; dense=true) returns; w the VARIANCE (the library roots it).
+# Returns mcrep, xmean, xcov, jmean 28 x B, jcov 28 x 28 x B, mcnav NAV_NREP x B (row MCNAV_MAX_FED + 1 where navrep has NAV_PEAK),
+# and with dense flights, xland, dx0, navfed 14 x K x S x B, navK 14 x S x B.
+const MCNAV_MAX_FED = 5   # SCVX_MCNAV_MAX_FED
+
+function _mc_nav_outputs(B::Int, S::Int, K::Int, dense::Bool)
+    return (Matrix{Float64}(undef, 28, B), Array{Float64,3}(undef, 28, 28, B), Matrix{Float64}(undef, NAV_NREP, B),
+            dense ? Array{Float64,4}(undef, 14, K, S, B) : nothing, dense ? Array{Float64,3}(undef, 14, S, B) : nothing)
+end
+
+function track_mc_nav(b::Batch, C0::Array{Float64,3}, xi0::Matrix{Float64}, N0::Array{Float64,3}, CN::Array{Float64,3},
+                      xin::Matrix{Float64}, H, rm; nud::Union{Nothing,Array{Float64,3}}=nothing, eta::Union{Nothing,Array{Float64,3}}=nothing,
+                      w=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false, tol::Float64=0.0, dense::Bool=false)
+    NU = control_dim(b.cache)
+    S = size(xi0, 2); K = b.cache.problem.K
+    (size(C0) == (14, 14, b.B) && size(N0) == (14, 14, b.B) && size(CN) == (14, 14, b.B) && size(xi0, 1) == 14 && size(xin) == (14, S)) ||
+        throw(ArgumentError("C0, N0, CN must be 14 x 14 x B, xi0 and xin 14 x S"))
+    m, Hm, rmv = _nav_model(H, rm)
+    (m == 0 || (nud !== nothing && size(nud) == (m, K, S))) || throw(ArgumentError("nud must be m x K x S"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(b.B, S, K, dense)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv check(b.cache.ctx, ccall((:scvx_batch_track_mc_nav, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, xi0, _cov_opt(eta), _cov_opt(wv), N0, CN, xin,
+        _cov_opt(m > 0 ? nud : nothing), m, _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean,
+        jcov, mcnav, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK)), "scvx_batch_track_mc_nav")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK
+end
+
+function track_mc_nav(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, deriv::Array{Float64,4},
+                      gain::Array{Float64,4}, C0::Array{Float64,3}, xi0::Matrix{Float64}, CN::Array{Float64,3}, xin::Matrix{Float64}, H, rm;
+                      kf::Union{Nothing,Array{Float64,4}}=nothing, nud::Union{Nothing,Array{Float64,3}}=nothing,
+                      eta::Union{Nothing,Array{Float64,3}}=nothing, w=nothing, nsub::Int=10, clamp::Bool=false, tol::Float64=0.0,
+                      dense::Bool=false)
+    B, K, S = size(x, 3), size(x, 2) - 1, size(xi0, 2)
+    m, Hm, rmv = _nav_model(H, rm)
+    (m == 0 || (kf !== nothing && size(kf) == (m, 14, K, B) && nud !== nothing && size(nud) == (m, K, S))) ||
+        throw(ArgumentError("with measurements: kf m x 14 x K x B (navigation(...; dense=true)) and nud m x K x S"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(B, S, K, dense)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv check(cache.ctx, ccall((:scvx_track_mc_nav_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, xi0, _cov_opt(eta), _cov_opt(wv), deriv, _cov_opt(m > 0 ? kf : nothing), CN, xin,
+        _cov_opt(m > 0 ? nud : nothing), m, _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean, jcov,
+        mcnav, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK)), "scvx_track_mc_nav_f64_host")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK
+end
+
+# the same on device pointers, asynchronous on the context's stream; w (the variance), H (14 x m) and rm stay host arrays (or nothing)
+track_mc_nav_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                  gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble}, w::Union{Nothing,Vector{Float64}},
+                  deriv_dev::Ptr{Cdouble}, kf_dev::Ptr{Cdouble}, CN_dev::Ptr{Cdouble}, xin_dev::Ptr{Cdouble}, nud_dev::Ptr{Cdouble}, m::Int,
+                  H::Union{Nothing,Matrix{Float64}}, rm::Union{Nothing,Vector{Float64}}, nsub::Int, flags::Int, tol::Float64,
+                  mcrep_dev::Ptr{Cdouble}, xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble}, jmean_dev::Ptr{Cdouble}, jcov_dev::Ptr{Cdouble},
+                  mcnav_dev::Ptr{Cdouble}, flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble},
+                  navfed_dev::Ptr{Cdouble}, navK_dev::Ptr{Cdouble}) =
+    GC.@preserve w H rm check(cache.ctx, ccall((:scvx_track_mc_nav_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(w), deriv_dev, kf_dev, CN_dev, xin_dev,
+        nud_dev, m, _cov_opt(H), _cov_opt(rm), nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev,
+        flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev), "scvx_track_mc_nav_f64")
+
 # ---- thrust-band back-offs and covariance-driven replanning (new) ----------------------------------------------------------
 # include/scvx.h, "thrust-band back-offs".  Tmin + lo[k, b] <= |u_k| <= Tmax - hi[k, b], read by the conic solve alone; the flight
 # check and the tracking calls keep auditing against the true Tmin / Tmax.  psig is 5 x (K+1) x B (row PSIG_* + 1 holds that column).

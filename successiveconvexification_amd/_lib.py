@@ -79,6 +79,9 @@ MC_NREP = 48
 MC_COLUMNS = (tuple("MAX_" + n for n in FLIGHT_COLUMNS) + tuple("MEAN_" + n for n in FLIGHT_COLUMNS)
               + tuple("P_" + n[2:] for n in FLIGHT_COLUMNS[6:15]) + ("P_ANY", "OUT_LO", "OUT_HI", "N_BAD", "S"))
 MC_INDEX = {n: i for i, n in enumerate(MC_COLUMNS)}
+# scvx_track_mc_nav_*: the columns of the sampled navigation report [B][NAV_NREP]: navrep's, with MAX_FED where navrep has NAV_PEAK
+MCNAV_COLUMNS = ("NAV_M", "NAV_R", "NAV_V", "NAV_Q", "NAV_W", "MAX_FED", "EST_R", "EST_V")
+MCNAV_INDEX = {n: i for i, n in enumerate(MCNAV_COLUMNS)}
 
 _vp = C.c_void_p
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
@@ -119,6 +122,12 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp]),
     "scvx_track_mc_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int,
                                          C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_track_mc_nav_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp,
+                                        C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "scvx_track_mc_nav_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             _dp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),
@@ -155,6 +164,8 @@ SIGNATURES = {
     "scvx_batch_track_fly_nav": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "scvx_batch_track_mc": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp,
                                       _dp, _dp]),
+    "scvx_batch_track_mc_nav": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
+                                          C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_set_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
     "scvx_batch_get_thrust_margins": (C.c_int, [_vp, _dp, _dp]),
     "scvx_batch_thrust_margins_from_cov": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp]),

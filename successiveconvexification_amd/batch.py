@@ -252,13 +252,28 @@ class ScvxBatch:
                                                _p(xfly) if dense else None, _p(ufly) if dense else None), "scvx_batch_track_fly")
         return FlightReport(rep, xfly, "track", ufly)
 
-    def track_mc(self, S0, samples=256, seed=0, w=None, q=None, r=None, qf=None, nsub=None, clamp=False, tol=0.0, dense=(), draws=None):
+    def track_mc(self, S0, samples=256, seed=0, w=None, q=None, r=None, qf=None, nsub=None, clamp=False, tol=0.0, dense=(), draws=None,
+                 nav=None):
         """Sampled closed-loop dispersion of the batch's current accepted iterate under its LQR gains: `samples` flights per plan on
         the device, one dynamics.McReport row per plan (scvx_batch_track_mc; S0 -- a [14] vector of standard deviations, one [14][14]
         or [B][14][14] --, seed, w, clamp, tol, dense and draws as dynamics.track_mc_batch, weights as track_gains).  The batch is left
-        untouched."""
+        untouched.  nav = (N0, H, rm), the model of navigation(): the flights are flown on a navigation estimate whose error is
+        generated per flight on the device from the filter gains of that analysis (scvx_batch_track_mc_nav; dense and draws as
+        dynamics.track_mc_nav_batch): a dynamics.McNavReport."""
         from .dynamics import McReport, _mc_inputs, _mc_outputs, _track_weights
         qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
+        if nav is not None:
+            from .dynamics import McNavReport, _mc_nav_inputs, _mc_nav_outputs, _nav_arg
+            n0, m, Hm, rmv = _nav_arg(nav, self.B)
+            c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(S0, n0, self.B, self.K, m, samples, seed, w, draws)
+            S = xi0.shape[0]
+            red, dn = _mc_nav_outputs(self.B, S, self.K, dense)
+            opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+            self._chk(self._L.scvx_batch_track_mc_nav(
+                self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), _p(xi0), opt(eta), opt(wv), _p(n0), _p(cn), _p(xin), opt(nud), m, opt(Hm),
+                opt(rmv), int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red], *[opt(a) for a in dn]),
+                "scvx_batch_track_mc_nav")
+            return McNavReport(*red, *dn)
         c0, xi0, eta, sw = _mc_inputs(S0, self.B, self.K, samples, seed, w, draws)
         S = xi0.shape[0]
         rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(self.B, S, dense)

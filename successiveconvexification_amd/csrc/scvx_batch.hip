@@ -1071,6 +1071,71 @@ int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, con
     return SCVX_OK;
 }
 
+int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                            const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
+                            const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags, double tol,
+                            double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav, double* flights,
+                            double* xland, double* dx0, double* navfed, double* navK) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (nsub == 0) nsub = ctx->nsub;
+    // every check before anything is enqueued; the tiles and the outputs are the batch's or optional, so a placeholder stands in for
+    // them, and for kf, which the navigation launch below writes
+    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
+    if ((rc = scvx::check_track_mc_nav(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->x, C0, xi0, eta, w14, b->x, b->x, CN, xin, nud, m, H, rm,
+                                       nsub, flags, tol, b->x, b->x, b->x, b->x, b->x, b->x)))
+        return rc;
+    if (!N0) return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (N0)");
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    const int B = b->B, K = b->K;
+    const size_t nc = (size_t)B * 196, ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
+                 nf = (size_t)B * S * SCVX_FLIGHT_NREP, nl = (size_t)B * S * 14, nk = (size_t)B * K * 14 * m, nn = (size_t)S * K * m,
+                 nfed = (size_t)B * S * K * 14;
+    scvx::DevBuf<double> dc, di, de, dz, dn0, dcn, dxi, dnu, dk, dcr, dnr, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipSuccess;
+    auto in = [&](scvx::DevBuf<double>& d, const double* h, size_t n) {
+        if (e == hipSuccess) e = hipMalloc((void**)&d.p, n * 8);
+        if (e == hipSuccess && h) e = hipMemcpyAsync(d.p, h, n * 8, hipMemcpyHostToDevice, st);
+    };
+    in(dc, C0, nc), in(di, xi0, ni), in(dn0, N0, nc), in(dcn, CN, nc), in(dxi, xin, ni);
+    if (eta) in(de, eta, ne);
+    if (m > 0) in(dnu, nud, nn), in(dk, nullptr, nk);
+    in(dz, nullptr, nc), in(dcr, nullptr, (size_t)B * SCVX_COV_NREP), in(dnr, nullptr, (size_t)B * SCVX_NAV_NREP);
+    in(dr, nullptr, nr), in(dm, nullptr, nm), in(dv, nullptr, nc), in(djm, nullptr, (size_t)B * 28), in(djc, nullptr, (size_t)B * 784);
+    in(dnv, nullptr, (size_t)B * SCVX_NAV_NREP);
+    if (flights) in(df, nullptr, nf);
+    if (xland) in(dl, nullptr, nl);
+    if (dx0) in(d0, nullptr, nl);
+    if (navfed) in(dfe, nullptr, nfed);
+    if (navK) in(dnk, nullptr, nl);
+    // the filter gains: the navigation launch with the same N0, H, rm and w; Kf does not depend on S0, which is zero here
+    if (e == hipSuccess) e = hipMemsetAsync(dz.p, 0, nc * 8, st);
+    if (e == hipSuccess && m > 0)
+        e = b->deriv_f ? scvx::launch_nav_cov_f32(ctx, B, K, b->x, b->u, b->deriv_f, b->track_gain, dz.p, dn0.p, m, H, rm, w14, dcr.p, dnr.p,
+                                                  nullptr, nullptr, dk.p, nullptr, st)
+                       : scvx::launch_nav_cov(ctx, B, K, b->x, b->u, b->deriv, b->track_gain, dz.p, dn0.p, m, H, rm, w14, dcr.p, dnr.p, nullptr,
+                                              nullptr, dk.p, nullptr, st);
+    if (e == hipSuccess)
+        e = b->deriv_f ? scvx::launch_track_mc_nav_f32(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv_f,
+                                                       dk.p, dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p,
+                                                       dnv.p, df.p, dl.p, d0.p, dfe.p, dnk.p, st)
+                       : scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv, dk.p,
+                                                   dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p,
+                                                   df.p, dl.p, d0.p, dfe.p, dnk.p, st);
+    auto out = [&](double* h, scvx::DevBuf<double>& d, size_t n) {
+        if (e == hipSuccess && h) e = hipMemcpyAsync(h, d.p, n * 8, hipMemcpyDeviceToHost, st);
+    };
+    out(mcrep, dr, nr), out(xmean, dm, nm), out(xcov, dv, nc), out(jmean, djm, (size_t)B * 28), out(jcov, djc, (size_t)B * 784);
+    out(mcnav, dnv, (size_t)B * SCVX_NAV_NREP), out(flights, df, nf), out(xland, dl, nl), out(dx0, d0, nl), out(navfed, dfe, nfed);
+    out(navK, dnk, nl);
+    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_nav: ") + hipGetErrorString(e));
+    return SCVX_OK;
+}
+
 int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,
                        const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
                        double* navsig, double* kf, double* joint) {

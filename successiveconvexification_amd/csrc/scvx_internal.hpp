@@ -111,6 +111,26 @@ int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void
                    const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
                    const void* mcrep, const void* xmean, const void* xcov);
 void mc_workspace_free(scvx_ctx* ctx);
+// The same flown on a navigation estimate (scvx_mc_nav.hip): deriv[B][K][14+2NU+1][14] (double or float), kf[B][K][14][m] (nullptr with
+// m = 0), CN[B][14][14], xin[S][14], nud[S][K][m] (nullptr with m = 0); w, H, rm: host arrays (w the VARIANCE) or nullptr; jmean[B][28],
+// jcov[B][28][28], mcnav[B][SCVX_NAV_NREP]; navfed[B][S][K][14], navK[B][S][14] or nullptr.
+hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
+                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                               double* navfed, double* navK, hipStream_t st);
+hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                                   const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
+                                   const float* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                                   const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                                   double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                                   double* navfed, double* navK, hipStream_t st);
+int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
+                       const void* C0, const void* xi0, const void* eta, const double* w, const void* deriv, const void* kf,
+                       const void* CN, const void* xin, const void* nud, int m, const double* H, const double* rm, int nsub, int flags,
+                       double tol, const void* mcrep, const void* xmean, const void* xcov, const void* jmean, const void* jcov,
+                       const void* mcnav);
 
 // Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles (double or float) and the gains;
 // S0[B][14][14]; w: host array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.

@@ -18,30 +18,9 @@
 // past S flies sample S - 1 again, so that all 64 lanes reach the butterfly, and contributes nothing.
 #include <cmath>
 #include <limits>
-#include "scvx_internal.hpp"
+#include "scvx_mc.hpp"   // the partial row, McK and the wavefront reductions, shared with scvx_mc_nav.hip
 
 namespace scvx {
-
-// one partial row: 16 maxima, 16 sums, the counts of P_MASS .. P_FIN, P_ANY, OUT_LO, OUT_HI, N_BAD (as doubles: exact below 2^53),
-// the sum of the landing deviation e [14] and of the upper triangle of e e' [105]
-constexpr int MC_MAX = 0, MC_SUM = 16, MC_CNT = 32, MC_ANY = 41, MC_LO = 42, MC_HI = 43, MC_BAD = 44, MC_E = 45, MC_EE = 59, MC_NP = 164;
-
-struct McK {
-    double sw[14];   // sqrt(w): the size of the impulse per state component
-    double tol;
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ double wave_nan_max(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = nan_max(v, __shfl_xor(v, o));
-    return v;
-}
 
 template <bool AERO, bool FIN, bool TRQ>
 __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK c, McK m, int S, int K, const double* __restrict__ x,
@@ -321,7 +300,7 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(int S, int K, int nblk, 
 }
 
 // the context's workspace of partial rows, grown on demand (hipFree waits for whatever still reads the old one)
-static hipError_t mc_workspace(scvx_ctx* ctx, size_t doubles) {
+hipError_t mc_workspace(scvx_ctx* ctx, size_t doubles) {
     if (ctx->mc_ws_doubles >= doubles) return hipSuccess;
     if (ctx->mc_ws) (void)hipFree(ctx->mc_ws);
     ctx->mc_ws = nullptr;

@@ -433,7 +433,7 @@ def _mc_outputs(B, S, dense):
 
 
 def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=0, w=None, nsub=10, clamp=False, tol=0.0, dense=(),
-                   draws=None) -> McReport:
+                   draws=None, nav=None) -> McReport:
     """Sampled closed-loop dispersion of the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] tracked under the gains gain
     [B][K][nu][14+nu]: `samples` flights PER PLAN on the device, reduced there to one McReport row per plan (scvx_track_mc_f64_host;
     the model, the impulse convention and the limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one [14][14]
@@ -441,7 +441,14 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     are montecarlo.mc_draws(samples, K, seed), shared by all plans.  w: process-noise variance per segment, a scalar or [14] (None =
     no noise), applied as an impulse sqrt(w) * eta at every node -- the + diag(w) of cov_propagate_batch.  clamp as track_fly_batch;
     tol: the threshold of the P_* and OUT_* columns.  dense: True, or names out of "flights", "xland", "dx0".  draws = (xi0 [S][14],
-    eta [S][K][14] or None): use these instead of mc_draws (`samples` and `seed` are then ignored)."""
+    eta [S][K][14] or None): use these instead of mc_draws (`samples` and `seed` are then ignored).  nav = (N0, H, rm): the flights
+    are flown on a navigation estimate (track_mc_nav_batch on the plans' own linearisation, a McNavReport; draws then has four
+    entries); None: the law is fed the truth."""
+    if nav is not None:
+        n0, _, Hm, rv = _nav_arg(nav, np.shape(x)[0])
+        _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / np.shape(x)[1])
+        return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
+                                  tol=tol, dense=dense, draws=draws)
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     sigma = np.ascontiguousarray(sigma, np.float64)
@@ -562,6 +569,111 @@ def _nav_arg(nav, B):
     if m and not np.all(np.isfinite(Hm)):
         raise ValueError("H must be finite")
     return n0, m, Hm, rv
+
+
+class McNavReport(McReport):
+    """The report of a sampled dispersion flown on a navigation estimate (scvx_track_mc_nav_f64, include/scvx.h): everything a McReport
+    has, plus `jmean` [B][28] and `jcov` [B][28][28], the mean and the sample covariance of [e; eps_K] (e = x_fly[K] - xbar_K the landing
+    deviation, eps_K the error of the estimate there; xcov is jcov[:, :14, :14]), `navraw` [B][8] with one named numpy view per column
+    (report.NAV_R, report.MAX_FED, report.EST_R, ... -- _lib.MCNAV_COLUMNS) and the optional dense outputs `navfed` [B][S][K][14] (the
+    error eps+_k of the estimate the law was fed) and `navK` [B][S][14], or None."""
+
+    def __init__(self, raw, xmean, xcov, jmean, jcov, navraw, flights=None, xland=None, dx0=None, navfed=None, navK=None):
+        super().__init__(raw, xmean, xcov, flights, xland, dx0)
+        self.jmean, self.jcov = jmean, jcov
+        self.navraw = np.asarray(navraw, np.float64).reshape(-1, _lib.NAV_NREP)
+        self.navfed, self.navK = navfed, navK
+        for name, i in _lib.MCNAV_INDEX.items():
+            setattr(self, name, self.navraw[:, i])
+
+
+_MCNAV_DENSE = ("flights", "xland", "dx0", "navfed", "navK")
+
+
+def _mc_nav_dense(dense):
+    """dense: False / () / True (all five) / an iterable of names out of _MCNAV_DENSE -> the set of wanted outputs"""
+    if dense is True:
+        return set(_MCNAV_DENSE)
+    if not dense:
+        return set()
+    want = {dense} if isinstance(dense, str) else set(dense)
+    if not want <= set(_MCNAV_DENSE):
+        raise ValueError("dense: True, False or names out of %s, not %r" % (", ".join(repr(n) for n in _MCNAV_DENSE), dense))
+    return want
+
+
+def _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws):
+    """(C0, CN [B][14][14], xi0, eta or None, xin, nud or None, w [14] or None) of a sampled dispersion flown on an estimate: the factors
+    of every plan's two handover covariances (montecarlo.handover_factor), the draws of montecarlo.mc_draws and mc_nav_draws -- or
+    `draws` = (xi0, eta, xin, nud) -- and the process-noise VARIANCE, which the library roots"""
+    from .montecarlo import handover_factor, mc_draws, mc_nav_draws
+    s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
+    wv = _cov_noise(w)
+    c0 = np.ascontiguousarray(np.stack([handover_factor(s0[b]) for b in range(B)]))
+    cn = np.ascontiguousarray(np.stack([handover_factor(n0[b]) for b in range(B)]))
+    if draws is None:
+        if int(samples) < 1:
+            raise ValueError("samples must be >= 1")
+        xi0, eta = mc_draws(int(samples), K, seed, noise=wv is not None)
+        xin, nud = mc_nav_draws(int(samples), K, m, seed)
+    else:
+        if len(draws) != 4:
+            raise ValueError("draws = (xi0 [S][14], eta [S][K][14] or None, xin [S][14], nud [S][K][m] or None)")
+        xi0, xin = (np.ascontiguousarray(draws[i], np.float64) for i in (0, 2))
+        eta, nud = (None if draws[i] is None else np.ascontiguousarray(draws[i], np.float64) for i in (1, 3))
+        S = xi0.shape[0] if xi0.ndim == 2 else 0
+        if (S < 1 or xi0.shape != (S, 14) or xin.shape != (S, 14) or (eta is not None and eta.shape != (S, K, 14))
+                or (m > 0 and (nud is None or nud.shape != (S, K, m)))):
+            raise ValueError("shape mismatch: draws = (xi0 [S][14], eta [S][K][14] or None, xin [S][14], nud [S][K][m] or None)")
+    return c0, cn, n0, xi0, eta, xin, (nud if m else None), wv
+
+
+def _mc_nav_outputs(B, S, K, dense):
+    want = _mc_nav_dense(dense)
+    shapes = {"flights": (B, S, _lib.FLIGHT_NREP), "xland": (B, S, 14), "dx0": (B, S, 14), "navfed": (B, S, K, 14), "navK": (B, S, 14)}
+    return ((np.empty((B, _lib.MC_NREP)), np.empty((B, 14)), np.empty((B, 14, 14)), np.empty((B, 28)), np.empty((B, 28, 28)),
+             np.empty((B, _lib.NAV_NREP))), tuple(np.empty(shapes[n]) if n in want else None for n in _MCNAV_DENSE))
+
+
+def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0, H, rm, samples, seed=0, w=None, kf=None, nsub=10,
+                       clamp=False, tol=0.0, dense=(), draws=None) -> McNavReport:
+    """track_mc_batch with the law fed a navigation ESTIMATE whose error is generated per flight on the device (scvx_track_mc_nav_f64_host;
+    the model and its limits are in include/scvx.h): the sampled, nonlinear counterpart of nav_cov_batch, whose arguments deriv, N0, H,
+    rm and w mean here what they mean there.  The error starts at handover_factor(N0[b]) @ xin[s], is corrected at every node but the
+    last by the filter gains kf [B][K][14][m] with the measurement noise sqrt(rm) * nud, and receives the impulse sqrt(w) * eta that
+    the truth receives.  kf None: the gains of nav_cov_batch for the same model.  The draws are montecarlo.mc_draws and
+    montecarlo.mc_nav_draws of `seed`, or draws = (xi0, eta, xin, nud).  dense: True, or names out of "flights", "xland", "dx0",
+    "navfed", "navK"."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    gain = np.ascontiguousarray(gain, np.float64)
+    deriv = np.ascontiguousarray(deriv, np.float64)
+    nu = cache.nu
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu) or sigma.shape != (x.shape[0],):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % nu)
+    B, K1, _ = x.shape
+    K = K1 - 1
+    if gain.shape != (B, K, nu, 14 + nu):
+        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, 14 + nu))
+    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
+        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
+    m, Hm, rv = _nav_model(H, rm)
+    c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws)
+    if m and kf is None:
+        kf = nav_cov_batch(cache, x, u, deriv, gain, np.zeros((B, 14, 14)), n0, Hm, rv, wv, dense=("kf",)).kf
+    if m:
+        kf = np.ascontiguousarray(kf, np.float64)
+        if kf.shape != (B, K, 14, m):
+            raise ValueError("shape mismatch: kf [B][K][14][%d]" % m)
+    S = xi0.shape[0]
+    red, dn = _mc_nav_outputs(B, S, K, dense)
+    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    _lib.check(cache.handle, cache._L.scvx_track_mc_nav_f64_host(
+        cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(wv), _p(deriv), opt(kf if m else None),
+        _p(cn), _p(xin), opt(nud), m, opt(Hm), opt(rv), int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0,
+        float(tol), *[_p(a) for a in red], *[opt(a) for a in dn]), "scvx_track_mc_nav_f64_host")
+    return McNavReport(*red, *dn)
 
 
 def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None):

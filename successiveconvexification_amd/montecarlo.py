@@ -104,6 +104,23 @@ def mc_draws(samples, K, seed, noise=False, lo=0):
     return xi0, eta
 
 
+def mc_nav_draws(samples, K, m, seed, lo=0):
+    """The draws of the navigation error of a sampled dispersion flown on an estimate (dynamics.track_mc_nav_batch, ScvxBatch.track_mc
+    with `nav`): (xin [samples][14] for eps_0, nud [samples][K][m] for the measurement noise, or None with m = 0), standard normal.
+    Sample s draws from Philox stream s of `seed` with a counter word of its own, 5 in the SECOND word next to mc_draws' 4, so the draws
+    share nothing with those of mc_draws (the same flight's start and process noise), nav_error_samples or the dispersion laws above.
+    The 14 start draws come first, so xin does not depend on m, and a shard [lo, lo + samples) gets exactly the rows the whole set
+    would."""
+    xin = np.empty((samples, 14))
+    nud = np.empty((samples, K, m)) if m else None
+    for s in range(samples):
+        rng = np.random.Generator(np.random.Philox(key=seed, counter=[0, 5, 0, lo + s]))
+        xin[s] = rng.standard_normal(14)
+        if m:
+            nud[s] = rng.standard_normal(K * m).reshape(K, m)
+    return xin, nud
+
+
 _STATE_BLOCKS = {"r": (1, 4), "v": (4, 7), "q": (7, 11), "w": (11, 14)}
 
 
