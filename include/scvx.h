@@ -10,6 +10,7 @@
  *   (no counterpart: LQR gains + closed-loop flight)   ->  scvx_track_gains_f64[_host], scvx_track_fly_f64[_host], scvx_batch_track_*
  *   (no counterpart: closed-loop covariance analysis)  ->  scvx_cov_propagate_f64[_host], scvx_batch_cov
  *   (no counterpart: sampled closed-loop dispersion)   ->  scvx_track_mc_f64[_host], scvx_batch_track_mc
+ *   (no counterpart: its quantiles, per-node samples)   ->  scvx_order_stats_f64[_host], scvx_track_mc[_nav]_q_f64[_host], scvx_batch_track_mc[_nav]_q
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -54,6 +55,7 @@
 #ifndef SCVX_H
 #define SCVX_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -466,7 +468,8 @@ int scvx_track_fly_nav_f64_host(scvx_ctx *ctx, int B, int K, const double *x, co
  * offsets the device formed.  A non-finite gain, plan or C0 entry poisons the rows of its own plan only (N_BAD = S, NaN statistics).
  * Limits: the law is fed the TRUTH -- the sampled loop flown on a navigation estimate is scvx_track_mc_nav_f64 below, and `reserved`
  * (must be NULL) keeps its place in the argument list; the draws are shared across plans, so the rows of one call are not independent experiments;
- * quantiles are not reduced on the device -- take them from `flights`; w is the per-segment lump of the analyses, here as an impulse.
+ * order statistics of the flight columns and of the per-node path functions are reduced on the device by scvx_track_mc_q_f64 below
+ * (this call returns none); w is the per-segment lump of the analyses, here as an impulse.
  * x, u, sigma, gain, flags (SCVX_TRACK_CLAMP), nsub as scvx_track_fly_f64; tol >= 0.  The _f64 form takes device pointers (sw14 on
  * the host) and is asynchronous on the context's stream; its partial sums live in a workspace that belongs to the context, so two
  * calls on one context must not overlap on different streams.  SCVX_ERR_ARG for S < 1, B < 1 (or B > 65535), K != the problem's K,
@@ -530,6 +533,75 @@ int scvx_track_mc_nav_f64_host(scvx_ctx *ctx, int B, int K, int S, const double 
                                const double *H, const double *rm, int nsub, int flags, double tol, double *mcrep, double *xmean,
                                double *xcov, double *jmean, double *jcov, double *mcnav, double *flights, double *xland, double *dx0,
                                double *navfed, double *navK);
+
+/* ---- exact batched order statistics ------------------------------------------------------------------------------------------------
+ * Row r is the S values v[r * ld + s * inc], s = 0..S-1; out[r][i] is its element of rank ranks[i] in ASCENDING order, ranks 0-based,
+ * 0 <= rank < S (rank 0 the minimum, rank S - 1 the maximum), a HOST array of nq entries that need be neither sorted nor distinct,
+ * 1 <= nq <= SCVX_Q_MAX.  The order is -inf < .. < -0 = +0 < .. < +inf < every NaN (NaNs last, as numpy.sort puts them).  The result
+ * is a SELECTION, never an interpolation: the output is one of the inputs bit for bit; a NaN is returned as some NaN, and either zero
+ * may be returned for +-0.  A probability p maps to the rank min(S - 1, max(0, ceil(p S) - 1)) -- numpy's method="inverted_cdf", p = 0
+ * the minimum and p = 1 the maximum (montecarlo.quantile_ranks on the Python side).  Deterministic: integer histograms only, no
+ * floating-point atomics; two launches give bitwise equal output.  One workgroup per row, a most-significant-digit radix select over
+ * monotone 64-bit keys (csrc/scvx_quantile.hip); every S >= 1 is served.  The _f64 form takes device pointers (ranks on the host) and
+ * is asynchronous on the context's stream.  SCVX_ERR_ARG for R < 1, S < 1, nq outside [1, SCVX_Q_MAX], a rank outside [0, S), inc < 1,
+ * R > 1 with ld < (S - 1) inc + 1, a null v, ranks or out. */
+#define SCVX_Q_MAX 16
+int scvx_order_stats_f64(scvx_ctx *ctx, int R, int S, const double *v_dev, size_t ld, size_t inc, int nq, const int *ranks,
+                         double *out_dev);
+int scvx_order_stats_f64_host(scvx_ctx *ctx, int R, int S, const double *v, size_t ld, size_t inc, int nq, const int *ranks,
+                              double *out);
+
+/* ---- sampled closed-loop dispersion with order statistics and per-node samples ---------------------------------------------------
+ * scvx_track_mc_f64 and scvx_track_mc_nav_f64 reduce every column over the whole flight to MAX, MEAN and shares above one tol.  The
+ * _q forms take the argument list of the call they extend, verbatim, followed by
+ *     int nq, const int *ranks (host), double *flightq [B][16][nq], double *pathq [B][K+1][5][nq], double *pathv [B][K+1][5][S]
+ * Any of the three outputs may be NULL; all NULL with nq = 0 IS the call they extend (the old entry points are this path with nothing
+ * requested, and launch the kernels they always launched).  Ranks as scvx_order_stats_f64 (0-based, ascending, a selection).
+ * flightq: the order statistics over the S flights of each of the sixteen SCVX_FLIGHT_* columns of plan b.  A column that is -inf for
+ * the model stays -inf; a poisoned plan gives NaN.
+ * pathv: the five path functions of psig (SCVX_PSIG_*) sampled at EVERY node k = 0..K of every flight,
+ *     pathv[((b (K + 1) + k) 5 + f) S + s]                      (the sample is the fastest index)
+ * MASS = x[0], GLIDE = tan(gammaGs) |r[2:3]| - r[1], TILT = |q[3:4]|, RATE = |w|: the audit's own expressions, WITHOUT the constants the
+ * audit subtracts for tilt (sqcm) and rate (omMax), taken of the flown state as node k's feedback sees it -- node 0 is xbar_0 + dx0,
+ * node k >= 1 is after the impulse of segment k - 1.  In the navigation form this is the TRUTH, not the estimate: the constraints bind
+ * the vehicle (psig is read off the truth block for the same reason).  THRUST = the norm |u[1:3]| of the control COMMANDED for node k,
+ * BEFORE the clamp -- the quantity OUT_LO / OUT_HI test; at node 0 it is |ubar_0|; in the navigation form it is the command formed from
+ * the estimate.  With SCVX_TRACK_CLAMP it is still the unclamped command.
+ * pathq: the order statistics of each (b, k, f) row of pathv.
+ * Limits.  A tail quantile from S flights is itself uncertain: under a normal model the standard error of the p-quantile estimate is
+ * sqrt(p (1 - p) / S) / phi(z_p) standard deviations (0.26 sigma at p = 0.99865, S = 1,024 -- and at S (1 - p) < 1 the rank is the
+ * maximum of the sample, whatever p says).  The draws are shared across plans.  A back-off formed from the glide quantile buys
+ * tan(gammaGs) times what is written, as the covariance back-offs do.
+ * Workspace.  When the caller passes no dense flights / pathv but asks for their quantiles, the values live in a workspace that belongs
+ * to the context, grown on demand, beside the workspace of partial rows and under its rule: calls on one context must not overlap on
+ * different streams.  Its size is B S 16 doubles for flightq and B (K + 1) 5 S doubles for pathq: 267 MB at B = 128, S = 1,024, K = 50.
+ * The device-pointer forms are asynchronous on the context's stream (ranks on the host).  SCVX_ERR_ARG for everything the call extended
+ * refuses, and, unless nq = 0 with flightq = pathq = NULL, for nq outside [1, SCVX_Q_MAX], null ranks, a rank outside [0, S). */
+int scvx_track_mc_q_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                        const double *gain_dev, const double *C0_dev, const double *xi0_dev, const double *eta_dev,
+                        const double *sw14, const void *reserved, int nsub, int flags, double tol, double *mcrep_dev,
+                        double *xmean_dev, double *xcov_dev, double *flights_dev, double *xland_dev, double *dx0_dev, int nq,
+                        const int *ranks, double *flightq_dev, double *pathq_dev, double *pathv_dev);
+int scvx_track_mc_q_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                             const double *gain, const double *C0, const double *xi0, const double *eta, const double *sw14,
+                             const void *reserved, int nsub, int flags, double tol, double *mcrep, double *xmean, double *xcov,
+                             double *flights, double *xland, double *dx0, int nq, const int *ranks, double *flightq, double *pathq,
+                             double *pathv);
+int scvx_track_mc_nav_q_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                            const double *gain_dev, const double *C0_dev, const double *xi0_dev, const double *eta_dev,
+                            const double *w14, const double *deriv_dev, const double *kf_dev, const double *CN_dev,
+                            const double *xin_dev, const double *nud_dev, int m, const double *H, const double *rm, int nsub,
+                            int flags, double tol, double *mcrep_dev, double *xmean_dev, double *xcov_dev, double *jmean_dev,
+                            double *jcov_dev, double *mcnav_dev, double *flights_dev, double *xland_dev, double *dx0_dev,
+                            double *navfed_dev, double *navK_dev, int nq, const int *ranks, double *flightq_dev, double *pathq_dev,
+                            double *pathv_dev);
+int scvx_track_mc_nav_q_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                                 const double *gain, const double *C0, const double *xi0, const double *eta, const double *w14,
+                                 const double *deriv, const double *kf, const double *CN, const double *xin, const double *nud,
+                                 int m, const double *H, const double *rm, int nsub, int flags, double tol, double *mcrep,
+                                 double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav, double *flights,
+                                 double *xland, double *dx0, double *navfed, double *navK, int nq, const int *ranks,
+                                 double *flightq, double *pathq, double *pathv);
 
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
@@ -691,6 +763,21 @@ int scvx_batch_track_mc_nav(scvx_batch *b, const double *q14, const double *rNU,
                             const double *xin, const double *nud, int m, const double *H, const double *rm, int nsub, int flags,
                             double tol, double *mcrep, double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav,
                             double *flights, double *xland, double *dx0, double *navfed, double *navK);
+
+/* The two calls above with the order statistics and the per-node samples of scvx_track_mc_q_f64 / scvx_track_mc_nav_q_f64: their
+ * argument lists, verbatim, followed by nq, ranks, flightq [B][16][nq], pathq [B][K+1][5][nq] and pathv [B][K+1][5][S], all host
+ * arrays, each output NULL or wanted; nq = 0 with all three NULL is the call above.  Synchronises.  SCVX_ERR_ARG as the call extended,
+ * and as scvx_track_mc_q_f64 for nq and ranks. */
+int scvx_batch_track_mc_q(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                          const double *xi0, const double *eta, const double *sw14, const void *reserved, int nsub, int flags,
+                          double tol, double *mcrep, double *xmean, double *xcov, double *flights, double *xland, double *dx0,
+                          int nq, const int *ranks, double *flightq, double *pathq, double *pathv);
+int scvx_batch_track_mc_nav_q(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                              const double *xi0, const double *eta, const double *w14, const double *N0, const double *CN,
+                              const double *xin, const double *nud, int m, const double *H, const double *rm, int nsub, int flags,
+                              double tol, double *mcrep, double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav,
+                              double *flights, double *xland, double *dx0, double *navfed, double *navK, int nq, const int *ranks,
+                              double *flightq, double *pathq, double *pathv);
 
 /* ---- thrust-band back-offs and covariance-driven replanning (no counterpart in the reference) ---------------------------------
  * Per-trajectory, per-node back-offs of the thrust band, read by the conic solve alone:

@@ -661,6 +661,140 @@ track_mc_nav_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_d
         nud_dev, m, _cov_opt(H), _cov_opt(rm), nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev,
         flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev), "scvx_track_mc_nav_f64")
 
+# ---- order statistics, and the sampled dispersions with them and the per-node samples (new) ----------------------------------
+# include/scvx.h, "exact batched order statistics": v is S x R (one row of the library per COLUMN here), ranks are the library's 0-based
+# ascending ranks (quantile_ranks maps probabilities to them: numpy's "inverted_cdf"); the result is nq x R, a selection of the inputs.
+const Q_MAX = 16
+quantile_ranks(p, S::Int) = Cint[min(S - 1, max(0, ceil(Int, x * S) - 1)) for x in p]
+
+function order_stats(cache::Cache, v::Matrix{Float64}, ranks::Vector{Cint})
+    S, R = size(v)
+    out = Matrix{Float64}(undef, length(ranks), R)
+    check(cache.ctx, ccall((:scvx_order_stats_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Csize_t, Csize_t, Cint, Ptr{Cint}, Ptr{Cdouble}),
+        cache.ctx, R, S, v, S, 1, length(ranks), ranks, out), "scvx_order_stats_f64_host")
+    return out
+end
+
+# on device pointers, asynchronous on the context's stream: row r is the S values v_dev[r * ld + s * inc]; ranks stay a host array
+order_stats_dev!(cache::Cache, R::Int, S::Int, v_dev::Ptr{Cdouble}, ld::Int, inc::Int, ranks::Vector{Cint}, out_dev::Ptr{Cdouble}) =
+    GC.@preserve ranks check(cache.ctx, ccall((:scvx_order_stats_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Csize_t, Csize_t, Cint, Ptr{Cint}, Ptr{Cdouble}),
+        cache.ctx, R, S, v_dev, ld, inc, length(ranks), ranks, out_dev), "scvx_order_stats_f64")
+
+# include/scvx.h, "sampled closed-loop dispersion with order statistics and per-node samples": track_mc / track_mc_nav followed by the
+# ranks.  Besides their returns: flightq nq x 16 x B, and with per_node pathq nq x 5 x (K+1) x B (row PSIG_* + 1 holds that function),
+# with pathv the samples themselves S x 5 x (K+1) x B.
+function _mc_q_outputs(B::Int, S::Int, K::Int, nq::Int, per_node::Bool, pathv::Bool)
+    return (Array{Float64,3}(undef, nq, FLIGHT_NREP, B), per_node ? Array{Float64,4}(undef, nq, 5, K + 1, B) : nothing,
+            pathv ? Array{Float64,4}(undef, S, 5, K + 1, B) : nothing)
+end
+
+function track_mc_q(b::Batch, C0::Array{Float64,3}, xi0::Matrix{Float64}, ranks::Vector{Cint}; eta::Union{Nothing,Array{Float64,3}}=nothing,
+                    w=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false, tol::Float64=0.0, dense::Bool=false,
+                    per_node::Bool=false, pathv::Bool=false)
+    NU = control_dim(b.cache)
+    S = size(xi0, 2); K = b.cache.problem.K
+    size(C0) == (14, 14, b.B) && size(xi0, 1) == 14 || throw(ArgumentError("C0 must be 14 x 14 x B, xi0 14 x S"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    flightq, pathq, pv = _mc_q_outputs(b.B, S, K, length(ranks), per_node, pathv)
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    GC.@preserve sw ranks check(b.cache.ctx, ccall((:scvx_batch_track_mc_q, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, xi0, _cov_opt(eta), _cov_opt(sw), C_NULL, nsub,
+        clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), length(ranks), ranks,
+        flightq, _cov_opt(pathq), _cov_opt(pv)), "scvx_batch_track_mc_q")
+    return mcrep, xmean, xcov, flights, xland, dx0, flightq, pathq, pv
+end
+
+function track_mc_q(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, gain::Array{Float64,4},
+                    C0::Array{Float64,3}, xi0::Matrix{Float64}, ranks::Vector{Cint}; eta::Union{Nothing,Array{Float64,3}}=nothing,
+                    w=nothing, nsub::Int=10, clamp::Bool=false, tol::Float64=0.0, dense::Bool=false, per_node::Bool=false,
+                    pathv::Bool=false)
+    B, K, S = size(x, 3), size(x, 2) - 1, size(xi0, 2)
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    flightq, pathq, pv = _mc_q_outputs(B, S, K, length(ranks), per_node, pathv)
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    GC.@preserve sw ranks check(cache.ctx, ccall((:scvx_track_mc_q_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, xi0, _cov_opt(eta), _cov_opt(sw), C_NULL, nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep,
+        xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), length(ranks), ranks, flightq, _cov_opt(pathq), _cov_opt(pv)),
+        "scvx_track_mc_q_f64_host")
+    return mcrep, xmean, xcov, flights, xland, dx0, flightq, pathq, pv
+end
+
+# on device pointers, asynchronous on the context's stream; sw = sqrt(w) and ranks stay host arrays; C_NULL for an output not wanted
+track_mc_q_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble}, sw::Union{Nothing,Vector{Float64}},
+                nsub::Int, flags::Int, tol::Float64, mcrep_dev::Ptr{Cdouble}, xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble},
+                flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble}, ranks::Vector{Cint}, flightq_dev::Ptr{Cdouble},
+                pathq_dev::Ptr{Cdouble}, pathv_dev::Ptr{Cdouble}) =
+    GC.@preserve sw ranks check(cache.ctx, ccall((:scvx_track_mc_q_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(sw), C_NULL, nsub, flags, tol, mcrep_dev,
+        xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, length(ranks), ranks, flightq_dev, pathq_dev, pathv_dev), "scvx_track_mc_q_f64")
+
+function track_mc_nav_q(b::Batch, C0::Array{Float64,3}, xi0::Matrix{Float64}, N0::Array{Float64,3}, CN::Array{Float64,3},
+                        xin::Matrix{Float64}, H, rm, ranks::Vector{Cint}; nud::Union{Nothing,Array{Float64,3}}=nothing,
+                        eta::Union{Nothing,Array{Float64,3}}=nothing, w=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false,
+                        tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false)
+    NU = control_dim(b.cache)
+    S = size(xi0, 2); K = b.cache.problem.K
+    (size(C0) == (14, 14, b.B) && size(N0) == (14, 14, b.B) && size(CN) == (14, 14, b.B) && size(xi0, 1) == 14 && size(xin) == (14, S)) ||
+        throw(ArgumentError("C0, N0, CN must be 14 x 14 x B, xi0 and xin 14 x S"))
+    m, Hm, rmv = _nav_model(H, rm)
+    (m == 0 || (nud !== nothing && size(nud) == (m, K, S))) || throw(ArgumentError("nud must be m x K x S"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(b.B, S, K, dense)
+    flightq, pathq, pv = _mc_q_outputs(b.B, S, K, length(ranks), per_node, pathv)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv ranks check(b.cache.ctx, ccall((:scvx_batch_track_mc_nav_q, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, xi0, _cov_opt(eta), _cov_opt(wv), N0, CN, xin,
+        _cov_opt(m > 0 ? nud : nothing), m, _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean,
+        jcov, mcnav, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK), length(ranks), ranks, flightq,
+        _cov_opt(pathq), _cov_opt(pv)), "scvx_batch_track_mc_nav_q")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, flightq, pathq, pv
+end
+
+function track_mc_nav_q(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, deriv::Array{Float64,4},
+                        gain::Array{Float64,4}, C0::Array{Float64,3}, xi0::Matrix{Float64}, CN::Array{Float64,3}, xin::Matrix{Float64}, H,
+                        rm, ranks::Vector{Cint}; kf::Union{Nothing,Array{Float64,4}}=nothing,
+                        nud::Union{Nothing,Array{Float64,3}}=nothing, eta::Union{Nothing,Array{Float64,3}}=nothing, w=nothing,
+                        nsub::Int=10, clamp::Bool=false, tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false)
+    B, K, S = size(x, 3), size(x, 2) - 1, size(xi0, 2)
+    m, Hm, rmv = _nav_model(H, rm)
+    (m == 0 || (kf !== nothing && size(kf) == (m, 14, K, B) && nud !== nothing && size(nud) == (m, K, S))) ||
+        throw(ArgumentError("with measurements: kf m x 14 x K x B (navigation(...; dense=true)) and nud m x K x S"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(B, S, K, dense)
+    flightq, pathq, pv = _mc_q_outputs(B, S, K, length(ranks), per_node, pathv)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv ranks check(cache.ctx, ccall((:scvx_track_mc_nav_q_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, xi0, _cov_opt(eta), _cov_opt(wv), deriv, _cov_opt(m > 0 ? kf : nothing), CN, xin,
+        _cov_opt(m > 0 ? nud : nothing), m, _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean, jcov,
+        mcnav, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK), length(ranks), ranks, flightq,
+        _cov_opt(pathq), _cov_opt(pv)), "scvx_track_mc_nav_q_f64_host")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, flightq, pathq, pv
+end
+
+track_mc_nav_q_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                    gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble},
+                    w::Union{Nothing,Vector{Float64}}, deriv_dev::Ptr{Cdouble}, kf_dev::Ptr{Cdouble}, CN_dev::Ptr{Cdouble},
+                    xin_dev::Ptr{Cdouble}, nud_dev::Ptr{Cdouble}, m::Int, H::Union{Nothing,Matrix{Float64}},
+                    rm::Union{Nothing,Vector{Float64}}, nsub::Int, flags::Int, tol::Float64, mcrep_dev::Ptr{Cdouble},
+                    xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble}, jmean_dev::Ptr{Cdouble}, jcov_dev::Ptr{Cdouble},
+                    mcnav_dev::Ptr{Cdouble}, flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble},
+                    navfed_dev::Ptr{Cdouble}, navK_dev::Ptr{Cdouble}, ranks::Vector{Cint}, flightq_dev::Ptr{Cdouble},
+                    pathq_dev::Ptr{Cdouble}, pathv_dev::Ptr{Cdouble}) =
+    GC.@preserve w H rm ranks check(cache.ctx, ccall((:scvx_track_mc_nav_q_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(w), deriv_dev, kf_dev, CN_dev, xin_dev,
+        nud_dev, m, _cov_opt(H), _cov_opt(rm), nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev,
+        flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, length(ranks), ranks, flightq_dev, pathq_dev, pathv_dev),
+        "scvx_track_mc_nav_q_f64")
+
 # ---- thrust-band back-offs and covariance-driven replanning (new) ----------------------------------------------------------
 # include/scvx.h, "thrust-band back-offs".  Tmin + lo[k, b] <= |u_k| <= Tmax - hi[k, b], read by the conic solve alone; the flight
 # check and the tracking calls keep auditing against the true Tmin / Tmax.  psig is 5 x (K+1) x B (row PSIG_* + 1 holds that column).

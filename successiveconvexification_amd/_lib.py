@@ -128,6 +128,25 @@ SIGNATURES = {
     "scvx_track_mc_nav_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              _dp, _dp, _dp]),
+    # exact batched order statistics, and the sampled calls with them and the per-node samples: the old lists, then nq, ranks (host),
+    # flightq, pathq, pathv
+    "scvx_order_stats_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, C.c_int, _ip, _vp]),
+    "scvx_order_stats_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_size_t, C.c_size_t, C.c_int, _ip, _dp]),
+    "scvx_track_mc_q_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp, C.c_int, C.c_int,
+                                      C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _ip, _vp, _vp, _vp]),
+    "scvx_track_mc_q_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int,
+                                           C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "scvx_track_mc_nav_q_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp,
+                                          C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, C.c_int, _ip, _vp, _vp, _vp]),
+    "scvx_track_mc_nav_q_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                               _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                               _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "scvx_batch_track_mc_q": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp,
+                                        _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "scvx_batch_track_mc_nav_q": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                            C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int,
+                                            _ip, _dp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),

@@ -253,14 +253,18 @@ class ScvxBatch:
         return FlightReport(rep, xfly, "track", ufly)
 
     def track_mc(self, S0, samples=256, seed=0, w=None, q=None, r=None, qf=None, nsub=None, clamp=False, tol=0.0, dense=(), draws=None,
-                 nav=None):
+                 nav=None, quantiles=None, per_node=False):
         """Sampled closed-loop dispersion of the batch's current accepted iterate under its LQR gains: `samples` flights per plan on
         the device, one dynamics.McReport row per plan (scvx_batch_track_mc; S0 -- a [14] vector of standard deviations, one [14][14]
         or [B][14][14] --, seed, w, clamp, tol, dense and draws as dynamics.track_mc_batch, weights as track_gains).  The batch is left
         untouched.  nav = (N0, H, rm), the model of navigation(): the flights are flown on a navigation estimate whose error is
         generated per flight on the device from the filter gains of that analysis (scvx_batch_track_mc_nav; dense and draws as
-        dynamics.track_mc_nav_batch): a dynamics.McNavReport."""
-        from .dynamics import McReport, _mc_inputs, _mc_outputs, _track_weights
+        dynamics.track_mc_nav_batch): a dynamics.McNavReport.  quantiles (probabilities), per_node and the dense name "pathv" as
+        dynamics.track_mc_batch: order statistics of the flight columns and of the per-node path functions, reduced on the device
+        (scvx_batch_track_mc_q / scvx_batch_track_mc_nav_q); at their defaults the call is the one it was."""
+        from .dynamics import McReport, _McQ, _mc_inputs, _mc_outputs, _track_weights
+        mq = _McQ(quantiles, per_node, dense)
+        dense = mq.rest
         qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
         if nav is not None:
             from .dynamics import McNavReport, _mc_nav_inputs, _mc_nav_outputs, _nav_arg
@@ -269,19 +273,25 @@ class ScvxBatch:
             S = xi0.shape[0]
             red, dn = _mc_nav_outputs(self.B, S, self.K, dense)
             opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-            self._chk(self._L.scvx_batch_track_mc_nav(
-                self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), _p(xi0), opt(eta), opt(wv), _p(n0), _p(cn), _p(xin), opt(nud), m, opt(Hm),
-                opt(rmv), int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red], *[opt(a) for a in dn]),
-                "scvx_batch_track_mc_nav")
-            return McNavReport(*red, *dn)
+            args = (self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), _p(xi0), opt(eta), opt(wv), _p(n0), _p(cn), _p(xin), opt(nud), m,
+                    opt(Hm), opt(rmv), int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red],
+                    *[opt(a) for a in dn])
+            if mq.on:
+                self._chk(self._L.scvx_batch_track_mc_nav_q(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_nav_q")
+            else:
+                self._chk(self._L.scvx_batch_track_mc_nav(*args), "scvx_batch_track_mc_nav")
+            return McNavReport(*red, *dn)._with_q(mq)
         c0, xi0, eta, sw = _mc_inputs(S0, self.B, self.K, samples, seed, w, draws)
         S = xi0.shape[0]
         rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(self.B, S, dense)
         opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-        self._chk(self._L.scvx_batch_track_mc(self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), _p(xi0), opt(eta), opt(sw), None,
-                                              int(nsub or 0), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean),
-                                              _p(xcov), opt(flights), opt(xland), opt(dx0)), "scvx_batch_track_mc")
-        return McReport(rep, xmean, xcov, flights, xland, dx0)
+        args = (self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), _p(xi0), opt(eta), opt(sw), None, int(nsub or 0),
+                _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov), opt(flights), opt(xland), opt(dx0))
+        if mq.on:
+            self._chk(self._L.scvx_batch_track_mc_q(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_q")
+        else:
+            self._chk(self._L.scvx_batch_track_mc(*args), "scvx_batch_track_mc")
+        return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)
 
     def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False):
         """Closed-loop covariance analysis of the batch's current accepted iterate under its LQR gains (scvx_batch_cov; S0, w and
@@ -400,6 +410,30 @@ class ScvxBatch:
         that are not selected stay as they are.  Returns psig [B][K+1][5], read off the truth block of the joint covariance."""
         return self._margins_from_nav(S0, (N0, H, rm), w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
 
+    def margins_from_mc(self, S0, p=0.99865, samples=1024, constraints="all", cap=0.25, seed=0, w=None, clamp=False, nav=None, q=None,
+                        r=None, qf=None, nsub=None, tol=0.0, draws=None):
+        """Back-offs from the SAMPLED closed loop of the current accepted iterate -- nonlinear and aware of the clamp, where
+        margins_from_cov / margins_from_nav are first order: one track_mc call (truth-fed, or flown on an estimate with nav = (N0, H,
+        rm)) with the ranks of 1 - p and p and the per-node order statistics, montecarlo.margins_from_quantiles on them (the formulas,
+        caps and forced zeros are there; the thrust pair is asymmetric), and set_thrust_margins / set_path_margins for the kinds in
+        `constraints` (the others stay as they are).  Returns (rep, lo, hi, pm): the report (rep.pathq [B][K+1][5][2]) and the back-offs
+        as set.  Limits: the glide back-off buys tan(gammaGs) times what is written; a tail quantile from `samples` flights carries the
+        standard error montecarlo.quantile_stderr(p, samples) (0.26 sigma at the defaults, and beyond samples (1 - p) < 1 the rank is the
+        sample's extreme); the draws are shared across plans; with clamp=True the thrust function is still the unclamped command."""
+        from .montecarlo import margins_from_quantiles
+        mask = self._margin_mask(constraints)
+        names = [n for n, bit in _lib.MARGIN_BITS.items() if mask & bit]
+        rep = self.track_mc(S0, samples=samples, seed=seed, w=w, q=q, r=r, qf=qf, nsub=nsub, clamp=clamp, tol=tol, draws=draws, nav=nav,
+                            quantiles=(1.0 - p, p), per_node=True)
+        x, u, _ = self.trajectory()
+        cur = self.thrust_margins() + (self.path_margins(),)
+        lo, hi, pm = margins_from_quantiles(self.cache.problem, x, u, rep.pathq[..., 0], rep.pathq[..., 1], names, cap, current=cur)
+        if mask & _lib.MARGIN_BITS["thrust"]:
+            self.set_thrust_margins(lo, hi)
+        if mask & ~_lib.MARGIN_BITS["thrust"]:
+            self._chk(self._L.scvx_batch_set_path_margins(self.handle, _p(np.ascontiguousarray(pm))), "scvx_batch_set_path_margins")
+        return rep, lo, hi, pm
+
     def path_sigma(self, S0, w=None, q=None, r=None, qf=None, nav=None):
         """psig [B][K+1][5]: per node, one standard deviation of the mass, glide-slope, tilt, rate and thrust-norm path functions
         of the batch's current accepted iterate under its LQR gains (dynamics.cov_path_sigma_batch on the batch's own tiles).  The
@@ -419,7 +453,7 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_replan(self.handle), "scvx_batch_replan")
         return self
 
-    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",), nav=None):
+    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",), nav=None, mc=None):
         """Covariance-driven replanning.  Per round: the back-offs lo_k = hi_k = min(nsigma s_T(k), cap (Tmax - Tmin)) from the
         covariance analysis of the current iterate (scvx_batch_thrust_margins_from_cov, nothing returns to the host), replan(),
         solve().  Returns the last solve()'s (status, iters, nu_norm, dJ) plus (lo, hi).  First order, and only as good as Sigma_k;
@@ -431,12 +465,26 @@ class ScvxBatch:
         nav = (N0, H, rm): the s(k) come from the navigation analysis instead (scvx_batch_margins_from_nav per round), the closed loop
         flown on an estimate with the measurement H, rm at every node but the last; under navigation errors the covariance analysis'
         s(k) are too small, and a plan backed off by them keeps less than it shows.  Same limits, and the filter gain is the optimal
-        one for the stated model."""
+        one for the stated model.
+        mc = dict(p=..., samples=..., seed=..., clamp=...): the back-offs of each round come from the SAMPLED closed loop instead
+        (margins_from_mc: per-node order statistics Q_{1-p}, Q_p of `samples` flights, nonlinear and clamp-aware; nsigma is then not
+        used).  mc and nav combine: the flights are flown on the estimate.  Limits as margins_from_mc; mc=None is the call it was."""
         if int(rounds) < 1:
             raise ValueError("robustify: rounds >= 1")
         mask = self._margin_mask(constraints)
         thrust_only = mask == _lib.MARGIN_BITS["thrust"]
         out = None
+        if mc is not None:
+            if not isinstance(mc, dict) or not set(mc) <= {"p", "samples", "seed", "clamp"}:
+                raise ValueError("robustify: mc = dict(p=, samples=, seed=, clamp=)")
+            if nav is not None:
+                from .dynamics import _nav_arg
+                _nav_arg(nav, self.B)
+            for _ in range(int(rounds)):
+                self.margins_from_mc(S0, constraints=constraints, cap=cap, w=w, q=q, r=r, qf=qf, nav=nav, **mc)
+                self.replan()
+                out = self.solve()
+            return out + self.thrust_margins()
         if nav is not None:
             from .dynamics import _nav_arg
             _nav_arg(nav, self.B)   # a malformed model is refused before the first round

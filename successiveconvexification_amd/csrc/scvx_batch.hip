@@ -33,6 +33,7 @@
 
 #include <cstdio>
 #include "scvx_socp.hpp"
+#include "scvx_mc.hpp"   // McQ: what the _q forms of the sampled calls add
 
 using scvx::fail;
 
@@ -1030,6 +1031,14 @@ int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU
 int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
                         const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
                         double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0) {
+    return scvx_batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland,
+                                 dx0, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                          const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                          double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
+                          const int* ranks, double* flightq, double* pathq, double* pathv) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1039,12 +1048,18 @@ int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, con
     if ((rc = scvx::check_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->x, C0, xi0, eta, sw14, reserved, nsub, flags, tol, b->x,
                                    b->x, b->x)))
         return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const size_t nc = (size_t)b->B * 196, ni = (size_t)S * 14, ne = (size_t)S * b->K * 14, nr = (size_t)b->B * SCVX_MC_NREP,
-                 nm = (size_t)b->B * 14, nf = (size_t)b->B * S * SCVX_FLIGHT_NREP, nl = (size_t)b->B * S * 14;
-    scvx::DevBuf<double> dc, di, de, dr, dm, dv, df, dl, d0;
+                 nm = (size_t)b->B * 14, nf = (size_t)b->B * S * SCVX_FLIGHT_NREP, nl = (size_t)b->B * S * 14,
+                 nfq = (size_t)b->B * SCVX_FLIGHT_NREP * nq, npq = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N * nq,
+                 npv = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N * S;
+    scvx::DevBuf<double> dc, di, de, dr, dm, dv, df, dl, d0, dfq, dpq, dpv;
     hipStream_t st = ctx->stream;
     hipError_t e = hipMalloc((void**)&dc.p, nc * 8);
+    if (e == hipSuccess && flightq) e = hipMalloc((void**)&dfq.p, nfq * 8);
+    if (e == hipSuccess && pathq) e = hipMalloc((void**)&dpq.p, npq * 8);
+    if (e == hipSuccess && pathv) e = hipMalloc((void**)&dpv.p, npv * 8);
     if (e == hipSuccess) e = hipMalloc((void**)&di.p, ni * 8);
     if (e == hipSuccess && eta) e = hipMalloc((void**)&de.p, ne * 8);
     if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
@@ -1056,9 +1071,14 @@ int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, con
     if (e == hipSuccess) e = hipMemcpyAsync(dc.p, C0, nc * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && eta) e = hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st);
+    scvx::McQ mq;
+    mq.nq = nq, mq.ranks = ranks, mq.flightq = dfq.p, mq.pathq = dpq.p, mq.pathv = dpv.p;
     if (e == hipSuccess)
         e = scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p,
-                                  dm.p, dv.p, df.p, dl.p, d0.p, st);
+                                  dm.p, dv.p, df.p, dl.p, d0.p, st, (flightq || pathq || pathv) ? &mq : nullptr);
+    if (e == hipSuccess && flightq) e = hipMemcpyAsync(flightq, dfq.p, nfq * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && pathq) e = hipMemcpyAsync(pathq, dpq.p, npq * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && pathv) e = hipMemcpyAsync(pathv, dpv.p, npv * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && mcrep) e = hipMemcpyAsync(mcrep, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && xmean) e = hipMemcpyAsync(xmean, dm.p, nm * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && xcov) e = hipMemcpyAsync(xcov, dv.p, nc * 8, hipMemcpyDeviceToHost, st);
@@ -1067,7 +1087,7 @@ int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, con
     if (e == hipSuccess && dx0) e = hipMemcpyAsync(dx0, d0.p, nl * 8, hipMemcpyDeviceToHost, st);
     hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_q: ") + hipGetErrorString(e));
     return SCVX_OK;
 }
 
@@ -1076,6 +1096,16 @@ int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU,
                             const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags, double tol,
                             double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav, double* flights,
                             double* xland, double* dx0, double* navfed, double* navK) {
+    return scvx_batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean,
+                                     xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                              const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
+                              const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
+                              double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
+                              double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
+                              double* flightq, double* pathq, double* pathv) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1087,12 +1117,15 @@ int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU,
                                        nsub, flags, tol, b->x, b->x, b->x, b->x, b->x, b->x)))
         return rc;
     if (!N0) return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (N0)");
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const int B = b->B, K = b->K;
     const size_t nc = (size_t)B * 196, ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
                  nf = (size_t)B * S * SCVX_FLIGHT_NREP, nl = (size_t)B * S * 14, nk = (size_t)B * K * 14 * m, nn = (size_t)S * K * m,
                  nfed = (size_t)B * S * K * 14;
-    scvx::DevBuf<double> dc, di, de, dz, dn0, dcn, dxi, dnu, dk, dcr, dnr, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk;
+    const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
+                 npv = (size_t)B * (K + 1) * SCVX_PSIG_N * S;
+    scvx::DevBuf<double> dc, di, de, dz, dn0, dcn, dxi, dnu, dk, dcr, dnr, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, dfq, dpq, dpv;
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
     auto in = [&](scvx::DevBuf<double>& d, const double* h, size_t n) {
@@ -1110,6 +1143,12 @@ int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU,
     if (dx0) in(d0, nullptr, nl);
     if (navfed) in(dfe, nullptr, nfed);
     if (navK) in(dnk, nullptr, nl);
+    if (flightq) in(dfq, nullptr, nfq);
+    if (pathq) in(dpq, nullptr, npq);
+    if (pathv) in(dpv, nullptr, npv);
+    scvx::McQ mq;
+    mq.nq = nq, mq.ranks = ranks, mq.flightq = dfq.p, mq.pathq = dpq.p, mq.pathv = dpv.p;
+    const scvx::McQ* mqp = (flightq || pathq || pathv) ? &mq : nullptr;
     // the filter gains: the navigation launch with the same N0, H, rm and w; Kf does not depend on S0, which is zero here
     if (e == hipSuccess) e = hipMemsetAsync(dz.p, 0, nc * 8, st);
     if (e == hipSuccess && m > 0)
@@ -1120,19 +1159,19 @@ int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU,
     if (e == hipSuccess)
         e = b->deriv_f ? scvx::launch_track_mc_nav_f32(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv_f,
                                                        dk.p, dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p,
-                                                       dnv.p, df.p, dl.p, d0.p, dfe.p, dnk.p, st)
+                                                       dnv.p, df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp)
                        : scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv, dk.p,
                                                    dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p,
-                                                   df.p, dl.p, d0.p, dfe.p, dnk.p, st);
+                                                   df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp);
     auto out = [&](double* h, scvx::DevBuf<double>& d, size_t n) {
         if (e == hipSuccess && h) e = hipMemcpyAsync(h, d.p, n * 8, hipMemcpyDeviceToHost, st);
     };
     out(mcrep, dr, nr), out(xmean, dm, nm), out(xcov, dv, nc), out(jmean, djm, (size_t)B * 28), out(jcov, djc, (size_t)B * 784);
     out(mcnav, dnv, (size_t)B * SCVX_NAV_NREP), out(flights, df, nf), out(xland, dl, nl), out(dx0, d0, nl), out(navfed, dfe, nfed);
-    out(navK, dnk, nl);
+    out(navK, dnk, nl), out(flightq, dfq, nfq), out(pathq, dpq, npq), out(pathv, dpv, npv);
     hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_nav: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_nav_q: ") + hipGetErrorString(e));
     return SCVX_OK;
 }
 

@@ -33,6 +33,8 @@ struct scvx_ctx {
     scvx::TdCache* td = nullptr;
     double* mc_ws = nullptr;     // partial rows of scvx_track_mc_f64's reduction (scvx_mc.hip), grown on demand
     size_t mc_ws_doubles = 0;
+    double* mcq_ws = nullptr;    // dense flights / pathv of a _q call that asks for their order statistics only, grown on demand
+    size_t mcq_ws_doubles = 0;
     std::string err;
 };
 
@@ -101,12 +103,15 @@ int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const d
 int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
                     const void* report);
 
+struct McQ;   // what the _q forms add to a sampled call (scvx_mc.hpp); nullptr: nothing, the instantiations without per-node samples
+
 // Sampled dispersion (scvx_mc.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan; C0[B][14][14],
 // xi0[S][14], eta[S][K][14] or nullptr, sw: host array of 14 or nullptr; mcrep[B][SCVX_MC_NREP], xmean[B][14], xcov[B][14][14];
 // flights[B][S][16], xland[B][S][14], dx0[B][S][14] or nullptr.  The partial rows live in ctx->mc_ws.
 hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
-                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st);
+                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
+                           const McQ* q = nullptr);
 int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain, const void* C0,
                    const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
                    const void* mcrep, const void* xmean, const void* xcov);
@@ -119,13 +124,13 @@ hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, hipStream_t st);
+                               double* navfed, double* navK, hipStream_t st, const McQ* q = nullptr);
 hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
                                    const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
                                    const float* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
                                    const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                    double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                                   double* navfed, double* navK, hipStream_t st);
+                                   double* navfed, double* navK, hipStream_t st, const McQ* q = nullptr);
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
                        const void* C0, const void* xi0, const void* eta, const double* w, const void* deriv, const void* kf,
                        const void* CN, const void* xin, const void* nud, int m, const double* H, const double* rm, int nsub, int flags,

@@ -16,19 +16,27 @@
 // xor butterfly (32, 16, .., 1; lanes past S carry the neutral element) and lane 0 writes one partial row [MC_NP] per block into the
 // context's workspace; mc_finish_kernel (one block per plan) combines the ceil(S / 64) partial rows of its plan in block order.  A lane
 // past S flies sample S - 1 again, so that all 64 lanes reach the butterfly, and contributes nothing.
+//
+// PV (the last template parameter, as PS is for the covariance kernels): every live lane also stores the five path functions of psig at
+// every node into pathv [B][K+1][5][S] -- the sample is the fastest index, so a wavefront's 64 samples store one contiguous line per
+// value and each (b, k, f) row is contiguous for the order-statistics kernel (scvx_quantile.hip).  With PV off the instantiations keep
+// the parent's registers, LDS and scratch (profiles/mc_quantiles.md) and are what the entry points without the _q launch.  The _q forms
+// (scvx_track_mc_q_f64, include/scvx.h) follow the flight with order statistics of the flight columns and of the rows of pathv; flights
+// and pathv live in a second workspace of the context when only their order statistics are asked for.
 #include <cmath>
 #include <limits>
 #include "scvx_mc.hpp"   // the partial row, McK and the wavefront reductions, shared with scvx_mc_nav.hip
 
 namespace scvx {
 
-template <bool AERO, bool FIN, bool TRQ>
+template <bool AERO, bool FIN, bool TRQ, bool PV>
 __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK c, McK m, int S, int K, const double* __restrict__ x,
                                                     const double* __restrict__ u, const double* __restrict__ sigma,
                                                     const double* __restrict__ gain, const double* __restrict__ C0,
                                                     const double* __restrict__ xi0, const double* __restrict__ eta, double dt, int nsub,
                                                     int opt, double* __restrict__ part, double* __restrict__ flights,
-                                                    double* __restrict__ xland, double* __restrict__ dx0o) {
+                                                    double* __restrict__ xland, double* __restrict__ dx0o,
+                                                    double* __restrict__ pathv) {
     typedef double R;
     const int b = blockIdx.y;
     const int sl = blockIdx.x * 64 + threadIdx.x;
@@ -71,7 +79,12 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
     R g_mass = ninf, g_glide = ninf, g_tilt = ninf, g_rate = ninf, g_tmax = ninf, g_tmin = ninf, g_gimbal = ninf, g_dp = ninf,
       g_fin = ninf, qn = R(0.0);
     int n_lo = 0, n_hi = 0;         // commanded node controls k = 1..K outside the thrust band by more than tol, before the clamp
+    // PV: the five path functions at every node, pathv[((b (K + 1) + k) 5 + f) S + s] -- the sample is the fastest index, a wavefront
+    // stores one contiguous line per value
+    R* pvb = PV ? pathv + (size_t)b * (K + 1) * SCVX_PSIG_N * S + s_ : nullptr;
+    if (PV && live) pvb[(size_t)SCVX_PSIG_THRUST * S] = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
     for (int k = 0; k < K; k++) {
+        if (PV && live) mc_path_store(pvb + (size_t)k * SCVX_PSIG_N * S, S, c.tggs, xs);
         // ---- node k: the next node's control from the flown state and the applied control ----
         {
             R z[n];
@@ -94,6 +107,7 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
                 const R un = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
                 n_lo += (c.Tmin - un > m.tol) ? 1 : 0;
                 n_hi += (un - c.Tmax > m.tol) ? 1 : 0;
+                if (PV && live) pvb[((size_t)(k + 1) * SCVX_PSIG_N + SCVX_PSIG_THRUST) * S] = un;
             }
             if (clamp) {
                 const R un = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
@@ -173,6 +187,7 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
         }
     }
     // xs is the flown final node
+    if (PV && live) mc_path_store(pvb + (size_t)K * SCVX_PSIG_N * S, S, c.tggs, xs);
     R mr = R(0.0), mv = R(0.0), mq = R(0.0), mw = R(0.0);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -310,20 +325,66 @@ hipError_t mc_workspace(scvx_ctx* ctx, size_t doubles) {
     return e;
 }
 
+hipError_t mc_q_workspace(scvx_ctx* ctx, size_t doubles) {
+    if (ctx->mcq_ws_doubles >= doubles) return hipSuccess;
+    if (ctx->mcq_ws) (void)hipFree(ctx->mcq_ws);
+    ctx->mcq_ws = nullptr;
+    ctx->mcq_ws_doubles = 0;
+    hipError_t e = hipMalloc((void**)&ctx->mcq_ws, doubles * 8);
+    if (e == hipSuccess) ctx->mcq_ws_doubles = doubles;
+    return e;
+}
+
 void mc_workspace_free(scvx_ctx* ctx) {
     if (ctx->mc_ws) (void)hipFree(ctx->mc_ws);
     ctx->mc_ws = nullptr;
     ctx->mc_ws_doubles = 0;
+    if (ctx->mcq_ws) (void)hipFree(ctx->mcq_ws);
+    ctx->mcq_ws = nullptr;
+    ctx->mcq_ws_doubles = 0;
+}
+
+// flights: the caller's dense buffer or nullptr on entry; on return where the flying kernel writes the flights (the workspace when
+// only their order statistics are asked for), and pathv likewise (nullptr: the instantiations without per-node samples)
+hipError_t mc_q_buffers(scvx_ctx* ctx, int B, int K, int S, const McQ& q, double*& flights, double*& pathv) {
+    pathv = q.pathv;
+    const size_t nf = (q.flightq && !flights) ? (size_t)B * S * SCVX_FLIGHT_NREP : 0;
+    const size_t np = (q.pathq && !q.pathv) ? (size_t)B * (K + 1) * SCVX_PSIG_N * S : 0;
+    if (nf + np == 0) return hipSuccess;
+    hipError_t e = mc_q_workspace(ctx, nf + np);
+    if (e != hipSuccess) return e;
+    if (nf) flights = ctx->mcq_ws;
+    if (np) pathv = ctx->mcq_ws + nf;
+    return hipSuccess;
+}
+
+// the order statistics of the sixteen flight columns (rows of S values 16 apart) and of every (b, k, f) row of pathv (contiguous)
+hipError_t mc_q_finish(int B, int K, int S, const McQ& q, const double* flights, const double* pathv, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (q.flightq)
+        e = launch_order_stats(B * SCVX_FLIGHT_NREP, S, flights, (size_t)S * SCVX_FLIGHT_NREP, SCVX_FLIGHT_NREP, 1, SCVX_FLIGHT_NREP, q.nq,
+                               q.ranks, q.flightq, st);
+    if (e == hipSuccess && q.pathq)
+        e = launch_order_stats(B * (K + 1) * SCVX_PSIG_N, S, pathv, (size_t)S, 1, 0, 1, q.nq, q.ranks, q.pathq, st);
+    return e;
+}
+
+int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq) {
+    if (nq == 0 && !flightq && !pathq) return SCVX_OK;   // nothing asked for: the call it extends
+    return check_ranks(ctx, S, nq, ranks);
 }
 
 hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
-                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st) {
+                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
+                           const McQ* q) {
     const PathK c = path_constants(ctx->prob);
     const double dt = 1.0 / (K + 1);
     const int nblk = (S + 63) / 64;
     hipError_t e = mc_workspace(ctx, (size_t)B * nblk * MC_NP);
     if (e != hipSuccess) return e;
+    double* pv = nullptr;
+    if (q && (e = mc_q_buffers(ctx, B, K, S, *q, flights, pv)) != hipSuccess) return e;
     McK m{};
     m.tol = tol;
     bool noise = false;
@@ -336,9 +397,14 @@ hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, 
     const dim3 g((unsigned)nblk, (unsigned)B), blk(64);
     double* part = ctx->mc_ws;
     const DynP<double> dp(ctx->dyn);
-#define SCVX_MC(A, F, T, par)                                                                                                          \
-    hipLaunchKernelGGL((mc_fly_kernel<A, F, T>), g, blk, 0, st, par, c, m, S, K, x, u, sigma, gain, C0, xi0, eta, dt, nsub, flags, part, \
-                       flights, xland, dx0)
+#define SCVX_MC_PV(A, F, T, P, par)                                                                                                       \
+    hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P>), g, blk, 0, st, par, c, m, S, K, x, u, sigma, gain, C0, xi0, eta, dt, nsub, flags, part, \
+                       flights, xland, dx0, pv)
+#define SCVX_MC(A, F, T, par)                  \
+    do {                                       \
+        if (pv) SCVX_MC_PV(A, F, T, true, par); \
+        else SCVX_MC_PV(A, F, T, false, par);  \
+    } while (0)
     if (ctx->dyn.trq) {
         const DynPT<double> dpt(ctx->dyn);
         if (ctx->dyn.fin) SCVX_MC(true, true, true, dpt);
@@ -351,10 +417,13 @@ hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, 
     else
         SCVX_MC(false, false, false, dp);
 #undef SCVX_MC
+#undef SCVX_MC_PV
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mc_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov);
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess || !q) return e;
+    return mc_q_finish(B, K, S, *q, flights, pv, st);
 }
 
 int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain, const void* C0,
@@ -382,26 +451,58 @@ int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void
 
 extern "C" {
 
+int scvx_track_mc_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                        const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
+                        const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
+                        double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
+                        double* pathq_dev, double* pathv_dev) {
+    int rc = scvx::check_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags,
+                                  tol, mcrep_dev, xmean_dev, xcov_dev);
+    if (rc) return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
+    scvx::McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
+    const bool any = flightq_dev || pathq_dev || pathv_dev;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, nsub, flags, tol,
+                                        mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, ctx->stream, any ? &q : nullptr));
+    return SCVX_OK;
+}
+
 int scvx_track_mc_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                       const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
                       const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
                       double* flights_dev, double* xland_dev, double* dx0_dev) {
-    int rc = scvx::check_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags,
-                                  tol, mcrep_dev, xmean_dev, xcov_dev);
-    if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, nsub, flags, tol,
-                                        mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, ctx->stream));
-    return SCVX_OK;
+    return scvx_track_mc_q_f64(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags, tol,
+                               mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int scvx_track_mc_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
                            int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland,
                            double* dx0) {
+    return scvx_track_mc_q_f64_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
+                                    flights, xland, dx0, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                             const double* gain, const double* C0, const double* xi0, const double* eta, const double* sw14,
+                             const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                             double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
+                             double* pathv) {
     int rc = scvx::check_track_mc(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov);
     if (rc) return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
+                 npv = (size_t)B * (K + 1) * SCVX_PSIG_N * S;
+    scvx::DevBuf<double> dfq, dpq, dpv;
+    if (flightq) SCVX_HIP(ctx, hipMalloc((void**)&dfq.p, nfq * 8));
+    if (pathq) SCVX_HIP(ctx, hipMalloc((void**)&dpq.p, npq * 8));
+    if (pathv) SCVX_HIP(ctx, hipMalloc((void**)&dpv.p, npv * 8));
+    scvx::McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = dfq.p, q.pathq = dpq.p, q.pathv = dpv.p;
+    const bool any = flightq || pathq || pathv;
     const int NU = scvx_control_dim(ctx), n = 14 + NU;
     const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, ng = (size_t)B * K * NU * n, nc = (size_t)B * 196,
                  ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
@@ -429,7 +530,10 @@ int scvx_track_mc_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, 
     SCVX_HIP(ctx, hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st));
     if (eta) SCVX_HIP(ctx, hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st));
     SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, dx.p, du.p, ds.p, dg.p, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p, dm.p, dv.p,
-                                        df.p, dl.p, d0.p, st));
+                                        df.p, dl.p, d0.p, st, any ? &q : nullptr));
+    if (flightq) SCVX_HIP(ctx, hipMemcpyAsync(flightq, dfq.p, nfq * 8, hipMemcpyDeviceToHost, st));
+    if (pathq) SCVX_HIP(ctx, hipMemcpyAsync(pathq, dpq.p, npq * 8, hipMemcpyDeviceToHost, st));
+    if (pathv) SCVX_HIP(ctx, hipMemcpyAsync(pathv, dpv.p, npv * 8, hipMemcpyDeviceToHost, st));
     SCVX_HIP(ctx, hipMemcpyAsync(mcrep, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
     SCVX_HIP(ctx, hipMemcpyAsync(xmean, dm.p, nm * 8, hipMemcpyDeviceToHost, st));
     SCVX_HIP(ctx, hipMemcpyAsync(xcov, dv.p, nc * 8, hipMemcpyDeviceToHost, st));

@@ -29,7 +29,36 @@ __device__ __forceinline__ double wave_nan_max(double v) {
     return v;
 }
 
+// The four state path functions of one node of one flight into pathv (the flying kernels with PV set): MASS = x[0], GLIDE =
+// tan(gammaGs) |r[2:3]| - r[1], TILT = |q[3:4]|, RATE = |w| -- the audit's own expressions, the constants of tilt (sqcm) and rate
+// (omMax) NOT subtracted.  p points at (b, k, MASS, s); consecutive functions are S apart.  Plain vector stores.
+__device__ __forceinline__ void mc_path_store(double* __restrict__ p, int S, double tggs, const double* xs) {
+    p[(size_t)SCVX_PSIG_MASS * S] = xs[0];
+    p[(size_t)SCVX_PSIG_GLIDE * S] = tggs * sqrt(xs[2] * xs[2] + xs[3] * xs[3]) - xs[1];
+    p[(size_t)SCVX_PSIG_TILT * S] = sqrt(xs[9] * xs[9] + xs[10] * xs[10]);
+    p[(size_t)SCVX_PSIG_RATE * S] = sqrt(xs[11] * xs[11] + xs[12] * xs[12] + xs[13] * xs[13]);
+}
+
 // the context's workspace of partial rows, grown on demand (scvx_mc.hip)
 hipError_t mc_workspace(scvx_ctx* ctx, size_t doubles);
+// ... and, beside it, the workspace of the dense values whose order statistics are asked for without the dense output itself
+// (flights [B][S][16] and pathv [B][K+1][5][S]), under the same rule: no two calls on one context overlapping on different streams
+hipError_t mc_q_workspace(scvx_ctx* ctx, size_t doubles);
+
+// What the _q forms add to a sampled call (scvx_quantile.hip, scvx_mc.hip): nq ranks (host), flightq [B][16][nq], pathq
+// [B][K+1][5][nq], pathv [B][K+1][5][S], each a device pointer or nullptr.
+struct McQ {
+    int nq = 0;
+    const int* ranks = nullptr;
+    double *flightq = nullptr, *pathq = nullptr, *pathv = nullptr;
+};
+int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq);
+int check_ranks(scvx_ctx* ctx, int S, int nq, const int* ranks);
+// rows: row r starts at v[(r / inner) * ld_outer + (r % inner) * ld_inner], its S values inc apart; out [R][nq]
+hipError_t launch_order_stats(int R, int S, const double* v, size_t ld_outer, int inner, size_t ld_inner, size_t inc, int nq,
+                              const int* ranks, double* out, hipStream_t st);
+// where the flying kernel writes flights / pathv (the caller's buffer, the workspace, or nullptr), then after it: the order statistics
+hipError_t mc_q_buffers(scvx_ctx* ctx, int B, int K, int S, const McQ& q, double*& flights, double*& pathv);
+hipError_t mc_q_finish(int B, int K, int S, const McQ& q, const double* flights, const double* pathv, hipStream_t st);
 
 }  // namespace scvx

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void mc_nav_model_kernel(McNavK nv, double* __
 // square root of a variance (a rounded variance of -1e-40 is 0, a NaN stays a NaN)
 __device__ __forceinline__ double mcn_sd(double v) { return v > 0.0 ? sqrt(v) : (v != v ? v : 0.0); }
 
-template <bool AERO, bool FIN, bool TRQ, typename DS>
+template <bool AERO, bool FIN, bool TRQ, typename DS, bool PV>
 __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, PathK c, McK m, int mm, const double* __restrict__ hm, int S, int K,
                                                         const double* __restrict__ x, const double* __restrict__ u,
                                                         const double* __restrict__ sigma, const double* __restrict__ gain,
@@ -56,7 +56,8 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
                                                         const double* __restrict__ xin, const double* __restrict__ nud, double dt,
                                                         int nsub, int opt, double* __restrict__ part, double* __restrict__ flights,
                                                         double* __restrict__ xland, double* __restrict__ dx0o,
-                                                        double* __restrict__ navfed, double* __restrict__ navK) {
+                                                        double* __restrict__ navfed, double* __restrict__ navK,
+                                                        double* __restrict__ pathv) {
     // hm: H [m][14] then sqrt(rm) at MCN_SRM, in the workspace behind the partial rows
     typedef double R;
     __shared__ R epl[14][64];   // eps rests here while the segment is integrated: one column per lane, no lane reads another's
@@ -133,7 +134,12 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
     }
     if (mm > 0)
         for (int e = ln; e < MCN_MODEL; e += 64) Hl[e] = hm[e];
+    // PV: the five path functions at every node, as mc_fly_kernel stores them: of the TRUTH xs (the constraints bind the vehicle), the
+    // thrust norm of the command formed from the estimate
+    R* pvb = PV ? pathv + (size_t)b * (K + 1) * SCVX_PSIG_N * S + s_ : nullptr;
+    if (PV && live) pvb[(size_t)SCVX_PSIG_THRUST * S] = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
     for (int k = 0; k < K; k++) {
+        if (PV && live) mc_path_store(pvb + (size_t)k * SCVX_PSIG_N * S, S, c.tggs, xs);
         __syncthreads();   // the readers of the previous node's A and Kf are done
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -195,6 +201,7 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
                 const R un = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
                 n_lo += (c.Tmin - un > m.tol) ? 1 : 0;
                 n_hi += (un - c.Tmax > m.tol) ? 1 : 0;
+                if (PV && live) pvb[((size_t)(k + 1) * SCVX_PSIG_N + SCVX_PSIG_THRUST) * S] = un;
             }
             if (clamp) {
                 const R un = sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
@@ -299,6 +306,7 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
         }
     }
     // xs is the flown final node, eps the error eps_K of the estimate there (no measurement at node K)
+    if (PV && live) mc_path_store(pvb + (size_t)K * SCVX_PSIG_N * S, S, c.tggs, xs);
 #pragma unroll
     for (int i = 0; i < 14; i++) eps[i] = epl[i][ln];
     R mr = R(0.0), mv = R(0.0), mq = R(0.0), mw = R(0.0);
@@ -485,13 +493,15 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
                                         const DS* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int mm,
                                         const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                         double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland,
-                                        double* dx0, double* navfed, double* navK, hipStream_t st) {
+                                        double* dx0, double* navfed, double* navK, hipStream_t st, const McQ* q) {
     const PathK c = path_constants(ctx->prob);
     const double dt = 1.0 / (K + 1);
     const int nblk = (S + 63) / 64;
     const size_t nrows = (size_t)B * nblk * MCN_NP;
     hipError_t e = mc_workspace(ctx, nrows + MCN_MODEL);
     if (e != hipSuccess) return e;
+    double* pv = nullptr;
+    if (q && (e = mc_q_buffers(ctx, B, K, S, *q, flights, pv)) != hipSuccess) return e;
     McK m{};
     m.tol = tol;
     bool noise = false;
@@ -511,9 +521,14 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const DynP<double> dp(ctx->dyn);
-#define SCVX_MCN(A, F, T, par)                                                                                                          \
-    hipLaunchKernelGGL((mc_nav_fly_kernel<A, F, T, DS>), g, blk, 0, st, par, c, m, mm, hm, S, K, x, u, sigma, gain, C0, xi0, eta, deriv, kf, \
-                       CN, xin, nud, dt, nsub, flags, part, flights, xland, dx0, navfed, navK)
+#define SCVX_MCN_PV(A, F, T, P, par)                                                                                                          \
+    hipLaunchKernelGGL((mc_nav_fly_kernel<A, F, T, DS, P>), g, blk, 0, st, par, c, m, mm, hm, S, K, x, u, sigma, gain, C0, xi0, eta, deriv, kf, \
+                       CN, xin, nud, dt, nsub, flags, part, flights, xland, dx0, navfed, navK, pv)
+#define SCVX_MCN(A, F, T, par)                  \
+    do {                                        \
+        if (pv) SCVX_MCN_PV(A, F, T, true, par); \
+        else SCVX_MCN_PV(A, F, T, false, par);  \
+    } while (0)
     if (ctx->dyn.trq) {
         const DynPT<double> dpt(ctx->dyn);
         if (ctx->dyn.fin) SCVX_MCN(true, true, true, dpt);
@@ -526,10 +541,13 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
     else
         SCVX_MCN(false, false, false, dp);
 #undef SCVX_MCN
+#undef SCVX_MCN_PV
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mc_nav_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov, jmean, jcov, mcnav);
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess || !q) return e;
+    return mc_q_finish(B, K, S, *q, flights, pv, st);
 }
 
 hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
@@ -537,9 +555,9 @@ hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, hipStream_t st) {
+                               double* navfed, double* navK, hipStream_t st, const McQ* q) {
     return launch_track_mc_nav_t<double>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                         tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st);
+                                         tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q);
 }
 
 hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
@@ -547,9 +565,9 @@ hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const dou
                                    const float* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
                                    const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                    double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                                   double* navfed, double* navK, hipStream_t st) {
+                                   double* navfed, double* navK, hipStream_t st, const McQ* q) {
     return launch_track_mc_nav_t<float>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st);
+                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q);
 }
 
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
@@ -576,22 +594,38 @@ int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const 
 
 extern "C" {
 
+int scvx_track_mc_nav_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                            const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
+                            const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
+                            const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
+                            double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
+                            double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
+                            double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev) {
+    int rc = scvx::check_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
+                                      CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
+                                      jcov_dev, mcnav_dev);
+    if (rc) return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
+    scvx::McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
+    const bool any = flightq_dev || pathq_dev || pathv_dev;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev,
+                                            kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev,
+                                            jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev,
+                                            ctx->stream, any ? &q : nullptr));
+    return SCVX_OK;
+}
+
 int scvx_track_mc_nav_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                           const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
                           const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
                           const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
                           double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev, double* mcnav_dev,
                           double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev, double* navK_dev) {
-    int rc = scvx::check_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
-                                      CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
-                                      jcov_dev, mcnav_dev);
-    if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev,
-                                            kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev,
-                                            jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev,
-                                            ctx->stream));
-    return SCVX_OK;
+    return scvx_track_mc_nav_q_f64(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev, CN_dev,
+                                   xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev,
+                                   mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int scvx_track_mc_nav_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
@@ -600,10 +634,25 @@ int scvx_track_mc_nav_f64_host(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                double* navfed, double* navK) {
+    return scvx_track_mc_nav_q_f64_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
+                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr, nullptr,
+                                        nullptr, nullptr);
+}
+
+int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                                 const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
+                                 const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                                 const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                                 double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                                 double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
     int rc = scvx::check_track_mc_nav(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
                                       tol, mcrep, xmean, xcov, jmean, jcov, mcnav);
     if (rc) return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    scvx::DevBuf<double> dfq, dpq, dpv;
+    const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
+                 npv = (size_t)B * (K + 1) * SCVX_PSIG_N * S;
     const int NU = scvx_control_dim(ctx), n = 14 + NU;
     const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, ng = (size_t)B * K * NU * n, nc = (size_t)B * 196,
                  ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
@@ -618,7 +667,8 @@ int scvx_track_mc_nav_f64_host(scvx_ctx* ctx, int B, int K, int S, const double*
     const struct { scvx::DevBuf<double>* b; double* h; size_t n; bool want; } out[] = {
         {&dr, mcrep, nr, true},  {&dm, xmean, nm, true},  {&dv, xcov, nc, true},  {&djm, jmean, nj, true},
         {&djc, jcov, njc, true}, {&dnv, mcnav, nv, true}, {&df, flights, nf, flights != nullptr}, {&dl, xland, nl, xland != nullptr},
-        {&d0, dx0, nl, dx0 != nullptr}, {&dfe, navfed, nfed, navfed != nullptr}, {&dnk, navK, nl, navK != nullptr}};
+        {&d0, dx0, nl, dx0 != nullptr}, {&dfe, navfed, nfed, navfed != nullptr}, {&dnk, navK, nl, navK != nullptr},
+        {&dfq, flightq, nfq, flightq != nullptr}, {&dpq, pathq, npq, pathq != nullptr}, {&dpv, pathv, npv, pathv != nullptr}};
     hipStream_t st = ctx->stream;
     for (const auto& a : in)
         if (a.want) {
@@ -627,14 +677,16 @@ int scvx_track_mc_nav_f64_host(scvx_ctx* ctx, int B, int K, int S, const double*
         }
     for (const auto& a : out)
         if (a.want) SCVX_HIP(ctx, hipMalloc((void**)&a.b->p, a.n * 8));
+    scvx::McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = dfq.p, q.pathq = dpq.p, q.pathv = dpv.p;
     hipError_t e = scvx::launch_track_mc_nav(ctx, B, K, S, dx.p, du.p, ds.p, dg.p, dc.p, di.p, de.p, w14, dd.p, dk.p, dcn.p, dxi.p, dnu.p, m,
                                              H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p, df.p, dl.p, d0.p, dfe.p,
-                                             dnk.p, st);
+                                             dnk.p, st, (flightq || pathq || pathv) ? &q : nullptr);
     for (const auto& a : out)
         if (e == hipSuccess && a.want) e = hipMemcpyAsync(a.h, a.b->p, a.n * 8, hipMemcpyDeviceToHost, st);
     hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return scvx::fail(ctx, SCVX_ERR_HIP, std::string("scvx_track_mc_nav_f64_host: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return scvx::fail(ctx, SCVX_ERR_HIP, std::string("scvx_track_mc_nav_q_f64_host: ") + hipGetErrorString(e));
     return SCVX_OK;
 }
 

@@ -371,7 +371,13 @@ class McReport:
     """The report of a sampled dispersion (scvx_track_mc_f64, include/scvx.h): `raw` [B][48], one named numpy view per column
     (report.MAX_GAP, report.MEAN_MISS_R, report.P_TMIN, report.P_ANY, report.OUT_LO, report.N_BAD, ... -- _lib.MC_COLUMNS), the landing
     statistics `xmean` [B][14] and `xcov` [B][14][14] of x_fly[K] - xbar_K over the samples, and the optional dense outputs `flights`
-    [B][S][16], `xland` [B][S][14] and `dx0` [B][S][14], or None.  The draws are shared by all plans; quantiles come from `flights`."""
+    [B][S][16], `xland` [B][S][14] and `dx0` [B][S][14], or None.  The draws are shared by all plans.  With `quantiles=` / `per_node=`
+    (the _q forms of the call): `probs` and `ranks` (montecarlo.quantile_ranks), `q` [B][16][nq] the order statistics of the sixteen
+    flight columns over the samples -- rep.quantile("MISS_R", 0.99) --, `pathq` [B][K+1][5][nq] those of the five path functions
+    (_lib.PSIG_COLUMNS) at every node, and the dense `pathv` [B][K+1][5][S]; each None when not asked for.  A quantile is a selection
+    of one flight's value, with the sampling error of montecarlo.quantile_stderr."""
+
+    probs = ranks = q = pathq = pathv = None
 
     def __init__(self, raw, xmean, xcov, flights=None, xland=None, dx0=None):
         self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.MC_NREP)
@@ -379,6 +385,28 @@ class McReport:
         self.flights, self.xland, self.dx0 = flights, xland, dx0
         for name, i in _lib.MC_INDEX.items():
             setattr(self, name, self.raw[:, i])
+
+    def _with_q(self, mq):
+        self.probs, self.ranks, self.q, self.pathq, self.pathv = mq.probs, mq.ranks, mq.flightq, mq.pathq, mq.pathv
+        return self
+
+    def _qi(self, p):
+        if self.probs is None:
+            raise ValueError("the call was made without quantiles=")
+        hit = np.flatnonzero(self.probs == float(p))
+        if hit.size == 0:
+            raise ValueError("quantile %r was not asked for (probs = %s)" % (p, self.probs.tolist()))
+        return int(hit[0])
+
+    def quantile(self, column, p):
+        """[B]: the order statistic of probability p (one of `probs`) of flight column `column` (_lib.FLIGHT_COLUMNS) over the samples."""
+        return self.q[:, _lib.FLIGHT_INDEX[column], self._qi(p)]
+
+    def path_quantile(self, column, p):
+        """[B][K+1]: the order statistic of probability p of path function `column` (_lib.PSIG_COLUMNS) at every node (per_node=True)."""
+        if self.pathq is None:
+            raise ValueError("the call was made without per_node=True")
+        return self.pathq[:, :, _lib.PSIG_INDEX[column], self._qi(p)]
 
     def __len__(self):
         return self.raw.shape[0]
@@ -400,6 +428,42 @@ def _mc_dense(dense):
     if not want <= {"flights", "xland", "dx0"}:
         raise ValueError("dense: True, False or names out of 'flights', 'xland', 'dx0', not %r" % (dense,))
     return want
+
+
+class _McQ:
+    """What the _q forms of the sampled calls add: quantiles (an iterable of probabilities, or None), per_node, and "pathv" among the
+    dense names -> the five trailing C arguments (nq, ranks, flightq, pathq, pathv) and their host arrays.  `on` False: the call is
+    the old entry point, with exactly its arguments.  dense=True stays "all the dense outputs the call had": pathv is by name only."""
+
+    def __init__(self, quantiles, per_node, dense):
+        self.rest = dense
+        want_pv = False
+        if not (dense is True or not dense):
+            names = {dense} if isinstance(dense, str) else set(dense)
+            want_pv = "pathv" in names
+            self.rest = tuple(n for n in names if n != "pathv")
+        self.pq = None if quantiles is None else np.atleast_1d(np.asarray(list(np.atleast_1d(quantiles)), np.float64))
+        if self.pq is not None and not 1 <= self.pq.size <= 16:
+            raise ValueError("quantiles: between 1 and 16 probabilities")
+        if per_node and self.pq is None:
+            raise ValueError("per_node=True needs quantiles=")
+        self.per_node, self.want_pv = bool(per_node), want_pv
+        self.on = self.pq is not None or want_pv
+        self.probs = self.ranks = self.flightq = self.pathq = self.pathv = None
+
+    def args(self, B, K, S):
+        from .montecarlo import quantile_ranks
+        nq = 0
+        if self.pq is not None:
+            self.probs, self.ranks = self.pq, np.ascontiguousarray(quantile_ranks(self.pq, S), np.int32)
+            nq = int(self.ranks.size)
+            self.flightq = np.empty((B, _lib.FLIGHT_NREP, nq))
+            if self.per_node:
+                self.pathq = np.empty((B, K + 1, _lib.PSIG_N, nq))
+        if self.want_pv:
+            self.pathv = np.empty((B, K + 1, _lib.PSIG_N, S))
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        return (nq, self.ranks.ctypes.data_as(C.POINTER(C.c_int)) if nq else None, opt(self.flightq), opt(self.pathq), opt(self.pathv))
 
 
 def _mc_inputs(S0, B, K, samples, seed, w, draws):
@@ -433,7 +497,7 @@ def _mc_outputs(B, S, dense):
 
 
 def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=0, w=None, nsub=10, clamp=False, tol=0.0, dense=(),
-                   draws=None, nav=None) -> McReport:
+                   draws=None, nav=None, quantiles=None, per_node=False) -> McReport:
     """Sampled closed-loop dispersion of the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] tracked under the gains gain
     [B][K][nu][14+nu]: `samples` flights PER PLAN on the device, reduced there to one McReport row per plan (scvx_track_mc_f64_host;
     the model, the impulse convention and the limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one [14][14]
@@ -443,12 +507,19 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     tol: the threshold of the P_* and OUT_* columns.  dense: True, or names out of "flights", "xland", "dx0".  draws = (xi0 [S][14],
     eta [S][K][14] or None): use these instead of mc_draws (`samples` and `seed` are then ignored).  nav = (N0, H, rm): the flights
     are flown on a navigation estimate (track_mc_nav_batch on the plans' own linearisation, a McNavReport; draws then has four
-    entries); None: the law is fed the truth."""
+    entries); None: the law is fed the truth.
+    quantiles: an iterable of probabilities (at most 16): the report carries `q` [B][16][nq], the order statistics of the sixteen flight
+    columns over the samples, reduced on the device (scvx_track_mc_q_f64_host; probability -> rank by montecarlo.quantile_ranks, a
+    selection); per_node=True adds `pathq` [B][K+1][5][nq], those of the five path functions at every node, and dense may name "pathv"
+    for the samples themselves [B][K+1][5][S].  With the clamp the THRUST function is still the unclamped command.  With these keywords
+    at their defaults the call is the one it was."""
     if nav is not None:
         n0, _, Hm, rv = _nav_arg(nav, np.shape(x)[0])
         _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / np.shape(x)[1])
         return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
-                                  tol=tol, dense=dense, draws=draws)
+                                  tol=tol, dense=dense, draws=draws, quantiles=quantiles, per_node=per_node)
+    mq = _McQ(quantiles, per_node, dense)
+    dense = mq.rest
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     sigma = np.ascontiguousarray(sigma, np.float64)
@@ -462,11 +533,14 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     S = xi0.shape[0]
     rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    _lib.check(cache.handle, cache._L.scvx_track_mc_f64_host(
-        cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(sw), None,
-        int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov),
-        opt(flights), opt(xland), opt(dx0)), "scvx_track_mc_f64_host")
-    return McReport(rep, xmean, xcov, flights, xland, dx0)
+    args = (cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(sw), None,
+            int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov),
+            opt(flights), opt(xland), opt(dx0))
+    if mq.on:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_q_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_q_f64_host")
+    else:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_f64_host(*args), "scvx_track_mc_f64_host")
+    return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)
 
 
 class NavReport(CovReport):
@@ -636,14 +710,17 @@ def _mc_nav_outputs(B, S, K, dense):
 
 
 def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0, H, rm, samples, seed=0, w=None, kf=None, nsub=10,
-                       clamp=False, tol=0.0, dense=(), draws=None) -> McNavReport:
+                       clamp=False, tol=0.0, dense=(), draws=None, quantiles=None, per_node=False) -> McNavReport:
     """track_mc_batch with the law fed a navigation ESTIMATE whose error is generated per flight on the device (scvx_track_mc_nav_f64_host;
     the model and its limits are in include/scvx.h): the sampled, nonlinear counterpart of nav_cov_batch, whose arguments deriv, N0, H,
     rm and w mean here what they mean there.  The error starts at handover_factor(N0[b]) @ xin[s], is corrected at every node but the
     last by the filter gains kf [B][K][14][m] with the measurement noise sqrt(rm) * nud, and receives the impulse sqrt(w) * eta that
     the truth receives.  kf None: the gains of nav_cov_batch for the same model.  The draws are montecarlo.mc_draws and
     montecarlo.mc_nav_draws of `seed`, or draws = (xi0, eta, xin, nud).  dense: True, or names out of "flights", "xland", "dx0",
-    "navfed", "navK"."""
+    "navfed", "navK".  quantiles, per_node and the dense name "pathv" as track_mc_batch (scvx_track_mc_nav_q_f64_host): the state
+    path functions are those of the TRUTH, the thrust norm that of the command formed from the estimate."""
+    mq = _McQ(quantiles, per_node, dense)
+    dense = mq.rest
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     sigma = np.ascontiguousarray(sigma, np.float64)
@@ -669,11 +746,14 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     S = xi0.shape[0]
     red, dn = _mc_nav_outputs(B, S, K, dense)
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    _lib.check(cache.handle, cache._L.scvx_track_mc_nav_f64_host(
-        cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(wv), _p(deriv), opt(kf if m else None),
-        _p(cn), _p(xin), opt(nud), m, opt(Hm), opt(rv), int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0,
-        float(tol), *[_p(a) for a in red], *[opt(a) for a in dn]), "scvx_track_mc_nav_f64_host")
-    return McNavReport(*red, *dn)
+    args = (cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(wv), _p(deriv),
+            opt(kf if m else None), _p(cn), _p(xin), opt(nud), m, opt(Hm), opt(rv), int(cache.npts if nsub is None else nsub),
+            _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red], *[opt(a) for a in dn])
+    if mq.on:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_q_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_q_f64_host")
+    else:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_f64_host(*args), "scvx_track_mc_nav_f64_host")
+    return McNavReport(*red, *dn)._with_q(mq)
 
 
 def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None):

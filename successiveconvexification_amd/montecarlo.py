@@ -121,6 +121,97 @@ def mc_nav_draws(samples, K, m, seed, lo=0):
     return xin, nud
 
 
+def quantile_ranks(p, S):
+    """The 0-based ascending ranks of the probabilities `p` (a scalar or an iterable) in a sample of S values, as the order statistics of
+    the library count them (scvx_order_stats_f64, include/scvx.h): min(S - 1, max(0, ceil(p S) - 1)), numpy's method="inverted_cdf"
+    with p = 0 the minimum and p = 1 the maximum.  A selection, never an interpolation.  Returns an int32 array [len(p)]."""
+    pv = np.atleast_1d(np.asarray(p, np.float64))
+    S = int(S)
+    if S < 1:
+        raise ValueError("quantile_ranks: S >= 1")
+    if pv.ndim != 1 or not np.all((pv >= 0.0) & (pv <= 1.0)):
+        raise ValueError("quantile_ranks: probabilities in [0, 1]")
+    return np.clip(np.ceil(pv * S).astype(np.int64) - 1, 0, S - 1).astype(np.int32)
+
+
+def quantile_stderr(p, S):
+    """The standard error of the p-quantile estimated from S independent flights, in units of the quantity's standard deviation, under a
+    NORMAL model: sqrt(p (1 - p) / S) / phi(z_p).  0.26 at p = 0.99865, S = 1,024: a tail quantile from S flights is itself uncertain."""
+    from statistics import NormalDist
+    nd = NormalDist()
+    p = float(p)
+    return float(np.sqrt(p * (1.0 - p) / int(S)) / nd.pdf(nd.inv_cdf(p)))
+
+
+def path_functions(p, x, u):
+    """The five path functions of psig / pathv (_lib.PSIG_COLUMNS) of the plan's own nodes: g [..][K+1][5] from x [..][K+1][14] and u
+    [..][K+1][nu] -- MASS x[0], GLIDE tan(gammaGs) |r[2:3]| - r[1], TILT |q[3:4]|, RATE |w| (the constants of tilt and rate not
+    subtracted) and THRUST |u[1:3]|.  p: the problem (gammaGs in degrees)."""
+    x, u = np.asarray(x, np.float64), np.asarray(u, np.float64)
+    tg = np.tan(np.deg2rad(p.gammaGs))
+    return np.stack([x[..., 0], tg * np.sqrt(x[..., 2] ** 2 + x[..., 3] ** 2) - x[..., 1], np.sqrt(x[..., 9] ** 2 + x[..., 10] ** 2),
+                     np.sqrt(x[..., 11] ** 2 + x[..., 12] ** 2 + x[..., 13] ** 2),
+                     np.sqrt(u[..., 0] ** 2 + u[..., 1] ** 2 + u[..., 2] ** 2)], axis=-1)
+
+
+def margins_from_quantiles(p, x, u, pathq_lo, pathq_hi, constraints="all", cap=0.25, current=None):
+    """Per-node back-offs from the order statistics of a sampled closed loop (ScvxBatch.margins_from_mc): plain numpy.  p: the problem;
+    x [B][K+1][14], u [B][K+1][nu]: the plans; pathq_lo / pathq_hi [B][K+1][5]: the Q_{1-p} and the Q_p order statistic of the five
+    path functions at every node (one rank each of McReport.pathq).  With gbar_k = path_functions(p, x, u), the plan's own node:
+        lo_k    = max(0, |ubar_k| - Q_{1-p}(T_k))        hi_k = max(0, Q_p(T_k) - |ubar_k|)        (the pair is ASYMMETRIC here)
+        mass_k  = max(0, mbar_k - Q_{1-p}(m_k))          glide_k, tilt_k, rate_k = max(0, Q_p(g_k) - gbar_k)
+    each capped by `cap` times the width scvx_batch_margins_from_cov uses: Tmax - Tmin, mwet - mdry, sqcm, omMax, and for the glide slope
+    max(x_k[1], 0) / tan(gammaGs), which moves with the iterate.  Forced zeros as there: glide / tilt / rate at node K, mass / glide /
+    rate at node 0.  A trajectory with a NaN quantile in a selected column gets zeros in every selected kind.  constraints: a subset of
+    ("thrust", "mass", "glide", "tilt", "rate") or "all"; a kind that is not selected keeps the value of current = (lo, hi, pm) (zeros
+    without it).  Returns (lo [B][K+1], hi [B][K+1], pm [B][K+1][4]).
+    Limits: the glide back-off buys tan(gammaGs) times what is written, as the covariance one does; the quantiles carry the sampling
+    error of quantile_stderr(p, S); the draws are shared across plans; with the clamp on, T_k is still the UNCLAMPED command."""
+    from ._lib import MARGIN_BITS, PMARG_INDEX, PMARG_N, PSIG_INDEX
+    names = tuple(MARGIN_BITS) if isinstance(constraints, str) and constraints == "all" else tuple(constraints)
+    if isinstance(constraints, str) and constraints != "all" or len(names) == 0 or any(n not in MARGIN_BITS for n in names):
+        raise ValueError('constraints: a non-empty subset of %s, or "all"' % (tuple(MARGIN_BITS),))
+    x, u = np.asarray(x, np.float64), np.asarray(u, np.float64)
+    qlo, qhi = np.asarray(pathq_lo, np.float64), np.asarray(pathq_hi, np.float64)
+    B, K1 = x.shape[0], x.shape[1]
+    if x.shape != (B, K1, 14) or u.shape[:2] != (B, K1) or qlo.shape != (B, K1, 5) or qhi.shape != (B, K1, 5):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][nu], pathq_lo and pathq_hi [B][K+1][5]")
+    if current is None:
+        lo, hi, pm = np.zeros((B, K1)), np.zeros((B, K1)), np.zeros((B, K1, PMARG_N))
+    else:
+        lo, hi, pm = (np.array(a, np.float64) for a in current)
+    g = path_functions(p, x, u)
+    itan = 1.0 / np.tan(np.deg2rad(p.gammaGs))
+    sqcm = np.sqrt((1.0 - np.cos(np.deg2rad(p.thetaMax))) / 2.0)
+    iM, iG, iT, iR, iU = (PSIG_INDEX[n] for n in ("MASS", "GLIDE", "TILT", "RATE", "THRUST"))
+    sel = [PSIG_INDEX[n.upper()] for n in names]
+    bad = np.isnan(qlo[:, :, sel]).any(axis=(1, 2)) | np.isnan(qhi[:, :, sel]).any(axis=(1, 2))
+    ok = ~bad[:, None]
+    with np.errstate(invalid="ignore"):
+        if "thrust" in names:
+            w = cap * (p.Tmax - p.Tmin)
+            lo[:] = np.where(ok, np.minimum(np.maximum(0.0, g[:, :, iU] - qlo[:, :, iU]), w), 0.0)
+            hi[:] = np.where(ok, np.minimum(np.maximum(0.0, qhi[:, :, iU] - g[:, :, iU]), w), 0.0)
+        if "mass" in names:
+            v = np.where(ok, np.minimum(np.maximum(0.0, g[:, :, iM] - qlo[:, :, iM]), cap * (p.mwet - p.mdry)), 0.0)
+            v[:, 0] = 0.0
+            pm[:, :, PMARG_INDEX["MASS"]] = v
+        if "glide" in names:
+            width = np.maximum(x[:, :, 1], 0.0) * itan
+            v = np.where(ok, np.minimum(np.maximum(0.0, qhi[:, :, iG] - g[:, :, iG]), cap * width), 0.0)
+            v[:, 0] = v[:, K1 - 1] = 0.0
+            pm[:, :, PMARG_INDEX["GLIDE"]] = v
+        if "tilt" in names:
+            v = np.where(ok, np.minimum(np.maximum(0.0, qhi[:, :, iT] - g[:, :, iT]), cap * sqcm), 0.0)
+            v[:, K1 - 1] = 0.0
+            pm[:, :, PMARG_INDEX["TILT"]] = v
+        if "rate" in names:
+            v = np.where(ok, np.minimum(np.maximum(0.0, qhi[:, :, iR] - g[:, :, iR]), cap * p.omMax), 0.0)
+            v[:, 0] = v[:, K1 - 1] = 0.0
+            pm[:, :, PMARG_INDEX["RATE"]] = v
+    return lo, hi, pm
+
+
 _STATE_BLOCKS = {"r": (1, 4), "v": (4, 7), "q": (7, 11), "w": (11, 14)}
 
 

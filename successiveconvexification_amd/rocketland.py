@@ -82,12 +82,13 @@ def track(iteration: ProblemIteration, cache: IntegratorCache = None, dx0=None, 
 
 
 def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, samples=256, seed=0, w=None, q=None, r=None, qf=None,
-             nsub=None, clamp=False, tol=0.0, dense=(), nav=None):
+             nsub=None, clamp=False, tol=0.0, dense=(), nav=None, quantiles=None, per_node=False):
     """Sampled closed-loop dispersion of an iterate's plan tracked under the time-varying LQR gains about it: `samples` flights from
     Gaussian starts of covariance S0 ([14][14], or a [14] vector of standard deviations), with the per-segment process noise w as an
     impulse at the nodes (dynamics.track_gains_batch on the plan's own linearisation, dynamics.track_mc_batch).  A dynamics.McReport of
     one row.  nav = (N0, H, rm), navigation()'s model: the flights are flown on a navigation estimate (dynamics.track_mc_nav_batch on
-    the same linearisation), a dynamics.McNavReport of one row."""
+    the same linearisation), a dynamics.McNavReport of one row.  quantiles, per_node and the dense name "pathv" as
+    dynamics.track_mc_batch: order statistics over the samples, reduced on the device."""
     from .dynamics import linearize_batch, track_gains_batch, track_mc_batch
     if S0 is None:
         raise ValueError("track_mc: S0 (the handover covariance) is required")
@@ -101,8 +102,9 @@ def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None
         from .dynamics import _nav_arg, track_mc_nav_batch
         n0, _, Hm, rv = _nav_arg(nav, 1)
         return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
-                                  tol=tol, dense=dense)
-    return track_mc_batch(cache, x, u, sigma, gain, S0, samples, seed=seed, w=w, nsub=nsub, clamp=clamp, tol=tol, dense=dense)
+                                  tol=tol, dense=dense, quantiles=quantiles, per_node=per_node)
+    return track_mc_batch(cache, x, u, sigma, gain, S0, samples, seed=seed, w=w, nsub=nsub, clamp=clamp, tol=tol, dense=dense,
+                          quantiles=quantiles, per_node=per_node)
 
 
 def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False):
@@ -122,18 +124,20 @@ def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
 
 
 def robustify(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None,
-              r=None, qf=None, constraints=("thrust",), nav=None):
+              r=None, qf=None, constraints=("thrust",), nav=None, mc=None):
     """Replan an iterate under back-offs of the thrust band taken from its own covariance analysis (ScvxBatch.robustify on the
     iterate's device batch): Tmin + n s_T(k) <= |u_k| <= Tmax - n s_T(k).  Returns (the new ProblemIteration, lo [K+1], hi [K+1]);
     raises like solve_step when the conic solve fails.  The limits are those of ScvxBatch.robustify.  constraints: any subset of
     ("thrust", "mass", "glide", "tilt", "rate") or "all"; the path back-offs that were used are iteration.model.path_margins().
-    nav = (N0, H, rm): the back-offs come from the navigation analysis of the iterate (navigation()'s model), the law fed an estimate."""
+    nav = (N0, H, rm): the back-offs come from the navigation analysis of the iterate (navigation()'s model), the law fed an estimate.
+    mc = dict(p=, samples=, seed=, clamp=): they come from the sampled closed loop instead (ScvxBatch.margins_from_mc, its limits);
+    with nav the flights are flown on the estimate."""
     if S0 is None:
         raise ValueError("robustify: S0 (the handover covariance) is required")
     cache = cache if cache is not None else iteration.cache
     batch = iteration.model
     st, it, nu, dj, lo, hi = batch.robustify(S0, nsigma=nsigma, rounds=rounds, cap=cap, w=w, q=q, r=r, qf=qf, constraints=constraints,
-                                             nav=nav)
+                                             nav=nav, mc=mc)
     if st[0] in (3, 4, 5):  # rocketland.jl:273-276
         raise RuntimeError("Non-optimal result %s exiting" % {3: "SLOW_PROGRESS", 4: "NUMERICAL_ERROR", 5: "INFEASIBLE"}[int(st[0])])
     return _snapshot(iteration.problem, cache, batch), lo[0], hi[0]
