@@ -11,6 +11,7 @@
  *   (no counterpart: closed-loop covariance analysis)  ->  scvx_cov_propagate_f64[_host], scvx_batch_cov
  *   (no counterpart: sampled closed-loop dispersion)   ->  scvx_track_mc_f64[_host], scvx_batch_track_mc
  *   (no counterpart: its quantiles, per-node samples)   ->  scvx_order_stats_f64[_host], scvx_track_mc[_nav]_q_f64[_host], scvx_batch_track_mc[_nav]_q
+ *   (no counterpart: its draws made on the device)     ->  scvx_mc_draws_f64[_host], scvx_track_mc[_nav]_rng_f64[_host], scvx_batch_track_mc[_nav]_rng
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -570,7 +571,7 @@ int scvx_order_stats_f64_host(scvx_ctx *ctx, int R, int S, const double *v, size
  * pathq: the order statistics of each (b, k, f) row of pathv.
  * Limits.  A tail quantile from S flights is itself uncertain: under a normal model the standard error of the p-quantile estimate is
  * sqrt(p (1 - p) / S) / phi(z_p) standard deviations (0.26 sigma at p = 0.99865, S = 1,024 -- and at S (1 - p) < 1 the rank is the
- * maximum of the sample, whatever p says).  The draws are shared across plans.  A back-off formed from the glide quantile buys
+ * maximum of the sample, whatever p says).  The draws are shared across plans (the _rng forms below: unless independent = 1).  A back-off formed from the glide quantile buys
  * tan(gammaGs) times what is written, as the covariance back-offs do.
  * Workspace.  When the caller passes no dense flights / pathv but asks for their quantiles, the values live in a workspace that belongs
  * to the context, grown on demand, beside the workspace of partial rows and under its rule: calls on one context must not overlap on
@@ -602,6 +603,65 @@ int scvx_track_mc_nav_q_f64_host(scvx_ctx *ctx, int B, int K, int S, const doubl
                                  double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav, double *flights,
                                  double *xland, double *dx0, double *navfed, double *navK, int nq, const int *ranks,
                                  double *flightq, double *pathq, double *pathv);
+
+/* ---- sampled closed-loop dispersion with the draws made on the device ------------------------------------------------------------
+ * The calls above read standard-normal draws xi0, eta, xin, nud that the caller made and uploaded, shared by all plans.  In the _rng
+ * forms every lane makes its own from a counter-based generator: nothing is generated or uploaded by the host, and the draws may be
+ * independent per plan.  The stream, which a caller can reproduce word for word:
+ * Generator.  Philox4x64-10 exactly as numpy's np.random.Philox: multipliers M0 = 0xD2E7470EE14C6C93, M1 = 0xCA5A826395121157, Weyl
+ * constants 0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B added to the key after every round; one round maps the counter c to
+ *     [hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)];
+ * ten rounds, key [seed, 0].  Block j of the stream with base counter [0, c1, c2, c3] is the block of counter [1 + j, c1, c2, c3]
+ * (numpy increments before its first block): np.random.Philox(key=seed, counter=[0, c1, c2, c3]).random_raw(4 n) are blocks 0..n-1.
+ * Streams.  c1 = 6 for the truth (xi0, eta), c1 = 7 for the navigation error (xin, nud); c3 = s_lo + s for sample s of the call;
+ * c2 = 0 with shared draws (independent = 0: every plan flies the same draws, as in the calls above), c2 = 1 + b_lo + b for plan b
+ * with independent = 1: the B rows of one call are then independent experiments, and a statistic pooled over plans has B S flights.
+ * Layout.  A group of 14 draws occupies 4 blocks = 16 normals, draw i is normal i & 3 of block i >> 2 (two are unused).  Group 0 is
+ * the start (xi0 / xin), group 1 + k belongs to node k (eta[s][k][0:14] / nud[s][k][0:m], the first m of its 14).  So nud does not
+ * depend on m, xi0 does not depend on the noise, nothing depends on K, any (s, k, i) is random access, and the flights of
+ * s_lo = 64, S = 66 are flights 64..129 of s_lo = 0, S = 130.
+ * Normals.  Box-Muller per block: u_j = ((w_j >> 11) + 0.5) 2^-53 in double arithmetic (never 0), (z0, z1) = sqrt(-2 log u0)
+ * (cospi(2 u1), sinpi(2 u1)) and (z2, z3) likewise from u2, u3: the device's log and sincospi, a few ulp from the exact value.
+ * scvx_mc_draws_f64 writes the draws themselves, the same bits the flying kernels consume: xi0, xin [P][S][14] and eta, nud
+ * [P][S][K][14] (all 14 of a group), each NULL or wanted, for plans b = 0..P-1 (P = 1 with shared draws, B with independent ones).
+ * A flight of an _rng call is bitwise the flight of the _q call fed these arrays.
+ * scvx_track_mc_rng_f64 is scvx_track_mc_q_f64 with (xi0, eta) replaced by (rng, noise): noise != 0 is what eta != NULL is there (the
+ * truth receives the impulses sw14 * eta; sw14 is then required).  scvx_track_mc_nav_rng_f64 is scvx_track_mc_nav_q_f64 with (xi0,
+ * eta) replaced by (rng, noise) and (xin, nud) dropped -- the same rng defines them.  All outputs, dense outputs, quantile arguments
+ * and workspace rules are those of the _q forms.  SCVX_ERR_ARG as those forms, and for a null rng, a non-zero reserved, or independent
+ * outside {0, 1}; scvx_mc_draws_f64 also for P outside [1, 65535], S < 1 or K < 1. */
+typedef struct scvx_mc_rng {
+    uint64_t seed, s_lo, b_lo;
+    int32_t independent, reserved; /* reserved must be 0 */
+} scvx_mc_rng;
+int scvx_mc_draws_f64(scvx_ctx *ctx, const scvx_mc_rng *rng, int P, int S, int K, double *xi0_dev, double *eta_dev, double *xin_dev,
+                      double *nud_dev);
+int scvx_mc_draws_f64_host(scvx_ctx *ctx, const scvx_mc_rng *rng, int P, int S, int K, double *xi0, double *eta, double *xin,
+                           double *nud);
+int scvx_track_mc_rng_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                          const double *gain_dev, const double *C0_dev, const scvx_mc_rng *rng, int noise, const double *sw14,
+                          const void *reserved, int nsub, int flags, double tol, double *mcrep_dev, double *xmean_dev,
+                          double *xcov_dev, double *flights_dev, double *xland_dev, double *dx0_dev, int nq, const int *ranks,
+                          double *flightq_dev, double *pathq_dev, double *pathv_dev);
+int scvx_track_mc_rng_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                               const double *gain, const double *C0, const scvx_mc_rng *rng, int noise, const double *sw14,
+                               const void *reserved, int nsub, int flags, double tol, double *mcrep, double *xmean, double *xcov,
+                               double *flights, double *xland, double *dx0, int nq, const int *ranks, double *flightq,
+                               double *pathq, double *pathv);
+int scvx_track_mc_nav_rng_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                              const double *gain_dev, const double *C0_dev, const scvx_mc_rng *rng, int noise, const double *w14,
+                              const double *deriv_dev, const double *kf_dev, const double *CN_dev, int m, const double *H,
+                              const double *rm, int nsub, int flags, double tol, double *mcrep_dev, double *xmean_dev,
+                              double *xcov_dev, double *jmean_dev, double *jcov_dev, double *mcnav_dev, double *flights_dev,
+                              double *xland_dev, double *dx0_dev, double *navfed_dev, double *navK_dev, int nq, const int *ranks,
+                              double *flightq_dev, double *pathq_dev, double *pathv_dev);
+int scvx_track_mc_nav_rng_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                                   const double *gain, const double *C0, const scvx_mc_rng *rng, int noise, const double *w14,
+                                   const double *deriv, const double *kf, const double *CN, int m, const double *H,
+                                   const double *rm, int nsub, int flags, double tol, double *mcrep, double *xmean, double *xcov,
+                                   double *jmean, double *jcov, double *mcnav, double *flights, double *xland, double *dx0,
+                                   double *navfed, double *navK, int nq, const int *ranks, double *flightq, double *pathq,
+                                   double *pathv);
 
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
@@ -778,6 +838,20 @@ int scvx_batch_track_mc_nav_q(scvx_batch *b, const double *q14, const double *rN
                               double tol, double *mcrep, double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav,
                               double *flights, double *xland, double *dx0, double *navfed, double *navK, int nq, const int *ranks,
                               double *flightq, double *pathq, double *pathv);
+
+/* The two calls above with the draws made on the device (scvx_track_mc_rng_f64 / scvx_track_mc_nav_rng_f64): their argument lists with
+ * (xi0, eta) replaced by (rng, noise) and, in the navigation form, (xin, nud) dropped.  Nothing but C0 (and N0, CN) is uploaded.
+ * Synchronises.  SCVX_ERR_ARG as the calls above and as scvx_track_mc_rng_f64 for rng. */
+int scvx_batch_track_mc_rng(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                            const scvx_mc_rng *rng, int noise, const double *sw14, const void *reserved, int nsub, int flags,
+                            double tol, double *mcrep, double *xmean, double *xcov, double *flights, double *xland, double *dx0,
+                            int nq, const int *ranks, double *flightq, double *pathq, double *pathv);
+int scvx_batch_track_mc_nav_rng(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                                const scvx_mc_rng *rng, int noise, const double *w14, const double *N0, const double *CN, int m,
+                                const double *H, const double *rm, int nsub, int flags, double tol, double *mcrep, double *xmean,
+                                double *xcov, double *jmean, double *jcov, double *mcnav, double *flights, double *xland,
+                                double *dx0, double *navfed, double *navK, int nq, const int *ranks, double *flightq, double *pathq,
+                                double *pathv);
 
 /* ---- thrust-band back-offs and covariance-driven replanning (no counterpart in the reference) ---------------------------------
  * Per-trajectory, per-node back-offs of the thrust band, read by the conic solve alone:

@@ -795,6 +795,135 @@ track_mc_nav_q_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u
         flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, length(ranks), ranks, flightq_dev, pathq_dev, pathv_dev),
         "scvx_track_mc_nav_q_f64")
 
+# include/scvx.h, "sampled closed-loop dispersion with the draws made on the device": the _q calls with (xi0, eta) replaced by
+# (rng, noise) -- every lane makes its own draws from Philox4x64-10 (numpy's np.random.Philox; the stream is spelled out in the header),
+# shared by all plans or, with independent = true, per plan -- and, in the navigation form, (xin, nud) dropped.  An empty ranks
+# vector asks for no order statistics.  mc_draws returns the draws themselves, the bits the flying kernels consume.
+struct McRng
+    seed::UInt64
+    s_lo::UInt64
+    b_lo::UInt64
+    independent::Int32
+    reserved::Int32
+end
+McRng(seed::Integer; s_lo::Integer=0, b_lo::Integer=0, independent::Bool=false) =
+    McRng(UInt64(seed), UInt64(s_lo), UInt64(b_lo), Int32(independent), Int32(0))
+
+function mc_draws(cache::Cache, rng::McRng, S::Int; P::Int=1, K::Int=cache.problem.K)
+    xi0 = Array{Float64,3}(undef, 14, S, P); xin = similar(xi0)
+    eta = Array{Float64,4}(undef, 14, K, S, P); nud = similar(eta)
+    check(cache.ctx, ccall((:scvx_mc_draws_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Ref{McRng}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, rng, P, S, K, xi0, eta, xin, nud), "scvx_mc_draws_f64_host")
+    return xi0, eta, xin, nud
+end
+
+# on device pointers, asynchronous on the context's stream; C_NULL for an output not wanted
+mc_draws_dev!(cache::Cache, rng::McRng, P::Int, S::Int, K::Int, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble}, xin_dev::Ptr{Cdouble},
+              nud_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_mc_draws_f64, LIB), Cint,
+        (Ptr{Cvoid}, Ref{McRng}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, rng, P, S, K, xi0_dev, eta_dev, xin_dev, nud_dev), "scvx_mc_draws_f64")
+
+function track_mc_rng(b::Batch, C0::Array{Float64,3}, rng::McRng, S::Int; ranks::Vector{Cint}=Cint[], w=nothing, q=1.0, r=1.0, qf=100.0,
+                      nsub::Int=0, clamp::Bool=false, tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false)
+    NU = control_dim(b.cache); K = b.cache.problem.K; nq = length(ranks)
+    size(C0) == (14, 14, b.B) || throw(ArgumentError("C0 must be 14 x 14 x B"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    flightq, pathq, pv = _mc_q_outputs(b.B, S, K, nq, per_node && nq > 0, pathv)
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    GC.@preserve sw ranks check(b.cache.ctx, ccall((:scvx_batch_track_mc_rng, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ref{McRng}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, rng, sw === nothing ? 0 : 1, _cov_opt(sw), C_NULL, nsub,
+        clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), nq,
+        nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL, _cov_opt(pathq), _cov_opt(pv)), "scvx_batch_track_mc_rng")
+    return mcrep, xmean, xcov, flights, xland, dx0, (nq > 0 ? flightq : nothing), pathq, pv
+end
+
+function track_mc_rng(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, gain::Array{Float64,4},
+                      C0::Array{Float64,3}, rng::McRng, S::Int; ranks::Vector{Cint}=Cint[], w=nothing, nsub::Int=10, clamp::Bool=false,
+                      tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false)
+    B, K, nq = size(x, 3), size(x, 2) - 1, length(ranks)
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    flightq, pathq, pv = _mc_q_outputs(B, S, K, nq, per_node && nq > 0, pathv)
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    GC.@preserve sw ranks check(cache.ctx, ccall((:scvx_track_mc_rng_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{McRng}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, rng, sw === nothing ? 0 : 1, _cov_opt(sw), C_NULL, nsub, clamp ? TRACK_CLAMP : 0, tol,
+        mcrep, xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), nq, nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL,
+        _cov_opt(pathq), _cov_opt(pv)), "scvx_track_mc_rng_f64_host")
+    return mcrep, xmean, xcov, flights, xland, dx0, (nq > 0 ? flightq : nothing), pathq, pv
+end
+
+# on device pointers, asynchronous on the context's stream; sw = sqrt(w) and ranks stay host arrays; C_NULL for an output not wanted
+track_mc_rng_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                  gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, rng::McRng, sw::Union{Nothing,Vector{Float64}}, nsub::Int, flags::Int,
+                  tol::Float64, mcrep_dev::Ptr{Cdouble}, xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble}, flights_dev::Ptr{Cdouble},
+                  xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble}, ranks::Vector{Cint}, flightq_dev::Ptr{Cdouble},
+                  pathq_dev::Ptr{Cdouble}, pathv_dev::Ptr{Cdouble}) =
+    GC.@preserve sw ranks check(cache.ctx, ccall((:scvx_track_mc_rng_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{McRng}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, rng, sw === nothing ? 0 : 1, _cov_opt(sw), C_NULL, nsub, flags, tol,
+        mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, length(ranks), isempty(ranks) ? C_NULL : ranks, flightq_dev,
+        pathq_dev, pathv_dev), "scvx_track_mc_rng_f64")
+
+function track_mc_nav_rng(b::Batch, C0::Array{Float64,3}, N0::Array{Float64,3}, CN::Array{Float64,3}, H, rm, rng::McRng, S::Int;
+                          ranks::Vector{Cint}=Cint[], w=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false,
+                          tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false)
+    NU = control_dim(b.cache); K = b.cache.problem.K; nq = length(ranks)
+    (size(C0) == (14, 14, b.B) && size(N0) == (14, 14, b.B) && size(CN) == (14, 14, b.B)) ||
+        throw(ArgumentError("C0, N0, CN must be 14 x 14 x B"))
+    m, Hm, rmv = _nav_model(H, rm)
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(b.B, S, K, dense)
+    flightq, pathq, pv = _mc_q_outputs(b.B, S, K, nq, per_node && nq > 0, pathv)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv ranks check(b.cache.ctx, ccall((:scvx_batch_track_mc_nav_rng, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ref{McRng}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, rng, wv === nothing ? 0 : 1, _cov_opt(wv), N0, CN, m,
+        _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, _cov_opt(flights),
+        _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK), nq, nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL,
+        _cov_opt(pathq), _cov_opt(pv)), "scvx_batch_track_mc_nav_rng")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, (nq > 0 ? flightq : nothing), pathq, pv
+end
+
+function track_mc_nav_rng(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, deriv::Array{Float64,4},
+                          gain::Array{Float64,4}, C0::Array{Float64,3}, CN::Array{Float64,3}, H, rm, rng::McRng, S::Int;
+                          kf::Union{Nothing,Array{Float64,4}}=nothing, ranks::Vector{Cint}=Cint[], w=nothing, nsub::Int=10,
+                          clamp::Bool=false, tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false)
+    B, K, nq = size(x, 3), size(x, 2) - 1, length(ranks)
+    m, Hm, rmv = _nav_model(H, rm)
+    (m == 0 || (kf !== nothing && size(kf) == (m, 14, K, B))) ||
+        throw(ArgumentError("with measurements: kf m x 14 x K x B (navigation(...; dense=true))"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(B, S, K, dense)
+    flightq, pathq, pv = _mc_q_outputs(B, S, K, nq, per_node && nq > 0, pathv)
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    GC.@preserve wv Hm rmv ranks check(cache.ctx, ccall((:scvx_track_mc_nav_rng_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{McRng}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, rng, wv === nothing ? 0 : 1, _cov_opt(wv), deriv, _cov_opt(m > 0 ? kf : nothing), CN, m,
+        _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, _cov_opt(flights),
+        _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK), nq, nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL,
+        _cov_opt(pathq), _cov_opt(pv)), "scvx_track_mc_nav_rng_f64_host")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, (nq > 0 ? flightq : nothing), pathq, pv
+end
+
+# on device pointers, asynchronous on the context's stream; w (the VARIANCE), H, rm and ranks stay host arrays; C_NULL for an output not wanted
+track_mc_nav_rng_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                      gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, rng::McRng, w::Union{Nothing,Vector{Float64}},
+                      deriv_dev::Ptr{Cdouble}, kf_dev::Ptr{Cdouble}, CN_dev::Ptr{Cdouble}, m::Int, H::Union{Nothing,Matrix{Float64}},
+                      rm::Union{Nothing,Vector{Float64}}, nsub::Int, flags::Int, tol::Float64, mcrep_dev::Ptr{Cdouble},
+                      xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble}, jmean_dev::Ptr{Cdouble}, jcov_dev::Ptr{Cdouble},
+                      mcnav_dev::Ptr{Cdouble}, flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble},
+                      navfed_dev::Ptr{Cdouble}, navK_dev::Ptr{Cdouble}, ranks::Vector{Cint}, flightq_dev::Ptr{Cdouble},
+                      pathq_dev::Ptr{Cdouble}, pathv_dev::Ptr{Cdouble}) =
+    GC.@preserve w H rm ranks check(cache.ctx, ccall((:scvx_track_mc_nav_rng_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{McRng}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, rng, w === nothing ? 0 : 1, _cov_opt(w), deriv_dev, kf_dev, CN_dev,
+        m, _cov_opt(H), _cov_opt(rm), nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev, flights_dev,
+        xland_dev, dx0_dev, navfed_dev, navK_dev, length(ranks), isempty(ranks) ? C_NULL : ranks, flightq_dev, pathq_dev, pathv_dev),
+        "scvx_track_mc_nav_rng_f64")
+
 # ---- thrust-band back-offs and covariance-driven replanning (new) ----------------------------------------------------------
 # include/scvx.h, "thrust-band back-offs".  Tmin + lo[k, b] <= |u_k| <= Tmax - hi[k, b], read by the conic solve alone; the flight
 # check and the tracking calls keep auditing against the true Tmin / Tmax.  psig is 5 x (K+1) x B (row PSIG_* + 1 holds that column).

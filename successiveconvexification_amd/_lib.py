@@ -46,6 +46,11 @@ class ScvxThreedofOpts(C.Structure):
                 ("attitude", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ScvxMcRng(C.Structure):
+    """struct scvx_mc_rng (include/scvx.h): the stream of the draws the _rng forms of the sampled calls make on the device"""
+    _fields_ = [("seed", C.c_uint64), ("s_lo", C.c_uint64), ("b_lo", C.c_uint64), ("independent", C.c_int32), ("reserved", C.c_int32)]
+
+
 ABI_VERSION = 4   # SCVX_ABI_VERSION of the include/scvx.h these structs and signatures were written against
 
 # scvx_flight_check_*: modes and the columns of the report [B][FLIGHT_NREP] (the SCVX_FLIGHT_* macros of include/scvx.h)
@@ -84,6 +89,7 @@ MCNAV_COLUMNS = ("NAV_M", "NAV_R", "NAV_V", "NAV_Q", "NAV_W", "MAX_FED", "EST_R"
 MCNAV_INDEX = {n: i for i, n in enumerate(MCNAV_COLUMNS)}
 
 _vp = C.c_void_p
+_rp = C.POINTER(ScvxMcRng)
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
 SIGNATURES = {
     "scvx_abi_version": (C.c_int, []),
@@ -147,6 +153,24 @@ SIGNATURES = {
     "scvx_batch_track_mc_nav_q": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
                                             C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int,
                                             _ip, _dp, _dp, _dp]),
+    # the sampled calls with the draws made on the device: the _q lists with (xi0, eta) replaced by (rng, noise), (xin, nud) dropped
+    "scvx_mc_draws_f64": (C.c_int, [_vp, _rp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "scvx_mc_draws_f64_host": (C.c_int, [_vp, _rp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "scvx_track_mc_rng_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _rp, C.c_int, _dp, _vp, C.c_int, C.c_int,
+                                        C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _ip, _vp, _vp, _vp]),
+    "scvx_track_mc_rng_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _rp, C.c_int, _dp, _vp, C.c_int,
+                                             C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "scvx_track_mc_nav_rng_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _rp, C.c_int, _dp, _vp, _vp, _vp,
+                                            C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, C.c_int, _ip, _vp, _vp, _vp]),
+    "scvx_track_mc_nav_rng_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _rp, C.c_int, _dp, _dp, _dp, _dp,
+                                                 C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "scvx_batch_track_mc_rng": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _rp, C.c_int, _dp, _vp, C.c_int, C.c_int, C.c_double, _dp, _dp,
+                                          _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "scvx_batch_track_mc_nav_rng": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _rp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
+                                              C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _ip,
+                                              _dp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),

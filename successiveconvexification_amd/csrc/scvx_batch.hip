@@ -1035,10 +1035,11 @@ int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, con
                                  dx0, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
-int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                          const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
-                          double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
-                          const int* ranks, double* flightq, double* pathq, double* pathv) {
+// scvx_batch_track_mc_q and, with rg (then xi0 and eta are placeholders, nothing of them is uploaded), scvx_batch_track_mc_rng
+static int batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                            const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
+                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx::McRng* rg) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1048,7 +1049,9 @@ int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, c
     if ((rc = scvx::check_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->x, C0, xi0, eta, sw14, reserved, nsub, flags, tol, b->x,
                                    b->x, b->x)))
         return rc;
+    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
+    if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const size_t nc = (size_t)b->B * 196, ni = (size_t)S * 14, ne = (size_t)S * b->K * 14, nr = (size_t)b->B * SCVX_MC_NREP,
                  nm = (size_t)b->B * 14, nf = (size_t)b->B * S * SCVX_FLIGHT_NREP, nl = (size_t)b->B * S * 14,
@@ -1060,7 +1063,7 @@ int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, c
     if (e == hipSuccess && flightq) e = hipMalloc((void**)&dfq.p, nfq * 8);
     if (e == hipSuccess && pathq) e = hipMalloc((void**)&dpq.p, npq * 8);
     if (e == hipSuccess && pathv) e = hipMalloc((void**)&dpv.p, npv * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&di.p, ni * 8);
+    if (e == hipSuccess && xi0) e = hipMalloc((void**)&di.p, ni * 8);
     if (e == hipSuccess && eta) e = hipMalloc((void**)&de.p, ne * 8);
     if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
     if (e == hipSuccess) e = hipMalloc((void**)&dm.p, nm * 8);
@@ -1069,13 +1072,13 @@ int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, c
     if (e == hipSuccess && xland) e = hipMalloc((void**)&dl.p, nl * 8);
     if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, nl * 8);
     if (e == hipSuccess) e = hipMemcpyAsync(dc.p, C0, nc * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && xi0) e = hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && eta) e = hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st);
     scvx::McQ mq;
     mq.nq = nq, mq.ranks = ranks, mq.flightq = dfq.p, mq.pathq = dpq.p, mq.pathv = dpv.p;
     if (e == hipSuccess)
         e = scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p,
-                                  dm.p, dv.p, df.p, dl.p, d0.p, st, (flightq || pathq || pathv) ? &mq : nullptr);
+                                  dm.p, dv.p, df.p, dl.p, d0.p, st, (flightq || pathq || pathv) ? &mq : nullptr, rg);
     if (e == hipSuccess && flightq) e = hipMemcpyAsync(flightq, dfq.p, nfq * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && pathq) e = hipMemcpyAsync(pathq, dpq.p, npq * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && pathv) e = hipMemcpyAsync(pathv, dpv.p, npv * 8, hipMemcpyDeviceToHost, st);
@@ -1091,6 +1094,23 @@ int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, c
     return SCVX_OK;
 }
 
+int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                          const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                          double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
+                          const int* ranks, double* flightq, double* pathq, double* pathv) {
+    return batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland, dx0,
+                            nq, ranks, flightq, pathq, pathv, nullptr);
+}
+
+int scvx_batch_track_mc_rng(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                            const scvx_mc_rng* rng, int noise, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
+                            const int* ranks, double* flightq, double* pathq, double* pathv) {
+    const scvx::McRng rg{rng, noise};
+    return batch_track_mc_q(b, q14, rNU, qf14, S, C0, C0, noise ? C0 : nullptr, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
+                            flights, xland, dx0, nq, ranks, flightq, pathq, pathv, &rg);
+}
+
 int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
                             const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
                             const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags, double tol,
@@ -1100,12 +1120,13 @@ int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU,
                                      xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
-int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                              const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
-                              const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
-                              double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
-                              double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
-                              double* flightq, double* pathq, double* pathv) {
+// scvx_batch_track_mc_nav_q and, with rg (then xi0, eta, xin and nud are placeholders), scvx_batch_track_mc_nav_rng
+static int batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                                const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
+                                const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
+                                double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
+                                double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
+                                double* flightq, double* pathq, double* pathv, const scvx::McRng* rg) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1117,7 +1138,9 @@ int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rN
                                        nsub, flags, tol, b->x, b->x, b->x, b->x, b->x, b->x)))
         return rc;
     if (!N0) return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (N0)");
+    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
+    if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const int B = b->B, K = b->K;
     const size_t nc = (size_t)B * 196, ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
@@ -1132,9 +1155,12 @@ int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rN
         if (e == hipSuccess) e = hipMalloc((void**)&d.p, n * 8);
         if (e == hipSuccess && h) e = hipMemcpyAsync(d.p, h, n * 8, hipMemcpyHostToDevice, st);
     };
-    in(dc, C0, nc), in(di, xi0, ni), in(dn0, N0, nc), in(dcn, CN, nc), in(dxi, xin, ni);
+    in(dc, C0, nc), in(dn0, N0, nc), in(dcn, CN, nc);
+    if (xi0) in(di, xi0, ni);
+    if (xin) in(dxi, xin, ni);
     if (eta) in(de, eta, ne);
-    if (m > 0) in(dnu, nud, nn), in(dk, nullptr, nk);
+    if (m > 0 && nud) in(dnu, nud, nn);
+    if (m > 0) in(dk, nullptr, nk);
     in(dz, nullptr, nc), in(dcr, nullptr, (size_t)B * SCVX_COV_NREP), in(dnr, nullptr, (size_t)B * SCVX_NAV_NREP);
     in(dr, nullptr, nr), in(dm, nullptr, nm), in(dv, nullptr, nc), in(djm, nullptr, (size_t)B * 28), in(djc, nullptr, (size_t)B * 784);
     in(dnv, nullptr, (size_t)B * SCVX_NAV_NREP);
@@ -1159,10 +1185,10 @@ int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rN
     if (e == hipSuccess)
         e = b->deriv_f ? scvx::launch_track_mc_nav_f32(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv_f,
                                                        dk.p, dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p,
-                                                       dnv.p, df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp)
+                                                       dnv.p, df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp, rg)
                        : scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv, dk.p,
                                                    dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p,
-                                                   df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp);
+                                                   df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp, rg);
     auto out = [&](double* h, scvx::DevBuf<double>& d, size_t n) {
         if (e == hipSuccess && h) e = hipMemcpyAsync(h, d.p, n * 8, hipMemcpyDeviceToHost, st);
     };
@@ -1173,6 +1199,26 @@ int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rN
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_nav_q: ") + hipGetErrorString(e));
     return SCVX_OK;
+}
+
+int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                              const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
+                              const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
+                              double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
+                              double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
+                              double* flightq, double* pathq, double* pathv) {
+    return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean, xcov,
+                                jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv, nullptr);
+}
+
+int scvx_batch_track_mc_nav_rng(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                                const scvx_mc_rng* rng, int noise, const double* w14, const double* N0, const double* CN, int m,
+                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                                double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
+    const scvx::McRng rg{rng, noise};
+    return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, C0, noise ? C0 : nullptr, w14, N0, CN, C0, C0, m, H, rm, nsub, flags, tol, mcrep,
+                                xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv, &rg);
 }
 
 int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,

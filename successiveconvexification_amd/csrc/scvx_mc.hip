@@ -23,20 +23,26 @@
 // the parent's registers, LDS and scratch (profiles/mc_quantiles.md) and are what the entry points without the _q launch.  The _q forms
 // (scvx_track_mc_q_f64, include/scvx.h) follow the flight with order statistics of the flight columns and of the rows of pathv; flights
 // and pathv live in a second workspace of the context when only their order statistics are asked for.
+//
+// RNG (the last template parameter): the loads of the draws xi0 and eta become calls of mc_draw_group (scvx_rng.hpp) -- every lane makes
+// its own from Philox4x64-10, the four blocks of a group formed at the node and dead after it; everything else is statement for
+// statement, so a flight is bitwise the flight of the RNG-off kernel fed the draws mc_draws_kernel dumps (tests/test_gpu_mc_rng.py).
+// With RNG off the instantiations keep the parent's registers, LDS and scratch (profiles/mc_rng.md) and are what every entry point
+// without _rng launches.
 #include <cmath>
 #include <limits>
-#include "scvx_mc.hpp"   // the partial row, McK and the wavefront reductions, shared with scvx_mc_nav.hip
+#include "scvx_mc.hpp"   // the partial row, McK, the wavefront reductions and the draws made on the device, shared with scvx_mc_nav.hip
 
 namespace scvx {
 
-template <bool AERO, bool FIN, bool TRQ, bool PV>
+template <bool AERO, bool FIN, bool TRQ, bool PV, bool RNG>
 __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK c, McK m, int S, int K, const double* __restrict__ x,
                                                     const double* __restrict__ u, const double* __restrict__ sigma,
                                                     const double* __restrict__ gain, const double* __restrict__ C0,
                                                     const double* __restrict__ xi0, const double* __restrict__ eta, double dt, int nsub,
                                                     int opt, double* __restrict__ part, double* __restrict__ flights,
                                                     double* __restrict__ xland, double* __restrict__ dx0o,
-                                                    double* __restrict__ pathv) {
+                                                    double* __restrict__ pathv, McRngK rg) {
     typedef double R;
     const int b = blockIdx.y;
     const int sl = blockIdx.x * 64 + threadIdx.x;
@@ -48,8 +54,9 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
     const R* ub = u + (size_t)b * (K + 1) * NU;
     const R* gb = gain + (size_t)b * K * NU * n;
     const R* cb = C0 + (size_t)b * 196;
-    const R* xi = xi0 + (size_t)s_ * 14;
-    const R* et = eta ? eta + (size_t)s_ * K * 14 : nullptr;
+    const R* xi = RNG ? nullptr : xi0 + (size_t)s_ * 14;
+    const R* et = (!RNG && eta) ? eta + (size_t)s_ * K * 14 : nullptr;
+    const uint64_t rc2 = RNG ? mc_rng_c2(rg, b) : 0, rc3 = RNG ? mc_rng_c3(rg, s_) : 0;   // RNG: the flight's stream, scvx_rng.hpp
     const size_t fl = (size_t)b * S + s_;
     const R sig = sigma[b];
     const R h = dt / R(nsub);
@@ -59,9 +66,13 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
     R xs[14], ukv[NU], upv[NU];
     // ---- the start: dx0 = C0 xi0, summed with fma in ascending j ----
     {
-        R xv[14];
+        R xv[16];
+        if (RNG) {
+            mc_draw_group(rg.seed, MC_STREAM_TRUTH, rc2, rc3, 0, 14, xv);
+        } else {
 #pragma unroll
-        for (int j = 0; j < 14; j++) xv[j] = xi[j];
+            for (int j = 0; j < 14; j++) xv[j] = xi[j];
+        }
 #pragma unroll
         for (int i = 0; i < 14; i++) {
             R a = R(0.0);
@@ -173,7 +184,14 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
             for (int i = 0; i < 14; i++) xs[i] = xa[i];
         }
         // ---- the impulse of segment k: after its last sample, before node k + 1's gap, dense row and feedback ----
-        if (et) {
+        if (RNG) {
+            if (rg.noise) {
+                R ev[16];   // group 1 + k, formed here and dead after the impulse
+                mc_draw_group(rg.seed, MC_STREAM_TRUTH, rc2, rc3, 1 + k, 14, ev);
+#pragma unroll
+                for (int i = 0; i < 14; i++) xs[i] = fma(m.sw[i], ev[i], xs[i]);
+            }
+        } else if (et) {
 #pragma unroll
             for (int i = 0; i < 14; i++) xs[i] = fma(m.sw[i], et[(size_t)k * 14 + i], xs[i]);
         }
@@ -274,6 +292,35 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
     }
 }
 
+// The draws the RNG instantiations consume, written out (scvx_mc_draws_f64): one lane per (plan, s), grid (ceil(S / 64), P); xi0 / xin
+// [P][S][14], eta / nud [P][S][K][14] (all 14 columns of a group: nud[.., 0:m] is what a call with m rows reads), each or nullptr.
+__global__ __launch_bounds__(64) void mc_draws_kernel(McRngK rg, int S, int K, double* __restrict__ xi0, double* __restrict__ eta,
+                                                      double* __restrict__ xin, double* __restrict__ nud) {
+    const int p = blockIdx.y;
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= S) return;
+    const uint64_t rc2 = mc_rng_c2(rg, p), rc3 = mc_rng_c3(rg, s);
+    const size_t fl = (size_t)p * S + s;
+    for (int st = 0; st < 2; st++) {
+        double* z0 = st == 0 ? xi0 : xin;
+        double* zk = st == 0 ? eta : nud;
+        const uint64_t c1 = st == 0 ? MC_STREAM_TRUTH : MC_STREAM_NAV;
+        if (z0) {
+            double z[16];
+            mc_draw_group(rg.seed, c1, rc2, rc3, 0, 14, z);
+#pragma unroll
+            for (int i = 0; i < 14; i++) z0[fl * 14 + i] = z[i];
+        }
+        if (zk)
+            for (int k = 0; k < K; k++) {
+                double z[16];
+                mc_draw_group(rg.seed, c1, rc2, rc3, 1 + k, 14, z);
+#pragma unroll
+                for (int i = 0; i < 14; i++) zk[(fl * K + k) * 14 + i] = z[i];
+            }
+    }
+}
+
 // one block per plan: the partial rows of the plan combined in block order, then the report, the mean and the covariance
 __global__ __launch_bounds__(256) void mc_finish_kernel(int S, int K, int nblk, const double* __restrict__ part,
                                                         double* __restrict__ mcrep, double* __restrict__ xmean,
@@ -369,6 +416,14 @@ hipError_t mc_q_finish(int B, int K, int S, const McQ& q, const double* flights,
     return e;
 }
 
+int check_mc_rng(scvx_ctx* ctx, const scvx_mc_rng* rng) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (!rng) return fail(ctx, SCVX_ERR_ARG, "mc rng: null rng");
+    if (rng->reserved != 0) return fail(ctx, SCVX_ERR_ARG, "mc rng: reserved must be 0");
+    if (rng->independent != 0 && rng->independent != 1) return fail(ctx, SCVX_ERR_ARG, "mc rng: independent must be 0 or 1");
+    return SCVX_OK;
+}
+
 int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq) {
     if (nq == 0 && !flightq && !pathq) return SCVX_OK;   // nothing asked for: the call it extends
     return check_ranks(ctx, S, nq, ranks);
@@ -377,7 +432,7 @@ int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* fligh
 hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
-                           const McQ* q) {
+                           const McQ* q, const McRng* rng) {
     const PathK c = path_constants(ctx->prob);
     const double dt = 1.0 / (K + 1);
     const int nblk = (S + 63) / 64;
@@ -388,18 +443,24 @@ hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, 
     McK m{};
     m.tol = tol;
     bool noise = false;
-    if (eta && sw)
+    if ((rng ? rng->noise != 0 : eta != nullptr) && sw)
         for (int i = 0; i < 14; i++) {
             m.sw[i] = sw[i];
             noise = noise || sw[i] > 0.0;
         }
     if (!noise) eta = nullptr;   // sw all zero: the undisturbed kernel path, bit for bit
+    const McRngK rg = rng ? mc_rng_k(*rng, noise) : McRngK{};
     const dim3 g((unsigned)nblk, (unsigned)B), blk(64);
     double* part = ctx->mc_ws;
     const DynP<double> dp(ctx->dyn);
-#define SCVX_MC_PV(A, F, T, P, par)                                                                                                       \
-    hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P>), g, blk, 0, st, par, c, m, S, K, x, u, sigma, gain, C0, xi0, eta, dt, nsub, flags, part, \
-                       flights, xland, dx0, pv)
+#define SCVX_MC_RG(A, F, T, P, G, par)                                                                                                       \
+    hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G>), g, blk, 0, st, par, c, m, S, K, x, u, sigma, gain, C0, xi0, eta, dt, nsub, flags, part, \
+                       flights, xland, dx0, pv, rg)
+#define SCVX_MC_PV(A, F, T, P, par)                 \
+    do {                                            \
+        if (rng) SCVX_MC_RG(A, F, T, P, true, par); \
+        else SCVX_MC_RG(A, F, T, P, false, par);    \
+    } while (0)
 #define SCVX_MC(A, F, T, par)                  \
     do {                                       \
         if (pv) SCVX_MC_PV(A, F, T, true, par); \
@@ -418,6 +479,7 @@ hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, 
         SCVX_MC(false, false, false, dp);
 #undef SCVX_MC
 #undef SCVX_MC_PV
+#undef SCVX_MC_RG
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mc_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov);
@@ -447,26 +509,113 @@ int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void
     return SCVX_OK;
 }
 
+// scvx_track_mc_q_f64 and, with rg (then xi0_dev and eta_dev are placeholders that are never read), scvx_track_mc_rng_f64
+static int track_mc_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                          const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
+                          const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
+                          double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
+                          double* pathq_dev, double* pathv_dev, const McRng* rg) {
+    int rc = scvx::check_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags,
+                                  tol, mcrep_dev, xmean_dev, xcov_dev);
+    if (rc) return rc;
+    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
+    scvx::McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
+    const bool any = flightq_dev || pathq_dev || pathv_dev;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, rg ? nullptr : xi0_dev,
+                                        rg ? nullptr : eta_dev, sw14, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, flights_dev,
+                                        xland_dev, dx0_dev, ctx->stream, any ? &q : nullptr, rg));
+    return SCVX_OK;
+}
+
+// scvx_track_mc_q_f64_host and, with rg (xi0 and eta placeholders, nothing of them uploaded), scvx_track_mc_rng_f64_host
+static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
+                           const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
+                           int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0,
+                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg);
+
+// one lane per (plan, s): the draws the _rng forms consume (mc_draws_kernel); any of the four outputs may be nullptr
+hipError_t launch_mc_draws(const scvx_mc_rng& r, int P, int S, int K, double* xi0, double* eta, double* xin, double* nud, hipStream_t st) {
+    const McRng g{&r, 0};
+    hipLaunchKernelGGL(mc_draws_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)P), dim3(64), 0, st, mc_rng_k(g, false), S, K, xi0, eta,
+                       xin, nud);
+    return hipGetLastError();
+}
+
+int check_mc_draws(scvx_ctx* ctx, const scvx_mc_rng* rng, int P, int S, int K) {
+    int rc = check_mc_rng(ctx, rng);
+    if (rc) return rc;
+    if (P < 1 || P > 65535) return fail(ctx, SCVX_ERR_ARG, "mc draws: 1 <= P <= 65535 required");
+    if (S < 1) return fail(ctx, SCVX_ERR_ARG, "mc draws: S >= 1 required");
+    if (K < 1) return fail(ctx, SCVX_ERR_ARG, "mc draws: K >= 1 required");
+    return SCVX_OK;
+}
+
 }  // namespace scvx
 
 extern "C" {
+
+int scvx_mc_draws_f64(scvx_ctx* ctx, const scvx_mc_rng* rng, int P, int S, int K, double* xi0_dev, double* eta_dev, double* xin_dev,
+                      double* nud_dev) {
+    int rc = scvx::check_mc_draws(ctx, rng, P, S, K);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_mc_draws(*rng, P, S, K, xi0_dev, eta_dev, xin_dev, nud_dev, ctx->stream));
+    return SCVX_OK;
+}
+
+int scvx_mc_draws_f64_host(scvx_ctx* ctx, const scvx_mc_rng* rng, int P, int S, int K, double* xi0, double* eta, double* xin, double* nud) {
+    int rc = scvx::check_mc_draws(ctx, rng, P, S, K);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n0 = (size_t)P * S * 14, nk = n0 * K;
+    scvx::DevBuf<double> d0, d1, d2, d3;
+    if (xi0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
+    if (eta) SCVX_HIP(ctx, hipMalloc((void**)&d1.p, nk * 8));
+    if (xin) SCVX_HIP(ctx, hipMalloc((void**)&d2.p, n0 * 8));
+    if (nud) SCVX_HIP(ctx, hipMalloc((void**)&d3.p, nk * 8));
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, scvx::launch_mc_draws(*rng, P, S, K, d0.p, d1.p, d2.p, d3.p, st));
+    if (xi0) SCVX_HIP(ctx, hipMemcpyAsync(xi0, d0.p, n0 * 8, hipMemcpyDeviceToHost, st));
+    if (eta) SCVX_HIP(ctx, hipMemcpyAsync(eta, d1.p, nk * 8, hipMemcpyDeviceToHost, st));
+    if (xin) SCVX_HIP(ctx, hipMemcpyAsync(xin, d2.p, n0 * 8, hipMemcpyDeviceToHost, st));
+    if (nud) SCVX_HIP(ctx, hipMemcpyAsync(nud, d3.p, nk * 8, hipMemcpyDeviceToHost, st));
+    SCVX_HIP(ctx, hipStreamSynchronize(st));
+    return SCVX_OK;
+}
 
 int scvx_track_mc_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                         const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
                         const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
                         double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
                         double* pathq_dev, double* pathv_dev) {
-    int rc = scvx::check_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags,
-                                  tol, mcrep_dev, xmean_dev, xcov_dev);
-    if (rc) return rc;
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
-    scvx::McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
-    const bool any = flightq_dev || pathq_dev || pathv_dev;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, nsub, flags, tol,
-                                        mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, ctx->stream, any ? &q : nullptr));
-    return SCVX_OK;
+    return scvx::track_mc_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags, tol,
+                                mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, nq, ranks, flightq_dev, pathq_dev,
+                                pathv_dev, nullptr);
+}
+
+// the placeholders: xi0 any non-null pointer, eta non-null exactly when the truth receives impulses (check_track_mc's rules for them)
+int scvx_track_mc_rng_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                          const double* gain_dev, const double* C0_dev, const scvx_mc_rng* rng, int noise, const double* sw14,
+                          const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
+                          double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
+                          double* pathq_dev, double* pathv_dev) {
+    const scvx::McRng rg{rng, noise};
+    return scvx::track_mc_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, x_dev, noise ? x_dev : nullptr, sw14, reserved,
+                                nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, nq, ranks, flightq_dev,
+                                pathq_dev, pathv_dev, &rg);
+}
+
+int scvx_track_mc_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const scvx_mc_rng* rng, int noise, const double* sw14,
+                               const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                               double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
+                               double* pathv) {
+    const scvx::McRng rg{rng, noise};
+    return scvx::track_mc_q_host(ctx, B, K, S, x, u, sigma, gain, C0, x, noise ? x : nullptr, sw14, reserved, nsub, flags, tol, mcrep,
+                                 xmean, xcov, flights, xland, dx0, nq, ranks, flightq, pathq, pathv, &rg);
 }
 
 int scvx_track_mc_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
@@ -490,8 +639,22 @@ int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x
                              const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
                              double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
                              double* pathv) {
+    return scvx::track_mc_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
+                                 flights, xland, dx0, nq, ranks, flightq, pathq, pathv, nullptr);
+}
+
+}  // extern "C"
+
+namespace scvx {
+
+static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
+                           const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
+                           int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0,
+                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg) {
     int rc = scvx::check_track_mc(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov);
     if (rc) return rc;
+    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
+    if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
@@ -513,7 +676,7 @@ int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x
     SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nc * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&di.p, ni * 8));
+    if (xi0) SCVX_HIP(ctx, hipMalloc((void**)&di.p, ni * 8));
     if (eta) SCVX_HIP(ctx, hipMalloc((void**)&de.p, ne * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
     SCVX_HIP(ctx, hipMalloc((void**)&dm.p, nm * 8));
@@ -527,10 +690,10 @@ int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x
     SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
     SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
     SCVX_HIP(ctx, hipMemcpyAsync(dc.p, C0, nc * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st));
+    if (xi0) SCVX_HIP(ctx, hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st));
     if (eta) SCVX_HIP(ctx, hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st));
     SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, dx.p, du.p, ds.p, dg.p, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p, dm.p, dv.p,
-                                        df.p, dl.p, d0.p, st, any ? &q : nullptr));
+                                        df.p, dl.p, d0.p, st, any ? &q : nullptr, rg));
     if (flightq) SCVX_HIP(ctx, hipMemcpyAsync(flightq, dfq.p, nfq * 8, hipMemcpyDeviceToHost, st));
     if (pathq) SCVX_HIP(ctx, hipMemcpyAsync(pathq, dpq.p, npq * 8, hipMemcpyDeviceToHost, st));
     if (pathv) SCVX_HIP(ctx, hipMemcpyAsync(pathv, dpv.p, npv * 8, hipMemcpyDeviceToHost, st));
@@ -544,4 +707,4 @@ int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x
     return SCVX_OK;
 }
 
-}  // extern "C"
+}  // namespace scvx

@@ -2,6 +2,7 @@
 // the kernel-argument constants and the wavefront reductions.  Not part of the ABI.
 #pragma once
 #include "scvx_internal.hpp"
+#include "scvx_rng.hpp"
 
 namespace scvx {
 
@@ -52,6 +53,16 @@ struct McQ {
     const int* ranks = nullptr;
     double *flightq = nullptr, *pathq = nullptr, *pathv = nullptr;
 };
+// The _rng forms: the draws are made by the lanes (scvx_rng.hpp) and the pointers xi0 / eta / xin / nud of the launch are not read;
+// noise: whether the truth receives the impulses sqrt(w) eta (the role of eta != nullptr in the calls on uploaded draws).
+struct McRng {
+    const scvx_mc_rng* r = nullptr;
+    int noise = 0;
+};
+inline McRngK mc_rng_k(const McRng& g, bool noise) {
+    return McRngK{g.r->seed, g.r->s_lo, g.r->b_lo, g.r->independent, noise ? 1 : 0};
+}
+int check_mc_rng(scvx_ctx* ctx, const scvx_mc_rng* rng);
 int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq);
 int check_ranks(scvx_ctx* ctx, int S, int nq, const int* ranks);
 // rows: row r starts at v[(r / inner) * ld_outer + (r % inner) * ld_inner], its S values inc apart; out [R][nq]

@@ -24,6 +24,11 @@
 // mc_nav_finish_kernel (one block per plan) combining the blocks in order.  The row is mc_fly_kernel's, then the sums of eps_K [14] and
 // of the upper triangle of [e; eps_K][e; eps_K]' [406], and the largest |eps+_k|_inf fed.  The 14 x 14 corner of the triangle is written
 // to MC_EE as well and every landing statistic is formed by one expression, so xcov is bitwise jcov[:, :14, :14].
+//
+// RNG (the last template parameter, as in scvx_mc.hip): the four loads of draws become calls of mc_draw_group (scvx_rng.hpp).  eta_k is
+// formed once, at the error's time step, and rests in LDS (a column per lane, 7 KB per block) until the truth's impulse behind the
+// segment; of nud_k only the blocks that hold its first m draws are formed.  With RNG off the instantiations keep the parent's registers,
+// LDS and scratch (profiles/mc_rng.md).
 #include <cmath>
 #include <limits>
 #include "scvx_mc.hpp"
@@ -46,7 +51,7 @@ __global__ __launch_bounds__(256) void mc_nav_model_kernel(McNavK nv, double* __
 // square root of a variance (a rounded variance of -1e-40 is 0, a NaN stays a NaN)
 __device__ __forceinline__ double mcn_sd(double v) { return v > 0.0 ? sqrt(v) : (v != v ? v : 0.0); }
 
-template <bool AERO, bool FIN, bool TRQ, typename DS, bool PV>
+template <bool AERO, bool FIN, bool TRQ, typename DS, bool PV, bool RNG>
 __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, PathK c, McK m, int mm, const double* __restrict__ hm, int S, int K,
                                                         const double* __restrict__ x, const double* __restrict__ u,
                                                         const double* __restrict__ sigma, const double* __restrict__ gain,
@@ -57,11 +62,12 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
                                                         int nsub, int opt, double* __restrict__ part, double* __restrict__ flights,
                                                         double* __restrict__ xland, double* __restrict__ dx0o,
                                                         double* __restrict__ navfed, double* __restrict__ navK,
-                                                        double* __restrict__ pathv) {
+                                                        double* __restrict__ pathv, McRngK rg) {
     // hm: H [m][14] then sqrt(rm) at MCN_SRM, in the workspace behind the partial rows
     typedef double R;
     __shared__ R epl[14][64];   // eps rests here while the segment is integrated: one column per lane, no lane reads another's
     __shared__ R Al[196], Kl[196], Hl[MCN_MODEL];   // A_k, Kf_k and the model: written by the wave, read by every lane at one address
+    __shared__ R etl[RNG ? 14 : 1][64];   // RNG: eta_k rests here between the error's time step and the truth's impulse, a column per lane
     const int ln = threadIdx.x;
     const int b = blockIdx.y;
     const int sl = blockIdx.x * 64 + threadIdx.x;
@@ -77,10 +83,11 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
     const R* cnb = CN + (size_t)b * 196;
     const DS* tb = deriv + (size_t)b * K * DSZ;
     const R* kb = mm > 0 ? kf + (size_t)b * K * 14 * mm : nullptr;
-    const R* xi = xi0 + (size_t)s_ * 14;
-    const R* et = eta ? eta + (size_t)s_ * K * 14 : nullptr;
-    const R* xn_ = xin + (size_t)s_ * 14;
-    const R* nd = mm > 0 ? nud + (size_t)s_ * K * mm : nullptr;
+    const R* xi = RNG ? nullptr : xi0 + (size_t)s_ * 14;
+    const R* et = (!RNG && eta) ? eta + (size_t)s_ * K * 14 : nullptr;
+    const R* xn_ = RNG ? nullptr : xin + (size_t)s_ * 14;
+    const R* nd = (!RNG && mm > 0) ? nud + (size_t)s_ * K * mm : nullptr;
+    const uint64_t rc2 = RNG ? mc_rng_c2(rg, b) : 0, rc3 = RNG ? mc_rng_c3(rg, s_) : 0;   // RNG: the flight's streams, scvx_rng.hpp
     const size_t fl = (size_t)b * S + s_;
     const R sig = sigma[b];
     const R h = dt / R(nsub);
@@ -90,9 +97,13 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
     R xs[14], ukv[NU], upv[NU], eps[14];
     // ---- the start: dx0 = C0 xi0 and eps_0 = CN xin, summed with fma in ascending j ----
     {
-        R xv[14];
+        R xv[16];
+        if (RNG) {
+            mc_draw_group(rg.seed, MC_STREAM_TRUTH, rc2, rc3, 0, 14, xv);
+        } else {
 #pragma unroll
-        for (int j = 0; j < 14; j++) xv[j] = xi[j];
+            for (int j = 0; j < 14; j++) xv[j] = xi[j];
+        }
 #pragma unroll
         for (int i = 0; i < 14; i++) {
             R a = R(0.0);
@@ -101,8 +112,12 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
             if (dx0o && live) dx0o[fl * 14 + i] = a;
             xs[i] = a;
         }
+        if (RNG) {
+            mc_draw_group(rg.seed, MC_STREAM_NAV, rc2, rc3, 0, 14, xv);
+        } else {
 #pragma unroll
-        for (int j = 0; j < 14; j++) xv[j] = xn_[j];
+            for (int j = 0; j < 14; j++) xv[j] = xn_[j];
+        }
 #pragma unroll
         for (int i = 0; i < 14; i++) {
             R a = R(0.0);
@@ -155,11 +170,13 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
         // ---- node k: the measurement update of the estimate's error, eps+ = eps - Kf (H eps + sqrt(rm) nud) ----
         if (mm > 0) {
             R inn[14];
+            R zn[16];   // RNG: nud_k, the first mm draws of group 1 + k of the navigation stream
+            if (RNG) mc_draw_group(rg.seed, MC_STREAM_NAV, rc2, rc3, 1 + k, mm, zn);
 #pragma unroll
             for (int r = 0; r < 14; r++) {
                 inn[r] = R(0.0);
                 if (r < mm) {
-                    R a = Hl[MCN_SRM + r] * nd[(size_t)k * mm + r];
+                    R a = Hl[MCN_SRM + r] * (RNG ? zn[r] : nd[(size_t)k * mm + r]);
 #pragma unroll
                     for (int j = 0; j < 14; j++) a = fma(Hl[r * 14 + j], eps[j], a);
                     inn[r] = a;
@@ -223,12 +240,20 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
             R ep[14];
 #pragma unroll
             for (int i = 0; i < 14; i++) ep[i] = eps[i];
+            R ev[16];   // RNG: eta_k, group 1 + k of the truth's stream, formed here once
+            if (RNG && rg.noise) {
+                mc_draw_group(rg.seed, MC_STREAM_TRUTH, rc2, rc3, 1 + k, 14, ev);
+#pragma unroll
+                for (int i = 0; i < 14; i++) etl[i][ln] = ev[i];
+            }
 #pragma unroll
             for (int i = 0; i < 14; i++) {
                 R a = R(0.0);
 #pragma unroll
                 for (int j = 0; j < 14; j++) a = fma(Al[j * 14 + i], ep[j], a);
-                if (et) a = fma(m.sw[i], et[(size_t)k * 14 + i], a);
+                if (RNG) {
+                    if (rg.noise) a = fma(m.sw[i], ev[i], a);
+                } else if (et) a = fma(m.sw[i], et[(size_t)k * 14 + i], a);
                 epl[i][ln] = a;
                 bad = fma(a, R(0.0), bad);
             }
@@ -292,7 +317,12 @@ __global__ __launch_bounds__(64) void mc_nav_fly_kernel(DynPK<double, TRQ> p, Pa
             for (int i = 0; i < 14; i++) xs[i] = xa[i];
         }
         // ---- the impulse of segment k: after its last sample, before node k + 1's gap, dense row and feedback ----
-        if (et) {
+        if (RNG) {
+            if (rg.noise) {
+#pragma unroll
+                for (int i = 0; i < 14; i++) xs[i] = fma(m.sw[i], etl[i][ln], xs[i]);
+            }
+        } else if (et) {
 #pragma unroll
             for (int i = 0; i < 14; i++) xs[i] = fma(m.sw[i], et[(size_t)k * 14 + i], xs[i]);
         }
@@ -493,7 +523,7 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
                                         const DS* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int mm,
                                         const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                         double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland,
-                                        double* dx0, double* navfed, double* navK, hipStream_t st, const McQ* q) {
+                                        double* dx0, double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
     const PathK c = path_constants(ctx->prob);
     const double dt = 1.0 / (K + 1);
     const int nblk = (S + 63) / 64;
@@ -505,12 +535,13 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
     McK m{};
     m.tol = tol;
     bool noise = false;
-    if (eta && w)
+    if ((rng ? rng->noise != 0 : eta != nullptr) && w)
         for (int i = 0; i < 14; i++) {
             m.sw[i] = std::sqrt(w[i]);
             noise = noise || w[i] > 0.0;
         }
     if (!noise) eta = nullptr;   // w all zero: the undisturbed kernel path, bit for bit
+    const McRngK rg = rng ? mc_rng_k(*rng, noise) : McRngK{};
     McNavK nv{};
     for (int i = 0; i < mm; i++) nv.srm[i] = std::sqrt(rm[i]);
     for (int i = 0; i < mm * 14; i++) nv.H[i] = H[i];
@@ -521,9 +552,14 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const DynP<double> dp(ctx->dyn);
-#define SCVX_MCN_PV(A, F, T, P, par)                                                                                                          \
-    hipLaunchKernelGGL((mc_nav_fly_kernel<A, F, T, DS, P>), g, blk, 0, st, par, c, m, mm, hm, S, K, x, u, sigma, gain, C0, xi0, eta, deriv, kf, \
-                       CN, xin, nud, dt, nsub, flags, part, flights, xland, dx0, navfed, navK, pv)
+#define SCVX_MCN_RG(A, F, T, P, G, par)                                                                                                          \
+    hipLaunchKernelGGL((mc_nav_fly_kernel<A, F, T, DS, P, G>), g, blk, 0, st, par, c, m, mm, hm, S, K, x, u, sigma, gain, C0, xi0, eta, deriv, kf, \
+                       CN, xin, nud, dt, nsub, flags, part, flights, xland, dx0, navfed, navK, pv, rg)
+#define SCVX_MCN_PV(A, F, T, P, par)                 \
+    do {                                             \
+        if (rng) SCVX_MCN_RG(A, F, T, P, true, par); \
+        else SCVX_MCN_RG(A, F, T, P, false, par);    \
+    } while (0)
 #define SCVX_MCN(A, F, T, par)                  \
     do {                                        \
         if (pv) SCVX_MCN_PV(A, F, T, true, par); \
@@ -542,6 +578,7 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
         SCVX_MCN(false, false, false, dp);
 #undef SCVX_MCN
 #undef SCVX_MCN_PV
+#undef SCVX_MCN_RG
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mc_nav_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov, jmean, jcov, mcnav);
@@ -555,9 +592,9 @@ hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, hipStream_t st, const McQ* q) {
+                               double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
     return launch_track_mc_nav_t<double>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                         tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q);
+                                         tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q, rng);
 }
 
 hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
@@ -565,9 +602,9 @@ hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const dou
                                    const float* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
                                    const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                    double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                                   double* navfed, double* navK, hipStream_t st, const McQ* q) {
+                                   double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
     return launch_track_mc_nav_t<float>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q);
+                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q, rng);
 }
 
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
@@ -590,6 +627,41 @@ int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const 
     return SCVX_OK;
 }
 
+// scvx_track_mc_nav_q_f64 and, with rg (then xi0, eta, xin and nud are placeholders that are never read), scvx_track_mc_nav_rng_f64
+static int track_mc_nav_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                              const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
+                              const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
+                              const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
+                              double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
+                              double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
+                              double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev,
+                              const McRng* rg) {
+    int rc = scvx::check_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
+                                      CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
+                                      jcov_dev, mcnav_dev);
+    if (rc) return rc;
+    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
+    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
+    if (rg) xi0_dev = eta_dev = xin_dev = nud_dev = nullptr;   // placeholders until here: the lanes make the draws
+    scvx::McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
+    const bool any = flightq_dev || pathq_dev || pathv_dev;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev,
+                                            kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev,
+                                            jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev,
+                                            ctx->stream, any ? &q : nullptr, rg));
+    return SCVX_OK;
+}
+
+static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
+                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                               double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
+                               const McRng* rg);
+
 }  // namespace scvx
 
 extern "C" {
@@ -601,20 +673,38 @@ int scvx_track_mc_nav_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_
                             double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
                             double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
                             double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev) {
-    int rc = scvx::check_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
-                                      CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
-                                      jcov_dev, mcnav_dev);
-    if (rc) return rc;
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
-    scvx::McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
-    const bool any = flightq_dev || pathq_dev || pathv_dev;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev,
-                                            kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev,
-                                            jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev,
-                                            ctx->stream, any ? &q : nullptr));
-    return SCVX_OK;
+    return scvx::track_mc_nav_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
+                                    CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
+                                    jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, nq, ranks, flightq_dev,
+                                    pathq_dev, pathv_dev, nullptr);
+}
+
+// the placeholders: xi0, xin and (with m > 0) nud any non-null pointer, eta non-null exactly when the truth receives impulses
+// (check_track_mc_nav's rules for them)
+int scvx_track_mc_nav_rng_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                              const double* gain_dev, const double* C0_dev, const scvx_mc_rng* rng, int noise, const double* w14,
+                              const double* deriv_dev, const double* kf_dev, const double* CN_dev, int m, const double* H,
+                              const double* rm, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev,
+                              double* xcov_dev, double* jmean_dev, double* jcov_dev, double* mcnav_dev, double* flights_dev,
+                              double* xland_dev, double* dx0_dev, double* navfed_dev, double* navK_dev, int nq, const int* ranks,
+                              double* flightq_dev, double* pathq_dev, double* pathv_dev) {
+    const scvx::McRng rg{rng, noise};
+    return scvx::track_mc_nav_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, x_dev, noise ? x_dev : nullptr, w14, deriv_dev,
+                                    kf_dev, CN_dev, x_dev, x_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
+                                    jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, nq, ranks, flightq_dev,
+                                    pathq_dev, pathv_dev, &rg);
+}
+
+int scvx_track_mc_nav_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                                   const double* gain, const double* C0, const scvx_mc_rng* rng, int noise, const double* w14,
+                                   const double* deriv, const double* kf, const double* CN, int m, const double* H, const double* rm,
+                                   int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov, double* jmean,
+                                   double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
+                                   double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
+    const scvx::McRng rg{rng, noise};
+    return scvx::track_mc_nav_q_host(ctx, B, K, S, x, u, sigma, gain, C0, x, noise ? x : nullptr, w14, deriv, kf, CN, x, x, m, H, rm, nsub,
+                                     flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks,
+                                     flightq, pathq, pathv, &rg);
 }
 
 int scvx_track_mc_nav_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
@@ -645,9 +735,27 @@ int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const doubl
                                  const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                  double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                  double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
+    return scvx::track_mc_nav_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags, tol,
+                                     mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq,
+                                     pathv, nullptr);
+}
+
+}  // extern "C"
+
+namespace scvx {
+
+static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
+                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                               double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
+                               const McRng* rg) {
     int rc = scvx::check_track_mc_nav(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
                                       tol, mcrep, xmean, xcov, jmean, jcov, mcnav);
     if (rc) return rc;
+    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
+    if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     scvx::DevBuf<double> dfq, dpq, dpv;
@@ -662,8 +770,8 @@ int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const doubl
     scvx::DevBuf<double> dx, du, ds, dg, dc, di, de, dd, dk, dcn, dxi, dnu, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk;
     const struct { scvx::DevBuf<double>* b; const double* h; size_t n; bool want; } in[] = {
         {&dx, x, nx, true},   {&du, u, nu, true},       {&ds, sigma, (size_t)B, true}, {&dg, gain, ng, true}, {&dc, C0, nc, true},
-        {&di, xi0, ni, true}, {&de, eta, ne, eta != nullptr}, {&dd, deriv, nd, true},  {&dk, kf, nk, m > 0},  {&dcn, CN, nc, true},
-        {&dxi, xin, ni, true}, {&dnu, nud, nn, m > 0}};
+        {&di, xi0, ni, xi0 != nullptr}, {&de, eta, ne, eta != nullptr}, {&dd, deriv, nd, true},  {&dk, kf, nk, m > 0},  {&dcn, CN, nc, true},
+        {&dxi, xin, ni, xin != nullptr}, {&dnu, nud, nn, m > 0 && nud != nullptr}};
     const struct { scvx::DevBuf<double>* b; double* h; size_t n; bool want; } out[] = {
         {&dr, mcrep, nr, true},  {&dm, xmean, nm, true},  {&dv, xcov, nc, true},  {&djm, jmean, nj, true},
         {&djc, jcov, njc, true}, {&dnv, mcnav, nv, true}, {&df, flights, nf, flights != nullptr}, {&dl, xland, nl, xland != nullptr},
@@ -681,7 +789,7 @@ int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const doubl
     q.nq = nq, q.ranks = ranks, q.flightq = dfq.p, q.pathq = dpq.p, q.pathv = dpv.p;
     hipError_t e = scvx::launch_track_mc_nav(ctx, B, K, S, dx.p, du.p, ds.p, dg.p, dc.p, di.p, de.p, w14, dd.p, dk.p, dcn.p, dxi.p, dnu.p, m,
                                              H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p, df.p, dl.p, d0.p, dfe.p,
-                                             dnk.p, st, (flightq || pathq || pathv) ? &q : nullptr);
+                                             dnk.p, st, (flightq || pathq || pathv) ? &q : nullptr, rg);
     for (const auto& a : out)
         if (e == hipSuccess && a.want) e = hipMemcpyAsync(a.h, a.b->p, a.n * 8, hipMemcpyDeviceToHost, st);
     hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
@@ -690,4 +798,4 @@ int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const doubl
     return SCVX_OK;
 }
 
-}  // extern "C"
+}  // namespace scvx

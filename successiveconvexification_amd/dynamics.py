@@ -371,7 +371,7 @@ class McReport:
     """The report of a sampled dispersion (scvx_track_mc_f64, include/scvx.h): `raw` [B][48], one named numpy view per column
     (report.MAX_GAP, report.MEAN_MISS_R, report.P_TMIN, report.P_ANY, report.OUT_LO, report.N_BAD, ... -- _lib.MC_COLUMNS), the landing
     statistics `xmean` [B][14] and `xcov` [B][14][14] of x_fly[K] - xbar_K over the samples, and the optional dense outputs `flights`
-    [B][S][16], `xland` [B][S][14] and `dx0` [B][S][14], or None.  The draws are shared by all plans.  With `quantiles=` / `per_node=`
+    [B][S][16], `xland` [B][S][14] and `dx0` [B][S][14], or None.  The draws are shared by all plans unless the call was made with independent=True.  With `quantiles=` / `per_node=`
     (the _q forms of the call): `probs` and `ranks` (montecarlo.quantile_ranks), `q` [B][16][nq] the order statistics of the sixteen
     flight columns over the samples -- rep.quantile("MISS_R", 0.99) --, `pathq` [B][K+1][5][nq] those of the five path functions
     (_lib.PSIG_COLUMNS) at every node, and the dense `pathv` [B][K+1][5][S]; each None when not asked for.  A quantile is a selection
@@ -466,17 +466,52 @@ class _McQ:
         return (nq, self.ranks.ctypes.data_as(C.POINTER(C.c_int)) if nq else None, opt(self.flightq), opt(self.pathq), opt(self.pathv))
 
 
-def _mc_inputs(S0, B, K, samples, seed, w, draws):
+def _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo):
+    """rng = "host" (the draws are made here and uploaded: None) or "device" (the lanes make them: the scvx_mc_rng of the _rng forms)"""
+    if rng not in ("host", "device"):
+        raise ValueError('rng: "host" or "device", not %r' % (rng,))
+    if rng == "host":
+        if independent:
+            raise ValueError('independent=True needs rng="device": uploaded draws are shared by all plans')
+        return None
+    if draws is not None:
+        raise ValueError('draws= cannot be combined with rng="device": the device makes its own (dynamics.mc_draws_device_batch)')
+    if int(sample_lo) < 0 or int(plan_lo) < 0:
+        raise ValueError("sample_lo and plan_lo must be >= 0")
+    return _lib.ScvxMcRng(int(seed) & (2 ** 64 - 1), int(sample_lo), int(plan_lo), 1 if independent else 0, 0)
+
+
+def mc_draws_device_batch(cache: IntegratorCache, samples, K=None, seed=0, sample_lo=0, plan_lo=0, plans=None):
+    """The draws the device makes with rng="device", dumped (scvx_mc_draws_f64_host; the stream is spelled out in include/scvx.h): a dict
+    of xi0, xin [samples][14] and eta, nud [samples][K][14] (all 14 draws of every node's group: a call with m measurement rows reads
+    nud[..., :m]) with shared draws (plans None); plans = P: [P][samples][..], the independent draws of plans plan_lo..plan_lo+P-1.
+    The same bits the flying kernels consume: track_mc_batch(..., draws=) fed them is bitwise the rng="device" call.
+    montecarlo.mc_draws_device / mc_nav_draws_device are the numpy twin, a few ulp away."""
+    K = int(cache.problem.K if K is None else K)
+    S, P = int(samples), 1 if plans is None else int(plans)
+    rg = _mc_rng("device", None, plans is not None, seed, sample_lo, plan_lo)
+    out = {n: np.empty((P, S, 14) if n in ("xi0", "xin") else (P, S, K, 14)) for n in ("xi0", "eta", "xin", "nud")}
+    _lib.check(cache.handle, cache._L.scvx_mc_draws_f64_host(cache.handle, C.byref(rg), P, S, K, *[_p(a) for a in out.values()]),
+               "scvx_mc_draws_f64_host")
+    return {n: (a[0] if plans is None else a) for n, a in out.items()}
+
+
+def _mc_inputs(S0, B, K, samples, seed, w, draws, lo=0, device=False):
     """(C0 [B][14][14], xi0 [S][14], eta [S][K][14] or None, sw [14] or None) of a sampled dispersion: the factor of every plan's
-    handover covariance (montecarlo.handover_factor), the draws of montecarlo.mc_draws -- or `draws` = (xi0, eta) -- and sqrt(w)"""
+    handover covariance (montecarlo.handover_factor), the draws of montecarlo.mc_draws -- or `draws` = (xi0, eta); both None with
+    `device`, the lanes make them -- and sqrt(w)"""
     from .montecarlo import handover_factor, mc_draws
     s0 = _cov_s0(S0, B)
     wv = _cov_noise(w)
     c0 = np.ascontiguousarray(np.stack([handover_factor(s0[b]) for b in range(B)]))
-    if draws is None:
+    if device:
         if int(samples) < 1:
             raise ValueError("samples must be >= 1")
-        xi0, eta = mc_draws(int(samples), K, seed, noise=wv is not None)
+        xi0 = eta = None
+    elif draws is None:
+        if int(samples) < 1:
+            raise ValueError("samples must be >= 1")
+        xi0, eta = mc_draws(int(samples), K, seed, noise=wv is not None, lo=lo)
     else:
         xi0 = np.ascontiguousarray(draws[0], np.float64)
         eta = None if draws[1] is None else np.ascontiguousarray(draws[1], np.float64)
@@ -497,7 +532,8 @@ def _mc_outputs(B, S, dense):
 
 
 def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=0, w=None, nsub=10, clamp=False, tol=0.0, dense=(),
-                   draws=None, nav=None, quantiles=None, per_node=False) -> McReport:
+                   draws=None, nav=None, quantiles=None, per_node=False, rng="host", independent=False, sample_lo=0,
+                   plan_lo=0) -> McReport:
     """Sampled closed-loop dispersion of the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] tracked under the gains gain
     [B][K][nu][14+nu]: `samples` flights PER PLAN on the device, reduced there to one McReport row per plan (scvx_track_mc_f64_host;
     the model, the impulse convention and the limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one [14][14]
@@ -512,12 +548,19 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     columns over the samples, reduced on the device (scvx_track_mc_q_f64_host; probability -> rank by montecarlo.quantile_ranks, a
     selection); per_node=True adds `pathq` [B][K+1][5][nq], those of the five path functions at every node, and dense may name "pathv"
     for the samples themselves [B][K+1][5][S].  With the clamp the THRUST function is still the unclamped command.  With these keywords
-    at their defaults the call is the one it was."""
+    at their defaults the call is the one it was.
+    rng="device": every lane makes its own draws from a counter-based generator (scvx_track_mc_rng_f64_host; the stream is spelled out
+    in include/scvx.h): nothing is generated or uploaded here, and the flights are bitwise those of the call fed
+    mc_draws_device_batch's dump.  independent=True (device only): every plan flies draws of its own, plan b the stream plan_lo + b, so
+    the rows of one call are independent experiments; sample_lo: the first sample, so that shards of one sample set can be flown by
+    separate calls.  rng="host" (the default) makes exactly the C calls it always made; draws= cannot be combined with "device"."""
+    rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
     if nav is not None:
         n0, _, Hm, rv = _nav_arg(nav, np.shape(x)[0])
         _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / np.shape(x)[1])
         return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
-                                  tol=tol, dense=dense, draws=draws, quantiles=quantiles, per_node=per_node)
+                                  tol=tol, dense=dense, draws=draws, quantiles=quantiles, per_node=per_node, rng=rng,
+                                  independent=independent, sample_lo=sample_lo, plan_lo=plan_lo)
     mq = _McQ(quantiles, per_node, dense)
     dense = mq.rest
     x = np.ascontiguousarray(x, np.float64)
@@ -529,14 +572,17 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     B, K1, _ = x.shape
     if gain.shape != (B, K1 - 1, cache.nu, 14 + cache.nu):
         raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (cache.nu, 14 + cache.nu))
-    c0, xi0, eta, sw = _mc_inputs(S0, B, K1 - 1, samples, seed, w, draws)
-    S = xi0.shape[0]
+    c0, xi0, eta, sw = _mc_inputs(S0, B, K1 - 1, samples, seed, w, draws, sample_lo, rg is not None)
+    S = int(samples) if rg is not None else xi0.shape[0]
     rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    args = (cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(sw), None,
+    drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None else (_p(xi0), opt(eta))
+    args = (cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), *drw, opt(sw), None,
             int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov),
             opt(flights), opt(xland), opt(dx0))
-    if mq.on:
+    if rg is not None:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_rng_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_rng_f64_host")
+    elif mq.on:
         _lib.check(cache.handle, cache._L.scvx_track_mc_q_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_q_f64_host")
     else:
         _lib.check(cache.handle, cache._L.scvx_track_mc_f64_host(*args), "scvx_track_mc_f64_host")
@@ -676,7 +722,7 @@ def _mc_nav_dense(dense):
     return want
 
 
-def _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws):
+def _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws, lo=0, device=False):
     """(C0, CN [B][14][14], xi0, eta or None, xin, nud or None, w [14] or None) of a sampled dispersion flown on an estimate: the factors
     of every plan's two handover covariances (montecarlo.handover_factor), the draws of montecarlo.mc_draws and mc_nav_draws -- or
     `draws` = (xi0, eta, xin, nud) -- and the process-noise VARIANCE, which the library roots"""
@@ -685,11 +731,15 @@ def _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws):
     wv = _cov_noise(w)
     c0 = np.ascontiguousarray(np.stack([handover_factor(s0[b]) for b in range(B)]))
     cn = np.ascontiguousarray(np.stack([handover_factor(n0[b]) for b in range(B)]))
-    if draws is None:
+    if device:   # the lanes make the four
         if int(samples) < 1:
             raise ValueError("samples must be >= 1")
-        xi0, eta = mc_draws(int(samples), K, seed, noise=wv is not None)
-        xin, nud = mc_nav_draws(int(samples), K, m, seed)
+        xi0 = eta = xin = nud = None
+    elif draws is None:
+        if int(samples) < 1:
+            raise ValueError("samples must be >= 1")
+        xi0, eta = mc_draws(int(samples), K, seed, noise=wv is not None, lo=lo)
+        xin, nud = mc_nav_draws(int(samples), K, m, seed, lo=lo)
     else:
         if len(draws) != 4:
             raise ValueError("draws = (xi0 [S][14], eta [S][K][14] or None, xin [S][14], nud [S][K][m] or None)")
@@ -710,7 +760,8 @@ def _mc_nav_outputs(B, S, K, dense):
 
 
 def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0, H, rm, samples, seed=0, w=None, kf=None, nsub=10,
-                       clamp=False, tol=0.0, dense=(), draws=None, quantiles=None, per_node=False) -> McNavReport:
+                       clamp=False, tol=0.0, dense=(), draws=None, quantiles=None, per_node=False, rng="host", independent=False,
+                       sample_lo=0, plan_lo=0) -> McNavReport:
     """track_mc_batch with the law fed a navigation ESTIMATE whose error is generated per flight on the device (scvx_track_mc_nav_f64_host;
     the model and its limits are in include/scvx.h): the sampled, nonlinear counterpart of nav_cov_batch, whose arguments deriv, N0, H,
     rm and w mean here what they mean there.  The error starts at handover_factor(N0[b]) @ xin[s], is corrected at every node but the
@@ -718,7 +769,9 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     the truth receives.  kf None: the gains of nav_cov_batch for the same model.  The draws are montecarlo.mc_draws and
     montecarlo.mc_nav_draws of `seed`, or draws = (xi0, eta, xin, nud).  dense: True, or names out of "flights", "xland", "dx0",
     "navfed", "navK".  quantiles, per_node and the dense name "pathv" as track_mc_batch (scvx_track_mc_nav_q_f64_host): the state
-    path functions are those of the TRUTH, the thrust norm that of the command formed from the estimate."""
+    path functions are those of the TRUTH, the thrust norm that of the command formed from the estimate.  rng, independent, sample_lo
+    and plan_lo as track_mc_batch (scvx_track_mc_nav_rng_f64_host): with "device" the lanes make all four draws."""
+    rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
     mq = _McQ(quantiles, per_node, dense)
     dense = mq.rest
     x = np.ascontiguousarray(x, np.float64)
@@ -736,20 +789,24 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
         raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
     m, Hm, rv = _nav_model(H, rm)
-    c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws)
+    c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws, sample_lo, rg is not None)
     if m and kf is None:
         kf = nav_cov_batch(cache, x, u, deriv, gain, np.zeros((B, 14, 14)), n0, Hm, rv, wv, dense=("kf",)).kf
     if m:
         kf = np.ascontiguousarray(kf, np.float64)
         if kf.shape != (B, K, 14, m):
             raise ValueError("shape mismatch: kf [B][K][14][%d]" % m)
-    S = xi0.shape[0]
+    S = int(samples) if rg is not None else xi0.shape[0]
     red, dn = _mc_nav_outputs(B, S, K, dense)
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    args = (cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), _p(xi0), opt(eta), opt(wv), _p(deriv),
-            opt(kf if m else None), _p(cn), _p(xin), opt(nud), m, opt(Hm), opt(rv), int(cache.npts if nsub is None else nsub),
-            _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red], *[opt(a) for a in dn])
-    if mq.on:
+    drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None else (_p(xi0), opt(eta))
+    args = (cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), *drw, opt(wv), _p(deriv),
+            opt(kf if m else None), _p(cn), *(() if rg is not None else (_p(xin), opt(nud))), m, opt(Hm), opt(rv),
+            int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red],
+            *[opt(a) for a in dn])
+    if rg is not None:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_rng_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_rng_f64_host")
+    elif mq.on:
         _lib.check(cache.handle, cache._L.scvx_track_mc_nav_q_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_q_f64_host")
     else:
         _lib.check(cache.handle, cache._L.scvx_track_mc_nav_f64_host(*args), "scvx_track_mc_nav_f64_host")

@@ -121,6 +121,87 @@ def mc_nav_draws(samples, K, m, seed, lo=0):
     return xin, nud
 
 
+_PHILOX_M0, _PHILOX_M1 = 0xD2E7470EE14C6C93, 0xCA5A826395121157
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B
+MC_STREAM_TRUTH, MC_STREAM_NAV = 6, 7   # the second counter word of the device's two streams, beside mc_draws' 4 and mc_nav_draws' 5
+
+
+def _mulhilo64(a, b):
+    """(hi, lo) of the 128-bit product of the constant a (a Python int below 2^64) and the uint64 array b, by 32-bit halves"""
+    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    a0, a1 = np.uint64(a & 0xFFFFFFFF), np.uint64(a >> 32)
+    b0, b1 = b & m32, b >> s32
+    t = a0 * b0
+    lo0, k = t & m32, t >> s32
+    t = a1 * b0 + k
+    w1, w2 = t & m32, t >> s32
+    t = a0 * b1 + w1
+    return a1 * b1 + w2 + (t >> s32), (t << s32) | lo0
+
+
+def philox4x64_blocks(seed, c0, c1, c2, c3):
+    """The Philox4x64-10 blocks of the counters [c0, c1, c2, c3] (uint64 arrays of one shape, or scalars that broadcast) under the key
+    [seed, 0]: uint64 words [...][4], vectorised.  np.random.Philox(key=seed, counter=[0, c1, c2, c3]).random_raw(4 n) is the blocks of
+    c0 = 1..n (numpy increments the counter before its first block); include/scvx.h spells out the round."""
+    c0, c1, c2, c3 = (np.array(a, np.uint64) for a in np.broadcast_arrays(*(np.asarray(a, np.uint64) for a in (c0, c1, c2, c3))))
+    k0, k1 = int(seed) & (2 ** 64 - 1), 0
+    with np.errstate(over="ignore"):
+        for _ in range(10):
+            h0, l0 = _mulhilo64(_PHILOX_M0, c0)
+            h1, l1 = _mulhilo64(_PHILOX_M1, c2)
+            c0, c1, c2, c3 = h1 ^ c1 ^ np.uint64(k0), l1, h0 ^ c3 ^ np.uint64(k1), l0
+            k0, k1 = (k0 + _PHILOX_W0) & (2 ** 64 - 1), (k1 + _PHILOX_W1) & (2 ** 64 - 1)
+    return np.stack([c0, c1, c2, c3], axis=-1)
+
+
+def box_muller(words, dtype=np.float64):
+    """The normals of the device's draws from Philox words [...][4]: u_j = ((w_j >> 11) + 0.5) 2^-53 in float64 arithmetic (what the
+    device forms; never 0), (z0, z1) = sqrt(-2 log u0) (cospi(2 u1), sinpi(2 u1)), (z2, z3) likewise from u2, u3 -> [...][4] of
+    `dtype` (float64, or longdouble for the yardstick).  The angle is reduced EXACTLY before cos / sin: v = 2 u is dyadic, n = rint(2 v)
+    and t = v - n / 2 in [-1/4, 1/4] without rounding, cos(pi v) and sin(pi v) from cos(pi t), sin(pi t) by the quarter turn n mod 4."""
+    u = ((np.asarray(words, np.uint64) >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+    r = np.sqrt(-2 * np.log(u[..., 0::2].astype(dtype)))
+    v = 2.0 * u[..., 1::2]
+    n = np.rint(2.0 * v)
+    t = (v - 0.5 * n).astype(dtype)
+    pi = 4 * np.arctan(dtype(1))
+    ct, st = np.cos(pi * t), np.sin(pi * t)
+    q = n.astype(np.int64) & 3
+    c = np.where(q == 0, ct, np.where(q == 1, -st, np.where(q == 2, -ct, st)))
+    s = np.where(q == 0, st, np.where(q == 1, ct, np.where(q == 2, -st, -ct)))
+    return np.stack([r * c, r * s], axis=-1).reshape(np.shape(words))
+
+
+def _device_groups(seed, stream, samples, lo, plans, g0, g1, dtype=np.float64):
+    """groups g0..g1-1 of `stream` for samples lo..lo+samples-1: [S][G][14] with shared draws (plans None), else [P][S][G][14] for the
+    absolute plan indices `plans`"""
+    if int(samples) < 1:
+        raise ValueError("samples must be >= 1")
+    c2 = np.zeros(1, np.uint64) if plans is None else np.uint64(1) + np.asarray(list(plans), np.uint64)
+    c3 = np.uint64(int(lo) & (2 ** 64 - 1)) + np.arange(int(samples), dtype=np.uint64)
+    j = np.uint64(1) + np.arange(4 * g0, 4 * g1, dtype=np.uint64)
+    w = philox4x64_blocks(seed, j[None, None, :], np.uint64(stream), c2[:, None, None], c3[None, :, None])   # [P][S][4 G][4]
+    z = box_muller(w, dtype).reshape(c2.size, int(samples), g1 - g0, 16)[..., :14]
+    return z[0] if plans is None else z
+
+
+def mc_draws_device(samples, K, seed, noise=False, lo=0, plans=None):
+    """The float64 numpy twin of the draws the DEVICE makes with rng="device" (dynamics.track_mc_batch; the stream is spelled out in
+    include/scvx.h): (xi0 [samples][14], eta [samples][K][14] or None without `noise`) with shared draws, [P][samples][..] for the
+    absolute plan indices `plans` of independent draws.  lo: the first sample (sample_lo).  The words are numpy's Philox words
+    (philox4x64_blocks against random_raw: tests/test_mc_rng_cpu.py), Box-Muller by box_muller; the device's log and sincospi differ from
+    numpy's by a few ulp, so the device's own draws are dynamics.mc_draws_device_batch."""
+    z = _device_groups(seed, MC_STREAM_TRUTH, samples, lo, plans, 0, 1 + (int(K) if noise else 0))
+    return np.ascontiguousarray(z[..., 0, :]), (np.ascontiguousarray(z[..., 1:, :]) if noise else None)
+
+
+def mc_nav_draws_device(samples, K, m, seed, lo=0, plans=None):
+    """mc_draws_device for the navigation error: (xin [samples][14], nud [samples][K][m] or None with m = 0), the first m of the 14 draws
+    of every node's group, so nud at m = 3 is the first three columns of nud at m = 14."""
+    z = _device_groups(seed, MC_STREAM_NAV, samples, lo, plans, 0, 1 + (int(K) if m else 0))
+    return np.ascontiguousarray(z[..., 0, :]), (np.ascontiguousarray(z[..., 1:, :int(m)]) if m else None)
+
+
 def quantile_ranks(p, S):
     """The 0-based ascending ranks of the probabilities `p` (a scalar or an iterable) in a sample of S values, as the order statistics of
     the library count them (scvx_order_stats_f64, include/scvx.h): min(S - 1, max(0, ceil(p S) - 1)), numpy's method="inverted_cdf"
@@ -166,7 +247,7 @@ def margins_from_quantiles(p, x, u, pathq_lo, pathq_hi, constraints="all", cap=0
     ("thrust", "mass", "glide", "tilt", "rate") or "all"; a kind that is not selected keeps the value of current = (lo, hi, pm) (zeros
     without it).  Returns (lo [B][K+1], hi [B][K+1], pm [B][K+1][4]).
     Limits: the glide back-off buys tan(gammaGs) times what is written, as the covariance one does; the quantiles carry the sampling
-    error of quantile_stderr(p, S); the draws are shared across plans; with the clamp on, T_k is still the UNCLAMPED command."""
+    error of quantile_stderr(p, S); the draws are shared across plans unless the call was made with independent=True; with the clamp on, T_k is still the UNCLAMPED command."""
     from ._lib import MARGIN_BITS, PMARG_INDEX, PMARG_N, PSIG_INDEX
     names = tuple(MARGIN_BITS) if isinstance(constraints, str) and constraints == "all" else tuple(constraints)
     if isinstance(constraints, str) and constraints != "all" or len(names) == 0 or any(n not in MARGIN_BITS for n in names):
