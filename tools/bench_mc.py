@@ -39,7 +39,7 @@ def resources(log):
     """{mangled kernel name: {field: value}} from a verbose build log; the translation units compile side by side, so the remarks are
     taken file by file, where they are in order"""
     per = collections.defaultdict(list)
-    pat = re.compile(r"(\S+?\.hip):\d+:\d+: remark:\s+(Function Name|%s): (\S+)" % "|".join(re.escape(f) for f in FIELDS))
+    pat = re.compile(r"(\S+?\.h(?:ip|pp)):\d+:\d+: remark:\s+(Function Name|%s): (\S+)" % "|".join(re.escape(f) for f in FIELDS))
     for line in open(log):
         m = pat.match(line)
         if m:
