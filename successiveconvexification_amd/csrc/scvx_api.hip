@@ -5,6 +5,7 @@
 #include <type_traits>
 #include <vector>
 #include "scvx_internal.hpp"
+#include "scvx_stage.hpp"
 
 using scvx::fail;
 
@@ -323,50 +324,39 @@ int scvx_propagate_f32(scvx_ctx* ctx, int B, int K, const float* x_dev, const fl
 
 }  // extern "C"
 
-// scvx_linearize_* / scvx_propagate_*_host at the element type T: upload, K1 (with_deriv) or K2, download
+// scvx_linearize_* / scvx_propagate_*_host at the element type T: upload, K1 (with deriv) or K2, download
 template <typename T>
-static int disc_host(scvx_ctx* ctx, int B, int K, const T* x, const T* u, const T* sigma, T dt, T* endpoint, T* deriv, bool with_deriv) {
+static int disc_host(const char* entry, scvx_ctx* ctx, int B, int K, const T* x, const T* u, const T* sigma, T dt, T* endpoint, T* deriv,
+                     bool with_deriv) {
     int rc = check_disc(ctx, B, K, x, u, sigma, endpoint);
     if (rc) return rc;
     if (B == 0) return SCVX_OK;
     if (with_deriv && !deriv) return fail(ctx, SCVX_ERR_ARG, "null buffer");
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx);
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, ne = (size_t)B * K * 14,
-                 nd = (size_t)B * K * 14 * (14 + 2 * NU + 1);
-    scvx::DevBuf<T> dx, du, ds, de, dd;
-    SCVX_HIP(ctx, hipMalloc(&dx.p, nx * sizeof(T)));
-    SCVX_HIP(ctx, hipMalloc(&du.p, nu * sizeof(T)));
-    SCVX_HIP(ctx, hipMalloc(&ds.p, (size_t)B * sizeof(T)));
-    SCVX_HIP(ctx, hipMalloc(&de.p, ne * sizeof(T)));
-    if (with_deriv) SCVX_HIP(ctx, hipMalloc(&dd.p, nd * sizeof(T)));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * sizeof(T), hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * sizeof(T), hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * sizeof(T), hipMemcpyHostToDevice, st));
-    if constexpr (std::is_same_v<T, float>) {
-        if (with_deriv) SCVX_HIP(ctx, scvx::launch_linearize_f32(ctx, B, K, dx.p, du.p, ds.p, dt, de.p, dd.p, st));
-        else SCVX_HIP(ctx, scvx::launch_propagate_f32(ctx, B, K, dx.p, du.p, ds.p, dt, de.p, st));
-    } else {
-        if (with_deriv) SCVX_HIP(ctx, scvx::launch_linearize(ctx, B, K, dx.p, du.p, ds.p, dt, de.p, dd.p, st));
-        else SCVX_HIP(ctx, scvx::launch_propagate(ctx, B, K, dx.p, du.p, ds.p, dt, de.p, st));
-    }
-    SCVX_HIP(ctx, hipMemcpyAsync(endpoint, de.p, ne * sizeof(T), hipMemcpyDeviceToHost, st));
-    if (with_deriv) SCVX_HIP(ctx, hipMemcpyAsync(deriv, dd.p, nd * sizeof(T), hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const T *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b);
+    T *de = s.out(endpoint, d.seg), *dd = s.out(with_deriv ? deriv : nullptr, d.deriv);
+    s.launch([&] {
+        if constexpr (std::is_same_v<T, float>)
+            return with_deriv ? scvx::launch_linearize_f32(ctx, B, K, dx, du, ds, dt, de, dd, s.st)
+                              : scvx::launch_propagate_f32(ctx, B, K, dx, du, ds, dt, de, s.st);
+        else
+            return with_deriv ? scvx::launch_linearize(ctx, B, K, dx, du, ds, dt, de, dd, s.st)
+                              : scvx::launch_propagate(ctx, B, K, dx, du, ds, dt, de, s.st);
+    });
+    return s.finish(entry);
 }
 
 extern "C" {
 
 int scvx_linearize_f32_host(scvx_ctx* ctx, int B, int K, const float* x, const float* u, const float* sigma, float dt,
                             float* endpoint, float* deriv) {
-    return disc_host<float>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, true);
+    return disc_host<float>("scvx_linearize_f32_host", ctx, B, K, x, u, sigma, dt, endpoint, deriv, true);
 }
 
 int scvx_propagate_f32_host(scvx_ctx* ctx, int B, int K, const float* x, const float* u, const float* sigma, float dt,
                             float* xnext) {
-    return disc_host<float>(ctx, B, K, x, u, sigma, dt, xnext, nullptr, false);
+    return disc_host<float>("scvx_propagate_f32_host", ctx, B, K, x, u, sigma, dt, xnext, nullptr, false);
 }
 
 int scvx_flight_check_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev, int nsub,
@@ -382,34 +372,22 @@ int scvx_flight_check_f64_host(scvx_ctx* ctx, int B, int K, const double* x, con
                                int mode, double* report, double* xfly) {
     int rc = scvx::check_flight(ctx, B, K, x, u, sigma, nsub, mode, report);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx);
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP;
-    scvx::DevBuf<double> dx, du, ds, dr, df;
-    SCVX_HIP(ctx, hipMalloc(&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc(&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc(&ds.p, (size_t)B * 8));
-    SCVX_HIP(ctx, hipMalloc(&dr.p, nr * 8));
-    if (xfly) SCVX_HIP(ctx, hipMalloc(&df.p, nx * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_flight(ctx, B, K, dx.p, du.p, ds.p, nsub, mode, dr.p, df.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    if (xfly) SCVX_HIP(ctx, hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b);
+    double *dr = s.out(report, d.frep), *df = s.out(xfly, d.x);
+    s.launch([&] { return scvx::launch_flight(ctx, B, K, dx, du, ds, nsub, mode, dr, df, s.st); });
+    return s.finish("scvx_flight_check_f64_host");
 }
 
 int scvx_linearize_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma,
                             double dt, double* endpoint, double* deriv) {
-    return disc_host<double>(ctx, B, K, x, u, sigma, dt, endpoint, deriv, true);
+    return disc_host<double>("scvx_linearize_f64_host", ctx, B, K, x, u, sigma, dt, endpoint, deriv, true);
 }
 
 int scvx_propagate_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma,
                             double dt, double* xnext) {
-    return disc_host<double>(ctx, B, K, x, u, sigma, dt, xnext, nullptr, false);
+    return disc_host<double>("scvx_propagate_f64_host", ctx, B, K, x, u, sigma, dt, xnext, nullptr, false);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@
 #include <cstdio>
 #include "scvx_socp.hpp"
 #include "scvx_mc.hpp"   // McQ: what the _q forms of the sampled calls add
+#include "scvx_stage.hpp"
 
 using scvx::fail;
 
@@ -278,6 +279,7 @@ struct scvx_batch {
     double *cx = nullptr, *cu = nullptr, *csigma = nullptr;       // split views of cand
     double *endpoint = nullptr, *deriv = nullptr, *xprop = nullptr, *nu = nullptr;
     float* deriv_f = nullptr;   // the derivative tiles in float (scvx_batch_set_linearization_f32): then `deriv` is not allocated
+    scvx::Tiles tiles() const { return deriv_f ? scvx::Tiles{nullptr, deriv_f} : scvx::Tiles{deriv, nullptr}; }
     double *rk = nullptr, *cost = nullptr, *ic = nullptr, *info = nullptr, *out = nullptr, *work = nullptr;
     double *ttr = nullptr;   // trust-region norm bound at the last optimum (reuse_inactive_tr)
     double *acc = nullptr;   // scvx::ACC_N running totals (scvx_batch_get_step_stats)
@@ -887,17 +889,11 @@ int scvx_batch_flight_check(scvx_batch* b, int nsub, int mode, double* report, d
     // b->x / u / sigma are the split views of the accepted iterate (kept current by every step); only read here
     rc = scvx::check_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, report);
     if (rc) return rc;
-    const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14;
-    scvx::DevBuf<double> dr, df;
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    hipError_t e = xfly ? hipMalloc((void**)&df.p, nx * 8) : hipSuccess;
-    hipStream_t st = ctx->stream;
-    if (e == hipSuccess) e = scvx::launch_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, dr.p, df.p, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_flight_check: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    const scvx::Dims d(b->B, b->K, b->NU);
+    scvx::Staging s(ctx);
+    double *dr = s.out(report, d.frep), *df = s.out(xfly, d.x);
+    s.launch([&] { return scvx::launch_flight(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, mode, dr, df, s.st); });
+    return s.finish("scvx_batch_flight_check");
 }
 
 // The gains of the batch's current iterate into b->track_gain / b->track_p0 (enqueued on the context's stream).  The tiles in
@@ -912,10 +908,7 @@ static int enqueue_track_gains(scvx_batch* b, const double* q, const double* r, 
         SCVX_HIP(ctx, hipMalloc((void**)&b->track_gain, (size_t)b->B * b->K * b->NU * n * 8));
         SCVX_HIP(ctx, hipMalloc((void**)&b->track_p0, (size_t)b->B * n * n * 8));
     }
-    if (b->deriv_f)
-        SCVX_HIP(ctx, scvx::launch_track_gains_f32(ctx, b->B, b->K, b->deriv_f, q, r, qf, b->track_gain, b->track_p0, ctx->stream));
-    else
-        SCVX_HIP(ctx, scvx::launch_track_gains(ctx, b->B, b->K, b->deriv, q, r, qf, b->track_gain, b->track_p0, ctx->stream));
+    SCVX_HIP(ctx, scvx::launch_track_gains(ctx, b->B, b->K, b->tiles(), q, r, qf, b->track_gain, b->track_p0, ctx->stream));
     return SCVX_OK;
 }
 
@@ -942,23 +935,12 @@ int scvx_batch_track_fly(scvx_batch* b, const double* q14, const double* rNU, co
     if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
     if ((rc = scvx::check_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->x, nsub, flags, b->x))) return rc;
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14, nu = (size_t)b->B * (b->K + 1) * b->NU;
-    scvx::DevBuf<double> dr, df, dc, d0;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&dr.p, nr * 8);
-    if (e == hipSuccess && xfly) e = hipMalloc((void**)&df.p, nx * 8);
-    if (e == hipSuccess && ufly) e = hipMalloc((void**)&dc.p, nu * 8);
-    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, (size_t)b->B * 14 * 8);
-    if (e == hipSuccess && dx0) e = hipMemcpyAsync(d0.p, dx0, (size_t)b->B * 14 * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = scvx::launch_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0.p, nsub, flags, dr.p, df.p, dc.p, st);
-    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && ufly) e = hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_fly: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    const scvx::Dims d(b->B, b->K, b->NU);
+    scvx::Staging s(ctx);
+    double *dr = s.out_always(report, d.frep), *df = s.out(xfly, d.x), *dc = s.out(ufly, d.u);
+    const double* d0 = s.in(dx0, d.b14);
+    s.launch([&] { return scvx::launch_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0, nsub, flags, dr, df, dc, s.st); });
+    return s.finish("scvx_batch_track_fly");
 }
 
 int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
@@ -970,29 +952,12 @@ int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const do
     if (!S0) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
     if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const size_t n = 14 + b->NU;
-    const size_t n0 = (size_t)b->B * 196, nr = (size_t)b->B * SCVX_COV_NREP, ns = (size_t)b->B * (b->K + 1) * n, nk = (size_t)b->B * n * n,
-                 nc = (size_t)b->B * (b->K + 1) * n * n;
-    scvx::DevBuf<double> d0, dr, ds, dk, dc;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&d0.p, n0 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
-    if (e == hipSuccess && sig) e = hipMalloc((void**)&ds.p, ns * 8);
-    if (e == hipSuccess && covK) e = hipMalloc((void**)&dk.p, nk * 8);
-    if (e == hipSuccess && cov) e = hipMalloc((void**)&dc.p, nc * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = b->deriv_f
-                ? scvx::launch_cov_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, d0.p, w14, dr.p, ds.p, dk.p, dc.p, st)
-                : scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, d0.p, w14, dr.p, ds.p, dk.p, dc.p, st);
-    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && sig) e = hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && covK) e = hipMemcpyAsync(covK, dk.p, nk * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && cov) e = hipMemcpyAsync(cov, dc.p, nc * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_cov: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    const scvx::Dims d(b->B, b->K, b->NU);
+    scvx::Staging s(ctx);
+    const double* d0 = s.in(S0, d.c14);
+    double *dr = s.out_always(report, d.crep), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK), *dc = s.out(cov, d.cov);
+    s.launch([&] { return scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, w14, dr, ds, dk, dc, s.st); });
+    return s.finish("scvx_batch_cov");
 }
 
 int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* dx0,
@@ -1006,26 +971,14 @@ int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU
     if ((rc = scvx::check_track_fly(ctx, b->B, b->K, b->x, b->u, b->sigma, b->x, nsub, flags, b->x))) return rc;
     if (!nav) return fail(ctx, SCVX_ERR_ARG, "track fly nav: null nav (without one, call scvx_batch_track_fly)");
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const size_t nr = (size_t)b->B * SCVX_FLIGHT_NREP, nx = (size_t)b->B * (b->K + 1) * 14, nu = (size_t)b->B * (b->K + 1) * b->NU,
-                 nv = (size_t)b->B * b->K * 14;
-    scvx::DevBuf<double> dr, df, dc, d0, dv;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&dr.p, nr * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dv.p, nv * 8);
-    if (e == hipSuccess && xfly) e = hipMalloc((void**)&df.p, nx * 8);
-    if (e == hipSuccess && ufly) e = hipMalloc((void**)&dc.p, nu * 8);
-    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, (size_t)b->B * 14 * 8);
-    if (e == hipSuccess && dx0) e = hipMemcpyAsync(d0.p, dx0, (size_t)b->B * 14 * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dv.p, nav, nv * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = scvx::launch_track_fly_nav(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0.p, dv.p, nsub, flags, dr.p, df.p, dc.p, st);
-    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xfly) e = hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && ufly) e = hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_fly_nav: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    const scvx::Dims d(b->B, b->K, b->NU);
+    scvx::Staging s(ctx);
+    double *dr = s.out_always(report, d.frep), *df = s.out(xfly, d.x), *dc = s.out(ufly, d.u);
+    const double *d0 = s.in(dx0, d.b14), *dv = s.in(nav, d.seg);
+    s.launch([&] {
+        return scvx::launch_track_fly_nav(ctx, b->B, b->K, b->x, b->u, b->sigma, b->track_gain, d0, dv, nsub, flags, dr, df, dc, s.st);
+    });
+    return s.finish("scvx_batch_track_fly_nav");
 }
 
 int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1053,45 +1006,19 @@ static int batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU,
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
     if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const size_t nc = (size_t)b->B * 196, ni = (size_t)S * 14, ne = (size_t)S * b->K * 14, nr = (size_t)b->B * SCVX_MC_NREP,
-                 nm = (size_t)b->B * 14, nf = (size_t)b->B * S * SCVX_FLIGHT_NREP, nl = (size_t)b->B * S * 14,
-                 nfq = (size_t)b->B * SCVX_FLIGHT_NREP * nq, npq = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N * nq,
-                 npv = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N * S;
-    scvx::DevBuf<double> dc, di, de, dr, dm, dv, df, dl, d0, dfq, dpq, dpv;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&dc.p, nc * 8);
-    if (e == hipSuccess && flightq) e = hipMalloc((void**)&dfq.p, nfq * 8);
-    if (e == hipSuccess && pathq) e = hipMalloc((void**)&dpq.p, npq * 8);
-    if (e == hipSuccess && pathv) e = hipMalloc((void**)&dpv.p, npv * 8);
-    if (e == hipSuccess && xi0) e = hipMalloc((void**)&di.p, ni * 8);
-    if (e == hipSuccess && eta) e = hipMalloc((void**)&de.p, ne * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dm.p, nm * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dv.p, nc * 8);
-    if (e == hipSuccess && flights) e = hipMalloc((void**)&df.p, nf * 8);
-    if (e == hipSuccess && xland) e = hipMalloc((void**)&dl.p, nl * 8);
-    if (e == hipSuccess && dx0) e = hipMalloc((void**)&d0.p, nl * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc.p, C0, nc * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && xi0) e = hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && eta) e = hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st);
+    const scvx::Dims d(b->B, b->K, b->NU, S, 0, nq);
+    scvx::Staging s(ctx);
+    const double* dc = s.in(C0, d.c14);
     scvx::McQ mq;
-    mq.nq = nq, mq.ranks = ranks, mq.flightq = dfq.p, mq.pathq = dpq.p, mq.pathv = dpv.p;
-    if (e == hipSuccess)
-        e = scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p,
-                                  dm.p, dv.p, df.p, dl.p, d0.p, st, (flightq || pathq || pathv) ? &mq : nullptr, rg);
-    if (e == hipSuccess && flightq) e = hipMemcpyAsync(flightq, dfq.p, nfq * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && pathq) e = hipMemcpyAsync(pathq, dpq.p, npq * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && pathv) e = hipMemcpyAsync(pathv, dpv.p, npv * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mcrep) e = hipMemcpyAsync(mcrep, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xmean) e = hipMemcpyAsync(xmean, dm.p, nm * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xcov) e = hipMemcpyAsync(xcov, dv.p, nc * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && flights) e = hipMemcpyAsync(flights, df.p, nf * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && xland) e = hipMemcpyAsync(xland, dl.p, nl * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dx0) e = hipMemcpyAsync(dx0, d0.p, nl * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_q: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    mq.nq = nq, mq.ranks = ranks, mq.flightq = s.out(flightq, d.flightq), mq.pathq = s.out(pathq, d.pathq), mq.pathv = s.out(pathv, d.pathv);
+    const double *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta);
+    double *dr = s.out_always(mcrep, d.mcrep), *dm = s.out_always(xmean, d.b14), *dv = s.out_always(xcov, d.c14),
+           *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14);
+    s.launch([&] {
+        return scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc, di, de, sw14, nsub, flags, tol, dr, dm, dv, df,
+                                     dl, d0, s.st, (flightq || pathq || pathv) ? &mq : nullptr, rg);
+    });
+    return s.finish("scvx_batch_track_mc_q");
 }
 
 int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1143,62 +1070,30 @@ static int batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* 
     if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const int B = b->B, K = b->K;
-    const size_t nc = (size_t)B * 196, ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
-                 nf = (size_t)B * S * SCVX_FLIGHT_NREP, nl = (size_t)B * S * 14, nk = (size_t)B * K * 14 * m, nn = (size_t)S * K * m,
-                 nfed = (size_t)B * S * K * 14;
-    const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
-                 npv = (size_t)B * (K + 1) * SCVX_PSIG_N * S;
-    scvx::DevBuf<double> dc, di, de, dz, dn0, dcn, dxi, dnu, dk, dcr, dnr, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, dfq, dpq, dpv;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipSuccess;
-    auto in = [&](scvx::DevBuf<double>& d, const double* h, size_t n) {
-        if (e == hipSuccess) e = hipMalloc((void**)&d.p, n * 8);
-        if (e == hipSuccess && h) e = hipMemcpyAsync(d.p, h, n * 8, hipMemcpyHostToDevice, st);
-    };
-    in(dc, C0, nc), in(dn0, N0, nc), in(dcn, CN, nc);
-    if (xi0) in(di, xi0, ni);
-    if (xin) in(dxi, xin, ni);
-    if (eta) in(de, eta, ne);
-    if (m > 0 && nud) in(dnu, nud, nn);
-    if (m > 0) in(dk, nullptr, nk);
-    in(dz, nullptr, nc), in(dcr, nullptr, (size_t)B * SCVX_COV_NREP), in(dnr, nullptr, (size_t)B * SCVX_NAV_NREP);
-    in(dr, nullptr, nr), in(dm, nullptr, nm), in(dv, nullptr, nc), in(djm, nullptr, (size_t)B * 28), in(djc, nullptr, (size_t)B * 784);
-    in(dnv, nullptr, (size_t)B * SCVX_NAV_NREP);
-    if (flights) in(df, nullptr, nf);
-    if (xland) in(dl, nullptr, nl);
-    if (dx0) in(d0, nullptr, nl);
-    if (navfed) in(dfe, nullptr, nfed);
-    if (navK) in(dnk, nullptr, nl);
-    if (flightq) in(dfq, nullptr, nfq);
-    if (pathq) in(dpq, nullptr, npq);
-    if (pathv) in(dpv, nullptr, npv);
+    const scvx::Dims d(B, K, b->NU, S, m, nq);
+    scvx::Staging s(ctx);
+    const double *dc = s.in(C0, d.c14), *dn0 = s.in(N0, d.c14), *dcn = s.in(CN, d.c14), *di = s.in(xi0, d.xi), *dxi = s.in(xin, d.xi),
+                 *de = s.in(eta, d.eta), *dnu = s.in(m > 0 ? nud : nullptr, d.nud);
+    // the filter gains, written by the navigation launch with the same N0, H, rm and w; Kf does not depend on S0, which is zero here
+    double *dk = m > 0 ? s.tmp(d.kf) : nullptr, *dz = s.tmp(d.c14), *dcr = s.tmp(d.crep), *dnr = s.tmp(d.nrep);
+    double *dr = s.out_always(mcrep, d.mcrep), *dm = s.out_always(xmean, d.b14), *dv = s.out_always(xcov, d.c14),
+           *djm = s.out_always(jmean, d.jmean), *djc = s.out_always(jcov, d.jcov), *dnv = s.out_always(mcnav, d.nrep),
+           *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14), *dfe = s.out(navfed, d.fed),
+           *dnk = s.out(navK, d.s14);
     scvx::McQ mq;
-    mq.nq = nq, mq.ranks = ranks, mq.flightq = dfq.p, mq.pathq = dpq.p, mq.pathv = dpv.p;
-    const scvx::McQ* mqp = (flightq || pathq || pathv) ? &mq : nullptr;
-    // the filter gains: the navigation launch with the same N0, H, rm and w; Kf does not depend on S0, which is zero here
-    if (e == hipSuccess) e = hipMemsetAsync(dz.p, 0, nc * 8, st);
-    if (e == hipSuccess && m > 0)
-        e = b->deriv_f ? scvx::launch_nav_cov_f32(ctx, B, K, b->x, b->u, b->deriv_f, b->track_gain, dz.p, dn0.p, m, H, rm, w14, dcr.p, dnr.p,
-                                                  nullptr, nullptr, dk.p, nullptr, st)
-                       : scvx::launch_nav_cov(ctx, B, K, b->x, b->u, b->deriv, b->track_gain, dz.p, dn0.p, m, H, rm, w14, dcr.p, dnr.p, nullptr,
-                                              nullptr, dk.p, nullptr, st);
-    if (e == hipSuccess)
-        e = b->deriv_f ? scvx::launch_track_mc_nav_f32(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv_f,
-                                                       dk.p, dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p,
-                                                       dnv.p, df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp, rg)
-                       : scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc.p, di.p, de.p, w14, b->deriv, dk.p,
-                                                   dcn.p, dxi.p, dnu.p, m, H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p,
-                                                   df.p, dl.p, d0.p, dfe.p, dnk.p, st, mqp, rg);
-    auto out = [&](double* h, scvx::DevBuf<double>& d, size_t n) {
-        if (e == hipSuccess && h) e = hipMemcpyAsync(h, d.p, n * 8, hipMemcpyDeviceToHost, st);
-    };
-    out(mcrep, dr, nr), out(xmean, dm, nm), out(xcov, dv, nc), out(jmean, djm, (size_t)B * 28), out(jcov, djc, (size_t)B * 784);
-    out(mcnav, dnv, (size_t)B * SCVX_NAV_NREP), out(flights, df, nf), out(xland, dl, nl), out(dx0, d0, nl), out(navfed, dfe, nfed);
-    out(navK, dnk, nl), out(flightq, dfq, nfq), out(pathq, dpq, npq), out(pathv, dpv, npv);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_track_mc_nav_q: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    mq.nq = nq, mq.ranks = ranks, mq.flightq = s.out(flightq, d.flightq), mq.pathq = s.out(pathq, d.pathq), mq.pathv = s.out(pathv, d.pathv);
+    s.launch([&] { return hipMemsetAsync(dz, 0, d.c14 * 8, s.st); });
+    if (m > 0)
+        s.launch([&] {
+            return scvx::launch_nav_cov(ctx, B, K, b->x, b->u, b->tiles(), b->track_gain, dz, dn0, m, H, rm, w14, dcr, dnr, nullptr, nullptr, dk,
+                                        nullptr, s.st);
+        });
+    s.launch([&] {
+        return scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc, di, de, w14, b->tiles(), dk, dcn, dxi, dnu, m, H,
+                                         rm, nsub, flags, tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st,
+                                         (flightq || pathq || pathv) ? &mq : nullptr, rg);
+    });
+    return s.finish("scvx_batch_track_mc_nav_q");
 }
 
 int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1232,38 +1127,15 @@ int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, cons
     if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
     if ((rc = scvx::check_nav_model(ctx, m, H, rm))) return rc;
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const size_t n = 14 + b->NU, N = n + 14;
-    const size_t n0 = (size_t)b->B * 196, nr = (size_t)b->B * SCVX_COV_NREP, nn = (size_t)b->B * SCVX_NAV_NREP,
-                 ns = (size_t)b->B * (b->K + 1) * n, nv = (size_t)b->B * (b->K + 1) * 14, nk = (size_t)b->B * b->K * 14 * m,
-                 nj = (size_t)b->B * (b->K + 1) * N * N;
-    const bool wk = kf && m > 0;
-    scvx::DevBuf<double> d0, dn, dr, dq, ds, dv, dk, dj;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&d0.p, n0 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dn.p, n0 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dr.p, nr * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dq.p, nn * 8);
-    if (e == hipSuccess && sig) e = hipMalloc((void**)&ds.p, ns * 8);
-    if (e == hipSuccess && navsig) e = hipMalloc((void**)&dv.p, nv * 8);
-    if (e == hipSuccess && wk) e = hipMalloc((void**)&dk.p, nk * 8);
-    if (e == hipSuccess && joint) e = hipMalloc((void**)&dj.p, nj * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dn.p, N0, n0 * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = b->deriv_f ? scvx::launch_nav_cov_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, d0.p, dn.p, m, H, rm, w14, dr.p,
-                                                  dq.p, ds.p, dv.p, dk.p, dj.p, st)
-                       : scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, d0.p, dn.p, m, H, rm, w14, dr.p, dq.p,
-                                              ds.p, dv.p, dk.p, dj.p, st);
-    if (e == hipSuccess && report) e = hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && navrep) e = hipMemcpyAsync(navrep, dq.p, nn * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && sig) e = hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && navsig) e = hipMemcpyAsync(navsig, dv.p, nv * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && wk) e = hipMemcpyAsync(kf, dk.p, nk * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && joint) e = hipMemcpyAsync(joint, dj.p, nj * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(ctx, SCVX_ERR_HIP, std::string("scvx_batch_nav_cov: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    const scvx::Dims d(b->B, b->K, b->NU, 0, m);
+    scvx::Staging s(ctx);
+    const double *d0 = s.in(S0, d.c14), *dn = s.in(N0, d.c14);
+    double *dr = s.out_always(report, d.crep), *dq = s.out_always(navrep, d.nrep), *ds = s.out(sig, d.sig), *dv = s.out(navsig, d.navsig),
+           *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint);
+    s.launch([&] {
+        return scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st);
+    });
+    return s.finish("scvx_batch_nav_cov");
 }
 
 int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
@@ -1407,13 +1279,11 @@ static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU,
     SCVX_HIP(ctx, hipStreamSynchronize(st));   // the caller's S0 (and N0) is consumed when the call returns; nothing comes back
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     if (nav)
-        SCVX_HIP(ctx, b->deriv_f ? scvx::launch_nav_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, b->nav_n0, nav->m,
-                                                             nav->H, nav->rm, w14, b->cov_rep, b->nav_rep, b->cov_psig, st)
-                                 : scvx::launch_nav_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H,
-                                                         nav->rm, w14, b->cov_rep, b->nav_rep, b->cov_psig, st));
+        SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H, nav->rm,
+                                           w14, b->cov_rep, b->nav_rep, nullptr, nullptr, nullptr, nullptr, st, b->cov_psig));
     else
-        SCVX_HIP(ctx, b->deriv_f ? scvx::launch_cov_psig_f32(ctx, b->B, b->K, b->x, b->u, b->deriv_f, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st)
-                                 : scvx::launch_cov_psig(ctx, b->B, b->K, b->x, b->u, b->deriv, b->track_gain, b->cov_s0, w14, b->cov_rep, b->cov_psig, st));
+        SCVX_HIP(ctx, scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, w14, b->cov_rep, nullptr, nullptr,
+                                       nullptr, st, b->cov_psig));
     const bool path = (which & ~(unsigned)SCVX_MARGIN_THRUST) != 0u;
     if (path && !b->pmarg_on)   // "as they are" of an unselected path constraint of a batch that has none: 0
         SCVX_HIP(ctx, hipMemsetAsync(b->pmarg, 0, (size_t)b->B * (b->K + 1) * SCVX_PMARG_N * 8, st));

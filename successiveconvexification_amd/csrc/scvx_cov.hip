@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <limits>
 #include "scvx_internal.hpp"
+#include "scvx_stage.hpp"
 
 namespace scvx {
 
@@ -359,25 +360,11 @@ static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* 
     return hipGetLastError();
 }
 
-hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
-                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
-    return launch_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, w, report, sig, covK, cov, st);
-}
-
-hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                          const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st) {
-    return launch_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, w, report, sig, covK, cov, st);
-}
-
-// the same launch with the per-node s of the path functions kept (psig [B][K+1][SCVX_PSIG_N], not null)
-hipError_t launch_cov_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
-                           const double* S0, const double* w, double* report, double* psig, hipStream_t st) {
-    return launch_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, w, report, nullptr, nullptr, nullptr, st, psig);
-}
-
-hipError_t launch_cov_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                               const double* S0, const double* w, double* report, double* psig, hipStream_t st) {
-    return launch_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, w, report, nullptr, nullptr, nullptr, st, psig);
+hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
+                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
+                      double* psig) {
+    return deriv.d ? launch_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, w, report, sig, covK, cov, st, psig)
+                   : launch_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, w, report, sig, covK, cov, st, psig);
 }
 
 int check_cov_noise(scvx_ctx* ctx, const double* w) {
@@ -408,8 +395,8 @@ int scvx_cov_propagate_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, con
     int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
     if (rc) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev, sig_dev, covK_dev, cov_dev,
-                                   ctx->stream));
+    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, sig_dev,
+                                   covK_dev, cov_dev, ctx->stream));
     return SCVX_OK;
 }
 
@@ -419,7 +406,8 @@ int scvx_cov_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, co
     if (rc) return rc;
     if (!psig_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "cov: null buffer (psig)");
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_cov_psig(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev, psig_dev, ctx->stream));
+    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, nullptr,
+                                   nullptr, nullptr, ctx->stream, psig_dev));
     return SCVX_OK;
 }
 
@@ -428,63 +416,26 @@ int scvx_cov_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, c
     int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
     if (rc) return rc;
     if (!psig) return scvx::fail(ctx, SCVX_ERR_ARG, "cov: null buffer (psig)");
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
-                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, np = (size_t)B * (K + 1) * SCVX_PSIG_N;
-    scvx::DevBuf<double> dx, du, dd, dg, d0, dr, dp;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_cov_psig(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, w14, dr.p, dp.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(psig, dp.p, np * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14);
+    double *dr = s.out(report, d.crep), *dp = s.out(psig, d.psig);
+    s.launch([&] {
+        return scvx::launch_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, w14, dr, nullptr, nullptr, nullptr, s.st, dp);
+    });
+    return s.finish("scvx_cov_path_sigma_f64_host");
 }
 
 int scvx_cov_propagate_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                                 const double* S0, const double* w14, double* report, double* sig, double* covK, double* cov) {
     int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
-                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, ns = (size_t)B * (K + 1) * n,
-                 nk = (size_t)B * n * n, nc = (size_t)B * (K + 1) * n * n;
-    scvx::DevBuf<double> dx, du, dd, dg, d0, dr, ds, dk, dc;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    if (sig) SCVX_HIP(ctx, hipMalloc((void**)&ds.p, ns * 8));
-    if (covK) SCVX_HIP(ctx, hipMalloc((void**)&dk.p, nk * 8));
-    if (cov) SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nc * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, w14, dr.p, ds.p, dk.p, dc.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    if (sig) SCVX_HIP(ctx, hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st));
-    if (covK) SCVX_HIP(ctx, hipMemcpyAsync(covK, dk.p, nk * 8, hipMemcpyDeviceToHost, st));
-    if (cov) SCVX_HIP(ctx, hipMemcpyAsync(cov, dc.p, nc * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14);
+    double *dr = s.out(report, d.crep), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK), *dc = s.out(cov, d.cov);
+    s.launch([&] { return scvx::launch_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, w14, dr, ds, dk, dc, s.st); });
+    return s.finish("scvx_cov_propagate_f64_host");
 }
 
 }  // extern "C"

@@ -70,13 +70,11 @@ PathK path_constants(const scvx_problem& P);
 __device__ __forceinline__ double nan_max(double a, double v) { return (v > a || v != v) ? v : a; }
 __device__ __forceinline__ double nan_min(double a, double v) { return (v < a || v != v) ? v : a; }
 
-// a device buffer of one host-side call, freed when the call returns
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
+// the derivative tiles of a launch that reads them in either format: double, or float as scvx_batch_set_linearization_f32 stores them;
+// exactly one member is set
+struct Tiles {
+    const double* d = nullptr;
+    const float* f = nullptr;
 };
 
 // Flight check (scvx_flight.hip): report[B][SCVX_FLIGHT_NREP], xfly[B][K+1][14] or nullptr; one lane per trajectory, dt = 1 / (K + 1).
@@ -85,13 +83,11 @@ hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, con
 // argument checks shared by scvx_flight_check_f64[_host] and scvx_batch_flight_check (scvx_api.hip)
 int check_flight(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, int nsub, int mode, const void* report);
 
-// Plan tracking (scvx_track.hip).  Gains: one wavefront per trajectory over the derivative tiles (double, or float as
-// scvx_batch_set_linearization_f32 stores them); gain[B][K][NU][14+NU], p0[B][14+NU][14+NU] or nullptr; q / r / qf are host arrays.
+// Plan tracking (scvx_track.hip).  Gains: one wavefront per trajectory over the derivative tiles; gain[B][K][NU][14+NU],
+// p0[B][14+NU][14+NU] or nullptr; q / r / qf are host arrays.
 // Closed-loop flight (the flight check's kernel with TRACK set, scvx_flight.hip): dx0[B][14], xfly[B][K+1][14], ufly[B][K+1][NU] or nullptr.
-hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, const double* deriv, const double* q, const double* r, const double* qf,
+hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, Tiles deriv, const double* q, const double* r, const double* qf,
                               double* gain, double* p0, hipStream_t st);
-hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float* deriv, const double* q, const double* r,
-                                  const double* qf, double* gain, double* p0, hipStream_t st);
 hipError_t launch_track_fly(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, const double* gain,
                             const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly, hipStream_t st);
 // the same with the law fed a navigation estimate: nav[B][K][14], the estimate's error at node k (never nullptr)
@@ -117,59 +113,38 @@ int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void
                    const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
                    const void* mcrep, const void* xmean, const void* xcov);
 void mc_workspace_free(scvx_ctx* ctx);
-// The same flown on a navigation estimate (scvx_mc_nav.hip): deriv[B][K][14+2NU+1][14] (double or float), kf[B][K][14][m] (nullptr with
+// The same flown on a navigation estimate (scvx_mc_nav.hip): deriv[B][K][14+2NU+1][14], kf[B][K][14][m] (nullptr with
 // m = 0), CN[B][14][14], xin[S][14], nud[S][K][m] (nullptr with m = 0); w, H, rm: host arrays (w the VARIANCE) or nullptr; jmean[B][28],
 // jcov[B][28][28], mcnav[B][SCVX_NAV_NREP]; navfed[B][S][K][14], navK[B][S][14] or nullptr.
 hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
-                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, hipStream_t st, const McQ* q = nullptr, const McRng* rng = nullptr);
-hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                                   const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
-                                   const float* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                                   const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                                   double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                                   double* navfed, double* navK, hipStream_t st, const McQ* q = nullptr, const McRng* rng = nullptr);
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w, Tiles deriv,
+                               const double* kf, const double* CN, const double* xin, const double* nud, int m, const double* H,
+                               const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                               double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
+                               double* navK, hipStream_t st, const McQ* q = nullptr, const McRng* rng = nullptr);
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
                        const void* C0, const void* xi0, const void* eta, const double* w, const void* deriv, const void* kf,
                        const void* CN, const void* xin, const void* nud, int m, const double* H, const double* rm, int nsub, int flags,
                        double tol, const void* mcrep, const void* xmean, const void* xcov, const void* jmean, const void* jcov,
                        const void* mcnav);
 
-// Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles (double or float) and the gains;
-// S0[B][14][14]; w: host array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.
-hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
-                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
-hipError_t launch_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                          const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st);
-// ... with the per-node s of the five path functions kept: psig [B][K+1][SCVX_PSIG_N] (scvx_cov_path_sigma_f64)
-hipError_t launch_cov_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
-                           const double* S0, const double* w, double* report, double* psig, hipStream_t st);
-hipError_t launch_cov_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                               const double* S0, const double* w, double* report, double* psig, hipStream_t st);
+// Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles and the gains; S0[B][14][14]; w: host
+// array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.  With psig
+// [B][K+1][SCVX_PSIG_N] the per-node s of the five path functions are kept (scvx_cov_path_sigma_f64) and sig, covK, cov are nullptr.
+hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
+                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
+                      double* psig = nullptr);
 int check_cov_noise(scvx_ctx* ctx, const double* w);
 int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
               const double* w, const void* report);
 
 // Navigation-error covariance analysis (scvx_nav.hip): cov_propagate_kernel on the joint [z; eps], N = 14 + NU + 14.  N0[B][14][14];
 // m measurements per node, H[m][14] and rm[m] host arrays (nullptr with m = 0); navrep[B][SCVX_NAV_NREP]; sig[B][K+1][n],
-// navsig[B][K+1][14], kf[B][K][14][m], joint[B][K+1][N][N] or nullptr.
-hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+// navsig[B][K+1][14], kf[B][K][14][m], joint[B][K+1][N][N] or nullptr.  With psig [B][K+1][SCVX_PSIG_N] the per-node s of the five path
+// functions are kept, read off the truth block Xi_k[z,z] (scvx_nav_path_sigma_f64), and sig, navsig, kf, joint are nullptr.
+hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st);
-hipError_t launch_nav_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                              const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
-                              double* report, double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st);
-// ... with the per-node s of the five path functions kept, read off the truth block Xi_k[z,z]: psig [B][K+1][SCVX_PSIG_N], never nullptr
-// (scvx_nav_path_sigma_f64)
-hipError_t launch_nav_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
-                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                           double* navrep, double* psig, hipStream_t st);
-hipError_t launch_nav_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                               const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
-                               double* report, double* navrep, double* psig, hipStream_t st);
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig = nullptr);
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm);
 
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],

@@ -11,6 +11,7 @@
 // flight with order statistics of the flight columns and of the rows of pathv; flights and pathv live in a second workspace of the
 // context when only their order statistics are asked for.  The entry points without _rng launch the instantiations with RNG off;
 // mc_draws_kernel writes out the draws the RNG instantiations consume.
+#include "scvx_stage.hpp"
 #include "scvx_mc_fly.hpp"   // the flying kernel, mc_finish_front, the noise and the launch, shared with scvx_mc_nav.hip
 
 namespace scvx {
@@ -223,21 +224,11 @@ int scvx_mc_draws_f64(scvx_ctx* ctx, const scvx_mc_rng* rng, int P, int S, int K
 int scvx_mc_draws_f64_host(scvx_ctx* ctx, const scvx_mc_rng* rng, int P, int S, int K, double* xi0, double* eta, double* xin, double* nud) {
     int rc = scvx::check_mc_draws(ctx, rng, P, S, K);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n0 = (size_t)P * S * 14, nk = n0 * K;
-    scvx::DevBuf<double> d0, d1, d2, d3;
-    if (xi0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
-    if (eta) SCVX_HIP(ctx, hipMalloc((void**)&d1.p, nk * 8));
-    if (xin) SCVX_HIP(ctx, hipMalloc((void**)&d2.p, n0 * 8));
-    if (nud) SCVX_HIP(ctx, hipMalloc((void**)&d3.p, nk * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, scvx::launch_mc_draws(*rng, P, S, K, d0.p, d1.p, d2.p, d3.p, st));
-    if (xi0) SCVX_HIP(ctx, hipMemcpyAsync(xi0, d0.p, n0 * 8, hipMemcpyDeviceToHost, st));
-    if (eta) SCVX_HIP(ctx, hipMemcpyAsync(eta, d1.p, nk * 8, hipMemcpyDeviceToHost, st));
-    if (xin) SCVX_HIP(ctx, hipMemcpyAsync(xin, d2.p, n0 * 8, hipMemcpyDeviceToHost, st));
-    if (nud) SCVX_HIP(ctx, hipMemcpyAsync(nud, d3.p, nk * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    scvx::Staging s(ctx);
+    double *d0 = s.out(xi0, n0), *d1 = s.out(eta, nk), *d2 = s.out(xin, n0), *d3 = s.out(nud, nk);
+    s.launch([&] { return scvx::launch_mc_draws(*rng, P, S, K, d0, d1, d2, d3, s.st); });
+    return s.finish("scvx_mc_draws_f64_host");
 }
 
 int scvx_track_mc_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
@@ -310,55 +301,19 @@ static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, 
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
-                 npv = (size_t)B * (K + 1) * SCVX_PSIG_N * S;
-    scvx::DevBuf<double> dfq, dpq, dpv;
-    if (flightq) SCVX_HIP(ctx, hipMalloc((void**)&dfq.p, nfq * 8));
-    if (pathq) SCVX_HIP(ctx, hipMalloc((void**)&dpq.p, npq * 8));
-    if (pathv) SCVX_HIP(ctx, hipMalloc((void**)&dpv.p, npv * 8));
-    scvx::McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = dfq.p, q.pathq = dpq.p, q.pathv = dpv.p;
-    const bool any = flightq || pathq || pathv;
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, ng = (size_t)B * K * NU * n, nc = (size_t)B * 196,
-                 ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
-                 nf = (size_t)B * S * SCVX_FLIGHT_NREP, nl = (size_t)B * S * 14;
-    scvx::DevBuf<double> dx, du, ds, dg, dc, di, de, dr, dm, dv, df, dl, d0;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nc * 8));
-    if (xi0) SCVX_HIP(ctx, hipMalloc((void**)&di.p, ni * 8));
-    if (eta) SCVX_HIP(ctx, hipMalloc((void**)&de.p, ne * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dm.p, nm * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dv.p, nc * 8));
-    if (flights) SCVX_HIP(ctx, hipMalloc((void**)&df.p, nf * 8));
-    if (xland) SCVX_HIP(ctx, hipMalloc((void**)&dl.p, nl * 8));
-    if (dx0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, nl * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dc.p, C0, nc * 8, hipMemcpyHostToDevice, st));
-    if (xi0) SCVX_HIP(ctx, hipMemcpyAsync(di.p, xi0, ni * 8, hipMemcpyHostToDevice, st));
-    if (eta) SCVX_HIP(ctx, hipMemcpyAsync(de.p, eta, ne * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, dx.p, du.p, ds.p, dg.p, dc.p, di.p, de.p, sw14, nsub, flags, tol, dr.p, dm.p, dv.p,
-                                        df.p, dl.p, d0.p, st, any ? &q : nullptr, rg));
-    if (flightq) SCVX_HIP(ctx, hipMemcpyAsync(flightq, dfq.p, nfq * 8, hipMemcpyDeviceToHost, st));
-    if (pathq) SCVX_HIP(ctx, hipMemcpyAsync(pathq, dpq.p, npq * 8, hipMemcpyDeviceToHost, st));
-    if (pathv) SCVX_HIP(ctx, hipMemcpyAsync(pathv, dpv.p, npv * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(mcrep, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(xmean, dm.p, nm * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(xcov, dv.p, nc * 8, hipMemcpyDeviceToHost, st));
-    if (flights) SCVX_HIP(ctx, hipMemcpyAsync(flights, df.p, nf * 8, hipMemcpyDeviceToHost, st));
-    if (xland) SCVX_HIP(ctx, hipMemcpyAsync(xland, dl.p, nl * 8, hipMemcpyDeviceToHost, st));
-    if (dx0) SCVX_HIP(ctx, hipMemcpyAsync(dx0, d0.p, nl * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const Dims d(B, K, scvx_control_dim(ctx), S, 0, nq);
+    Staging s(ctx);
+    McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = s.out(flightq, d.flightq), q.pathq = s.out(pathq, d.pathq), q.pathv = s.out(pathv, d.pathv);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dc = s.in(C0, d.c14),
+                 *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta);
+    double *dr = s.out(mcrep, d.mcrep), *dm = s.out(xmean, d.b14), *dv = s.out(xcov, d.c14), *df = s.out(flights, d.flights),
+           *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14);
+    s.launch([&] {
+        return launch_track_mc(ctx, B, K, S, dx, du, ds, dg, dc, di, de, sw14, nsub, flags, tol, dr, dm, dv, df, dl, d0, s.st,
+                               (flightq || pathq || pathv) ? &q : nullptr, rg);
+    });
+    return s.finish("scvx_track_mc_q_f64_host");
 }
 
 }  // namespace scvx

@@ -16,6 +16,7 @@
 // mc_nav_finish_kernel (one block per plan) combines the partial rows [MCN_NP] in block order.  The row is the plain one, then the sums
 // of eps_K [14] and of the upper triangle of [e; eps_K][e; eps_K]' [406], and the largest |eps+_k|_inf fed; mcrep, xmean and xcov come
 // from mc_finish_front, the expressions mc_finish_kernel uses.
+#include "scvx_stage.hpp"
 #include "scvx_mc_fly.hpp"
 
 namespace scvx {
@@ -116,23 +117,17 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
 }
 
 hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
-                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
-    return launch_track_mc_nav_t<double>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                         tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q, rng);
-}
-
-hipError_t launch_track_mc_nav_f32(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                                   const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
-                                   const float* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                                   const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                                   double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                                   double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
-    return launch_track_mc_nav_t<float>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q, rng);
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w, Tiles deriv,
+                               const double* kf, const double* CN, const double* xin, const double* nud, int m, const double* H,
+                               const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                               double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
+                               double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
+    return deriv.d ? launch_track_mc_nav_t<double>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv.d, kf, CN, xin, nud, m, H, rm, nsub,
+                                                   flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st,
+                                                   q, rng)
+                   : launch_track_mc_nav_t<float>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv.f, kf, CN, xin, nud, m, H, rm, nsub,
+                                                  flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q,
+                                                  rng);
 }
 
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
@@ -175,10 +170,10 @@ static int track_mc_nav_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* 
     q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
     const bool any = flightq_dev || pathq_dev || pathv_dev;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev,
-                                            kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev,
-                                            jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev,
-                                            ctx->stream, any ? &q : nullptr, rg));
+    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14,
+                                            scvx::Tiles{deriv_dev, nullptr}, kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol,
+                                            mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev,
+                                            navfed_dev, navK_dev, ctx->stream, any ? &q : nullptr, rg));
     return SCVX_OK;
 }
 
@@ -285,45 +280,21 @@ static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double*
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    scvx::DevBuf<double> dfq, dpq, dpv;
-    const size_t nfq = (size_t)B * SCVX_FLIGHT_NREP * nq, npq = (size_t)B * (K + 1) * SCVX_PSIG_N * nq,
-                 npv = (size_t)B * (K + 1) * SCVX_PSIG_N * S;
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, ng = (size_t)B * K * NU * n, nc = (size_t)B * 196,
-                 ni = (size_t)S * 14, ne = (size_t)S * K * 14, nr = (size_t)B * SCVX_MC_NREP, nm = (size_t)B * 14,
-                 nf = (size_t)B * S * SCVX_FLIGHT_NREP, nl = (size_t)B * S * 14, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
-                 nk = (size_t)B * K * 14 * m, nn = (size_t)S * K * m, nj = (size_t)B * 28, njc = (size_t)B * 784,
-                 nv = (size_t)B * SCVX_NAV_NREP, nfed = (size_t)B * S * K * 14;
-    scvx::DevBuf<double> dx, du, ds, dg, dc, di, de, dd, dk, dcn, dxi, dnu, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk;
-    const struct { scvx::DevBuf<double>* b; const double* h; size_t n; bool want; } in[] = {
-        {&dx, x, nx, true},   {&du, u, nu, true},       {&ds, sigma, (size_t)B, true}, {&dg, gain, ng, true}, {&dc, C0, nc, true},
-        {&di, xi0, ni, xi0 != nullptr}, {&de, eta, ne, eta != nullptr}, {&dd, deriv, nd, true},  {&dk, kf, nk, m > 0},  {&dcn, CN, nc, true},
-        {&dxi, xin, ni, xin != nullptr}, {&dnu, nud, nn, m > 0 && nud != nullptr}};
-    const struct { scvx::DevBuf<double>* b; double* h; size_t n; bool want; } out[] = {
-        {&dr, mcrep, nr, true},  {&dm, xmean, nm, true},  {&dv, xcov, nc, true},  {&djm, jmean, nj, true},
-        {&djc, jcov, njc, true}, {&dnv, mcnav, nv, true}, {&df, flights, nf, flights != nullptr}, {&dl, xland, nl, xland != nullptr},
-        {&d0, dx0, nl, dx0 != nullptr}, {&dfe, navfed, nfed, navfed != nullptr}, {&dnk, navK, nl, navK != nullptr},
-        {&dfq, flightq, nfq, flightq != nullptr}, {&dpq, pathq, npq, pathq != nullptr}, {&dpv, pathv, npv, pathv != nullptr}};
-    hipStream_t st = ctx->stream;
-    for (const auto& a : in)
-        if (a.want) {
-            SCVX_HIP(ctx, hipMalloc((void**)&a.b->p, a.n * 8));
-            SCVX_HIP(ctx, hipMemcpyAsync(a.b->p, a.h, a.n * 8, hipMemcpyHostToDevice, st));
-        }
-    for (const auto& a : out)
-        if (a.want) SCVX_HIP(ctx, hipMalloc((void**)&a.b->p, a.n * 8));
-    scvx::McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = dfq.p, q.pathq = dpq.p, q.pathv = dpv.p;
-    hipError_t e = scvx::launch_track_mc_nav(ctx, B, K, S, dx.p, du.p, ds.p, dg.p, dc.p, di.p, de.p, w14, dd.p, dk.p, dcn.p, dxi.p, dnu.p, m,
-                                             H, rm, nsub, flags, tol, dr.p, dm.p, dv.p, djm.p, djc.p, dnv.p, df.p, dl.p, d0.p, dfe.p,
-                                             dnk.p, st, (flightq || pathq || pathv) ? &q : nullptr, rg);
-    for (const auto& a : out)
-        if (e == hipSuccess && a.want) e = hipMemcpyAsync(a.h, a.b->p, a.n * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return scvx::fail(ctx, SCVX_ERR_HIP, std::string("scvx_track_mc_nav_q_f64_host: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    const Dims d(B, K, scvx_control_dim(ctx), S, m, nq);
+    Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dc = s.in(C0, d.c14),
+                 *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta), *dd = s.in(deriv, d.deriv), *dk = s.in(m > 0 ? kf : nullptr, d.kf),
+                 *dcn = s.in(CN, d.c14), *dxi = s.in(xin, d.xi), *dnu = s.in(m > 0 ? nud : nullptr, d.nud);
+    double *dr = s.out(mcrep, d.mcrep), *dm = s.out(xmean, d.b14), *dv = s.out(xcov, d.c14), *djm = s.out(jmean, d.jmean),
+           *djc = s.out(jcov, d.jcov), *dnv = s.out(mcnav, d.nrep), *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14),
+           *d0 = s.out(dx0, d.s14), *dfe = s.out(navfed, d.fed), *dnk = s.out(navK, d.s14);
+    McQ q;
+    q.nq = nq, q.ranks = ranks, q.flightq = s.out(flightq, d.flightq), q.pathq = s.out(pathq, d.pathq), q.pathv = s.out(pathv, d.pathv);
+    s.launch([&] {
+        return launch_track_mc_nav(ctx, B, K, S, dx, du, ds, dg, dc, di, de, w14, Tiles{dd, nullptr}, dk, dcn, dxi, dnu, m, H, rm, nsub, flags,
+                                   tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st, (flightq || pathq || pathv) ? &q : nullptr, rg);
+    });
+    return s.finish("scvx_track_mc_nav_q_f64_host");
 }
 
 }  // namespace scvx

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <limits>
 #include "scvx_internal.hpp"
+#include "scvx_stage.hpp"
 
 namespace scvx {
 
@@ -438,31 +439,13 @@ static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, int B, int K, const doub
     return hipGetLastError();
 }
 
-hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st) {
-    return launch_nav_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st);
-}
-
-hipError_t launch_nav_cov_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                              const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
-                              double* report, double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st) {
-    return launch_nav_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st);
-}
-
-// the same launch with the per-node s of the path functions kept (psig [B][K+1][SCVX_PSIG_N], not null)
-hipError_t launch_nav_psig(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
-                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                           double* navrep, double* psig, hipStream_t st) {
-    return launch_nav_cov_t<double>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, nullptr, nullptr, nullptr, nullptr,
-                                    st, psig);
-}
-
-hipError_t launch_nav_psig_f32(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const float* deriv, const double* gain,
-                               const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w,
-                               double* report, double* navrep, double* psig, hipStream_t st) {
-    return launch_nav_cov_t<float>(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w, report, navrep, nullptr, nullptr, nullptr, nullptr,
-                                   st, psig);
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig) {
+    return deriv.d ? launch_nav_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint,
+                                              st, psig)
+                   : launch_nav_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st,
+                                             psig);
 }
 
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm) {
@@ -495,8 +478,8 @@ int scvx_nav_cov_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const dou
     int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
     if (rc) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev,
-                                       sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream));
+    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
+                                       report_dev, navrep_dev, sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream));
     return SCVX_OK;
 }
 
@@ -507,8 +490,8 @@ int scvx_nav_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, co
     if (rc) return rc;
     if (!psig_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "nav: null buffer (psig)");
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_nav_psig(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev,
-                                        psig_dev, ctx->stream));
+    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
+                                       report_dev, navrep_dev, nullptr, nullptr, nullptr, nullptr, ctx->stream, psig_dev));
     return SCVX_OK;
 }
 
@@ -518,34 +501,16 @@ int scvx_nav_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, c
     int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
     if (rc) return rc;
     if (!psig) return scvx::fail(ctx, SCVX_ERR_ARG, "nav: null buffer (psig)");
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
-                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, nn = (size_t)B * SCVX_NAV_NREP,
-                 np = (size_t)B * (K + 1) * SCVX_PSIG_N;
-    scvx::DevBuf<double> dx, du, dd, dg, d0, dn, dr, dq, dp;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dn.p, n0 * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dq.p, nn * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dn.p, N0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_nav_psig(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, dn.p, m, H, rm, w14, dr.p, dq.p, dp.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(navrep, dq.p, nn * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(psig, dp.p, np * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
+                 *dn = s.in(N0, d.c14);
+    double *dr = s.out(report, d.crep), *dq = s.out(navrep, d.nrep), *dp = s.out(psig, d.psig);
+    s.launch([&] {
+        return scvx::launch_nav_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, dn, m, H, rm, w14, dr, dq, nullptr, nullptr, nullptr,
+                                    nullptr, s.st, dp);
+    });
+    return s.finish("scvx_nav_path_sigma_f64_host");
 }
 
 int scvx_nav_cov_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
@@ -553,42 +518,16 @@ int scvx_nav_cov_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const do
                           double* navrep, double* sig, double* navsig, double* kf, double* joint) {
     int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU, N = n + 14;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nd = (size_t)B * K * 14 * (14 + 2 * NU + 1),
-                 ng = (size_t)B * K * NU * n, n0 = (size_t)B * 196, nr = (size_t)B * SCVX_COV_NREP, nn = (size_t)B * SCVX_NAV_NREP,
-                 ns = (size_t)B * (K + 1) * n, nv = (size_t)B * (K + 1) * 14, nk = (size_t)B * K * 14 * m,
-                 nj = (size_t)B * (K + 1) * N * N;
-    const bool wk = kf && m > 0;
-    scvx::DevBuf<double> dx, du, dd, dg, d0, dn, dr, dq, ds, dv, dk, dj;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&d0.p, n0 * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dn.p, n0 * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dq.p, nn * 8));
-    if (sig) SCVX_HIP(ctx, hipMalloc((void**)&ds.p, ns * 8));
-    if (navsig) SCVX_HIP(ctx, hipMalloc((void**)&dv.p, nv * 8));
-    if (wk) SCVX_HIP(ctx, hipMalloc((void**)&dk.p, nk * 8));
-    if (joint) SCVX_HIP(ctx, hipMalloc((void**)&dj.p, nj * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(d0.p, S0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dn.p, N0, n0 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, dx.p, du.p, dd.p, dg.p, d0.p, dn.p, m, H, rm, w14, dr.p, dq.p, ds.p, dv.p, dk.p, dj.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(navrep, dq.p, nn * 8, hipMemcpyDeviceToHost, st));
-    if (sig) SCVX_HIP(ctx, hipMemcpyAsync(sig, ds.p, ns * 8, hipMemcpyDeviceToHost, st));
-    if (navsig) SCVX_HIP(ctx, hipMemcpyAsync(navsig, dv.p, nv * 8, hipMemcpyDeviceToHost, st));
-    if (wk) SCVX_HIP(ctx, hipMemcpyAsync(kf, dk.p, nk * 8, hipMemcpyDeviceToHost, st));
-    if (joint) SCVX_HIP(ctx, hipMemcpyAsync(joint, dj.p, nj * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx), 0, m);
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
+                 *dn = s.in(N0, d.c14);
+    double *dr = s.out(report, d.crep), *dq = s.out(navrep, d.nrep), *ds = s.out(sig, d.sig), *dv = s.out(navsig, d.navsig),
+           *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint);
+    s.launch([&] {
+        return scvx::launch_nav_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st);
+    });
+    return s.finish("scvx_nav_cov_f64_host");
 }
 
 int scvx_track_fly_nav_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev,
@@ -608,33 +547,13 @@ int scvx_track_fly_nav_f64_host(scvx_ctx* ctx, int B, int K, const double* x, co
     int rc = scvx::check_track_fly(ctx, B, K, x, u, sigma, gain, nsub, flags, report);
     if (rc) return rc;
     if (!nav) return scvx::fail(ctx, SCVX_ERR_ARG, "track fly nav: null nav (without one, call scvx_track_fly_f64_host)");
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP,
-                 ng = (size_t)B * K * NU * n, nv = (size_t)B * K * 14;
-    scvx::DevBuf<double> dx, du, ds, dg, d0, dv, dr, df, dc;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dv.p, nv * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    if (dx0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, (size_t)B * 14 * 8));
-    if (xfly) SCVX_HIP(ctx, hipMalloc((void**)&df.p, nx * 8));
-    if (ufly) SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nu * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dv.p, nav, nv * 8, hipMemcpyHostToDevice, st));
-    if (dx0) SCVX_HIP(ctx, hipMemcpyAsync(d0.p, dx0, (size_t)B * 14 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_track_fly_nav(ctx, B, K, dx.p, du.p, ds.p, dg.p, d0.p, dv.p, nsub, flags, dr.p, df.p, dc.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    if (xfly) SCVX_HIP(ctx, hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st));
-    if (ufly) SCVX_HIP(ctx, hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dv = s.in(nav, d.seg),
+                 *d0 = s.in(dx0, d.b14);
+    double *dr = s.out(report, d.frep), *df = s.out(xfly, d.x), *dc = s.out(ufly, d.u);
+    s.launch([&] { return scvx::launch_track_fly_nav(ctx, B, K, dx, du, ds, dg, d0, dv, nsub, flags, dr, df, dc, s.st); });
+    return s.finish("scvx_track_fly_nav_f64_host");
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 //     measurement of both paths on those rows.
 // The LDS is dynamic, sized by min(S, QLDS) and nq, so that the small rows do not reserve what an 8,192-row needs.
 #include "scvx_mc.hpp"
+#include "scvx_stage.hpp"
 
 namespace scvx {
 
@@ -161,19 +162,11 @@ int scvx_order_stats_f64(scvx_ctx* ctx, int R, int S, const double* v_dev, size_
 int scvx_order_stats_f64_host(scvx_ctx* ctx, int R, int S, const double* v, size_t ld, size_t inc, int nq, const int* ranks, double* out) {
     int rc = scvx::check_order_stats(ctx, R, S, v, ld, inc, nq, ranks, out);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nv = (size_t)(R - 1) * ld + (size_t)(S - 1) * inc + 1, no = (size_t)R * nq;   // the last row need not be padded
-    scvx::DevBuf<double> dv, dout;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMalloc((void**)&dv.p, nv * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout.p, no * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(dv.p, v, nv * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = scvx::launch_order_stats(R, S, dv.p, ld, 1, 0, inc, nq, ranks, dout.p, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, no * 8, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);   // also on an error: the buffers are freed behind whatever was enqueued
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return scvx::fail(ctx, SCVX_ERR_HIP, std::string("scvx_order_stats_f64_host: ") + hipGetErrorString(e));
-    return SCVX_OK;
+    scvx::Staging s(ctx);
+    const double* dv = s.in(v, (size_t)(R - 1) * ld + (size_t)(S - 1) * inc + 1);   // the last row need not be padded
+    double* dout = s.out(out, (size_t)R * nq);
+    s.launch([&] { return scvx::launch_order_stats(R, S, dv, ld, 1, 0, inc, nq, ranks, dout, s.st); });
+    return s.finish("scvx_order_stats_f64_host");
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 #include "scvx_internal.hpp"
+#include "scvx_stage.hpp"
 
 namespace scvx {
 
@@ -230,14 +231,10 @@ static TrackW pack_weights(const scvx_ctx* ctx, const double* q, const double* r
     return w;
 }
 
-hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, const double* deriv, const double* q, const double* r, const double* qf,
+hipError_t launch_track_gains(const scvx_ctx* ctx, int B, int K, Tiles deriv, const double* q, const double* r, const double* qf,
                               double* gain, double* p0, hipStream_t st) {
-    return launch_gains_t<double>(ctx, B, K, deriv, pack_weights(ctx, q, r, qf), gain, p0, st);
-}
-
-hipError_t launch_track_gains_f32(const scvx_ctx* ctx, int B, int K, const float* deriv, const double* q, const double* r,
-                                  const double* qf, double* gain, double* p0, hipStream_t st) {
-    return launch_gains_t<float>(ctx, B, K, deriv, pack_weights(ctx, q, r, qf), gain, p0, st);
+    const TrackW w = pack_weights(ctx, q, r, qf);
+    return deriv.d ? launch_gains_t<double>(ctx, B, K, deriv.d, w, gain, p0, st) : launch_gains_t<float>(ctx, B, K, deriv.f, w, gain, p0, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -284,7 +281,7 @@ int scvx_track_gains_f64(scvx_ctx* ctx, int B, int K, const double* deriv_dev, c
     int rc = scvx::check_track_gains(ctx, B, K, deriv_dev, q14, rNU, qf14, gain_dev);
     if (rc) return rc;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_gains(ctx, B, K, deriv_dev, q14, rNU, qf14, gain_dev, p0_dev, ctx->stream));
+    SCVX_HIP(ctx, scvx::launch_track_gains(ctx, B, K, scvx::Tiles{deriv_dev, nullptr}, q14, rNU, qf14, gain_dev, p0_dev, ctx->stream));
     return SCVX_OK;
 }
 
@@ -292,20 +289,12 @@ int scvx_track_gains_f64_host(scvx_ctx* ctx, int B, int K, const double* deriv, 
                               const double* qf14, double* gain, double* p0) {
     int rc = scvx::check_track_gains(ctx, B, K, deriv, q14, rNU, qf14, gain);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nd = (size_t)B * K * 14 * (14 + 2 * NU + 1), ng = (size_t)B * K * NU * n, np = (size_t)B * n * n;
-    scvx::DevBuf<double> dd, dg, dp;
-    SCVX_HIP(ctx, hipMalloc((void**)&dd.p, nd * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    if (p0) SCVX_HIP(ctx, hipMalloc((void**)&dp.p, np * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dd.p, deriv, nd * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_track_gains(ctx, B, K, dd.p, q14, rNU, qf14, dg.p, dp.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(gain, dg.p, ng * 8, hipMemcpyDeviceToHost, st));
-    if (p0) SCVX_HIP(ctx, hipMemcpyAsync(p0, dp.p, np * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double* dd = s.in(deriv, d.deriv);
+    double *dg = s.out(gain, d.gain), *dp = s.out(p0, d.p0);
+    s.launch([&] { return scvx::launch_track_gains(ctx, B, K, scvx::Tiles{dd, nullptr}, q14, rNU, qf14, dg, dp, s.st); });
+    return s.finish("scvx_track_gains_f64_host");
 }
 
 int scvx_track_fly_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev,
@@ -323,31 +312,12 @@ int scvx_track_fly_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const 
                             const double* dx0, int nsub, int flags, double* report, double* xfly, double* ufly) {
     int rc = scvx::check_track_fly(ctx, B, K, x, u, sigma, gain, nsub, flags, report);
     if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    const int NU = scvx_control_dim(ctx), n = 14 + NU;
-    const size_t nx = (size_t)B * (K + 1) * 14, nu = (size_t)B * (K + 1) * NU, nr = (size_t)B * SCVX_FLIGHT_NREP,
-                 ng = (size_t)B * K * NU * n;
-    scvx::DevBuf<double> dx, du, ds, dg, d0, dr, df, dc;
-    SCVX_HIP(ctx, hipMalloc((void**)&dx.p, nx * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&du.p, nu * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&ds.p, (size_t)B * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dg.p, ng * 8));
-    SCVX_HIP(ctx, hipMalloc((void**)&dr.p, nr * 8));
-    if (dx0) SCVX_HIP(ctx, hipMalloc((void**)&d0.p, (size_t)B * 14 * 8));
-    if (xfly) SCVX_HIP(ctx, hipMalloc((void**)&df.p, nx * 8));
-    if (ufly) SCVX_HIP(ctx, hipMalloc((void**)&dc.p, nu * 8));
-    hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(dx.p, x, nx * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(du.p, u, nu * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(ds.p, sigma, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(dg.p, gain, ng * 8, hipMemcpyHostToDevice, st));
-    if (dx0) SCVX_HIP(ctx, hipMemcpyAsync(d0.p, dx0, (size_t)B * 14 * 8, hipMemcpyHostToDevice, st));
-    SCVX_HIP(ctx, scvx::launch_track_fly(ctx, B, K, dx.p, du.p, ds.p, dg.p, d0.p, nsub, flags, dr.p, df.p, dc.p, st));
-    SCVX_HIP(ctx, hipMemcpyAsync(report, dr.p, nr * 8, hipMemcpyDeviceToHost, st));
-    if (xfly) SCVX_HIP(ctx, hipMemcpyAsync(xfly, df.p, nx * 8, hipMemcpyDeviceToHost, st));
-    if (ufly) SCVX_HIP(ctx, hipMemcpyAsync(ufly, dc.p, nu * 8, hipMemcpyDeviceToHost, st));
-    SCVX_HIP(ctx, hipStreamSynchronize(st));
-    return SCVX_OK;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *d0 = s.in(dx0, d.b14);
+    double *dr = s.out(report, d.frep), *df = s.out(xfly, d.x), *dc = s.out(ufly, d.u);
+    s.launch([&] { return scvx::launch_track_fly(ctx, B, K, dx, du, ds, dg, d0, nsub, flags, dr, df, dc, s.st); });
+    return s.finish("scvx_track_fly_f64_host");
 }
 
 }  // extern "C"
