@@ -39,10 +39,11 @@ def build(force: bool = False) -> str:
     """Compile liboracle.so (gcc) and liboracle_port.so (g++); recipe: oracle/Makefile."""
     so = os.path.join(_HERE, "liboracle.so")
     port = os.path.join(_HERE, "liboracle_port.so")
-    core = os.path.join(os.path.dirname(_HERE), "successiveconvexification_amd", "csrc", "scvx_ipm_core.hpp")
+    csrc = os.path.join(os.path.dirname(_HERE), "successiveconvexification_amd", "csrc")
+    cores = [os.path.join(csrc, f) for f in ("scvx_ipm_core.hpp", "scvx_threedof_core.hpp")]
     if force or _stale(so, [os.path.join(_HERE, "scvx_oracle.c")]):
         subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
-    if force or _stale(port, [os.path.join(_HERE, "scvx_port.cpp"), core]):
+    if force or _stale(port, [os.path.join(_HERE, "scvx_port.cpp")] + cores):
         subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle_port.so"], stdout=subprocess.DEVNULL)
     return so
 

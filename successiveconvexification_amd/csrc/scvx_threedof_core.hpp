@@ -1024,6 +1024,18 @@ struct Solver {
         each2<4>(T.nb + 1, [&](int p) { return -ru[p]; }, [&](int p, double v) { bu[p] = v; });
         ex.sync();
     }
+    // is every entry of the step (du, dz, ds) finite?  step_pass cannot tell: its step-length search is made of comparisons, and a
+    // comparison with a NaN is false, so a NaN row is taken for one that does not limit the step (alpha = 1).  Asked only
+    // for an iterate inside the near- or almost-optimal band (solve()), where the KKT system is on its pivot floors.
+    SCVX_HD_NI bool finite_step() {
+        cgptr du = w + L.du, dz = w + L.dz, ds = w + L.ds;
+        double fin = 1.0;
+        each(T.nb + 1, [&](int p) { if (!(fabs(du[p]) < INFINITY)) fin = 0.0; });
+        each(T.m, [&](int r) { if (!(fabs(dz[r]) < INFINITY) || !(fabs(ds[r]) < INFINITY)) fin = 0.0; });
+        fin = ex.min(fin);
+        ex.sync();
+        return fin > 0.0;
+    }
     SCVX_HD_NI void take_step(double alpha) {
         gptr u = w + L.u, s = w + L.s, z = w + L.z;
         cgptr du = w + L.du, dz = w + L.dz, ds = w + L.ds;
@@ -1099,7 +1111,11 @@ struct Solver {
             // primal infeasibility shows as a primal residual that stops falling while complementarity and the dual
             // residual converge (the multipliers run off along a Farkas ray, dobj grows without bound)
             if (pres < 0.9 * best_pres) { best_pres = pres; flat = 0; } else flat++;
-            if (flat >= 5 && dres < 1e-6 && relgap < 1e-6) { R.status = TD_INFEASIBLE; break; }
+            // (a primal residual that has stopped falling BELOW 1e-6 is the numerical floor of a solved problem, not a Farkas ray: at
+            // K = 1 a few starts in a thousand sit there for five iterations with gap 1e-7 -- reported like the other floors.  So a
+            // problem whose primal residual is stuck below 1e-6 with dres and the gap converged is never called infeasible: it ends
+            // almost optimal (4), or optimal (0) when all three are inside the near band, and only then does it become a start)
+            if (flat >= 5 && dres < 1e-6 && relgap < 1e-6) { R.status = near ? TD_OPTIMAL : (almost ? TD_ALMOST : TD_INFEASIBLE); break; }
             if (it == T.max_iter) break;
 
             scale(false);
@@ -1131,6 +1147,13 @@ struct Solver {
             // the numerical floor: an iterate that is a certified near-optimum (the band the oracle's solver, oracle/ipm.py,
             // and Mosek / ECOS at their default tolerances report as OPTIMAL) is accepted when the KKT system breaks down
             if (!(alpha >= 1e-8)) { R.status = near ? TD_OPTIMAL : (almost ? TD_ALMOST : (alpha == alpha ? TD_STALLED : TD_NONFINITE)); break; }
+            // the third breakdown: a factorisation on its pivot floors that stays finite (ok) while the border solve and the predictor
+            // direction grow to 1e150; their Jordan product in corr_rhs overflows, the corrector direction is NaN, and the rule above
+            // does not see it (finite_step).  Taking that step would write NaN over a certified near-optimum and end in
+            // TD_NONFINITE one iteration later (K = 1, 2 of 64 dispersed starts); the iterate is returned as it is instead.
+            // Outside the bands nothing is asked: a NaN step there is still taken and ends in TD_NONFINITE with a NaN record, which
+            // is the truth about an iterate that was no answer (the record kernel of scvx_batch_init_threedof skips every status but 0).
+            if ((near || almost) && !finite_step()) { R.status = near ? TD_OPTIMAL : TD_ALMOST; break; }
             take_step(alpha);
             TD_TE(t10_, 10);
         }

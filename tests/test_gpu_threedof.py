@@ -16,20 +16,9 @@ pytestmark = pytest.mark.gpu
 KEYS = ("T", "r", "v", "ma", "ga", "kaR", "ar", "nkaR")
 
 
-def _product(po):
-    """the product-side DescentProblem with the oracle problem's numbers"""
-    from successiveconvexification_amd.defns import DescentProblem
-    p = DescentProblem()
-    for f in ("g", "mdry", "mwet", "Tmin", "Tmax", "deltaMax", "thetaMax", "gammaGs", "omMax", "alpha", "K", "tf_guess", "imax"):
-        setattr(p, f, getattr(po, f))
-    for f in ("rIi", "vIi", "rIf", "vIf", "rTB", "rFB", "jB", "qBIf", "wBi", "wBf"):
-        setattr(p, f, np.array(getattr(po, f), float))
-    return p
-
-
 def _cache(po, npts=10):
-    from successiveconvexification_amd.dynamics import IntegratorCache
-    return IntegratorCache(_product(po), npts=npts)
+    import k0_path_reference as kp
+    return kp.device_cache(po, npts)
 
 
 def _config0():
@@ -41,6 +30,10 @@ def _flyable(K=30):
     from oracle import model
     return replace(model.DescentProblem(), K=K, tf_guess=6.0, rIi=np.array([4.0, 2.0, 0.0]), vIi=np.array([-0.5, -0.5, 0.3]),
                    mdry=1.0, mwet=2.0, alpha=0.05)
+
+
+def _tally(st):
+    return {int(k): int(n) for k, n in zip(*np.unique(st, return_counts=True))}
 
 
 def _T_of(tnorm, q):
@@ -102,6 +95,50 @@ def test_device_tiny_horizons(K):
     assert st[0] == 0 and tst[0] == 0 and abs(info[0, 1] - tinfo[0, 1]) < 1e-8
     # K = 3 ends on the numerical floor (gap 2e-8) on both sides, an iteration apart: the flat thrust directions differ by 5e-5
     assert _linf(sol, 0, {k: tw[k][0] for k in KEYS}) < 2e-4
+
+
+@pytest.mark.parametrize("K", [1, 2, 3])
+def test_device_tiny_horizons_dispersed(K):
+    """64 dispersed starts at the horizons where the KKT system ends on its pivot floors.  Before solve() asked finite_step(), 2 of the
+    64 starts at K = 1 ended with status 3 and a record of NaN on either build of the twin: a factorisation that stayed finite on its
+    floors, a predictor direction of 1e154, its Jordan product overflowing in corr_rhs, and a step-length search whose comparisons all
+    drop a NaN (alpha = 1) -- from an iterate with gap 1e-7 and residuals 1e-12.  And start 36 of the K = 1 batch ended "infeasible"
+    (5) on the device with the objective within 8e-9 of the twin's: the infeasibility rule fired on the numerical floor of a solved
+    problem (it ends almost optimal, 4, now).  Every start ends optimal or almost optimal, no record holds a NaN, the objectives are
+    the parity twin's -- within 1e-8 where both end 0, within 2e-7 elsewhere; and the 6-DoF start built from the batch holds no NaN
+    either.  Measured on one MI355X (profiles/k0_path_parity.md): statuses {0: 63, 4: 1}, {0: 64}, {0: 64} at K = 1, 2, 3; objectives
+    within 6.5e-9 (8.0e-9 on the start that ends 4), 1.8e-9 and 1.0e-11."""
+    from oracle import model, port
+    from successiveconvexification_amd import first_round
+    from successiveconvexification_amd.batch import ScvxBatch
+    po = _flyable(K=K)
+    B = 64
+    ic = model.disperse_ics(po, B, 20261020)
+    c = _cache(po)
+    sol, st, info = first_round.solve_initial_batch(c, ic)
+    tw, tst, tinfo = port.threedof(po, ic)
+    rel = np.abs(info[:, 1] - tinfo[:, 1]) / np.maximum(1.0, np.abs(tinfo[:, 1]))
+    both = (st == 0) & (tst == 0)
+    print("K = %d: device statuses %s, twin statuses %s; objective device against twin: %.1e where both end 0 (%d starts), %.1e elsewhere"
+          % (K, _tally(st), _tally(tst), rel[both].max(initial=0.0),
+             int(both.sum()), rel[~both].max(initial=0.0)))
+    assert np.all(np.isin(st, (0, 4))), (st, info[:, 0])
+    assert all(np.isfinite(sol[k]).all() for k in KEYS) and np.isfinite(info).all()
+    assert np.all(np.isin(tst, (0, 4))) and np.isfinite(tinfo).all()
+    assert rel[both].max(initial=0.0) < 1e-8 and rel[~both].max(initial=0.0) < 2e-7
+    # what scvx_batch_init_threedof's record kernel is handed: only an optimal solve replaces the straight line, so no NaN arrives
+    b = ScvxBatch(c, B)
+    st3 = b.init_threedof(ic)
+    x, u, s = b.trajectory()
+    assert np.array_equal(st3, st) and np.isfinite(x).all() and np.isfinite(u).all() and np.isfinite(s).all()
+    # ... and a solve that ends on the iteration cap (an iterate far from feasible) leaves the straight line exactly as init() made it
+    assert np.all(b.init_threedof(ic, max_iter=3) == 1)
+    xc, uc, sc = b.trajectory()
+    b.init(ic)
+    x0, u0, s0 = b.trajectory()
+    assert np.array_equal(xc, x0) and np.array_equal(uc, u0) and np.array_equal(sc, s0)
+    b.close()
+    c.close()
 
 
 def test_device_long_horizon_K100():

@@ -64,6 +64,50 @@ def test_twin_tiny_horizons(K):
     assert abs(info[0, 1] - ref.pobj) <= 2e-7 * max(1.0, abs(ref.pobj)) and linf(sol, 0, o) < 1e-3
 
 
+DISPERSED_SEED = 20261020
+# starts 11 and 25 (parity build) and 2 and 37 (native build) of the K = 1 batch ended with status 3 and a record of NaN before
+# solve() asked finite_step(); start 36 ended "infeasible" (5) on the device with the objective within 8e-9 of the optimum
+ORACLE_SAMPLE = (0, 2, 11, 25, 36, 37, 50, 63)
+
+
+@pytest.mark.parametrize("K", [1, 2, 3])
+def test_twin_tiny_horizons_dispersed(K):
+    """64 dispersed starts at the horizons where the KKT system ends on its pivot floors: every start ends optimal or almost
+    optimal on both builds of the twin, no record holds a NaN, and the objective is the independent oracle's."""
+    import oracle
+    p = flyable(K=K)
+    ic = model.disperse_ics(p, 64, DISPERSED_SEED)
+    sol, st, info = port.threedof(p, ic)
+    assert np.all(np.isin(st, (0, 4))), (st, info[:, 0])
+    assert all(np.isfinite(sol[k]).all() for k in KEYS) and np.isfinite(info).all()
+    for b in ORACLE_SAMPLE:      # the oracle solves all eight, the starts that failed before among them
+        ref, o, _ = threedof.solve_initial(replace(p, rIi=ic[b, :3], vIi=ic[b, 3:]))
+        assert ref.status == "optimal", (b, ref.status)
+        assert abs(info[b, 1] - ref.pobj) <= 2e-7 * max(1.0, abs(ref.pobj)), (b, info[b], ref.pobj)
+    oracle.use_native(True)
+    try:
+        nsol, nst, ninfo = port.threedof(p, ic)
+    finally:
+        oracle.use_native(False)
+    assert np.all(np.isin(nst, (0, 4))), (nst, ninfo[:, 0])
+    assert all(np.isfinite(nsol[k]).all() for k in KEYS) and np.isfinite(ninfo).all()
+    assert np.abs(ninfo[:, 1] - info[:, 1]).max() <= 2e-7 * max(1.0, np.abs(info[:, 1]).max())
+
+
+def test_twin_floor_of_a_solved_problem_is_not_reported_infeasible():
+    """K = 1: starts 122, 190, 307 of 4096 dispersed ones sit for five iterations with a primal residual that no longer falls -- at
+    1e-10 ... 1e-7, with gap 1e-7: the numerical floor of a solved problem.  The infeasibility rule (a primal residual stuck while
+    the dual residual and the gap converge) reported them as infeasible (5); an infeasible problem is stuck ABOVE 1e-6
+    (test_twin_reports_an_infeasible_instance)."""
+    p = flyable(K=1)
+    ic = model.disperse_ics(p, 4096, DISPERSED_SEED)[[122, 190, 307]]
+    sol, st, info = port.threedof(p, ic)
+    assert np.all(np.isin(st, (0, 4))) and info[:, 3].max() < 1e-6, (st, info)
+    for b in range(3):
+        ref, o, _ = threedof.solve_initial(replace(p, rIi=ic[b, :3], vIi=ic[b, 3:]))
+        assert ref.status == "optimal" and abs(info[b, 1] - ref.pobj) <= 2e-7 * max(1.0, abs(ref.pobj)), (b, info[b], ref.pobj)
+
+
 def test_twin_reports_an_infeasible_instance():
     # the normalised 6-DoF sample problem at tf_guess = 1: the fuel between mwet and mdry cannot pay for Tmin over the
     # whole horizon, whatever the virtual acceleration does -- the oracle's IPM ends "kkt_singular" with the primal
