@@ -12,6 +12,7 @@
  *   (no counterpart: sampled closed-loop dispersion)   ->  scvx_track_mc_f64[_host], scvx_batch_track_mc
  *   (no counterpart: its quantiles, per-node samples)   ->  scvx_order_stats_f64[_host], scvx_track_mc[_nav]_q_f64[_host], scvx_batch_track_mc[_nav]_q
  *   (no counterpart: its draws made on the device)     ->  scvx_mc_draws_f64[_host], scvx_track_mc[_nav]_rng_f64[_host], scvx_batch_track_mc[_nav]_rng
+ *   (no counterpart: per-flight vehicle errors)        ->  scvx_track_mc[_nav]_veh_f64[_host], scvx_batch_track_mc[_nav]_veh
  *   Rocketland.create_initial     rocketland.jl:34-39  ->  scvx_batch_create + scvx_batch_init
  *   FirstRound.solve_initial      initial_solve.jl:17-110 -> scvx_threedof_solve, scvx_batch_init_threedof
  *   Rocketland.solve_step         rocketland.jl:226-321->  scvx_solve_step
@@ -663,6 +664,66 @@ int scvx_track_mc_nav_rng_f64_host(scvx_ctx *ctx, int B, int K, int S, const dou
                                    double *navfed, double *navK, int nq, const int *ranks, double *flightq, double *pathq,
                                    double *pathv);
 
+/* ---- sampled closed-loop dispersion with per-flight VEHICLE ERRORS ------------------------------------------------------------------
+ * The calls above fly one vehicle, the nominal one: their flights differ in the start and in the impulses only.  The _veh forms add
+ * errors of the vehicle itself that are CONSTANT over a flight, which neither S0 nor w can express:
+ *     theta = mu + sp (.) zeta        (fma(sp_i, zeta_i, mu_i)),  zeta ~ N(0, I_6) per flight,  SCVX_VEH_N = 6 components: */
+#define SCVX_VEH_N 6
+#define SCVX_VEH_THRUST 0 /* relative thrust error:      ua[0:3] = (1 + th0) (uu[0:3] + d x uu[0:3]),  d = (0, th1, th2)                  */
+#define SCVX_VEH_MIS_Y 1  /* misalignment of the thrust axis about body y and z, in radians: the d above.  A FIRST-ORDER rotation, kept  */
+#define SCVX_VEH_MIS_Z 2  /* first order: |u + d x u| = |u| sqrt(1 + O(|d|^2)), so the applied thrust (and the mass flow) grow by O(|d|^2) */
+#define SCVX_VEH_ISP 3    /* alpha -> alpha (1 + th3) in the mass equation, which sees |ua|                                              */
+#define SCVX_VEH_AERO 4   /* force_scalar -> force_scalar (1 + th4), trq_scalar alike with SCVX_MODEL_AERO_TORQUE; aerodynamic models only */
+#define SCVX_VEH_FIN 5    /* ua[3:5] = (1 + th5) uu[3:5]; fin models only                                                                */
+/* uu is the commanded first-order hold at the RK stage, formed exactly as in the calls above; ua replaces it in the right-hand side of
+ * the TRUTH and nowhere else.  The error lies BEHIND the command: the law's z, the clamp, OUT_LO / OUT_HI, the THRUST column of pathv
+ * and G_TMAX, G_TMIN, G_GIMBAL, G_FIN see the command, as they do in the calls above; the state columns and the landing statistics see
+ * the vehicle that flew.  In the navigation form the recursion of eps is unchanged (the analysis's A_k); the truth is flown with theta.
+ * Limits: constant over the flight; no wind, centre-of-gravity or inertia errors; the rotation is first order (above); a 1 + th <= 0
+ * is not refused (the model is meant for |th| << 1).
+ * Each _veh form takes the argument list of the _q form it extends, verbatim, followed by
+ *     const scvx_mc_rng *rng, int noise, const scvx_mc_vehicle *veh, const double *zeta [S][6], double *theta [B][S][6]
+ * rng != NULL: the lanes make the draws as in the _rng forms, and the uploaded draws (xi0, eta, xin, nud, zeta) must all be NULL; zeta
+ * is then the first six normals of group 0 of Philox stream c1 = 8, with c2 / c3 as for streams 6 and 7 (shards and `independent` work
+ * unchanged).  rng == NULL: noise must be 0 (eta != NULL says it, as in the _q forms), and zeta, shared by all plans like xi0, is
+ * required as soon as any sp > 0.  theta (optional, dense): the errors every flight flew.  veh == NULL IS the _q / _rng call (zeta and
+ * theta must then be NULL) and launches the kernels those launch.  SCVX_ERR_ARG as the form extended and as the _rng forms for rng; for
+ * a non-finite mu, a negative or non-finite sp, a non-zero reserved; for a non-zero mu or sp of AERO on a model without aerodynamics
+ * or of FIN on a model without fins. */
+typedef struct scvx_mc_vehicle {
+    double mu[SCVX_VEH_N], sp[SCVX_VEH_N];
+    int32_t reserved[2]; /* must be 0 */
+} scvx_mc_vehicle;
+int scvx_track_mc_veh_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                          const double *gain_dev, const double *C0_dev, const double *xi0_dev, const double *eta_dev,
+                          const double *sw14, const void *reserved, int nsub, int flags, double tol, double *mcrep_dev,
+                          double *xmean_dev, double *xcov_dev, double *flights_dev, double *xland_dev, double *dx0_dev, int nq,
+                          const int *ranks, double *flightq_dev, double *pathq_dev, double *pathv_dev, const scvx_mc_rng *rng,
+                          int noise, const scvx_mc_vehicle *veh, const double *zeta_dev, double *theta_dev);
+int scvx_track_mc_veh_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                               const double *gain, const double *C0, const double *xi0, const double *eta, const double *sw14,
+                               const void *reserved, int nsub, int flags, double tol, double *mcrep, double *xmean, double *xcov,
+                               double *flights, double *xland, double *dx0, int nq, const int *ranks, double *flightq, double *pathq,
+                               double *pathv, const scvx_mc_rng *rng, int noise, const scvx_mc_vehicle *veh, const double *zeta,
+                               double *theta);
+int scvx_track_mc_nav_veh_f64(scvx_ctx *ctx, int B, int K, int S, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                              const double *gain_dev, const double *C0_dev, const double *xi0_dev, const double *eta_dev,
+                              const double *w14, const double *deriv_dev, const double *kf_dev, const double *CN_dev,
+                              const double *xin_dev, const double *nud_dev, int m, const double *H, const double *rm, int nsub,
+                              int flags, double tol, double *mcrep_dev, double *xmean_dev, double *xcov_dev, double *jmean_dev,
+                              double *jcov_dev, double *mcnav_dev, double *flights_dev, double *xland_dev, double *dx0_dev,
+                              double *navfed_dev, double *navK_dev, int nq, const int *ranks, double *flightq_dev, double *pathq_dev,
+                              double *pathv_dev, const scvx_mc_rng *rng, int noise, const scvx_mc_vehicle *veh,
+                              const double *zeta_dev, double *theta_dev);
+int scvx_track_mc_nav_veh_f64_host(scvx_ctx *ctx, int B, int K, int S, const double *x, const double *u, const double *sigma,
+                                   const double *gain, const double *C0, const double *xi0, const double *eta, const double *w14,
+                                   const double *deriv, const double *kf, const double *CN, const double *xin, const double *nud,
+                                   int m, const double *H, const double *rm, int nsub, int flags, double tol, double *mcrep,
+                                   double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav, double *flights,
+                                   double *xland, double *dx0, double *navfed, double *navK, int nq, const int *ranks,
+                                   double *flightq, double *pathq, double *pathv, const scvx_mc_rng *rng, int noise,
+                                   const scvx_mc_vehicle *veh, const double *zeta, double *theta);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -852,6 +913,22 @@ int scvx_batch_track_mc_nav_rng(scvx_batch *b, const double *q14, const double *
                                 double *xcov, double *jmean, double *jcov, double *mcnav, double *flights, double *xland,
                                 double *dx0, double *navfed, double *navK, int nq, const int *ranks, double *flightq, double *pathq,
                                 double *pathv);
+
+/* The two _q calls above with per-flight vehicle errors (scvx_track_mc_veh_f64 / scvx_track_mc_nav_veh_f64): their argument lists,
+ * verbatim, followed by rng, noise, veh, zeta [S][6] and theta [B][S][6] (host arrays).  veh == NULL is the _q call (rng == NULL) or
+ * the _rng call.  Synchronises.  SCVX_ERR_ARG as the call extended and as scvx_track_mc_veh_f64 for the five. */
+int scvx_batch_track_mc_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                            const double *xi0, const double *eta, const double *sw14, const void *reserved, int nsub, int flags,
+                            double tol, double *mcrep, double *xmean, double *xcov, double *flights, double *xland, double *dx0,
+                            int nq, const int *ranks, double *flightq, double *pathq, double *pathv, const scvx_mc_rng *rng,
+                            int noise, const scvx_mc_vehicle *veh, const double *zeta, double *theta);
+int scvx_batch_track_mc_nav_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, int S, const double *C0,
+                                const double *xi0, const double *eta, const double *w14, const double *N0, const double *CN,
+                                const double *xin, const double *nud, int m, const double *H, const double *rm, int nsub, int flags,
+                                double tol, double *mcrep, double *xmean, double *xcov, double *jmean, double *jcov, double *mcnav,
+                                double *flights, double *xland, double *dx0, double *navfed, double *navK, int nq, const int *ranks,
+                                double *flightq, double *pathq, double *pathv, const scvx_mc_rng *rng, int noise,
+                                const scvx_mc_vehicle *veh, const double *zeta, double *theta);
 
 /* ---- thrust-band back-offs and covariance-driven replanning (no counterpart in the reference) ---------------------------------
  * Per-trajectory, per-node back-offs of the thrust band, read by the conic solve alone:

@@ -924,6 +924,145 @@ track_mc_nav_rng_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble},
         xland_dev, dx0_dev, navfed_dev, navK_dev, length(ranks), isempty(ranks) ? C_NULL : ranks, flightq_dev, pathq_dev, pathv_dev),
         "scvx_track_mc_nav_rng_f64")
 
+# include/scvx.h, "sampled closed-loop dispersion with per-flight VEHICLE ERRORS": the _q calls followed by (rng, noise, veh, zeta,
+# theta) -- every flight flies a vehicle of its own, theta = mu + sp .* zeta constant over the flight, in the order THRUST, MIS_Y,
+# MIS_Z, ISP, AERO, FIN (the model and its limits are in the header).  rng = nothing: the uploaded draws xi0 (14 x S), eta (14 x K x S
+# or nothing), zeta (6 x S; needed as soon as any sp > 0), with nav also xin and nud; rng::McRng: the lanes make all of them (zeta from
+# stream 8) and the uploaded ones must stay nothing.  theta = true returns the errors flown, 6 x S x B.
+struct McVehicle
+    mu::NTuple{6,Float64}
+    sp::NTuple{6,Float64}
+    reserved::NTuple{2,Int32}
+end
+McVehicle(mu::AbstractVector, sp::AbstractVector) = McVehicle(Tuple(Float64.(mu)), Tuple(Float64.(sp)), (Int32(0), Int32(0)))
+McVehicle(; thrust=0.0, mis_y=0.0, mis_z=0.0, isp=0.0, aero=0.0, fin=0.0, mean=zeros(6)) =
+    McVehicle(mean, [thrust, mis_y, mis_z, isp, aero, fin])
+_mc_rng_ptr(rng) = rng === nothing ? C_NULL : Ref(rng)
+
+function track_mc_veh(b::Batch, C0::Array{Float64,3}, veh::McVehicle, S::Int; rng::Union{Nothing,McRng}=nothing, xi0=nothing, eta=nothing,
+                      zeta=nothing, ranks::Vector{Cint}=Cint[], w=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false,
+                      tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false, theta::Bool=false)
+    NU = control_dim(b.cache); K = b.cache.problem.K; nq = length(ranks)
+    size(C0) == (14, 14, b.B) || throw(ArgumentError("C0 must be 14 x 14 x B"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    flightq, pathq, pv = _mc_q_outputs(b.B, S, K, nq, per_node && nq > 0, pathv)
+    th = theta ? Array{Float64,3}(undef, 6, S, b.B) : nothing
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    rp = _mc_rng_ptr(rng); vr = Ref(veh)
+    GC.@preserve sw ranks rp vr check(b.cache.ctx, ccall((:scvx_batch_track_mc_veh, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{McRng}, Cint, Ptr{McVehicle}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, _cov_opt(xi0), _cov_opt(eta), _cov_opt(sw), C_NULL, nsub,
+        clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), nq,
+        nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL, _cov_opt(pathq), _cov_opt(pv), rp, (rng !== nothing && sw !== nothing) ? 1 : 0,
+        vr, _cov_opt(zeta), _cov_opt(th)), "scvx_batch_track_mc_veh")
+    return mcrep, xmean, xcov, flights, xland, dx0, (nq > 0 ? flightq : nothing), pathq, pv, th
+end
+
+function track_mc_veh(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, gain::Array{Float64,4},
+                      C0::Array{Float64,3}, veh::McVehicle, S::Int; rng::Union{Nothing,McRng}=nothing, xi0=nothing, eta=nothing,
+                      zeta=nothing, ranks::Vector{Cint}=Cint[], w=nothing, nsub::Int=10, clamp::Bool=false, tol::Float64=0.0,
+                      dense::Bool=false, per_node::Bool=false, pathv::Bool=false, theta::Bool=false)
+    B, K, nq = size(x, 3), size(x, 2) - 1, length(ranks)
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    flightq, pathq, pv = _mc_q_outputs(B, S, K, nq, per_node && nq > 0, pathv)
+    th = theta ? Array{Float64,3}(undef, 6, S, B) : nothing
+    sw = w === nothing ? nothing : sqrt.(_track_w(w, 14))
+    rp = _mc_rng_ptr(rng); vr = Ref(veh)
+    GC.@preserve sw ranks rp vr check(cache.ctx, ccall((:scvx_track_mc_veh_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{McRng}, Cint, Ptr{McVehicle}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, _cov_opt(xi0), _cov_opt(eta), _cov_opt(sw), C_NULL, nsub, clamp ? TRACK_CLAMP : 0, tol,
+        mcrep, xmean, xcov, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), nq, nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL,
+        _cov_opt(pathq), _cov_opt(pv), rp, (rng !== nothing && sw !== nothing) ? 1 : 0, vr, _cov_opt(zeta), _cov_opt(th)),
+        "scvx_track_mc_veh_f64_host")
+    return mcrep, xmean, xcov, flights, xland, dx0, (nq > 0 ? flightq : nothing), pathq, pv, th
+end
+
+# on device pointers, asynchronous on the context's stream; sw = sqrt(w) and ranks stay host arrays; C_NULL for an array not given
+track_mc_veh_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                  gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble},
+                  sw::Union{Nothing,Vector{Float64}}, nsub::Int, flags::Int, tol::Float64, mcrep_dev::Ptr{Cdouble},
+                  xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble}, flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble},
+                  dx0_dev::Ptr{Cdouble}, ranks::Vector{Cint}, flightq_dev::Ptr{Cdouble}, pathq_dev::Ptr{Cdouble},
+                  pathv_dev::Ptr{Cdouble}, rng::Union{Nothing,McRng}, noise::Bool, veh::McVehicle, zeta_dev::Ptr{Cdouble},
+                  theta_dev::Ptr{Cdouble}) = begin
+    rp = _mc_rng_ptr(rng); vr = Ref(veh)
+    GC.@preserve sw ranks rp vr check(cache.ctx, ccall((:scvx_track_mc_veh_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{McRng}, Cint, Ptr{McVehicle}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(sw), C_NULL, nsub, flags, tol,
+        mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, length(ranks), isempty(ranks) ? C_NULL : ranks, flightq_dev,
+        pathq_dev, pathv_dev, rp, noise ? 1 : 0, vr, zeta_dev, theta_dev), "scvx_track_mc_veh_f64")
+end
+
+function track_mc_nav_veh(b::Batch, C0::Array{Float64,3}, N0::Array{Float64,3}, CN::Array{Float64,3}, H, rm, veh::McVehicle, S::Int;
+                          rng::Union{Nothing,McRng}=nothing, xi0=nothing, eta=nothing, xin=nothing, nud=nothing, zeta=nothing,
+                          ranks::Vector{Cint}=Cint[], w=nothing, q=1.0, r=1.0, qf=100.0, nsub::Int=0, clamp::Bool=false,
+                          tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false, theta::Bool=false)
+    NU = control_dim(b.cache); K = b.cache.problem.K; nq = length(ranks)
+    (size(C0) == (14, 14, b.B) && size(N0) == (14, 14, b.B) && size(CN) == (14, 14, b.B)) ||
+        throw(ArgumentError("C0, N0, CN must be 14 x 14 x B"))
+    m, Hm, rmv = _nav_model(H, rm)
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(b.B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(b.B, S, K, dense)
+    flightq, pathq, pv = _mc_q_outputs(b.B, S, K, nq, per_node && nq > 0, pathv)
+    th = theta ? Array{Float64,3}(undef, 6, S, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    rp = _mc_rng_ptr(rng); vr = Ref(veh)
+    GC.@preserve wv Hm rmv ranks rp vr check(b.cache.ctx, ccall((:scvx_batch_track_mc_nav_veh, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{McRng}, Cint, Ptr{McVehicle}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S, C0, _cov_opt(xi0), _cov_opt(eta), _cov_opt(wv), N0, CN, _cov_opt(xin),
+        _cov_opt(m > 0 ? nud : nothing), m, _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean, xcov, jmean, jcov,
+        mcnav, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK), nq, nq > 0 ? ranks : C_NULL,
+        nq > 0 ? flightq : C_NULL, _cov_opt(pathq), _cov_opt(pv), rp, (rng !== nothing && wv !== nothing) ? 1 : 0, vr, _cov_opt(zeta),
+        _cov_opt(th)), "scvx_batch_track_mc_nav_veh")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, (nq > 0 ? flightq : nothing), pathq, pv, th
+end
+
+function track_mc_nav_veh(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}, deriv::Array{Float64,4},
+                          gain::Array{Float64,4}, C0::Array{Float64,3}, CN::Array{Float64,3}, H, rm, veh::McVehicle, S::Int;
+                          rng::Union{Nothing,McRng}=nothing, xi0=nothing, eta=nothing, xin=nothing, nud=nothing, zeta=nothing,
+                          kf::Union{Nothing,Array{Float64,4}}=nothing, ranks::Vector{Cint}=Cint[], w=nothing, nsub::Int=10,
+                          clamp::Bool=false, tol::Float64=0.0, dense::Bool=false, per_node::Bool=false, pathv::Bool=false,
+                          theta::Bool=false)
+    B, K, nq = size(x, 3), size(x, 2) - 1, length(ranks)
+    m, Hm, rmv = _nav_model(H, rm)
+    (m == 0 || (kf !== nothing && size(kf) == (m, 14, K, B))) ||
+        throw(ArgumentError("with measurements: kf m x 14 x K x B (navigation(...; dense=true))"))
+    mcrep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
+    jmean, jcov, mcnav, navfed, navK = _mc_nav_outputs(B, S, K, dense)
+    flightq, pathq, pv = _mc_q_outputs(B, S, K, nq, per_node && nq > 0, pathv)
+    th = theta ? Array{Float64,3}(undef, 6, S, B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    rp = _mc_rng_ptr(rng); vr = Ref(veh)
+    GC.@preserve wv Hm rmv ranks rp vr check(cache.ctx, ccall((:scvx_track_mc_nav_veh_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{McRng}, Cint, Ptr{McVehicle}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x, u, sigma, gain, C0, _cov_opt(xi0), _cov_opt(eta), _cov_opt(wv), deriv, _cov_opt(m > 0 ? kf : nothing), CN,
+        _cov_opt(xin), _cov_opt(m > 0 ? nud : nothing), m, _cov_opt(Hm), _cov_opt(rmv), nsub, clamp ? TRACK_CLAMP : 0, tol, mcrep, xmean,
+        xcov, jmean, jcov, mcnav, _cov_opt(flights), _cov_opt(xland), _cov_opt(dx0), _cov_opt(navfed), _cov_opt(navK), nq,
+        nq > 0 ? ranks : C_NULL, nq > 0 ? flightq : C_NULL, _cov_opt(pathq), _cov_opt(pv), rp,
+        (rng !== nothing && wv !== nothing) ? 1 : 0, vr, _cov_opt(zeta), _cov_opt(th)), "scvx_track_mc_nav_veh_f64_host")
+    return mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, (nq > 0 ? flightq : nothing), pathq, pv, th
+end
+
+# on device pointers, asynchronous on the context's stream; w (the VARIANCE), H, rm and ranks stay host arrays; C_NULL for an array not given
+track_mc_nav_veh_dev!(cache::Cache, B::Int, K::Int, S::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble},
+                      gain_dev::Ptr{Cdouble}, C0_dev::Ptr{Cdouble}, xi0_dev::Ptr{Cdouble}, eta_dev::Ptr{Cdouble},
+                      w::Union{Nothing,Vector{Float64}}, deriv_dev::Ptr{Cdouble}, kf_dev::Ptr{Cdouble}, CN_dev::Ptr{Cdouble},
+                      xin_dev::Ptr{Cdouble}, nud_dev::Ptr{Cdouble}, m::Int, H::Union{Nothing,Matrix{Float64}},
+                      rm::Union{Nothing,Vector{Float64}}, nsub::Int, flags::Int, tol::Float64, mcrep_dev::Ptr{Cdouble},
+                      xmean_dev::Ptr{Cdouble}, xcov_dev::Ptr{Cdouble}, jmean_dev::Ptr{Cdouble}, jcov_dev::Ptr{Cdouble},
+                      mcnav_dev::Ptr{Cdouble}, flights_dev::Ptr{Cdouble}, xland_dev::Ptr{Cdouble}, dx0_dev::Ptr{Cdouble},
+                      navfed_dev::Ptr{Cdouble}, navK_dev::Ptr{Cdouble}, ranks::Vector{Cint}, flightq_dev::Ptr{Cdouble},
+                      pathq_dev::Ptr{Cdouble}, pathv_dev::Ptr{Cdouble}, rng::Union{Nothing,McRng}, noise::Bool, veh::McVehicle,
+                      zeta_dev::Ptr{Cdouble}, theta_dev::Ptr{Cdouble}) = begin
+    rp = _mc_rng_ptr(rng); vr = Ref(veh)
+    GC.@preserve w H rm ranks rp vr check(cache.ctx, ccall((:scvx_track_mc_nav_veh_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{McRng}, Cint, Ptr{McVehicle}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, _cov_opt(w), deriv_dev, kf_dev, CN_dev, xin_dev,
+        nud_dev, m, _cov_opt(H), _cov_opt(rm), nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev,
+        flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, length(ranks), isempty(ranks) ? C_NULL : ranks, flightq_dev, pathq_dev,
+        pathv_dev, rp, noise ? 1 : 0, vr, zeta_dev, theta_dev), "scvx_track_mc_nav_veh_f64")
+end
+
 # ---- thrust-band back-offs and covariance-driven replanning (new) ----------------------------------------------------------
 # include/scvx.h, "thrust-band back-offs".  Tmin + lo[k, b] <= |u_k| <= Tmax - hi[k, b], read by the conic solve alone; the flight
 # check and the tracking calls keep auditing against the true Tmin / Tmax.  psig is 5 x (K+1) x B (row PSIG_* + 1 holds that column).

@@ -51,6 +51,16 @@ class ScvxMcRng(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("s_lo", C.c_uint64), ("b_lo", C.c_uint64), ("independent", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ScvxMcVehicle(C.Structure):
+    """struct scvx_mc_vehicle (include/scvx.h): mean and 1 sigma of the six per-flight vehicle errors of the _veh forms"""
+    _fields_ = [("mu", C.c_double * 6), ("sp", C.c_double * 6), ("reserved", C.c_int32 * 2)]
+
+
+# the components of the vehicle errors (the SCVX_VEH_* macros of include/scvx.h)
+VEH_N = 6
+VEH_COLUMNS = ("THRUST", "MIS_Y", "MIS_Z", "ISP", "AERO", "FIN")
+VEH_INDEX = {n: i for i, n in enumerate(VEH_COLUMNS)}
+
 ABI_VERSION = 4   # SCVX_ABI_VERSION of the include/scvx.h these structs and signatures were written against
 
 # scvx_flight_check_*: modes and the columns of the report [B][FLIGHT_NREP] (the SCVX_FLIGHT_* macros of include/scvx.h)
@@ -90,6 +100,7 @@ MCNAV_INDEX = {n: i for i, n in enumerate(MCNAV_COLUMNS)}
 
 _vp = C.c_void_p
 _rp = C.POINTER(ScvxMcRng)
+_hp = C.POINTER(ScvxMcVehicle)
 # name -> (restype, argtypes); must list every symbol include/scvx.h declares (tests check this)
 SIGNATURES = {
     "scvx_abi_version": (C.c_int, []),
@@ -171,6 +182,24 @@ SIGNATURES = {
     "scvx_batch_track_mc_nav_rng": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _rp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
                                               C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _ip,
                                               _dp, _dp, _dp]),
+    # the sampled calls with per-flight vehicle errors: the _q lists, then rng, noise, veh, zeta, theta
+    "scvx_track_mc_veh_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp, C.c_int, C.c_int,
+                                        C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _ip, _vp, _vp, _vp, _rp, C.c_int, _hp, _vp,
+                                        _vp]),
+    "scvx_track_mc_veh_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _vp, C.c_int,
+                                             C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _rp,
+                                             C.c_int, _hp, _dp, _dp]),
+    "scvx_track_mc_nav_veh_f64": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp,
+                                            _vp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, C.c_int, _ip, _vp, _vp, _vp, _rp, C.c_int, _hp, _vp, _vp]),
+    "scvx_track_mc_nav_veh_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 _dp, _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _rp, C.c_int, _hp, _dp, _dp]),
+    "scvx_batch_track_mc_veh": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _vp, C.c_int, C.c_int, C.c_double, _dp, _dp,
+                                          _dp, _dp, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _rp, C.c_int, _hp, _dp, _dp]),
+    "scvx_batch_track_mc_nav_veh": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                              C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                              C.c_int, _ip, _dp, _dp, _dp, _rp, C.c_int, _hp, _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),

@@ -253,7 +253,7 @@ class ScvxBatch:
         return FlightReport(rep, xfly, "track", ufly)
 
     def track_mc(self, S0, samples=256, seed=0, w=None, q=None, r=None, qf=None, nsub=None, clamp=False, tol=0.0, dense=(), draws=None,
-                 nav=None, quantiles=None, per_node=False, rng="host", independent=False, sample_lo=0, plan_lo=0):
+                 nav=None, quantiles=None, per_node=False, rng="host", independent=False, sample_lo=0, plan_lo=0, vehicle=None):
         """Sampled closed-loop dispersion of the batch's current accepted iterate under its LQR gains: `samples` flights per plan on
         the device, one dynamics.McReport row per plan (scvx_batch_track_mc; S0 -- a [14] vector of standard deviations, one [14][14]
         or [B][14][14] --, seed, w, clamp, tol, dense and draws as dynamics.track_mc_batch, weights as track_gains).  The batch is left
@@ -263,11 +263,14 @@ class ScvxBatch:
         dynamics.track_mc_batch: order statistics of the flight columns and of the per-node path functions, reduced on the device
         (scvx_batch_track_mc_q / scvx_batch_track_mc_nav_q); at their defaults the call is the one it was.  rng="device", independent,
         sample_lo and plan_lo as dynamics.track_mc_batch: the lanes make the draws, per plan if asked (scvx_batch_track_mc_rng /
-        scvx_batch_track_mc_nav_rng); rng="host" is the call it was."""
+        scvx_batch_track_mc_nav_rng); rng="host" is the call it was.  vehicle = (mu, sp) and the dense name "theta" as
+        dynamics.track_mc_batch: per-flight vehicle errors (scvx_batch_track_mc_veh / scvx_batch_track_mc_nav_veh); None is the call it
+        was."""
         import ctypes as C
-        from .dynamics import McReport, _McQ, _mc_inputs, _mc_outputs, _mc_rng, _track_weights
+        from .dynamics import McReport, _McQ, _McVeh, _mc_inputs, _mc_outputs, _mc_rng, _track_weights
         rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
-        mq = _McQ(quantiles, per_node, dense)
+        vh = _McVeh(vehicle, dense)
+        mq = _McQ(quantiles, per_node, vh.rest)
         dense = mq.rest
         qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
         if nav is not None:
@@ -278,31 +281,39 @@ class ScvxBatch:
             S = int(samples) if rg is not None else xi0.shape[0]
             red, dn = _mc_nav_outputs(self.B, S, self.K, dense)
             opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-            drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None else (_p(xi0), opt(eta))
+            drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
             args = (self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), *drw, opt(wv), _p(n0), _p(cn),
-                    *(() if rg is not None else (_p(xin), opt(nud))), m, opt(Hm), opt(rmv), int(nsub or 0),
+                    *(() if rg is not None and not vh.on else (opt(xin), opt(nud))), m, opt(Hm), opt(rmv), int(nsub or 0),
                     _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red], *[opt(a) for a in dn])
-            if rg is not None:
+            if vh.on:
+                self._chk(self._L.scvx_batch_track_mc_nav_veh(*args, *mq.args(self.B, self.K, S),
+                                                              *vh.args(self.B, S, rg, wv is not None, seed, sample_lo)),
+                          "scvx_batch_track_mc_nav_veh")
+            elif rg is not None:
                 self._chk(self._L.scvx_batch_track_mc_nav_rng(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_nav_rng")
             elif mq.on:
                 self._chk(self._L.scvx_batch_track_mc_nav_q(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_nav_q")
             else:
                 self._chk(self._L.scvx_batch_track_mc_nav(*args), "scvx_batch_track_mc_nav")
-            return McNavReport(*red, *dn)._with_q(mq)
+            return McNavReport(*red, *dn)._with_q(mq)._with_veh(vh)
         c0, xi0, eta, sw = _mc_inputs(S0, self.B, self.K, samples, seed, w, draws, sample_lo, rg is not None)
         S = int(samples) if rg is not None else xi0.shape[0]
         rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(self.B, S, dense)
         opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-        drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None else (_p(xi0), opt(eta))
+        drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
         args = (self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), *drw, opt(sw), None, int(nsub or 0),
                 _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov), opt(flights), opt(xland), opt(dx0))
-        if rg is not None:
+        if vh.on:
+            self._chk(self._L.scvx_batch_track_mc_veh(*args, *mq.args(self.B, self.K, S),
+                                                      *vh.args(self.B, S, rg, sw is not None, seed, sample_lo)),
+                      "scvx_batch_track_mc_veh")
+        elif rg is not None:
             self._chk(self._L.scvx_batch_track_mc_rng(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_rng")
         elif mq.on:
             self._chk(self._L.scvx_batch_track_mc_q(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_q")
         else:
             self._chk(self._L.scvx_batch_track_mc(*args), "scvx_batch_track_mc")
-        return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)
+        return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)._with_veh(vh)
 
     def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False):
         """Closed-loop covariance analysis of the batch's current accepted iterate under its LQR gains (scvx_batch_cov; S0, w and
@@ -422,7 +433,8 @@ class ScvxBatch:
         return self._margins_from_nav(S0, (N0, H, rm), w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
 
     def margins_from_mc(self, S0, p=0.99865, samples=1024, constraints="all", cap=0.25, seed=0, w=None, clamp=False, nav=None, q=None,
-                        r=None, qf=None, nsub=None, tol=0.0, draws=None, rng="host", independent=False, sample_lo=0, plan_lo=0):
+                        r=None, qf=None, nsub=None, tol=0.0, draws=None, rng="host", independent=False, sample_lo=0, plan_lo=0,
+                        vehicle=None):
         """Back-offs from the SAMPLED closed loop of the current accepted iterate -- nonlinear and aware of the clamp, where
         margins_from_cov / margins_from_nav are first order: one track_mc call (truth-fed, or flown on an estimate with nav = (N0, H,
         rm)) with the ranks of 1 - p and p and the per-node order statistics, montecarlo.margins_from_quantiles on them (the formulas,
@@ -431,13 +443,15 @@ class ScvxBatch:
         as set.  Limits: the glide back-off buys tan(gammaGs) times what is written; a tail quantile from `samples` flights carries the
         standard error montecarlo.quantile_stderr(p, samples) (0.26 sigma at the defaults, and beyond samples (1 - p) < 1 the rank is the
         sample's extreme); the draws are shared across plans unless `independent=True` (with rng="device": the lanes make the draws,
-        track_mc's keywords); with clamp=True the thrust function is still the unclamped command."""
+        track_mc's keywords); with clamp=True the thrust function is still the unclamped command.  vehicle = (mu, sp): the flights
+        carry per-flight vehicle errors (track_mc's keyword); the thrust pair still comes from the COMMAND, which only sees them through
+        the feedback."""
         from .montecarlo import margins_from_quantiles
         mask = self._margin_mask(constraints)
         names = [n for n, bit in _lib.MARGIN_BITS.items() if mask & bit]
         rep = self.track_mc(S0, samples=samples, seed=seed, w=w, q=q, r=r, qf=qf, nsub=nsub, clamp=clamp, tol=tol, draws=draws, nav=nav,
                             quantiles=(1.0 - p, p), per_node=True, rng=rng, independent=independent, sample_lo=sample_lo,
-                            plan_lo=plan_lo)
+                            plan_lo=plan_lo, vehicle=vehicle)
         x, u, _ = self.trajectory()
         cur = self.thrust_margins() + (self.path_margins(),)
         lo, hi, pm = margins_from_quantiles(self.cache.problem, x, u, rep.pathq[..., 0], rep.pathq[..., 1], names, cap, current=cur)
@@ -479,7 +493,7 @@ class ScvxBatch:
         flown on an estimate with the measurement H, rm at every node but the last; under navigation errors the covariance analysis'
         s(k) are too small, and a plan backed off by them keeps less than it shows.  Same limits, and the filter gain is the optimal
         one for the stated model.
-        mc = dict(p=..., samples=..., seed=..., clamp=..., rng=..., independent=..., sample_lo=..., plan_lo=...): the back-offs of each round come from the SAMPLED closed loop instead
+        mc = dict(p=..., samples=..., seed=..., clamp=..., rng=..., independent=..., sample_lo=..., plan_lo=..., vehicle=...): the back-offs of each round come from the SAMPLED closed loop instead
         (margins_from_mc: per-node order statistics Q_{1-p}, Q_p of `samples` flights, nonlinear and clamp-aware; nsigma is then not
         used).  mc and nav combine: the flights are flown on the estimate.  Limits as margins_from_mc; mc=None is the call it was."""
         if int(rounds) < 1:
@@ -488,8 +502,9 @@ class ScvxBatch:
         thrust_only = mask == _lib.MARGIN_BITS["thrust"]
         out = None
         if mc is not None:
-            if not isinstance(mc, dict) or not set(mc) <= {"p", "samples", "seed", "clamp", "rng", "independent", "sample_lo", "plan_lo"}:
-                raise ValueError("robustify: mc = dict(p=, samples=, seed=, clamp=, rng=, independent=, sample_lo=, plan_lo=)")
+            if not isinstance(mc, dict) or not set(mc) <= {"p", "samples", "seed", "clamp", "rng", "independent", "sample_lo", "plan_lo",
+                                                           "vehicle"}:
+                raise ValueError("robustify: mc = dict(p=, samples=, seed=, clamp=, rng=, independent=, sample_lo=, plan_lo=, vehicle=)")
             if nav is not None:
                 from .dynamics import _nav_arg
                 _nav_arg(nav, self.B)

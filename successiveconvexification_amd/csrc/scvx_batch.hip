@@ -992,7 +992,8 @@ int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, con
 static int batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
                             const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
                             double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
-                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx::McRng* rg) {
+                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx::McRng* rg,
+                            const scvx::McVeh* vh = nullptr, const char* entry = "scvx_batch_track_mc_q") {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1004,10 +1005,14 @@ static int batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU,
         return rc;
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
+    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
+    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
     if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const scvx::Dims d(b->B, b->K, b->NU, S, 0, nq);
     scvx::Staging s(ctx);
+    scvx::McVeh dvh;   // the vehicle errors with zeta and theta on the device
+    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
     const double* dc = s.in(C0, d.c14);
     scvx::McQ mq;
     mq.nq = nq, mq.ranks = ranks, mq.flightq = s.out(flightq, d.flightq), mq.pathq = s.out(pathq, d.pathq), mq.pathv = s.out(pathv, d.pathv);
@@ -1016,9 +1021,9 @@ static int batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU,
            *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14);
     s.launch([&] {
         return scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc, di, de, sw14, nsub, flags, tol, dr, dm, dv, df,
-                                     dl, d0, s.st, (flightq || pathq || pathv) ? &mq : nullptr, rg);
+                                     dl, d0, s.st, (flightq || pathq || pathv) ? &mq : nullptr, rg, vh ? &dvh : nullptr);
     });
-    return s.finish("scvx_batch_track_mc_q");
+    return s.finish(entry);
 }
 
 int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1053,7 +1058,8 @@ static int batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* 
                                 const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
                                 double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
                                 double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
-                                double* flightq, double* pathq, double* pathv, const scvx::McRng* rg) {
+                                double* flightq, double* pathq, double* pathv, const scvx::McRng* rg,
+                                const scvx::McVeh* vh = nullptr, const char* entry = "scvx_batch_track_mc_nav_q") {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1067,11 +1073,15 @@ static int batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* 
     if (!N0) return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (N0)");
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
+    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
+    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
     if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
     const int B = b->B, K = b->K;
     const scvx::Dims d(B, K, b->NU, S, m, nq);
     scvx::Staging s(ctx);
+    scvx::McVeh dvh;   // the vehicle errors with zeta and theta on the device
+    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
     const double *dc = s.in(C0, d.c14), *dn0 = s.in(N0, d.c14), *dcn = s.in(CN, d.c14), *di = s.in(xi0, d.xi), *dxi = s.in(xin, d.xi),
                  *de = s.in(eta, d.eta), *dnu = s.in(m > 0 ? nud : nullptr, d.nud);
     // the filter gains, written by the navigation launch with the same N0, H, rm and w; Kf does not depend on S0, which is zero here
@@ -1091,9 +1101,9 @@ static int batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* 
     s.launch([&] {
         return scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc, di, de, w14, b->tiles(), dk, dcn, dxi, dnu, m, H,
                                          rm, nsub, flags, tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st,
-                                         (flightq || pathq || pathv) ? &mq : nullptr, rg);
+                                         (flightq || pathq || pathv) ? &mq : nullptr, rg, vh ? &dvh : nullptr);
     });
-    return s.finish("scvx_batch_track_mc_nav_q");
+    return s.finish(entry);
 }
 
 int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1114,6 +1124,40 @@ int scvx_batch_track_mc_nav_rng(scvx_batch* b, const double* q14, const double* 
     const scvx::McRng rg{rng, noise};
     return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, C0, noise ? C0 : nullptr, w14, N0, CN, C0, C0, m, H, rm, nsub, flags, tol, mcrep,
                                 xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv, &rg);
+}
+
+// the _veh forms: the _q call (rng == NULL) or the _rng call (its placeholders as above) with the vehicle errors behind it
+int scvx_batch_track_mc_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                            const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
+                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx_mc_rng* rng, int noise,
+                            const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    if ((rc = scvx::check_mc_veh_draws(b->ctx, rng, noise, xi0, eta, nullptr, nullptr, zeta))) return rc;
+    const scvx::McRng rg{rng, noise};
+    const scvx::McVeh vh{veh, zeta, theta};
+    if (rng) xi0 = C0, eta = noise ? C0 : nullptr;
+    return batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland, dx0,
+                            nq, ranks, flightq, pathq, pathv, rng ? &rg : nullptr, &vh, "scvx_batch_track_mc_veh");
+}
+
+int scvx_batch_track_mc_nav_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                                const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
+                                const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
+                                double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
+                                double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
+                                double* flightq, double* pathq, double* pathv, const scvx_mc_rng* rng, int noise,
+                                const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    if ((rc = scvx::check_mc_veh_draws(b->ctx, rng, noise, xi0, eta, xin, nud, zeta))) return rc;
+    const scvx::McRng rg{rng, noise};
+    const scvx::McVeh vh{veh, zeta, theta};
+    if (rng) xi0 = xin = nud = C0, eta = noise ? C0 : nullptr;
+    return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean, xcov,
+                                jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv,
+                                rng ? &rg : nullptr, &vh, "scvx_batch_track_mc_nav_veh");
 }
 
 int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,

@@ -101,6 +101,7 @@ int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, c
 
 struct McQ;   // what the _q forms add to a sampled call (scvx_mc.hpp); nullptr: nothing, the instantiations without per-node samples
 struct McRng; // the _rng forms (scvx_mc.hpp): the draws are made on the device; nullptr: the uploaded draws, the instantiations without RNG
+struct McVeh; // the _veh forms (scvx_mc.hpp): per-flight vehicle errors; nullptr: the nominal vehicle, the instantiations without ACT
 
 // Sampled dispersion (scvx_mc.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan; C0[B][14][14],
 // xi0[S][14], eta[S][K][14] or nullptr, sw: host array of 14 or nullptr; mcrep[B][SCVX_MC_NREP], xmean[B][14], xcov[B][14][14];
@@ -108,7 +109,7 @@ struct McRng; // the _rng forms (scvx_mc.hpp): the draws are made on the device;
 hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
-                           const McQ* q = nullptr, const McRng* rng = nullptr);
+                           const McQ* q = nullptr, const McRng* rng = nullptr, const McVeh* veh = nullptr);
 int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain, const void* C0,
                    const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
                    const void* mcrep, const void* xmean, const void* xcov);
@@ -121,7 +122,7 @@ hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* kf, const double* CN, const double* xin, const double* nud, int m, const double* H,
                                const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
                                double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
-                               double* navK, hipStream_t st, const McQ* q = nullptr, const McRng* rng = nullptr);
+                               double* navK, hipStream_t st, const McQ* q = nullptr, const McRng* rng = nullptr, const McVeh* veh = nullptr);
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
                        const void* C0, const void* xi0, const void* eta, const double* w, const void* deriv, const void* kf,
                        const void* CN, const void* xin, const void* nud, int m, const double* H, const double* rm, int nsub, int flags,

@@ -124,7 +124,7 @@ int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* fligh
 hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
-                           const McQ* q, const McRng* rng) {
+                           const McQ* q, const McRng* rng, const McVeh* veh) {
     const int nblk = (S + 63) / 64;
     hipError_t e = mc_workspace(ctx, (size_t)B * nblk * MC_NP);
     if (e != hipSuccess) return e;
@@ -135,7 +135,7 @@ hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, 
     const McRngK rg = mc_noise(m, sw, false, eta, rng);
     double* part = ctx->mc_ws;
     e = launch_mc_fly<false>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng, rg, st,
-                             McNavA<double>{});
+                             McNavA<double>{}, veh);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mc_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov);
     e = hipGetLastError();
@@ -169,19 +169,21 @@ static int track_mc_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* x_de
                           const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
                           const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
                           double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
-                          double* pathq_dev, double* pathv_dev, const McRng* rg) {
+                          double* pathq_dev, double* pathv_dev, const McRng* rg, const McVeh* vh = nullptr) {
     int rc = scvx::check_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags,
                                   tol, mcrep_dev, xmean_dev, xcov_dev);
     if (rc) return rc;
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
+    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
+    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
     scvx::McQ q;
     q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
     const bool any = flightq_dev || pathq_dev || pathv_dev;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
     SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, rg ? nullptr : xi0_dev,
                                         rg ? nullptr : eta_dev, sw14, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, flights_dev,
-                                        xland_dev, dx0_dev, ctx->stream, any ? &q : nullptr, rg));
+                                        xland_dev, dx0_dev, ctx->stream, any ? &q : nullptr, rg, vh));
     return SCVX_OK;
 }
 
@@ -189,7 +191,8 @@ static int track_mc_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* x_de
 static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
                            int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0,
-                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg);
+                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg,
+                           const McVeh* vh = nullptr, const char* entry = "scvx_track_mc_q_f64_host");
 
 // one lane per (plan, s): the draws the _rng forms consume (mc_draws_kernel); any of the four outputs may be nullptr
 hipError_t launch_mc_draws(const scvx_mc_rng& r, int P, int S, int K, double* xi0, double* eta, double* xin, double* nud, hipStream_t st) {
@@ -263,6 +266,39 @@ int scvx_track_mc_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double*
                                  xmean, xcov, flights, xland, dx0, nq, ranks, flightq, pathq, pathv, &rg);
 }
 
+// the _veh forms: the _q call (rng == NULL) or the _rng call (its placeholders as above) with the vehicle errors behind it
+int scvx_track_mc_veh_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                          const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
+                          const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
+                          double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
+                          double* pathq_dev, double* pathv_dev, const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh,
+                          const double* zeta_dev, double* theta_dev) {
+    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0_dev, eta_dev, nullptr, nullptr, zeta_dev);
+    if (rc) return rc;
+    const scvx::McRng rg{rng, noise};
+    const scvx::McVeh vh{veh, zeta_dev, theta_dev};
+    if (rng) xi0_dev = x_dev, eta_dev = noise ? x_dev : nullptr;
+    return scvx::track_mc_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags, tol,
+                                mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, nq, ranks, flightq_dev, pathq_dev,
+                                pathv_dev, rng ? &rg : nullptr, &vh);
+}
+
+int scvx_track_mc_veh_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* sw14,
+                               const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                               double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
+                               double* pathv, const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta,
+                               double* theta) {
+    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0, eta, nullptr, nullptr, zeta);
+    if (rc) return rc;
+    const scvx::McRng rg{rng, noise};
+    const scvx::McVeh vh{veh, zeta, theta};
+    if (rng) xi0 = x, eta = noise ? x : nullptr;
+    return scvx::track_mc_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
+                                 flights, xland, dx0, nq, ranks, flightq, pathq, pathv, rng ? &rg : nullptr, &vh,
+                                 "scvx_track_mc_veh_f64_host");
+}
+
 int scvx_track_mc_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                       const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
                       const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
@@ -295,14 +331,19 @@ namespace scvx {
 static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
                            int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0,
-                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg) {
+                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg, const McVeh* vh,
+                           const char* entry) {
     int rc = scvx::check_track_mc(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov);
     if (rc) return rc;
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
+    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
+    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
     const Dims d(B, K, scvx_control_dim(ctx), S, 0, nq);
     Staging s(ctx);
+    McVeh dvh;   // the vehicle errors with zeta and theta on the device
+    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
     McQ q;
     q.nq = nq, q.ranks = ranks, q.flightq = s.out(flightq, d.flightq), q.pathq = s.out(pathq, d.pathq), q.pathv = s.out(pathv, d.pathv);
     const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dc = s.in(C0, d.c14),
@@ -311,9 +352,9 @@ static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, 
            *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14);
     s.launch([&] {
         return launch_track_mc(ctx, B, K, S, dx, du, ds, dg, dc, di, de, sw14, nsub, flags, tol, dr, dm, dv, df, dl, d0, s.st,
-                               (flightq || pathq || pathv) ? &q : nullptr, rg);
+                               (flightq || pathq || pathv) ? &q : nullptr, rg, vh ? &dvh : nullptr);
     });
-    return s.finish("scvx_track_mc_q_f64_host");
+    return s.finish(entry);
 }
 
 }  // namespace scvx

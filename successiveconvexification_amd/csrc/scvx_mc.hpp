@@ -62,6 +62,31 @@ struct McRng {
 inline McRngK mc_rng_k(const McRng& g, bool noise) {
     return McRngK{g.r->seed, g.r->s_lo, g.r->b_lo, g.r->independent, noise ? 1 : 0};
 }
+// The _veh forms: per-flight vehicle errors theta = mu + sp * zeta (include/scvx.h).  zeta [S][6] and theta [B][S][6] are device
+// pointers or nullptr (zeta is not read when the lanes make the draws); McVehK is what the ACT instantiations take as their last
+// kernel argument.
+struct McVeh {
+    const scvx_mc_vehicle* v = nullptr;
+    const double* zeta = nullptr;
+    double* theta = nullptr;
+};
+struct McVehK {
+    double mu[SCVX_VEH_N], sp[SCVX_VEH_N];
+    const double* zeta;
+    double* theta;
+};
+inline McVehK mc_veh_k(const McVeh& h) {
+    McVehK k{};
+    for (int i = 0; i < SCVX_VEH_N; i++) k.mu[i] = h.v->mu[i], k.sp[i] = h.v->sp[i];
+    k.zeta = h.zeta, k.theta = h.theta;
+    return k;
+}
+// veh may be nullptr (then zeta and theta must be); rng: whether the lanes make the draws
+int check_mc_vehicle(scvx_ctx* ctx, const scvx_mc_vehicle* veh, const void* zeta, const void* theta, bool rng);
+// what the _veh entry points ask of the draws before they become a _q or an _rng call: with rng every uploaded draw must be NULL,
+// without it noise must be 0
+int check_mc_veh_draws(scvx_ctx* ctx, const scvx_mc_rng* rng, int noise, const void* xi0, const void* eta, const void* xin,
+                       const void* nud, const void* zeta);
 int check_mc_rng(scvx_ctx* ctx, const scvx_mc_rng* rng);
 int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq);
 int check_ranks(scvx_ctx* ctx, int S, int nq, const int* ranks);

@@ -1,6 +1,6 @@
 // The flying kernel of the sampled closed-loop dispersion, its launch and the front of its finish: ONE body for the flight on the true
-// state (scvx_mc.hip instantiates it with NAV = false) and for the flight on a navigation estimate (scvx_mc_nav.hip: NAV = true).  Not
-// part of the ABI.
+// state (scvx_mc.hip instantiates it with NAV = false) and for the flight on a navigation estimate (scvx_mc_nav.hip: NAV = true), and
+// for both with per-flight vehicle errors (ACT = true: scvx_mc_veh.hip and scvx_mc_nav_veh.hip).  Not part of the ABI.
 //
 // mc_fly_kernel: ONE LANE PER FLIGHT (plan b, sample s); the 64 lanes of a wavefront are 64 consecutive samples of the SAME plan, blocks
 // of one wavefront, grid (ceil(S / 64), B).  Every read of the plan -- x, u, sigma, the gains -- is then one address for the whole
@@ -42,6 +42,16 @@
 // of the RNG-off kernel fed the draws mc_draws_kernel dumps (tests/test_gpu_mc_rng.py).  With NAV eta_k is formed once, at the error's
 // time step, and rests in LDS (a column per lane, 7 KB per block) until the truth's impulse behind the segment; of nud_k only the blocks
 // that hold its first m draws are formed.
+//
+// ACT: per-flight vehicle errors theta = fma(sp, zeta, mu) (include/scvx.h "vehicle errors"), six per lane in registers, formed before
+// the start -- from zeta [S][6], or with RNG from the first six normals of group 0 of stream 8.  Every statement of it is under
+// `if constexpr (ACT)`, and its kernel argument (McVehK) is a trailing pack that is empty without it: an instantiation without ACT has
+// the argument block and the body it had.  The error lies BEHIND the command: the law, the clamp, the counters, the samples of the
+// thrust band and pathv see the commanded hold uu; only the control handed to rhs_only at the four RK stages is the applied one,
+//     ua[0:3] = (1 + th0) (uu[0:3] + d x uu[0:3]),  d = (0, th1, th2);      ua[3:5] = (1 + th5) uu[3:5]
+// and rhs_only reads alpha (1 + th3), force_scalar (1 + th4) and trq_scalar (1 + th4) from a per-lane copy of the parameter block,
+// of which only these three fields leave the scalar registers.  With NAV the recursion of eps is untouched.  The ACT instantiations
+// live in translation units of their own (scvx_mc_veh.hip, scvx_mc_nav_veh.hip), compiled beside the others.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -55,7 +65,11 @@ constexpr int MCN_SRM = 196, MCN_MODEL = 210;
 // The argument list is the same with and without NAV (without it mm = 0 and hm, deriv .. nud, navfed, navK are nullptr and never read).
 // DS is the tiles' storage type (double, or float with scvx_batch_set_linearization_f32: widened on load, as nav_cov_kernel does);
 // without NAV only DS = double is instantiated.
-template <bool AERO, bool FIN, bool TRQ, bool PV, bool RNG, bool NAV, typename DS = double>
+template <typename T>
+__device__ __forceinline__ const T& mc_first(const T& t) { return t; }
+struct McNone {};
+
+template <bool AERO, bool FIN, bool TRQ, bool PV, bool RNG, bool NAV, typename DS = double, bool ACT = false, typename... VA>
 __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK c, McK m, int mm, const double* __restrict__ hm, int S, int K,
                                                     const double* __restrict__ x, const double* __restrict__ u,
                                                     const double* __restrict__ sigma, const double* __restrict__ gain,
@@ -66,7 +80,8 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
                                                     int nsub, int opt, double* __restrict__ part, double* __restrict__ flights,
                                                     double* __restrict__ xland, double* __restrict__ dx0o,
                                                     double* __restrict__ navfed, double* __restrict__ navK,
-                                                    double* __restrict__ pathv, McRngK rg) {
+                                                    double* __restrict__ pathv, McRngK rg, VA... va) {
+    static_assert(sizeof...(VA) == (ACT ? 1 : 0), "the ACT instantiations take one McVehK behind rg, the others nothing");
     typedef double R;
     // NAV only (without it none of these is referenced and none remains: LDS 0).  epl: eps rests here while the segment is integrated,
     // one column per lane, no lane reads another's; Al, Kl, Hl: A_k, Kf_k and the model (hm), written by the wave, read by every lane at
@@ -101,6 +116,30 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
     const R ninf = -std::numeric_limits<double>::infinity();
     const bool clamp = (opt & SCVX_TRACK_CLAMP) != 0;
     R xs[14], ukv[NU], upv[NU], eps[NAV ? 14 : 1];
+    R th[ACT ? SCVX_VEH_N : 1];       // ACT: the vehicle errors of this flight
+    // ACT: the parameter block with this flight's alpha, force_scalar and trq_scalar (without ACT: nothing)
+    auto pl = [&] {
+        if constexpr (ACT) return p;
+        else return McNone{};
+    }();
+    if constexpr (ACT) {
+        const McVehK& vk = mc_first(va...);
+        R zv[16];
+        if (RNG) {
+            mc_draw_group(rg.seed, MC_STREAM_VEH, rc2, rc3, 0, SCVX_VEH_N, zv);
+        } else {
+#pragma unroll
+            for (int i = 0; i < SCVX_VEH_N; i++) zv[i] = vk.zeta ? vk.zeta[(size_t)s_ * SCVX_VEH_N + i] : R(0.0);
+        }
+#pragma unroll
+        for (int i = 0; i < SCVX_VEH_N; i++) {
+            th[i] = fma(vk.sp[i], zv[i], vk.mu[i]);
+            if (vk.theta && live) vk.theta[fl * SCVX_VEH_N + i] = th[i];
+        }
+        pl.alpha = p.alpha * (R(1.0) + th[SCVX_VEH_ISP]);
+        if constexpr (AERO) pl.force_scalar = p.force_scalar * (R(1.0) + th[SCVX_VEH_AERO]);
+        if constexpr (TRQ) pl.trq_scalar = p.trq_scalar * (R(1.0) + th[SCVX_VEH_AERO]);
+    }
     // ---- the start: dx0 = C0 xi0 (and eps_0 = CN xin), summed with fma in ascending j ----
     {
         R xv[16];
@@ -322,7 +361,21 @@ __global__ __launch_bounds__(64) void mc_fly_kernel(DynPK<double, TRQ> p, PathK 
 #pragma unroll
                 for (int j = 0; j < NU; j++) uu[j] = fma(ukv[j], lkm, upv[j] * lkp);
                 R g[14];
-                rhs_only<AERO, FIN, TRQ>(p, xt, uu, g);
+                if constexpr (ACT) {
+                    // the applied control: scale and first-order rotation of the thrust, scale of the fins
+                    const R sc = R(1.0) + th[SCVX_VEH_THRUST];
+                    R ua[NU];
+                    ua[0] = sc * (uu[0] + (th[SCVX_VEH_MIS_Y] * uu[2] - th[SCVX_VEH_MIS_Z] * uu[1]));
+                    ua[1] = sc * (uu[1] + th[SCVX_VEH_MIS_Z] * uu[0]);
+                    ua[2] = sc * (uu[2] - th[SCVX_VEH_MIS_Y] * uu[0]);
+                    if constexpr (FIN) {
+                        ua[3] = (R(1.0) + th[SCVX_VEH_FIN]) * uu[3];
+                        ua[4] = (R(1.0) + th[SCVX_VEH_FIN]) * uu[4];
+                    }
+                    rhs_only<AERO, FIN, TRQ>(pl, xt, ua, g);
+                } else {
+                    rhs_only<AERO, FIN, TRQ>(p, xt, uu, g);
+                }
                 const R wacc = h * ((stg == 0 || stg == 3) ? (R(1.0) / R(6.0)) : (R(1.0) / R(3.0)));
                 const R wnext = h * (stg == 2 ? R(1.0) : R(0.5));
 #pragma unroll
@@ -554,20 +607,27 @@ struct McNavA {
     double *navfed, *navK;
 };
 
-// The launch of the flying kernel, for both translation units: the instantiation of the context's model, with PV when pathv is asked
-// for and RNG when the lanes make the draws.
-template <bool NAV, typename DS>
-hipError_t launch_mc_fly(scvx_ctx* ctx, const McK& m, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                         const double* gain, const double* C0, const double* xi0, const double* eta, int nsub, int flags, double* part,
-                         double* flights, double* xland, double* dx0, double* pv, const McRng* rng, const McRngK& rg, hipStream_t st,
-                         const McNavA<DS>& n) {
+// The launch of the flying kernel, for all four translation units: the instantiation of the context's model, with PV when pathv is
+// asked for and RNG when the lanes make the draws.  ACT: the instantiations with vehicle errors, veh their argument (else nullptr).
+template <bool NAV, typename DS, bool ACT>
+hipError_t launch_mc_fly_t(scvx_ctx* ctx, const McK& m, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                           const double* gain, const double* C0, const double* xi0, const double* eta, int nsub, int flags, double* part,
+                           double* flights, double* xland, double* dx0, double* pv, const McRng* rng, const McRngK& rg, hipStream_t st,
+                           const McNavA<DS>& n, const McVeh* veh) {
     const PathK c = path_constants(ctx->prob);
     const double dt = 1.0 / (K + 1);
     const dim3 g((unsigned)((S + 63) / 64), (unsigned)B), blk(64);
     const DynP<double> dp(ctx->dyn);
-#define SCVX_MC_RG(A, F, T, P, G, par)                                                                                                      \
-    hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G, NAV, DS>), g, blk, 0, st, par, c, m, n.mm, n.hm, S, K, x, u, sigma, gain, C0, xi0, eta, \
-                       n.deriv, n.kf, n.CN, n.xin, n.nud, dt, nsub, flags, part, flights, xland, dx0, n.navfed, n.navK, pv, rg)
+#define SCVX_MC_ARGS(par) \
+    par, c, m, n.mm, n.hm, S, K, x, u, sigma, gain, C0, xi0, eta, n.deriv, n.kf, n.CN, n.xin, n.nud, dt, nsub, flags, part, flights, xland, dx0, \
+        n.navfed, n.navK, pv, rg
+#define SCVX_MC_RG(A, F, T, P, G, par)                                                                                           \
+    do {                                                                                                                         \
+        if constexpr (ACT)                                                                                                       \
+            hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G, NAV, DS, true, McVehK>), g, blk, 0, st, SCVX_MC_ARGS(par), mc_veh_k(*veh)); \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G, NAV, DS>), g, blk, 0, st, SCVX_MC_ARGS(par));                        \
+    } while (0)
 #define SCVX_MC_PV(A, F, T, P, par)                 \
     do {                                            \
         if (rng) SCVX_MC_RG(A, F, T, P, true, par); \
@@ -592,7 +652,31 @@ hipError_t launch_mc_fly(scvx_ctx* ctx, const McK& m, int B, int K, int S, const
 #undef SCVX_MC
 #undef SCVX_MC_PV
 #undef SCVX_MC_RG
+#undef SCVX_MC_ARGS
     return hipGetLastError();
+}
+
+// The ACT instantiations of the launch are made in scvx_mc_veh.hip (NAV = false) and scvx_mc_nav_veh.hip (NAV = true, DS double and
+// float) alone: these declarations keep every other translation unit from instantiating them, and with them their kernels.
+#define SCVX_MC_FLY_ACT(NAV, DS)                                                                                                         \
+    hipError_t launch_mc_fly_t<NAV, DS, true>(scvx_ctx*, const McK&, int, int, int, const double*, const double*, const double*,         \
+                                              const double*, const double*, const double*, const double*, int, int, double*, double*,    \
+                                              double*, double*, double*, const McRng*, const McRngK&, hipStream_t, const McNavA<DS>&,    \
+                                              const McVeh*)
+extern template SCVX_MC_FLY_ACT(false, double);
+extern template SCVX_MC_FLY_ACT(true, double);
+extern template SCVX_MC_FLY_ACT(true, float);
+
+template <bool NAV, typename DS>
+hipError_t launch_mc_fly(scvx_ctx* ctx, const McK& m, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                         const double* gain, const double* C0, const double* xi0, const double* eta, int nsub, int flags, double* part,
+                         double* flights, double* xland, double* dx0, double* pv, const McRng* rng, const McRngK& rg, hipStream_t st,
+                         const McNavA<DS>& n, const McVeh* veh = nullptr) {
+    if (veh)
+        return launch_mc_fly_t<NAV, DS, true>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng,
+                                              rg, st, n, veh);
+    return launch_mc_fly_t<NAV, DS, false>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng,
+                                           rg, st, n, nullptr);
 }
 
 }  // namespace scvx

@@ -89,7 +89,8 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
                                         const DS* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int mm,
                                         const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                         double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland,
-                                        double* dx0, double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
+                                        double* dx0, double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng,
+                                        const McVeh* veh) {
     const int nblk = (S + 63) / 64;
     const size_t nrows = (size_t)B * nblk * MCN_NP;
     hipError_t e = mc_workspace(ctx, nrows + MCN_MODEL);
@@ -108,7 +109,8 @@ static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, cons
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const McNavA<DS> na{mm, hm, deriv, kf, CN, xin, nud, navfed, navK};
-    e = launch_mc_fly<true>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng, rg, st, na);
+    e = launch_mc_fly<true>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng, rg, st, na,
+                            veh);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mc_nav_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov, jmean, jcov, mcnav);
     e = hipGetLastError();
@@ -121,13 +123,13 @@ hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* kf, const double* CN, const double* xin, const double* nud, int m, const double* H,
                                const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
                                double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
-                               double* navK, hipStream_t st, const McQ* q, const McRng* rng) {
+                               double* navK, hipStream_t st, const McQ* q, const McRng* rng, const McVeh* veh) {
     return deriv.d ? launch_track_mc_nav_t<double>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv.d, kf, CN, xin, nud, m, H, rm, nsub,
                                                    flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st,
-                                                   q, rng)
+                                                   q, rng, veh)
                    : launch_track_mc_nav_t<float>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv.f, kf, CN, xin, nud, m, H, rm, nsub,
                                                   flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q,
-                                                  rng);
+                                                  rng, veh);
 }
 
 int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
@@ -158,13 +160,15 @@ static int track_mc_nav_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* 
                               double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
                               double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
                               double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev,
-                              const McRng* rg) {
+                              const McRng* rg, const McVeh* vh = nullptr) {
     int rc = scvx::check_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
                                       CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
                                       jcov_dev, mcnav_dev);
     if (rc) return rc;
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
+    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
+    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
     if (rg) xi0_dev = eta_dev = xin_dev = nud_dev = nullptr;   // placeholders until here: the lanes make the draws
     scvx::McQ q;
     q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
@@ -173,7 +177,7 @@ static int track_mc_nav_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* 
     SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14,
                                             scvx::Tiles{deriv_dev, nullptr}, kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol,
                                             mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev,
-                                            navfed_dev, navK_dev, ctx->stream, any ? &q : nullptr, rg));
+                                            navfed_dev, navK_dev, ctx->stream, any ? &q : nullptr, rg, vh));
     return SCVX_OK;
 }
 
@@ -183,7 +187,7 @@ static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
-                               const McRng* rg);
+                               const McRng* rg, const McVeh* vh = nullptr, const char* entry = "scvx_track_mc_nav_q_f64_host");
 
 }  // namespace scvx
 
@@ -230,6 +234,43 @@ int scvx_track_mc_nav_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const dou
                                      flightq, pathq, pathv, &rg);
 }
 
+// the _veh forms: the _q call (rng == NULL) or the _rng call (its placeholders as above) with the vehicle errors behind it
+int scvx_track_mc_nav_veh_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                              const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev,
+                              const double* w14, const double* deriv_dev, const double* kf_dev, const double* CN_dev,
+                              const double* xin_dev, const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags,
+                              double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
+                              double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
+                              double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev,
+                              const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta_dev, double* theta_dev) {
+    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0_dev, eta_dev, xin_dev, nud_dev, zeta_dev);
+    if (rc) return rc;
+    const scvx::McRng rg{rng, noise};
+    const scvx::McVeh vh{veh, zeta_dev, theta_dev};
+    if (rng) xi0_dev = xin_dev = nud_dev = x_dev, eta_dev = noise ? x_dev : nullptr;
+    return scvx::track_mc_nav_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
+                                    CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
+                                    jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, nq, ranks, flightq_dev,
+                                    pathq_dev, pathv_dev, rng ? &rg : nullptr, &vh);
+}
+
+int scvx_track_mc_nav_veh_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                                   const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
+                                   const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                                   const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                                   double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                                   double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
+                                   const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
+    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0, eta, xin, nud, zeta);
+    if (rc) return rc;
+    const scvx::McRng rg{rng, noise};
+    const scvx::McVeh vh{veh, zeta, theta};
+    if (rng) xi0 = xin = nud = x, eta = noise ? x : nullptr;
+    return scvx::track_mc_nav_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags, tol,
+                                     mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq,
+                                     pathv, rng ? &rg : nullptr, &vh, "scvx_track_mc_nav_veh_f64_host");
+}
+
 int scvx_track_mc_nav_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                           const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
                           const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
@@ -273,15 +314,19 @@ static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double*
                                const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
-                               const McRng* rg) {
+                               const McRng* rg, const McVeh* vh, const char* entry) {
     int rc = scvx::check_track_mc_nav(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
                                       tol, mcrep, xmean, xcov, jmean, jcov, mcnav);
     if (rc) return rc;
     if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
     if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
     if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
+    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
+    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
     const Dims d(B, K, scvx_control_dim(ctx), S, m, nq);
     Staging s(ctx);
+    McVeh dvh;   // the vehicle errors with zeta and theta on the device
+    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
     const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dc = s.in(C0, d.c14),
                  *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta), *dd = s.in(deriv, d.deriv), *dk = s.in(m > 0 ? kf : nullptr, d.kf),
                  *dcn = s.in(CN, d.c14), *dxi = s.in(xin, d.xi), *dnu = s.in(m > 0 ? nud : nullptr, d.nud);
@@ -292,9 +337,10 @@ static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double*
     q.nq = nq, q.ranks = ranks, q.flightq = s.out(flightq, d.flightq), q.pathq = s.out(pathq, d.pathq), q.pathv = s.out(pathv, d.pathv);
     s.launch([&] {
         return launch_track_mc_nav(ctx, B, K, S, dx, du, ds, dg, dc, di, de, w14, Tiles{dd, nullptr}, dk, dcn, dxi, dnu, m, H, rm, nsub, flags,
-                                   tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st, (flightq || pathq || pathv) ? &q : nullptr, rg);
+                                   tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st, (flightq || pathq || pathv) ? &q : nullptr, rg,
+                                   vh ? &dvh : nullptr);
     });
-    return s.finish("scvx_track_mc_nav_q_f64_host");
+    return s.finish(entry);
 }
 
 }  // namespace scvx

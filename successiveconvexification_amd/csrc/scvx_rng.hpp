@@ -18,7 +18,7 @@ namespace scvx {
 
 constexpr uint64_t PHILOX_M0 = 0xD2E7470EE14C6C93ull, PHILOX_M1 = 0xCA5A826395121157ull;
 constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CAA73Bull;
-constexpr uint64_t MC_STREAM_TRUTH = 6, MC_STREAM_NAV = 7;
+constexpr uint64_t MC_STREAM_TRUTH = 6, MC_STREAM_NAV = 7, MC_STREAM_VEH = 8;   // VEH: the vehicle errors, the first six normals of group 0
 
 // scvx_mc_rng as the kernels take it, and whether the truth receives impulses
 struct McRngK {

@@ -377,7 +377,7 @@ class McReport:
     (_lib.PSIG_COLUMNS) at every node, and the dense `pathv` [B][K+1][5][S]; each None when not asked for.  A quantile is a selection
     of one flight's value, with the sampling error of montecarlo.quantile_stderr."""
 
-    probs = ranks = q = pathq = pathv = None
+    probs = ranks = q = pathq = pathv = theta = None
 
     def __init__(self, raw, xmean, xcov, flights=None, xland=None, dx0=None):
         self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.MC_NREP)
@@ -388,6 +388,11 @@ class McReport:
 
     def _with_q(self, mq):
         self.probs, self.ranks, self.q, self.pathq, self.pathv = mq.probs, mq.ranks, mq.flightq, mq.pathq, mq.pathv
+        return self
+
+    def _with_veh(self, vh):
+        """`theta` [B][S][6]: the vehicle errors every flight flew (a call with vehicle= and the dense name "theta"), else None"""
+        self.theta = vh.theta
         return self
 
     def _qi(self, p):
@@ -466,6 +471,50 @@ class _McQ:
         return (nq, self.ranks.ctypes.data_as(C.POINTER(C.c_int)) if nq else None, opt(self.flightq), opt(self.pathq), opt(self.pathv))
 
 
+class _McVeh:
+    """What the _veh forms of the sampled calls add: vehicle = None, (mu, sp) as montecarlo.vehicle_errors returns them, or (mu, sp,
+    zeta [S][6]) with draws of the caller's own, and "theta" among the dense names -> the five trailing C arguments (rng, noise, veh,
+    zeta, theta).  `on` False: the call is the one it was, with exactly its arguments."""
+
+    def __init__(self, vehicle, dense):
+        self.rest = dense
+        want = False
+        if not (dense is True or not dense):
+            names = {dense} if isinstance(dense, str) else set(dense)
+            want = "theta" in names
+            self.rest = tuple(n for n in names if n != "theta")
+        self.on = vehicle is not None
+        if want and not self.on:
+            raise ValueError('dense "theta" needs vehicle=')
+        self.want, self.theta, self.zeta, self.veh = want, None, None, None
+        if self.on:
+            if len(vehicle) not in (2, 3):
+                raise ValueError("vehicle = (mu [6], sp [6]) or (mu, sp, zeta [S][6]): montecarlo.vehicle_errors")
+            mu, sp = (np.ascontiguousarray(v, np.float64) for v in vehicle[:2])
+            if mu.shape != (6,) or sp.shape != (6,):
+                raise ValueError("vehicle = (mu [6], sp [6]) or (mu, sp, zeta [S][6]): montecarlo.vehicle_errors")
+            self.veh = _lib.ScvxMcVehicle((C.c_double * 6)(*mu), (C.c_double * 6)(*sp), (C.c_int32 * 2)(0, 0))
+            self.sp = sp
+            self.zeta = None if len(vehicle) == 2 or vehicle[2] is None else np.ascontiguousarray(vehicle[2], np.float64)
+
+    def args(self, B, S, rg, noise, seed, lo):
+        """(rng, noise, veh, zeta, theta) of a call with `S` samples; rg: the scvx_mc_rng of rng="device" or None"""
+        from .montecarlo import mc_vehicle_draws
+        if rg is not None:
+            if self.zeta is not None:
+                raise ValueError('vehicle: zeta cannot be combined with rng="device": the device makes its own '
+                                 "(montecarlo.mc_vehicle_draws_device is its twin)")
+        elif self.zeta is None:
+            self.zeta = mc_vehicle_draws(S, seed, lo)
+        elif self.zeta.shape != (S, 6):
+            raise ValueError("shape mismatch: zeta [S][6]")
+        if self.want:
+            self.theta = np.empty((B, S, 6))
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        return (C.byref(rg) if rg is not None else None, (1 if noise else 0) if rg is not None else 0, C.byref(self.veh),
+                opt(self.zeta), opt(self.theta))
+
+
 def _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo):
     """rng = "host" (the draws are made here and uploaded: None) or "device" (the lanes make them: the scvx_mc_rng of the _rng forms)"""
     if rng not in ("host", "device"):
@@ -533,7 +582,7 @@ def _mc_outputs(B, S, dense):
 
 def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=0, w=None, nsub=10, clamp=False, tol=0.0, dense=(),
                    draws=None, nav=None, quantiles=None, per_node=False, rng="host", independent=False, sample_lo=0,
-                   plan_lo=0) -> McReport:
+                   plan_lo=0, vehicle=None) -> McReport:
     """Sampled closed-loop dispersion of the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] tracked under the gains gain
     [B][K][nu][14+nu]: `samples` flights PER PLAN on the device, reduced there to one McReport row per plan (scvx_track_mc_f64_host;
     the model, the impulse convention and the limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one [14][14]
@@ -553,15 +602,23 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     in include/scvx.h): nothing is generated or uploaded here, and the flights are bitwise those of the call fed
     mc_draws_device_batch's dump.  independent=True (device only): every plan flies draws of its own, plan b the stream plan_lo + b, so
     the rows of one call are independent experiments; sample_lo: the first sample, so that shards of one sample set can be flown by
-    separate calls.  rng="host" (the default) makes exactly the C calls it always made; draws= cannot be combined with "device"."""
+    separate calls.  rng="host" (the default) makes exactly the C calls it always made; draws= cannot be combined with "device".
+    vehicle = (mu, sp) (montecarlo.vehicle_errors): every flight flies a vehicle of its own, theta = mu + sp * zeta constant over the
+    flight -- thrust scale, thrust misalignment, specific impulse, aerodynamic scale, fin scale (scvx_track_mc_veh_f64_host; the model
+    and its limits are in include/scvx.h).  The error lies behind the command: the law, the clamp, OUT_LO / OUT_HI and the thrust
+    columns see the command, the state columns and the landing statistics the vehicle that flew.  zeta [S][6] is
+    montecarlo.mc_vehicle_draws of `seed` with rng="host" (or the third entry of vehicle), the device's stream 8 with "device"
+    (montecarlo.mc_vehicle_draws_device is its twin); dense may name "theta" for the errors flown, `theta` [B][S][6].  None (the
+    default): exactly the C calls made without it."""
     rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
     if nav is not None:
         n0, _, Hm, rv = _nav_arg(nav, np.shape(x)[0])
         _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / np.shape(x)[1])
         return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
                                   tol=tol, dense=dense, draws=draws, quantiles=quantiles, per_node=per_node, rng=rng,
-                                  independent=independent, sample_lo=sample_lo, plan_lo=plan_lo)
-    mq = _McQ(quantiles, per_node, dense)
+                                  independent=independent, sample_lo=sample_lo, plan_lo=plan_lo, vehicle=vehicle)
+    vh = _McVeh(vehicle, dense)
+    mq = _McQ(quantiles, per_node, vh.rest)
     dense = mq.rest
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
@@ -576,17 +633,43 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     S = int(samples) if rg is not None else xi0.shape[0]
     rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None else (_p(xi0), opt(eta))
+    drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
     args = (cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), *drw, opt(sw), None,
             int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov),
             opt(flights), opt(xland), opt(dx0))
-    if rg is not None:
+    if vh.on:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_veh_f64_host(*args, *mq.args(B, K1 - 1, S),
+                                                                     *vh.args(B, S, rg, sw is not None, seed, sample_lo)),
+                   "scvx_track_mc_veh_f64_host")
+    elif rg is not None:
         _lib.check(cache.handle, cache._L.scvx_track_mc_rng_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_rng_f64_host")
     elif mq.on:
         _lib.check(cache.handle, cache._L.scvx_track_mc_q_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_q_f64_host")
     else:
         _lib.check(cache.handle, cache._L.scvx_track_mc_f64_host(*args), "scvx_track_mc_f64_host")
-    return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)
+    return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)._with_veh(vh)
+
+
+def vehicle_sensitivity_batch(cache: IntegratorCache, x, u, sigma, gain, h=2.0 ** -10, nsub=10, clamp=False):
+    """J [B][14][6] = d x_K / d theta of the closed loop about the nominal vehicle and the planned start: central differences of step h
+    from ONE sampled launch (track_mc_batch with vehicle=) -- C0 = 0, no noise, twelve flights with zeta = +-e_i, sp = h, the dense
+    landings.  The column of a component the model does not have (AERO without aerodynamics, FIN without fins) is zero.  The error
+    of a central difference is h^2 / 6 times the third derivative plus the flights' rounding over 2 h; montecarlo.vehicle_budget turns
+    J into each component's share of the landing variance."""
+    B = np.shape(x)[0]
+    sp = np.full(6, float(h))
+    if not isinstance(cache.problem.aero, AtmosphericData):
+        sp[_lib.VEH_INDEX["AERO"]] = 0.0
+    if cache.nu != 5:
+        sp[_lib.VEH_INDEX["FIN"]] = 0.0
+    zeta = np.zeros((12, 6))
+    zeta[0::2] = np.eye(6)
+    zeta[1::2] = -np.eye(6)
+    rep = track_mc_batch(cache, x, u, sigma, gain, np.zeros(14), 12, nsub=nsub, clamp=clamp, dense=("xland",),
+                         draws=(np.zeros((12, 14)), None), vehicle=(np.zeros(6), sp, zeta))
+    J = (rep.xland[:, 0::2] - rep.xland[:, 1::2]) / (2.0 * float(h))   # [B][6][14]
+    J[:, sp == 0.0] = 0.0
+    return np.ascontiguousarray(np.swapaxes(J, 1, 2))
 
 
 class NavReport(CovReport):
@@ -761,7 +844,7 @@ def _mc_nav_outputs(B, S, K, dense):
 
 def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0, H, rm, samples, seed=0, w=None, kf=None, nsub=10,
                        clamp=False, tol=0.0, dense=(), draws=None, quantiles=None, per_node=False, rng="host", independent=False,
-                       sample_lo=0, plan_lo=0) -> McNavReport:
+                       sample_lo=0, plan_lo=0, vehicle=None) -> McNavReport:
     """track_mc_batch with the law fed a navigation ESTIMATE whose error is generated per flight on the device (scvx_track_mc_nav_f64_host;
     the model and its limits are in include/scvx.h): the sampled, nonlinear counterpart of nav_cov_batch, whose arguments deriv, N0, H,
     rm and w mean here what they mean there.  The error starts at handover_factor(N0[b]) @ xin[s], is corrected at every node but the
@@ -770,9 +853,12 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     montecarlo.mc_nav_draws of `seed`, or draws = (xi0, eta, xin, nud).  dense: True, or names out of "flights", "xland", "dx0",
     "navfed", "navK".  quantiles, per_node and the dense name "pathv" as track_mc_batch (scvx_track_mc_nav_q_f64_host): the state
     path functions are those of the TRUTH, the thrust norm that of the command formed from the estimate.  rng, independent, sample_lo
-    and plan_lo as track_mc_batch (scvx_track_mc_nav_rng_f64_host): with "device" the lanes make all four draws."""
+    and plan_lo as track_mc_batch (scvx_track_mc_nav_rng_f64_host): with "device" the lanes make all four draws.  vehicle and the
+    dense name "theta" as track_mc_batch (scvx_track_mc_nav_veh_f64_host): the truth is flown with the vehicle errors, the recursion
+    of the estimate's error is the analysis's, unchanged."""
     rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
-    mq = _McQ(quantiles, per_node, dense)
+    vh = _McVeh(vehicle, dense)
+    mq = _McQ(quantiles, per_node, vh.rest)
     dense = mq.rest
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
@@ -799,18 +885,22 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     S = int(samples) if rg is not None else xi0.shape[0]
     red, dn = _mc_nav_outputs(B, S, K, dense)
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None else (_p(xi0), opt(eta))
+    drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
     args = (cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), *drw, opt(wv), _p(deriv),
-            opt(kf if m else None), _p(cn), *(() if rg is not None else (_p(xin), opt(nud))), m, opt(Hm), opt(rv),
+            opt(kf if m else None), _p(cn), *(() if rg is not None and not vh.on else (opt(xin), opt(nud))), m, opt(Hm), opt(rv),
             int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red],
             *[opt(a) for a in dn])
-    if rg is not None:
+    if vh.on:
+        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_veh_f64_host(*args, *mq.args(B, K, S),
+                                                                         *vh.args(B, S, rg, wv is not None, seed, sample_lo)),
+                   "scvx_track_mc_nav_veh_f64_host")
+    elif rg is not None:
         _lib.check(cache.handle, cache._L.scvx_track_mc_nav_rng_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_rng_f64_host")
     elif mq.on:
         _lib.check(cache.handle, cache._L.scvx_track_mc_nav_q_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_q_f64_host")
     else:
         _lib.check(cache.handle, cache._L.scvx_track_mc_nav_f64_host(*args), "scvx_track_mc_nav_f64_host")
-    return McNavReport(*red, *dn)._with_q(mq)
+    return McNavReport(*red, *dn)._with_q(mq)._with_veh(vh)
 
 
 def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None):

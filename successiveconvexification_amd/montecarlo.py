@@ -202,6 +202,61 @@ def mc_nav_draws_device(samples, K, m, seed, lo=0, plans=None):
     return np.ascontiguousarray(z[..., 0, :]), (np.ascontiguousarray(z[..., 1:, :int(m)]) if m else None)
 
 
+def mc_vehicle_draws(samples, seed, lo=0):
+    """The draws of the vehicle errors made on the HOST (vehicle= with rng="host"): zeta [samples][6], standard normal.  Sample s draws
+    from Philox stream s of `seed` with 9 in the second counter word, beside mc_draws' 4 and mc_nav_draws' 5; a shard [lo, lo + samples)
+    gets exactly the rows the whole set would."""
+    zeta = np.empty((samples, 6))
+    for s in range(samples):
+        zeta[s] = np.random.Generator(np.random.Philox(key=seed, counter=[0, 9, 0, lo + s])).standard_normal(6)
+    return zeta
+
+
+MC_STREAM_VEH = 8   # the device's stream of the vehicle errors: the first six normals of its group 0
+
+
+def mc_vehicle_draws_device(samples, seed, lo=0, plans=None):
+    """mc_draws_device for the vehicle errors (dynamics.track_mc_batch(vehicle=, rng="device")): zeta [samples][6], or
+    [P][samples][6] for the absolute plan indices `plans`, the first six normals of group 0 of stream 8; theta = mu + sp * zeta."""
+    z = _device_groups(seed, MC_STREAM_VEH, samples, lo, plans, 0, 1)
+    return np.ascontiguousarray(z[..., 0, :6])
+
+
+VEHICLE_COMPONENTS = ("thrust", "mis_y", "mis_z", "isp", "aero", "fin")   # the SCVX_VEH_* order of include/scvx.h
+
+
+def vehicle_errors(thrust=0.0, misalign=0.0, isp=0.0, aero=0.0, fin=0.0, mean=None):
+    """(mu [6], sp [6]) of the per-flight vehicle errors theta = mu + sp * zeta (include/scvx.h "vehicle errors"), the vehicle= of the
+    sampled calls: the 1 sigma of the relative thrust error, of the misalignment of the thrust axis (radians; a scalar for both body
+    axes, or (about y, about z)), and of the relative errors of the specific impulse (alpha), of the aerodynamic scale (force_scalar)
+    and of the fin forces.  mean: None (zero), or [6] in the same order.  aero needs an aerodynamic model, fin a model with fins: the
+    library refuses a non-zero entry otherwise."""
+    my, mz = (misalign, misalign) if np.ndim(misalign) == 0 else misalign
+    sp = np.array([thrust, my, mz, isp, aero, fin], np.float64)
+    mu = np.zeros(6) if mean is None else np.array(mean, np.float64)
+    if mu.shape != (6,):
+        raise ValueError("mean: [6] in the order " + ", ".join(VEHICLE_COMPONENTS))
+    return mu, sp
+
+
+def vehicle_budget(J, sp, covK):
+    """Each component's share of the first-order landing variance Sigma_K + J diag(sp^2) J': J [14][6] = d x_K / d theta of the closed
+    loop (dynamics.vehicle_sensitivity_batch), sp [6], covK [14][14] the landing covariance without vehicle errors (the [:14, :14] block
+    of the analysis's).  Returns a dict: "cov" [14][14] the sum; "var" [7][14] the variance each of the six components and (row 6)
+    covK contribute to each landing state, so var.sum(0) = diag(cov); "share" [7] the shares of the trace; "sigma_r" [7] and "sigma_v"
+    [7] the root of each row's variance summed over position (states 1..3) and velocity (4..6).  First order: it ignores the O(theta^2)
+    growth of the thrust norm under misalignment and every interaction."""
+    J = np.asarray(J, np.float64)
+    sp = np.asarray(sp, np.float64)
+    cK = np.asarray(covK, np.float64)[:14, :14]
+    if J.shape != (14, 6) or sp.shape != (6,) or cK.shape != (14, 14):
+        raise ValueError("shape mismatch: J [14][6], sp [6], covK [14][14]")
+    var = np.concatenate([(J * sp[None, :]).T ** 2, np.diag(cK)[None, :]])
+    tot = var.sum()
+    return {"cov": cK + (J * sp[None, :] ** 2) @ J.T, "var": var, "share": var.sum(1) / tot if tot > 0.0 else np.zeros(7),
+            "sigma_r": np.sqrt(var[:, 1:4].sum(1)), "sigma_v": np.sqrt(var[:, 4:7].sum(1))}
+
+
 def quantile_ranks(p, S):
     """The 0-based ascending ranks of the probabilities `p` (a scalar or an iterable) in a sample of S values, as the order statistics of
     the library count them (scvx_order_stats_f64, include/scvx.h): min(S - 1, max(0, ceil(p S) - 1)), numpy's method="inverted_cdf"

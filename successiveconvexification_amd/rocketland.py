@@ -83,14 +83,15 @@ def track(iteration: ProblemIteration, cache: IntegratorCache = None, dx0=None, 
 
 def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, samples=256, seed=0, w=None, q=None, r=None, qf=None,
              nsub=None, clamp=False, tol=0.0, dense=(), nav=None, quantiles=None, per_node=False, rng="host", independent=False,
-             sample_lo=0, plan_lo=0):
+             sample_lo=0, plan_lo=0, vehicle=None):
     """Sampled closed-loop dispersion of an iterate's plan tracked under the time-varying LQR gains about it: `samples` flights from
     Gaussian starts of covariance S0 ([14][14], or a [14] vector of standard deviations), with the per-segment process noise w as an
     impulse at the nodes (dynamics.track_gains_batch on the plan's own linearisation, dynamics.track_mc_batch).  A dynamics.McReport of
     one row.  nav = (N0, H, rm), navigation()'s model: the flights are flown on a navigation estimate (dynamics.track_mc_nav_batch on
     the same linearisation), a dynamics.McNavReport of one row.  quantiles, per_node and the dense name "pathv" as
     dynamics.track_mc_batch: order statistics over the samples, reduced on the device.  rng="device", independent, sample_lo and
-    plan_lo as dynamics.track_mc_batch: the draws are made on the device."""
+    plan_lo as dynamics.track_mc_batch: the draws are made on the device.  vehicle = (mu, sp) (montecarlo.vehicle_errors) and the dense
+    name "theta" as dynamics.track_mc_batch: per-flight vehicle errors."""
     from .dynamics import linearize_batch, track_gains_batch, track_mc_batch
     if S0 is None:
         raise ValueError("track_mc: S0 (the handover covariance) is required")
@@ -105,9 +106,10 @@ def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None
         n0, _, Hm, rv = _nav_arg(nav, 1)
         return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
                                   tol=tol, dense=dense, quantiles=quantiles, per_node=per_node, rng=rng, independent=independent,
-                                  sample_lo=sample_lo, plan_lo=plan_lo)
+                                  sample_lo=sample_lo, plan_lo=plan_lo, vehicle=vehicle)
     return track_mc_batch(cache, x, u, sigma, gain, S0, samples, seed=seed, w=w, nsub=nsub, clamp=clamp, tol=tol, dense=dense,
-                          quantiles=quantiles, per_node=per_node, rng=rng, independent=independent, sample_lo=sample_lo, plan_lo=plan_lo)
+                          quantiles=quantiles, per_node=per_node, rng=rng, independent=independent, sample_lo=sample_lo, plan_lo=plan_lo,
+                          vehicle=vehicle)
 
 
 def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False):
