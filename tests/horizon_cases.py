@@ -17,7 +17,17 @@ HORIZONS = SHORT + (LONG,)
 MODELS = ("exo", "aero+fins")
 FLIGHT_ONLY_MODEL = "aero+fins+torque"
 FIN_SPAN = 1e-3            # the sample's finmxf is 0.01
+# the sampled closed-loop dispersion (test_mc_horizons_cpu.py, test_gpu_mc_horizons.py): K = 3 is pinned by the modules of the calls
+MC_HORIZONS = (1, 2, LONG)
+MC_SHORT = (1, 2)
+MC_S, MC_S_BLOCKS = 5, 130  # the CPU-chain parities; three blocks per plan, the last with two live lanes
+MC_SEED = 31                # of the impulse parities, whose count comparison test_mc_horizons_cpu.py vets
 _CASES = {}
+
+
+def mc_nsub(K):
+    """substeps per segment of the sampled-dispersion cases: the long horizon's reference chain stays within seconds"""
+    return 4 if K == LONG else 2
 
 
 def problems(model, K, tables):

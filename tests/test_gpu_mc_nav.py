@@ -101,14 +101,14 @@ def test_no_estimate_error_is_the_old_call_at_a_short_horizon(model, aero_tables
     c.close()
 
 
-def _bitwise_against_the_flyer_on_estimates(tag, c, x, u, s, d, L, S0, m, S, seed):
+def _bitwise_against_the_flyer_on_estimates(tag, c, x, u, s, d, L, S0, m, S, seed, nsub=10):
     from successiveconvexification_amd.dynamics import track_fly_batch, track_mc_nav_batch
     B, K = x.shape[0], x.shape[1] - 1
     H, rm = _model(m, x[0, 0])
     for clamp in (False, True):
-        r = track_mc_nav_batch(c, x, u, s, d, L, S0, 0.25 * S0, H, rm, S, seed=seed, nsub=10, clamp=clamp, dense=True)
+        r = track_mc_nav_batch(c, x, u, s, d, L, S0, 0.25 * S0, H, rm, S, seed=seed, nsub=nsub, clamp=clamp, dense=True)
         assert r.navfed.shape == (B, S, K, 14) and r.navK.shape == (B, S, 14) and r.navfed.any()
-        t = track_fly_batch(c, cr.rep(x, S), cr.rep(u, S), cr.rep(s, S), cr.rep(L, S), r.dx0.reshape(B * S, 14), nsub=10, clamp=clamp,
+        t = track_fly_batch(c, cr.rep(x, S), cr.rep(u, S), cr.rep(s, S), cr.rep(L, S), r.dx0.reshape(B * S, 14), nsub=nsub, clamp=clamp,
                             dense=True, nav=r.navfed.reshape(B * S, K, 14))
         fl, xl = r.flights.reshape(B * S, 16), r.xland.reshape(B * S, 14)
         print("%s m %d S %d clamp %s: flights bitwise %s (largest difference %.3e), xland bitwise %s, finite flights %d of %d, MAX_FED %s"
@@ -116,7 +116,7 @@ def _bitwise_against_the_flyer_on_estimates(tag, c, x, u, s, d, L, S0, m, S, see
                  np.isfinite(fl[:, 0]).sum(), B * S, r.MAX_FED))
         assert _same(fl, t.raw)
         assert _same(xl, t.xfly[:, K])
-        quiet = track_mc_nav_batch(c, x, u, s, d, L, S0, np.zeros((14, 14)), None, None, S, seed=seed, nsub=10, clamp=clamp, dense=True)
+        quiet = track_mc_nav_batch(c, x, u, s, d, L, S0, np.zeros((14, 14)), None, None, S, seed=seed, nsub=nsub, clamp=clamp, dense=True)
         assert not _same(quiet.xland, r.xland)                      # the estimate's error is felt
 
 
@@ -137,7 +137,7 @@ def test_bitwise_against_the_flyer_on_estimates_on_unconverged_torque_plans(aero
     c.close()
 
 
-def _recursion_against_the_reference(tag, c, x, u, s, d, L, S0, S, seed, nsub):
+def _recursion_against_the_reference(tag, c, x, u, s, d, L, S0, S, seed, nsub, ms=(0, 3, 6, 14)):
     """navfed and navK of the device against the longdouble recursion from the same draws, gains and tiles, over m and eta"""
     from successiveconvexification_amd.dynamics import nav_cov_batch, track_mc_nav_batch
     from successiveconvexification_amd.montecarlo import handover_factor, mc_draws, mc_nav_draws
@@ -145,7 +145,7 @@ def _recursion_against_the_reference(tag, c, x, u, s, d, L, S0, S, seed, nsub):
     N0 = 0.25 * S0
     w = np.full(14, 1e-8)
     w[0] = 0.0
-    for m in (0, 3, 6, 14):
+    for m in ms:
         H, rm = _model(m, x[0, 0])
         xin, nud = mc_nav_draws(S, K, m, seed)
         for noise in (False, True):
@@ -205,6 +205,7 @@ def _impulse_parity(tag, c, po, dyn, par, x, u, s, m, nsub, S, seed):
     kf = nav_cov_batch(c, x, u, d, L, np.zeros((B, 14, 14)), N0, H, rm, w, dense=("kf",)).kf
     dev = track_mc_nav_batch(c, x, u, s, d, L, S0, N0, H, rm, S, seed=seed, w=w, kf=kf, nsub=nsub, dense=True)
     imp = eta * np.sqrt(w)
+    taken = []                                                     # per plan: was the count comparison below made
     for b in range(B):
         dx0 = xi0 @ handover_factor(S0[b]).T
         fed, before = mn.eps_recursion(d[b], kf[b], H, rm, handover_factor(N0[b]), xin, nud, w, eta)
@@ -220,8 +221,10 @@ def _impulse_parity(tag, c, po, dyn, par, x, u, s, m, nsub, S, seed):
         margin = float(np.minimum(np.abs(cmd - po.Tmin), np.abs(cmd - po.Tmax)).min())
         print("    commanded norms outside the band: reference %d / %d, device %.1f / %.1f (closest to a bound %.3e)"
               % (lo, hi, dev.OUT_LO[b] * S * K, dev.OUT_HI[b] * S * K, margin))
-        if margin > bound * max(1.0, float(np.abs(L).max())):
+        taken.append(margin > bound * max(1.0, float(np.abs(L).max())))
+        if taken[-1]:
             assert dev.OUT_LO[b] == lo / (S * K) and dev.OUT_HI[b] == hi / (S * K)
+    return taken
 
 
 @pytest.mark.parametrize("model,m", [("exo", 3), ("aero+fins", 14)])

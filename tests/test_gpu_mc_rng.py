@@ -37,18 +37,40 @@ def _eq(a, b):
     return (a is None and b is None) or (a is not None and b is not None and _same(a, b))
 
 
-def _reference(s_lo):
-    """the longdouble reference and the float64 twin of the largest case (P = 3, S = 130, K = 50), both streams: every smaller case is a
+def _reference(s_lo, K=50):
+    """the longdouble reference and the float64 twin of the largest case (P = 3, S = 130, K nodes), both streams: every smaller case is a
     slice of it -- the layout is random access by definition"""
-    if s_lo not in _REF:
+    if (s_lo, K) not in _REF:
         from successiveconvexification_amd.montecarlo import mc_draws_device, mc_nav_draws_device
         out = {}
         for plans in (None, (0, 1, 2)):
-            ld = [rr.draws(SEED, st, 130, 50, s_lo, plans) for st in (rr.STREAM_TRUTH, rr.STREAM_NAV)]
-            tw = mc_draws_device(130, 50, SEED, noise=True, lo=s_lo, plans=plans) + mc_nav_draws_device(130, 50, 14, SEED, lo=s_lo, plans=plans)
+            ld = [rr.draws(SEED, st, 130, K, s_lo, plans) for st in (rr.STREAM_TRUTH, rr.STREAM_NAV)]
+            tw = mc_draws_device(130, K, SEED, noise=True, lo=s_lo, plans=plans) + mc_nav_draws_device(130, K, 14, SEED, lo=s_lo, plans=plans)
             out[1 if plans is None else 3] = ((ld[0][0], ld[0][1], ld[1][0], ld[1][1]), tuple(a[None] if plans is None else a for a in tw))
-        _REF[s_lo] = out
-    return _REF[s_lo]
+        _REF[(s_lo, K)] = out
+    return _REF[(s_lo, K)]
+
+
+def _dump_against_the_reference(c, ld, tw, s_lo, P, S, K):
+    """one dump of P plans, S samples and K nodes against the slices of the reference ld and the twin tw: (the dump, largest error /
+    (8 x the twin's own distance + 4 ulp))"""
+    from successiveconvexification_amd.dynamics import mc_draws_device_batch
+    d = mc_draws_device_batch(c, S, K=K, seed=SEED, sample_lo=s_lo, plans=None if P == 1 else P)
+    again = mc_draws_device_batch(c, S, K=K, seed=SEED, sample_lo=s_lo, plans=None if P == 1 else P)
+    worst = 0.0
+    for i, n in enumerate(("xi0", "eta", "xin", "nud")):
+        dev = d[n][None] if P == 1 else d[n]
+        sl = (slice(None), slice(0, S)) + ((slice(0, K),) if i % 2 else ())
+        r, t = ld[i][sl], tw[i][sl]
+        assert dev.shape == r.shape == t.shape, (n, dev.shape, r.shape, t.shape)
+        own = np.abs(t.astype(np.longdouble) - r)
+        ulp = np.spacing(np.abs(r).astype(np.float64)).astype(np.longdouble)
+        err = np.abs(dev.astype(np.longdouble) - r)
+        ratio = float((err / (8 * own + 4 * ulp)).max())
+        worst = max(worst, ratio)
+        assert np.isfinite(dev).all() and np.all(err <= 8 * own + 4 * ulp), (P, S, K, n, ratio, float((err / ulp).max()))
+        assert _same(d[n], again[n]), (P, S, K, n)                 # two launches: bit for bit
+    return d, worst
 
 
 @pytest.mark.parametrize("s_lo", [64, 2 ** 33])
@@ -62,20 +84,8 @@ def test_dumped_draws_against_the_longdouble_reference(s_lo):
         ld, tw = ref[P]
         for S in (1, 63, 64, 65, 130):
             for K in (1, 3, 50):
-                d = mc_draws_device_batch(c, S, K=K, seed=SEED, sample_lo=s_lo, plans=None if P == 1 else P)
-                again = mc_draws_device_batch(c, S, K=K, seed=SEED, sample_lo=s_lo, plans=None if P == 1 else P)
-                for i, n in enumerate(names):
-                    dev = d[n][None] if P == 1 else d[n]
-                    sl = (slice(None), slice(0, S)) + ((slice(0, K),) if i % 2 else ())
-                    r, t = ld[i][sl], tw[i][sl]
-                    assert dev.shape == r.shape == t.shape, (n, dev.shape, r.shape, t.shape)
-                    own = np.abs(t.astype(np.longdouble) - r)
-                    ulp = np.spacing(np.abs(r).astype(np.float64)).astype(np.longdouble)
-                    err = np.abs(dev.astype(np.longdouble) - r)
-                    ratio = float((err / (8 * own + 4 * ulp)).max())
-                    worst = max(worst, ratio)
-                    assert np.isfinite(dev).all() and np.all(err <= 8 * own + 4 * ulp), (P, S, K, n, ratio, float((err / ulp).max()))
-                    assert _same(d[n], again[n]), (P, S, K, n)                 # two launches: bit for bit
+                d, ratio = _dump_against_the_reference(c, ld, tw, s_lo, P, S, K)
+                worst = max(worst, ratio)
                 if S == 130 and K == 50:
                     eu = max(float((np.abs(d[n].reshape(ld[i].shape).astype(np.longdouble) - ld[i])
                                     / np.spacing(np.abs(ld[i]).astype(np.float64))).max()) for i, n in enumerate(names))

@@ -66,28 +66,32 @@ def _null_veh(monkeypatch, L):
 def test_null_veh_is_the_q_and_the_rng_call(model, m, aero_tables, monkeypatch):
     """veh = NULL through scvx_track_mc_veh_f64_host / scvx_track_mc_nav_veh_f64_host: every output bitwise the _q call's (uploaded
     draws) and the _rng call's (device draws); m None: truth-fed, else flown on an estimate with m measurement rows"""
-    from successiveconvexification_amd.dynamics import track_mc_batch
     c, po, dyn, par, x, u, s, d, L, S0 = _plans(model, aero_tables)
+    _null_veh_is_the_plain_call("%s m %s" % (model, m), monkeypatch, c, x, u, s, L, S0, m, (1, 3), (1, 65, 130), 10)
+    c.close()
+
+
+def _null_veh_is_the_plain_call(tag, monkeypatch, c, x, u, s, L, S0, m, Bs, Ss, nsub):
+    from successiveconvexification_amd.dynamics import track_mc_batch
     nav = None if m is None else (0.25 * S0, *_model(m, x[0, 0]))
     names = OLD if m is None else OLD_NAV
     dn = ("flights", "xland", "dx0", "pathv") + (() if m is None else ("navfed", "navK"))
     zero = (np.zeros(6), np.zeros(6))
     n = 0
-    for B in (1, 3):
-        for S in (1, 65, 130):
+    for B in Bs:
+        for S in Ss:
             for rng in ("host", "device"):
                 nb = None if nav is None else (nav[0][:B],) + nav[1:]
-                kw = dict(seed=11, w=W if S != 65 else None, nsub=10, clamp=S == 130, tol=1e-6, quantiles=PROBS, per_node=True, dense=dn,
+                kw = dict(seed=11, w=W if S != 65 else None, nsub=nsub, clamp=S == 130, tol=1e-6, quantiles=PROBS, per_node=True, dense=dn,
                           nav=nb, rng=rng)
                 old = track_mc_batch(c, x[:B], u[:B], s[:B], L[:B], S0[:B], S, **kw)
                 with monkeypatch.context() as mp:
                     _null_veh(mp, c._L)
                     new = track_mc_batch(c, x[:B], u[:B], s[:B], L[:B], S0[:B], S, vehicle=zero, **kw)
                 same = {nm: _eq(getattr(old, nm), getattr(new, nm)) for nm in names}
-                assert all(same.values()), (model, m, B, S, rng, same)
+                assert all(same.values()), (tag, B, S, rng, same)
                 n += 1
-    print("%s m %s: %d calls with veh = NULL through the new entry point bitwise the _q / _rng call" % (model, m, n))
-    c.close()
+    print("%s: %d calls with veh = NULL through the new entry point bitwise the _q / _rng call" % (tag, n))
 
 
 @pytest.mark.parametrize("model", ["exo", "aero+fins+torque"])
