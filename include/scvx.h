@@ -724,6 +724,62 @@ int scvx_track_mc_nav_veh_f64_host(scvx_ctx *ctx, int B, int K, int S, const dou
                                    double *flightq, double *pathq, double *pathv, const scvx_mc_rng *rng, int noise,
                                    const scvx_mc_vehicle *veh, const double *zeta, double *theta);
 
+/* ---- VEHICLE ERRORS in the first-order analyses (consider parameters) -----------------------------------------------------------------
+ * scvx_cov_propagate_f64, scvx_cov_path_sigma_f64, scvx_nav_cov_f64 and scvx_nav_path_sigma_f64 analyse the nominal vehicle.  The forms
+ * below add the six vehicle errors of the sampled calls above, theta = sp (.) zeta, zeta ~ N(0, I_6), constant over the flight and
+ * independent of the handover, of the process noise and of the navigation error.  With J_k = d z_k / d theta (n x 6, n = 14 + NU):
+ *     J_0 = 0,   J_{k+1} = M_k J_k + [Gamma_k; 0],   M_k = F_k + G_k L_k (the M of scvx_cov_propagate_f64),
+ *     Sigma_k^tot = Sigma_k + J_k diag(sp^2) J_k'
+ * and every output of the call extended (report, psig, sig, covK, cov) is read off Sigma_k^tot; the recursion of Sigma_k itself is that
+ * of the plain call.  In the navigation form the same J_k diag(sp^2) J_k' is added to the truth block Xi_k[z, z] of the joint
+ * wherever report, psig, sig and joint read it; the z-eps and eps-eps blocks, NAV_*, navsig and kf are those of the plain call (the
+ * recursion of eps does not see theta).  SCVX_NAV_EST_R / EST_V, the trace of Cov(xhat_K - xbar_K) = Xi[x,x] - C - C' + P, receive
+ * J P J' in their Xi[x,x] term alone: xhat = x - eps moves with the truth, and eps is independent of theta.
+ * Gamma_k = d x_{k+1} / d theta (14 x 6) about the plan at theta = 0 and the context's nsub.  Four columns are in the derivative tiles
+ * (the applied control is linear in the first-order hold and RK4 is linear in the forcing; d x u as above):
+ *     Gamma[:, THRUST] = B-_k ubar_k[0:3] + B+_k ubar_{k+1}[0:3]
+ *     Gamma[:, MIS_Y]  = B-_k (e_y x ubar_k[0:3]) + B+_k (e_y x ubar_{k+1}[0:3])          (MIS_Z with e_z)
+ *     Gamma[:, FIN]    = B-_k[:, 3:5] ubar_k[3:5] + B+_k[:, 3:5] ubar_{k+1}[3:5]           (fin models)
+ * and two are not: scvx_vehicle_tiles_f64 integrates them, vtile [B][K][SCVX_VTILE_N][14], */
+#define SCVX_VTILE_N 2
+#define SCVX_VTILE_ISP 0  /* d x_{k+1} / d theta_ISP:  c' = sigma (A c + e_0 (-alpha |uu|)),  c(0) = 0                                     */
+#define SCVX_VTILE_AERO 1 /* d x_{k+1} / d theta_AERO: forcing F_aero / m in the v rows, + Jinv tau_aero in the w rows with                 */
+                          /* SCVX_MODEL_AERO_TORQUE (what scales with force_scalar; not the fin force); all zeros without aerodynamics     */
+/* beside the state from the planned node x_k under the planned hold, with the integrator, nsub and dt = 1 / (K + 1) of
+ * scvx_propagate_f64: the derivative of the discrete flow the derivative tiles differentiate.  Refusals as scvx_propagate_f64.
+ * The _vehicle forms take the argument list of scvx_cov_path_sigma_f64 (of scvx_nav_path_sigma_f64 followed by the dense outputs
+ * sig, navsig, kf, joint of scvx_nav_cov_f64) with psig OPTIONAL, followed by
+ *     double *sig, double *covK, double *cov (covariance form only: the dense outputs of scvx_cov_propagate_f64, optional),
+ *     const double *vtile, const double *sp6 (HOST, the six standard deviations), double *sens [B][K+1][n][6] or NULL (J_k, unscaled)
+ * vtile may be NULL only when sp[ISP] = sp[AERO] = 0.  SCVX_ERR_ARG for everything the call extended refuses, for a NULL sp6, a negative
+ * or non-finite sp, sp[AERO] != 0 on a model without aerodynamics, sp[FIN] != 0 on a model without fins.  With sp = 0 every output is
+ * that of the call extended.
+ * There is NO mu: the analysis is about the nominal vehicle, theta = 0 in the mean.
+ * Limits: first order about the plan; errors constant over the flight; the filter does not know theta (kf is the analysis's optimal
+ * gain for the stated model, which has no theta); the [u, u] block, hence S_THRUST, N_TMIN, N_TMAX and the THRUST column of psig, is
+ * the dispersion of the COMMAND, as in the sampled forms (the bottom NU rows of the forcing are zero: the command sees theta only
+ * through the feedback).  Out of scope: a mean shift for mu != 0, time-varying errors, wind, centre-of-gravity and inertia errors, an
+ * estimator that solves for theta. */
+int scvx_vehicle_tiles_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *sigma_dev,
+                           double *vtile_dev);
+int scvx_vehicle_tiles_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *sigma, double *vtile);
+int scvx_cov_vehicle_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                         const double *gain_dev, const double *S0_dev, const double *w14, double *report_dev, double *psig_dev,
+                         double *sig_dev, double *covK_dev, double *cov_dev, const double *vtile_dev, const double *sp6,
+                         double *sens_dev);
+int scvx_cov_vehicle_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv, const double *gain,
+                              const double *S0, const double *w14, double *report, double *psig, double *sig, double *covK,
+                              double *cov, const double *vtile, const double *sp6, double *sens);
+int scvx_nav_cov_vehicle_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                             const double *gain_dev, const double *S0_dev, const double *N0_dev, int m, const double *H,
+                             const double *rm, const double *w14, double *report_dev, double *navrep_dev, double *psig_dev,
+                             double *sig_dev, double *navsig_dev, double *kf_dev, double *joint_dev, const double *vtile_dev,
+                             const double *sp6, double *sens_dev);
+int scvx_nav_cov_vehicle_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv,
+                                  const double *gain, const double *S0, const double *N0, int m, const double *H, const double *rm,
+                                  const double *w14, double *report, double *navrep, double *psig, double *sig, double *navsig,
+                                  double *kf, double *joint, const double *vtile, const double *sp6, double *sens);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -1024,6 +1080,22 @@ int scvx_batch_margins_from_cov(scvx_batch *b, const double *q14, const double *
 int scvx_batch_margins_from_nav(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
                                 const double *N0, int m, const double *H, const double *rm, const double *w14, double nsigma,
                                 double cap, unsigned which, double *psig);
+
+/* The batch-level analyses with VEHICLE ERRORS as consider parameters ("VEHICLE ERRORS in the first-order analyses" above): each takes
+ * the argument list of the call it extends followed by const double *sp6 (host, the six standard deviations; there is no mu).  Each
+ * runs scvx_vehicle_tiles_f64 on the batch's current accepted iterate in front of the analysis, on the same stream: nothing returns
+ * to the host between that launch and the analysis or the back-off kernel.  SCVX_ERR_ARG as the call extended and as
+ * scvx_cov_vehicle_f64 for sp6. */
+int scvx_batch_cov_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0, const double *w14,
+                       double *report, double *sig, double *covK, double *cov, const double *sp6);
+int scvx_batch_nav_cov_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
+                           const double *N0, int m, const double *H, const double *rm, const double *w14, double *report,
+                           double *navrep, double *sig, double *navsig, double *kf, double *joint, const double *sp6);
+int scvx_batch_margins_from_cov_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
+                                    const double *w14, double nsigma, double cap, unsigned which, double *psig, const double *sp6);
+int scvx_batch_margins_from_nav_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
+                                    const double *N0, int m, const double *H, const double *rm, const double *w14, double nsigma,
+                                    double cap, unsigned which, double *psig, const double *sp6);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

@@ -1265,6 +1265,159 @@ end
 reference_iteration(it::Iteration, cache::IntegratorCache) =
     ProblemIteration(it.problem, cache, it.sigma, it.about, it.dynam, placeholder_model(it.model), it.iter, it.rk, it.cost)
 
+# ---- vehicle errors in the first-order analyses (new) ------------------------------------------------------------------------------
+# include/scvx.h, "VEHICLE ERRORS in the first-order analyses": the six errors of the sampled calls as consider parameters, sp their
+# standard deviations (there is no mu).  vtile 14 x 2 x K x B: d x_{k+1} / d theta_ISP and / d theta_AERO of every segment.
+const VTILE_N = 2
+const VEH_N = 6     # SCVX_VEH_N
+_veh_sp(sp) = (length(sp) == VEH_N || error("sp must have $(VEH_N) components"); Vector{Float64}(sp))
+
+function vehicle_tiles(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64})
+    K = size(x, 2) - 1; B = size(x, 3)
+    vt = Array{Float64,4}(undef, 14, VTILE_N, K, B)
+    check(cache.ctx, ccall((:scvx_vehicle_tiles_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, sigma, vt), "scvx_vehicle_tiles_f64_host")
+    return vt
+end
+
+vehicle_tiles_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble}, vtile_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_vehicle_tiles_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, sigma_dev, vtile_dev), "scvx_vehicle_tiles_f64")
+
+# any plans (host arrays, as covariance(cache, ...)) with vehicle errors: (report, psig, sig, covK, cov, sens); sens 6 x n x (K+1) x B
+function covariance_vehicle(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                            S0::Array{Float64,3}, sp; vtile=nothing, w=nothing, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); n = 14 + size(u, 1)
+    size(S0) == (14, 14, B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    ps = Array{Float64,3}(undef, PSIG_N, K + 1, B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, B) : nothing
+    covK = dense ? Array{Float64,3}(undef, n, n, B) : nothing
+    cov = dense ? Array{Float64,4}(undef, n, n, K + 1, B) : nothing
+    sens = dense ? Array{Float64,4}(undef, VEH_N, n, K + 1, B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    spv = _veh_sp(sp)
+    GC.@preserve wv spv check(cache.ctx, ccall((:scvx_cov_vehicle_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, _cov_opt(wv), report, ps, _cov_opt(sig), _cov_opt(covK), _cov_opt(cov), _cov_opt(vtile),
+        spv, _cov_opt(sens)), "scvx_cov_vehicle_f64_host")
+    return report, ps, sig, covK, cov, sens
+end
+
+covariance_vehicle_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble},
+                        gain_dev::Ptr{Cdouble}, S0_dev::Ptr{Cdouble}, w::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble},
+                        psig_dev::Ptr{Cdouble}, sig_dev::Ptr{Cdouble}, covK_dev::Ptr{Cdouble}, cov_dev::Ptr{Cdouble},
+                        vtile_dev::Ptr{Cdouble}, sp::Vector{Float64}, sens_dev::Ptr{Cdouble}) =
+    GC.@preserve w sp check(cache.ctx, ccall((:scvx_cov_vehicle_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), report_dev, psig_dev, sig_dev, covK_dev, cov_dev,
+        vtile_dev, sp, sens_dev), "scvx_cov_vehicle_f64")
+
+# the same flown on an estimate: (report, navrep, psig, sig, navsig, kf, joint, sens)
+function navigation_vehicle(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                            S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm, sp; vtile=nothing, w=nothing, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); n = 14 + size(u, 1); N = n + 14
+    (size(S0) == (14, 14, B) && size(N0) == (14, 14, B)) || error("S0 and N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    navrep = Matrix{Float64}(undef, NAV_NREP, B)
+    ps = Array{Float64,3}(undef, PSIG_N, K + 1, B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, B) : nothing
+    navsig = dense ? Array{Float64,3}(undef, 14, K + 1, B) : nothing
+    kf = dense && m > 0 ? Array{Float64,4}(undef, m, 14, K, B) : nothing
+    joint = dense ? Array{Float64,4}(undef, N, N, K + 1, B) : nothing
+    sens = dense ? Array{Float64,4}(undef, VEH_N, n, K + 1, B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    spv = _veh_sp(sp)
+    GC.@preserve wv Hm rmv spv check(cache.ctx, ccall((:scvx_nav_cov_vehicle_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), report, navrep, ps, _cov_opt(sig),
+        _cov_opt(navsig), _cov_opt(kf), _cov_opt(joint), _cov_opt(vtile), spv, _cov_opt(sens)), "scvx_nav_cov_vehicle_f64_host")
+    return report, navrep, ps, sig, navsig, kf, joint, sens
+end
+
+navigation_vehicle_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble},
+                        gain_dev::Ptr{Cdouble}, S0_dev::Ptr{Cdouble}, N0_dev::Ptr{Cdouble}, m::Int, H, rm,
+                        w::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble}, navrep_dev::Ptr{Cdouble}, psig_dev::Ptr{Cdouble},
+                        sig_dev::Ptr{Cdouble}, navsig_dev::Ptr{Cdouble}, kf_dev::Ptr{Cdouble}, joint_dev::Ptr{Cdouble},
+                        vtile_dev::Ptr{Cdouble}, sp::Vector{Float64}, sens_dev::Ptr{Cdouble}) =
+    GC.@preserve w H rm sp check(cache.ctx, ccall((:scvx_nav_cov_vehicle_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, _cov_opt(H), _cov_opt(rm), _cov_opt(w), report_dev,
+        navrep_dev, psig_dev, sig_dev, navsig_dev, kf_dev, joint_dev, vtile_dev, sp, sens_dev), "scvx_nav_cov_vehicle_f64")
+
+# the batch-level forms on the current accepted iterate: the vehicle tiles of the iterate, then the analysis
+function covariance_vehicle(b::Batch, S0::Array{Float64,3}, sp; w=nothing, q=1.0, r=1.0, qf=100.0, dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx)); n = 14 + NU
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, b.B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, b.B) : nothing
+    covK = dense ? Array{Float64,3}(undef, n, n, b.B) : nothing
+    cov = dense ? Array{Float64,4}(undef, n, n, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    spv = _veh_sp(sp)
+    GC.@preserve wv spv check(b.cache.ctx, ccall((:scvx_batch_cov_veh, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, _cov_opt(wv), report, _cov_opt(sig), _cov_opt(covK), _cov_opt(cov), spv),
+        "scvx_batch_cov_veh")
+    return report, sig, covK, cov
+end
+
+function navigation_vehicle(b::Batch, S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm, sp; w=nothing, q=1.0, r=1.0, qf=100.0,
+                            dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx)); n = 14 + NU; N = n + 14
+    (size(S0) == (14, 14, b.B) && size(N0) == (14, 14, b.B)) || error("S0 and N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    report = Matrix{Float64}(undef, COV_NREP, b.B)
+    navrep = Matrix{Float64}(undef, NAV_NREP, b.B)
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, b.B) : nothing
+    navsig = dense ? Array{Float64,3}(undef, 14, K + 1, b.B) : nothing
+    kf = dense && m > 0 ? Array{Float64,4}(undef, m, 14, K, b.B) : nothing
+    joint = dense ? Array{Float64,4}(undef, N, N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    spv = _veh_sp(sp)
+    GC.@preserve wv Hm rmv spv check(b.cache.ctx, ccall((:scvx_batch_nav_cov_veh, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), report, navrep,
+        _cov_opt(sig), _cov_opt(navsig), _cov_opt(kf), _cov_opt(joint), spv), "scvx_batch_nav_cov_veh")
+    return report, navrep, sig, navsig, kf, joint
+end
+
+function margins_from_cov_vehicle!(b::Batch, S0::Array{Float64,3}, sp; which::Integer=MARGIN_ALL, nsigma::Real=3.0, cap::Real=0.25,
+                                   w=nothing, q=1.0, r=1.0, qf=100.0, psig::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    ps = psig ? Array{Float64,3}(undef, PSIG_N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    spv = _veh_sp(sp)
+    GC.@preserve wv spv check(b.cache.ctx, ccall((:scvx_batch_margins_from_cov_veh, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cuint, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, _cov_opt(wv), Float64(nsigma), Float64(cap), UInt32(which),
+        _cov_opt(ps), spv), "scvx_batch_margins_from_cov_veh")
+    return ps
+end
+
+function margins_from_nav_vehicle!(b::Batch, S0::Array{Float64,3}, N0::Array{Float64,3}, H, rm, sp; which::Integer=MARGIN_ALL,
+                                   nsigma::Real=3.0, cap::Real=0.25, w=nothing, q=1.0, r=1.0, qf=100.0, psig::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx))
+    (size(S0) == (14, 14, b.B) && size(N0) == (14, 14, b.B)) || error("S0 and N0 must be 14 x 14 x B")
+    m, Hm, rmv = _nav_model(H, rm)
+    ps = psig ? Array{Float64,3}(undef, PSIG_N, K + 1, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    spv = _veh_sp(sp)
+    GC.@preserve wv Hm rmv spv check(b.cache.ctx, ccall((:scvx_batch_margins_from_nav_veh, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cuint, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, N0, m, _cov_opt(Hm), _cov_opt(rmv), _cov_opt(wv), Float64(nsigma),
+        Float64(cap), UInt32(which), _cov_opt(ps), spv), "scvx_batch_margins_from_nav_veh")
+    return ps
+end
+
 function install!()
     @eval HOST.Dynamics begin
         function make_dynamics_module(info::ProbInfo)

@@ -60,6 +60,9 @@ class ScvxMcVehicle(C.Structure):
 VEH_N = 6
 VEH_COLUMNS = ("THRUST", "MIS_Y", "MIS_Z", "ISP", "AERO", "FIN")
 VEH_INDEX = {n: i for i, n in enumerate(VEH_COLUMNS)}
+# scvx_vehicle_tiles_*: the rows of vtile [B][K][VTILE_N][14] (the SCVX_VTILE_* macros of include/scvx.h)
+VTILE_N = 2
+VTILE_COLUMNS = ("ISP", "AERO")
 
 ABI_VERSION = 4   # SCVX_ABI_VERSION of the include/scvx.h these structs and signatures were written against
 
@@ -200,6 +203,19 @@ SIGNATURES = {
     "scvx_batch_track_mc_nav_veh": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
                                               C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                               C.c_int, _ip, _dp, _dp, _dp, _rp, C.c_int, _hp, _dp, _dp]),
+    "scvx_vehicle_tiles_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "scvx_vehicle_tiles_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "scvx_cov_vehicle_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _vp]),
+    "scvx_cov_vehicle_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_nav_cov_vehicle_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _dp, _dp, _dp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _dp, _vp]),
+    "scvx_nav_cov_vehicle_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_batch_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_batch_nav_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_batch_margins_from_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint, _dp, _dp]),
+    "scvx_batch_margins_from_nav_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint,
+                                                  _dp, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),

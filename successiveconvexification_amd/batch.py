@@ -315,9 +315,16 @@ class ScvxBatch:
             self._chk(self._L.scvx_batch_track_mc(*args), "scvx_batch_track_mc")
         return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)._with_veh(vh)
 
-    def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False):
+    def _vehicle_sp(self, vehicle):
+        """sp [6] of vehicle = (mu, sp) for the first-order analyses (dynamics._cov_vehicle's refusals; the tiles are the batch's own)"""
+        from .dynamics import _cov_vehicle
+        return _cov_vehicle(self.cache, vehicle, np.zeros((self.B, self.K, _lib.VTILE_N, 14)), (), self.B, self.K)[0]
+
+    def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False, vehicle=None):
         """Closed-loop covariance analysis of the batch's current accepted iterate under its LQR gains (scvx_batch_cov; S0, w and
-        dense as dynamics.cov_propagate_batch, weights as track_gains): a dynamics.CovReport.  The batch is left untouched."""
+        dense as dynamics.cov_propagate_batch, weights as track_gains): a dynamics.CovReport.  The batch is left untouched.
+        vehicle = (mu, sp) of montecarlo.vehicle_errors, mu = 0: the report and the dense outputs of Sigma_k + J_k diag(sp^2) J_k', the
+        vehicle errors as consider parameters (scvx_batch_cov_veh: the vehicle tiles of the iterate, then the analysis)."""
         from .dynamics import CovReport, _cov_dense, _cov_noise, _cov_s0, _track_weights
         nu = self.cache.nu
         n = 14 + nu
@@ -330,6 +337,11 @@ class ScvxBatch:
         covK = np.empty((self.B, n, n)) if "covK" in want else None
         cov = np.empty((self.B, self.K + 1, n, n)) if "cov" in want else None
         opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        if vehicle is not None:
+            sp = self._vehicle_sp(vehicle)
+            self._chk(self._L.scvx_batch_cov_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), opt(wv), _p(rep), opt(sig), opt(covK),
+                                                 opt(cov), _p(sp)), "scvx_batch_cov_veh")
+            return CovReport(rep, sig, covK, cov)
         self._chk(self._L.scvx_batch_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), opt(wv), _p(rep), opt(sig), opt(covK), opt(cov)),
                   "scvx_batch_cov")
         return CovReport(rep, sig, covK, cov)
@@ -393,12 +405,19 @@ class ScvxBatch:
             mask |= _lib.MARGIN_BITS[n]
         return mask
 
-    def _margins_from_cov(self, S0, w, q, r, qf, nsigma, cap, want_psig, mask=None):
+    def _margins_from_cov(self, S0, w, q, r, qf, nsigma, cap, want_psig, mask=None, vehicle=None):
         from .dynamics import _cov_noise, _cov_s0, _track_weights
         qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
         s0 = _cov_s0(S0, self.B)
         wv = _cov_noise(w)
         psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
+        if vehicle is not None:
+            sp = self._vehicle_sp(vehicle)
+            self._chk(self._L.scvx_batch_margins_from_cov_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0),
+                                                              _p(wv) if wv is not None else None, float(nsigma), float(cap),
+                                                              int(mask if mask is not None else _lib.MARGIN_BITS["thrust"]),
+                                                              _p(psig) if want_psig else None, _p(sp)), "scvx_batch_margins_from_cov_veh")
+            return psig
         if mask is not None:
             self._chk(self._L.scvx_batch_margins_from_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(wv) if wv is not None else None,
                                                           float(nsigma), float(cap), int(mask), _p(psig) if want_psig else None),
@@ -409,12 +428,13 @@ class ScvxBatch:
                   "scvx_batch_thrust_margins_from_cov")
         return psig
 
-    def margins_from_cov(self, S0, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None):
+    def margins_from_cov(self, S0, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None, vehicle=None):
         """The back-offs min(nsigma s(k), cap width_k) of `constraints` from the covariance analysis of the current accepted iterate
-        (scvx_batch_margins_from_cov; the others stay as they are): returns psig [B][K+1][5]."""
-        return self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
+        (scvx_batch_margins_from_cov; the others stay as they are): returns psig [B][K+1][5].  vehicle = (mu, sp), mu = 0: the s(k) of
+        Sigma_k + J_k diag(sp^2) J_k' (scvx_batch_margins_from_cov_veh)."""
+        return self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints), vehicle)
 
-    def _margins_from_nav(self, S0, nav, w, q, r, qf, nsigma, cap, want_psig, mask):
+    def _margins_from_nav(self, S0, nav, w, q, r, qf, nsigma, cap, want_psig, mask, vehicle=None):
         from .dynamics import _cov_noise, _cov_s0, _nav_arg, _track_weights
         n0, m, Hm, rmv = _nav_arg(nav, self.B)
         qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
@@ -422,15 +442,22 @@ class ScvxBatch:
         wv = _cov_noise(w)
         psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
         opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        if vehicle is not None:
+            sp = self._vehicle_sp(vehicle)
+            self._chk(self._L.scvx_batch_margins_from_nav_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv),
+                                                              opt(wv), float(nsigma), float(cap), int(mask), opt(psig), _p(sp)),
+                      "scvx_batch_margins_from_nav_veh")
+            return psig
         self._chk(self._L.scvx_batch_margins_from_nav(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv),
                                                       float(nsigma), float(cap), int(mask), opt(psig)), "scvx_batch_margins_from_nav")
         return psig
 
-    def margins_from_nav(self, S0, N0, H, rm, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None):
+    def margins_from_nav(self, S0, N0, H, rm, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None, vehicle=None):
         """margins_from_cov with the per-node s(k) of the NAVIGATION analysis of the current accepted iterate, the closed loop flown on
         an estimate (scvx_batch_margins_from_nav; N0, H, rm as navigation()): the same widths, caps and forced zeros, the constraints
-        that are not selected stay as they are.  Returns psig [B][K+1][5], read off the truth block of the joint covariance."""
-        return self._margins_from_nav(S0, (N0, H, rm), w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints))
+        that are not selected stay as they are.  Returns psig [B][K+1][5], read off the truth block of the joint covariance.
+        vehicle = (mu, sp), mu = 0: with J_k diag(sp^2) J_k' on the truth block (scvx_batch_margins_from_nav_veh)."""
+        return self._margins_from_nav(S0, (N0, H, rm), w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints), vehicle)
 
     def margins_from_mc(self, S0, p=0.99865, samples=1024, constraints="all", cap=0.25, seed=0, w=None, clamp=False, nav=None, q=None,
                         r=None, qf=None, nsub=None, tol=0.0, draws=None, rng="host", independent=False, sample_lo=0, plan_lo=0,
@@ -461,18 +488,20 @@ class ScvxBatch:
             self._chk(self._L.scvx_batch_set_path_margins(self.handle, _p(np.ascontiguousarray(pm))), "scvx_batch_set_path_margins")
         return rep, lo, hi, pm
 
-    def path_sigma(self, S0, w=None, q=None, r=None, qf=None, nav=None):
+    def path_sigma(self, S0, w=None, q=None, r=None, qf=None, nav=None, vehicle=None):
         """psig [B][K+1][5]: per node, one standard deviation of the mass, glide-slope, tilt, rate and thrust-norm path functions
         of the batch's current accepted iterate under its LQR gains (dynamics.cov_path_sigma_batch on the batch's own tiles).  The
         batch's iterate, scalars and flags are left untouched and so are its thrust back-offs.  nav = (N0, H, rm): the same of the
-        navigation analysis, the law fed an estimate (dynamics.nav_path_sigma_batch)."""
-        from .dynamics import _nav_arg, cov_path_sigma_batch, nav_path_sigma_batch
+        navigation analysis, the law fed an estimate (dynamics.nav_path_sigma_batch).  vehicle = (mu, sp), mu = 0: the s(k) with the
+        vehicle errors as consider parameters, the vehicle tiles from dynamics.vehicle_tiles_batch on the iterate."""
+        from .dynamics import _nav_arg, cov_path_sigma_batch, nav_path_sigma_batch, vehicle_tiles_batch
         if nav is not None:
-            n0, _, Hm, rmv = _nav_arg(nav, self.B)
-            x, u, _ = self.trajectory()
-            return nav_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, n0, Hm, rmv, w)[1]
-        x, u, _ = self.trajectory()
-        return cov_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, w)[1]
+            n0, _, Hm, rmv = _nav_arg(nav, self.B)   # a malformed model is refused before anything is read back
+        x, u, sg = self.trajectory()
+        kw = {} if vehicle is None else dict(vehicle=vehicle, vtile=vehicle_tiles_batch(self.cache, x, u, sg))
+        if nav is not None:
+            return nav_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, n0, Hm, rmv, w, **kw)[1]
+        return cov_path_sigma_batch(self.cache, x, u, self.linearization()[1], self.track_gains(q, r, qf), S0, w, **kw)[1]
 
     def replan(self):
         """Start the SCvx loop again from the current iterate (scvx_batch_replan: rk = 100, cost = Inf, iter = 0, RUNNING, live for
@@ -480,7 +509,8 @@ class ScvxBatch:
         self._chk(self._L.scvx_batch_replan(self.handle), "scvx_batch_replan")
         return self
 
-    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",), nav=None, mc=None):
+    def robustify(self, S0, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None, r=None, qf=None, constraints=("thrust",), nav=None, mc=None,
+                  vehicle=None):
         """Covariance-driven replanning.  Per round: the back-offs lo_k = hi_k = min(nsigma s_T(k), cap (Tmax - Tmin)) from the
         covariance analysis of the current iterate (scvx_batch_thrust_margins_from_cov, nothing returns to the host), replan(),
         solve().  Returns the last solve()'s (status, iters, nu_norm, dJ) plus (lo, hi).  First order, and only as good as Sigma_k;
@@ -495,9 +525,17 @@ class ScvxBatch:
         one for the stated model.
         mc = dict(p=..., samples=..., seed=..., clamp=..., rng=..., independent=..., sample_lo=..., plan_lo=..., vehicle=...): the back-offs of each round come from the SAMPLED closed loop instead
         (margins_from_mc: per-node order statistics Q_{1-p}, Q_p of `samples` flights, nonlinear and clamp-aware; nsigma is then not
-        used).  mc and nav combine: the flights are flown on the estimate.  Limits as margins_from_mc; mc=None is the call it was."""
+        used).  mc and nav combine: the flights are flown on the estimate.  Limits as margins_from_mc; mc=None is the call it was.
+        vehicle = (mu, sp) of montecarlo.vehicle_errors, mu = 0: the s(k) of the covariance or (with nav) the navigation path carry the
+        vehicle errors as consider parameters (scvx_batch_margins_from_cov_veh / _nav_veh per round; first order, the thrust row is the
+        command's).  The sampled path has its own: mc=dict(vehicle=...); giving both is refused."""
         if int(rounds) < 1:
             raise ValueError("robustify: rounds >= 1")
+        if vehicle is not None:
+            if mc is not None:
+                raise ValueError("robustify: vehicle= belongs to the covariance and navigation paths; the sampled path takes "
+                                 "mc=dict(vehicle=...)")
+            self._vehicle_sp(vehicle)   # refused before the first round
         mask = self._margin_mask(constraints)
         thrust_only = mask == _lib.MARGIN_BITS["thrust"]
         out = None
@@ -517,20 +555,21 @@ class ScvxBatch:
             from .dynamics import _nav_arg
             _nav_arg(nav, self.B)   # a malformed model is refused before the first round
             for _ in range(int(rounds)):
-                self._margins_from_nav(S0, nav, w, q, r, qf, nsigma, cap, False, mask)
+                self._margins_from_nav(S0, nav, w, q, r, qf, nsigma, cap, False, mask, vehicle)
                 self.replan()
                 out = self.solve()
             return out + self.thrust_margins()
         for _ in range(int(rounds)):
-            self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, False, None if thrust_only else mask)
+            self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, False, None if thrust_only else mask, vehicle)
             self.replan()
             out = self.solve()
         return out + self.thrust_margins()
 
-    def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False):
+    def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False, vehicle=None):
         """Navigation-error covariance analysis of the batch's current accepted iterate flown on an estimate under its LQR gains
         (scvx_batch_nav_cov; S0, N0, H, rm, w and dense as dynamics.nav_cov_batch, weights as track_gains): a dynamics.NavReport.
-        The batch is left untouched."""
+        The batch is left untouched.  vehicle = (mu, sp), mu = 0: J_k diag(sp^2) J_k' on the truth block (scvx_batch_nav_cov_veh); the
+        filter does not know theta, so navsig, kf and NAV_* are those of the call without it."""
         from .dynamics import NavReport, _cov_noise, _cov_s0, _nav_dense, _nav_model, _track_weights
         nu = self.cache.nu
         n = 14 + nu
@@ -545,6 +584,12 @@ class ScvxBatch:
         kf = np.empty((self.B, self.K, 14, m)) if "kf" in want else None
         joint = np.empty((self.B, self.K + 1, n + 14, n + 14)) if "joint" in want else None
         opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        if vehicle is not None:
+            sp = self._vehicle_sp(vehicle)
+            self._chk(self._L.scvx_batch_nav_cov_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv),
+                                                     _p(rep), _p(navrep), opt(sig), opt(navsig), opt(kf), opt(joint), _p(sp)),
+                      "scvx_batch_nav_cov_veh")
+            return NavReport(rep, navrep, sig, navsig, kf, joint)
         self._chk(self._L.scvx_batch_nav_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv), _p(rep),
                                              _p(navrep), opt(sig), opt(navsig), opt(kf), opt(joint)), "scvx_batch_nav_cov")
         return NavReport(rep, navrep, sig, navsig, kf, joint)

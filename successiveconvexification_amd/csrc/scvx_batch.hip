@@ -289,6 +289,7 @@ struct scvx_batch {
     bool pmarg_on = false;    // scvx_batch_set_path_margins / scvx_batch_margins_from_cov set it, NULL and scvx_batch_init clear it
     double *cov_s0 = nullptr, *cov_rep = nullptr, *cov_psig = nullptr;   // scratch of scvx_batch_thrust_margins_from_cov: allocated on first use
     double *nav_n0 = nullptr, *nav_rep = nullptr;   // scratch of scvx_batch_margins_from_nav on top of the three above: allocated on first use
+    double* vtile = nullptr;   // the vehicle tiles of the _veh analyses [B][K][SCVX_VTILE_N][14]: allocated on first use
     double *track_gain = nullptr, *track_p0 = nullptr;   // scratch of scvx_batch_track_*: allocated on first use, freed with the batch
     int *k1skip = nullptr;   // per trajectory: >= SCVX_ST_REJECTED = the reference point did not change in the last step (K1 skips it)
     int *d_nlive = nullptr;  // device-side count of live trajectories (scvx_solve), mirrored asynchronously into pinned h_nlive[2]
@@ -668,7 +669,7 @@ void scvx_batch_destroy(scvx_batch* b) {
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
                     b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip,
-                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig, b->nav_n0, b->nav_rep};
+                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig, b->nav_n0, b->nav_rep, b->vtile};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -943,6 +944,36 @@ int scvx_batch_track_fly(scvx_batch* b, const double* q14, const double* rNU, co
     return s.finish("scvx_batch_track_fly");
 }
 
+// the vehicle tiles of the batch's current accepted iterate into b->vtile, enqueued on st (the _veh analyses)
+static int enqueue_vehicle_tiles(scvx_batch* b, hipStream_t st) {
+    scvx_ctx* ctx = b->ctx;
+    if (!b->vtile) SCVX_HIP(ctx, hipMalloc((void**)&b->vtile, (size_t)b->B * b->K * SCVX_VTILE_N * 14 * 8));
+    SCVX_HIP(ctx, scvx::launch_vehicle_tiles(ctx, b->B, b->K, b->x, b->u, b->sigma, b->vtile, st));
+    return SCVX_OK;
+}
+
+int scvx_batch_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
+                       double* report, double* sig, double* covK, double* cov, const double* sp6) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    // every check before anything is enqueued
+    if (!S0) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
+    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
+    if ((rc = scvx::check_cov_vehicle(ctx, b, sp6))) return rc;   // the tiles are the batch's own: never missing
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    if ((rc = enqueue_vehicle_tiles(b, ctx->stream))) return rc;
+    const scvx::Dims d(b->B, b->K, b->NU);
+    scvx::Staging s(ctx);
+    const double* d0 = s.in(S0, d.c14);
+    double *dr = s.out_always(report, d.crep), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK), *dc = s.out(cov, d.cov);
+    const scvx::CovVeh v(b->vtile, sp6, nullptr);
+    s.launch([&] {
+        return scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, w14, dr, ds, dk, dc, s.st, nullptr, &v);
+    });
+    return s.finish("scvx_batch_cov_veh");
+}
+
 int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
                    double* report, double* sig, double* covK, double* cov) {
     int rc = check_batch(b, true);
@@ -1160,6 +1191,32 @@ int scvx_batch_track_mc_nav_veh(scvx_batch* b, const double* q14, const double* 
                                 rng ? &rg : nullptr, &vh, "scvx_batch_track_mc_nav_veh");
 }
 
+int scvx_batch_nav_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0,
+                           int m, const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
+                           double* navsig, double* kf, double* joint, const double* sp6) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    // every check before anything is enqueued
+    if (!S0 || !N0) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (S0, N0)");
+    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
+    if ((rc = scvx::check_nav_model(ctx, m, H, rm))) return rc;
+    if ((rc = scvx::check_cov_vehicle(ctx, b, sp6))) return rc;
+    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
+    if ((rc = enqueue_vehicle_tiles(b, ctx->stream))) return rc;
+    const scvx::Dims d(b->B, b->K, b->NU, 0, m);
+    scvx::Staging s(ctx);
+    const double *d0 = s.in(S0, d.c14), *dn = s.in(N0, d.c14);
+    double *dr = s.out_always(report, d.crep), *dq = s.out_always(navrep, d.nrep), *ds = s.out(sig, d.sig), *dv = s.out(navsig, d.navsig),
+           *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint);
+    const scvx::CovVeh v(b->vtile, sp6, nullptr);
+    s.launch([&] {
+        return scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st,
+                                    nullptr, &v);
+    });
+    return s.finish("scvx_batch_nav_cov_veh");
+}
+
 int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,
                        const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
                        double* navsig, double* kf, double* joint) {
@@ -1290,7 +1347,8 @@ struct NavModel {
 
 // the covariance- and the navigation-driven calls; thrust_call: scvx_batch_thrust_margins_from_cov, whose refusals keep their wording
 static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
-                            double nsigma, double cap, unsigned which, double* psig, bool thrust_call, const NavModel* nav = nullptr) {
+                            double nsigma, double cap, unsigned which, double* psig, bool thrust_call, const NavModel* nav = nullptr,
+                            bool veh = false, const double* sp6 = nullptr) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
@@ -1307,6 +1365,7 @@ static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU,
     if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
     if (nav && (rc = scvx::check_nav_model(ctx, nav->m, nav->H, nav->rm))) return rc;
     if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
+    if (veh && (rc = scvx::check_cov_vehicle(ctx, b, sp6))) return rc;   // the tiles are the batch's own: never missing
     const size_t n0 = (size_t)b->B * 196, np = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N;
     if (!b->cov_s0) {
         SCVX_HIP(ctx, hipMalloc((void**)&b->cov_s0, n0 * 8));
@@ -1322,7 +1381,17 @@ static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU,
     if (nav) SCVX_HIP(ctx, hipMemcpyAsync(b->nav_n0, nav->N0, n0 * 8, hipMemcpyHostToDevice, st));
     SCVX_HIP(ctx, hipStreamSynchronize(st));   // the caller's S0 (and N0) is consumed when the call returns; nothing comes back
     if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    if (nav)
+    if (veh) {
+        // the _veh forms: the tiles of the current accepted iterate, then the analysis with them; nothing returns to the host in between
+        if ((rc = enqueue_vehicle_tiles(b, st))) return rc;
+        const scvx::CovVeh v(b->vtile, sp6, nullptr);
+        if (nav)
+            SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H,
+                                               nav->rm, w14, b->cov_rep, b->nav_rep, nullptr, nullptr, nullptr, nullptr, st, b->cov_psig, &v));
+        else
+            SCVX_HIP(ctx, scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, w14, b->cov_rep, nullptr,
+                                           nullptr, nullptr, st, b->cov_psig, &v));
+    } else if (nav)
         SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H, nav->rm,
                                            w14, b->cov_rep, b->nav_rep, nullptr, nullptr, nullptr, nullptr, st, b->cov_psig));
     else
@@ -1355,6 +1424,18 @@ int scvx_batch_margins_from_nav(scvx_batch* b, const double* q14, const double* 
                                 unsigned which, double* psig) {
     const NavModel nav{N0, m, H, rm};
     return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, &nav);
+}
+
+int scvx_batch_margins_from_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
+                                    const double* w14, double nsigma, double cap, unsigned which, double* psig, const double* sp6) {
+    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, nullptr, true, sp6);
+}
+
+int scvx_batch_margins_from_nav_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
+                                    const double* N0, int m, const double* H, const double* rm, const double* w14, double nsigma,
+                                    double cap, unsigned which, double* psig, const double* sp6) {
+    const NavModel nav{N0, m, H, rm};
+    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, &nav, true, sp6);
 }
 
 int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,

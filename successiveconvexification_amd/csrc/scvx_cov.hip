@@ -62,16 +62,27 @@ __device__ __forceinline__ void cov_mm16(FA fa, FB fb, FC store, int lane) {
 // MF: 0 = one lane per element, 1 = the 16 x 16 corner of the two n-deep products on the matrix pipe
 // PS: 1 = also keep the per-node s = sqrt(c' Sigma_k c) of the five path functions that lanes 1..5 form for the margins
 // (scvx_cov_path_sigma_f64: psig [B][K+1][SCVX_PSIG_N]); 0 = the report alone, and nothing of it is compiled in
-template <typename DS, int NU, int MF, int PS = 0>
+// VEH: 1 = vehicle errors as consider parameters (scvx_cov_vehicle_f64, include/scvx.h).  J_k = d z_k / d theta (n x 6) is carried in LDS
+// beside Sigma_k, J_{k+1} = M_k J_k + [Gamma_k; 0], in two buffers that alternate (the update rides in the V pass: no barrier of its
+// own).  Gamma_k's four control columns are formed from the tile's B- / B+ columns and the plan's controls BEFORE Mtop overwrites
+// [A B-] in place (one barrier), its ISP and AERO columns are read from vtile.  Everything node_out and the final report read comes
+// from Sigma_k^tot = Sigma_k + J_k diag(sp^2) J_k', formed in V (dead between the T pass and the next step's V pass) behind the step's
+// last barrier (one more barrier); Sigma_k itself is never touched.  Every statement of it sits under `if constexpr (VEH)` and its
+// kernel argument (CovVehK) is a trailing pack that is empty without it: the instantiations without VEH keep their code.
+template <typename DS, int NU, int MF, int PS = 0, int VEH = 0, typename... VA>
 __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
                                                            const DS* __restrict__ deriv, const double* __restrict__ gain,
                                                            const double* __restrict__ S0, double* __restrict__ report,
                                                            double* __restrict__ sig, double* __restrict__ covK, double* __restrict__ cov,
-                                                           double* __restrict__ psig) {
+                                                           double* __restrict__ psig, VA... va) {
+    static_assert(sizeof...(VA) == (VEH ? 1 : 0), "the VEH instantiations take one CovVehK behind psig, the others nothing");
     constexpr int n = 14 + NU, m = 14 + 2 * NU, NC = m + 1, DSZ = 14 * NC, ND = 14 * m, NL = NU * n, NN = n * n;
+    constexpr int NJ = n * SCVX_VEH_N;
     constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
     constexpr int NBORD = NN - 256;   // elements of an n x n product outside its 16 x 16 corner
     __shared__ double Sl[NN], Dl[ND], Ll[NL], Vl[NN], Rl[SCVX_COV_NREP + 1];
+    __shared__ double Jl[VEH ? 2 * NJ : 1], Gml[VEH ? 14 * SCVX_VEH_N : 1];   // VEH: J_k and J_{k+1}; Gamma_k, column-major
+    const double* const So = VEH ? Vl : Sl;   // what the outputs read: Sigma_k, with VEH Sigma_k^tot
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= B) return;
     const DS* tiles = deriv + (size_t)b * K * DSZ;
@@ -90,6 +101,8 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
     }
     for (int e = lane; e < ND; e += 64) Dl[e] = (double)tiles[e];
     for (int e = lane; e < NL; e += 64) Ll[e] = gb[e];
+    if constexpr (VEH)
+        for (int e = lane; e < NJ; e += 64) Jl[e] = 0.0;
     // the running columns: lane 0 SIG_PEAK (and the non-finite flag), 1 N_MASS, 2 N_GLIDE, 3 N_TILT, 4 N_RATE, 5 S_THRUST / N_TMAX / N_TMIN
     double acc0 = lane == 0 ? 0.0 : inf, acc1 = inf, acc2 = 0.0, bad = 0.0;
     double pv0 = 0.0, pv1 = 0.0, pv2 = 0.0;
@@ -128,24 +141,24 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
     // dense outputs and the running columns at node k (Sigma_k in Sl; pv*: the plan values of node k this lane's column reads)
     auto node_out = [&](int k) {
         if (covb)
-            for (int e = lane; e < NN; e += 64) covb[(size_t)k * NN + e] = Sl[e];
-        if (sigb && lane < n) sigb[(size_t)k * n + lane] = cov_sd(Sl[lane * n + lane]);
+            for (int e = lane; e < NN; e += 64) covb[(size_t)k * NN + e] = So[e];
+        if (sigb && lane < n) sigb[(size_t)k * n + lane] = cov_sd(So[lane * n + lane]);
         if (lane == 0) {
             double tr = 0.0;
 #pragma unroll
-            for (int i = 0; i < 14; i++) tr += Sl[i * n + i];
+            for (int i = 0; i < 14; i++) tr += So[i * n + i];
             bad = fma(tr, 0.0, bad);
             acc0 = nan_max(acc0, cov_sd(tr));
         } else if (k > 0 && lane < 6) {
             double sv = 0.0;   // PS: this lane's s at node k (0 where the margin skips the node)
             if (lane == 1) {
-                const double s = cov_sd(Sl[0]);
+                const double s = cov_sd(So[0]);
                 sv = s;
                 if (!(s == 0.0)) acc0 = nan_min(acc0, -(c.mdry - pv0) / s);
             } else if (lane == 5) {
                 const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
                 if (!(nr == 0.0)) {
-                    const double s = cov_sd(cov_quad3(Sl, n, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
+                    const double s = cov_sd(cov_quad3(So, n, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
                     acc2 = nan_max(acc2, s);
                     sv = s;
                     if (!(s == 0.0)) {
@@ -161,13 +174,13 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
                     double g, q;
                     if (lane == 2) {
                         g = c.tggs * nr - pv0;
-                        q = cov_quad3(Sl, n, 1, 2, 3, -1.0, c.tggs * a0 / nr, c.tggs * a1 / nr);
+                        q = cov_quad3(So, n, 1, 2, 3, -1.0, c.tggs * a0 / nr, c.tggs * a1 / nr);
                     } else if (lane == 3) {
                         g = nr - c.sqcm;
-                        q = cov_quad3(Sl, n, 9, 10, 10, a0 / nr, a1 / nr, 0.0);
+                        q = cov_quad3(So, n, 9, 10, 10, a0 / nr, a1 / nr, 0.0);
                     } else {
                         g = nr - c.omMax;
-                        q = cov_quad3(Sl, n, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
+                        q = cov_quad3(So, n, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
                     }
                     const double s = cov_sd(q);
                     sv = s;
@@ -179,6 +192,25 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             psb[lane - 1] = 0.0;   // node 0: no margin reads it
         }
     };
+    // VEH: Sigma_k^tot = Sigma_k + J_k diag(sp^2) J_k' into V, J_k (in the buffer k & 1) out as sens; (J J) p keeps it symmetric bit for bit,
+    // and a zero update leaves the very Sigma_k
+    auto tot = [&](int k) {
+        if constexpr (VEH) {
+            const CovVehK& vk = veh_first(va...);
+            const double* Jc = Jl + (k & 1) * NJ;
+            for (int e = lane; e < NN; e += 64) {
+                const int a = e / n, cc = e % n;
+                double t = 0.0;
+#pragma unroll
+                for (int j = 0; j < SCVX_VEH_N; j++) t = fma(Jc[a * SCVX_VEH_N + j] * Jc[cc * SCVX_VEH_N + j], vk.p[j], t);
+                Vl[e] = t == 0.0 ? Sl[e] : Sl[e] + t;
+            }
+            if (vk.sens)
+                for (int e = lane; e < NJ; e += 64) vk.sens[((size_t)b * (K + 1) + k) * NJ + e] = Jc[e];
+            __syncthreads();
+        }
+    };
+    tot(0);
     node_out(0);
     for (int k = 0; k < K; k++) {
         // the next step's tile and gain block, and the plan values of node k + 1, in flight while this step computes
@@ -206,6 +238,13 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             pv1 = lane == 1 ? 0.0 : p[1];
             pv2 = (lane == 1 || lane == 3) ? 0.0 : p[2];
         }
+        if constexpr (VEH) {
+            // Gamma_k's columns (include/scvx.h), while the tile still holds B-
+            const CovVehK& vk = veh_first(va...);
+            const double* vt = vk.vtile ? vk.vtile + ((size_t)b * K + k) * SCVX_VTILE_N * 14 : nullptr;
+            for (int e = lane; e < 14 * SCVX_VEH_N; e += 64) Gml[e] = veh_gamma<NU>(Dl, ub + (size_t)k * NU, vt, e % 14, e / 14);
+            __syncthreads();
+        }
         // Mtop = [A B-] + B+ L, in place
         for (int e = lane; e < 14 * n; e += 64) {
             const int i = e % 14, cc = e / 14;
@@ -228,6 +267,20 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             for (int e = lane; e < NN; e += 64) {
                 const int a = e % n, cc = e / n;
                 Vl[a * n + cc] = velem(a, cc);
+            }
+        }
+        if constexpr (VEH) {
+            // J_{k+1} = M J_k + [Gamma_k; 0] into the other buffer
+            const double* Jc = Jl + (k & 1) * NJ;
+            double* Jn = Jl + ((k + 1) & 1) * NJ;
+            for (int e = lane; e < NJ; e += 64) {
+                const int a = e / SCVX_VEH_N, cI = e % SCVX_VEH_N;
+                int st;
+                const double* mp = mrow(a, st);
+                double s = a < 14 ? Gml[cI * 14 + a] : 0.0;
+#pragma unroll
+                for (int l = 0; l < n; l++) s = fma(mp[l * st], Jc[l * SCVX_VEH_N + cI], s);
+                Jn[e] = s;
             }
         }
         __syncthreads();
@@ -272,16 +325,17 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             }
         }
         __syncthreads();
+        tot(k + 1);
         node_out(k + 1);
     }
     // the report: running columns from their lanes, the final columns off Sigma_K
     if (covK) {
         double* o = covK + (size_t)b * NN;
-        for (int e = lane; e < NN; e += 64) o[e] = Sl[e];
+        for (int e = lane; e < NN; e += 64) o[e] = So[e];
     }
     auto blk = [&](int i0, int i1) {
         double t = 0.0;
-        for (int i = i0; i < i1; i++) t += Sl[i * n + i];
+        for (int i = i0; i < i1; i++) t += So[i * n + i];
         return cov_sd(t);
     };
     if (lane == 0) {
@@ -300,7 +354,7 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
         Rl[SCVX_COV_N_TMAX] = acc0;
         Rl[SCVX_COV_N_TMIN] = acc1;
     } else if (lane == 6) {
-        Rl[SCVX_COV_SIG_M] = cov_sd(Sl[0]);
+        Rl[SCVX_COV_SIG_M] = cov_sd(So[0]);
     } else if (lane == 7) {
         Rl[SCVX_COV_SIG_R] = blk(1, 4);
     } else if (lane == 8) {
@@ -311,7 +365,7 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
         Rl[SCVX_COV_SIG_W] = blk(11, 14);
     } else if (lane == 11) {
         // eigenvalues of [[a, h], [h, d]], the horizontal block of Sigma_K (state indices 2, 3), closed form
-        const double a = Sl[2 * n + 2], d = Sl[3 * n + 3], h = Sl[2 * n + 3];
+        const double a = So[2 * n + 2], d = So[3 * n + 3], h = So[2 * n + 3];
         const double mean = 0.5 * (a + d), dif = 0.5 * (a - d), rad = sqrt(dif * dif + h * h);
         Rl[SCVX_COV_ELL_A] = cov_sd(mean + rad);
         Rl[SCVX_COV_ELL_B] = cov_sd(mean - rad);
@@ -332,7 +386,7 @@ constexpr bool kCovMfmaDefault = false;   // the lane form, which the parity tes
 template <typename DS>
 static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv, const double* gain,
                                const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
-                               double* psig = nullptr) {
+                               double* psig = nullptr, const CovVeh* veh = nullptr) {
     const PathK pk = path_constants(ctx->prob);
     CovK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}};
     for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
@@ -340,9 +394,16 @@ static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* 
     bool mf = kCovMfmaDefault;
     if (const char* v = std::getenv("SCVX_COV_MFMA"); v && *v) mf = std::atoi(v) != 0;
     const dim3 g((unsigned)B), blk(64);
+    const CovVehK vk(veh);
 #define SCVX_COV_LAUNCH(NU, MF)                                                                                                        \
     do {                                                                                                                               \
-        if (psig)                                                                                                                      \
+        if (veh && psig)                                                                                                               \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, \
+                               sig, covK, cov, psig, vk);                                                                              \
+        else if (veh)                                                                                                                  \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, \
+                               sig, covK, cov, psig, vk);                                                                              \
+        else if (psig)                                                                                                                      \
             hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, \
                                cov, psig);                                                                                             \
         else                                                                                                                           \
@@ -362,10 +423,25 @@ static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* 
 
 hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
                       const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
-                      double* psig) {
-    return deriv.d ? launch_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, w, report, sig, covK, cov, st, psig)
-                   : launch_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, w, report, sig, covK, cov, st, psig);
+                      double* psig, const CovVeh* veh) {
+    return deriv.d ? launch_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, w, report, sig, covK, cov, st, psig, veh)
+                   : launch_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, w, report, sig, covK, cov, st, psig, veh);
 }
+
+// what the _vehicle forms refuse beyond the call they extend
+int check_cov_vehicle(scvx_ctx* ctx, const void* vtile, const double* sp6) {
+    if (!ctx) return SCVX_ERR_ARG;
+    if (!sp6) return fail(ctx, SCVX_ERR_ARG, "vehicle: null sp6");
+    for (int i = 0; i < SCVX_VEH_N; i++)
+        if (!(sp6[i] >= 0.0) || !std::isfinite(sp6[i])) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp must be finite and >= 0");
+    if (sp6[SCVX_VEH_AERO] != 0.0 && !ctx->dyn.aero)
+        return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[AERO] != 0 on a model without aerodynamics");
+    if (sp6[SCVX_VEH_FIN] != 0.0 && !ctx->dyn.fin) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[FIN] != 0 on a model without fins");
+    if (!vtile && (sp6[SCVX_VEH_ISP] != 0.0 || sp6[SCVX_VEH_AERO] != 0.0))
+        return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[ISP] or sp[AERO] != 0 needs vtile (scvx_vehicle_tiles_f64)");
+    return SCVX_OK;
+}
+
 
 int check_cov_noise(scvx_ctx* ctx, const double* w) {
     if (!ctx) return SCVX_ERR_ARG;
@@ -409,6 +485,37 @@ int scvx_cov_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, co
     SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, nullptr,
                                    nullptr, nullptr, ctx->stream, psig_dev));
     return SCVX_OK;
+}
+
+int scvx_cov_vehicle_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                         const double* gain_dev, const double* S0_dev, const double* w14, double* report_dev, double* psig_dev,
+                         double* sig_dev, double* covK_dev, double* cov_dev, const double* vtile_dev, const double* sp6,
+                         double* sens_dev) {
+    int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    if (rc) return rc;
+    if ((rc = scvx::check_cov_vehicle(ctx, vtile_dev, sp6))) return rc;
+    const scvx::CovVeh v = scvx::CovVeh(vtile_dev, sp6, sens_dev);
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, sig_dev,
+                                   covK_dev, cov_dev, ctx->stream, psig_dev, &v));
+    return SCVX_OK;
+}
+
+int scvx_cov_vehicle_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                              const double* S0, const double* w14, double* report, double* psig, double* sig, double* covK, double* cov,
+                              const double* vtile, const double* sp6, double* sens) {
+    int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
+    if (rc) return rc;
+    if ((rc = scvx::check_cov_vehicle(ctx, vtile, sp6))) return rc;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx));
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
+                 *dv = s.in(vtile, d.vtile);
+    double *dr = s.out(report, d.crep), *dp = s.out(psig, d.psig), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK),
+           *dc = s.out(cov, d.cov), *dj = s.out(sens, d.sens);
+    const scvx::CovVeh v = scvx::CovVeh(dv, sp6, dj);
+    s.launch([&] { return scvx::launch_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, w14, dr, ds, dk, dc, s.st, dp, &v); });
+    return s.finish("scvx_cov_vehicle_f64_host");
 }
 
 int scvx_cov_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,

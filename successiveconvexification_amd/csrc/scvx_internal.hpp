@@ -101,6 +101,7 @@ int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, c
 
 struct McQ;   // what the _q forms add to a sampled call (scvx_mc.hpp); nullptr: nothing, the instantiations without per-node samples
 struct McRng; // the _rng forms (scvx_mc.hpp): the draws are made on the device; nullptr: the uploaded draws, the instantiations without RNG
+struct CovVeh; // the _vehicle forms of the covariance and navigation analyses (below); nullptr: the plain call
 struct McVeh; // the _veh forms (scvx_mc.hpp): per-flight vehicle errors; nullptr: the nominal vehicle, the instantiations without ACT
 
 // Sampled dispersion (scvx_mc.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan; C0[B][14][14],
@@ -134,7 +135,7 @@ int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const 
 // [B][K+1][SCVX_PSIG_N] the per-node s of the five path functions are kept (scvx_cov_path_sigma_f64) and sig, covK, cov are nullptr.
 hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
                       const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
-                      double* psig = nullptr);
+                      double* psig = nullptr, const CovVeh* veh = nullptr);
 int check_cov_noise(scvx_ctx* ctx, const double* w);
 int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
               const double* w, const void* report);
@@ -145,8 +146,63 @@ int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const v
 // functions are kept, read off the truth block Xi_k[z,z] (scvx_nav_path_sigma_f64), and sig, navsig, kf, joint are nullptr.
 hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig = nullptr);
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig = nullptr,
+                          const CovVeh* veh = nullptr);
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm);
+
+// Vehicle errors in the two analyses above (include/scvx.h "consider parameters").  CovVeh: what the _vehicle forms add to a launch;
+// nullptr: the plain call, the instantiations without VEH.  vtile[B][K][SCVX_VTILE_N][14] (scvx_vtile.hip) or nullptr, sp: the six
+// standard deviations (host), sens[B][K+1][n][6] or nullptr.
+struct CovVeh {
+    const double* vtile;
+    double sp[SCVX_VEH_N];
+    double* sens;
+    CovVeh(const double* vtile_, const double* sp6, double* sens_) : vtile(vtile_), sens(sens_) {
+        for (int i = 0; i < SCVX_VEH_N; i++) sp[i] = sp6[i];
+    }
+};
+// the kernel argument of the VEH instantiations: p = sp^2
+struct CovVehK {
+    const double* vtile;
+    double* sens;
+    double p[SCVX_VEH_N];
+    explicit CovVehK(const CovVeh* v) : vtile(v ? v->vtile : nullptr), sens(v ? v->sens : nullptr) {
+        for (int i = 0; i < SCVX_VEH_N; i++) p[i] = v ? v->sp[i] * v->sp[i] : 0.0;
+    }
+};
+// the one element of a VEH instantiation's trailing kernel-argument pack
+template <typename T>
+__device__ __forceinline__ const T& veh_first(const T& t) { return t; }
+// Element (i, cI) of Gamma_k = d x_{k+1} / d theta (include/scvx.h): D the segment's tile (column-major, stride 14: A | B- | B+), uk =
+// ubar_k with ubar_{k+1} behind it, vt the segment's vehicle tile [SCVX_VTILE_N][14] or nullptr.  w- / w+ are d ua / d theta at the two
+// ends of the hold: THRUST u;  MIS_Y e_y x u = (u2, 0, -u0);  MIS_Z e_z x u = (-u1, u0, 0);  FIN u[3:5].
+template <int NU>
+__device__ __forceinline__ double veh_gamma(const double* D, const double* uk, const double* vt, int i, int cI) {
+    constexpr int n = 14 + NU;
+    double s = 0.0;
+    if (cI == SCVX_VEH_ISP || cI == SCVX_VEH_AERO) {
+        if (vt) s = vt[(cI == SCVX_VEH_ISP ? SCVX_VTILE_ISP : SCVX_VTILE_AERO) * 14 + i];
+    } else if (cI == SCVX_VEH_FIN) {
+        if constexpr (NU == 5) {
+#pragma unroll
+            for (int j = 3; j < 5; j++) s = fma(D[(14 + j) * 14 + i], uk[j], fma(D[(n + j) * 14 + i], uk[NU + j], s));
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const double sy = j == 0 ? 1.0 : (j == 2 ? -1.0 : 0.0), sz = j == 0 ? -1.0 : (j == 1 ? 1.0 : 0.0);
+            const int jy = j == 0 ? 2 : 0, jz = j == 0 ? 1 : 0;
+            const double wm = cI == SCVX_VEH_THRUST ? uk[j] : (cI == SCVX_VEH_MIS_Y ? sy * uk[jy] : sz * uk[jz]);
+            const double wp = cI == SCVX_VEH_THRUST ? uk[NU + j] : (cI == SCVX_VEH_MIS_Y ? sy * uk[NU + jy] : sz * uk[NU + jz]);
+            s = fma(D[(14 + j) * 14 + i], wm, fma(D[(n + j) * 14 + i], wp, s));
+        }
+    }
+    return s;
+}
+hipError_t launch_vehicle_tiles(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, double* vtile,
+                                hipStream_t st);
+int check_vehicle_tiles(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* vtile);
+int check_cov_vehicle(scvx_ctx* ctx, const void* vtile, const double* sp6);
 
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],
 // info [B][6] = status, iters, pobj, gap, pres, dres.  threedof_to_record overwrites the trajectory records [B][(K+1)*(14+NU)+1]

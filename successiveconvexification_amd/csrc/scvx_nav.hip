@@ -46,13 +46,21 @@ __device__ __forceinline__ double nav_quad3(const double* S, int n, int i0, int 
 
 // PS: 1 = also keep the per-node s of the five path functions (psig [B][K+1][SCVX_PSIG_N], lane - 1 is the column: SCVX_PSIG_MASS, GLIDE,
 // TILT, RATE, THRUST); 0 = the reports alone, and nothing of it is compiled in
-template <typename DS, int NU, int PS = 0>
+// VEH: 1 = vehicle errors as consider parameters (scvx_nav_cov_vehicle_f64; cov_propagate_kernel's VEH on the joint).  J_k = d z_k / d
+// theta (n x 6: the eps rows are zero, the recursion of eps does not see theta) alternates between two LDS buffers, J_{k+1} = [Mtop; L]
+// J_k + [Gamma_k; 0], updated in the V pass.  The outputs read Xi_k with J_k diag(sp^2) J_k' added to its [z, z] block, formed in V
+// behind the step's last barrier; V is the update's scratch too, so the next step starts behind one more barrier.  Xi_k itself, and
+// with it the eps blocks, kf and the navigation report, are the plain call's.  All of it under `if constexpr (VEH)`, the kernel
+// argument a trailing pack that is empty without it.
+template <typename DS, int NU, int PS = 0, int VEH = 0, typename... VA>
 __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
                                                      const DS* __restrict__ deriv, const double* __restrict__ gain,
                                                      const double* __restrict__ S0, const double* __restrict__ N0,
                                                      double* __restrict__ report, double* __restrict__ navrep, double* __restrict__ sig,
                                                      double* __restrict__ navsig, double* __restrict__ kf, double* __restrict__ joint,
-                                                     double* __restrict__ psig) {
+                                                     double* __restrict__ psig, VA... va) {
+    static_assert(sizeof...(VA) == (VEH ? 1 : 0), "the VEH instantiations take one CovVehK behind psig, the others nothing");
+    constexpr int NJ = (14 + NU) * SCVX_VEH_N;
     constexpr int n = 14 + NU, N = n + 14, mt = 14 + 2 * NU, NC = mt + 1, DSZ = 14 * NC, ND = 14 * mt, NL = NU * n, NN = N * N;
     constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
     constexpr int NR = SCVX_COV_NREP + SCVX_NAV_NREP;
@@ -60,6 +68,8 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
     __shared__ double Xl[NN], Vl[NN], Dl[ND], Ml[14 * n], Gl[196], Ll[NL], Hl[196], rml[14], tl[14], Rl[NR + 2];
     // Kl: HP, then Kf' (m x 14);  Sl: S, then its factor C, dead before Y is born in its place
     double *Yl = Vl, *Sl = Vl, *Jl = Vl + N * 14, *Kl = Jl + 196;
+    __shared__ double Tl[VEH ? 2 * NJ : 1], Gml[VEH ? 14 * SCVX_VEH_N : 1];   // VEH: d z / d theta at nodes k and k + 1; Gamma_k, column-major
+    const double* const Xo = VEH ? Vl : Xl;   // what the outputs read: Xi_k, with VEH its [z, z] block + J_k diag(sp^2) J_k'
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= B) return;
     const int m = c.m;
@@ -87,6 +97,8 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
     for (int e = lane; e < NL; e += 64) Ll[e] = gb[e];
     for (int e = lane; e < m * 14; e += 64) Hl[e] = c.H[e];
     if (lane < 14) rml[lane] = c.rm[lane];
+    if constexpr (VEH)
+        for (int e = lane; e < NJ; e += 64) Tl[e] = 0.0;
     // the running columns: lane 0 SIG_PEAK (and its non-finite flag), 1 N_MASS, 2 N_GLIDE, 3 N_TILT, 4 N_RATE, 5 S_THRUST / N_TMAX /
     // N_TMIN, 12 NAV_PEAK (and its non-finite flag)
     double acc0 = (lane == 0 || lane == 12) ? 0.0 : inf, acc1 = inf, acc2 = 0.0, bad = 0.0;
@@ -115,26 +127,26 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
     // dense outputs and the running columns at node k (the pre-update Xi_k in Xl; pv*: the plan values of node k this lane reads)
     auto node_out = [&](int k) {
         if (jb)
-            for (int e = lane; e < NN; e += 64) jb[(size_t)k * NN + e] = Xl[e];
-        if (sigb && lane < n) sigb[(size_t)k * n + lane] = nav_sd(Xl[lane * N + lane]);
-        if (nsb && lane >= 32 && lane < 46) nsb[(size_t)k * 14 + lane - 32] = nav_sd(Xl[(n + lane - 32) * N + n + lane - 32]);
+            for (int e = lane; e < NN; e += 64) jb[(size_t)k * NN + e] = Xo[e];
+        if (sigb && lane < n) sigb[(size_t)k * n + lane] = nav_sd(Xo[lane * N + lane]);
+        if (nsb && lane >= 32 && lane < 46) nsb[(size_t)k * 14 + lane - 32] = nav_sd(Xo[(n + lane - 32) * N + n + lane - 32]);
         if (lane == 0 || lane == 12) {
             const int o = lane == 0 ? 0 : n;
             double tr = 0.0;
 #pragma unroll
-            for (int i = 0; i < 14; i++) tr += Xl[(o + i) * N + o + i];
+            for (int i = 0; i < 14; i++) tr += Xo[(o + i) * N + o + i];
             bad = fma(tr, 0.0, bad);
             acc0 = nan_max(acc0, nav_sd(tr));
         } else if (k > 0 && lane < 6) {
             [[maybe_unused]] double sv = 0.0;   // PS: this lane's s at node k (0 where the margin skips the node: an undefined gradient)
             if (lane == 1) {
-                const double s = nav_sd(Xl[0]);
+                const double s = nav_sd(Xo[0]);
                 if constexpr (PS != 0) sv = s;
                 if (!(s == 0.0)) acc0 = nan_min(acc0, -(c.mdry - pv0) / s);
             } else if (lane == 5) {
                 const double nr = sqrt(pv0 * pv0 + pv1 * pv1 + pv2 * pv2);
                 if (!(nr == 0.0)) {
-                    const double s = nav_sd(nav_quad3(Xl, N, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
+                    const double s = nav_sd(nav_quad3(Xo, N, 14, 15, 16, pv0 / nr, pv1 / nr, pv2 / nr));
                     acc2 = nan_max(acc2, s);
                     if constexpr (PS != 0) sv = s;
                     if (!(s == 0.0)) {
@@ -150,13 +162,13 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
                     double g, q;
                     if (lane == 2) {
                         g = c.tggs * nr - pv0;
-                        q = nav_quad3(Xl, N, 1, 2, 3, -1.0, c.tggs * a0 / nr, c.tggs * a1 / nr);
+                        q = nav_quad3(Xo, N, 1, 2, 3, -1.0, c.tggs * a0 / nr, c.tggs * a1 / nr);
                     } else if (lane == 3) {
                         g = nr - c.sqcm;
-                        q = nav_quad3(Xl, N, 9, 10, 10, a0 / nr, a1 / nr, 0.0);
+                        q = nav_quad3(Xo, N, 9, 10, 10, a0 / nr, a1 / nr, 0.0);
                     } else {
                         g = nr - c.omMax;
-                        q = nav_quad3(Xl, N, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
+                        q = nav_quad3(Xo, N, 11, 12, 13, a0 / nr, a1 / nr, a2 / nr);
                     }
                     const double s = nav_sd(q);
                     if constexpr (PS != 0) sv = s;
@@ -168,6 +180,26 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
         if constexpr (PS != 0)
             if (k == 0 && lane >= 1 && lane < 6) psb[lane - 1] = 0.0;   // node 0: no margin reads it
     };
+    // VEH: Xi_k with J_k diag(sp^2) J_k' on its [z, z] block into V, J_k (in the buffer k & 1) out as sens
+    auto tot = [&](int k) {
+        if constexpr (VEH) {
+            const CovVehK& vk = veh_first(va...);
+            const double* Jc = Tl + (k & 1) * NJ;
+            for (int e = lane; e < NN; e += 64) {
+                const int a = e / N, cc = e % N;
+                double t = 0.0;
+                if (a < n && cc < n) {
+#pragma unroll
+                    for (int j = 0; j < SCVX_VEH_N; j++) t = fma(Jc[a * SCVX_VEH_N + j] * Jc[cc * SCVX_VEH_N + j], vk.p[j], t);
+                }
+                Vl[e] = t == 0.0 ? Xl[e] : Xl[e] + t;
+            }
+            if (vk.sens)
+                for (int e = lane; e < NJ; e += 64) vk.sens[((size_t)b * (K + 1) + k) * NJ + e] = Jc[e];
+            __syncthreads();
+        }
+    };
+    tot(0);
     node_out(0);
     for (int k = 0; k < K; k++) {
         // the next step's tile and gain block, and the plan values of node k + 1, in flight while this step computes
@@ -194,6 +226,13 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
             pv0 = p[0];
             pv1 = lane == 1 ? 0.0 : p[1];
             pv2 = (lane == 1 || lane == 3) ? 0.0 : p[2];
+        }
+        if constexpr (VEH) {
+            // Gamma_k's columns (include/scvx.h)
+            const CovVehK& vk = veh_first(va...);
+            const double* vt = vk.vtile ? vk.vtile + ((size_t)b * K + k) * SCVX_VTILE_N * 14 : nullptr;
+            for (int e = lane; e < 14 * SCVX_VEH_N; e += 64) Gml[e] = veh_gamma<NU>(Dl, ub + (size_t)k * NU, vt, e % 14, e / 14);
+            __syncthreads();   // node_out's reads of V are done: the update may use it
         }
         // Mtop = [A B-] + B+ L and Gx = B+ Lx (read by the time step; written here, behind the previous step's last barrier)
         for (int e = lane; e < 14 * n + 196; e += 64) {
@@ -304,6 +343,18 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
             const int a = e / N, cc = e % N;
             Vl[e] = tdot(a, [&](int l) { return Xl[cc * N + l]; });
         }
+        if constexpr (VEH) {
+            // J_{k+1} = [Mtop; L] J_k + [Gamma_k; 0] into the other buffer
+            const double* Jc = Tl + (k & 1) * NJ;
+            double* Jn = Tl + ((k + 1) & 1) * NJ;
+            for (int e = lane; e < NJ; e += 64) {
+                const int a = e / SCVX_VEH_N, cI = e % SCVX_VEH_N;
+                double s = a < 14 ? Gml[cI * 14 + a] : 0.0;
+#pragma unroll
+                for (int l = 0; l < n; l++) s = fma(a < 14 ? Ml[l * 14 + a] : Ll[(a - 14) * n + l], Jc[l * SCVX_VEH_N + cI], s);
+                Jn[e] = s;
+            }
+        }
         __syncthreads();
         // R = V T', over Xi (no longer read): lanes run down a column of R
         for (int e = lane; e < NN; e += 64) {
@@ -337,18 +388,19 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
             }
         }
         __syncthreads();
+        tot(k + 1);
         node_out(k + 1);
     }
     // the reports: running columns from their lanes, the final columns off Xi_K; Rl[NR], Rl[NR + 1]: the two non-finite flags
     auto blk = [&](int o, int i0, int i1) {
         double t = 0.0;
-        for (int i = i0; i < i1; i++) t += Xl[(o + i) * N + o + i];
+        for (int i = i0; i < i1; i++) t += Xo[(o + i) * N + o + i];
         return nav_sd(t);
     };
     // trace over [i0, i1) of Cov(xhat_K - xbar_K) = Sigma_xx - C - C' + P
     auto est = [&](int i0, int i1) {
         double t = 0.0;
-        for (int i = i0; i < i1; i++) t += Xl[i * N + i] - Xl[i * N + n + i] - Xl[(n + i) * N + i] + Xl[(n + i) * N + n + i];
+        for (int i = i0; i < i1; i++) t += Xo[i * N + i] - Xo[i * N + n + i] - Xo[(n + i) * N + i] + Xo[(n + i) * N + n + i];
         return nav_sd(t);
     };
     double* Nl = Rl + SCVX_COV_NREP;
@@ -368,7 +420,7 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
         Rl[SCVX_COV_N_TMAX] = acc0;
         Rl[SCVX_COV_N_TMIN] = acc1;
     } else if (lane == 6) {
-        Rl[SCVX_COV_SIG_M] = nav_sd(Xl[0]);
+        Rl[SCVX_COV_SIG_M] = nav_sd(Xo[0]);
     } else if (lane == 7) {
         Rl[SCVX_COV_SIG_R] = blk(0, 1, 4);
     } else if (lane == 8) {
@@ -379,7 +431,7 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
         Rl[SCVX_COV_SIG_W] = blk(0, 11, 14);
     } else if (lane == 11) {
         // eigenvalues of [[a, h], [h, d]], the horizontal block of Sigma_K (state indices 2, 3), closed form
-        const double a = Xl[2 * N + 2], d = Xl[3 * N + 3], h = Xl[2 * N + 3];
+        const double a = Xo[2 * N + 2], d = Xo[3 * N + 3], h = Xo[2 * N + 3];
         const double mean = 0.5 * (a + d), dif = 0.5 * (a - d), rad = sqrt(dif * dif + h * h);
         Rl[SCVX_COV_ELL_A] = nav_sd(mean + rad);
         Rl[SCVX_COV_ELL_B] = nav_sd(mean - rad);
@@ -417,16 +469,23 @@ template <typename DS>
 static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv,
                                    const double* gain, const double* S0, const double* N0, int m, const double* H, const double* rm,
                                    const double* w, double* report, double* navrep, double* sig, double* navsig, double* kf,
-                                   double* joint, hipStream_t st, double* psig = nullptr) {
+                                   double* joint, hipStream_t st, double* psig = nullptr, const CovVeh* veh = nullptr) {
     const PathK pk = path_constants(ctx->prob);
     NavK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}, {}, {}, m};
     for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
     for (int i = 0; i < m; i++) c.rm[i] = rm[i];
     for (int i = 0; i < m * 14; i++) c.H[i] = H[i];
     const dim3 g((unsigned)B), blk(64);
+    const CovVehK vk(veh);
 #define SCVX_NAV_LAUNCH(NU)                                                                                                            \
     do {                                                                                                                               \
-        if (psig)                                                                                                                      \
+        if (veh && psig)                                                                                                               \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, \
+                               sig, navsig, kf, joint, psig, vk);                                                                      \
+        else if (veh)                                                                                                                  \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 0, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, \
+                               sig, navsig, kf, joint, psig, vk);                                                                      \
+        else if (psig)                                                                                                                      \
             hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig,     \
                                navsig, kf, joint, psig);                                                                               \
         else                                                                                                                           \
@@ -441,11 +500,12 @@ static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, int B, int K, const doub
 
 hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig) {
+                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig,
+                          const CovVeh* veh) {
     return deriv.d ? launch_nav_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint,
-                                              st, psig)
+                                              st, psig, veh)
                    : launch_nav_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st,
-                                             psig);
+                                             psig, veh);
 }
 
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm) {
@@ -493,6 +553,42 @@ int scvx_nav_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, co
     SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
                                        report_dev, navrep_dev, nullptr, nullptr, nullptr, nullptr, ctx->stream, psig_dev));
     return SCVX_OK;
+}
+
+int scvx_nav_cov_vehicle_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                             const double* gain_dev, const double* S0_dev, const double* N0_dev, int m, const double* H, const double* rm,
+                             const double* w14, double* report_dev, double* navrep_dev, double* psig_dev, double* sig_dev,
+                             double* navsig_dev, double* kf_dev, double* joint_dev, const double* vtile_dev, const double* sp6,
+                             double* sens_dev) {
+    int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
+    if (rc) return rc;
+    if ((rc = scvx::check_cov_vehicle(ctx, vtile_dev, sp6))) return rc;
+    const scvx::CovVeh v(vtile_dev, sp6, sens_dev);
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
+                                       report_dev, navrep_dev, sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream, psig_dev, &v));
+    return SCVX_OK;
+}
+
+int scvx_nav_cov_vehicle_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                                  const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w14,
+                                  double* report, double* navrep, double* psig, double* sig, double* navsig, double* kf, double* joint,
+                                  const double* vtile, const double* sp6, double* sens) {
+    int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
+    if (rc) return rc;
+    if ((rc = scvx::check_cov_vehicle(ctx, vtile, sp6))) return rc;
+    const scvx::Dims d(B, K, scvx_control_dim(ctx), 0, m);
+    scvx::Staging s(ctx);
+    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
+                 *dn = s.in(N0, d.c14), *dt = s.in(vtile, d.vtile);
+    double *dr = s.out(report, d.crep), *dq = s.out(navrep, d.nrep), *dp = s.out(psig, d.psig), *ds = s.out(sig, d.sig),
+           *dv = s.out(navsig, d.navsig), *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint), *de = s.out(sens, d.sens);
+    const scvx::CovVeh v(dt, sp6, de);
+    s.launch([&] {
+        return scvx::launch_nav_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st, dp,
+                                    &v);
+    });
+    return s.finish("scvx_nav_cov_vehicle_f64_host");
 }
 
 int scvx_nav_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,

@@ -245,6 +245,61 @@ def track_fly_batch(cache: IntegratorCache, x, u, sigma, gain, dx0=None, nsub=No
     return FlightReport(rep, xfly, "track", ufly)
 
 
+def vehicle_tiles_batch(cache: IntegratorCache, x, u, sigma):
+    """The two per-segment sensitivities to the vehicle errors that the derivative tiles do not hold (scvx_vehicle_tiles_f64_host,
+    include/scvx.h): vtile [B][K][2][14], row 0 = d x_{k+1} / d theta_ISP, row 1 = d x_{k+1} / d theta_AERO (zeros without
+    aerodynamics), about the plan x [B][K+1][14], u [B][K+1][nu], sigma [B] at theta = 0, with the context's npts and dt = 1 / (K + 1).
+    What vtile= of the first-order analyses takes when ISP or AERO is dispersed."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], cache.nu) or sigma.shape != (x.shape[0],):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % cache.nu)
+    B, K = x.shape[0], x.shape[1] - 1
+    vt = np.empty((B, K, _lib.VTILE_N, 14))
+    _lib.check(cache.handle, cache._L.scvx_vehicle_tiles_f64_host(cache.handle, B, K, _p(x), _p(u), _p(sigma), _p(vt)),
+               "scvx_vehicle_tiles_f64_host")
+    return vt
+
+
+def _cov_vehicle(cache, vehicle, vtile, dense, B, K):
+    """vehicle= of the first-order analyses: None, or (mu [6], sp [6]) as montecarlo.vehicle_errors returns them; vtile: what
+    vehicle_tiles_batch returns, needed when sp[ISP] or sp[AERO] is not 0; dense: the call's, "sens" among its names asks for J_k
+    -> (sp or None, vtile or None, sens [B][K+1][n][6] or None, dense without "sens").  Every refusal of the library is a ValueError here."""
+    rest, want = dense, False
+    if not (dense is True or not dense):
+        names = {dense} if isinstance(dense, str) else set(dense)
+        want = "sens" in names
+        rest = tuple(n for n in names if n != "sens")
+    if vehicle is None:
+        if want or vtile is not None:
+            raise ValueError('dense "sens" and vtile= need vehicle=')
+        return None, None, None, rest
+    if not isinstance(vehicle, (tuple, list)) or len(vehicle) != 2:
+        raise ValueError("vehicle = (mu [6], sp [6]): montecarlo.vehicle_errors")
+    mu, sp = (np.ascontiguousarray(v, np.float64) for v in vehicle)
+    if mu.shape != (6,) or sp.shape != (6,):
+        raise ValueError("vehicle = (mu [6], sp [6]): montecarlo.vehicle_errors")
+    if np.any(mu != 0.0):
+        raise ValueError("vehicle: the first-order analyses are about the nominal vehicle, mu must be 0 (a mean shift is out of scope; "
+                         "the sampled calls fly one)")
+    if not (np.all(np.isfinite(sp)) and np.all(sp >= 0.0)):
+        raise ValueError("vehicle: sp must be finite and >= 0")
+    if sp[_lib.VEH_INDEX["FIN"]] != 0.0 and cache.nu != 5:
+        raise ValueError("vehicle: sp[FIN] != 0 on a model without fins")
+    if sp[_lib.VEH_INDEX["AERO"]] != 0.0 and not isinstance(cache.problem.aero, AtmosphericData):
+        raise ValueError("vehicle: sp[AERO] != 0 on a model without aerodynamics")
+    vt = None
+    if vtile is not None:
+        vt = np.ascontiguousarray(vtile, np.float64)
+        if vt.shape != (B, K, _lib.VTILE_N, 14):
+            raise ValueError("shape mismatch: vtile [B][K][%d][14] (vehicle_tiles_batch)" % _lib.VTILE_N)
+    elif sp[_lib.VEH_INDEX["ISP"]] != 0.0 or sp[_lib.VEH_INDEX["AERO"]] != 0.0:
+        raise ValueError("vehicle: sp[ISP] or sp[AERO] != 0 needs vtile= (vehicle_tiles_batch)")
+    sens = np.empty((B, K + 1, 14 + cache.nu, _lib.VEH_N)) if want else None
+    return sp, vt, sens, rest
+
+
 class CovReport:
     """The dispersion report of a covariance analysis (scvx_cov_propagate_f64, include/scvx.h): `raw` [B][16], one named numpy view
     per column (report.SIG_R, report.N_TMIN, ... -- _lib.COV_COLUMNS), and the optional dense outputs `sig` [B][K+1][14+nu] (the
@@ -254,11 +309,12 @@ class CovReport:
 
     N_COLUMNS = tuple(n for n in _lib.COV_COLUMNS if n.startswith("N_"))
 
-    def __init__(self, raw, sig=None, covK=None, cov=None):
+    def __init__(self, raw, sig=None, covK=None, cov=None, sens=None):
         self.raw = np.asarray(raw, np.float64).reshape(-1, _lib.COV_NREP)
         self.sig = sig
         self.covK = covK
         self.cov = cov
+        self.sens = sens   # vehicle= with dense "sens": J_k = d z_k / d theta [B][K+1][n][6], else None
         for name, i in _lib.COV_INDEX.items():
             setattr(self, name, self.raw[:, i])
 
@@ -305,12 +361,15 @@ def _cov_dense(dense):
     return want
 
 
-def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, dense=False) -> CovReport:
+def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, dense=False, vehicle=None, vtile=None) -> CovReport:
     """Closed-loop covariance of the plans x [B][K+1][14], u [B][K+1][nu] tracked under the gains gain [B][K][nu][14+nu] (what
     track_gains_batch returns) from the derivative tiles deriv [B][K][14+2nu+1][14] (what linearize_batch returns), on the device
     (scvx_cov_propagate_f64_host; the recursion and its limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one
     [14][14] for all, or a [14] vector of standard deviations; only its symmetric part is used.  w: process-noise variance added per
-    segment, a scalar or [14] (None = 0).  dense: True for sig, covK and cov, or a subset of those names."""
+    segment, a scalar or [14] (None = 0).  dense: True for sig, covK and cov, or a subset of those names.
+    vehicle: (mu, sp) of montecarlo.vehicle_errors with mu = 0 -- every output is then read off Sigma_k + J_k diag(sp^2) J_k'
+    (scvx_cov_vehicle_f64_host; first order, the thrust columns are the command's), vtile: vehicle_tiles_batch's, needed when ISP or
+    AERO is dispersed; dense may then name "sens" (report.sens = J_k).  Without vehicle the call is the one it was."""
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     gain = np.ascontiguousarray(gain, np.float64)
@@ -327,22 +386,29 @@ def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, d
         raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
     s0 = _cov_s0(S0, B)
     wv = _cov_noise(w)
+    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
     want = _cov_dense(dense)
     rep = np.empty((B, _lib.COV_NREP))
     sig = np.empty((B, K1, n)) if "sig" in want else None
     covK = np.empty((B, n, n)) if "covK" in want else None
     cov = np.empty((B, K1, n, n)) if "cov" in want else None
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    if sp is not None:
+        _lib.check(cache.handle, cache._L.scvx_cov_vehicle_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
+                                                                    _p(rep), None, opt(sig), opt(covK), opt(cov), opt(vt), _p(sp),
+                                                                    opt(sens)), "scvx_cov_vehicle_f64_host")
+        return CovReport(rep, sig, covK, cov, sens)
     _lib.check(cache.handle, cache._L.scvx_cov_propagate_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
                                                                   _p(rep), opt(sig), opt(covK), opt(cov)), "scvx_cov_propagate_f64_host")
     return CovReport(rep, sig, covK, cov)
 
 
-def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None):
+def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, vehicle=None, vtile=None, dense=()):
     """What the margins of cov_propagate_batch are made of (scvx_cov_path_sigma_f64_host; same arguments): (CovReport, psig) with psig
     [B][K+1][5] = s = sqrt(c' Sigma_k c) at every node for the path functions of the mass, glide-slope, tilt and rate margins and of the
     thrust norm (_lib.PSIG_COLUMNS).  Node 0 and a node its margin skips are 0; a non-finite tile, gain or S0 entry makes the rows of
-    its own trajectory NaN.  psig[:, :, 4] is the s_T(k) that ScvxBatch.robustify turns into back-offs of the thrust band."""
+    its own trajectory NaN.  psig[:, :, 4] is the s_T(k) that ScvxBatch.robustify turns into back-offs of the thrust band.
+    vehicle, vtile: as cov_propagate_batch (psig and the report are then read off Sigma_k^tot); dense: () or ("sens",)."""
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     gain = np.ascontiguousarray(gain, np.float64)
@@ -359,8 +425,17 @@ def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None):
         raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
     s0 = _cov_s0(S0, B)
     wv = _cov_noise(w)
+    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
+    if dense:
+        raise ValueError('dense: () or ("sens",), not %r' % (dense,))
     rep = np.empty((B, _lib.COV_NREP))
     psig = np.empty((B, K1, _lib.PSIG_N))
+    if sp is not None:
+        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        _lib.check(cache.handle, cache._L.scvx_cov_vehicle_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
+                                                                    _p(rep), _p(psig), None, None, None, opt(vt), _p(sp), opt(sens)),
+                   "scvx_cov_vehicle_f64_host")
+        return CovReport(rep, sens=sens), psig
     _lib.check(cache.handle, cache._L.scvx_cov_path_sigma_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0),
                                                                    _p(wv) if wv is not None else None, _p(rep), _p(psig)),
                "scvx_cov_path_sigma_f64_host")
@@ -679,8 +754,8 @@ class NavReport(CovReport):
     [B][K+1][14] (the 1 sigma of the navigation error before the update at each node), `kf` [B][K][14][m] (the filter gains) and
     `joint` [B][K+1][N][N], N = 14 + nu + 14 (the covariance of [z; eps] before the update at each node), or None."""
 
-    def __init__(self, raw, navraw, sig=None, navsig=None, kf=None, joint=None):
-        super().__init__(raw, sig)
+    def __init__(self, raw, navraw, sig=None, navsig=None, kf=None, joint=None, sens=None):
+        super().__init__(raw, sig, sens=sens)
         self.navraw = np.asarray(navraw, np.float64).reshape(-1, _lib.NAV_NREP)
         self.navsig = navsig
         self.kf = kf
@@ -718,13 +793,16 @@ def _nav_dense(dense):
     return want
 
 
-def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None, dense=False) -> NavReport:
+def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None, dense=False, vehicle=None, vtile=None) -> NavReport:
     """Covariance of the closed loop flown on a navigation ESTIMATE: the joint of the truth dispersion z and the navigation error eps
     of the plans x, u tracked under `gain` from the tiles `deriv` (all as cov_propagate_batch), on the device (scvx_nav_cov_f64_host;
     the recursion and its limits are in include/scvx.h).  S0: the handover covariance of the truth, N0: that of the navigation error
     (each [B][14][14], one [14][14], or a [14] vector of standard deviations).  H [m][14] (montecarlo.measurement_rows) and rm (variances, a
     scalar or [m]): the measurement taken at every node but the last; H None: inertial propagation only.  w: process-noise variance per
-    segment, which moves the truth and is missed by the estimate alike.  dense: True for sig, navsig, kf and joint, or a subset."""
+    segment, which moves the truth and is missed by the estimate alike.  dense: True for sig, navsig, kf and joint, or a subset.
+    vehicle, vtile: as cov_propagate_batch (scvx_nav_cov_vehicle_f64_host): J_k diag(sp^2) J_k' is added to the truth block wherever
+    the report, sig and joint read it; the eps blocks, navsig, kf and NAV_* are untouched -- the filter does not know theta -- and
+    EST_R / EST_V receive it in their truth term.  dense may then name "sens"."""
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     gain = np.ascontiguousarray(gain, np.float64)
@@ -742,6 +820,7 @@ def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=No
     s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
     m, Hm, rv = _nav_model(H, rm)
     wv = _cov_noise(w)
+    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
     want = _nav_dense(dense)
     rep, navrep = np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.NAV_NREP))
     sig = np.empty((B, K1, n)) if "sig" in want else None
@@ -749,6 +828,11 @@ def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=No
     kf = np.empty((B, K, 14, m)) if "kf" in want else None
     joint = np.empty((B, K1, n + 14, n + 14)) if "joint" in want else None
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    if sp is not None:
+        _lib.check(cache.handle, cache._L.scvx_nav_cov_vehicle_f64_host(
+            cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), None,
+            opt(sig), opt(navsig), opt(kf), opt(joint), opt(vt), _p(sp), opt(sens)), "scvx_nav_cov_vehicle_f64_host")
+        return NavReport(rep, navrep, sig, navsig, kf, joint, sens)
     _lib.check(cache.handle, cache._L.scvx_nav_cov_f64_host(
         cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), opt(sig),
         opt(navsig), opt(kf), opt(joint)), "scvx_nav_cov_f64_host")
@@ -903,11 +987,12 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     return McNavReport(*red, *dn)._with_q(mq)._with_veh(vh)
 
 
-def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None):
+def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None, vehicle=None, vtile=None, dense=()):
     """What the margins of nav_cov_batch are made of (scvx_nav_path_sigma_f64_host; same arguments without dense): (NavReport, psig) with
     psig [B][K+1][5] as cov_path_sigma_batch, read off the TRUTH block of the joint covariance before the update at each node -- the
     constraints bind the vehicle, not its estimate.  Node 0 and a node its margin skips are 0; a non-finite tile, gain, S0 or N0 entry
-    makes the rows of its own trajectory NaN.  With N0 = 0 this is cov_path_sigma_batch's psig to rounding."""
+    makes the rows of its own trajectory NaN.  With N0 = 0 this is cov_path_sigma_batch's psig to rounding.
+    vehicle, vtile: as nav_cov_batch (psig and the report are then read off the truth block + J_k diag(sp^2) J_k'); dense: () or ("sens",)."""
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     gain = np.ascontiguousarray(gain, np.float64)
@@ -925,9 +1010,17 @@ def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, r
     s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
     m, Hm, rv = _nav_model(H, rm)
     wv = _cov_noise(w)
+    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
+    if dense:
+        raise ValueError('dense: () or ("sens",), not %r' % (dense,))
     rep, navrep = np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.NAV_NREP))
     psig = np.empty((B, K1, _lib.PSIG_N))
     opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+    if sp is not None:
+        _lib.check(cache.handle, cache._L.scvx_nav_cov_vehicle_f64_host(
+            cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep),
+            _p(psig), None, None, None, None, opt(vt), _p(sp), opt(sens)), "scvx_nav_cov_vehicle_f64_host")
+        return NavReport(rep, navrep, sens=sens), psig
     _lib.check(cache.handle, cache._L.scvx_nav_path_sigma_f64_host(
         cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), _p(psig)),
         "scvx_nav_path_sigma_f64_host")

@@ -112,11 +112,13 @@ def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None
                           vehicle=vehicle)
 
 
-def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False):
+def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False,
+               vehicle=None):
     """Closed-loop covariance analysis of an iterate's plan tracked under the time-varying LQR gains about it, from the handover
     covariance S0 ([14][14], or a [14] vector of standard deviations) with the per-segment process noise w (dynamics.track_gains_batch
-    on the plan's own linearisation, dynamics.cov_propagate_batch).  A dynamics.CovReport of one row."""
-    from .dynamics import cov_propagate_batch, linearize_batch, track_gains_batch
+    on the plan's own linearisation, dynamics.cov_propagate_batch).  A dynamics.CovReport of one row.  vehicle = (mu, sp) of
+    montecarlo.vehicle_errors, mu = 0: the vehicle errors as consider parameters (dynamics.vehicle_tiles_batch on the plan)."""
+    from .dynamics import cov_propagate_batch, linearize_batch, track_gains_batch, vehicle_tiles_batch
     if S0 is None:
         raise ValueError("covariance: S0 (the handover covariance) is required")
     cache = cache if cache is not None else iteration.cache
@@ -125,36 +127,38 @@ def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
     sigma = np.array([float(iteration.sigma)])
     _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
     gain = track_gains_batch(cache, deriv, q, r, qf)
-    return cov_propagate_batch(cache, x, u, deriv, gain, S0, w, dense=dense)
+    kw = {} if vehicle is None else dict(vehicle=vehicle, vtile=vehicle_tiles_batch(cache, x, u, sigma))
+    return cov_propagate_batch(cache, x, u, deriv, gain, S0, w, dense=dense, **kw)
 
 
 def robustify(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, nsigma=3.0, rounds=1, cap=0.25, w=None, q=None,
-              r=None, qf=None, constraints=("thrust",), nav=None, mc=None):
+              r=None, qf=None, constraints=("thrust",), nav=None, mc=None, vehicle=None):
     """Replan an iterate under back-offs of the thrust band taken from its own covariance analysis (ScvxBatch.robustify on the
     iterate's device batch): Tmin + n s_T(k) <= |u_k| <= Tmax - n s_T(k).  Returns (the new ProblemIteration, lo [K+1], hi [K+1]);
     raises like solve_step when the conic solve fails.  The limits are those of ScvxBatch.robustify.  constraints: any subset of
     ("thrust", "mass", "glide", "tilt", "rate") or "all"; the path back-offs that were used are iteration.model.path_margins().
     nav = (N0, H, rm): the back-offs come from the navigation analysis of the iterate (navigation()'s model), the law fed an estimate.
     mc = dict(p=, samples=, seed=, clamp=): they come from the sampled closed loop instead (ScvxBatch.margins_from_mc, its limits);
-    with nav the flights are flown on the estimate."""
+    with nav the flights are flown on the estimate.  vehicle = (mu, sp), mu = 0: the covariance or navigation path with the vehicle
+    errors as consider parameters (ScvxBatch.robustify's keyword; not with mc, which has its own)."""
     if S0 is None:
         raise ValueError("robustify: S0 (the handover covariance) is required")
     cache = cache if cache is not None else iteration.cache
     batch = iteration.model
     st, it, nu, dj, lo, hi = batch.robustify(S0, nsigma=nsigma, rounds=rounds, cap=cap, w=w, q=q, r=r, qf=qf, constraints=constraints,
-                                             nav=nav, mc=mc)
+                                             nav=nav, mc=mc, vehicle=vehicle)
     if st[0] in (3, 4, 5):  # rocketland.jl:273-276
         raise RuntimeError("Non-optimal result %s exiting" % {3: "SLOW_PROGRESS", 4: "NUMERICAL_ERROR", 5: "INFEASIBLE"}[int(st[0])])
     return _snapshot(iteration.problem, cache, batch), lo[0], hi[0]
 
 
 def navigation(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, N0=None, H=None, rm=None, w=None, q=None, r=None,
-               qf=None, dense=False):
+               qf=None, dense=False, vehicle=None):
     """Navigation-error covariance analysis of an iterate's plan flown on an estimate under the time-varying LQR gains about it: S0 the
     handover covariance of the truth, N0 that of the navigation error, H [m][14] and rm the measurement taken at every node but the
     last (H None: inertial propagation only), w the per-segment process noise (dynamics.track_gains_batch on the plan's own
-    linearisation, dynamics.nav_cov_batch).  A dynamics.NavReport of one row."""
-    from .dynamics import linearize_batch, nav_cov_batch, track_gains_batch
+    linearisation, dynamics.nav_cov_batch).  A dynamics.NavReport of one row.  vehicle = (mu, sp), mu = 0: as covariance()."""
+    from .dynamics import linearize_batch, nav_cov_batch, track_gains_batch, vehicle_tiles_batch
     if S0 is None or N0 is None:
         raise ValueError("navigation: S0 and N0 (the handover covariances of the truth and of the navigation error) are required")
     cache = cache if cache is not None else iteration.cache
@@ -163,7 +167,8 @@ def navigation(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
     sigma = np.array([float(iteration.sigma)])
     _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
     gain = track_gains_batch(cache, deriv, q, r, qf)
-    return nav_cov_batch(cache, x, u, deriv, gain, S0, N0, H, rm, w, dense=dense)
+    kw = {} if vehicle is None else dict(vehicle=vehicle, vtile=vehicle_tiles_batch(cache, x, u, sigma))
+    return nav_cov_batch(cache, x, u, deriv, gain, S0, N0, H, rm, w, dense=dense, **kw)
 
 
 def run_iters(iprob: DescentProblem, niters: int, cache: IntegratorCache = None):
