@@ -1012,48 +1012,34 @@ int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU
     return s.finish("scvx_batch_track_fly_nav");
 }
 
-int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                        const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
-                        double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0) {
-    return scvx_batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland,
-                                 dx0, 0, nullptr, nullptr, nullptr, nullptr);
-}
-
-// scvx_batch_track_mc_q and, with rg (then xi0 and eta are placeholders, nothing of them is uploaded), scvx_batch_track_mc_rng
-static int batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                            const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
-                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
-                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx::McRng* rg,
-                            const scvx::McVeh* vh = nullptr, const char* entry = "scvx_batch_track_mc_q") {
+// The eight batch-level forms of the sampled dispersion: the record of scvx_mc.hpp with the plan, the gains and the tiles the batch's own.
+// Every check comes before anything is enqueued.  With nav the filter gains kf are written first, by the navigation launch with the
+// same N0, H, rm and w; Kf does not depend on S0, which is zero here.
+static int batch_track_mc_call(scvx_batch* b, scvx::McCall c, const scvx::McBatch& own, const char* entry) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
-    if (nsub == 0) nsub = ctx->nsub;
-    // every check before anything is enqueued; the outputs are optional here, so a placeholder stands in for them
-    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
-    if ((rc = scvx::check_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->x, C0, xi0, eta, sw14, reserved, nsub, flags, tol, b->x,
-                                   b->x, b->x)))
-        return rc;
-    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
-    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
-    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
-    if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const scvx::Dims d(b->B, b->K, b->NU, S, 0, nq);
+    c.B = b->B, c.K = b->K;
+    if (c.nsub == 0) c.nsub = ctx->nsub;
+    if ((rc = scvx::check_mc_call(ctx, c, &own))) return rc;
+    if ((rc = enqueue_track_gains(b, own.q14, own.rNU, own.qf14))) return rc;
+    const scvx::Dims d(c.B, c.K, b->NU, c.S, c.m, c.q.nq);
     scvx::Staging s(ctx);
-    scvx::McVeh dvh;   // the vehicle errors with zeta and theta on the device
-    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
-    const double* dc = s.in(C0, d.c14);
-    scvx::McQ mq;
-    mq.nq = nq, mq.ranks = ranks, mq.flightq = s.out(flightq, d.flightq), mq.pathq = s.out(pathq, d.pathq), mq.pathv = s.out(pathv, d.pathv);
-    const double *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta);
-    double *dr = s.out_always(mcrep, d.mcrep), *dm = s.out_always(xmean, d.b14), *dv = s.out_always(xcov, d.c14),
-           *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14);
-    s.launch([&] {
-        return scvx::launch_track_mc(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->track_gain, dc, di, de, sw14, nsub, flags, tol, dr, dm, dv, df,
-                                     dl, d0, s.st, (flightq || pathq || pathv) ? &mq : nullptr, rg, vh ? &dvh : nullptr);
-    });
+    const double* dn0 = c.nav ? s.in(own.N0, d.c14) : nullptr;
+    double *dk = c.nav && c.m > 0 ? s.tmp(d.kf) : nullptr, *dz = nullptr, *dcr = nullptr, *dnr = nullptr;
+    if (c.nav) dz = s.tmp(d.c14), dcr = s.tmp(d.crep), dnr = s.tmp(d.nrep);
+    scvx::McCall dev = scvx::stage_mc(s, d, c, true);
+    dev.x = b->x, dev.u = b->u, dev.sigma = b->sigma, dev.gain = b->track_gain;
+    if (c.nav) {
+        dev.deriv = b->tiles(), dev.kf = dk;
+        s.launch([&] { return hipMemsetAsync(dz, 0, d.c14 * 8, s.st); });
+        if (c.m > 0)
+            s.launch([&] {
+                return scvx::launch_nav_cov(ctx, c.B, c.K, b->x, b->u, b->tiles(), b->track_gain, dz, dn0, c.m, c.H, c.rm, c.w, dcr, dnr,
+                                            nullptr, nullptr, dk, nullptr, s.st);
+            });
+    }
+    s.launch([&] { return scvx::launch_mc(ctx, dev, s.st); });
     return s.finish(entry);
 }
 
@@ -1061,80 +1047,40 @@ int scvx_batch_track_mc_q(scvx_batch* b, const double* q14, const double* rNU, c
                           const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
                           const int* ranks, double* flightq, double* pathq, double* pathv) {
-    return batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland, dx0,
-                            nq, ranks, flightq, pathq, pathv, nullptr);
+    scvx::McCall c;
+    c.S = S, c.C0 = C0, c.w = sw14, c.reserved = reserved, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean;
+    c.xcov = xcov, c.flights = flights, c.xland = xland, c.dx0 = dx0, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta;
+    return batch_track_mc_call(b, c, {q14, rNU, qf14, nullptr}, "scvx_batch_track_mc_q");
 }
 
 int scvx_batch_track_mc_rng(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
                             const scvx_mc_rng* rng, int noise, const double* sw14, const void* reserved, int nsub, int flags, double tol,
                             double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
                             const int* ranks, double* flightq, double* pathq, double* pathv) {
-    const scvx::McRng rg{rng, noise};
-    return batch_track_mc_q(b, q14, rNU, qf14, S, C0, C0, noise ? C0 : nullptr, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
-                            flights, xland, dx0, nq, ranks, flightq, pathq, pathv, &rg);
+    scvx::McCall c;
+    c.S = S, c.C0 = C0, c.w = sw14, c.reserved = reserved, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean;
+    c.xcov = xcov, c.flights = flights, c.xland = xland, c.dx0 = dx0, c.q = {nq, ranks, flightq, pathq, pathv}, c.drawn = true;
+    c.rng = rng, c.noise = noise;
+    return batch_track_mc_call(b, c, {q14, rNU, qf14, nullptr}, "scvx_batch_track_mc_rng");
 }
 
-int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                            const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
-                            const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags, double tol,
-                            double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav, double* flights,
-                            double* xland, double* dx0, double* navfed, double* navK) {
-    return scvx_batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean,
-                                     xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr, nullptr, nullptr, nullptr);
+int scvx_batch_track_mc_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                            const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags,
+                            double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
+                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx_mc_rng* rng, int noise,
+                            const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
+    scvx::McCall c;
+    c.S = S, c.C0 = C0, c.w = sw14, c.reserved = reserved, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean;
+    c.xcov = xcov, c.flights = flights, c.xland = xland, c.dx0 = dx0, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta;
+    c.drawn = rng != nullptr, c.rng = rng, c.noise = noise, c.veh = {veh, zeta, theta};
+    return batch_track_mc_call(b, c, {q14, rNU, qf14, nullptr}, "scvx_batch_track_mc_veh");
 }
 
-// scvx_batch_track_mc_nav_q and, with rg (then xi0, eta, xin and nud are placeholders), scvx_batch_track_mc_nav_rng
-static int batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                                const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN,
-                                const double* xin, const double* nud, int m, const double* H, const double* rm, int nsub, int flags,
-                                double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
-                                double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
-                                double* flightq, double* pathq, double* pathv, const scvx::McRng* rg,
-                                const scvx::McVeh* vh = nullptr, const char* entry = "scvx_batch_track_mc_nav_q") {
-    int rc = check_batch(b, true);
-    if (rc) return rc;
-    scvx_ctx* ctx = b->ctx;
-    if (nsub == 0) nsub = ctx->nsub;
-    // every check before anything is enqueued; the tiles and the outputs are the batch's or optional, so a placeholder stands in for
-    // them, and for kf, which the navigation launch below writes
-    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
-    if ((rc = scvx::check_track_mc_nav(ctx, b->B, b->K, S, b->x, b->u, b->sigma, b->x, C0, xi0, eta, w14, b->x, b->x, CN, xin, nud, m, H, rm,
-                                       nsub, flags, tol, b->x, b->x, b->x, b->x, b->x, b->x)))
-        return rc;
-    if (!N0) return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (N0)");
-    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
-    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
-    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
-    if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const int B = b->B, K = b->K;
-    const scvx::Dims d(B, K, b->NU, S, m, nq);
-    scvx::Staging s(ctx);
-    scvx::McVeh dvh;   // the vehicle errors with zeta and theta on the device
-    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
-    const double *dc = s.in(C0, d.c14), *dn0 = s.in(N0, d.c14), *dcn = s.in(CN, d.c14), *di = s.in(xi0, d.xi), *dxi = s.in(xin, d.xi),
-                 *de = s.in(eta, d.eta), *dnu = s.in(m > 0 ? nud : nullptr, d.nud);
-    // the filter gains, written by the navigation launch with the same N0, H, rm and w; Kf does not depend on S0, which is zero here
-    double *dk = m > 0 ? s.tmp(d.kf) : nullptr, *dz = s.tmp(d.c14), *dcr = s.tmp(d.crep), *dnr = s.tmp(d.nrep);
-    double *dr = s.out_always(mcrep, d.mcrep), *dm = s.out_always(xmean, d.b14), *dv = s.out_always(xcov, d.c14),
-           *djm = s.out_always(jmean, d.jmean), *djc = s.out_always(jcov, d.jcov), *dnv = s.out_always(mcnav, d.nrep),
-           *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14), *dfe = s.out(navfed, d.fed),
-           *dnk = s.out(navK, d.s14);
-    scvx::McQ mq;
-    mq.nq = nq, mq.ranks = ranks, mq.flightq = s.out(flightq, d.flightq), mq.pathq = s.out(pathq, d.pathq), mq.pathv = s.out(pathv, d.pathv);
-    s.launch([&] { return hipMemsetAsync(dz, 0, d.c14 * 8, s.st); });
-    if (m > 0)
-        s.launch([&] {
-            return scvx::launch_nav_cov(ctx, B, K, b->x, b->u, b->tiles(), b->track_gain, dz, dn0, m, H, rm, w14, dcr, dnr, nullptr, nullptr, dk,
-                                        nullptr, s.st);
-        });
-    s.launch([&] {
-        return scvx::launch_track_mc_nav(ctx, B, K, S, b->x, b->u, b->sigma, b->track_gain, dc, di, de, w14, b->tiles(), dk, dcn, dxi, dnu, m, H,
-                                         rm, nsub, flags, tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st,
-                                         (flightq || pathq || pathv) ? &mq : nullptr, rg, vh ? &dvh : nullptr);
-    });
-    return s.finish(entry);
+int scvx_batch_track_mc(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                        const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
+                        double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0) {
+    return scvx_batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland,
+                                 dx0, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1143,8 +1089,12 @@ int scvx_batch_track_mc_nav_q(scvx_batch* b, const double* q14, const double* rN
                               double tol, double* mcrep, double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav,
                               double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
                               double* flightq, double* pathq, double* pathv) {
-    return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean, xcov,
-                                jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv, nullptr);
+    scvx::McCall c;
+    c.nav = true, c.S = S, c.C0 = C0, c.w = w14, c.CN = CN, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol;
+    c.mcrep = mcrep, c.xmean = xmean, c.xcov = xcov, c.jmean = jmean, c.jcov = jcov, c.mcnav = mcnav, c.flights = flights, c.xland = xland;
+    c.dx0 = dx0, c.navfed = navfed, c.navK = navK, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta, c.xin = xin;
+    c.nud = nud;
+    return batch_track_mc_call(b, c, {q14, rNU, qf14, N0}, "scvx_batch_track_mc_nav_q");
 }
 
 int scvx_batch_track_mc_nav_rng(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1152,25 +1102,11 @@ int scvx_batch_track_mc_nav_rng(scvx_batch* b, const double* q14, const double* 
                                 const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
                                 double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                 double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
-    const scvx::McRng rg{rng, noise};
-    return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, C0, noise ? C0 : nullptr, w14, N0, CN, C0, C0, m, H, rm, nsub, flags, tol, mcrep,
-                                xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv, &rg);
-}
-
-// the _veh forms: the _q call (rng == NULL) or the _rng call (its placeholders as above) with the vehicle errors behind it
-int scvx_batch_track_mc_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
-                            const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub, int flags, double tol,
-                            double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, int nq,
-                            const int* ranks, double* flightq, double* pathq, double* pathv, const scvx_mc_rng* rng, int noise,
-                            const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
-    int rc = check_batch(b, true);
-    if (rc) return rc;
-    if ((rc = scvx::check_mc_veh_draws(b->ctx, rng, noise, xi0, eta, nullptr, nullptr, zeta))) return rc;
-    const scvx::McRng rg{rng, noise};
-    const scvx::McVeh vh{veh, zeta, theta};
-    if (rng) xi0 = C0, eta = noise ? C0 : nullptr;
-    return batch_track_mc_q(b, q14, rNU, qf14, S, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov, flights, xland, dx0,
-                            nq, ranks, flightq, pathq, pathv, rng ? &rg : nullptr, &vh, "scvx_batch_track_mc_veh");
+    scvx::McCall c;
+    c.nav = true, c.S = S, c.C0 = C0, c.w = w14, c.CN = CN, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol;
+    c.mcrep = mcrep, c.xmean = xmean, c.xcov = xcov, c.jmean = jmean, c.jcov = jcov, c.mcnav = mcnav, c.flights = flights, c.xland = xland;
+    c.dx0 = dx0, c.navfed = navfed, c.navK = navK, c.q = {nq, ranks, flightq, pathq, pathv}, c.drawn = true, c.rng = rng, c.noise = noise;
+    return batch_track_mc_call(b, c, {q14, rNU, qf14, N0}, "scvx_batch_track_mc_nav_rng");
 }
 
 int scvx_batch_track_mc_nav_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
@@ -1180,15 +1116,21 @@ int scvx_batch_track_mc_nav_veh(scvx_batch* b, const double* q14, const double* 
                                 double* flights, double* xland, double* dx0, double* navfed, double* navK, int nq, const int* ranks,
                                 double* flightq, double* pathq, double* pathv, const scvx_mc_rng* rng, int noise,
                                 const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
-    int rc = check_batch(b, true);
-    if (rc) return rc;
-    if ((rc = scvx::check_mc_veh_draws(b->ctx, rng, noise, xi0, eta, xin, nud, zeta))) return rc;
-    const scvx::McRng rg{rng, noise};
-    const scvx::McVeh vh{veh, zeta, theta};
-    if (rng) xi0 = xin = nud = C0, eta = noise ? C0 : nullptr;
-    return batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean, xcov,
-                                jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq, pathv,
-                                rng ? &rg : nullptr, &vh, "scvx_batch_track_mc_nav_veh");
+    scvx::McCall c;
+    c.nav = true, c.S = S, c.C0 = C0, c.w = w14, c.CN = CN, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol;
+    c.mcrep = mcrep, c.xmean = xmean, c.xcov = xcov, c.jmean = jmean, c.jcov = jcov, c.mcnav = mcnav, c.flights = flights, c.xland = xland;
+    c.dx0 = dx0, c.navfed = navfed, c.navK = navK, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta, c.xin = xin;
+    c.nud = nud, c.drawn = rng != nullptr, c.rng = rng, c.noise = noise, c.veh = {veh, zeta, theta};
+    return batch_track_mc_call(b, c, {q14, rNU, qf14, N0}, "scvx_batch_track_mc_nav_veh");
+}
+
+int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, int S, const double* C0,
+                            const double* xi0, const double* eta, const double* w14, const double* N0, const double* CN, const double* xin,
+                            const double* nud, int m, const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep,
+                            double* xmean, double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland,
+                            double* dx0, double* navfed, double* navK) {
+    return scvx_batch_track_mc_nav_q(b, q14, rNU, qf14, S, C0, xi0, eta, w14, N0, CN, xin, nud, m, H, rm, nsub, flags, tol, mcrep, xmean,
+                                     xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int scvx_batch_nav_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0,

@@ -99,36 +99,11 @@ int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const d
 int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
                     const void* report);
 
-struct McQ;   // what the _q forms add to a sampled call (scvx_mc.hpp); nullptr: nothing, the instantiations without per-node samples
-struct McRng; // the _rng forms (scvx_mc.hpp): the draws are made on the device; nullptr: the uploaded draws, the instantiations without RNG
 struct CovVeh; // the _vehicle forms of the covariance and navigation analyses (below); nullptr: the plain call
-struct McVeh; // the _veh forms (scvx_mc.hpp): per-flight vehicle errors; nullptr: the nominal vehicle, the instantiations without ACT
 
-// Sampled dispersion (scvx_mc.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan; C0[B][14][14],
-// xi0[S][14], eta[S][K][14] or nullptr, sw: host array of 14 or nullptr; mcrep[B][SCVX_MC_NREP], xmean[B][14], xcov[B][14][14];
-// flights[B][S][16], xland[B][S][14], dx0[B][S][14] or nullptr.  The partial rows live in ctx->mc_ws.
-hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
-                           const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
-                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
-                           const McQ* q = nullptr, const McRng* rng = nullptr, const McVeh* veh = nullptr);
-int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain, const void* C0,
-                   const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
-                   const void* mcrep, const void* xmean, const void* xcov);
+// Sampled dispersion (scvx_mc.hip, scvx_mc_nav.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan.
+// Every form goes through one record, one check, one staging and one launch: scvx_mc.hpp.  The partial rows live in ctx->mc_ws.
 void mc_workspace_free(scvx_ctx* ctx);
-// The same flown on a navigation estimate (scvx_mc_nav.hip): deriv[B][K][14+2NU+1][14], kf[B][K][14][m] (nullptr with
-// m = 0), CN[B][14][14], xin[S][14], nud[S][K][m] (nullptr with m = 0); w, H, rm: host arrays (w the VARIANCE) or nullptr; jmean[B][28],
-// jcov[B][28][28], mcnav[B][SCVX_NAV_NREP]; navfed[B][S][K][14], navK[B][S][14] or nullptr.
-hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w, Tiles deriv,
-                               const double* kf, const double* CN, const double* xin, const double* nud, int m, const double* H,
-                               const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
-                               double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
-                               double* navK, hipStream_t st, const McQ* q = nullptr, const McRng* rng = nullptr, const McVeh* veh = nullptr);
-int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
-                       const void* C0, const void* xi0, const void* eta, const double* w, const void* deriv, const void* kf,
-                       const void* CN, const void* xin, const void* nud, int m, const double* H, const double* rm, int nsub, int flags,
-                       double tol, const void* mcrep, const void* xmean, const void* xcov, const void* jmean, const void* jcov,
-                       const void* mcnav);
 
 // Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles and the gains; S0[B][14][14]; w: host
 // array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.  With psig

@@ -53,24 +53,15 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(int S, int K, int nblk, 
     mc_finish_front<MC_NP>(S, K, nblk, part, sh, mcrep, xmean, xcov);
 }
 
-// the context's workspace of partial rows, grown on demand (hipFree waits for whatever still reads the old one)
-hipError_t mc_workspace(scvx_ctx* ctx, size_t doubles) {
-    if (ctx->mc_ws_doubles >= doubles) return hipSuccess;
-    if (ctx->mc_ws) (void)hipFree(ctx->mc_ws);
-    ctx->mc_ws = nullptr;
-    ctx->mc_ws_doubles = 0;
-    hipError_t e = hipMalloc((void**)&ctx->mc_ws, doubles * 8);
-    if (e == hipSuccess) ctx->mc_ws_doubles = doubles;
-    return e;
-}
-
-hipError_t mc_q_workspace(scvx_ctx* ctx, size_t doubles) {
-    if (ctx->mcq_ws_doubles >= doubles) return hipSuccess;
-    if (ctx->mcq_ws) (void)hipFree(ctx->mcq_ws);
-    ctx->mcq_ws = nullptr;
-    ctx->mcq_ws_doubles = 0;
-    hipError_t e = hipMalloc((void**)&ctx->mcq_ws, doubles * 8);
-    if (e == hipSuccess) ctx->mcq_ws_doubles = doubles;
+// a workspace of the context (the partial rows; the dense values of a _q call), grown on demand: hipFree waits for whatever still reads
+// the old one.  No two calls on one context may overlap on different streams.
+static hipError_t mc_grow(double*& ws, size_t& have, size_t doubles) {
+    if (have >= doubles) return hipSuccess;
+    if (ws) (void)hipFree(ws);
+    ws = nullptr;
+    have = 0;
+    hipError_t e = hipMalloc((void**)&ws, doubles * 8);
+    if (e == hipSuccess) have = doubles;
     return e;
 }
 
@@ -83,29 +74,47 @@ void mc_workspace_free(scvx_ctx* ctx) {
     ctx->mcq_ws_doubles = 0;
 }
 
-// flights: the caller's dense buffer or nullptr on entry; on return where the flying kernel writes the flights (the workspace when
-// only their order statistics are asked for), and pathv likewise (nullptr: the instantiations without per-node samples)
-hipError_t mc_q_buffers(scvx_ctx* ctx, int B, int K, int S, const McQ& q, double*& flights, double*& pathv) {
-    pathv = q.pathv;
-    const size_t nf = (q.flightq && !flights) ? (size_t)B * S * SCVX_FLIGHT_NREP : 0;
-    const size_t np = (q.pathq && !q.pathv) ? (size_t)B * (K + 1) * SCVX_PSIG_N * S : 0;
+// flights and q.pathv: the caller's dense buffers or nullptr on entry; on return where the flying kernel writes them -- the second
+// workspace when only their order statistics are asked for (q.pathv == nullptr: the instantiations without per-node samples)
+static hipError_t mc_q_buffers(scvx_ctx* ctx, McCall& c) {
+    const size_t nf = (c.q.flightq && !c.flights) ? (size_t)c.B * c.S * SCVX_FLIGHT_NREP : 0;
+    const size_t np = (c.q.pathq && !c.q.pathv) ? (size_t)c.B * (c.K + 1) * SCVX_PSIG_N * c.S : 0;
     if (nf + np == 0) return hipSuccess;
-    hipError_t e = mc_q_workspace(ctx, nf + np);
+    hipError_t e = mc_grow(ctx->mcq_ws, ctx->mcq_ws_doubles, nf + np);
     if (e != hipSuccess) return e;
-    if (nf) flights = ctx->mcq_ws;
-    if (np) pathv = ctx->mcq_ws + nf;
+    if (nf) c.flights = ctx->mcq_ws;
+    if (np) c.q.pathv = ctx->mcq_ws + nf;
     return hipSuccess;
 }
 
 // the order statistics of the sixteen flight columns (rows of S values 16 apart) and of every (b, k, f) row of pathv (contiguous)
-hipError_t mc_q_finish(int B, int K, int S, const McQ& q, const double* flights, const double* pathv, hipStream_t st) {
+static hipError_t mc_q_finish(const McCall& c, hipStream_t st) {
     hipError_t e = hipSuccess;
-    if (q.flightq)
-        e = launch_order_stats(B * SCVX_FLIGHT_NREP, S, flights, (size_t)S * SCVX_FLIGHT_NREP, SCVX_FLIGHT_NREP, 1, SCVX_FLIGHT_NREP, q.nq,
-                               q.ranks, q.flightq, st);
-    if (e == hipSuccess && q.pathq)
-        e = launch_order_stats(B * (K + 1) * SCVX_PSIG_N, S, pathv, (size_t)S, 1, 0, 1, q.nq, q.ranks, q.pathq, st);
+    if (c.q.flightq)
+        e = launch_order_stats(c.B * SCVX_FLIGHT_NREP, c.S, c.flights, (size_t)c.S * SCVX_FLIGHT_NREP, SCVX_FLIGHT_NREP, 1,
+                               SCVX_FLIGHT_NREP, c.q.nq, c.q.ranks, c.q.flightq, st);
+    if (e == hipSuccess && c.q.pathq)
+        e = launch_order_stats(c.B * (c.K + 1) * SCVX_PSIG_N, c.S, c.q.pathv, (size_t)c.S, 1, 0, 1, c.q.nq, c.q.ranks, c.q.pathq, st);
     return e;
+}
+
+hipError_t launch_mc(scvx_ctx* ctx, const McCall& dev, hipStream_t st) {
+    McCall c = dev;   // flights, q.pathv and eta become what the flying kernel is given
+    const int nblk = (c.S + 63) / 64;
+    hipError_t e = mc_grow(ctx->mc_ws, ctx->mc_ws_doubles, (size_t)c.B * nblk * (c.nav ? MCN_NP : MC_NP) + (c.nav ? MCN_MODEL : 0));
+    if (e != hipSuccess || (e = mc_q_buffers(ctx, c)) != hipSuccess) return e;
+    McK m{};
+    m.tol = c.tol;
+    const McRngK rg = mc_noise(m, c);
+    if (c.nav) {
+        e = launch_mc_nav(ctx, c, m, rg, st);
+    } else {
+        e = launch_mc_fly<false, double>(ctx, c, m, rg, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(mc_finish_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.S, c.K, nblk, ctx->mc_ws, c.mcrep, c.xmean, c.xcov);
+        e = hipGetLastError();
+    }
+    return e != hipSuccess ? e : mc_q_finish(c, st);
 }
 
 int check_mc_rng(scvx_ctx* ctx, const scvx_mc_rng* rng) {
@@ -116,88 +125,112 @@ int check_mc_rng(scvx_ctx* ctx, const scvx_mc_rng* rng) {
     return SCVX_OK;
 }
 
-int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq) {
-    if (nq == 0 && !flightq && !pathq) return SCVX_OK;   // nothing asked for: the call it extends
-    return check_ranks(ctx, S, nq, ranks);
-}
-
-hipError_t launch_track_mc(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
-                           const double* C0, const double* xi0, const double* eta, const double* sw, int nsub, int flags, double tol,
-                           double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0, hipStream_t st,
-                           const McQ* q, const McRng* rng, const McVeh* veh) {
-    const int nblk = (S + 63) / 64;
-    hipError_t e = mc_workspace(ctx, (size_t)B * nblk * MC_NP);
-    if (e != hipSuccess) return e;
-    double* pv = nullptr;
-    if (q && (e = mc_q_buffers(ctx, B, K, S, *q, flights, pv)) != hipSuccess) return e;
-    McK m{};
-    m.tol = tol;
-    const McRngK rg = mc_noise(m, sw, false, eta, rng);
-    double* part = ctx->mc_ws;
-    e = launch_mc_fly<false>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng, rg, st,
-                             McNavA<double>{}, veh);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov);
-    e = hipGetLastError();
-    if (e != hipSuccess || !q) return e;
-    return mc_q_finish(B, K, S, *q, flights, pv, st);
-}
-
-int check_track_mc(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain, const void* C0,
-                   const void* xi0, const void* eta, const double* sw, const void* reserved, int nsub, int flags, double tol,
-                   const void* mcrep, const void* xmean, const void* xcov) {
+int check_mc_vehicle(scvx_ctx* ctx, const scvx_mc_vehicle* veh, const void* zeta, const void* theta, bool rng) {
     if (!ctx) return SCVX_ERR_ARG;
-    if (B < 1 || B > 65535) return fail(ctx, SCVX_ERR_ARG, "track mc: 1 <= B <= 65535 required");
-    if (S < 1) return fail(ctx, SCVX_ERR_ARG, "track mc: S >= 1 required");
-    if (K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "track mc: K must equal the problem's K");
-    if (nsub < 1 || nsub > 1000) return fail(ctx, SCVX_ERR_ARG, "track mc: nsub must be in [1,1000]");
-    if (flags & ~SCVX_TRACK_CLAMP) return fail(ctx, SCVX_ERR_ARG, "track mc: unknown flags (SCVX_TRACK_CLAMP)");
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(ctx, SCVX_ERR_ARG, "track mc: tol must be finite and >= 0");
-    if (sw)
-        for (int i = 0; i < 14; i++)
-            if (!(sw[i] >= 0.0) || !std::isfinite(sw[i])) return fail(ctx, SCVX_ERR_ARG, "track mc: sw must be finite and >= 0");
-    if (eta && !sw) return fail(ctx, SCVX_ERR_ARG, "track mc: eta without sw");
-    if (reserved) return fail(ctx, SCVX_ERR_ARG, "track mc: the reserved argument must be NULL");
-    if (!x || !u || !sigma || !gain || !C0 || !xi0 || !mcrep || !xmean || !xcov) return fail(ctx, SCVX_ERR_ARG, "track mc: null buffer");
+    if (!veh) {
+        if (zeta || theta) return fail(ctx, SCVX_ERR_ARG, "vehicle: zeta / theta without veh");
+        return SCVX_OK;
+    }
+    if (veh->reserved[0] != 0 || veh->reserved[1] != 0) return fail(ctx, SCVX_ERR_ARG, "vehicle: reserved must be 0");
+    bool drawn = false;
+    for (int i = 0; i < SCVX_VEH_N; i++) {
+        if (!std::isfinite(veh->mu[i])) return fail(ctx, SCVX_ERR_ARG, "vehicle: mu must be finite");
+        if (!(veh->sp[i] >= 0.0) || !std::isfinite(veh->sp[i])) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp must be finite and >= 0");
+        drawn = drawn || veh->sp[i] > 0.0;
+    }
+    if (!ctx->dyn.aero && (veh->mu[SCVX_VEH_AERO] != 0.0 || veh->sp[SCVX_VEH_AERO] != 0.0))
+        return fail(ctx, SCVX_ERR_ARG, "vehicle: AERO on a model without aerodynamics");
+    if (!ctx->dyn.fin && (veh->mu[SCVX_VEH_FIN] != 0.0 || veh->sp[SCVX_VEH_FIN] != 0.0))
+        return fail(ctx, SCVX_ERR_ARG, "vehicle: FIN on a model without fins");
+    if (!rng && drawn && !zeta) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp > 0 needs zeta[S][6] (or rng)");
+    return SCVX_OK;
+}
+
+// The order is the contract: a call with two faults is refused for the one that comes first here.  The words say "track mc" for what
+// every form shares and "track mc nav" for what the flight on an estimate adds; the noise is checked where each family had it.
+int check_mc_call(scvx_ctx* ctx, const McCall& c, const McBatch* batch) {
+    if (!ctx) return SCVX_ERR_ARG;
+    int rc;
+    // the _veh forms' rule for the draws (no other form can break it): with rng nothing uploaded, without it no noise flag
+    if (c.drawn && (c.xi0 || c.eta || c.xin || c.nud || c.veh.zeta))
+        return fail(ctx, SCVX_ERR_ARG, "vehicle: with rng the uploaded draws (xi0, eta, xin, nud, zeta) must be NULL");
+    if (!c.drawn && c.noise != 0) return fail(ctx, SCVX_ERR_ARG, "vehicle: noise without rng (pass eta)");
+    if (batch && (rc = check_track_weights(ctx, batch->q14, batch->rNU, batch->qf14))) return rc;
+    if (c.B < 1 || c.B > 65535) return fail(ctx, SCVX_ERR_ARG, "track mc: 1 <= B <= 65535 required");
+    if (c.S < 1) return fail(ctx, SCVX_ERR_ARG, "track mc: S >= 1 required");
+    if (c.K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "track mc: K must equal the problem's K");
+    if (c.nsub < 1 || c.nsub > 1000) return fail(ctx, SCVX_ERR_ARG, "track mc: nsub must be in [1,1000]");
+    if (c.flags & ~SCVX_TRACK_CLAMP) return fail(ctx, SCVX_ERR_ARG, "track mc: unknown flags (SCVX_TRACK_CLAMP)");
+    if (!(c.tol >= 0.0) || !std::isfinite(c.tol)) return fail(ctx, SCVX_ERR_ARG, "track mc: tol must be finite and >= 0");
+    const bool impulses = c.drawn ? c.noise != 0 : c.eta != nullptr;
+    auto check_w = [&](const char* bad, const char* missing) {
+        if (c.w)
+            for (int i = 0; i < 14; i++)
+                if (!(c.w[i] >= 0.0) || !std::isfinite(c.w[i])) return fail(ctx, SCVX_ERR_ARG, bad);
+        return impulses && !c.w ? fail(ctx, SCVX_ERR_ARG, missing) : (int)SCVX_OK;
+    };
+    if (!c.nav && (rc = check_w("track mc: sw must be finite and >= 0", "track mc: eta without sw"))) return rc;
+    if (c.reserved) return fail(ctx, SCVX_ERR_ARG, "track mc: the reserved argument must be NULL");
+    const bool own = batch != nullptr;   // the plan, the gains, the tiles and kf are the batch's, the reduced outputs optional
+    if (!(own || (c.x && c.u && c.sigma && c.gain && c.mcrep && c.xmean && c.xcov)) || !c.C0 || !(c.drawn || c.xi0))
+        return fail(ctx, SCVX_ERR_ARG, "track mc: null buffer");
     if (ctx->prob.aero_kind == 1 && !ctx->dyn.aero)
         return fail(ctx, SCVX_ERR_STATE, "AtmosphericData problem: call scvx_set_aero_table first");
-    return SCVX_OK;
+    if (c.nav) {
+        if ((rc = check_w("track mc nav: w must be finite and >= 0", "track mc nav: eta without w14"))) return rc;
+        if ((rc = check_nav_model(ctx, c.m, c.H, c.rm))) return rc;
+        if (!(own || ((c.deriv.d || c.deriv.f) && c.jmean && c.jcov && c.mcnav)) || !c.CN || !(c.drawn || c.xin))
+            return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (deriv, CN, xin, jmean, jcov, mcnav)");
+        if (c.m > 0 && (!(own || c.kf) || !(c.drawn || c.nud)))
+            return fail(ctx, SCVX_ERR_ARG, "track mc nav: m > 0 needs kf[B][K][14][m] and nud[S][K][m]");
+        if (own && !batch->N0) return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (N0)");
+    }
+    if (c.drawn && (rc = check_mc_rng(ctx, c.rng))) return rc;
+    // the _q arguments: with nothing of them asked for, the call they extend
+    if ((c.q.nq != 0 || c.q.flightq || c.q.pathq) && (rc = check_ranks(ctx, c.S, c.q.nq, c.q.ranks))) return rc;
+    return check_mc_vehicle(ctx, c.veh.v, c.veh.zeta, c.veh.theta, c.drawn);
 }
 
-// scvx_track_mc_q_f64 and, with rg (then xi0_dev and eta_dev are placeholders that are never read), scvx_track_mc_rng_f64
-static int track_mc_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
-                          const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
-                          const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
-                          double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
-                          double* pathq_dev, double* pathv_dev, const McRng* rg, const McVeh* vh = nullptr) {
-    int rc = scvx::check_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags,
-                                  tol, mcrep_dev, xmean_dev, xcov_dev);
+// the buffers in the order the hand-written sequences declared them: the vehicle's, the inputs, the outputs, the order statistics
+McCall stage_mc(Staging& s, const Dims& d, const McCall& host, bool reduced_always) {
+    McCall v = host;
+    auto reduced = [&](double* p, size_t n) { return reduced_always ? s.out_always(p, n) : s.out(p, n); };
+    v.veh.zeta = s.in(host.veh.zeta, d.zeta), v.veh.theta = s.out(host.veh.theta, d.theta);
+    v.x = s.in(host.x, d.x), v.u = s.in(host.u, d.u), v.sigma = s.in(host.sigma, d.b), v.gain = s.in(host.gain, d.gain);
+    v.C0 = s.in(host.C0, d.c14), v.xi0 = s.in(host.xi0, d.xi), v.eta = s.in(host.eta, d.eta);
+    if (host.nav) {   // kf and nud are read with m > 0 only
+        v.deriv.d = s.in(host.deriv.d, d.deriv), v.kf = s.in(host.m > 0 ? host.kf : nullptr, d.kf), v.CN = s.in(host.CN, d.c14);
+        v.xin = s.in(host.xin, d.xi), v.nud = s.in(host.m > 0 ? host.nud : nullptr, d.nud);
+    }
+    v.mcrep = reduced(host.mcrep, d.mcrep), v.xmean = reduced(host.xmean, d.b14), v.xcov = reduced(host.xcov, d.c14);
+    if (host.nav) v.jmean = reduced(host.jmean, d.jmean), v.jcov = reduced(host.jcov, d.jcov), v.mcnav = reduced(host.mcnav, d.nrep);
+    v.flights = s.out(host.flights, d.flights), v.xland = s.out(host.xland, d.s14), v.dx0 = s.out(host.dx0, d.s14);
+    v.navfed = s.out(host.navfed, d.fed), v.navK = s.out(host.navK, d.s14);
+    v.q.flightq = s.out(host.q.flightq, d.flightq), v.q.pathq = s.out(host.q.pathq, d.pathq), v.q.pathv = s.out(host.q.pathv, d.pathv);
+    return v;
+}
+
+int mc_call_dev(scvx_ctx* ctx, const McCall& c) {
+    int rc = check_mc_call(ctx, c);
     if (rc) return rc;
-    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
-    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
-    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
-    scvx::McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
-    const bool any = flightq_dev || pathq_dev || pathv_dev;
     SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, rg ? nullptr : xi0_dev,
-                                        rg ? nullptr : eta_dev, sw14, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, flights_dev,
-                                        xland_dev, dx0_dev, ctx->stream, any ? &q : nullptr, rg, vh));
+    SCVX_HIP(ctx, launch_mc(ctx, c, ctx->stream));
     return SCVX_OK;
 }
 
-// scvx_track_mc_q_f64_host and, with rg (xi0 and eta placeholders, nothing of them uploaded), scvx_track_mc_rng_f64_host
-static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
-                           const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
-                           int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0,
-                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg,
-                           const McVeh* vh = nullptr, const char* entry = "scvx_track_mc_q_f64_host");
+int mc_call_host(scvx_ctx* ctx, const McCall& c, const char* entry) {
+    int rc = check_mc_call(ctx, c);
+    if (rc) return rc;
+    const Dims d(c.B, c.K, scvx_control_dim(ctx), c.S, c.m, c.q.nq);
+    Staging s(ctx);
+    const McCall dev = stage_mc(s, d, c, false);
+    s.launch([&] { return launch_mc(ctx, dev, s.st); });
+    return s.finish(entry);
+}
 
 // one lane per (plan, s): the draws the _rng forms consume (mc_draws_kernel); any of the four outputs may be nullptr
 hipError_t launch_mc_draws(const scvx_mc_rng& r, int P, int S, int K, double* xi0, double* eta, double* xin, double* nud, hipStream_t st) {
-    const McRng g{&r, 0};
-    hipLaunchKernelGGL(mc_draws_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)P), dim3(64), 0, st, mc_rng_k(g, false), S, K, xi0, eta,
+    hipLaunchKernelGGL(mc_draws_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)P), dim3(64), 0, st, mc_rng_k(r, false), S, K, xi0, eta,
                        xin, nud);
     return hipGetLastError();
 }
@@ -234,69 +267,46 @@ int scvx_mc_draws_f64_host(scvx_ctx* ctx, const scvx_mc_rng* rng, int P, int S, 
     return s.finish("scvx_mc_draws_f64_host");
 }
 
+// Every entry point below fills one record from its arguments.  The _q forms take the uploaded draws; the _rng forms have the lanes make
+// them; the _veh forms are either, by rng, with the vehicle errors; the forms without a suffix are the _q forms with nothing of q.
 int scvx_track_mc_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                         const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
                         const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
                         double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
                         double* pathq_dev, double* pathv_dev) {
-    return scvx::track_mc_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags, tol,
-                                mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, nq, ranks, flightq_dev, pathq_dev,
-                                pathv_dev, nullptr);
+    scvx::McCall c;
+    c.B = B, c.K = K, c.S = S, c.x = x_dev, c.u = u_dev, c.sigma = sigma_dev, c.gain = gain_dev, c.C0 = C0_dev, c.w = sw14;
+    c.reserved = reserved, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep_dev, c.xmean = xmean_dev, c.xcov = xcov_dev;
+    c.flights = flights_dev, c.xland = xland_dev, c.dx0 = dx0_dev, c.q = {nq, ranks, flightq_dev, pathq_dev, pathv_dev}, c.xi0 = xi0_dev;
+    c.eta = eta_dev;
+    return scvx::mc_call_dev(ctx, c);
 }
 
-// the placeholders: xi0 any non-null pointer, eta non-null exactly when the truth receives impulses (check_track_mc's rules for them)
 int scvx_track_mc_rng_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                           const double* gain_dev, const double* C0_dev, const scvx_mc_rng* rng, int noise, const double* sw14,
                           const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
                           double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
                           double* pathq_dev, double* pathv_dev) {
-    const scvx::McRng rg{rng, noise};
-    return scvx::track_mc_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, x_dev, noise ? x_dev : nullptr, sw14, reserved,
-                                nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, nq, ranks, flightq_dev,
-                                pathq_dev, pathv_dev, &rg);
+    scvx::McCall c;
+    c.B = B, c.K = K, c.S = S, c.x = x_dev, c.u = u_dev, c.sigma = sigma_dev, c.gain = gain_dev, c.C0 = C0_dev, c.w = sw14;
+    c.reserved = reserved, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep_dev, c.xmean = xmean_dev, c.xcov = xcov_dev;
+    c.flights = flights_dev, c.xland = xland_dev, c.dx0 = dx0_dev, c.q = {nq, ranks, flightq_dev, pathq_dev, pathv_dev}, c.drawn = true;
+    c.rng = rng, c.noise = noise;
+    return scvx::mc_call_dev(ctx, c);
 }
 
-int scvx_track_mc_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const scvx_mc_rng* rng, int noise, const double* sw14,
-                               const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
-                               double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
-                               double* pathv) {
-    const scvx::McRng rg{rng, noise};
-    return scvx::track_mc_q_host(ctx, B, K, S, x, u, sigma, gain, C0, x, noise ? x : nullptr, sw14, reserved, nsub, flags, tol, mcrep,
-                                 xmean, xcov, flights, xland, dx0, nq, ranks, flightq, pathq, pathv, &rg);
-}
-
-// the _veh forms: the _q call (rng == NULL) or the _rng call (its placeholders as above) with the vehicle errors behind it
 int scvx_track_mc_veh_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                           const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* sw14,
                           const void* reserved, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
                           double* flights_dev, double* xland_dev, double* dx0_dev, int nq, const int* ranks, double* flightq_dev,
                           double* pathq_dev, double* pathv_dev, const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh,
                           const double* zeta_dev, double* theta_dev) {
-    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0_dev, eta_dev, nullptr, nullptr, zeta_dev);
-    if (rc) return rc;
-    const scvx::McRng rg{rng, noise};
-    const scvx::McVeh vh{veh, zeta_dev, theta_dev};
-    if (rng) xi0_dev = x_dev, eta_dev = noise ? x_dev : nullptr;
-    return scvx::track_mc_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, sw14, reserved, nsub, flags, tol,
-                                mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, nq, ranks, flightq_dev, pathq_dev,
-                                pathv_dev, rng ? &rg : nullptr, &vh);
-}
-
-int scvx_track_mc_veh_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* sw14,
-                               const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
-                               double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
-                               double* pathv, const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta,
-                               double* theta) {
-    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0, eta, nullptr, nullptr, zeta);
-    if (rc) return rc;
-    const scvx::McRng rg{rng, noise};
-    const scvx::McVeh vh{veh, zeta, theta};
-    if (rng) xi0 = x, eta = noise ? x : nullptr;
-    return scvx::track_mc_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
-                                 flights, xland, dx0, nq, ranks, flightq, pathq, pathv, rng ? &rg : nullptr, &vh,
-                                 "scvx_track_mc_veh_f64_host");
+    scvx::McCall c;
+    c.B = B, c.K = K, c.S = S, c.x = x_dev, c.u = u_dev, c.sigma = sigma_dev, c.gain = gain_dev, c.C0 = C0_dev, c.w = sw14;
+    c.reserved = reserved, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep_dev, c.xmean = xmean_dev, c.xcov = xcov_dev;
+    c.flights = flights_dev, c.xland = xland_dev, c.dx0 = dx0_dev, c.q = {nq, ranks, flightq_dev, pathq_dev, pathv_dev}, c.xi0 = xi0_dev;
+    c.eta = eta_dev, c.drawn = rng != nullptr, c.rng = rng, c.noise = noise, c.veh = {veh, zeta_dev, theta_dev};
+    return scvx::mc_call_dev(ctx, c);
 }
 
 int scvx_track_mc_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
@@ -307,54 +317,48 @@ int scvx_track_mc_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, c
                                mcrep_dev, xmean_dev, xcov_dev, flights_dev, xland_dev, dx0_dev, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
+int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
+                             const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
+                             int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland,
+                             double* dx0, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
+    scvx::McCall c;
+    c.B = B, c.K = K, c.S = S, c.x = x, c.u = u, c.sigma = sigma, c.gain = gain, c.C0 = C0, c.w = sw14, c.reserved = reserved;
+    c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean, c.xcov = xcov, c.flights = flights, c.xland = xland;
+    c.dx0 = dx0, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta;
+    return scvx::mc_call_host(ctx, c, "scvx_track_mc_q_f64_host");
+}
+
+int scvx_track_mc_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const scvx_mc_rng* rng, int noise, const double* sw14,
+                               const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                               double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
+                               double* pathv) {
+    scvx::McCall c;
+    c.B = B, c.K = K, c.S = S, c.x = x, c.u = u, c.sigma = sigma, c.gain = gain, c.C0 = C0, c.w = sw14, c.reserved = reserved;
+    c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean, c.xcov = xcov, c.flights = flights, c.xland = xland;
+    c.dx0 = dx0, c.q = {nq, ranks, flightq, pathq, pathv}, c.drawn = true, c.rng = rng, c.noise = noise;
+    return scvx::mc_call_host(ctx, c, "scvx_track_mc_rng_f64_host");
+}
+
+int scvx_track_mc_veh_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* sw14,
+                               const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
+                               double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
+                               double* pathv, const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta,
+                               double* theta) {
+    scvx::McCall c;
+    c.B = B, c.K = K, c.S = S, c.x = x, c.u = u, c.sigma = sigma, c.gain = gain, c.C0 = C0, c.w = sw14, c.reserved = reserved;
+    c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean, c.xcov = xcov, c.flights = flights, c.xland = xland;
+    c.dx0 = dx0, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta, c.drawn = rng != nullptr, c.rng = rng;
+    c.noise = noise, c.veh = {veh, zeta, theta};
+    return scvx::mc_call_host(ctx, c, "scvx_track_mc_veh_f64_host");
+}
+
 int scvx_track_mc_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
                            const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
-                           int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland,
-                           double* dx0) {
+                           int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0) {
     return scvx_track_mc_q_f64_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
                                     flights, xland, dx0, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
-int scvx_track_mc_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                             const double* gain, const double* C0, const double* xi0, const double* eta, const double* sw14,
-                             const void* reserved, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
-                             double* flights, double* xland, double* dx0, int nq, const int* ranks, double* flightq, double* pathq,
-                             double* pathv) {
-    return scvx::track_mc_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov,
-                                 flights, xland, dx0, nq, ranks, flightq, pathq, pathv, nullptr);
-}
-
 }  // extern "C"
-
-namespace scvx {
-
-static int track_mc_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma, const double* gain,
-                           const double* C0, const double* xi0, const double* eta, const double* sw14, const void* reserved, int nsub,
-                           int flags, double tol, double* mcrep, double* xmean, double* xcov, double* flights, double* xland, double* dx0,
-                           int nq, const int* ranks, double* flightq, double* pathq, double* pathv, const McRng* rg, const McVeh* vh,
-                           const char* entry) {
-    int rc = scvx::check_track_mc(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, sw14, reserved, nsub, flags, tol, mcrep, xmean, xcov);
-    if (rc) return rc;
-    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
-    if (rg) xi0 = eta = nullptr;   // placeholders until here: the lanes make the draws
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
-    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
-    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
-    const Dims d(B, K, scvx_control_dim(ctx), S, 0, nq);
-    Staging s(ctx);
-    McVeh dvh;   // the vehicle errors with zeta and theta on the device
-    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
-    McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = s.out(flightq, d.flightq), q.pathq = s.out(pathq, d.pathq), q.pathv = s.out(pathv, d.pathv);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dc = s.in(C0, d.c14),
-                 *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta);
-    double *dr = s.out(mcrep, d.mcrep), *dm = s.out(xmean, d.b14), *dv = s.out(xcov, d.c14), *df = s.out(flights, d.flights),
-           *dl = s.out(xland, d.s14), *d0 = s.out(dx0, d.s14);
-    s.launch([&] {
-        return launch_track_mc(ctx, B, K, S, dx, du, ds, dg, dc, di, de, sw14, nsub, flags, tol, dr, dm, dv, df, dl, d0, s.st,
-                               (flightq || pathq || pathv) ? &q : nullptr, rg, vh ? &dvh : nullptr);
-    });
-    return s.finish(entry);
-}
-
-}  // namespace scvx

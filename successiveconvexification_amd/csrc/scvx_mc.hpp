@@ -40,12 +40,6 @@ __device__ __forceinline__ void mc_path_store(double* __restrict__ p, int S, dou
     p[(size_t)SCVX_PSIG_RATE * S] = sqrt(xs[11] * xs[11] + xs[12] * xs[12] + xs[13] * xs[13]);
 }
 
-// the context's workspace of partial rows, grown on demand (scvx_mc.hip)
-hipError_t mc_workspace(scvx_ctx* ctx, size_t doubles);
-// ... and, beside it, the workspace of the dense values whose order statistics are asked for without the dense output itself
-// (flights [B][S][16] and pathv [B][K+1][5][S]), under the same rule: no two calls on one context overlapping on different streams
-hipError_t mc_q_workspace(scvx_ctx* ctx, size_t doubles);
-
 // What the _q forms add to a sampled call (scvx_quantile.hip, scvx_mc.hip): nq ranks (host), flightq [B][16][nq], pathq
 // [B][K+1][5][nq], pathv [B][K+1][5][S], each a device pointer or nullptr.
 struct McQ {
@@ -53,18 +47,10 @@ struct McQ {
     const int* ranks = nullptr;
     double *flightq = nullptr, *pathq = nullptr, *pathv = nullptr;
 };
-// The _rng forms: the draws are made by the lanes (scvx_rng.hpp) and the pointers xi0 / eta / xin / nud of the launch are not read;
-// noise: whether the truth receives the impulses sqrt(w) eta (the role of eta != nullptr in the calls on uploaded draws).
-struct McRng {
-    const scvx_mc_rng* r = nullptr;
-    int noise = 0;
-};
-inline McRngK mc_rng_k(const McRng& g, bool noise) {
-    return McRngK{g.r->seed, g.r->s_lo, g.r->b_lo, g.r->independent, noise ? 1 : 0};
-}
-// The _veh forms: per-flight vehicle errors theta = mu + sp * zeta (include/scvx.h).  zeta [S][6] and theta [B][S][6] are device
-// pointers or nullptr (zeta is not read when the lanes make the draws); McVehK is what the ACT instantiations take as their last
-// kernel argument.
+inline McRngK mc_rng_k(const scvx_mc_rng& r, bool noise) { return McRngK{r.seed, r.s_lo, r.b_lo, r.independent, noise ? 1 : 0}; }
+// The _veh forms: per-flight vehicle errors theta = mu + sp * zeta (include/scvx.h).  v == nullptr: the nominal vehicle, the
+// instantiations without ACT.  zeta [S][6] and theta [B][S][6] or nullptr (zeta is not read when the lanes make the draws); McVehK is
+// what the ACT instantiations take as their last kernel argument.
 struct McVeh {
     const scvx_mc_vehicle* v = nullptr;
     const double* zeta = nullptr;
@@ -81,20 +67,60 @@ inline McVehK mc_veh_k(const McVeh& h) {
     k.zeta = h.zeta, k.theta = h.theta;
     return k;
 }
+
+// One sampled call, whichever of the 24 entry points it came through: everything such a call can carry, under the names of
+// include/scvx.h.  What a form does not take stays nullptr / 0.  The arrays are the caller's -- host arrays at the _host and the
+// batch-level forms -- or, behind stage_mc, their device copies; w, H, rm, q.ranks, rng and veh.v are always host memory.
+struct McCall {
+    int B = 0, K = 0, S = 0;
+    const double *x = nullptr, *u = nullptr, *sigma = nullptr, *gain = nullptr, *C0 = nullptr;   // the plan, its gains, the dispersion
+    const double *xi0 = nullptr, *eta = nullptr;                                                  // uploaded draws
+    const double* w = nullptr;   // sw14 (flown on the truth: the impulse's size) or w14 (nav: its VARIANCE)
+    const void* reserved = nullptr;
+    int nsub = 0, flags = 0;
+    double tol = 0.0;
+    double *mcrep = nullptr, *xmean = nullptr, *xcov = nullptr, *flights = nullptr, *xland = nullptr, *dx0 = nullptr;
+    McQ q;
+    // drawn: the lanes make the draws (the _rng forms, the _veh forms with rng) from rng, no draw is uploaded, and noise says whether
+    // the truth receives the impulses -- the role of eta != nullptr in a call on uploaded draws
+    bool drawn = false;
+    const scvx_mc_rng* rng = nullptr;
+    int noise = 0;
+    McVeh veh;
+    bool nav = false;   // flown on a navigation estimate (scvx_mc_nav.hip): everything below applies
+    Tiles deriv;
+    const double *kf = nullptr, *CN = nullptr, *xin = nullptr, *nud = nullptr;
+    int m = 0;
+    const double *H = nullptr, *rm = nullptr;
+    double *jmean = nullptr, *jcov = nullptr, *mcnav = nullptr, *navfed = nullptr, *navK = nullptr;
+};
+// what a batch-level form checks besides: the tracking weights and, with nav, N0 (host arrays).  The plan, the gains, the tiles and
+// kf are then the batch's own and the reduced outputs optional: check_mc_call does not ask for them.
+struct McBatch {
+    const double *q14, *rNU, *qf14, *N0;
+};
+class Staging;
+struct Dims;
+
+// every refusal of a sampled call, in one order for all the forms (tests/golden/mc_refusals.txt, mc_batch_refusals.txt)
+int check_mc_call(scvx_ctx* ctx, const McCall& c, const McBatch* batch = nullptr);
+// the device copy of a record of host arrays: the inputs uploaded, the outputs asked for downloaded by s.finish();
+// reduced_always: mcrep, xmean, xcov (jmean, jcov, mcnav) are allocated also where the caller does not want them
+McCall stage_mc(Staging& s, const Dims& d, const McCall& host, bool reduced_always);
+// the whole call on device arrays: workspaces, noise, the flights, the reduction, the order statistics (scvx_mc.hip; the flight on an
+// estimate and its reduction are launch_mc_nav's, in scvx_mc_nav.hip beside their kernels)
+hipError_t launch_mc(scvx_ctx* ctx, const McCall& dev, hipStream_t st);
+hipError_t launch_mc_nav(scvx_ctx* ctx, const McCall& dev, const McK& m, const McRngK& rg, hipStream_t st);
+// the two context-level shapes of an entry point: check and launch on the caller's device arrays; check, stage, launch, finish
+int mc_call_dev(scvx_ctx* ctx, const McCall& c);
+int mc_call_host(scvx_ctx* ctx, const McCall& c, const char* entry);
+
 // veh may be nullptr (then zeta and theta must be); rng: whether the lanes make the draws
 int check_mc_vehicle(scvx_ctx* ctx, const scvx_mc_vehicle* veh, const void* zeta, const void* theta, bool rng);
-// what the _veh entry points ask of the draws before they become a _q or an _rng call: with rng every uploaded draw must be NULL,
-// without it noise must be 0
-int check_mc_veh_draws(scvx_ctx* ctx, const scvx_mc_rng* rng, int noise, const void* xi0, const void* eta, const void* xin,
-                       const void* nud, const void* zeta);
 int check_mc_rng(scvx_ctx* ctx, const scvx_mc_rng* rng);
-int check_mc_q(scvx_ctx* ctx, int S, int nq, const int* ranks, const void* flightq, const void* pathq);
 int check_ranks(scvx_ctx* ctx, int S, int nq, const int* ranks);
 // rows: row r starts at v[(r / inner) * ld_outer + (r % inner) * ld_inner], its S values inc apart; out [R][nq]
 hipError_t launch_order_stats(int R, int S, const double* v, size_t ld_outer, int inner, size_t ld_inner, size_t inc, int nq,
                               const int* ranks, double* out, hipStream_t st);
-// where the flying kernel writes flights / pathv (the caller's buffer, the workspace, or nullptr), then after it: the order statistics
-hipError_t mc_q_buffers(scvx_ctx* ctx, int B, int K, int S, const McQ& q, double*& flights, double*& pathv);
-hipError_t mc_q_finish(int B, int K, int S, const McQ& q, const double* flights, const double* pathv, hipStream_t st);
 
 }  // namespace scvx

@@ -55,6 +55,7 @@
 #pragma once
 #include <cmath>
 #include <limits>
+#include <type_traits>
 #include "scvx_mc.hpp"
 
 namespace scvx {
@@ -584,59 +585,65 @@ __device__ __forceinline__ void mc_finish_front(int S, int K, int nblk, const do
     }
 }
 
-// The noise of a sampled call, for both launches: the impulse's size into m.sw (from sw itself, or from the variance w), eta = nullptr
-// when no component receives an impulse (the undisturbed kernel path, bit for bit), and the streams of the _rng forms.
-inline McRngK mc_noise(McK& m, const double* sw, bool variance, const double*& eta, const McRng* rng) {
+// The noise of a sampled call: the impulse's size into m.sw (from sw itself, or with nav from the variance w), eta = nullptr when no
+// component receives an impulse (the undisturbed kernel path, bit for bit), and the streams of the forms whose lanes make the draws.
+inline McRngK mc_noise(McK& m, McCall& mc) {
     bool noise = false;
-    if ((rng ? rng->noise != 0 : eta != nullptr) && sw)
+    if ((mc.drawn ? mc.noise != 0 : mc.eta != nullptr) && mc.w)
         for (int i = 0; i < 14; i++) {
-            m.sw[i] = variance ? std::sqrt(sw[i]) : sw[i];
-            noise = noise || sw[i] > 0.0;
+            m.sw[i] = mc.nav ? std::sqrt(mc.w[i]) : mc.w[i];
+            noise = noise || mc.w[i] > 0.0;
         }
-    if (!noise) eta = nullptr;
-    return rng ? mc_rng_k(*rng, noise) : McRngK{};
+    if (!noise) mc.eta = nullptr;
+    return mc.drawn ? mc_rng_k(*mc.rng, noise) : McRngK{};
 }
 
-// What the flight on an estimate adds to the launch (scvx_mc_nav.hip); all zero for the flight on the true state.
+// What the flight on an estimate adds to the kernel's arguments, read off the record; all zero for the flight on the true state.
 template <typename DS>
 struct McNavA {
     int mm;              // rows of the measurement model
-    const double* hm;    // the model in the workspace
+    const double* hm;    // the model in the workspace, behind the partial rows (mc_nav_model)
     const DS* deriv;
     const double *kf, *CN, *xin, *nud;
     double *navfed, *navK;
 };
+inline double* mc_nav_model(const scvx_ctx* ctx, const McCall& mc) { return ctx->mc_ws + (size_t)mc.B * ((mc.S + 63) / 64) * MCN_NP; }
 
 // The launch of the flying kernel, for all four translation units: the instantiation of the context's model, with PV when pathv is
-// asked for and RNG when the lanes make the draws.  ACT: the instantiations with vehicle errors, veh their argument (else nullptr).
+// asked for and RNG when the lanes make the draws.  mc: the device record as launch_mc prepared it (flights and q.pathv where the
+// kernel writes them, eta behind mc_noise); the partial rows go to ctx->mc_ws.  ACT: the instantiations with vehicle errors.
 template <bool NAV, typename DS, bool ACT>
-hipError_t launch_mc_fly_t(scvx_ctx* ctx, const McK& m, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                           const double* gain, const double* C0, const double* xi0, const double* eta, int nsub, int flags, double* part,
-                           double* flights, double* xland, double* dx0, double* pv, const McRng* rng, const McRngK& rg, hipStream_t st,
-                           const McNavA<DS>& n, const McVeh* veh) {
+hipError_t launch_mc_fly_t(scvx_ctx* ctx, const McCall& mc, const McK& m, const McRngK& rg, hipStream_t st) {
     const PathK c = path_constants(ctx->prob);
-    const double dt = 1.0 / (K + 1);
-    const dim3 g((unsigned)((S + 63) / 64), (unsigned)B), blk(64);
+    const double dt = 1.0 / (mc.K + 1);
+    const dim3 g((unsigned)((mc.S + 63) / 64), (unsigned)mc.B), blk(64);
     const DynP<double> dp(ctx->dyn);
-#define SCVX_MC_ARGS(par) \
-    par, c, m, n.mm, n.hm, S, K, x, u, sigma, gain, C0, xi0, eta, n.deriv, n.kf, n.CN, n.xin, n.nud, dt, nsub, flags, part, flights, xland, dx0, \
-        n.navfed, n.navK, pv, rg
+    McNavA<DS> n{};
+    if constexpr (NAV) {
+        if constexpr (std::is_same<DS, double>::value) n.deriv = mc.deriv.d;
+        else n.deriv = mc.deriv.f;
+        n.mm = mc.m, n.hm = mc_nav_model(ctx, mc), n.kf = mc.kf, n.CN = mc.CN, n.xin = mc.xin, n.nud = mc.nud;
+        n.navfed = mc.navfed, n.navK = mc.navK;
+    }
+#define SCVX_MC_ARGS(par)                                                                                                         \
+    par, c, m, n.mm, n.hm, mc.S, mc.K, mc.x, mc.u, mc.sigma, mc.gain, mc.C0, mc.xi0, mc.eta, n.deriv, n.kf, n.CN, n.xin, n.nud, dt, \
+        mc.nsub, mc.flags, ctx->mc_ws, mc.flights, mc.xland, mc.dx0, n.navfed, n.navK, mc.q.pathv, rg
 #define SCVX_MC_RG(A, F, T, P, G, par)                                                                                           \
     do {                                                                                                                         \
         if constexpr (ACT)                                                                                                       \
-            hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G, NAV, DS, true, McVehK>), g, blk, 0, st, SCVX_MC_ARGS(par), mc_veh_k(*veh)); \
+            hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G, NAV, DS, true, McVehK>), g, blk, 0, st, SCVX_MC_ARGS(par), mc_veh_k(mc.veh)); \
         else                                                                                                                     \
             hipLaunchKernelGGL((mc_fly_kernel<A, F, T, P, G, NAV, DS>), g, blk, 0, st, SCVX_MC_ARGS(par));                        \
     } while (0)
-#define SCVX_MC_PV(A, F, T, P, par)                 \
-    do {                                            \
-        if (rng) SCVX_MC_RG(A, F, T, P, true, par); \
-        else SCVX_MC_RG(A, F, T, P, false, par);    \
+#define SCVX_MC_PV(A, F, T, P, par)                      \
+    do {                                                 \
+        if (mc.drawn) SCVX_MC_RG(A, F, T, P, true, par); \
+        else SCVX_MC_RG(A, F, T, P, false, par);         \
     } while (0)
-#define SCVX_MC(A, F, T, par)                   \
-    do {                                        \
-        if (pv) SCVX_MC_PV(A, F, T, true, par); \
-        else SCVX_MC_PV(A, F, T, false, par);   \
+#define SCVX_MC(A, F, T, par)                           \
+    do {                                                \
+        if (mc.q.pathv) SCVX_MC_PV(A, F, T, true, par); \
+        else SCVX_MC_PV(A, F, T, false, par);           \
     } while (0)
     if (ctx->dyn.trq) {
         const DynPT<double> dpt(ctx->dyn);
@@ -658,25 +665,15 @@ hipError_t launch_mc_fly_t(scvx_ctx* ctx, const McK& m, int B, int K, int S, con
 
 // The ACT instantiations of the launch are made in scvx_mc_veh.hip (NAV = false) and scvx_mc_nav_veh.hip (NAV = true, DS double and
 // float) alone: these declarations keep every other translation unit from instantiating them, and with them their kernels.
-#define SCVX_MC_FLY_ACT(NAV, DS)                                                                                                         \
-    hipError_t launch_mc_fly_t<NAV, DS, true>(scvx_ctx*, const McK&, int, int, int, const double*, const double*, const double*,         \
-                                              const double*, const double*, const double*, const double*, int, int, double*, double*,    \
-                                              double*, double*, double*, const McRng*, const McRngK&, hipStream_t, const McNavA<DS>&,    \
-                                              const McVeh*)
+#define SCVX_MC_FLY_ACT(NAV, DS) \
+    hipError_t launch_mc_fly_t<NAV, DS, true>(scvx_ctx*, const McCall&, const McK&, const McRngK&, hipStream_t)
 extern template SCVX_MC_FLY_ACT(false, double);
 extern template SCVX_MC_FLY_ACT(true, double);
 extern template SCVX_MC_FLY_ACT(true, float);
 
 template <bool NAV, typename DS>
-hipError_t launch_mc_fly(scvx_ctx* ctx, const McK& m, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                         const double* gain, const double* C0, const double* xi0, const double* eta, int nsub, int flags, double* part,
-                         double* flights, double* xland, double* dx0, double* pv, const McRng* rng, const McRngK& rg, hipStream_t st,
-                         const McNavA<DS>& n, const McVeh* veh = nullptr) {
-    if (veh)
-        return launch_mc_fly_t<NAV, DS, true>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng,
-                                              rg, st, n, veh);
-    return launch_mc_fly_t<NAV, DS, false>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng,
-                                           rg, st, n, nullptr);
+hipError_t launch_mc_fly(scvx_ctx* ctx, const McCall& mc, const McK& m, const McRngK& rg, hipStream_t st) {
+    return mc.veh.v ? launch_mc_fly_t<NAV, DS, true>(ctx, mc, m, rg, st) : launch_mc_fly_t<NAV, DS, false>(ctx, mc, m, rg, st);
 }
 
 }  // namespace scvx

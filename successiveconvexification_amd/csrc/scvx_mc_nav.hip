@@ -16,7 +16,6 @@
 // mc_nav_finish_kernel (one block per plan) combines the partial rows [MCN_NP] in block order.  The row is the plain one, then the sums
 // of eps_K [14] and of the upper triangle of [e; eps_K][e; eps_K]' [406], and the largest |eps+_k|_inf fed; mcrep, xmean and xcov come
 // from mc_finish_front, the expressions mc_finish_kernel uses.
-#include "scvx_stage.hpp"
 #include "scvx_mc_fly.hpp"
 
 namespace scvx {
@@ -83,158 +82,60 @@ __global__ __launch_bounds__(256) void mc_nav_finish_kernel(int S, int K, int nb
     }
 }
 
-template <typename DS>
-static hipError_t launch_track_mc_nav_t(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                                        const double* gain, const double* C0, const double* xi0, const double* eta, const double* w,
-                                        const DS* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int mm,
-                                        const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                                        double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland,
-                                        double* dx0, double* navfed, double* navK, hipStream_t st, const McQ* q, const McRng* rng,
-                                        const McVeh* veh) {
-    const int nblk = (S + 63) / 64;
-    const size_t nrows = (size_t)B * nblk * MCN_NP;
-    hipError_t e = mc_workspace(ctx, nrows + MCN_MODEL);
-    if (e != hipSuccess) return e;
-    double* pv = nullptr;
-    if (q && (e = mc_q_buffers(ctx, B, K, S, *q, flights, pv)) != hipSuccess) return e;
-    McK m{};
-    m.tol = tol;
-    const McRngK rg = mc_noise(m, w, true, eta, rng);
+// The flight on an estimate and its reduction, for launch_mc (scvx_mc.hip), which has grown the workspace and prepared the record: the
+// measurement model into the workspace, the flights with the tiles as they are stored -- deriv.d ? <double> : <float>, in that order
+// (profiles/host_staging.md) -- and the finish kernel.
+hipError_t launch_mc_nav(scvx_ctx* ctx, const McCall& c, const McK& m, const McRngK& rg, hipStream_t st) {
     McNavK nv{};
-    for (int i = 0; i < mm; i++) nv.srm[i] = std::sqrt(rm[i]);
-    for (int i = 0; i < mm * 14; i++) nv.H[i] = H[i];
-    double* part = ctx->mc_ws;
-    double* hm = ctx->mc_ws + nrows;
-    hipLaunchKernelGGL(mc_nav_model_kernel, dim3(1), dim3(256), 0, st, nv, hm);
-    e = hipGetLastError();
+    for (int i = 0; i < c.m; i++) nv.srm[i] = std::sqrt(c.rm[i]);
+    for (int i = 0; i < c.m * 14; i++) nv.H[i] = c.H[i];
+    hipLaunchKernelGGL(mc_nav_model_kernel, dim3(1), dim3(256), 0, st, nv, mc_nav_model(ctx, c));
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const McNavA<DS> na{mm, hm, deriv, kf, CN, xin, nud, navfed, navK};
-    e = launch_mc_fly<true>(ctx, m, B, K, S, x, u, sigma, gain, C0, xi0, eta, nsub, flags, part, flights, xland, dx0, pv, rng, rg, st, na,
-                            veh);
+    e = c.deriv.d ? launch_mc_fly<true, double>(ctx, c, m, rg, st) : launch_mc_fly<true, float>(ctx, c, m, rg, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_nav_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, S, K, nblk, part, mcrep, xmean, xcov, jmean, jcov, mcnav);
-    e = hipGetLastError();
-    if (e != hipSuccess || !q) return e;
-    return mc_q_finish(B, K, S, *q, flights, pv, st);
+    hipLaunchKernelGGL(mc_nav_finish_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.S, c.K, (c.S + 63) / 64, ctx->mc_ws, c.mcrep, c.xmean,
+                       c.xcov, c.jmean, c.jcov, c.mcnav);
+    return hipGetLastError();
 }
-
-hipError_t launch_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w, Tiles deriv,
-                               const double* kf, const double* CN, const double* xin, const double* nud, int m, const double* H,
-                               const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov,
-                               double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
-                               double* navK, hipStream_t st, const McQ* q, const McRng* rng, const McVeh* veh) {
-    return deriv.d ? launch_track_mc_nav_t<double>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv.d, kf, CN, xin, nud, m, H, rm, nsub,
-                                                   flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st,
-                                                   q, rng, veh)
-                   : launch_track_mc_nav_t<float>(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w, deriv.f, kf, CN, xin, nud, m, H, rm, nsub,
-                                                  flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, st, q,
-                                                  rng, veh);
-}
-
-int check_track_mc_nav(scvx_ctx* ctx, int B, int K, int S, const void* x, const void* u, const void* sigma, const void* gain,
-                       const void* C0, const void* xi0, const void* eta, const double* w, const void* deriv, const void* kf,
-                       const void* CN, const void* xin, const void* nud, int m, const double* H, const double* rm, int nsub, int flags,
-                       double tol, const void* mcrep, const void* xmean, const void* xcov, const void* jmean, const void* jcov,
-                       const void* mcnav) {
-    if (!ctx) return SCVX_ERR_ARG;
-    // everything scvx_track_mc_f64 refuses (its sw is checked below, as the variance w), in its words
-    int rc = check_track_mc(ctx, B, K, S, x, u, sigma, gain, C0, xi0, nullptr, nullptr, nullptr, nsub, flags, tol, mcrep, xmean, xcov);
-    if (rc) return rc;
-    if (w)
-        for (int i = 0; i < 14; i++)
-            if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(ctx, SCVX_ERR_ARG, "track mc nav: w must be finite and >= 0");
-    if (eta && !w) return fail(ctx, SCVX_ERR_ARG, "track mc nav: eta without w14");
-    if ((rc = check_nav_model(ctx, m, H, rm))) return rc;
-    if (!deriv || !CN || !xin || !jmean || !jcov || !mcnav)
-        return fail(ctx, SCVX_ERR_ARG, "track mc nav: null buffer (deriv, CN, xin, jmean, jcov, mcnav)");
-    if (m > 0 && (!kf || !nud)) return fail(ctx, SCVX_ERR_ARG, "track mc nav: m > 0 needs kf[B][K][14][m] and nud[S][K][m]");
-    return SCVX_OK;
-}
-
-// scvx_track_mc_nav_q_f64 and, with rg (then xi0, eta, xin and nud are placeholders that are never read), scvx_track_mc_nav_rng_f64
-static int track_mc_nav_q_dev(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
-                              const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
-                              const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
-                              const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
-                              double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
-                              double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
-                              double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev,
-                              const McRng* rg, const McVeh* vh = nullptr) {
-    int rc = scvx::check_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
-                                      CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
-                                      jcov_dev, mcnav_dev);
-    if (rc) return rc;
-    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq_dev, pathq_dev))) return rc;
-    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
-    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
-    if (rg) xi0_dev = eta_dev = xin_dev = nud_dev = nullptr;   // placeholders until here: the lanes make the draws
-    scvx::McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = flightq_dev, q.pathq = pathq_dev, q.pathv = pathv_dev;
-    const bool any = flightq_dev || pathq_dev || pathv_dev;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_track_mc_nav(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14,
-                                            scvx::Tiles{deriv_dev, nullptr}, kf_dev, CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol,
-                                            mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev,
-                                            navfed_dev, navK_dev, ctx->stream, any ? &q : nullptr, rg, vh));
-    return SCVX_OK;
-}
-
-static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
-                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
-                               const McRng* rg, const McVeh* vh = nullptr, const char* entry = "scvx_track_mc_nav_q_f64_host");
 
 }  // namespace scvx
 
 extern "C" {
 
+// Every entry point below fills one record from its arguments, as those of scvx_mc.hip do, with nav set and the estimate's group.
 int scvx_track_mc_nav_q_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                             const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
                             const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
                             const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
-                            double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev,
-                            double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
-                            double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev) {
-    return scvx::track_mc_nav_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
-                                    CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
-                                    jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, nq, ranks, flightq_dev,
-                                    pathq_dev, pathv_dev, nullptr);
+                            double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev, double* mcnav_dev,
+                            double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev, double* navK_dev, int nq,
+                            const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev) {
+    scvx::McCall c;
+    c.nav = true, c.B = B, c.K = K, c.S = S, c.x = x_dev, c.u = u_dev, c.sigma = sigma_dev, c.gain = gain_dev, c.C0 = C0_dev, c.w = w14;
+    c.deriv.d = deriv_dev, c.kf = kf_dev, c.CN = CN_dev, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol;
+    c.mcrep = mcrep_dev, c.xmean = xmean_dev, c.xcov = xcov_dev, c.jmean = jmean_dev, c.jcov = jcov_dev, c.mcnav = mcnav_dev;
+    c.flights = flights_dev, c.xland = xland_dev, c.dx0 = dx0_dev, c.navfed = navfed_dev, c.navK = navK_dev;
+    c.q = {nq, ranks, flightq_dev, pathq_dev, pathv_dev}, c.xi0 = xi0_dev, c.eta = eta_dev, c.xin = xin_dev, c.nud = nud_dev;
+    return scvx::mc_call_dev(ctx, c);
 }
 
-// the placeholders: xi0, xin and (with m > 0) nud any non-null pointer, eta non-null exactly when the truth receives impulses
-// (check_track_mc_nav's rules for them)
 int scvx_track_mc_nav_rng_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                               const double* gain_dev, const double* C0_dev, const scvx_mc_rng* rng, int noise, const double* w14,
                               const double* deriv_dev, const double* kf_dev, const double* CN_dev, int m, const double* H,
-                              const double* rm, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev,
-                              double* xcov_dev, double* jmean_dev, double* jcov_dev, double* mcnav_dev, double* flights_dev,
-                              double* xland_dev, double* dx0_dev, double* navfed_dev, double* navK_dev, int nq, const int* ranks,
-                              double* flightq_dev, double* pathq_dev, double* pathv_dev) {
-    const scvx::McRng rg{rng, noise};
-    return scvx::track_mc_nav_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, x_dev, noise ? x_dev : nullptr, w14, deriv_dev,
-                                    kf_dev, CN_dev, x_dev, x_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
-                                    jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, nq, ranks, flightq_dev,
-                                    pathq_dev, pathv_dev, &rg);
+                              const double* rm, int nsub, int flags, double tol, double* mcrep_dev, double* xmean_dev, double* xcov_dev,
+                              double* jmean_dev, double* jcov_dev, double* mcnav_dev, double* flights_dev, double* xland_dev,
+                              double* dx0_dev, double* navfed_dev, double* navK_dev, int nq, const int* ranks, double* flightq_dev,
+                              double* pathq_dev, double* pathv_dev) {
+    scvx::McCall c;
+    c.nav = true, c.B = B, c.K = K, c.S = S, c.x = x_dev, c.u = u_dev, c.sigma = sigma_dev, c.gain = gain_dev, c.C0 = C0_dev, c.w = w14;
+    c.deriv.d = deriv_dev, c.kf = kf_dev, c.CN = CN_dev, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol;
+    c.mcrep = mcrep_dev, c.xmean = xmean_dev, c.xcov = xcov_dev, c.jmean = jmean_dev, c.jcov = jcov_dev, c.mcnav = mcnav_dev;
+    c.flights = flights_dev, c.xland = xland_dev, c.dx0 = dx0_dev, c.navfed = navfed_dev, c.navK = navK_dev;
+    c.q = {nq, ranks, flightq_dev, pathq_dev, pathv_dev}, c.drawn = true, c.rng = rng, c.noise = noise;
+    return scvx::mc_call_dev(ctx, c);
 }
 
-int scvx_track_mc_nav_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                                   const double* gain, const double* C0, const scvx_mc_rng* rng, int noise, const double* w14,
-                                   const double* deriv, const double* kf, const double* CN, int m, const double* H, const double* rm,
-                                   int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov, double* jmean,
-                                   double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed,
-                                   double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
-    const scvx::McRng rg{rng, noise};
-    return scvx::track_mc_nav_q_host(ctx, B, K, S, x, u, sigma, gain, C0, x, noise ? x : nullptr, w14, deriv, kf, CN, x, x, m, H, rm, nsub,
-                                     flags, tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks,
-                                     flightq, pathq, pathv, &rg);
-}
-
-// the _veh forms: the _q call (rng == NULL) or the _rng call (its placeholders as above) with the vehicle errors behind it
 int scvx_track_mc_nav_veh_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
                               const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev,
                               const double* w14, const double* deriv_dev, const double* kf_dev, const double* CN_dev,
@@ -243,15 +144,54 @@ int scvx_track_mc_nav_veh_f64(scvx_ctx* ctx, int B, int K, int S, const double* 
                               double* mcnav_dev, double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev,
                               double* navK_dev, int nq, const int* ranks, double* flightq_dev, double* pathq_dev, double* pathv_dev,
                               const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta_dev, double* theta_dev) {
-    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0_dev, eta_dev, xin_dev, nud_dev, zeta_dev);
-    if (rc) return rc;
-    const scvx::McRng rg{rng, noise};
-    const scvx::McVeh vh{veh, zeta_dev, theta_dev};
-    if (rng) xi0_dev = xin_dev = nud_dev = x_dev, eta_dev = noise ? x_dev : nullptr;
-    return scvx::track_mc_nav_q_dev(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
-                                    CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
-                                    jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, nq, ranks, flightq_dev,
-                                    pathq_dev, pathv_dev, rng ? &rg : nullptr, &vh);
+    scvx::McCall c;
+    c.nav = true, c.B = B, c.K = K, c.S = S, c.x = x_dev, c.u = u_dev, c.sigma = sigma_dev, c.gain = gain_dev, c.C0 = C0_dev, c.w = w14;
+    c.deriv.d = deriv_dev, c.kf = kf_dev, c.CN = CN_dev, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol;
+    c.mcrep = mcrep_dev, c.xmean = xmean_dev, c.xcov = xcov_dev, c.jmean = jmean_dev, c.jcov = jcov_dev, c.mcnav = mcnav_dev;
+    c.flights = flights_dev, c.xland = xland_dev, c.dx0 = dx0_dev, c.navfed = navfed_dev, c.navK = navK_dev;
+    c.q = {nq, ranks, flightq_dev, pathq_dev, pathv_dev}, c.xi0 = xi0_dev, c.eta = eta_dev, c.xin = xin_dev, c.nud = nud_dev;
+    c.drawn = rng != nullptr, c.rng = rng, c.noise = noise, c.veh = {veh, zeta_dev, theta_dev};
+    return scvx::mc_call_dev(ctx, c);
+}
+
+int scvx_track_mc_nav_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
+                          const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
+                          const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
+                          const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
+                          double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev, double* mcnav_dev,
+                          double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev, double* navK_dev) {
+    return scvx_track_mc_nav_q_f64(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev,
+                                   CN_dev, xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev,
+                                   jcov_dev, mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, 0, nullptr, nullptr,
+                                   nullptr, nullptr);
+}
+
+int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                                 const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
+                                 const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
+                                 const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
+                                 double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
+                                 double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
+    scvx::McCall c;
+    c.nav = true, c.B = B, c.K = K, c.S = S, c.x = x, c.u = u, c.sigma = sigma, c.gain = gain, c.C0 = C0, c.w = w14, c.deriv.d = deriv;
+    c.kf = kf, c.CN = CN, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean;
+    c.xcov = xcov, c.jmean = jmean, c.jcov = jcov, c.mcnav = mcnav, c.flights = flights, c.xland = xland, c.dx0 = dx0, c.navfed = navfed;
+    c.navK = navK, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta, c.xin = xin, c.nud = nud;
+    return scvx::mc_call_host(ctx, c, "scvx_track_mc_nav_q_f64_host");
+}
+
+int scvx_track_mc_nav_rng_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
+                                   const double* gain, const double* C0, const scvx_mc_rng* rng, int noise, const double* w14,
+                                   const double* deriv, const double* kf, const double* CN, int m, const double* H, const double* rm,
+                                   int nsub, int flags, double tol, double* mcrep, double* xmean, double* xcov, double* jmean,
+                                   double* jcov, double* mcnav, double* flights, double* xland, double* dx0, double* navfed, double* navK,
+                                   int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
+    scvx::McCall c;
+    c.nav = true, c.B = B, c.K = K, c.S = S, c.x = x, c.u = u, c.sigma = sigma, c.gain = gain, c.C0 = C0, c.w = w14, c.deriv.d = deriv;
+    c.kf = kf, c.CN = CN, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean;
+    c.xcov = xcov, c.jmean = jmean, c.jcov = jcov, c.mcnav = mcnav, c.flights = flights, c.xland = xland, c.dx0 = dx0, c.navfed = navfed;
+    c.navK = navK, c.q = {nq, ranks, flightq, pathq, pathv}, c.drawn = true, c.rng = rng, c.noise = noise;
+    return scvx::mc_call_host(ctx, c, "scvx_track_mc_nav_rng_f64_host");
 }
 
 int scvx_track_mc_nav_veh_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
@@ -261,25 +201,13 @@ int scvx_track_mc_nav_veh_f64_host(scvx_ctx* ctx, int B, int K, int S, const dou
                                    double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                    double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
                                    const scvx_mc_rng* rng, int noise, const scvx_mc_vehicle* veh, const double* zeta, double* theta) {
-    int rc = scvx::check_mc_veh_draws(ctx, rng, noise, xi0, eta, xin, nud, zeta);
-    if (rc) return rc;
-    const scvx::McRng rg{rng, noise};
-    const scvx::McVeh vh{veh, zeta, theta};
-    if (rng) xi0 = xin = nud = x, eta = noise ? x : nullptr;
-    return scvx::track_mc_nav_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags, tol,
-                                     mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq,
-                                     pathv, rng ? &rg : nullptr, &vh, "scvx_track_mc_nav_veh_f64_host");
-}
-
-int scvx_track_mc_nav_f64(scvx_ctx* ctx, int B, int K, int S, const double* x_dev, const double* u_dev, const double* sigma_dev,
-                          const double* gain_dev, const double* C0_dev, const double* xi0_dev, const double* eta_dev, const double* w14,
-                          const double* deriv_dev, const double* kf_dev, const double* CN_dev, const double* xin_dev,
-                          const double* nud_dev, int m, const double* H, const double* rm, int nsub, int flags, double tol,
-                          double* mcrep_dev, double* xmean_dev, double* xcov_dev, double* jmean_dev, double* jcov_dev, double* mcnav_dev,
-                          double* flights_dev, double* xland_dev, double* dx0_dev, double* navfed_dev, double* navK_dev) {
-    return scvx_track_mc_nav_q_f64(ctx, B, K, S, x_dev, u_dev, sigma_dev, gain_dev, C0_dev, xi0_dev, eta_dev, w14, deriv_dev, kf_dev, CN_dev,
-                                   xin_dev, nud_dev, m, H, rm, nsub, flags, tol, mcrep_dev, xmean_dev, xcov_dev, jmean_dev, jcov_dev,
-                                   mcnav_dev, flights_dev, xland_dev, dx0_dev, navfed_dev, navK_dev, 0, nullptr, nullptr, nullptr, nullptr);
+    scvx::McCall c;
+    c.nav = true, c.B = B, c.K = K, c.S = S, c.x = x, c.u = u, c.sigma = sigma, c.gain = gain, c.C0 = C0, c.w = w14, c.deriv.d = deriv;
+    c.kf = kf, c.CN = CN, c.m = m, c.H = H, c.rm = rm, c.nsub = nsub, c.flags = flags, c.tol = tol, c.mcrep = mcrep, c.xmean = xmean;
+    c.xcov = xcov, c.jmean = jmean, c.jcov = jcov, c.mcnav = mcnav, c.flights = flights, c.xland = xland, c.dx0 = dx0, c.navfed = navfed;
+    c.navK = navK, c.q = {nq, ranks, flightq, pathq, pathv}, c.xi0 = xi0, c.eta = eta, c.xin = xin, c.nud = nud, c.drawn = rng != nullptr;
+    c.rng = rng, c.noise = noise, c.veh = {veh, zeta, theta};
+    return scvx::mc_call_host(ctx, c, "scvx_track_mc_nav_veh_f64_host");
 }
 
 int scvx_track_mc_nav_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
@@ -289,58 +217,8 @@ int scvx_track_mc_nav_f64_host(scvx_ctx* ctx, int B, int K, int S, const double*
                                double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
                                double* navfed, double* navK) {
     return scvx_track_mc_nav_q_f64_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr, nullptr,
-                                        nullptr, nullptr);
-}
-
-int scvx_track_mc_nav_q_f64_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                                 const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
-                                 const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                                 const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                                 double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                                 double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv) {
-    return scvx::track_mc_nav_q_host(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags, tol,
-                                     mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, nq, ranks, flightq, pathq,
-                                     pathv, nullptr);
+                                        tol, mcrep, xmean, xcov, jmean, jcov, mcnav, flights, xland, dx0, navfed, navK, 0, nullptr,
+                                        nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"
-
-namespace scvx {
-
-static int track_mc_nav_q_host(scvx_ctx* ctx, int B, int K, int S, const double* x, const double* u, const double* sigma,
-                               const double* gain, const double* C0, const double* xi0, const double* eta, const double* w14,
-                               const double* deriv, const double* kf, const double* CN, const double* xin, const double* nud, int m,
-                               const double* H, const double* rm, int nsub, int flags, double tol, double* mcrep, double* xmean,
-                               double* xcov, double* jmean, double* jcov, double* mcnav, double* flights, double* xland, double* dx0,
-                               double* navfed, double* navK, int nq, const int* ranks, double* flightq, double* pathq, double* pathv,
-                               const McRng* rg, const McVeh* vh, const char* entry) {
-    int rc = scvx::check_track_mc_nav(ctx, B, K, S, x, u, sigma, gain, C0, xi0, eta, w14, deriv, kf, CN, xin, nud, m, H, rm, nsub, flags,
-                                      tol, mcrep, xmean, xcov, jmean, jcov, mcnav);
-    if (rc) return rc;
-    if (rg && (rc = scvx::check_mc_rng(ctx, rg->r))) return rc;
-    if (rg) xi0 = eta = xin = nud = nullptr;   // placeholders until here: the lanes make the draws
-    if ((rc = scvx::check_mc_q(ctx, S, nq, ranks, flightq, pathq))) return rc;
-    if (vh && (rc = scvx::check_mc_vehicle(ctx, vh->v, vh->zeta, vh->theta, rg != nullptr))) return rc;
-    if (vh && !vh->v) vh = nullptr;   // veh == NULL: the call without vehicle errors
-    const Dims d(B, K, scvx_control_dim(ctx), S, m, nq);
-    Staging s(ctx);
-    McVeh dvh;   // the vehicle errors with zeta and theta on the device
-    if (vh) dvh.v = vh->v, dvh.zeta = s.in(rg ? nullptr : vh->zeta, d.zeta), dvh.theta = s.out(vh->theta, d.theta);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *ds = s.in(sigma, d.b), *dg = s.in(gain, d.gain), *dc = s.in(C0, d.c14),
-                 *di = s.in(xi0, d.xi), *de = s.in(eta, d.eta), *dd = s.in(deriv, d.deriv), *dk = s.in(m > 0 ? kf : nullptr, d.kf),
-                 *dcn = s.in(CN, d.c14), *dxi = s.in(xin, d.xi), *dnu = s.in(m > 0 ? nud : nullptr, d.nud);
-    double *dr = s.out(mcrep, d.mcrep), *dm = s.out(xmean, d.b14), *dv = s.out(xcov, d.c14), *djm = s.out(jmean, d.jmean),
-           *djc = s.out(jcov, d.jcov), *dnv = s.out(mcnav, d.nrep), *df = s.out(flights, d.flights), *dl = s.out(xland, d.s14),
-           *d0 = s.out(dx0, d.s14), *dfe = s.out(navfed, d.fed), *dnk = s.out(navK, d.s14);
-    McQ q;
-    q.nq = nq, q.ranks = ranks, q.flightq = s.out(flightq, d.flightq), q.pathq = s.out(pathq, d.pathq), q.pathv = s.out(pathv, d.pathv);
-    s.launch([&] {
-        return launch_track_mc_nav(ctx, B, K, S, dx, du, ds, dg, dc, di, de, w14, Tiles{dd, nullptr}, dk, dcn, dxi, dnu, m, H, rm, nsub, flags,
-                                   tol, dr, dm, dv, djm, djc, dnv, df, dl, d0, dfe, dnk, s.st, (flightq || pathq || pathv) ? &q : nullptr, rg,
-                                   vh ? &dvh : nullptr);
-    });
-    return s.finish(entry);
-}
-
-}  // namespace scvx

@@ -14,7 +14,9 @@
 // was linked against the staging code as it stood BEFORE csrc/scvx_stage.hpp existed; the test requires the same lines, so the staging
 // helper allocates, copies, launches and synchronises exactly what the hand-written sequences did.  And the runtime can make the n-th
 // hipMalloc, hipMemcpyAsync or launch of a call fail: sweep() does that at every position of one small call of every form and checks the
-// error contract of scvx::Staging.  tests/test_host_staging_sanitizers.py holds the build recipe and runs the program.
+// error contract of scvx::Staging.  refusals() pins what the sampled calls refuse, in which words, and which of two faults wins
+// (tests/golden/mc_refusals.txt).  tests/test_host_staging_sanitizers.py holds the build recipe and runs the program.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -362,7 +364,185 @@ static int error_paths() {
     return 0;
 }
 
+// ---- the refusals ----------------------------------------------------------------------------------------------------------------------
+// Every argument of the sixteen scvx_track_mc* forms, valid for B = 2, K = 3, S = 2, NU = 3 and m rows, each array of its documented
+// size.  refusals() starts every form from this call, makes one argument (or two) bad and prints "refusal <entry> <case> <rc> <message>";
+// a refused call allocates nothing.  tests/golden/mc_refusals.txt holds the lines as the six hand-written bodies gave them, before
+// check_mc_call replaced their checks: which message a bad call gets, and which fault wins when two are present.
+enum { F_NAV = 1, F_Q = 2, F_UP = 4, F_RNG = 8, F_VEH = 16, F_TRUTH = 32, F_M = 64 };
+struct McArgs {
+    int B = 2, K = 3, S = 2, m, nsub = 10, flags = 0, nq = 1, noise = 0;
+    double tol = 0.0;
+    V vx, vu, vsg, vgain, vC0, vxi0, veta, vw, vderiv, vkf, vCN, vxin, vnud, vH, vrm, vzeta, vrep, vxm, vxc, vjm, vjc, vnv, vfl, vxl, vd0, vfed,
+        vnk, vfq, vpq, vpv, vth;
+    std::vector<int> vranks{1};
+    const double *x, *u, *sigma, *gain, *C0, *xi0, *eta, *w, *deriv, *kf, *CN, *xin, *nud, *H, *rm, *zeta = nullptr;
+    const void* reserved = nullptr;
+    double *mcrep, *xmean, *xcov, *jmean, *jcov, *mcnav, *flights, *xland, *dx0, *navfed, *navK, *flightq, *pathq, *pathv, *theta = nullptr;
+    const int* ranks;
+    scvx_mc_rng rngv{20261020u, 0u, 0u, 0, 0};
+    const scvx_mc_rng* rng = nullptr;
+    scvx_mc_vehicle vehv{};
+    const scvx_mc_vehicle* veh = nullptr;
+    scvx_ctx ctx;
+    McArgs(int traits, int m_)
+        : m(m_), vx(2 * 4 * 14, 1.0), vu(2 * 4 * 3, 1.0), vsg(2, 1.0), vgain(2 * 3 * 3 * 17), vC0(2 * 196), vxi0(2 * 14), veta(2 * 3 * 14),
+          vw(14, 1e-3), vderiv(2 * 3 * 14 * 21), vkf(2 * 3 * 14 * (m_ ? m_ : 1)), vCN(2 * 196), vxin(2 * 14), vnud(2 * 3 * (m_ ? m_ : 1)),
+          vH((m_ ? m_ : 1) * 14, 0.0), vrm(m_ ? m_ : 1, 1e-6), vzeta(2 * SCVX_VEH_N), vrep(2 * SCVX_MC_NREP), vxm(2 * 14), vxc(2 * 196),
+          vjm(2 * 28), vjc(2 * 784), vnv(2 * SCVX_NAV_NREP), vfl(2 * 2 * SCVX_FLIGHT_NREP), vxl(2 * 2 * 14), vd0(2 * 2 * 14),
+          vfed(2 * 2 * 3 * 14), vnk(2 * 2 * 14), vfq(2 * 16), vpq(2 * 4 * 5), vpv(2 * 4 * 5 * 2), vth(2 * 2 * SCVX_VEH_N) {
+        x = vx.data(), u = vu.data(), sigma = vsg.data(), gain = vgain.data(), C0 = vC0.data(), w = vw.data(), deriv = vderiv.data();
+        CN = vCN.data(), kf = m ? vkf.data() : nullptr, H = m ? vH.data() : nullptr, rm = m ? vrm.data() : nullptr;
+        const bool up = traits & F_UP;
+        xi0 = up ? vxi0.data() : nullptr, eta = up ? veta.data() : nullptr, xin = up ? vxin.data() : nullptr;
+        nud = up && m ? vnud.data() : nullptr;
+        mcrep = vrep.data(), xmean = vxm.data(), xcov = vxc.data(), jmean = vjm.data(), jcov = vjc.data(), mcnav = vnv.data();
+        flights = vfl.data(), xland = vxl.data(), dx0 = vd0.data(), navfed = vfed.data(), navK = vnk.data();
+        flightq = vfq.data(), pathq = vpq.data(), pathv = vpv.data(), ranks = vranks.data();
+        if (traits & F_RNG) rng = &rngv, noise = 1;
+        if (traits & F_VEH) {
+            vehv.sp[SCVX_VEH_THRUST] = 1e-3;
+            veh = &vehv, theta = vth.data(), zeta = up ? vzeta.data() : nullptr;
+        }
+        ctx.prob.K = K;
+    }
+    McArgs(const McArgs&) = delete;
+};
+
+struct McForm {
+    const char* entry;
+    int traits;
+    int (*call)(McArgs&);
+};
+#define MC_A &a.ctx, a.B, a.K, a.S, a.x, a.u, a.sigma, a.gain, a.C0
+#define MC_T a.w, a.reserved, a.nsub, a.flags, a.tol, a.mcrep, a.xmean, a.xcov, a.flights, a.xland, a.dx0
+#define MC_N1 a.w, a.deriv, a.kf, a.CN
+#define MC_N2 \
+    a.m, a.H, a.rm, a.nsub, a.flags, a.tol, a.mcrep, a.xmean, a.xcov, a.jmean, a.jcov, a.mcnav, a.flights, a.xland, a.dx0, a.navfed, a.navK
+#define MC_Q a.nq, a.ranks, a.flightq, a.pathq, a.pathv
+#define MC_V a.rng, a.noise, a.veh, a.zeta, a.theta
+#define MC_FORM(name, traits, ...) {#name, traits, [](McArgs& a) { return name(__VA_ARGS__); }}
+#define MC_BOTH(name, traits, ...) MC_FORM(name, traits, __VA_ARGS__), MC_FORM(name##_host, traits, __VA_ARGS__)
+static const McForm g_forms[] = {
+    MC_BOTH(scvx_track_mc_f64, F_TRUTH | F_UP, MC_A, a.xi0, a.eta, MC_T),
+    MC_BOTH(scvx_track_mc_q_f64, F_TRUTH | F_UP | F_Q, MC_A, a.xi0, a.eta, MC_T, MC_Q),
+    MC_BOTH(scvx_track_mc_rng_f64, F_TRUTH | F_RNG | F_Q, MC_A, a.rng, a.noise, MC_T, MC_Q),
+    MC_BOTH(scvx_track_mc_nav_f64, F_NAV | F_UP, MC_A, a.xi0, a.eta, MC_N1, a.xin, a.nud, MC_N2),
+    MC_BOTH(scvx_track_mc_nav_q_f64, F_NAV | F_UP | F_Q, MC_A, a.xi0, a.eta, MC_N1, a.xin, a.nud, MC_N2, MC_Q),
+    MC_BOTH(scvx_track_mc_nav_rng_f64, F_NAV | F_RNG | F_Q, MC_A, a.rng, a.noise, MC_N1, MC_N2, MC_Q),
+    // the _veh forms, on uploaded draws and with rng: tests/host_staging_vehicle_asan.cpp
+    MC_BOTH(scvx_track_mc_veh_f64, F_TRUTH | F_UP | F_Q | F_VEH, MC_A, a.xi0, a.eta, MC_T, MC_Q, MC_V),
+    MC_BOTH(scvx_track_mc_veh_f64, F_TRUTH | F_RNG | F_Q | F_VEH, MC_A, a.xi0, a.eta, MC_T, MC_Q, MC_V),
+    MC_BOTH(scvx_track_mc_nav_veh_f64, F_NAV | F_UP | F_Q | F_VEH, MC_A, a.xi0, a.eta, MC_N1, a.xin, a.nud, MC_N2, MC_Q, MC_V),
+    MC_BOTH(scvx_track_mc_nav_veh_f64, F_NAV | F_RNG | F_Q | F_VEH, MC_A, a.xi0, a.eta, MC_N1, a.xin, a.nud, MC_N2, MC_Q, MC_V),
+};
+
+// one bad argument: applies to the forms that have every trait of `need` and none of `not_`
+struct McFault {
+    const char* name;
+    int need, not_;
+    std::function<void(McArgs&)> make;
+};
+static const double g_nan = std::nan(""), g_wneg[14] = {1e-3, 1e-3, -1e-3}, g_wnan[14] = {1e-3, g_nan};
+static const int g_rank_lo[1] = {-1}, g_rank_hi[1] = {2};
+#define BAD(name, need, not_, ...) {name, need, not_, [](McArgs& a) { __VA_ARGS__; }}
+static const McFault g_faults[] = {
+    BAD("x=NULL", 0, 0, a.x = nullptr), BAD("u=NULL", 0, 0, a.u = nullptr), BAD("sigma=NULL", 0, 0, a.sigma = nullptr),
+    BAD("gain=NULL", 0, 0, a.gain = nullptr), BAD("C0=NULL", 0, 0, a.C0 = nullptr), BAD("xi0=NULL", F_UP, 0, a.xi0 = nullptr),
+    BAD("mcrep=NULL", 0, 0, a.mcrep = nullptr), BAD("xmean=NULL", 0, 0, a.xmean = nullptr), BAD("xcov=NULL", 0, 0, a.xcov = nullptr),
+    BAD("deriv=NULL", F_NAV, 0, a.deriv = nullptr), BAD("CN=NULL", F_NAV, 0, a.CN = nullptr), BAD("xin=NULL", F_NAV | F_UP, 0, a.xin = nullptr),
+    BAD("jmean=NULL", F_NAV, 0, a.jmean = nullptr), BAD("jcov=NULL", F_NAV, 0, a.jcov = nullptr), BAD("mcnav=NULL", F_NAV, 0, a.mcnav = nullptr),
+    BAD("B=0", 0, 0, a.B = 0), BAD("B=65536", 0, 0, a.B = 65536), BAD("S=0", 0, 0, a.S = 0), BAD("K=4", 0, 0, a.K = 4),
+    BAD("nsub=0", 0, 0, a.nsub = 0), BAD("nsub=1001", 0, 0, a.nsub = 1001), BAD("flags=2", 0, 0, a.flags = 2),
+    BAD("tol=-1", 0, 0, a.tol = -1.0), BAD("tol=NaN", 0, 0, a.tol = g_nan), BAD("w<0", 0, 0, a.w = g_wneg), BAD("w=NaN", 0, 0, a.w = g_wnan),
+    BAD("eta-without-w", 0, 0, a.w = nullptr), BAD("reserved", F_TRUTH, 0, a.reserved = &a),
+    BAD("rng=NULL", F_RNG, F_VEH, a.rng = nullptr), BAD("rng.reserved=1", F_RNG, 0, a.rngv.reserved = 1),
+    BAD("rng.independent=2", F_RNG, 0, a.rngv.independent = 2),
+    BAD("nq=0", F_Q, 0, a.nq = 0), BAD("nq=17", F_Q, 0, a.nq = SCVX_Q_MAX + 1), BAD("ranks=NULL", F_Q, 0, a.ranks = nullptr),
+    BAD("rank=-1", F_Q, 0, a.ranks = g_rank_lo), BAD("rank=S", F_Q, 0, a.ranks = g_rank_hi),
+    BAD("zeta-without-veh", F_VEH | F_UP, 0, a.veh = nullptr, a.theta = nullptr), BAD("theta-without-veh", F_VEH, 0, a.veh = nullptr, a.zeta = nullptr),
+    BAD("veh.reserved=1", F_VEH, 0, a.vehv.reserved[1] = 1), BAD("veh.mu=NaN", F_VEH, 0, a.vehv.mu[SCVX_VEH_ISP] = g_nan),
+    BAD("veh.sp<0", F_VEH, 0, a.vehv.sp[SCVX_VEH_ISP] = -1.0), BAD("veh.sp=NaN", F_VEH, 0, a.vehv.sp[SCVX_VEH_ISP] = g_nan),
+    BAD("veh.aero", F_VEH, 0, a.vehv.mu[SCVX_VEH_AERO] = 1e-3), BAD("veh.fin", F_VEH, 0, a.vehv.sp[SCVX_VEH_FIN] = 1e-3),
+    BAD("veh.sp-without-zeta", F_VEH | F_UP, 0, a.zeta = nullptr),
+    BAD("rng+xi0", F_VEH | F_RNG, 0, a.xi0 = a.vxi0.data()), BAD("rng+zeta", F_VEH | F_RNG, 0, a.zeta = a.vzeta.data()),
+    BAD("noise-without-rng", F_VEH | F_UP, 0, a.noise = 1),
+    BAD("m=-1", F_NAV, 0, a.m = -1), BAD("m=15", F_NAV, 0, a.m = 15), BAD("H=NULL", F_NAV | F_M, 0, a.H = nullptr),
+    BAD("rm=NULL", F_NAV | F_M, 0, a.rm = nullptr), BAD("kf=NULL", F_NAV | F_M, 0, a.kf = nullptr),
+    BAD("nud=NULL", F_NAV | F_M | F_UP, 0, a.nud = nullptr),
+    BAD("aero-without-table", 0, 0, a.ctx.prob.aero_kind = 1),
+};
+// two faults at once: the first named is of the part every form shares, or of an earlier check than the second
+static const char* const g_pairs[][2] = {
+    {"B=0", "rng.reserved=1"}, {"x=NULL", "rng=NULL"}, {"B=0", "nq=17"}, {"xcov=NULL", "rank=S"}, {"B=0", "veh.reserved=1"},
+    {"x=NULL", "theta-without-veh"}, {"x=NULL", "w<0"}, {"aero-without-table", "w=NaN"}, {"B=0", "m=15"}, {"C0=NULL", "H=NULL"},
+    {"tol=NaN", "CN=NULL"}, {"mcrep=NULL", "kf=NULL"}, {"B=0", "noise-without-rng"}, {"S=0", "rng+xi0"}, {"w<0", "reserved"},
+    {"rng.reserved=1", "nq=0"}, {"rank=-1", "veh.mu=NaN"}, {"rng.independent=2", "veh.fin"}, {"m=-1", "jcov=NULL"}, {"w=NaN", "m=15"},
+    {"CN=NULL", "kf=NULL"}, {"nud=NULL", "nq=17"},
+};
+
+static const McFault* fault(const char* name, int traits) {
+    for (const McFault& f : g_faults)
+        if (!strcmp(f.name, name)) return (traits & f.need) == f.need && !(traits & f.not_) ? &f : nullptr;
+    fprintf(stderr, "no fault named %s\n", name);
+    abort();
+}
+
+static int refuse(const McForm& fm, int traits, int m, const McFault* f1, const McFault* f2) {
+    McArgs a(traits, m);
+    if (f1) f1->make(a);
+    if (f2) f2->make(a);
+    const size_t a0 = g_allocs;
+    const int rc = fm.call(a);
+    printf("refusal %s%s m=%d/%s%s%s %d %s\n", fm.entry, (traits & (F_VEH | F_RNG)) == (F_VEH | F_RNG) ? "+rng" : "", m,
+           f1 ? f1->name : "valid", f2 ? "+" : "", f2 ? f2->name : "", rc, a.ctx.err.empty() ? "-" : a.ctx.err.c_str());
+    if (f1) REQUIRE(rc != SCVX_OK && g_allocs == a0);
+    else REQUIRE(rc == SCVX_OK);
+    scvx::mc_workspace_free(&a.ctx);
+    return 0;
+}
+
+// veh: the _veh forms (their checks live in scvx_mc_veh.hip, which only the vehicle program links) or all the others
+static int refusals(bool veh) {
+    g_nu = 3;
+    for (const McForm& fm : g_forms) {
+        if (veh != ((fm.traits & F_VEH) != 0)) continue;
+        for (int m : {0, 2}) {
+            if (m && !(fm.traits & F_NAV)) continue;
+            const int traits = fm.traits | (m ? F_M : 0);
+            if (refuse(fm, traits, m, nullptr, nullptr)) return 1;
+            for (const McFault& f : g_faults)
+                if (fault(f.name, traits) && refuse(fm, traits, m, &f, nullptr)) return 1;
+            for (const auto& p : g_pairs) {
+                const McFault *f1 = fault(p[0], traits), *f2 = fault(p[1], traits);
+                if (f1 && f2 && refuse(fm, traits, m, f1, f2)) return 1;
+            }
+        }
+    }
+    if (veh) return 0;
+    // scvx_mc_draws_f64[_host]
+    V d0(2 * 2 * 14), dk(2 * 2 * 3 * 14);
+    struct {
+        const char* name;
+        int rng, reserved, independent, P, S, K;
+    } const draws[] = {{"rng=NULL", 0, 0, 0, 2, 2, 3},     {"rng.reserved=1", 1, 1, 0, 2, 2, 3}, {"rng.independent=2", 1, 0, 2, 2, 2, 3},
+                       {"P=0", 1, 0, 0, 0, 2, 3},          {"P=65536", 1, 0, 0, 65536, 2, 3},    {"S=0", 1, 0, 0, 2, 0, 3},
+                       {"K=0", 1, 0, 0, 2, 2, 0},          {"rng=NULL+P=0", 0, 0, 0, 0, 2, 3},   {"rng.reserved=1+S=0", 1, 1, 0, 2, 0, 3}};
+    for (int host = 0; host < 2; host++)
+        for (const auto& c : draws) {
+            scvx_ctx ctx;
+            const scvx_mc_rng rg{1u, 0u, 0u, c.independent, c.reserved};
+            const size_t a0 = g_allocs;
+            const int rc = (host ? scvx_mc_draws_f64_host : scvx_mc_draws_f64)(&ctx, c.rng ? &rg : nullptr, c.P, c.S, c.K, d0.data(), dk.data(),
+                                                                               d0.data(), dk.data());
+            printf("refusal %s %s %d %s\n", host ? "scvx_mc_draws_f64_host" : "scvx_mc_draws_f64", c.name, rc, ctx.err.c_str());
+            REQUIRE(rc != SCVX_OK && g_allocs == a0);
+        }
+    return 0;
+}
+
 int main() {
+    if (refusals(false)) return 1;
     for (int nu : {3, 5})
         for (int m : {0, 6})
             for (int nq : {0, 1, 16})

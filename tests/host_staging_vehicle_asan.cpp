@@ -133,6 +133,7 @@ static int veh_error_paths() {
 }
 
 int main() {
+    if (refusals(true)) return 1;   // the _veh forms of the table of tests/host_staging_asan.cpp
     for (int nu : {3, 5})
         for (int m : {0, 6})
             for (int nq : {0, 16})

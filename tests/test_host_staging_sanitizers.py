@@ -50,6 +50,21 @@ def build_program(tmp_path, csrc=CSRC):
     return exe
 
 
+def golden_lines(name, prefix, keep=lambda line: True):
+    """the lines of tests/golden/<name>, every one beginning with `prefix`, that `keep` selects"""
+    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
+        want = f.read().splitlines()
+    assert all(line.startswith(prefix) for line in want)
+    return [line for line in want if keep(line)]
+
+
+def require_same_lines(got, want, at_least):
+    assert len(want) > at_least
+    for g, w in zip(got, want):
+        assert g == w
+    assert len(got) == len(want)
+
+
 def test_host_staging_is_clean_under_asan_and_ubsan(tmp_path):
     exe = build_program(tmp_path)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
@@ -59,13 +74,11 @@ def test_host_staging_is_clean_under_asan_and_ubsan(tmp_path):
     assert "sanitizers on" in run.stdout                              # the objects really are instrumented
     assert "host staging:" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
     # the same allocations, copies, launches and synchronises, call by call, as the staging code made before the helper: equality
-    with open(os.path.join(ROOT, "tests", "golden", "host_staging_traffic.txt")) as f:
-        want = f.read().splitlines()
-    got = [line for line in run.stdout.splitlines() if line.startswith("traffic ")]
-    assert len(want) > 200 and all(line.startswith("traffic ") for line in want)
-    for g, w in zip(got, want):
-        assert g == w
-    assert len(got) == len(want)
+    require_same_lines([line for line in run.stdout.splitlines() if line.startswith("traffic ")],
+                       golden_lines("host_staging_traffic.txt", "traffic "), 200)
+    # what the sampled calls refuse, in which words, and which of two faults wins: as the six hand-written bodies had it
+    require_same_lines([line for line in run.stdout.splitlines() if line.startswith("refusal ")],
+                       golden_lines("mc_refusals.txt", "refusal ", lambda line: "_veh_" not in line), 700)
     # every allocation, copy and launch of one call of each form was made to fail, and the error contract held
     swept = [line.split()[2].rstrip(":") for line in run.stdout.splitlines() if line.startswith("error path ")]
     assert swept == list(SWEPT)

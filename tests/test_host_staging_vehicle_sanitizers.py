@@ -45,5 +45,10 @@ def test_vehicle_staging_is_clean_under_asan_and_ubsan(tmp_path):
     assert "host staging (vehicle errors):" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
     calls = [line for line in run.stdout.splitlines() if line.startswith("traffic veh ") and "_veh_" in line]
     assert len(calls) == 17 * 9
+    # the traffic and the refusals of the _veh forms, as the hand-written bodies had them before check_mc_call and stage_mc
+    hs.require_same_lines([line for line in run.stdout.splitlines() if line.startswith("traffic ")],
+                          hs.golden_lines("host_staging_vehicle_traffic.txt", "traffic "), 200)
+    hs.require_same_lines([line for line in run.stdout.splitlines() if line.startswith("refusal ")],
+                          hs.golden_lines("mc_refusals.txt", "refusal ", lambda line: "_veh_" in line), 600)
     swept = [line.split()[2].rstrip(":") for line in run.stdout.splitlines() if line.startswith("error path ")]
     assert swept == list(SWEPT)
