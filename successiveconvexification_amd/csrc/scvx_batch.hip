@@ -34,7 +34,7 @@
 #include <cstdio>
 #include "scvx_socp.hpp"
 #include "scvx_mc.hpp"   // McQ: what the _q forms of the sampled calls add
-#include "scvx_stage.hpp"
+#include "scvx_cov.hpp"   // CovCall: the record of the first-order analyses
 
 using scvx::fail;
 
@@ -952,43 +952,36 @@ static int enqueue_vehicle_tiles(scvx_batch* b, hipStream_t st) {
     return SCVX_OK;
 }
 
-int scvx_batch_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
-                       double* report, double* sig, double* covK, double* cov, const double* sp6) {
+// The four batch-level analyses: the record of scvx_cov.hpp with the plan, the gains, the tiles and the vehicle tiles the batch's own.
+// Every check comes before anything is enqueued.
+static int batch_cov_call(scvx_batch* b, scvx::CovCall c, const scvx::CovBatch& own, const char* entry) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
-    // every check before anything is enqueued
-    if (!S0) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
-    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
-    if ((rc = scvx::check_cov_vehicle(ctx, b, sp6))) return rc;   // the tiles are the batch's own: never missing
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    if ((rc = enqueue_vehicle_tiles(b, ctx->stream))) return rc;
-    const scvx::Dims d(b->B, b->K, b->NU);
+    c.B = b->B, c.K = b->K;
+    if ((rc = scvx::check_cov_call(ctx, c, &own))) return rc;
+    if ((rc = enqueue_track_gains(b, own.q14, own.rNU, own.qf14))) return rc;
+    if (c.veh && (rc = enqueue_vehicle_tiles(b, ctx->stream))) return rc;
+    const scvx::Dims d(c.B, c.K, b->NU, 0, c.m);
     scvx::Staging s(ctx);
-    const double* d0 = s.in(S0, d.c14);
-    double *dr = s.out_always(report, d.crep), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK), *dc = s.out(cov, d.cov);
-    const scvx::CovVeh v(b->vtile, sp6, nullptr);
-    s.launch([&] {
-        return scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, w14, dr, ds, dk, dc, s.st, nullptr, &v);
-    });
-    return s.finish("scvx_batch_cov_veh");
+    scvx::CovCall dev = scvx::stage_cov(s, d, c, true);
+    dev.x = b->x, dev.u = b->u, dev.deriv = b->tiles(), dev.gain = b->track_gain, dev.vtile = b->vtile;
+    s.launch([&] { return scvx::launch_cov_call(ctx, dev, s.st); });
+    return s.finish(entry);
+}
+
+int scvx_batch_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
+                       double* report, double* sig, double* covK, double* cov, const double* sp6) {
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.report = report, c.sig = sig, c.covK = covK, c.cov = cov, c.veh = true, c.sp6 = sp6;
+    return batch_cov_call(b, c, {q14, rNU, qf14}, "scvx_batch_cov_veh");
 }
 
 int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
                    double* report, double* sig, double* covK, double* cov) {
-    int rc = check_batch(b, true);
-    if (rc) return rc;
-    scvx_ctx* ctx = b->ctx;
-    // every check before anything is enqueued
-    if (!S0) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
-    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const scvx::Dims d(b->B, b->K, b->NU);
-    scvx::Staging s(ctx);
-    const double* d0 = s.in(S0, d.c14);
-    double *dr = s.out_always(report, d.crep), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK), *dc = s.out(cov, d.cov);
-    s.launch([&] { return scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, w14, dr, ds, dk, dc, s.st); });
-    return s.finish("scvx_batch_cov");
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.report = report, c.sig = sig, c.covK = covK, c.cov = cov;
+    return batch_cov_call(b, c, {q14, rNU, qf14}, "scvx_batch_cov");
 }
 
 int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* dx0,
@@ -1033,11 +1026,12 @@ static int batch_track_mc_call(scvx_batch* b, scvx::McCall c, const scvx::McBatc
     if (c.nav) {
         dev.deriv = b->tiles(), dev.kf = dk;
         s.launch([&] { return hipMemsetAsync(dz, 0, d.c14 * 8, s.st); });
-        if (c.m > 0)
-            s.launch([&] {
-                return scvx::launch_nav_cov(ctx, c.B, c.K, b->x, b->u, b->tiles(), b->track_gain, dz, dn0, c.m, c.H, c.rm, c.w, dcr, dnr,
-                                            nullptr, nullptr, dk, nullptr, s.st);
-            });
+        if (c.m > 0) {
+            scvx::CovCall kc;
+            kc.B = c.B, kc.K = c.K, kc.x = b->x, kc.u = b->u, kc.deriv = b->tiles(), kc.gain = b->track_gain, kc.S0 = dz, kc.w = c.w;
+            kc.report = dcr, kc.nav = true, kc.N0 = dn0, kc.m = c.m, kc.H = c.H, kc.rm = c.rm, kc.navrep = dnr, kc.kf = dk;
+            s.launch([&] { return scvx::launch_cov_call(ctx, kc, s.st); });
+        }
     }
     s.launch([&] { return scvx::launch_mc(ctx, dev, s.st); });
     return s.finish(entry);
@@ -1136,49 +1130,19 @@ int scvx_batch_track_mc_nav(scvx_batch* b, const double* q14, const double* rNU,
 int scvx_batch_nav_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0,
                            int m, const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
                            double* navsig, double* kf, double* joint, const double* sp6) {
-    int rc = check_batch(b, true);
-    if (rc) return rc;
-    scvx_ctx* ctx = b->ctx;
-    // every check before anything is enqueued
-    if (!S0 || !N0) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (S0, N0)");
-    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
-    if ((rc = scvx::check_nav_model(ctx, m, H, rm))) return rc;
-    if ((rc = scvx::check_cov_vehicle(ctx, b, sp6))) return rc;
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    if ((rc = enqueue_vehicle_tiles(b, ctx->stream))) return rc;
-    const scvx::Dims d(b->B, b->K, b->NU, 0, m);
-    scvx::Staging s(ctx);
-    const double *d0 = s.in(S0, d.c14), *dn = s.in(N0, d.c14);
-    double *dr = s.out_always(report, d.crep), *dq = s.out_always(navrep, d.nrep), *ds = s.out(sig, d.sig), *dv = s.out(navsig, d.navsig),
-           *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint);
-    const scvx::CovVeh v(b->vtile, sp6, nullptr);
-    s.launch([&] {
-        return scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st,
-                                    nullptr, &v);
-    });
-    return s.finish("scvx_batch_nav_cov_veh");
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.report = report, c.sig = sig, c.nav = true, c.N0 = N0, c.m = m, c.H = H, c.rm = rm, c.navrep = navrep;
+    c.navsig = navsig, c.kf = kf, c.joint = joint, c.veh = true, c.sp6 = sp6;
+    return batch_cov_call(b, c, {q14, rNU, qf14}, "scvx_batch_nav_cov_veh");
 }
 
 int scvx_batch_nav_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* N0, int m,
                        const double* H, const double* rm, const double* w14, double* report, double* navrep, double* sig,
                        double* navsig, double* kf, double* joint) {
-    int rc = check_batch(b, true);
-    if (rc) return rc;
-    scvx_ctx* ctx = b->ctx;
-    // every check before anything is enqueued
-    if (!S0 || !N0) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (S0, N0)");
-    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
-    if ((rc = scvx::check_nav_model(ctx, m, H, rm))) return rc;
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    const scvx::Dims d(b->B, b->K, b->NU, 0, m);
-    scvx::Staging s(ctx);
-    const double *d0 = s.in(S0, d.c14), *dn = s.in(N0, d.c14);
-    double *dr = s.out_always(report, d.crep), *dq = s.out_always(navrep, d.nrep), *ds = s.out(sig, d.sig), *dv = s.out(navsig, d.navsig),
-           *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint);
-    s.launch([&] {
-        return scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st);
-    });
-    return s.finish("scvx_batch_nav_cov");
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.report = report, c.sig = sig, c.nav = true, c.N0 = N0, c.m = m, c.H = H, c.rm = rm, c.navrep = navrep;
+    c.navsig = navsig, c.kf = kf, c.joint = joint;
+    return batch_cov_call(b, c, {q14, rNU, qf14}, "scvx_batch_nav_cov");
 }
 
 int scvx_batch_set_trajectory(scvx_batch* b, const double* traj) {
@@ -1280,71 +1244,43 @@ int scvx_batch_get_path_margins(scvx_batch* b, double* pm) {
     return SCVX_OK;
 }
 
-// the navigation model of scvx_batch_margins_from_nav (nullptr: the covariance-driven calls)
-struct NavModel {
-    const double* N0;
-    int m;
-    const double *H, *rm;
-};
-
-// the covariance- and the navigation-driven calls; thrust_call: scvx_batch_thrust_margins_from_cov, whose refusals keep their wording
-static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
-                            double nsigma, double cap, unsigned which, double* psig, bool thrust_call, const NavModel* nav = nullptr,
-                            bool veh = false, const double* sp6 = nullptr) {
+// The covariance- and the navigation-driven margins calls: c holds S0 (and N0, the navigation model, sp6) as the caller gave them; the
+// analysis runs on the batch's persistent copies and keeps psig alone.  own.thrust: scvx_batch_thrust_margins_from_cov.
+static int margins_from_cov(scvx_batch* b, scvx::CovCall c, const scvx::CovBatch& own, double* psig) {
     int rc = check_batch(b, true);
     if (rc) return rc;
     scvx_ctx* ctx = b->ctx;
     // every check before anything is enqueued
-    const std::string who = thrust_call ? "thrust margins: " : nav ? "margins from nav: " : "margins from cov: ";
-    if (!S0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (S0)");
-    if (nav && !nav->N0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (N0)");
-    if (!(nsigma >= 0.0) || !std::isfinite(nsigma)) return fail(ctx, SCVX_ERR_ARG, who + "nsigma must be finite and >= 0");
-    if (!(cap > 0.0 && cap < 0.5))
-        return fail(ctx, SCVX_ERR_ARG, who + (thrust_call ? "cap must lie in (0, 0.5), a fraction of Tmax - Tmin"
-                                                          : "cap must lie in (0, 0.5), a fraction of the constraint's width"));
-    if (which == 0u || (which & ~(unsigned)SCVX_MARGIN_ALL))
-        return fail(ctx, SCVX_ERR_ARG, (nav ? who : std::string("margins from cov: ")) + "which must be a non-empty mask of SCVX_MARGIN_*");
-    if ((rc = scvx::check_cov_noise(ctx, w14))) return rc;
-    if (nav && (rc = scvx::check_nav_model(ctx, nav->m, nav->H, nav->rm))) return rc;
-    if ((rc = scvx::check_track_weights(ctx, q14, rNU, qf14))) return rc;
-    if (veh && (rc = scvx::check_cov_vehicle(ctx, b, sp6))) return rc;   // the tiles are the batch's own: never missing
+    c.B = b->B, c.K = b->K;
+    if ((rc = scvx::check_cov_call(ctx, c, &own))) return rc;
     const size_t n0 = (size_t)b->B * 196, np = (size_t)b->B * (b->K + 1) * SCVX_PSIG_N;
     if (!b->cov_s0) {
         SCVX_HIP(ctx, hipMalloc((void**)&b->cov_s0, n0 * 8));
         SCVX_HIP(ctx, hipMalloc((void**)&b->cov_rep, (size_t)b->B * SCVX_COV_NREP * 8));
         SCVX_HIP(ctx, hipMalloc((void**)&b->cov_psig, np * 8));
     }
-    if (nav && !b->nav_n0) {
+    if (c.nav && !b->nav_n0) {
         SCVX_HIP(ctx, hipMalloc((void**)&b->nav_n0, n0 * 8));
         SCVX_HIP(ctx, hipMalloc((void**)&b->nav_rep, (size_t)b->B * SCVX_NAV_NREP * 8));
     }
     hipStream_t st = ctx->stream;
-    SCVX_HIP(ctx, hipMemcpyAsync(b->cov_s0, S0, n0 * 8, hipMemcpyHostToDevice, st));
-    if (nav) SCVX_HIP(ctx, hipMemcpyAsync(b->nav_n0, nav->N0, n0 * 8, hipMemcpyHostToDevice, st));
+    SCVX_HIP(ctx, hipMemcpyAsync(b->cov_s0, c.S0, n0 * 8, hipMemcpyHostToDevice, st));
+    if (c.nav) SCVX_HIP(ctx, hipMemcpyAsync(b->nav_n0, c.N0, n0 * 8, hipMemcpyHostToDevice, st));
     SCVX_HIP(ctx, hipStreamSynchronize(st));   // the caller's S0 (and N0) is consumed when the call returns; nothing comes back
-    if ((rc = enqueue_track_gains(b, q14, rNU, qf14))) return rc;
-    if (veh) {
-        // the _veh forms: the tiles of the current accepted iterate, then the analysis with them; nothing returns to the host in between
-        if ((rc = enqueue_vehicle_tiles(b, st))) return rc;
-        const scvx::CovVeh v(b->vtile, sp6, nullptr);
-        if (nav)
-            SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H,
-                                               nav->rm, w14, b->cov_rep, b->nav_rep, nullptr, nullptr, nullptr, nullptr, st, b->cov_psig, &v));
-        else
-            SCVX_HIP(ctx, scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, w14, b->cov_rep, nullptr,
-                                           nullptr, nullptr, st, b->cov_psig, &v));
-    } else if (nav)
-        SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, b->nav_n0, nav->m, nav->H, nav->rm,
-                                           w14, b->cov_rep, b->nav_rep, nullptr, nullptr, nullptr, nullptr, st, b->cov_psig));
-    else
-        SCVX_HIP(ctx, scvx::launch_cov(ctx, b->B, b->K, b->x, b->u, b->tiles(), b->track_gain, b->cov_s0, w14, b->cov_rep, nullptr, nullptr,
-                                       nullptr, st, b->cov_psig));
+    if ((rc = enqueue_track_gains(b, own.q14, own.rNU, own.qf14))) return rc;
+    // the _veh forms: the tiles of the current accepted iterate, then the analysis with them; nothing returns to the host in between
+    if (c.veh && (rc = enqueue_vehicle_tiles(b, st))) return rc;
+    c.x = b->x, c.u = b->u, c.deriv = b->tiles(), c.gain = b->track_gain, c.S0 = b->cov_s0, c.N0 = b->nav_n0, c.vtile = b->vtile;
+    c.report = b->cov_rep, c.navrep = b->nav_rep, c.psig = b->cov_psig;
+    SCVX_HIP(ctx, scvx::launch_cov_call(ctx, c, st));
+    const unsigned which = own.which;
+    const double cap = own.cap;   // a fraction of each constraint's width
     const bool path = (which & ~(unsigned)SCVX_MARGIN_THRUST) != 0u;
     if (path && !b->pmarg_on)   // "as they are" of an unselected path constraint of a batch that has none: 0
         SCVX_HIP(ctx, hipMemsetAsync(b->pmarg, 0, (size_t)b->B * (b->K + 1) * SCVX_PMARG_N * 8, st));
     const scvx::MarginCaps capw{cap * (b->C.Tmax - b->C.Tmin), cap * (b->C.mwet - b->C.mdry), cap * b->C.sqcm, cap * b->C.omMax, cap, b->C.itan};
-    hipLaunchKernelGGL(scvx::margins_from_psig_kernel, dim3(b->B), dim3(64), 0, st, b->B, b->K, b->cov_psig, b->x, nsigma, capw, which, b->marg,
-                       b->pmarg);
+    hipLaunchKernelGGL(scvx::margins_from_psig_kernel, dim3(b->B), dim3(64), 0, st, b->B, b->K, b->cov_psig, b->x, own.nsigma, capw, which,
+                       b->marg, b->pmarg);
     SCVX_HIP(ctx, hipGetLastError());
     if (which & SCVX_MARGIN_THRUST) b->marg_on = true;
     if (path) b->pmarg_on = true;
@@ -1356,33 +1292,49 @@ static int margins_from_cov(scvx_batch* b, const double* q14, const double* rNU,
     return SCVX_OK;
 }
 
+// the companion of a margins call; thrust: scvx_batch_thrust_margins_from_cov
+static scvx::CovBatch margins_own(const double* q14, const double* rNU, const double* qf14, double nsigma, double cap, unsigned which,
+                                  bool thrust = false) {
+    scvx::CovBatch own{q14, rNU, qf14};
+    own.margins = true, own.thrust = thrust, own.nsigma = nsigma, own.cap = cap, own.which = which;
+    return own;
+}
+
 int scvx_batch_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
                                 const double* w14, double nsigma, double cap, unsigned which, double* psig) {
-    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false);
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14;
+    return margins_from_cov(b, c, margins_own(q14, rNU, qf14, nsigma, cap, which), psig);
 }
 
 int scvx_batch_margins_from_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
                                 const double* N0, int m, const double* H, const double* rm, const double* w14, double nsigma, double cap,
                                 unsigned which, double* psig) {
-    const NavModel nav{N0, m, H, rm};
-    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, &nav);
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.nav = true, c.N0 = N0, c.m = m, c.H = H, c.rm = rm;
+    return margins_from_cov(b, c, margins_own(q14, rNU, qf14, nsigma, cap, which), psig);
 }
 
 int scvx_batch_margins_from_cov_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
                                     const double* w14, double nsigma, double cap, unsigned which, double* psig, const double* sp6) {
-    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, nullptr, true, sp6);
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.veh = true, c.sp6 = sp6;
+    return margins_from_cov(b, c, margins_own(q14, rNU, qf14, nsigma, cap, which), psig);
 }
 
 int scvx_batch_margins_from_nav_veh(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
                                     const double* N0, int m, const double* H, const double* rm, const double* w14, double nsigma,
                                     double cap, unsigned which, double* psig, const double* sp6) {
-    const NavModel nav{N0, m, H, rm};
-    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, which, psig, false, &nav, true, sp6);
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.nav = true, c.N0 = N0, c.m = m, c.H = H, c.rm = rm, c.veh = true, c.sp6 = sp6;
+    return margins_from_cov(b, c, margins_own(q14, rNU, qf14, nsigma, cap, which), psig);
 }
 
 int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0,
                                        const double* w14, double nsigma, double cap, double* psig) {
-    return margins_from_cov(b, q14, rNU, qf14, S0, w14, nsigma, cap, SCVX_MARGIN_THRUST, psig, true);
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14;
+    return margins_from_cov(b, c, margins_own(q14, rNU, qf14, nsigma, cap, SCVX_MARGIN_THRUST, true), psig);
 }
 
 int scvx_batch_replan(scvx_batch* b) {

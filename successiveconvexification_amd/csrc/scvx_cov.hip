@@ -19,8 +19,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <limits>
-#include "scvx_internal.hpp"
-#include "scvx_stage.hpp"
+#include "scvx_cov.hpp"
 
 namespace scvx {
 
@@ -384,31 +383,26 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
 constexpr bool kCovMfmaDefault = false;   // the lane form, which the parity tests pin, until the A/B of tools/bench_cov.py is measured
 
 template <typename DS>
-static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv, const double* gain,
-                               const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
-                               double* psig = nullptr, const CovVeh* veh = nullptr) {
+static hipError_t launch_cov_t(const scvx_ctx* ctx, const CovCall& a, const DS* deriv, hipStream_t st) {
     const PathK pk = path_constants(ctx->prob);
     CovK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}};
-    for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
+    for (int i = 0; i < 14; i++) c.w[i] = a.w ? a.w[i] : 0.0;
     // SCVX_COV_MFMA = 0 / 1 forces the lane-per-element / matrix-pipe form of the two n-deep products (A/B: tools/bench_cov.py)
     bool mf = kCovMfmaDefault;
     if (const char* v = std::getenv("SCVX_COV_MFMA"); v && *v) mf = std::atoi(v) != 0;
-    const dim3 g((unsigned)B), blk(64);
-    const CovVehK vk(veh);
-#define SCVX_COV_LAUNCH(NU, MF)                                                                                                        \
-    do {                                                                                                                               \
-        if (veh && psig)                                                                                                               \
-            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, \
-                               sig, covK, cov, psig, vk);                                                                              \
-        else if (veh)                                                                                                                  \
-            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, \
-                               sig, covK, cov, psig, vk);                                                                              \
-        else if (psig)                                                                                                                      \
-            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, \
-                               cov, psig);                                                                                             \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, report, sig, covK, \
-                               cov, psig);                                                                                             \
+    const dim3 g((unsigned)a.B), blk(64);
+    const CovVehK vk = cov_veh_k(a);
+#define SCVX_COV_ARGS g, blk, 0, st, c, a.B, a.K, a.x, a.u, deriv, a.gain, a.S0, a.report, a.sig, a.covK, a.cov, a.psig
+#define SCVX_COV_LAUNCH(NU, MF)                                                                      \
+    do {                                                                                             \
+        if (a.veh && a.psig)                                                                         \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1, 1, CovVehK>), SCVX_COV_ARGS, vk); \
+        else if (a.veh)                                                                              \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0, 1, CovVehK>), SCVX_COV_ARGS, vk); \
+        else if (a.psig)                                                                             \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1>), SCVX_COV_ARGS);                \
+        else                                                                                         \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0>), SCVX_COV_ARGS);                \
     } while (0)
     if (ctx->dyn.fin) {
         if (mf) SCVX_COV_LAUNCH(5, 1);
@@ -418,47 +412,88 @@ static hipError_t launch_cov_t(const scvx_ctx* ctx, int B, int K, const double* 
         else SCVX_COV_LAUNCH(3, 0);
     }
 #undef SCVX_COV_LAUNCH
+#undef SCVX_COV_ARGS
     return hipGetLastError();
 }
 
-hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
-                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
-                      double* psig, const CovVeh* veh) {
-    return deriv.d ? launch_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, w, report, sig, covK, cov, st, psig, veh)
-                   : launch_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, w, report, sig, covK, cov, st, psig, veh);
+hipError_t launch_cov_call(const scvx_ctx* ctx, const CovCall& c, hipStream_t st) {
+    if (c.nav) return launch_nav_call(ctx, c, st);
+    return c.deriv.d ? launch_cov_t(ctx, c, c.deriv.d, st) : launch_cov_t(ctx, c, c.deriv.f, st);
 }
 
-// what the _vehicle forms refuse beyond the call they extend
-int check_cov_vehicle(scvx_ctx* ctx, const void* vtile, const double* sp6) {
+int check_cov_call(scvx_ctx* ctx, const CovCall& c, const CovBatch* own) {
     if (!ctx) return SCVX_ERR_ARG;
-    if (!sp6) return fail(ctx, SCVX_ERR_ARG, "vehicle: null sp6");
-    for (int i = 0; i < SCVX_VEH_N; i++)
-        if (!(sp6[i] >= 0.0) || !std::isfinite(sp6[i])) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp must be finite and >= 0");
-    if (sp6[SCVX_VEH_AERO] != 0.0 && !ctx->dyn.aero)
-        return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[AERO] != 0 on a model without aerodynamics");
-    if (sp6[SCVX_VEH_FIN] != 0.0 && !ctx->dyn.fin) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[FIN] != 0 on a model without fins");
-    if (!vtile && (sp6[SCVX_VEH_ISP] != 0.0 || sp6[SCVX_VEH_AERO] != 0.0))
-        return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[ISP] or sp[AERO] != 0 needs vtile (scvx_vehicle_tiles_f64)");
-    return SCVX_OK;
-}
-
-
-int check_cov_noise(scvx_ctx* ctx, const double* w) {
-    if (!ctx) return SCVX_ERR_ARG;
-    if (w)
+    const bool margins = own && own->margins;
+    int rc;
+    if (!own) {
+        if (c.B < 1) return fail(ctx, SCVX_ERR_ARG, "cov: B >= 1 required");
+        if (c.K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "cov: K must equal the problem's K");
+        if (!c.x || !c.u || !(c.deriv.d || c.deriv.f) || !c.gain || !c.S0 || !c.report) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
+    } else if (margins) {
+        const std::string who = own->thrust ? "thrust margins: " : c.nav ? "margins from nav: " : "margins from cov: ";
+        if (!c.S0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (S0)");
+        if (c.nav && !c.N0) return fail(ctx, SCVX_ERR_ARG, who + "null buffer (N0)");
+        if (!(own->nsigma >= 0.0) || !std::isfinite(own->nsigma)) return fail(ctx, SCVX_ERR_ARG, who + "nsigma must be finite and >= 0");
+        if (!(own->cap > 0.0 && own->cap < 0.5))
+            return fail(ctx, SCVX_ERR_ARG, who + (own->thrust ? "cap must lie in (0, 0.5), a fraction of Tmax - Tmin"
+                                                              : "cap must lie in (0, 0.5), a fraction of the constraint's width"));
+        if (own->which == 0u || (own->which & ~(unsigned)SCVX_MARGIN_ALL))
+            return fail(ctx, SCVX_ERR_ARG, (c.nav ? who : std::string("margins from cov: ")) + "which must be a non-empty mask of SCVX_MARGIN_*");
+    } else if (!c.S0 || (c.nav && !c.N0)) {
+        return fail(ctx, SCVX_ERR_ARG, c.nav ? "nav: null buffer (S0, N0)" : "cov: null buffer");
+    }
+    if (c.w)
         for (int i = 0; i < 14; i++)
-            if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
-                return fail(ctx, SCVX_ERR_ARG, "cov: the process noise w must be finite and >= 0");
+            if (!(c.w[i] >= 0.0) || !std::isfinite(c.w[i])) return fail(ctx, SCVX_ERR_ARG, "cov: the process noise w must be finite and >= 0");
+    if (c.nav) {
+        if (!own && (!c.N0 || !c.navrep)) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (N0, navrep)");
+        if ((rc = check_nav_model(ctx, c.m, c.H, c.rm))) return rc;
+    }
+    if (c.need_psig && !c.psig) return fail(ctx, SCVX_ERR_ARG, c.nav ? "nav: null buffer (psig)" : "cov: null buffer (psig)");
+    // the tracking weights: the margins calls refuse them before the vehicle, the batch-level analyses after it
+    if (margins && (rc = check_track_weights(ctx, own->q14, own->rNU, own->qf14))) return rc;
+    if (c.veh) {
+        const double* sp = c.sp6;
+        if (!sp) return fail(ctx, SCVX_ERR_ARG, "vehicle: null sp6");
+        for (int i = 0; i < SCVX_VEH_N; i++)
+            if (!(sp[i] >= 0.0) || !std::isfinite(sp[i])) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp must be finite and >= 0");
+        if (sp[SCVX_VEH_AERO] != 0.0 && !ctx->dyn.aero)
+            return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[AERO] != 0 on a model without aerodynamics");
+        if (sp[SCVX_VEH_FIN] != 0.0 && !ctx->dyn.fin) return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[FIN] != 0 on a model without fins");
+        if (!own && !c.vtile && (sp[SCVX_VEH_ISP] != 0.0 || sp[SCVX_VEH_AERO] != 0.0))   // a batch's tiles are its own: never missing
+            return fail(ctx, SCVX_ERR_ARG, "vehicle: sp[ISP] or sp[AERO] != 0 needs vtile (scvx_vehicle_tiles_f64)");
+    }
+    return own && !margins ? check_track_weights(ctx, own->q14, own->rNU, own->qf14) : (int)SCVX_OK;
+}
+
+CovCall stage_cov(Staging& s, const Dims& d, const CovCall& c, bool own) {
+    CovCall dev = c;
+    if (!own) dev.x = s.in(c.x, d.x), dev.u = s.in(c.u, d.u), dev.deriv = Tiles{s.in(c.deriv.d, d.deriv), nullptr}, dev.gain = s.in(c.gain, d.gain);
+    dev.S0 = s.in(c.S0, d.c14), dev.N0 = s.in(c.N0, d.c14);
+    if (!own) dev.vtile = s.in(c.vtile, d.vtile);
+    dev.report = s.out_always(c.report, d.crep), dev.navrep = c.nav ? s.out_always(c.navrep, d.nrep) : nullptr;
+    dev.psig = s.out(c.psig, d.psig), dev.sig = s.out(c.sig, d.sig), dev.navsig = s.out(c.navsig, d.navsig);
+    dev.covK = s.out(c.covK, d.covK), dev.cov = s.out(c.cov, d.cov), dev.kf = s.out(c.m > 0 ? c.kf : nullptr, d.kf);
+    dev.joint = s.out(c.joint, d.joint), dev.sens = s.out(c.sens, d.sens);
+    return dev;
+}
+
+int cov_call_dev(scvx_ctx* ctx, const CovCall& c) {
+    int rc = check_cov_call(ctx, c);
+    if (rc) return rc;
+    SCVX_HIP(ctx, hipSetDevice(ctx->device));
+    SCVX_HIP(ctx, launch_cov_call(ctx, c, ctx->stream));
     return SCVX_OK;
 }
 
-int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
-              const double* w, const void* report) {
-    if (!ctx) return SCVX_ERR_ARG;
-    if (B < 1) return fail(ctx, SCVX_ERR_ARG, "cov: B >= 1 required");
-    if (K != ctx->prob.K) return fail(ctx, SCVX_ERR_ARG, "cov: K must equal the problem's K");
-    if (!x || !u || !deriv || !gain || !S0 || !report) return fail(ctx, SCVX_ERR_ARG, "cov: null buffer");
-    return check_cov_noise(ctx, w);
+int cov_call_host(scvx_ctx* ctx, const CovCall& c, const char* entry) {
+    int rc = check_cov_call(ctx, c);
+    if (rc) return rc;
+    const Dims d(c.B, c.K, scvx_control_dim(ctx), 0, c.m);
+    Staging s(ctx);
+    const CovCall dev = stage_cov(s, d, c, false);
+    s.launch([&] { return launch_cov_call(ctx, dev, s.st); });
+    return s.finish(entry);
 }
 
 }  // namespace scvx
@@ -468,81 +503,47 @@ extern "C" {
 int scvx_cov_propagate_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
                            const double* gain_dev, const double* S0_dev, const double* w14, double* report_dev, double* sig_dev,
                            double* covK_dev, double* cov_dev) {
-    int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
-    if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, sig_dev,
-                                   covK_dev, cov_dev, ctx->stream));
-    return SCVX_OK;
+    scvx::CovCall c = scvx::cov_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    c.sig = sig_dev, c.covK = covK_dev, c.cov = cov_dev;
+    return scvx::cov_call_dev(ctx, c);
 }
 
 int scvx_cov_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
                             const double* gain_dev, const double* S0_dev, const double* w14, double* report_dev, double* psig_dev) {
-    int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
-    if (rc) return rc;
-    if (!psig_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "cov: null buffer (psig)");
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, nullptr,
-                                   nullptr, nullptr, ctx->stream, psig_dev));
-    return SCVX_OK;
+    scvx::CovCall c = scvx::cov_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    c.psig = psig_dev, c.need_psig = true;
+    return scvx::cov_call_dev(ctx, c);
 }
 
 int scvx_cov_vehicle_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
                          const double* gain_dev, const double* S0_dev, const double* w14, double* report_dev, double* psig_dev,
                          double* sig_dev, double* covK_dev, double* cov_dev, const double* vtile_dev, const double* sp6,
                          double* sens_dev) {
-    int rc = scvx::check_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
-    if (rc) return rc;
-    if ((rc = scvx::check_cov_vehicle(ctx, vtile_dev, sp6))) return rc;
-    const scvx::CovVeh v = scvx::CovVeh(vtile_dev, sp6, sens_dev);
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, w14, report_dev, sig_dev,
-                                   covK_dev, cov_dev, ctx->stream, psig_dev, &v));
-    return SCVX_OK;
+    scvx::CovCall c = scvx::cov_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    c.psig = psig_dev, c.sig = sig_dev, c.covK = covK_dev, c.cov = cov_dev, c.veh = true, c.vtile = vtile_dev, c.sp6 = sp6, c.sens = sens_dev;
+    return scvx::cov_call_dev(ctx, c);
 }
 
 int scvx_cov_vehicle_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                               const double* S0, const double* w14, double* report, double* psig, double* sig, double* covK, double* cov,
                               const double* vtile, const double* sp6, double* sens) {
-    int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
-    if (rc) return rc;
-    if ((rc = scvx::check_cov_vehicle(ctx, vtile, sp6))) return rc;
-    const scvx::Dims d(B, K, scvx_control_dim(ctx));
-    scvx::Staging s(ctx);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
-                 *dv = s.in(vtile, d.vtile);
-    double *dr = s.out(report, d.crep), *dp = s.out(psig, d.psig), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK),
-           *dc = s.out(cov, d.cov), *dj = s.out(sens, d.sens);
-    const scvx::CovVeh v = scvx::CovVeh(dv, sp6, dj);
-    s.launch([&] { return scvx::launch_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, w14, dr, ds, dk, dc, s.st, dp, &v); });
-    return s.finish("scvx_cov_vehicle_f64_host");
+    scvx::CovCall c = scvx::cov_record(B, K, x, u, deriv, gain, S0, w14, report);
+    c.psig = psig, c.sig = sig, c.covK = covK, c.cov = cov, c.veh = true, c.vtile = vtile, c.sp6 = sp6, c.sens = sens;
+    return scvx::cov_call_host(ctx, c, "scvx_cov_vehicle_f64_host");
 }
 
 int scvx_cov_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                                  const double* S0, const double* w14, double* report, double* psig) {
-    int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
-    if (rc) return rc;
-    if (!psig) return scvx::fail(ctx, SCVX_ERR_ARG, "cov: null buffer (psig)");
-    const scvx::Dims d(B, K, scvx_control_dim(ctx));
-    scvx::Staging s(ctx);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14);
-    double *dr = s.out(report, d.crep), *dp = s.out(psig, d.psig);
-    s.launch([&] {
-        return scvx::launch_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, w14, dr, nullptr, nullptr, nullptr, s.st, dp);
-    });
-    return s.finish("scvx_cov_path_sigma_f64_host");
+    scvx::CovCall c = scvx::cov_record(B, K, x, u, deriv, gain, S0, w14, report);
+    c.psig = psig, c.need_psig = true;
+    return scvx::cov_call_host(ctx, c, "scvx_cov_path_sigma_f64_host");
 }
 
 int scvx_cov_propagate_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                                 const double* S0, const double* w14, double* report, double* sig, double* covK, double* cov) {
-    int rc = scvx::check_cov(ctx, B, K, x, u, deriv, gain, S0, w14, report);
-    if (rc) return rc;
-    const scvx::Dims d(B, K, scvx_control_dim(ctx));
-    scvx::Staging s(ctx);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14);
-    double *dr = s.out(report, d.crep), *ds = s.out(sig, d.sig), *dk = s.out(covK, d.covK), *dc = s.out(cov, d.cov);
-    s.launch([&] { return scvx::launch_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, w14, dr, ds, dk, dc, s.st); });
-    return s.finish("scvx_cov_propagate_f64_host");
+    scvx::CovCall c = scvx::cov_record(B, K, x, u, deriv, gain, S0, w14, report);
+    c.sig = sig, c.covK = covK, c.cov = cov;
+    return scvx::cov_call_host(ctx, c, "scvx_cov_propagate_f64_host");
 }
 
 }  // extern "C"

@@ -99,51 +99,26 @@ int check_track_weights(scvx_ctx* ctx, const double* q, const double* r, const d
 int check_track_fly(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* gain, int nsub, int flags,
                     const void* report);
 
-struct CovVeh; // the _vehicle forms of the covariance and navigation analyses (below); nullptr: the plain call
-
 // Sampled dispersion (scvx_mc.hip, scvx_mc_nav.hip): S flights per plan, one lane per flight, a wavefront = 64 samples of one plan.
 // Every form goes through one record, one check, one staging and one launch: scvx_mc.hpp.  The partial rows live in ctx->mc_ws.
 void mc_workspace_free(scvx_ctx* ctx);
 
 // Covariance analysis (scvx_cov.hip): one wavefront per trajectory over the derivative tiles and the gains; S0[B][14][14]; w: host
 // array of 14 or nullptr; report[B][SCVX_COV_NREP]; sig[B][K+1][n], covK[B][n][n], cov[B][K+1][n][n] or nullptr.  With psig
-// [B][K+1][SCVX_PSIG_N] the per-node s of the five path functions are kept (scvx_cov_path_sigma_f64) and sig, covK, cov are nullptr.
-hipError_t launch_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
-                      const double* S0, const double* w, double* report, double* sig, double* covK, double* cov, hipStream_t st,
-                      double* psig = nullptr, const CovVeh* veh = nullptr);
-int check_cov_noise(scvx_ctx* ctx, const double* w);
-int check_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
-              const double* w, const void* report);
-
+// [B][K+1][SCVX_PSIG_N] the per-node s of the five path functions are kept (scvx_cov_path_sigma_f64).
 // Navigation-error covariance analysis (scvx_nav.hip): cov_propagate_kernel on the joint [z; eps], N = 14 + NU + 14.  N0[B][14][14];
 // m measurements per node, H[m][14] and rm[m] host arrays (nullptr with m = 0); navrep[B][SCVX_NAV_NREP]; sig[B][K+1][n],
-// navsig[B][K+1][14], kf[B][K][14][m], joint[B][K+1][N][N] or nullptr.  With psig [B][K+1][SCVX_PSIG_N] the per-node s of the five path
-// functions are kept, read off the truth block Xi_k[z,z] (scvx_nav_path_sigma_f64), and sig, navsig, kf, joint are nullptr.
-hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
-                          const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig = nullptr,
-                          const CovVeh* veh = nullptr);
-int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm);
+// navsig[B][K+1][14], kf[B][K][14][m], joint[B][K+1][N][N] or nullptr; psig as above, read off the truth block Xi_k[z,z].
+// Vehicle errors in the two (include/scvx.h "consider parameters"): vtile[B][K][SCVX_VTILE_N][14] (scvx_vtile.hip) or nullptr, sp6: the
+// six standard deviations (host), sens[B][K+1][n][6] or nullptr.
+// Every form of both goes through one record, one check, one staging and one launch: scvx_cov.hpp.
+int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm);   // shared with the sampled flights on an estimate
 
-// Vehicle errors in the two analyses above (include/scvx.h "consider parameters").  CovVeh: what the _vehicle forms add to a launch;
-// nullptr: the plain call, the instantiations without VEH.  vtile[B][K][SCVX_VTILE_N][14] (scvx_vtile.hip) or nullptr, sp: the six
-// standard deviations (host), sens[B][K+1][n][6] or nullptr.
-struct CovVeh {
-    const double* vtile;
-    double sp[SCVX_VEH_N];
-    double* sens;
-    CovVeh(const double* vtile_, const double* sp6, double* sens_) : vtile(vtile_), sens(sens_) {
-        for (int i = 0; i < SCVX_VEH_N; i++) sp[i] = sp6[i];
-    }
-};
-// the kernel argument of the VEH instantiations: p = sp^2
+// the kernel argument of the VEH instantiations: p = sp^2 (cov_veh_k, scvx_cov.hpp)
 struct CovVehK {
     const double* vtile;
     double* sens;
     double p[SCVX_VEH_N];
-    explicit CovVehK(const CovVeh* v) : vtile(v ? v->vtile : nullptr), sens(v ? v->sens : nullptr) {
-        for (int i = 0; i < SCVX_VEH_N; i++) p[i] = v ? v->sp[i] * v->sp[i] : 0.0;
-    }
 };
 // the one element of a VEH instantiation's trailing kernel-argument pack
 template <typename T>
@@ -177,7 +152,6 @@ __device__ __forceinline__ double veh_gamma(const double* D, const double* uk, c
 hipError_t launch_vehicle_tiles(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, double* vtile,
                                 hipStream_t st);
 int check_vehicle_tiles(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, const void* vtile);
-int check_cov_vehicle(scvx_ctx* ctx, const void* vtile, const double* sp6);
 
 // K0 (scvx_threedof.hip): the batched 3-DoF landing SOCP on device arrays, enqueued on ctx->stream; sol [B][(K+1)*15+1],
 // info [B][6] = status, iters, pobj, gap, pres, dres.  threedof_to_record overwrites the trajectory records [B][(K+1)*(14+NU)+1]

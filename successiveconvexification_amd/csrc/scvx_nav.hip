@@ -23,8 +23,7 @@
 // the update does not touch -- the constraints bind the vehicle, not its estimate.
 #include <cmath>
 #include <limits>
-#include "scvx_internal.hpp"
-#include "scvx_stage.hpp"
+#include "scvx_cov.hpp"
 
 namespace scvx {
 
@@ -466,46 +465,36 @@ __global__ __launch_bounds__(64) void nav_cov_kernel(NavK c, int B, int K, const
 }
 
 template <typename DS>
-static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const DS* deriv,
-                                   const double* gain, const double* S0, const double* N0, int m, const double* H, const double* rm,
-                                   const double* w, double* report, double* navrep, double* sig, double* navsig, double* kf,
-                                   double* joint, hipStream_t st, double* psig = nullptr, const CovVeh* veh = nullptr) {
+static hipError_t launch_nav_cov_t(const scvx_ctx* ctx, const CovCall& a, const DS* deriv, hipStream_t st) {
     const PathK pk = path_constants(ctx->prob);
-    NavK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}, {}, {}, m};
-    for (int i = 0; i < 14; i++) c.w[i] = w ? w[i] : 0.0;
-    for (int i = 0; i < m; i++) c.rm[i] = rm[i];
-    for (int i = 0; i < m * 14; i++) c.H[i] = H[i];
-    const dim3 g((unsigned)B), blk(64);
-    const CovVehK vk(veh);
-#define SCVX_NAV_LAUNCH(NU)                                                                                                            \
-    do {                                                                                                                               \
-        if (veh && psig)                                                                                                               \
-            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, \
-                               sig, navsig, kf, joint, psig, vk);                                                                      \
-        else if (veh)                                                                                                                  \
-            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 0, 1, CovVehK>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, \
-                               sig, navsig, kf, joint, psig, vk);                                                                      \
-        else if (psig)                                                                                                                      \
-            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig,     \
-                               navsig, kf, joint, psig);                                                                               \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 0>), g, blk, 0, st, c, B, K, x, u, deriv, gain, S0, N0, report, navrep, sig,     \
-                               navsig, kf, joint, psig);                                                                               \
+    NavK c{pk.mdry, pk.tggs, pk.sqcm, pk.omMax, pk.Tmax, pk.Tmin, {}, {}, {}, a.m};
+    for (int i = 0; i < 14; i++) c.w[i] = a.w ? a.w[i] : 0.0;
+    for (int i = 0; i < a.m; i++) c.rm[i] = a.rm[i];
+    for (int i = 0; i < a.m * 14; i++) c.H[i] = a.H[i];
+    const dim3 g((unsigned)a.B), blk(64);
+    const CovVehK vk = cov_veh_k(a);
+#define SCVX_NAV_ARGS \
+    g, blk, 0, st, c, a.B, a.K, a.x, a.u, deriv, a.gain, a.S0, a.N0, a.report, a.navrep, a.sig, a.navsig, a.kf, a.joint, a.psig
+#define SCVX_NAV_LAUNCH(NU)                                                                    \
+    do {                                                                                       \
+        if (a.veh && a.psig)                                                                   \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1, 1, CovVehK>), SCVX_NAV_ARGS, vk);    \
+        else if (a.veh)                                                                        \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 0, 1, CovVehK>), SCVX_NAV_ARGS, vk);    \
+        else if (a.psig)                                                                       \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 1>), SCVX_NAV_ARGS);                    \
+        else                                                                                   \
+            hipLaunchKernelGGL((nav_cov_kernel<DS, NU, 0>), SCVX_NAV_ARGS);                    \
     } while (0)
     if (ctx->dyn.fin) SCVX_NAV_LAUNCH(5);
     else SCVX_NAV_LAUNCH(3);
 #undef SCVX_NAV_LAUNCH
+#undef SCVX_NAV_ARGS
     return hipGetLastError();
 }
 
-hipError_t launch_nav_cov(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, Tiles deriv, const double* gain,
-                          const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w, double* report,
-                          double* navrep, double* sig, double* navsig, double* kf, double* joint, hipStream_t st, double* psig,
-                          const CovVeh* veh) {
-    return deriv.d ? launch_nav_cov_t<double>(ctx, B, K, x, u, deriv.d, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint,
-                                              st, psig, veh)
-                   : launch_nav_cov_t<float>(ctx, B, K, x, u, deriv.f, gain, S0, N0, m, H, rm, w, report, navrep, sig, navsig, kf, joint, st,
-                                             psig, veh);
+hipError_t launch_nav_call(const scvx_ctx* ctx, const CovCall& c, hipStream_t st) {
+    return c.deriv.d ? launch_nav_cov_t(ctx, c, c.deriv.d, st) : launch_nav_cov_t(ctx, c, c.deriv.f, st);
 }
 
 int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm) {
@@ -519,15 +508,16 @@ int check_nav_model(scvx_ctx* ctx, int m, const double* H, const double* rm) {
     return SCVX_OK;
 }
 
-int check_nav_cov(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* deriv, const void* gain, const void* S0,
-                  const void* N0, int m, const double* H, const double* rm, const double* w, const void* report, const void* navrep) {
-    int rc = check_cov(ctx, B, K, x, u, deriv, gain, S0, w, report);
-    if (rc) return rc;
-    if (!N0 || !navrep) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (N0, navrep)");
-    return check_nav_model(ctx, m, H, rm);
-}
-
 }  // namespace scvx
+
+// the record of the navigation forms: what every one of them takes
+static scvx::CovCall nav_record(int B, int K, const double* x, const double* u, const double* deriv, const double* gain, const double* S0,
+                                const double* N0, int m, const double* H, const double* rm, const double* w14, double* report,
+                                double* navrep) {
+    scvx::CovCall c = scvx::cov_record(B, K, x, u, deriv, gain, S0, w14, report);
+    c.nav = true, c.N0 = N0, c.m = m, c.H = H, c.rm = rm, c.navrep = navrep;
+    return c;
+}
 
 extern "C" {
 
@@ -535,24 +525,17 @@ int scvx_nav_cov_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const dou
                      const double* gain_dev, const double* S0_dev, const double* N0_dev, int m, const double* H, const double* rm,
                      const double* w14, double* report_dev, double* navrep_dev, double* sig_dev, double* navsig_dev, double* kf_dev,
                      double* joint_dev) {
-    int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
-    if (rc) return rc;
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
-                                       report_dev, navrep_dev, sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream));
-    return SCVX_OK;
+    scvx::CovCall c = nav_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
+    c.sig = sig_dev, c.navsig = navsig_dev, c.kf = kf_dev, c.joint = joint_dev;
+    return scvx::cov_call_dev(ctx, c);
 }
 
 int scvx_nav_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
                             const double* gain_dev, const double* S0_dev, const double* N0_dev, int m, const double* H, const double* rm,
                             const double* w14, double* report_dev, double* navrep_dev, double* psig_dev) {
-    int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
-    if (rc) return rc;
-    if (!psig_dev) return scvx::fail(ctx, SCVX_ERR_ARG, "nav: null buffer (psig)");
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
-                                       report_dev, navrep_dev, nullptr, nullptr, nullptr, nullptr, ctx->stream, psig_dev));
-    return SCVX_OK;
+    scvx::CovCall c = nav_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
+    c.psig = psig_dev, c.need_psig = true;
+    return scvx::cov_call_dev(ctx, c);
 }
 
 int scvx_nav_cov_vehicle_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
@@ -560,70 +543,35 @@ int scvx_nav_cov_vehicle_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, c
                              const double* w14, double* report_dev, double* navrep_dev, double* psig_dev, double* sig_dev,
                              double* navsig_dev, double* kf_dev, double* joint_dev, const double* vtile_dev, const double* sp6,
                              double* sens_dev) {
-    int rc = scvx::check_nav_cov(ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
-    if (rc) return rc;
-    if ((rc = scvx::check_cov_vehicle(ctx, vtile_dev, sp6))) return rc;
-    const scvx::CovVeh v(vtile_dev, sp6, sens_dev);
-    SCVX_HIP(ctx, hipSetDevice(ctx->device));
-    SCVX_HIP(ctx, scvx::launch_nav_cov(ctx, B, K, x_dev, u_dev, scvx::Tiles{deriv_dev, nullptr}, gain_dev, S0_dev, N0_dev, m, H, rm, w14,
-                                       report_dev, navrep_dev, sig_dev, navsig_dev, kf_dev, joint_dev, ctx->stream, psig_dev, &v));
-    return SCVX_OK;
+    scvx::CovCall c = nav_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, N0_dev, m, H, rm, w14, report_dev, navrep_dev);
+    c.psig = psig_dev, c.sig = sig_dev, c.navsig = navsig_dev, c.kf = kf_dev, c.joint = joint_dev;
+    c.veh = true, c.vtile = vtile_dev, c.sp6 = sp6, c.sens = sens_dev;
+    return scvx::cov_call_dev(ctx, c);
 }
 
 int scvx_nav_cov_vehicle_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                                   const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w14,
                                   double* report, double* navrep, double* psig, double* sig, double* navsig, double* kf, double* joint,
                                   const double* vtile, const double* sp6, double* sens) {
-    int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
-    if (rc) return rc;
-    if ((rc = scvx::check_cov_vehicle(ctx, vtile, sp6))) return rc;
-    const scvx::Dims d(B, K, scvx_control_dim(ctx), 0, m);
-    scvx::Staging s(ctx);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
-                 *dn = s.in(N0, d.c14), *dt = s.in(vtile, d.vtile);
-    double *dr = s.out(report, d.crep), *dq = s.out(navrep, d.nrep), *dp = s.out(psig, d.psig), *ds = s.out(sig, d.sig),
-           *dv = s.out(navsig, d.navsig), *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint), *de = s.out(sens, d.sens);
-    const scvx::CovVeh v(dt, sp6, de);
-    s.launch([&] {
-        return scvx::launch_nav_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st, dp,
-                                    &v);
-    });
-    return s.finish("scvx_nav_cov_vehicle_f64_host");
+    scvx::CovCall c = nav_record(B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
+    c.psig = psig, c.sig = sig, c.navsig = navsig, c.kf = kf, c.joint = joint, c.veh = true, c.vtile = vtile, c.sp6 = sp6, c.sens = sens;
+    return scvx::cov_call_host(ctx, c, "scvx_nav_cov_vehicle_f64_host");
 }
 
 int scvx_nav_path_sigma_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                                  const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w14,
                                  double* report, double* navrep, double* psig) {
-    int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
-    if (rc) return rc;
-    if (!psig) return scvx::fail(ctx, SCVX_ERR_ARG, "nav: null buffer (psig)");
-    const scvx::Dims d(B, K, scvx_control_dim(ctx));
-    scvx::Staging s(ctx);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
-                 *dn = s.in(N0, d.c14);
-    double *dr = s.out(report, d.crep), *dq = s.out(navrep, d.nrep), *dp = s.out(psig, d.psig);
-    s.launch([&] {
-        return scvx::launch_nav_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, dn, m, H, rm, w14, dr, dq, nullptr, nullptr, nullptr,
-                                    nullptr, s.st, dp);
-    });
-    return s.finish("scvx_nav_path_sigma_f64_host");
+    scvx::CovCall c = nav_record(B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
+    c.psig = psig, c.need_psig = true;
+    return scvx::cov_call_host(ctx, c, "scvx_nav_path_sigma_f64_host");
 }
 
 int scvx_nav_cov_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
                           const double* S0, const double* N0, int m, const double* H, const double* rm, const double* w14, double* report,
                           double* navrep, double* sig, double* navsig, double* kf, double* joint) {
-    int rc = scvx::check_nav_cov(ctx, B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
-    if (rc) return rc;
-    const scvx::Dims d(B, K, scvx_control_dim(ctx), 0, m);
-    scvx::Staging s(ctx);
-    const double *dx = s.in(x, d.x), *du = s.in(u, d.u), *dd = s.in(deriv, d.deriv), *dg = s.in(gain, d.gain), *d0 = s.in(S0, d.c14),
-                 *dn = s.in(N0, d.c14);
-    double *dr = s.out(report, d.crep), *dq = s.out(navrep, d.nrep), *ds = s.out(sig, d.sig), *dv = s.out(navsig, d.navsig),
-           *dk = s.out(m > 0 ? kf : nullptr, d.kf), *dj = s.out(joint, d.joint);
-    s.launch([&] {
-        return scvx::launch_nav_cov(ctx, B, K, dx, du, scvx::Tiles{dd, nullptr}, dg, d0, dn, m, H, rm, w14, dr, dq, ds, dv, dk, dj, s.st);
-    });
-    return s.finish("scvx_nav_cov_f64_host");
+    scvx::CovCall c = nav_record(B, K, x, u, deriv, gain, S0, N0, m, H, rm, w14, report, navrep);
+    c.sig = sig, c.navsig = navsig, c.kf = kf, c.joint = joint;
+    return scvx::cov_call_host(ctx, c, "scvx_nav_cov_f64_host");
 }
 
 int scvx_track_fly_nav_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* sigma_dev,

@@ -14,8 +14,9 @@
 // was linked against the staging code as it stood BEFORE csrc/scvx_stage.hpp existed; the test requires the same lines, so the staging
 // helper allocates, copies, launches and synchronises exactly what the hand-written sequences did.  And the runtime can make the n-th
 // hipMalloc, hipMemcpyAsync or launch of a call fail: sweep() does that at every position of one small call of every form and checks the
-// error contract of scvx::Staging.  refusals() pins what the sampled calls refuse, in which words, and which of two faults wins
-// (tests/golden/mc_refusals.txt).  tests/test_host_staging_sanitizers.py holds the build recipe and runs the program.
+// error contract of scvx::Staging.  refusals() and cov_refusals() pin what the sampled calls and the first-order analyses refuse, in which
+// words, and which of two faults wins (tests/golden/mc_refusals.txt, cov_refusals.txt).  tests/test_host_staging_sanitizers.py holds the
+// build recipe and runs the program.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -541,8 +542,125 @@ static int refusals(bool veh) {
     return 0;
 }
 
+// ---- the refusals of the first-order analyses ---------------------------------------------------------------------------------------------
+// Every argument of the twelve scvx_cov_* / scvx_nav_* forms, valid for B = 2, K = 3, NU = 3 and m rows, each array of its documented
+// size.  cov_refusals() starts every form from this call, makes one argument (or two) bad and prints
+// "cov-refusal <entry> <case> <rc> <message>"; a refused call allocates nothing.  tests/golden/cov_refusals.txt holds the lines as the
+// twelve hand-written bodies gave them: which message a bad call gets, and which fault wins when two are present.
+enum { C_NAV = 1, C_PS = 2, C_VEH = 4, C_M = 8 };
+struct CovArgs {
+    int B = 2, K = 3, m;
+    V vx, vu, vderiv, vgain, vS0, vN0, vH, vrm, vw, vvtile, vsp, vrep, vnrep, vpsig, vsig, vcovK, vcov, vnavsig, vkf, vjoint, vsens;
+    const double *x, *u, *deriv, *gain, *S0, *N0, *H, *rm, *w, *vtile, *sp6;
+    double *report, *navrep, *psig, *sig, *covK, *cov, *navsig, *kf, *joint, *sens;
+    scvx_ctx ctx;
+    explicit CovArgs(int m_)
+        : m(m_), vx(2 * 4 * 14, 1.0), vu(2 * 4 * 3, 1.0), vderiv(2 * 3 * 14 * 21), vgain(2 * 3 * 3 * 17), vS0(2 * 196), vN0(2 * 196),
+          vH((m_ ? m_ : 1) * 14, 0.0), vrm(m_ ? m_ : 1, 1e-6), vw(14, 1e-6), vvtile(2 * 3 * SCVX_VTILE_N * 14), vsp(SCVX_VEH_N, 0.0),
+          vrep(2 * SCVX_COV_NREP), vnrep(2 * SCVX_NAV_NREP), vpsig(2 * 4 * SCVX_PSIG_N), vsig(2 * 4 * 17), vcovK(2 * 17 * 17),
+          vcov(2 * 4 * 17 * 17), vnavsig(2 * 4 * 14), vkf(2 * 3 * 14 * (m_ ? m_ : 1)), vjoint(2 * 4 * 31 * 31), vsens(2 * 4 * 17 * SCVX_VEH_N) {
+        vsp[SCVX_VEH_THRUST] = 1e-3;
+        x = vx.data(), u = vu.data(), deriv = vderiv.data(), gain = vgain.data(), S0 = vS0.data(), N0 = vN0.data(), w = vw.data();
+        H = m ? vH.data() : nullptr, rm = m ? vrm.data() : nullptr, vtile = vvtile.data(), sp6 = vsp.data();
+        report = vrep.data(), navrep = vnrep.data(), psig = vpsig.data(), sig = vsig.data(), covK = vcovK.data(), cov = vcov.data();
+        navsig = vnavsig.data(), kf = m ? vkf.data() : nullptr, joint = vjoint.data(), sens = vsens.data();
+        ctx.prob.K = K;
+    }
+    CovArgs(const CovArgs&) = delete;
+};
+
+struct CovForm {
+    const char* entry;
+    int traits;
+    int (*call)(CovArgs&);
+};
+#define COV_A &a.ctx, a.B, a.K, a.x, a.u, a.deriv, a.gain, a.S0
+#define COV_N a.N0, a.m, a.H, a.rm
+#define COV_V a.vtile, a.sp6, a.sens
+#define COV_FORM(name, traits, ...) {#name, traits, [](CovArgs& a) { return name(__VA_ARGS__); }}
+#define COV_BOTH(name, traits, ...) COV_FORM(name, traits, __VA_ARGS__), COV_FORM(name##_host, traits, __VA_ARGS__)
+static const CovForm g_cov_forms[] = {
+    COV_BOTH(scvx_cov_propagate_f64, 0, COV_A, a.w, a.report, a.sig, a.covK, a.cov),
+    COV_BOTH(scvx_cov_path_sigma_f64, C_PS, COV_A, a.w, a.report, a.psig),
+    COV_BOTH(scvx_cov_vehicle_f64, C_VEH, COV_A, a.w, a.report, a.psig, a.sig, a.covK, a.cov, COV_V),
+    COV_BOTH(scvx_nav_cov_f64, C_NAV, COV_A, COV_N, a.w, a.report, a.navrep, a.sig, a.navsig, a.kf, a.joint),
+    COV_BOTH(scvx_nav_path_sigma_f64, C_NAV | C_PS, COV_A, COV_N, a.w, a.report, a.navrep, a.psig),
+    COV_BOTH(scvx_nav_cov_vehicle_f64, C_NAV | C_VEH, COV_A, COV_N, a.w, a.report, a.navrep, a.psig, a.sig, a.navsig, a.kf, a.joint, COV_V),
+};
+
+// one bad argument: applies to the forms that have every trait of `need`
+struct CovFault {
+    const char* name;
+    int need;
+    void (*make)(CovArgs&);
+};
+static const double g_cwneg[14] = {1e-6, 1e-6, -1e-6}, g_cwnan[14] = {1e-6, g_nan};
+#define CBAD(name, need, ...) {name, need, [](CovArgs& a) { __VA_ARGS__; }}
+static const CovFault g_cov_faults[] = {
+    CBAD("x=NULL", 0, a.x = nullptr), CBAD("u=NULL", 0, a.u = nullptr), CBAD("deriv=NULL", 0, a.deriv = nullptr),
+    CBAD("gain=NULL", 0, a.gain = nullptr), CBAD("S0=NULL", 0, a.S0 = nullptr), CBAD("report=NULL", 0, a.report = nullptr),
+    CBAD("N0=NULL", C_NAV, a.N0 = nullptr), CBAD("navrep=NULL", C_NAV, a.navrep = nullptr), CBAD("psig=NULL", C_PS, a.psig = nullptr),
+    CBAD("B=0", 0, a.B = 0), CBAD("K=4", 0, a.K = 4), CBAD("w<0", 0, a.w = g_cwneg), CBAD("w=NaN", 0, a.w = g_cwnan),
+    CBAD("m=-1", C_NAV, a.m = -1), CBAD("m=15", C_NAV, a.m = 15), CBAD("H=NULL", C_NAV | C_M, a.H = nullptr),
+    CBAD("rm=NULL", C_NAV | C_M, a.rm = nullptr), CBAD("rm=0", C_NAV | C_M, a.vrm[1] = 0.0), CBAD("rm=NaN", C_NAV | C_M, a.vrm[0] = g_nan),
+    CBAD("H=NaN", C_NAV | C_M, a.vH[15] = g_nan),
+    CBAD("sp6=NULL", C_VEH, a.sp6 = nullptr), CBAD("sp<0", C_VEH, a.vsp[SCVX_VEH_MIS_Y] = -1e-3), CBAD("sp=NaN", C_VEH, a.vsp[SCVX_VEH_MIS_Z] = g_nan),
+    CBAD("sp.aero", C_VEH, a.vsp[SCVX_VEH_AERO] = 1e-3), CBAD("sp.fin", C_VEH, a.vsp[SCVX_VEH_FIN] = 1e-3),
+    CBAD("sp.isp-without-vtile", C_VEH, a.vsp[SCVX_VEH_ISP] = 1e-3, a.vtile = nullptr),
+};
+// two faults at once, one from each of two groups of checks (shape, null buffers, w, the navigation model, psig, the vehicle) and a few
+// within a group; whichever check comes first in a form decides the line
+static const char* const g_cov_pairs[][2] = {
+    {"B=0", "K=4"},          {"B=0", "x=NULL"},           {"K=4", "w<0"},          {"B=0", "m=15"},        {"K=4", "N0=NULL"},
+    {"B=0", "psig=NULL"},    {"K=4", "sp6=NULL"},         {"gain=NULL", "w=NaN"},  {"report=NULL", "H=NULL"}, {"S0=NULL", "N0=NULL"},
+    {"u=NULL", "m=-1"},      {"N0=NULL", "m=-1"},         {"navrep=NULL", "rm=0"}, {"S0=NULL", "psig=NULL"}, {"navrep=NULL", "psig=NULL"},
+    {"u=NULL", "sp<0"},      {"N0=NULL", "sp.fin"},       {"w<0", "m=15"},         {"w=NaN", "N0=NULL"},   {"w<0", "psig=NULL"},
+    {"w=NaN", "sp=NaN"},     {"m=15", "H=NULL"},          {"rm=NULL", "H=NaN"},    {"rm=NaN", "H=NaN"},    {"rm=0", "psig=NULL"},
+    {"m=15", "psig=NULL"},   {"H=NaN", "sp.aero"},        {"m=-1", "sp6=NULL"},    {"sp<0", "sp.fin"},     {"sp.aero", "sp.isp-without-vtile"},
+};
+
+static const CovFault* cov_fault(const char* name, int traits) {
+    for (const CovFault& f : g_cov_faults)
+        if (!strcmp(f.name, name)) return (traits & f.need) == f.need ? &f : nullptr;
+    fprintf(stderr, "no fault named %s\n", name);
+    abort();
+}
+
+static int cov_refuse(const CovForm& fm, int m, const CovFault* f1, const CovFault* f2) {
+    CovArgs a(m);
+    if (f1) f1->make(a);
+    if (f2) f2->make(a);
+    const size_t a0 = g_allocs, f0 = g_frees;
+    const int rc = fm.call(a);
+    printf("cov-refusal %s m=%d/%s%s%s %d %s\n", fm.entry, m, f1 ? f1->name : "valid", f2 ? "+" : "", f2 ? f2->name : "", rc,
+           a.ctx.err.empty() ? "-" : a.ctx.err.c_str());
+    if (f1) REQUIRE(rc != SCVX_OK && g_allocs == a0);
+    else REQUIRE(rc == SCVX_OK && g_allocs - a0 == g_frees - f0);
+    return 0;
+}
+
+// veh: the _vehicle forms (tests/host_staging_cov_vehicle_asan.cpp runs them) or all the others
+static int cov_refusals(bool veh) {
+    g_nu = 3;
+    for (const CovForm& fm : g_cov_forms) {
+        if (veh != ((fm.traits & C_VEH) != 0)) continue;
+        for (int m : {0, 2}) {
+            if (m && !(fm.traits & C_NAV)) continue;
+            const int traits = fm.traits | (m ? C_M : 0);
+            if (cov_refuse(fm, m, nullptr, nullptr)) return 1;
+            for (const CovFault& f : g_cov_faults)
+                if (cov_fault(f.name, traits) && cov_refuse(fm, m, &f, nullptr)) return 1;
+            for (const auto& p : g_cov_pairs) {
+                const CovFault *f1 = cov_fault(p[0], traits), *f2 = cov_fault(p[1], traits);
+                if (f1 && f2 && cov_refuse(fm, m, f1, f2)) return 1;
+            }
+        }
+    }
+    return 0;
+}
+
 int main() {
-    if (refusals(false)) return 1;
+    if (refusals(false) || cov_refusals(false)) return 1;
     for (int nu : {3, 5})
         for (int m : {0, 6})
             for (int nq : {0, 1, 16})

@@ -8,7 +8,8 @@
 // scvx_cov_path_sigma_f64_host stages and the navigation form what scvx_nav_path_sigma_f64_host stages; vtile costs one upload of
 // B K 2 14 doubles, sens one download of B (K + 1) n 6 doubles, every dense output one download of its documented size, psig = NULL one
 // download less; the launches are the same in number.  The tile call stages three uploads and one download.  A refusal allocates
-// nothing.  The error sweep covers the three forms.  tests/test_host_staging_cov_vehicle_sanitizers.py holds the build recipe.
+// nothing.  The error sweep covers the three forms.  cov_refusals(true) pins what the _vehicle forms refuse, in which words, and which
+// of two faults wins (tests/golden/cov_refusals.txt).  tests/test_host_staging_cov_vehicle_sanitizers.py holds the build recipe.
 #define main host_staging_main
 #include "host_staging_asan.cpp"
 #undef main
@@ -98,6 +99,7 @@ static int veh_error_paths() {
 }
 
 int main() {
+    if (cov_refusals(true)) return 1;   // the _vehicle forms of the table of tests/host_staging_asan.cpp
     for (int nu : {3, 5})
         for (int m : {0, 6})
             if (run_veh(nu, 3, 4, m)) return 1;

@@ -47,3 +47,6 @@ def test_cov_vehicle_staging_is_clean_under_asan_and_ubsan(tmp_path):
     assert len(calls) == 5 * 8                                        # five scenarios: one tile call, four covariance and three navigation forms
     swept = [line.split()[2].rstrip(":") for line in run.stdout.splitlines() if line.startswith("error path ")]
     assert swept == list(SWEPT)
+    # what the _vehicle forms refuse, in which words, and which of two faults wins: as the hand-written bodies had it
+    hs.require_same_lines([line for line in run.stdout.splitlines() if line.startswith("cov-refusal ")],
+                          hs.golden_lines("cov_refusals.txt", "cov-refusal ", lambda line: "_vehicle_" in line), 150)

@@ -79,6 +79,9 @@ def test_host_staging_is_clean_under_asan_and_ubsan(tmp_path):
     # what the sampled calls refuse, in which words, and which of two faults wins: as the six hand-written bodies had it
     require_same_lines([line for line in run.stdout.splitlines() if line.startswith("refusal ")],
                        golden_lines("mc_refusals.txt", "refusal ", lambda line: "_veh_" not in line), 700)
+    # the same for the covariance and navigation analyses (their _vehicle forms: tests/test_host_staging_cov_vehicle_sanitizers.py)
+    require_same_lines([line for line in run.stdout.splitlines() if line.startswith("cov-refusal ")],
+                       golden_lines("cov_refusals.txt", "cov-refusal ", lambda line: "_vehicle_" not in line), 300)
     # every allocation, copy and launch of one call of each form was made to fail, and the error contract held
     swept = [line.split()[2].rstrip(":") for line in run.stdout.splitlines() if line.startswith("error path ")]
     assert swept == list(SWEPT)
