@@ -780,6 +780,78 @@ int scvx_nav_cov_vehicle_f64_host(scvx_ctx *ctx, int B, int K, const double *x, 
                                   const double *w14, double *report, double *navrep, double *psig, double *sig, double *navsig,
                                   double *kf, double *joint, const double *vtile, const double *sp6, double *sens);
 
+/* ---- CLAMP-AWARE covariance analysis by statistical linearisation (no counterpart in the reference) --------------------------------
+ * scvx_cov_propagate_f64 does not model the clamp of SCVX_TRACK_CLAMP, and the plans this solver produces ride Tmin: a clamped flight
+ * loses authority at 12 to 49 of 100 node controls.  This call is the classical CADET (covariance analysis with random-input
+ * describing functions): the thrust clamp is replaced, node by node, by the gain that fits it best in the mean square for a Gaussian
+ * input, and a mean is carried beside the covariance.  It is an APPROXIMATION; the only statistically exact clamp-aware evidence
+ * remains scvx_track_mc_f64.  Notation is that of scvx_cov_propagate_f64; z_k = [x_k - xbar_k; u_k - ubar_k] with u the APPLIED
+ * control, the z that the law of scvx_track_fly_f64 with SCVX_TRACK_CLAMP sees.  A mean mu_k (n) and a central covariance Sigma_k
+ * (n x n) are carried from mu_0 = 0, Sigma_0 = blockdiag((S0 + S0') / 2, 0).  Step k = 0..K-1, with the band (Tlo, Thi) = (Tmin,
+ * Tmax) of the problem or the caller's band2:
+ *   1. mean command  chat = ubar_{k+1} + L_k mu_k  (NU)
+ *   2. That = |chat[0:3]|,  e = chat[0:3] / That
+ *   3. g = L_k[0:3,:]' e  (n),  s = sqrt(max(g' Sigma_k g, 0)): one sigma of the commanded thrust norm, to first order about chat
+ *   4. a = (Tlo - That) / s,  b = (Thi - That) / s,  P_lo = erfc(-a / sqrt 2) / 2,  P_hi = erfc(b / sqrt 2) / 2,  gamma = 1 - P_lo - P_hi
+ *   5. E = Tlo P_lo + Thi P_hi + That gamma + s (phi(a) - phi(b)),  phi the standard normal density, evaluated as E = That + dE with
+ *      dE = s (a P_lo + b P_hi + phi(a) - phi(b)), the same number without a difference of large terms (a term with P_hi is 0 where
+ *      P_hi == 0, so Thi = +inf is allowed; with Tlo == 0 there is no lower clamp -- a norm is never below 0, and the flight's clamp
+ *      does nothing there -- so P_lo = 0 and phi(a) is dropped, the mass a Gaussian puts below 0 being the linearisation's own):
+ *      E = E[sat(t)] for t ~ N(That, s^2), and gamma = E[sat(t) (t - That)] / s^2 is the
+ *      random-input describing-function gain of the clamp
+ *   6. N = I_NU with the thrust block N[0:3,0:3] = gamma e e' + (E / That)(I - e e');  applied mean ahat = chat with ahat[0:3] = E e
+ *   7. mu_{k+1} = F_k mu_k + G_k (ahat - ubar_{k+1})   (evaluated as L_k mu_k, plus dE e on the thrust rows of a saturated node: the
+ *      same vector without the round trip through the plan's control)
+ *   8. Ltilde_k = N L_k,  Mtilde_k = F_k + G_k Ltilde_k
+ *   9. Sigma_{k+1} = sym(Mtilde_k Sigma_k Mtilde_k') + blockdiag(diag(w), 0), symmetrised exactly as the plain call does.
+ * Special cases, part of the contract.  UNSATURATED NODE: P_lo == 0 and P_hi == 0 exactly in double -> N = I, ahat = chat and the rows
+ * of L_k are left untouched: with a band nobody reaches Sigma_k is BITWISE scvx_cov_propagate_f64's and mu_k is exactly 0.  s == 0:
+ * gamma = 1 if Tlo <= That <= Thi, else 0; E = min(max(That, Tlo), Thi); P_lo = (That < Tlo), P_hi = (That > Thi).  That == 0: no
+ * clamp at that node (the flight's clamp leaves a zero thrust alone): P_lo = P_hi = s = 0, gamma = 1.  A non-finite tile, gain, S0 or
+ * planned control makes its own trajectory's report and satrep NaN, and its dense rows from the node it enters, and touches no other.
+ * Limits: FIRST ORDER about the plan in the dynamics; QUASI-LINEAR in the clamp (Gaussian input, the norm linearised about the mean
+ * command, the remnant Var(sat) - gamma^2 s^2 dropped); the covariances live at the nodes; w is the per-segment lump; the fin-norm
+ * clamp of SCVX_MODEL_FINS is NOT modelled (N's fin block is I: a mean fin command of zero has no direction to linearise along); the
+ * gimbal cone is not projected, as in the flight.  Expect a factor of about 2 in standard deviation; this is not a statistical match.
+ * Measured with the CPU reference (tests/cov_clamp_reference.py against 2,048 clamped flights of the C oracle per case; the two golden
+ * plans, handover factor scaled by 0.1, 0.3 and 1; SL this call, LIN scvx_cov_propagate_f64), ranges over the six cases:
+ *     trace of the landing v block, LIN / sampled 0.017 - 0.115     SL / sampled 0.28 - 1.64
+ *     trace of the landing r block, LIN / sampled 0.012 - 0.90      SL / sampled 0.30 - 1.60
+ *     SL / sampled: mass variance 0.76 - 0.99, q block 0.70 - 0.99, w block 0.93 - 1.03
+ *     landing bias (LIN predicts none): cosine with the sampled mean 0.949 - 0.998, norm SL / sampled 0.98 - 2.38
+ *     share of commands clamped (LIN predicts none): P_LO / sampled OUT_LO 1.28 - 1.46,  P_HI / sampled OUT_HI 1.10 - 1.22
+ *
+ * satrep, SCVX_SAT_NREP doubles per trajectory: */
+#define SCVX_SAT_NREP 16
+#define SCVX_SAT_SIG_M 0       /* SIG_M .. SIG_W as SCVX_COV_SIG_M .. SIG_W, from Sigma_K                                       */
+#define SCVX_SAT_SIG_R 1
+#define SCVX_SAT_SIG_V 2
+#define SCVX_SAT_SIG_Q 3
+#define SCVX_SAT_SIG_W 4
+#define SCVX_SAT_BIAS_M 5      /* |mu_K[0]|, and the norms of the r, v, q, w blocks of mu_K: the predicted landing bias          */
+#define SCVX_SAT_BIAS_R 6
+#define SCVX_SAT_BIAS_V 7
+#define SCVX_SAT_BIAS_Q 8
+#define SCVX_SAT_BIAS_W 9
+#define SCVX_SAT_RMS_R 10      /* sqrt(SIG_R^2 + BIAS_R^2): the root mean square landing miss about the planned node              */
+#define SCVX_SAT_RMS_V 11      /* the same for v                                                                                  */
+#define SCVX_SAT_P_LO 12       /* mean over k of P_lo, of P_hi: the predicted shares of node commands clamped from below, from    */
+#define SCVX_SAT_P_HI 13       /* above -- the counterparts of SCVX_MC_OUT_LO / OUT_HI of a flight with the clamp                 */
+#define SCVX_SAT_GAIN_MIN 14   /* min over k of gamma_k: 1 = the law keeps its authority everywhere, 0 = a node where it has none */
+#define SCVX_SAT_BIAS_PEAK 15  /* max over nodes 0..K of |mu_k[0:14]|_2                                                           */
+/* Arguments up to w14 as scvx_cov_propagate_f64.  band2: a HOST array (Tlo, Thi) in both forms, or NULL for the problem's (Tmin,
+ * Tmax).  report [B][SCVX_COV_NREP]: the plain report read off Sigma_k by the code of scvx_cov_propagate_f64; its N_TMAX / N_TMIN /
+ * S_THRUST then describe the APPLIED control about the planned one and are not headroom figures.  satrep [B][SCVX_SAT_NREP].
+ * Optional dense outputs (NULL = not wanted): mean [B][K+1][n] = mu_k; sig, covK, cov as the plain call; satk [B][K][4] = (That, s,
+ * P_lo, P_hi) of node k + 1.  The _f64 form is asynchronous on the context's stream.  SCVX_ERR_ARG for everything
+ * scvx_cov_propagate_f64 refuses, a null satrep, and a band2 with a non-finite Tlo, a NaN Thi, Tlo < 0 or Tlo > Thi. */
+int scvx_cov_clamp_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *deriv_dev,
+                       const double *gain_dev, const double *S0_dev, const double *w14, const double *band2, double *report_dev,
+                       double *satrep_dev, double *mean_dev, double *sig_dev, double *covK_dev, double *cov_dev, double *satk_dev);
+int scvx_cov_clamp_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *deriv, const double *gain,
+                            const double *S0, const double *w14, const double *band2, double *report, double *satrep, double *mean,
+                            double *sig, double *covK, double *cov, double *satk);
+
 /* fp32 forms of the two discretisation entry points (SURVEY.md 8b "_f64/_f32"; BASELINE configs[3-4] name fp32): the
  * same layouts in float, float arithmetic throughout (RK4 state + sensitivity columns), tables read from the same
  * double coefficients.  Stated tolerance against the fp64 path: 2e-5 relative on endpoint, 2e-4 on derivative at
@@ -1096,6 +1168,13 @@ int scvx_batch_margins_from_cov_veh(scvx_batch *b, const double *q14, const doub
 int scvx_batch_margins_from_nav_veh(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0,
                                     const double *N0, int m, const double *H, const double *rm, const double *w14, double nsigma,
                                     double cap, unsigned which, double *psig, const double *sp6);
+
+/* scvx_cov_clamp_f64 on the batch's current accepted iterate, its own derivative tiles (float tiles are widened on load) and the gains
+ * of q14 / rNU / qf14, as scvx_batch_cov: S0, w14, band2 and every output are host arrays, and every output may be NULL.  The batch is
+ * left untouched.  SCVX_ERR_ARG as scvx_batch_cov and for the band2 that scvx_cov_clamp_f64 refuses. */
+int scvx_batch_cov_clamp(scvx_batch *b, const double *q14, const double *rNU, const double *qf14, const double *S0, const double *w14,
+                         const double *band2, double *report, double *satrep, double *mean, double *sig, double *covK, double *cov,
+                         double *satk);
 
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,

@@ -440,6 +440,68 @@ cov_propagate_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr
         (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), report_dev, sig_dev, covK_dev, cov_dev), "scvx_cov_propagate_f64")
 
+# ---- clamp-aware covariance analysis by statistical linearisation (new) ---------------------------------------------------------
+# include/scvx.h, "CLAMP-AWARE covariance analysis": the thrust clamp of the closed-loop flight as a random-input describing function, a
+# mean beside the covariance; an approximation.  band = (Tlo, Thi) or nothing (the problem's Tmin, Tmax).  satrep is SAT_NREP x B
+# (rows SAT_* + 1); dense outputs: mean n x (K+1) x B, sig, covK, cov as covariance, satk 4 x K x B = (That, s, P_lo, P_hi).
+const SAT_NREP = 16   # SCVX_SAT_NREP
+const SAT_SIG_M = 0; const SAT_SIG_R = 1; const SAT_SIG_V = 2; const SAT_SIG_Q = 3; const SAT_SIG_W = 4
+const SAT_BIAS_M = 5; const SAT_BIAS_R = 6; const SAT_BIAS_V = 7; const SAT_BIAS_Q = 8; const SAT_BIAS_W = 9
+const SAT_RMS_R = 10; const SAT_RMS_V = 11; const SAT_P_LO = 12; const SAT_P_HI = 13; const SAT_GAIN_MIN = 14; const SAT_BIAS_PEAK = 15
+_cov_band(band) = band === nothing ? nothing : Float64[band[1], band[2]]
+
+# the current accepted iterate of a batch under its own LQR gains: (report, satrep, mean, sig, covK, cov, satk)
+function cov_clamp(b::Batch, S0::Array{Float64,3}; w=nothing, band=nothing, q=1.0, r=1.0, qf=100.0, dense::Bool=false)
+    K = b.cache.problem.K
+    NU = Int(ccall((:scvx_control_dim, LIB), Cint, (Ptr{Cvoid},), b.cache.ctx)); n = 14 + NU
+    size(S0) == (14, 14, b.B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, b.B)
+    satrep = Matrix{Float64}(undef, SAT_NREP, b.B)
+    mean = dense ? Array{Float64,3}(undef, n, K + 1, b.B) : nothing
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, b.B) : nothing
+    covK = dense ? Array{Float64,3}(undef, n, n, b.B) : nothing
+    cov = dense ? Array{Float64,4}(undef, n, n, K + 1, b.B) : nothing
+    satk = dense ? Array{Float64,3}(undef, 4, K, b.B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    bd = _cov_band(band)
+    GC.@preserve wv bd check(b.cache.ctx, ccall((:scvx_batch_cov_clamp, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, _track_w(q, 14), _track_w(r, NU), _track_w(qf, 14), S0, _cov_opt(wv), _cov_opt(bd), report, satrep, _cov_opt(mean),
+        _cov_opt(sig), _cov_opt(covK), _cov_opt(cov), _cov_opt(satk)), "scvx_batch_cov_clamp")
+    return report, satrep, mean, sig, covK, cov, satk
+end
+
+# any plans (host arrays), shapes as covariance(cache, ...)
+function cov_clamp(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, deriv::Array{Float64,4}, gain::Array{Float64,4},
+                   S0::Array{Float64,3}; w=nothing, band=nothing, dense::Bool=false)
+    K = size(x, 2) - 1; B = size(x, 3); NU = size(u, 1); n = 14 + NU
+    size(S0) == (14, 14, B) || error("S0 must be 14 x 14 x B")
+    report = Matrix{Float64}(undef, COV_NREP, B)
+    satrep = Matrix{Float64}(undef, SAT_NREP, B)
+    mean = dense ? Array{Float64,3}(undef, n, K + 1, B) : nothing
+    sig = dense ? Array{Float64,3}(undef, n, K + 1, B) : nothing
+    covK = dense ? Array{Float64,3}(undef, n, n, B) : nothing
+    cov = dense ? Array{Float64,4}(undef, n, n, K + 1, B) : nothing
+    satk = dense ? Array{Float64,3}(undef, 4, K, B) : nothing
+    wv = w === nothing ? nothing : _track_w(w, 14)
+    bd = _cov_band(band)
+    GC.@preserve wv bd check(cache.ctx, ccall((:scvx_cov_clamp_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, deriv, gain, S0, _cov_opt(wv), _cov_opt(bd), report, satrep, _cov_opt(mean), _cov_opt(sig), _cov_opt(covK),
+        _cov_opt(cov), _cov_opt(satk)), "scvx_cov_clamp_f64_host")
+    return report, satrep, mean, sig, covK, cov, satk
+end
+
+# the same on device pointers, asynchronous on the context's stream; w and band stay host vectors (or nothing)
+cov_clamp_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, deriv_dev::Ptr{Cdouble}, gain_dev::Ptr{Cdouble},
+               S0_dev::Ptr{Cdouble}, w::Union{Nothing,Vector{Float64}}, band::Union{Nothing,Vector{Float64}}, report_dev::Ptr{Cdouble},
+               satrep_dev::Ptr{Cdouble}, mean_dev::Ptr{Cdouble}, sig_dev::Ptr{Cdouble}, covK_dev::Ptr{Cdouble}, cov_dev::Ptr{Cdouble},
+               satk_dev::Ptr{Cdouble}) =
+    GC.@preserve w band check(cache.ctx, ccall((:scvx_cov_clamp_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, _cov_opt(w), _cov_opt(band), report_dev, satrep_dev, mean_dev,
+        sig_dev, covK_dev, cov_dev, satk_dev), "scvx_cov_clamp_f64")
+
 # ---- navigation-error (LQG) covariance analysis (new): the closed loop flown on an estimate, to first order --------------------
 # include/scvx.h, "navigation-error (LQG) covariance analysis".  S0, N0 are 14 x 14 x B; H is 14 x m (column-major == [m][14]) or
 # nothing (no measurement), rm a scalar or m variances; the reports are COV_NREP x B and NAV_NREP x B (rows NAV_* + 1); dense outputs:

@@ -78,6 +78,11 @@ COV_NREP = 16
 COV_COLUMNS = ("SIG_M", "SIG_R", "SIG_V", "SIG_Q", "SIG_W", "ELL_A", "ELL_B", "ELL_ANG", "SIG_PEAK", "S_THRUST", "N_MASS", "N_GLIDE",
                "N_TILT", "N_RATE", "N_TMAX", "N_TMIN")
 COV_INDEX = {n: i for i, n in enumerate(COV_COLUMNS)}
+# scvx_cov_clamp_*: the columns of satrep [B][SAT_NREP] (the SCVX_SAT_* macros of include/scvx.h)
+SAT_NREP = 16
+SAT_COLUMNS = ("SIG_M", "SIG_R", "SIG_V", "SIG_Q", "SIG_W", "BIAS_M", "BIAS_R", "BIAS_V", "BIAS_Q", "BIAS_W", "RMS_R", "RMS_V", "P_LO", "P_HI",
+               "GAIN_MIN", "BIAS_PEAK")
+SAT_INDEX = {n: i for i, n in enumerate(SAT_COLUMNS)}
 # scvx_cov_path_sigma_*: the columns of psig [B][K+1][PSIG_N] (the SCVX_PSIG_* macros of include/scvx.h)
 PSIG_N = 5
 PSIG_COLUMNS = ("MASS", "GLIDE", "TILT", "RATE", "THRUST")
@@ -211,6 +216,10 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp, _dp, _vp]),
     "scvx_nav_cov_vehicle_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # the clamp-aware covariance analysis: the plain lists with band2 (host) behind w14 and satrep, mean behind report, satk last
+    "scvx_cov_clamp_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _dp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "scvx_cov_clamp_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "scvx_batch_cov_clamp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_nav_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "scvx_batch_margins_from_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint, _dp, _dp]),

@@ -320,17 +320,32 @@ class ScvxBatch:
         from .dynamics import _cov_vehicle
         return _cov_vehicle(self.cache, vehicle, np.zeros((self.B, self.K, _lib.VTILE_N, 14)), (), self.B, self.K)[0]
 
-    def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False, vehicle=None):
+    def covariance(self, S0, w=None, q=None, r=None, qf=None, dense=False, vehicle=None, clamp=False, band=None):
         """Closed-loop covariance analysis of the batch's current accepted iterate under its LQR gains (scvx_batch_cov; S0, w and
         dense as dynamics.cov_propagate_batch, weights as track_gains): a dynamics.CovReport.  The batch is left untouched.
         vehicle = (mu, sp) of montecarlo.vehicle_errors, mu = 0: the report and the dense outputs of Sigma_k + J_k diag(sp^2) J_k', the
-        vehicle errors as consider parameters (scvx_batch_cov_veh: the vehicle tiles of the iterate, then the analysis)."""
-        from .dynamics import CovReport, _cov_dense, _cov_noise, _cov_s0, _track_weights
+        vehicle errors as consider parameters (scvx_batch_cov_veh: the vehicle tiles of the iterate, then the analysis).
+        clamp=True: the clamp-aware analysis by statistical linearisation (scvx_batch_cov_clamp; band and dense as
+        dynamics.cov_propagate_batch with clamp=True): a dynamics.SatCovReport.  Not together with vehicle."""
+        from .dynamics import (CovReport, SatCovReport, _cov_band, _cov_clamp_outputs, _cov_dense, _cov_noise, _cov_s0,
+                               _track_weights)
+        if clamp and vehicle is not None:
+            raise ValueError("clamp=True has no vehicle-error form: vehicle= must be None")
+        if not clamp and band is not None:
+            raise ValueError("band= needs clamp=True")
         nu = self.cache.nu
         n = 14 + nu
         qv, rv, qfv = _track_weights(nu, q, r, qf)
         s0 = _cov_s0(S0, self.B)
         wv = _cov_noise(w)
+        if clamp:
+            bd = _cov_band(band)
+            outs = _cov_clamp_outputs(self.B, self.K, n, dense)
+            ptr = lambda a: _p(a) if a is not None else None   # noqa: E731
+            self._chk(self._L.scvx_batch_cov_clamp(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), ptr(wv), ptr(bd),
+                                                   *[ptr(a) for a in outs]), "scvx_batch_cov_clamp")
+            rep, srep, mean, sig, covK, cov, satk = outs
+            return SatCovReport(rep, srep, mean, sig, covK, cov, satk)
         want = _cov_dense(dense)
         rep = np.empty((self.B, _lib.COV_NREP))
         sig = np.empty((self.B, self.K + 1, n)) if "sig" in want else None
@@ -565,12 +580,14 @@ class ScvxBatch:
             out = self.solve()
         return out + self.thrust_margins()
 
-    def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False, vehicle=None):
+    def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False, vehicle=None, clamp=False):
         """Navigation-error covariance analysis of the batch's current accepted iterate flown on an estimate under its LQR gains
         (scvx_batch_nav_cov; S0, N0, H, rm, w and dense as dynamics.nav_cov_batch, weights as track_gains): a dynamics.NavReport.
         The batch is left untouched.  vehicle = (mu, sp), mu = 0: J_k diag(sp^2) J_k' on the truth block (scvx_batch_nav_cov_veh); the
         filter does not know theta, so navsig, kf and NAV_* are those of the call without it."""
         from .dynamics import NavReport, _cov_noise, _cov_s0, _nav_dense, _nav_model, _track_weights
+        if clamp:
+            raise ValueError("clamp=True: the clamp-aware analysis has no navigation form (covariance(clamp=True) feeds the law the truth)")
         nu = self.cache.nu
         n = 14 + nu
         qv, rv, qfv = _track_weights(nu, q, r, qf)

@@ -984,6 +984,15 @@ int scvx_batch_cov(scvx_batch* b, const double* q14, const double* rNU, const do
     return batch_cov_call(b, c, {q14, rNU, qf14}, "scvx_batch_cov");
 }
 
+int scvx_batch_cov_clamp(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* S0, const double* w14,
+                         const double* band2, double* report, double* satrep, double* mean, double* sig, double* covK, double* cov,
+                         double* satk) {
+    scvx::CovCall c;
+    c.S0 = S0, c.w = w14, c.report = report, c.sig = sig, c.covK = covK, c.cov = cov;
+    c.sat = true, c.band2 = band2, c.satrep = satrep, c.mean = mean, c.satk = satk;
+    return batch_cov_call(b, c, {q14, rNU, qf14}, "scvx_batch_cov_clamp");
+}
+
 int scvx_batch_track_fly_nav(scvx_batch* b, const double* q14, const double* rNU, const double* qf14, const double* dx0,
                              const double* nav, int nsub, int flags, double* report, double* xfly, double* ufly) {
     int rc = check_batch(b, true);

@@ -68,19 +68,29 @@ __device__ __forceinline__ void cov_mm16(FA fa, FB fb, FC store, int lane) {
 // from Sigma_k^tot = Sigma_k + J_k diag(sp^2) J_k', formed in V (dead between the T pass and the next step's V pass) behind the step's
 // last barrier (one more barrier); Sigma_k itself is never touched.  Every statement of it sits under `if constexpr (VEH)` and its
 // kernel argument (CovVehK) is a trailing pack that is empty without it: the instantiations without VEH keep their code.
-template <typename DS, int NU, int MF, int PS = 0, int VEH = 0, typename... VA>
+// SAT: 1 = the clamp-aware analysis by statistical linearisation (scvx_cov_clamp_f64, include/scvx.h): a mean mu_k (n, in LDS) is
+// carried beside Sigma_k, and at every step, BEFORE Mtop overwrites [A B-] in place, the mean command chat = ubar_{k+1} + L mu (lane
+// j < NU one n-deep dot product, then NU shuffles: no barrier), g = L[0:3,:]' e and s^2 = g' Sigma g (one n-deep matrix-vector pass, one barrier, a wavefront
+// reduction that leaves every lane the same bits), the scalars P_lo, P_hi, gamma, E (uniform: a wavefront runs them once for all its
+// lanes), mu_{k+1} from the untouched [A | B- | B+] columns (kept in a register until Mtop's barrier), and the three thrust rows of L
+// overwritten with N L (one more barrier).  After that the step is the plain one.  An unsaturated node (P_lo == P_hi == 0) touches
+// neither L nor the arithmetic of Sigma.  Every statement of it sits under `if constexpr (SAT)` and its kernel argument (CovSatK) is the
+// trailing pack's one element; SAT with VEH is not instantiated.
+template <typename DS, int NU, int MF, int PS = 0, int VEH = 0, int SAT = 0, typename... VA>
 __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K, const double* __restrict__ x, const double* __restrict__ u,
                                                            const DS* __restrict__ deriv, const double* __restrict__ gain,
                                                            const double* __restrict__ S0, double* __restrict__ report,
                                                            double* __restrict__ sig, double* __restrict__ covK, double* __restrict__ cov,
                                                            double* __restrict__ psig, VA... va) {
-    static_assert(sizeof...(VA) == (VEH ? 1 : 0), "the VEH instantiations take one CovVehK behind psig, the others nothing");
+    static_assert(sizeof...(VA) == (VEH || SAT ? 1 : 0), "the VEH / SAT instantiations take one CovVehK / CovSatK behind psig, the others nothing");
+    static_assert(!(VEH && SAT), "the clamp-aware analysis has no vehicle-error form");
     constexpr int n = 14 + NU, m = 14 + 2 * NU, NC = m + 1, DSZ = 14 * NC, ND = 14 * m, NL = NU * n, NN = n * n;
     constexpr int NJ = n * SCVX_VEH_N;
     constexpr int NPRE = (ND + 63) / 64, NLPRE = (NL + 63) / 64;
     constexpr int NBORD = NN - 256;   // elements of an n x n product outside its 16 x 16 corner
     __shared__ double Sl[NN], Dl[ND], Ll[NL], Vl[NN], Rl[SCVX_COV_NREP + 1];
     __shared__ double Jl[VEH ? 2 * NJ : 1], Gml[VEH ? 14 * SCVX_VEH_N : 1];   // VEH: J_k and J_{k+1}; Gamma_k, column-major
+    __shared__ double Mul[SAT ? n : 1], Gl[SAT ? n : 1];                       // SAT: mu_k; g = L[0:3,:]' e
     const double* const So = VEH ? Vl : Sl;   // what the outputs read: Sigma_k, with VEH Sigma_k^tot
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= B) return;
@@ -102,6 +112,15 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
     for (int e = lane; e < NL; e += 64) Ll[e] = gb[e];
     if constexpr (VEH)
         for (int e = lane; e < NJ; e += 64) Jl[e] = 0.0;
+    // SAT: the running columns of satrep, the same in every lane: sums of P_lo and P_hi, min gamma, max |mu_k[0:14]|
+    [[maybe_unused]] double splo = 0.0, sphi = 0.0, gmin = inf, bpk = 0.0;
+    if constexpr (SAT) {
+        const CovSatK& sk = veh_first(va...);
+        if (lane < n) {
+            Mul[lane] = 0.0;
+            if (sk.mean) sk.mean[(size_t)b * (K + 1) * n + lane] = 0.0;
+        }
+    }
     // the running columns: lane 0 SIG_PEAK (and the non-finite flag), 1 N_MASS, 2 N_GLIDE, 3 N_TILT, 4 N_RATE, 5 S_THRUST / N_TMAX / N_TMIN
     double acc0 = lane == 0 ? 0.0 : inf, acc1 = inf, acc2 = 0.0, bad = 0.0;
     double pv0 = 0.0, pv1 = 0.0, pv2 = 0.0;
@@ -237,6 +256,93 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             pv1 = lane == 1 ? 0.0 : p[1];
             pv2 = (lane == 1 || lane == 3) ? 0.0 : p[2];
         }
+        [[maybe_unused]] double mun = 0.0;   // SAT: mu_{k+1}[lane], stored behind Mtop's barrier
+        if constexpr (SAT) {
+            const CovSatK& sk = veh_first(va...);
+            const double* un = ub + (size_t)(k + 1) * NU;
+            // 1, 2: the mean command, its norm and direction; dl = L mu is the mean deviation of the command
+            // (lane j < NU forms row j's dot product, the lanes behind it row NU - 1 again; every lane then takes all NU)
+            double dl[NU];
+            double dj = 0.0;
+            {
+                const double* lr = Ll + (lane < NU ? lane : NU - 1) * n;
+#pragma unroll
+                for (int l = 0; l < n; l++) dj = fma(lr[l], Mul[l], dj);
+            }
+#pragma unroll
+            for (int j = 0; j < NU; j++) dl[j] = __shfl(dj, j);
+            const double c0 = un[0] + dl[0], c1 = un[1] + dl[1], c2 = un[2] + dl[2];
+            const double That = sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+            const bool zero = That == 0.0;   // the flight's clamp leaves a zero thrust alone
+            const double e0 = zero ? 0.0 : c0 / That, e1 = zero ? 0.0 : c1 / That, e2 = zero ? 0.0 : c2 / That;
+            // 3: g and s
+            double gl = 0.0;
+            if (lane < n) {
+                gl = fma(Ll[2 * n + lane], e2, fma(Ll[n + lane], e1, Ll[lane] * e0));
+                Gl[lane] = gl;
+            }
+            __syncthreads();
+            double q = 0.0;
+            if (lane < n) {
+                double t = 0.0;
+#pragma unroll
+                for (int l = 0; l < n; l++) t = fma(Sl[lane * n + l], Gl[l], t);
+                q = gl * t;
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o);
+            const double s = cov_sd(q);
+            // 4, 5: the shares, the describing-function gain and the mean of the clamped norm
+            // (E is formed as That + dE, dE = E - That = s (a P_lo + b P_hi + phi(a) - phi(b)): where the clamp is rarely reached every
+            // term of dE is small, and the mean's input dE e does not come out of a difference of terms of the plan's own size)
+            double plo, phi, gam, dE;
+            if (zero) {
+                plo = 0.0, phi = 0.0, gam = 1.0, dE = 0.0;
+            } else if (s == 0.0) {
+                plo = That < sk.Tlo ? 1.0 : 0.0, phi = That > sk.Thi ? 1.0 : 0.0;
+                gam = (plo == 0.0 && phi == 0.0) ? 1.0 : 0.0;
+                dE = fmin(fmax(That, sk.Tlo), sk.Thi) - That;
+            } else {
+                constexpr double r2 = 1.4142135623730951, i2p = 0.3989422804014327;   // sqrt 2, 1 / sqrt(2 pi)
+                const double a = (sk.Tlo - That) / s, bb = (sk.Thi - That) / s;
+                const bool nolo = sk.Tlo == 0.0;   // a norm is never below 0: no lower clamp, as Thi = +inf is no upper one
+                plo = nolo ? 0.0 : 0.5 * erfc(-a / r2), phi = 0.5 * erfc(bb / r2);
+                gam = 1.0 - plo - phi;
+                const double hi = phi == 0.0 ? 0.0 : bb * phi, pa = nolo ? 0.0 : i2p * exp(-0.5 * a * a);
+                dE = s * (a * plo + hi + (pa - i2p * exp(-0.5 * bb * bb)));
+            }
+            const double E = That + dE;
+            const bool satd = !(plo == 0.0 && phi == 0.0);   // a NaN saturates: it reaches L, Sigma and the reports
+            // 6, 7: the applied mean about the plan, and mu_{k+1} from the untouched tile
+            if (satd) dl[0] = fma(dE, e0, dl[0]), dl[1] = fma(dE, e1, dl[1]), dl[2] = fma(dE, e2, dl[2]);   // E e - ubar = L mu + dE e
+            if (lane < 14) {
+                double t = 0.0;
+#pragma unroll
+                for (int l = 0; l < n; l++) t = fma(Dl[l * 14 + lane], Mul[l], t);
+#pragma unroll
+                for (int j = 0; j < NU; j++) t = fma(Dl[(n + j) * 14 + lane], dl[j], t);
+                mun = t;
+            } else if (lane < n) {
+#pragma unroll
+                for (int j = 0; j < NU; j++)
+                    if (lane == 14 + j) mun = dl[j];
+            }
+            // 8: the thrust rows of L become N L = (E / That) L + (gamma - E / That) e g'
+            if (satd && lane < n) {
+                const double r = E / That, d = (gam - r) * gl;
+                Ll[lane] = fma(r, Ll[lane], d * e0);
+                Ll[n + lane] = fma(r, Ll[n + lane], d * e1);
+                Ll[2 * n + lane] = fma(r, Ll[2 * n + lane], d * e2);
+            }
+            if (lane == 0 && sk.satk) {
+                double* o = sk.satk + ((size_t)b * K + k) * 4;
+                o[0] = That, o[1] = s, o[2] = plo, o[3] = phi;
+            }
+            if (sk.mean && lane < n) sk.mean[((size_t)b * (K + 1) + k + 1) * n + lane] = mun;
+            splo += plo, sphi += phi;
+            gmin = nan_min(gmin, gam);
+            __syncthreads();
+        }
         if constexpr (VEH) {
             // Gamma_k's columns (include/scvx.h), while the tile still holds B-
             const CovVehK& vk = veh_first(va...);
@@ -253,6 +359,8 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             Dl[e] = s;
         }
         __syncthreads();
+        if constexpr (SAT)
+            if (lane < n) Mul[lane] = mun;   // next read behind the step's later barriers
         // V = M Sigma
         if (MF) {
             cov_mm16<n>([&](int i, int l) { int st; const double* mp = mrow(i, st); return mp[l * st]; },
@@ -324,6 +432,12 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
             }
         }
         __syncthreads();
+        if constexpr (SAT) {
+            double t = 0.0;
+#pragma unroll
+            for (int i = 0; i < 14; i++) t = fma(Mul[i], Mul[i], t);
+            bpk = nan_max(bpk, sqrt(t));
+        }
         tot(k + 1);
         node_out(k + 1);
     }
@@ -372,6 +486,42 @@ __global__ __launch_bounds__(64) void cov_propagate_kernel(CovK c, int B, int K,
     }
     __syncthreads();
     if (lane < SCVX_COV_NREP) report[(size_t)b * SCVX_COV_NREP + lane] = Rl[lane] + Rl[SCVX_COV_NREP];
+    if constexpr (SAT) {
+        // satrep: one column per lane; the poison of the report is its poison
+        const CovSatK& sk = veh_first(va...);
+        auto mblk = [&](int i0, int i1) {
+            double t = 0.0;
+            for (int i = i0; i < i1; i++) t += Mul[i] * Mul[i];
+            return sqrt(t);
+        };
+        if (lane < SCVX_SAT_NREP) {
+            double v;
+            if (lane <= SCVX_SAT_SIG_W) {
+                v = Rl[lane];   // SCVX_SAT_SIG_* are SCVX_COV_SIG_*
+            } else if (lane == SCVX_SAT_BIAS_M) {
+                v = fabs(Mul[0]);
+            } else if (lane == SCVX_SAT_BIAS_R || lane == SCVX_SAT_RMS_R) {
+                v = mblk(1, 4);
+                if (lane == SCVX_SAT_RMS_R) v = sqrt(Rl[SCVX_COV_SIG_R] * Rl[SCVX_COV_SIG_R] + v * v);
+            } else if (lane == SCVX_SAT_BIAS_V || lane == SCVX_SAT_RMS_V) {
+                v = mblk(4, 7);
+                if (lane == SCVX_SAT_RMS_V) v = sqrt(Rl[SCVX_COV_SIG_V] * Rl[SCVX_COV_SIG_V] + v * v);
+            } else if (lane == SCVX_SAT_BIAS_Q) {
+                v = mblk(7, 11);
+            } else if (lane == SCVX_SAT_BIAS_W) {
+                v = mblk(11, 14);
+            } else if (lane == SCVX_SAT_P_LO) {
+                v = splo / K;
+            } else if (lane == SCVX_SAT_P_HI) {
+                v = sphi / K;
+            } else if (lane == SCVX_SAT_GAIN_MIN) {
+                v = gmin;
+            } else {
+                v = bpk;
+            }
+            sk.satrep[(size_t)b * SCVX_SAT_NREP + lane] = v + Rl[SCVX_COV_NREP];
+        }
+    }
     if constexpr (PS != 0) {
         // a non-finite Sigma anywhere poisons the report; the rows of this trajectory follow it
         const double bd = Rl[SCVX_COV_NREP];
@@ -392,13 +542,16 @@ static hipError_t launch_cov_t(const scvx_ctx* ctx, const CovCall& a, const DS* 
     if (const char* v = std::getenv("SCVX_COV_MFMA"); v && *v) mf = std::atoi(v) != 0;
     const dim3 g((unsigned)a.B), blk(64);
     const CovVehK vk = cov_veh_k(a);
+    const CovSatK sk = cov_sat_k(a, pk.Tmin, pk.Tmax);
 #define SCVX_COV_ARGS g, blk, 0, st, c, a.B, a.K, a.x, a.u, deriv, a.gain, a.S0, a.report, a.sig, a.covK, a.cov, a.psig
 #define SCVX_COV_LAUNCH(NU, MF)                                                                      \
     do {                                                                                             \
-        if (a.veh && a.psig)                                                                         \
-            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1, 1, CovVehK>), SCVX_COV_ARGS, vk); \
+        if (a.sat)                                                                                   \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0, 0, 1, CovSatK>), SCVX_COV_ARGS, sk); \
+        else if (a.veh && a.psig)                                                                    \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1, 1, 0, CovVehK>), SCVX_COV_ARGS, vk); \
         else if (a.veh)                                                                              \
-            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0, 1, CovVehK>), SCVX_COV_ARGS, vk); \
+            hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 0, 1, 0, CovVehK>), SCVX_COV_ARGS, vk); \
         else if (a.psig)                                                                             \
             hipLaunchKernelGGL((cov_propagate_kernel<DS, NU, MF, 1>), SCVX_COV_ARGS);                \
         else                                                                                         \
@@ -449,6 +602,14 @@ int check_cov_call(scvx_ctx* ctx, const CovCall& c, const CovBatch* own) {
         if (!own && (!c.N0 || !c.navrep)) return fail(ctx, SCVX_ERR_ARG, "nav: null buffer (N0, navrep)");
         if ((rc = check_nav_model(ctx, c.m, c.H, c.rm))) return rc;
     }
+    if (c.sat) {
+        if (!own && !c.satrep) return fail(ctx, SCVX_ERR_ARG, "cov clamp: null buffer (satrep)");
+        if (c.band2) {
+            const double lo = c.band2[0], hi = c.band2[1];
+            if (!std::isfinite(lo) || hi != hi || lo < 0.0 || lo > hi)
+                return fail(ctx, SCVX_ERR_ARG, "cov clamp: band2 must be (Tlo, Thi) with a finite Tlo >= 0 and Tlo <= Thi (Thi may be +inf)");
+        }
+    }
     if (c.need_psig && !c.psig) return fail(ctx, SCVX_ERR_ARG, c.nav ? "nav: null buffer (psig)" : "cov: null buffer (psig)");
     // the tracking weights: the margins calls refuse them before the vehicle, the batch-level analyses after it
     if (margins && (rc = check_track_weights(ctx, own->q14, own->rNU, own->qf14))) return rc;
@@ -475,6 +636,7 @@ CovCall stage_cov(Staging& s, const Dims& d, const CovCall& c, bool own) {
     dev.psig = s.out(c.psig, d.psig), dev.sig = s.out(c.sig, d.sig), dev.navsig = s.out(c.navsig, d.navsig);
     dev.covK = s.out(c.covK, d.covK), dev.cov = s.out(c.cov, d.cov), dev.kf = s.out(c.m > 0 ? c.kf : nullptr, d.kf);
     dev.joint = s.out(c.joint, d.joint), dev.sens = s.out(c.sens, d.sens);
+    dev.satrep = c.sat ? s.out_always(c.satrep, d.srep) : nullptr, dev.mean = s.out(c.mean, d.sig), dev.satk = s.out(c.satk, d.satk);
     return dev;
 }
 
@@ -513,6 +675,22 @@ int scvx_cov_path_sigma_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, co
     scvx::CovCall c = scvx::cov_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
     c.psig = psig_dev, c.need_psig = true;
     return scvx::cov_call_dev(ctx, c);
+}
+
+int scvx_cov_clamp_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,
+                       const double* gain_dev, const double* S0_dev, const double* w14, const double* band2, double* report_dev,
+                       double* satrep_dev, double* mean_dev, double* sig_dev, double* covK_dev, double* cov_dev, double* satk_dev) {
+    scvx::CovCall c = scvx::cov_record(B, K, x_dev, u_dev, deriv_dev, gain_dev, S0_dev, w14, report_dev);
+    c.sig = sig_dev, c.covK = covK_dev, c.cov = cov_dev, c.sat = true, c.band2 = band2, c.satrep = satrep_dev, c.mean = mean_dev, c.satk = satk_dev;
+    return scvx::cov_call_dev(ctx, c);
+}
+
+int scvx_cov_clamp_f64_host(scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* deriv, const double* gain,
+                            const double* S0, const double* w14, const double* band2, double* report, double* satrep, double* mean,
+                            double* sig, double* covK, double* cov, double* satk) {
+    scvx::CovCall c = scvx::cov_record(B, K, x, u, deriv, gain, S0, w14, report);
+    c.sig = sig, c.covK = covK, c.cov = cov, c.sat = true, c.band2 = band2, c.satrep = satrep, c.mean = mean, c.satk = satk;
+    return scvx::cov_call_host(ctx, c, "scvx_cov_clamp_f64_host");
 }
 
 int scvx_cov_vehicle_f64(scvx_ctx* ctx, int B, int K, const double* x_dev, const double* u_dev, const double* deriv_dev,

@@ -24,6 +24,10 @@ struct CovCall {
     bool veh = false;
     const double *vtile = nullptr, *sp6 = nullptr;
     double* sens = nullptr;
+    // sat: a _clamp form (the SAT instantiations); band2: (Tlo, Thi), a host array, or nullptr for the problem's (Tmin, Tmax)
+    bool sat = false;
+    const double* band2 = nullptr;
+    double *satrep = nullptr, *mean = nullptr, *satk = nullptr;
 };
 
 // the record of a context-level form: what every one of them takes
@@ -61,6 +65,11 @@ inline CovVehK cov_veh_k(const CovCall& c) {
     CovVehK k{c.veh ? c.vtile : nullptr, c.veh ? c.sens : nullptr, {}};
     for (int i = 0; i < SCVX_VEH_N; i++) k.p[i] = c.veh ? c.sp6[i] * c.sp6[i] : 0.0;
     return k;
+}
+
+// the kernel argument of the SAT instantiations: the caller's band, or the problem's
+inline CovSatK cov_sat_k(const CovCall& c, double Tmin, double Tmax) {
+    return CovSatK{c.band2 ? c.band2[0] : Tmin, c.band2 ? c.band2[1] : Tmax, c.satrep, c.mean, c.satk};
 }
 
 }  // namespace scvx

@@ -120,7 +120,13 @@ struct CovVehK {
     double* sens;
     double p[SCVX_VEH_N];
 };
-// the one element of a VEH instantiation's trailing kernel-argument pack
+// the kernel argument of the SAT instantiations (scvx_cov_clamp_f64): the band, satrep [B][SCVX_SAT_NREP], and mean [B][K+1][n],
+// satk [B][K][4] or nullptr (cov_sat_k, scvx_cov.hpp)
+struct CovSatK {
+    double Tlo, Thi;
+    double *satrep, *mean, *satk;
+};
+// the one element of a VEH or SAT instantiation's trailing kernel-argument pack
 template <typename T>
 __device__ __forceinline__ const T& veh_first(const T& t) { return t; }
 // Element (i, cI) of Gamma_k = d x_{k+1} / d theta (include/scvx.h): D the segment's tile (column-major, stride 14: A | B- | B+), uk =

@@ -90,6 +90,7 @@ struct Dims {
     size_t x, u, b, seg, deriv, gain, p0, c14, b14, frep, crep, nrep, mcrep, sig, covK, cov, psig, navsig, kf, joint;   // per plan
     size_t xi, eta, nud, flights, s14, fed, jmean, jcov, flightq, pathq, pathv, zeta, theta;                           // sampled
     size_t vtile, sens;                                                                                                // vehicle errors
+    size_t srep, satk;                                                                                                 // clamp-aware covariance
     Dims(int B_, int K_, int NU, int S_ = 0, int m_ = 0, int nq_ = 0) {
         const size_t B = (size_t)B_, K = (size_t)K_, S = (size_t)S_, m = (size_t)m_, nq = (size_t)nq_, n = 14 + (size_t)NU, N = n + 14;
         x = B * (K + 1) * 14, u = B * (K + 1) * NU, b = B, seg = B * K * 14, deriv = B * K * 14 * (14 + 2 * NU + 1);
@@ -101,6 +102,7 @@ struct Dims {
         jmean = B * 28, jcov = B * 784, flightq = B * SCVX_FLIGHT_NREP * nq, pathq = psig * nq, pathv = psig * S;
         zeta = S * SCVX_VEH_N, theta = B * S * SCVX_VEH_N;
         vtile = B * K * SCVX_VTILE_N * 14, sens = B * (K + 1) * n * SCVX_VEH_N;
+        srep = B * SCVX_SAT_NREP, satk = B * K * 4;
     }
 };
 

@@ -327,6 +327,55 @@ class CovReport:
         return np.where(np.isnan(g).any(axis=1), np.nan, np.min(np.nan_to_num(g, nan=np.inf), axis=1))
 
 
+class SatCovReport(CovReport):
+    """The two reports of a clamp-aware covariance analysis (scvx_cov_clamp_f64, include/scvx.h): everything a CovReport has, read off
+    the statistically linearised Sigma_k (N_TMAX / N_TMIN / S_THRUST then describe the applied control and are no headroom figures),
+    plus `satraw` [B][16] with one named view per column (report.BIAS_R, report.P_LO, report.GAIN_MIN, ... -- _lib.SAT_COLUMNS; the SIG_*
+    views are the CovReport's, which hold the same values) and the optional dense outputs `mean` [B][K+1][14+nu] = mu_k and `satk`
+    [B][K][4] = (That, s, P_lo, P_hi) of node k + 1, or None.  An approximation: expect a factor of about 2 in standard deviation."""
+
+    def __init__(self, raw, satraw, mean=None, sig=None, covK=None, cov=None, satk=None):
+        super().__init__(raw, sig, covK, cov)
+        self.satraw = np.asarray(satraw, np.float64).reshape(-1, _lib.SAT_NREP)
+        self.mean = mean
+        self.satk = satk
+        for name, i in _lib.SAT_INDEX.items():
+            if not name.startswith("SIG_"):
+                setattr(self, name, self.satraw[:, i])
+
+
+def _cov_band(band):
+    """band of the clamp-aware analysis: None (the problem's Tmin, Tmax) or (Tlo, Thi) -> None or a contiguous [2]; what the library
+    refuses is a ValueError here"""
+    if band is None:
+        return None
+    a = np.ascontiguousarray(band, np.float64)
+    if a.shape != (2,) or not np.isfinite(a[0]) or np.isnan(a[1]) or a[0] < 0.0 or a[0] > a[1]:
+        raise ValueError("band = (Tlo, Thi) with a finite Tlo >= 0 and Tlo <= Thi (Thi may be inf), not %r" % (band,))
+    return a
+
+
+def _cov_clamp_dense(dense):
+    """dense of the clamp-aware analysis: False / True (all five) / names out of "mean", "sig", "covK", "cov", "satk" -> the set"""
+    names = {"mean", "sig", "covK", "cov", "satk"}
+    if dense is True:
+        return names
+    if not dense:
+        return set()
+    want = {dense} if isinstance(dense, str) else set(dense)
+    if not want <= names:
+        raise ValueError("dense: True, False or names out of 'mean', 'sig', 'covK', 'cov', 'satk', not %r" % (dense,))
+    return want
+
+
+def _cov_clamp_outputs(B, K, n, dense):
+    """(report, satrep, mean, sig, covK, cov, satk): the outputs of a _clamp call in the order of its argument list, None = not wanted"""
+    want = _cov_clamp_dense(dense)
+    return (np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.SAT_NREP)), np.empty((B, K + 1, n)) if "mean" in want else None,
+            np.empty((B, K + 1, n)) if "sig" in want else None, np.empty((B, n, n)) if "covK" in want else None,
+            np.empty((B, K + 1, n, n)) if "cov" in want else None, np.empty((B, K, 4)) if "satk" in want else None)
+
+
 def _cov_s0(S0, B):
     """S0 as [B][14][14], one [14][14] for all, or a [14] vector of standard deviations (S0 = diag(sd^2)) -> contiguous [B][14][14]"""
     a = np.asarray(S0, np.float64)
@@ -361,7 +410,8 @@ def _cov_dense(dense):
     return want
 
 
-def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, dense=False, vehicle=None, vtile=None) -> CovReport:
+def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, dense=False, vehicle=None, vtile=None, clamp=False,
+                        band=None) -> CovReport:
     """Closed-loop covariance of the plans x [B][K+1][14], u [B][K+1][nu] tracked under the gains gain [B][K][nu][14+nu] (what
     track_gains_batch returns) from the derivative tiles deriv [B][K][14+2nu+1][14] (what linearize_batch returns), on the device
     (scvx_cov_propagate_f64_host; the recursion and its limits are in include/scvx.h).  S0: the handover covariance, [B][14][14], one
@@ -369,7 +419,15 @@ def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, d
     segment, a scalar or [14] (None = 0).  dense: True for sig, covK and cov, or a subset of those names.
     vehicle: (mu, sp) of montecarlo.vehicle_errors with mu = 0 -- every output is then read off Sigma_k + J_k diag(sp^2) J_k'
     (scvx_cov_vehicle_f64_host; first order, the thrust columns are the command's), vtile: vehicle_tiles_batch's, needed when ISP or
-    AERO is dispersed; dense may then name "sens" (report.sens = J_k).  Without vehicle the call is the one it was."""
+    AERO is dispersed; dense may then name "sens" (report.sens = J_k).  Without vehicle the call is the one it was.
+    clamp: True for the clamp-aware analysis by statistical linearisation (scvx_cov_clamp_f64_host: the thrust clamp of
+    track_fly_batch(clamp=True) as a random-input describing function, a mean beside the covariance; an approximation, see
+    include/scvx.h) -- a SatCovReport; band: (Tlo, Thi) in place of the problem's (Tmin, Tmax); dense then: True or names out of
+    "mean", "sig", "covK", "cov", "satk".  Not together with vehicle.  With clamp=False the call is the one it was."""
+    if clamp and (vehicle is not None or vtile is not None):
+        raise ValueError("clamp=True has no vehicle-error form: vehicle= and vtile= must be None")
+    if not clamp and band is not None:
+        raise ValueError("band= needs clamp=True")
     x = np.ascontiguousarray(x, np.float64)
     u = np.ascontiguousarray(u, np.float64)
     gain = np.ascontiguousarray(gain, np.float64)
@@ -386,6 +444,14 @@ def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, d
         raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
     s0 = _cov_s0(S0, B)
     wv = _cov_noise(w)
+    if clamp:
+        bd = _cov_band(band)
+        outs = _cov_clamp_outputs(B, K, n, dense)
+        ptr = lambda a: _p(a) if a is not None else None   # noqa: E731
+        _lib.check(cache.handle, cache._L.scvx_cov_clamp_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), ptr(wv),
+                                                                  ptr(bd), *[ptr(a) for a in outs]), "scvx_cov_clamp_f64_host")
+        rep, srep, mean, sig, covK, cov, satk = outs
+        return SatCovReport(rep, srep, mean, sig, covK, cov, satk)
     sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
     want = _cov_dense(dense)
     rep = np.empty((B, _lib.COV_NREP))

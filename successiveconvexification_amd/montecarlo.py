@@ -542,6 +542,28 @@ def dispersion_summary(covreport, status):
     return out
 
 
+def clamp_summary(rep, status):
+    """What a batch of plans has to say once its clamp-aware covariance analysis is done.  rep: a dynamics.SatCovReport or its satraw
+    [N][16] array; status [N]: the SCvx statuses of scvx_solve.  Returns a plain dict: counts by SCvx status, the number of converged
+    plans, and min / median / p99 / max of every column of _lib.SAT_COLUMNS over the converged plans (None where there is none).
+    Pure numpy."""
+    from ._lib import SAT_COLUMNS, SAT_INDEX, SAT_NREP
+    names = {0: "converged", 1: "running", 2: "rejected", 3: "solver", 4: "nonfinite", 5: "infeasible"}
+    raw = np.asarray(getattr(rep, "satraw", rep), np.float64).reshape(-1, SAT_NREP)
+    status = np.asarray(status).reshape(-1)
+    if status.shape[0] != raw.shape[0]:
+        raise ValueError("report has %d rows, status %d" % (raw.shape[0], status.shape[0]))
+    counts = {n: int(np.sum(status == c)) for c, n in names.items()}
+    counts["other"] = int(status.shape[0] - sum(counts.values()))
+    conv = raw[status == 0]
+    out = {"n": int(raw.shape[0]), "counts": counts, "converged": int(conv.shape[0]), "stats": {}}
+    for n in SAT_COLUMNS:
+        c = conv[:, SAT_INDEX[n]]
+        out["stats"][n] = None if c.shape[0] == 0 else {"min": float(np.min(c)), "median": float(np.median(c)),
+                                                         "p99": float(np.percentile(c, 99)), "max": float(np.max(c))}
+    return out
+
+
 def mc_summary(rep, status):
     """What a batch of plans has to say once its sampled dispersion is done.  rep: a dynamics.McReport or its raw [N][48] array; status
     [N]: the SCvx statuses of scvx_solve.  Returns a plain dict: counts by SCvx status, the number of converged plans, the samples per

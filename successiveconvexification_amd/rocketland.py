@@ -113,14 +113,18 @@ def track_mc(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None
 
 
 def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, w=None, q=None, r=None, qf=None, dense=False,
-               vehicle=None):
+               vehicle=None, clamp=False, band=None):
     """Closed-loop covariance analysis of an iterate's plan tracked under the time-varying LQR gains about it, from the handover
     covariance S0 ([14][14], or a [14] vector of standard deviations) with the per-segment process noise w (dynamics.track_gains_batch
     on the plan's own linearisation, dynamics.cov_propagate_batch).  A dynamics.CovReport of one row.  vehicle = (mu, sp) of
-    montecarlo.vehicle_errors, mu = 0: the vehicle errors as consider parameters (dynamics.vehicle_tiles_batch on the plan)."""
+    montecarlo.vehicle_errors, mu = 0: the vehicle errors as consider parameters (dynamics.vehicle_tiles_batch on the plan).
+    clamp=True: the clamp-aware analysis by statistical linearisation, a dynamics.SatCovReport (band, dense: cov_propagate_batch's);
+    not together with vehicle."""
     from .dynamics import cov_propagate_batch, linearize_batch, track_gains_batch, vehicle_tiles_batch
     if S0 is None:
         raise ValueError("covariance: S0 (the handover covariance) is required")
+    if clamp and vehicle is not None:
+        raise ValueError("clamp=True has no vehicle-error form: vehicle= must be None")
     cache = cache if cache is not None else iteration.cache
     x = np.stack([pt.state for pt in iteration.about])[None]
     u = np.stack([pt.control for pt in iteration.about])[None]
@@ -128,6 +132,8 @@ def covariance(iteration: ProblemIteration, cache: IntegratorCache = None, S0=No
     _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / x.shape[1])
     gain = track_gains_batch(cache, deriv, q, r, qf)
     kw = {} if vehicle is None else dict(vehicle=vehicle, vtile=vehicle_tiles_batch(cache, x, u, sigma))
+    if clamp or band is not None:
+        kw.update(clamp=clamp, band=band)
     return cov_propagate_batch(cache, x, u, deriv, gain, S0, w, dense=dense, **kw)
 
 
@@ -153,12 +159,14 @@ def robustify(iteration: ProblemIteration, cache: IntegratorCache = None, S0=Non
 
 
 def navigation(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, N0=None, H=None, rm=None, w=None, q=None, r=None,
-               qf=None, dense=False, vehicle=None):
+               qf=None, dense=False, vehicle=None, clamp=False):
     """Navigation-error covariance analysis of an iterate's plan flown on an estimate under the time-varying LQR gains about it: S0 the
     handover covariance of the truth, N0 that of the navigation error, H [m][14] and rm the measurement taken at every node but the
     last (H None: inertial propagation only), w the per-segment process noise (dynamics.track_gains_batch on the plan's own
     linearisation, dynamics.nav_cov_batch).  A dynamics.NavReport of one row.  vehicle = (mu, sp), mu = 0: as covariance()."""
     from .dynamics import linearize_batch, nav_cov_batch, track_gains_batch, vehicle_tiles_batch
+    if clamp:
+        raise ValueError("clamp=True: the clamp-aware analysis has no navigation form (covariance(clamp=True) feeds the law the truth)")
     if S0 is None or N0 is None:
         raise ValueError("navigation: S0 and N0 (the handover covariances of the truth and of the navigation error) are required")
     cache = cache if cache is not None else iteration.cache
