@@ -5,7 +5,7 @@ of a node, one process per GPU, and all-gathers the final trajectories over RCCL
 import ctypes as C
 import numpy as np
 
-from . import _lib
+from . import _calls, _lib
 from .dynamics import IntegratorCache
 
 _dp = C.POINTER(C.c_double)
@@ -266,54 +266,31 @@ class ScvxBatch:
         scvx_batch_track_mc_nav_rng); rng="host" is the call it was.  vehicle = (mu, sp) and the dense name "theta" as
         dynamics.track_mc_batch: per-flight vehicle errors (scvx_batch_track_mc_veh / scvx_batch_track_mc_nav_veh); None is the call it
         was."""
-        import ctypes as C
-        from .dynamics import McReport, _McQ, _McVeh, _mc_inputs, _mc_outputs, _mc_rng, _track_weights
-        rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
-        vh = _McVeh(vehicle, dense)
-        mq = _McQ(quantiles, per_node, vh.rest)
-        dense = mq.rest
-        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
+        from .dynamics import _mc_call, _mc_inputs, _mc_keywords, _mc_nav_inputs, _nav_arg
+        rg, vh, mq = _mc_keywords(rng, draws, independent, seed, sample_lo, plan_lo, vehicle, dense, quantiles, per_node)
+        f = self._record(q, r, qf)
+        f.update(nsub=nsub or 0, flags=_lib.TRACK_CLAMP if clamp else 0, tol=tol)
         if nav is not None:
-            from .dynamics import McNavReport, _mc_nav_inputs, _mc_nav_outputs, _nav_arg
             n0, m, Hm, rmv = _nav_arg(nav, self.B)
             c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(S0, n0, self.B, self.K, m, samples, seed, w, draws, sample_lo,
                                                                 rg is not None)
-            S = int(samples) if rg is not None else xi0.shape[0]
-            red, dn = _mc_nav_outputs(self.B, S, self.K, dense)
-            opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-            drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
-            args = (self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), *drw, opt(wv), _p(n0), _p(cn),
-                    *(() if rg is not None and not vh.on else (opt(xin), opt(nud))), m, opt(Hm), opt(rmv), int(nsub or 0),
-                    _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red], *[opt(a) for a in dn])
-            if vh.on:
-                self._chk(self._L.scvx_batch_track_mc_nav_veh(*args, *mq.args(self.B, self.K, S),
-                                                              *vh.args(self.B, S, rg, wv is not None, seed, sample_lo)),
-                          "scvx_batch_track_mc_nav_veh")
-            elif rg is not None:
-                self._chk(self._L.scvx_batch_track_mc_nav_rng(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_nav_rng")
-            elif mq.on:
-                self._chk(self._L.scvx_batch_track_mc_nav_q(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_nav_q")
-            else:
-                self._chk(self._L.scvx_batch_track_mc_nav(*args), "scvx_batch_track_mc_nav")
-            return McNavReport(*red, *dn)._with_q(mq)._with_veh(vh)
-        c0, xi0, eta, sw = _mc_inputs(S0, self.B, self.K, samples, seed, w, draws, sample_lo, rg is not None)
-        S = int(samples) if rg is not None else xi0.shape[0]
-        rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(self.B, S, dense)
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-        drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
-        args = (self.handle, _p(qv), _p(rv), _p(qfv), S, _p(c0), *drw, opt(sw), None, int(nsub or 0),
-                _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov), opt(flights), opt(xland), opt(dx0))
-        if vh.on:
-            self._chk(self._L.scvx_batch_track_mc_veh(*args, *mq.args(self.B, self.K, S),
-                                                      *vh.args(self.B, S, rg, sw is not None, seed, sample_lo)),
-                      "scvx_batch_track_mc_veh")
-        elif rg is not None:
-            self._chk(self._L.scvx_batch_track_mc_rng(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_rng")
-        elif mq.on:
-            self._chk(self._L.scvx_batch_track_mc_q(*args, *mq.args(self.B, self.K, S)), "scvx_batch_track_mc_q")
+            f.update(C0=c0, xi0=xi0, eta=eta, w14=wv, N0=n0, CN=cn, xin=xin, nud=nud, m=m, H=Hm, rm=rmv)
         else:
-            self._chk(self._L.scvx_batch_track_mc(*args), "scvx_batch_track_mc")
-        return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)._with_veh(vh)
+            c0, xi0, eta, sw = _mc_inputs(S0, self.B, self.K, samples, seed, w, draws, sample_lo, rg is not None)
+            f.update(C0=c0, xi0=xi0, eta=eta, sw14=sw, reserved=None)
+        return _mc_call(self._L, self.cache.handle, f, self.B, self.K, samples, rg, vh, mq, seed, sample_lo)
+
+    def _record(self, q, r, qf):
+        """the head of a record of a scvx_batch_ call of _calls.TABLE: the batch and the LQR weights (dynamics._track_weights)"""
+        from .dynamics import _track_weights
+        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
+        return dict(handle=self.handle, q14=qv, rNU=rv, qf14=qfv)
+
+    def _analysis(self, f, names):
+        """the shared end of the first-order analyses and their back-offs: allocate the outputs `names`, choose the entry point, call"""
+        f.update(_calls.analysis_outputs(self.B, self.K, self.cache.nu, names, f.get("m", 0)))
+        _calls.call(self._L, self.cache.handle, _calls.analysis_entry(f), f)
+        return f
 
     def _vehicle_sp(self, vehicle):
         """sp [6] of vehicle = (mu, sp) for the first-order analyses (dynamics._cov_vehicle's refusals; the tiles are the batch's own)"""
@@ -327,39 +304,22 @@ class ScvxBatch:
         vehicle errors as consider parameters (scvx_batch_cov_veh: the vehicle tiles of the iterate, then the analysis).
         clamp=True: the clamp-aware analysis by statistical linearisation (scvx_batch_cov_clamp; band and dense as
         dynamics.cov_propagate_batch with clamp=True): a dynamics.SatCovReport.  Not together with vehicle."""
-        from .dynamics import (CovReport, SatCovReport, _cov_band, _cov_clamp_outputs, _cov_dense, _cov_noise, _cov_s0,
-                               _track_weights)
+        from .dynamics import CovReport, SatCovReport, _cov_band, _cov_noise, _cov_s0
         if clamp and vehicle is not None:
             raise ValueError("clamp=True has no vehicle-error form: vehicle= must be None")
         if not clamp and band is not None:
             raise ValueError("band= needs clamp=True")
-        nu = self.cache.nu
-        n = 14 + nu
-        qv, rv, qfv = _track_weights(nu, q, r, qf)
-        s0 = _cov_s0(S0, self.B)
-        wv = _cov_noise(w)
+        f = self._record(q, r, qf)
+        f.update(S0=_cov_s0(S0, self.B), w14=_cov_noise(w))
         if clamp:
-            bd = _cov_band(band)
-            outs = _cov_clamp_outputs(self.B, self.K, n, dense)
-            ptr = lambda a: _p(a) if a is not None else None   # noqa: E731
-            self._chk(self._L.scvx_batch_cov_clamp(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), ptr(wv), ptr(bd),
-                                                   *[ptr(a) for a in outs]), "scvx_batch_cov_clamp")
-            rep, srep, mean, sig, covK, cov, satk = outs
-            return SatCovReport(rep, srep, mean, sig, covK, cov, satk)
-        want = _cov_dense(dense)
-        rep = np.empty((self.B, _lib.COV_NREP))
-        sig = np.empty((self.B, self.K + 1, n)) if "sig" in want else None
-        covK = np.empty((self.B, n, n)) if "covK" in want else None
-        cov = np.empty((self.B, self.K + 1, n, n)) if "cov" in want else None
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+            f["band2"] = _cov_band(band)
+            self._analysis(f, _calls.dense_names(dense, _calls.CLAMP_DENSE) | {"report", "satrep"})
+            return SatCovReport(f["report"], f["satrep"], f["mean"], f["sig"], f["covK"], f["cov"], f["satk"])
+        want = _calls.dense_names(dense, _calls.COV_DENSE)
         if vehicle is not None:
-            sp = self._vehicle_sp(vehicle)
-            self._chk(self._L.scvx_batch_cov_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), opt(wv), _p(rep), opt(sig), opt(covK),
-                                                 opt(cov), _p(sp)), "scvx_batch_cov_veh")
-            return CovReport(rep, sig, covK, cov)
-        self._chk(self._L.scvx_batch_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), opt(wv), _p(rep), opt(sig), opt(covK), opt(cov)),
-                  "scvx_batch_cov")
-        return CovReport(rep, sig, covK, cov)
+            f["sp6"] = self._vehicle_sp(vehicle)
+        self._analysis(f, want | {"report"})
+        return CovReport(f["report"], f["sig"], f["covK"], f["cov"])
 
     def set_thrust_margins(self, lo=None, hi=None):
         """Per-node back-offs of the thrust band for every conic solve that follows: Tmin + lo[b, k] <= |u_k| <= Tmax - hi[b, k]
@@ -421,27 +381,12 @@ class ScvxBatch:
         return mask
 
     def _margins_from_cov(self, S0, w, q, r, qf, nsigma, cap, want_psig, mask=None, vehicle=None):
-        from .dynamics import _cov_noise, _cov_s0, _track_weights
-        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
-        s0 = _cov_s0(S0, self.B)
-        wv = _cov_noise(w)
-        psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
-        if vehicle is not None:
-            sp = self._vehicle_sp(vehicle)
-            self._chk(self._L.scvx_batch_margins_from_cov_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0),
-                                                              _p(wv) if wv is not None else None, float(nsigma), float(cap),
-                                                              int(mask if mask is not None else _lib.MARGIN_BITS["thrust"]),
-                                                              _p(psig) if want_psig else None, _p(sp)), "scvx_batch_margins_from_cov_veh")
-            return psig
-        if mask is not None:
-            self._chk(self._L.scvx_batch_margins_from_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(wv) if wv is not None else None,
-                                                          float(nsigma), float(cap), int(mask), _p(psig) if want_psig else None),
-                      "scvx_batch_margins_from_cov")
-            return psig
-        self._chk(self._L.scvx_batch_thrust_margins_from_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(wv) if wv is not None else None,
-                                                             float(nsigma), float(cap), _p(psig) if want_psig else None),
-                  "scvx_batch_thrust_margins_from_cov")
-        return psig
+        from .dynamics import _cov_noise, _cov_s0
+        f = self._record(q, r, qf)
+        f.update(S0=_cov_s0(S0, self.B), w14=_cov_noise(w), nsigma=nsigma, cap=cap, which=mask)
+        if vehicle is not None:   # the _veh form has no thrust-only twin: the thrust bit says the same
+            f.update(sp6=self._vehicle_sp(vehicle), which=mask if mask is not None else _lib.MARGIN_BITS["thrust"])
+        return self._analysis(f, {"psig"} if want_psig else ())["psig"]
 
     def margins_from_cov(self, S0, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None, vehicle=None):
         """The back-offs min(nsigma s(k), cap width_k) of `constraints` from the covariance analysis of the current accepted iterate
@@ -450,22 +395,13 @@ class ScvxBatch:
         return self._margins_from_cov(S0, w, q, r, qf, nsigma, cap, True, self._margin_mask(constraints), vehicle)
 
     def _margins_from_nav(self, S0, nav, w, q, r, qf, nsigma, cap, want_psig, mask, vehicle=None):
-        from .dynamics import _cov_noise, _cov_s0, _nav_arg, _track_weights
+        from .dynamics import _cov_noise, _cov_s0, _nav_arg
         n0, m, Hm, rmv = _nav_arg(nav, self.B)
-        qv, rv, qfv = _track_weights(self.cache.nu, q, r, qf)
-        s0 = _cov_s0(S0, self.B)
-        wv = _cov_noise(w)
-        psig = np.empty((self.B, self.K + 1, _lib.PSIG_N)) if want_psig else None
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        f = self._record(q, r, qf)
+        f.update(S0=_cov_s0(S0, self.B), N0=n0, m=m, H=Hm, rm=rmv, w14=_cov_noise(w), nsigma=nsigma, cap=cap, which=mask)
         if vehicle is not None:
-            sp = self._vehicle_sp(vehicle)
-            self._chk(self._L.scvx_batch_margins_from_nav_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv),
-                                                              opt(wv), float(nsigma), float(cap), int(mask), opt(psig), _p(sp)),
-                      "scvx_batch_margins_from_nav_veh")
-            return psig
-        self._chk(self._L.scvx_batch_margins_from_nav(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv),
-                                                      float(nsigma), float(cap), int(mask), opt(psig)), "scvx_batch_margins_from_nav")
-        return psig
+            f["sp6"] = self._vehicle_sp(vehicle)
+        return self._analysis(f, {"psig"} if want_psig else ())["psig"]
 
     def margins_from_nav(self, S0, N0, H, rm, constraints="all", nsigma=3.0, cap=0.25, w=None, q=None, r=None, qf=None, vehicle=None):
         """margins_from_cov with the per-node s(k) of the NAVIGATION analysis of the current accepted iterate, the closed loop flown on
@@ -585,31 +521,18 @@ class ScvxBatch:
         (scvx_batch_nav_cov; S0, N0, H, rm, w and dense as dynamics.nav_cov_batch, weights as track_gains): a dynamics.NavReport.
         The batch is left untouched.  vehicle = (mu, sp), mu = 0: J_k diag(sp^2) J_k' on the truth block (scvx_batch_nav_cov_veh); the
         filter does not know theta, so navsig, kf and NAV_* are those of the call without it."""
-        from .dynamics import NavReport, _cov_noise, _cov_s0, _nav_dense, _nav_model, _track_weights
+        from .dynamics import NavReport, _cov_noise, _cov_s0, _nav_model
         if clamp:
             raise ValueError("clamp=True: the clamp-aware analysis has no navigation form (covariance(clamp=True) feeds the law the truth)")
-        nu = self.cache.nu
-        n = 14 + nu
-        qv, rv, qfv = _track_weights(nu, q, r, qf)
-        s0, n0 = _cov_s0(S0, self.B), _cov_s0(N0, self.B)
-        m, Hm, rmv = _nav_model(H, rm)
-        wv = _cov_noise(w)
-        want = _nav_dense(dense)
-        rep, navrep = np.empty((self.B, _lib.COV_NREP)), np.empty((self.B, _lib.NAV_NREP))
-        sig = np.empty((self.B, self.K + 1, n)) if "sig" in want else None
-        navsig = np.empty((self.B, self.K + 1, 14)) if "navsig" in want else None
-        kf = np.empty((self.B, self.K, 14, m)) if "kf" in want else None
-        joint = np.empty((self.B, self.K + 1, n + 14, n + 14)) if "joint" in want else None
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
+        f = self._record(q, r, qf)
+        f.update(S0=_cov_s0(S0, self.B), N0=_cov_s0(N0, self.B))
+        f["m"], f["H"], f["rm"] = _nav_model(H, rm)
+        f["w14"] = _cov_noise(w)
+        want = _calls.dense_names(dense, _calls.NAV_DENSE)
         if vehicle is not None:
-            sp = self._vehicle_sp(vehicle)
-            self._chk(self._L.scvx_batch_nav_cov_veh(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv),
-                                                     _p(rep), _p(navrep), opt(sig), opt(navsig), opt(kf), opt(joint), _p(sp)),
-                      "scvx_batch_nav_cov_veh")
-            return NavReport(rep, navrep, sig, navsig, kf, joint)
-        self._chk(self._L.scvx_batch_nav_cov(self.handle, _p(qv), _p(rv), _p(qfv), _p(s0), _p(n0), m, opt(Hm), opt(rmv), opt(wv), _p(rep),
-                                             _p(navrep), opt(sig), opt(navsig), opt(kf), opt(joint)), "scvx_batch_nav_cov")
-        return NavReport(rep, navrep, sig, navsig, kf, joint)
+            f["sp6"] = self._vehicle_sp(vehicle)
+        self._analysis(f, want | {"report", "navrep"})
+        return NavReport(f["report"], f["navrep"], f["sig"], f["navsig"], f["kf"], f["joint"])
 
     def set_profiling(self, on: bool):
         self._chk(self._L.scvx_batch_set_profiling(self.handle, 1 if on else 0), "scvx_batch_set_profiling")

@@ -11,7 +11,7 @@ plus the batched forms the GPU path exists for.  Everything computes in libscvx_
 import ctypes as C
 import numpy as np
 
-from . import _lib
+from . import _calls, _lib
 from .defns import AtmosphericData, DescentProblem, LinPoint, LinRes, ProbInfo
 
 _dp = C.POINTER(C.c_double)
@@ -266,11 +266,7 @@ def _cov_vehicle(cache, vehicle, vtile, dense, B, K):
     """vehicle= of the first-order analyses: None, or (mu [6], sp [6]) as montecarlo.vehicle_errors returns them; vtile: what
     vehicle_tiles_batch returns, needed when sp[ISP] or sp[AERO] is not 0; dense: the call's, "sens" among its names asks for J_k
     -> (sp or None, vtile or None, sens [B][K+1][n][6] or None, dense without "sens").  Every refusal of the library is a ValueError here."""
-    rest, want = dense, False
-    if not (dense is True or not dense):
-        names = {dense} if isinstance(dense, str) else set(dense)
-        want = "sens" in names
-        rest = tuple(n for n in names if n != "sens")
+    want, rest = _calls.split_dense(dense, ("sens",))
     if vehicle is None:
         if want or vtile is not None:
             raise ValueError('dense "sens" and vtile= need vehicle=')
@@ -355,27 +351,6 @@ def _cov_band(band):
     return a
 
 
-def _cov_clamp_dense(dense):
-    """dense of the clamp-aware analysis: False / True (all five) / names out of "mean", "sig", "covK", "cov", "satk" -> the set"""
-    names = {"mean", "sig", "covK", "cov", "satk"}
-    if dense is True:
-        return names
-    if not dense:
-        return set()
-    want = {dense} if isinstance(dense, str) else set(dense)
-    if not want <= names:
-        raise ValueError("dense: True, False or names out of 'mean', 'sig', 'covK', 'cov', 'satk', not %r" % (dense,))
-    return want
-
-
-def _cov_clamp_outputs(B, K, n, dense):
-    """(report, satrep, mean, sig, covK, cov, satk): the outputs of a _clamp call in the order of its argument list, None = not wanted"""
-    want = _cov_clamp_dense(dense)
-    return (np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.SAT_NREP)), np.empty((B, K + 1, n)) if "mean" in want else None,
-            np.empty((B, K + 1, n)) if "sig" in want else None, np.empty((B, n, n)) if "covK" in want else None,
-            np.empty((B, K + 1, n, n)) if "cov" in want else None, np.empty((B, K, 4)) if "satk" in want else None)
-
-
 def _cov_s0(S0, B):
     """S0 as [B][14][14], one [14][14] for all, or a [14] vector of standard deviations (S0 = diag(sd^2)) -> contiguous [B][14][14]"""
     a = np.asarray(S0, np.float64)
@@ -398,16 +373,10 @@ def _cov_noise(w):
     return np.ascontiguousarray(np.broadcast_to(a, (14,)), np.float64)
 
 
-def _cov_dense(dense):
-    """dense: False / True (all three) / an iterable of names out of "sig", "covK", "cov" -> the set of wanted outputs"""
-    if dense is True:
-        return {"sig", "covK", "cov"}
-    if not dense:
-        return set()
-    want = {dense} if isinstance(dense, str) else set(dense)
-    if not want <= {"sig", "covK", "cov"}:
-        raise ValueError("dense: True, False or names out of 'sig', 'covK', 'cov', not %r" % (dense,))
-    return want
+def _analysis(cache, f, names):
+    """the shared end of the four first-order analyses: allocate the outputs `names`, choose the entry point from the record f, call"""
+    f.update(_calls.analysis_outputs(f["B"], f["K"], cache.nu, names, f.get("m", 0)), handle=cache.handle)
+    _calls.call(cache._L, cache.handle, _calls.analysis_entry(f), f)
 
 
 def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, dense=False, vehicle=None, vtile=None, clamp=False,
@@ -428,45 +397,15 @@ def cov_propagate_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, d
         raise ValueError("clamp=True has no vehicle-error form: vehicle= and vtile= must be None")
     if not clamp and band is not None:
         raise ValueError("band= needs clamp=True")
-    x = np.ascontiguousarray(x, np.float64)
-    u = np.ascontiguousarray(u, np.float64)
-    gain = np.ascontiguousarray(gain, np.float64)
-    deriv = np.ascontiguousarray(deriv, np.float64)
-    nu = cache.nu
-    n = 14 + nu
-    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
-        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
-    B, K1, _ = x.shape
-    K = K1 - 1
-    if gain.shape != (B, K, nu, n):
-        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
-    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
-        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
-    s0 = _cov_s0(S0, B)
-    wv = _cov_noise(w)
+    f = _calls.plan_shapes(cache.nu, x, u, gain, deriv)
+    f.update(S0=_cov_s0(S0, f["B"]), w14=_cov_noise(w))
     if clamp:
-        bd = _cov_band(band)
-        outs = _cov_clamp_outputs(B, K, n, dense)
-        ptr = lambda a: _p(a) if a is not None else None   # noqa: E731
-        _lib.check(cache.handle, cache._L.scvx_cov_clamp_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), ptr(wv),
-                                                                  ptr(bd), *[ptr(a) for a in outs]), "scvx_cov_clamp_f64_host")
-        rep, srep, mean, sig, covK, cov, satk = outs
-        return SatCovReport(rep, srep, mean, sig, covK, cov, satk)
-    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
-    want = _cov_dense(dense)
-    rep = np.empty((B, _lib.COV_NREP))
-    sig = np.empty((B, K1, n)) if "sig" in want else None
-    covK = np.empty((B, n, n)) if "covK" in want else None
-    cov = np.empty((B, K1, n, n)) if "cov" in want else None
-    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    if sp is not None:
-        _lib.check(cache.handle, cache._L.scvx_cov_vehicle_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
-                                                                    _p(rep), None, opt(sig), opt(covK), opt(cov), opt(vt), _p(sp),
-                                                                    opt(sens)), "scvx_cov_vehicle_f64_host")
-        return CovReport(rep, sig, covK, cov, sens)
-    _lib.check(cache.handle, cache._L.scvx_cov_propagate_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
-                                                                  _p(rep), opt(sig), opt(covK), opt(cov)), "scvx_cov_propagate_f64_host")
-    return CovReport(rep, sig, covK, cov)
+        f["band2"] = _cov_band(band)
+        _analysis(cache, f, _calls.dense_names(dense, _calls.CLAMP_DENSE) | {"report", "satrep"})
+        return SatCovReport(f["report"], f["satrep"], f["mean"], f["sig"], f["covK"], f["cov"], f["satk"])
+    f["sp6"], f["vtile"], f["sens"], dense = _cov_vehicle(cache, vehicle, vtile, dense, f["B"], f["K"])
+    _analysis(cache, f, _calls.dense_names(dense, _calls.COV_DENSE) | {"report"})
+    return CovReport(f["report"], f["sig"], f["covK"], f["cov"], f["sens"])
 
 
 def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, vehicle=None, vtile=None, dense=()):
@@ -475,37 +414,13 @@ def cov_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, w=None, 
     thrust norm (_lib.PSIG_COLUMNS).  Node 0 and a node its margin skips are 0; a non-finite tile, gain or S0 entry makes the rows of
     its own trajectory NaN.  psig[:, :, 4] is the s_T(k) that ScvxBatch.robustify turns into back-offs of the thrust band.
     vehicle, vtile: as cov_propagate_batch (psig and the report are then read off Sigma_k^tot); dense: () or ("sens",)."""
-    x = np.ascontiguousarray(x, np.float64)
-    u = np.ascontiguousarray(u, np.float64)
-    gain = np.ascontiguousarray(gain, np.float64)
-    deriv = np.ascontiguousarray(deriv, np.float64)
-    nu = cache.nu
-    n = 14 + nu
-    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
-        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
-    B, K1, _ = x.shape
-    K = K1 - 1
-    if gain.shape != (B, K, nu, n):
-        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
-    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
-        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
-    s0 = _cov_s0(S0, B)
-    wv = _cov_noise(w)
-    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
+    f = _calls.plan_shapes(cache.nu, x, u, gain, deriv)
+    f.update(S0=_cov_s0(S0, f["B"]), w14=_cov_noise(w))
+    f["sp6"], f["vtile"], f["sens"], dense = _cov_vehicle(cache, vehicle, vtile, dense, f["B"], f["K"])
     if dense:
         raise ValueError('dense: () or ("sens",), not %r' % (dense,))
-    rep = np.empty((B, _lib.COV_NREP))
-    psig = np.empty((B, K1, _lib.PSIG_N))
-    if sp is not None:
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-        _lib.check(cache.handle, cache._L.scvx_cov_vehicle_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), opt(wv),
-                                                                    _p(rep), _p(psig), None, None, None, opt(vt), _p(sp), opt(sens)),
-                   "scvx_cov_vehicle_f64_host")
-        return CovReport(rep, sens=sens), psig
-    _lib.check(cache.handle, cache._L.scvx_cov_path_sigma_f64_host(cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0),
-                                                                   _p(wv) if wv is not None else None, _p(rep), _p(psig)),
-               "scvx_cov_path_sigma_f64_host")
-    return CovReport(rep), psig
+    _analysis(cache, f, {"report", "psig"})
+    return CovReport(f["report"], sens=f["sens"]), f["psig"]
 
 
 class McReport:
@@ -564,52 +479,35 @@ class McReport:
         return FlightReport(self.flights[b], None, "track")
 
 
-def _mc_dense(dense):
-    """dense: False / () / True (all three) / an iterable of names out of "flights", "xland", "dx0" -> the set of wanted outputs"""
-    if dense is True:
-        return {"flights", "xland", "dx0"}
-    if not dense:
-        return set()
-    want = {dense} if isinstance(dense, str) else set(dense)
-    if not want <= {"flights", "xland", "dx0"}:
-        raise ValueError("dense: True, False or names out of 'flights', 'xland', 'dx0', not %r" % (dense,))
-    return want
-
-
 class _McQ:
     """What the _q forms of the sampled calls add: quantiles (an iterable of probabilities, or None), per_node, and "pathv" among the
     dense names -> the five trailing C arguments (nq, ranks, flightq, pathq, pathv) and their host arrays.  `on` False: the call is
     the old entry point, with exactly its arguments.  dense=True stays "all the dense outputs the call had": pathv is by name only."""
 
     def __init__(self, quantiles, per_node, dense):
-        self.rest = dense
-        want_pv = False
-        if not (dense is True or not dense):
-            names = {dense} if isinstance(dense, str) else set(dense)
-            want_pv = "pathv" in names
-            self.rest = tuple(n for n in names if n != "pathv")
+        want_pv, self.rest = _calls.split_dense(dense, ("pathv",))
         self.pq = None if quantiles is None else np.atleast_1d(np.asarray(list(np.atleast_1d(quantiles)), np.float64))
         if self.pq is not None and not 1 <= self.pq.size <= 16:
             raise ValueError("quantiles: between 1 and 16 probabilities")
         if per_node and self.pq is None:
             raise ValueError("per_node=True needs quantiles=")
-        self.per_node, self.want_pv = bool(per_node), want_pv
-        self.on = self.pq is not None or want_pv
+        self.per_node, self.want_pv = bool(per_node), bool(want_pv)
+        self.on = self.pq is not None or self.want_pv
         self.probs = self.ranks = self.flightq = self.pathq = self.pathv = None
 
-    def args(self, B, K, S):
+    def fields(self, B, K, S):
+        """the five trailing fields of a call with `S` samples, allocated here"""
         from .montecarlo import quantile_ranks
-        nq = 0
+        names = set()
         if self.pq is not None:
             self.probs, self.ranks = self.pq, np.ascontiguousarray(quantile_ranks(self.pq, S), np.int32)
-            nq = int(self.ranks.size)
-            self.flightq = np.empty((B, _lib.FLIGHT_NREP, nq))
-            if self.per_node:
-                self.pathq = np.empty((B, K + 1, _lib.PSIG_N, nq))
+            names = {"flightq", "pathq"} if self.per_node else {"flightq"}
         if self.want_pv:
-            self.pathv = np.empty((B, K + 1, _lib.PSIG_N, S))
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-        return (nq, self.ranks.ctypes.data_as(C.POINTER(C.c_int)) if nq else None, opt(self.flightq), opt(self.pathq), opt(self.pathv))
+            names.add("pathv")
+        nq = 0 if self.ranks is None else int(self.ranks.size)
+        out = _calls.mc_outputs(B, K, S, names, nq)
+        self.flightq, self.pathq, self.pathv = out["flightq"], out["pathq"], out["pathv"]
+        return dict(nq=nq, ranks=self.ranks, flightq=self.flightq, pathq=self.pathq, pathv=self.pathv)
 
 
 class _McVeh:
@@ -618,16 +516,11 @@ class _McVeh:
     zeta, theta).  `on` False: the call is the one it was, with exactly its arguments."""
 
     def __init__(self, vehicle, dense):
-        self.rest = dense
-        want = False
-        if not (dense is True or not dense):
-            names = {dense} if isinstance(dense, str) else set(dense)
-            want = "theta" in names
-            self.rest = tuple(n for n in names if n != "theta")
+        want, self.rest = _calls.split_dense(dense, ("theta",))
         self.on = vehicle is not None
         if want and not self.on:
             raise ValueError('dense "theta" needs vehicle=')
-        self.want, self.theta, self.zeta, self.veh = want, None, None, None
+        self.want, self.theta, self.zeta, self.veh = bool(want), None, None, None
         if self.on:
             if len(vehicle) not in (2, 3):
                 raise ValueError("vehicle = (mu [6], sp [6]) or (mu, sp, zeta [S][6]): montecarlo.vehicle_errors")
@@ -638,9 +531,11 @@ class _McVeh:
             self.sp = sp
             self.zeta = None if len(vehicle) == 2 or vehicle[2] is None else np.ascontiguousarray(vehicle[2], np.float64)
 
-    def args(self, B, S, rg, noise, seed, lo):
-        """(rng, noise, veh, zeta, theta) of a call with `S` samples; rg: the scvx_mc_rng of rng="device" or None"""
+    def fields(self, B, S, rg, seed, lo):
+        """the fields veh, zeta and theta of a call with `S` samples; rg: the scvx_mc_rng of rng="device" or None"""
         from .montecarlo import mc_vehicle_draws
+        if not self.on:
+            return dict(veh=None, zeta=None, theta=None)
         if rg is not None:
             if self.zeta is not None:
                 raise ValueError('vehicle: zeta cannot be combined with rng="device": the device makes its own '
@@ -651,9 +546,7 @@ class _McVeh:
             raise ValueError("shape mismatch: zeta [S][6]")
         if self.want:
             self.theta = np.empty((B, S, 6))
-        opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-        return (C.byref(rg) if rg is not None else None, (1 if noise else 0) if rg is not None else 0, C.byref(self.veh),
-                opt(self.zeta), opt(self.theta))
+        return dict(veh=self.veh, zeta=self.zeta, theta=self.theta)
 
 
 def _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo):
@@ -714,11 +607,25 @@ def _mc_inputs(S0, B, K, samples, seed, w, draws, lo=0, device=False):
     return c0, xi0, eta, sw
 
 
-def _mc_outputs(B, S, dense):
-    want = _mc_dense(dense)
-    return (np.empty((B, _lib.MC_NREP)), np.empty((B, 14)), np.empty((B, 14, 14)),
-            np.empty((B, S, _lib.FLIGHT_NREP)) if "flights" in want else None, np.empty((B, S, 14)) if "xland" in want else None,
-            np.empty((B, S, 14)) if "dx0" in want else None)
+def _mc_keywords(rng, draws, independent, seed, sample_lo, plan_lo, vehicle, dense, quantiles, per_node):
+    """the keywords every sampled call starts with -> (the scvx_mc_rng or None, the _McVeh, the _McQ); mq.rest is what is left of dense"""
+    rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
+    vh = _McVeh(vehicle, dense)
+    return rg, vh, _McQ(quantiles, per_node, vh.rest)
+
+
+def _mc_call(L, err_handle, f, B, K, samples, rg, vh, mq, seed, lo):
+    """the shared end of the four sampled callers: the record f holds the head and the inputs; allocate the outputs, add the _q and _veh
+    tails, choose the entry point from the record, call, build the report (a McNavReport where the record has CN)"""
+    nav = "CN" in f
+    S = int(samples) if rg is not None else f["xi0"].shape[0]
+    reduced, dense = (_calls.MC_NAV_REDUCED, _calls.MC_NAV_DENSE) if nav else (_calls.MC_REDUCED, _calls.MC_DENSE)
+    f.update(_calls.mc_outputs(B, K, S, _calls.dense_names(mq.rest, dense) | set(reduced)))
+    f.update(mq.fields(B, K, S))
+    f.update(vh.fields(B, S, rg, seed, lo), S=S, rng=rg, noise=1 if rg is not None and f["w14" if nav else "sw14"] is not None else 0)
+    _calls.call(L, err_handle, _calls.mc_entry(f), f)
+    rep = (McNavReport if nav else McReport)(*[f[k] for k in reduced + dense])
+    return rep._with_q(mq)._with_veh(vh)
 
 
 def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=0, w=None, nsub=10, clamp=False, tol=0.0, dense=(),
@@ -751,44 +658,19 @@ def track_mc_batch(cache: IntegratorCache, x, u, sigma, gain, S0, samples, seed=
     montecarlo.mc_vehicle_draws of `seed` with rng="host" (or the third entry of vehicle), the device's stream 8 with "device"
     (montecarlo.mc_vehicle_draws_device is its twin); dense may name "theta" for the errors flown, `theta` [B][S][6].  None (the
     default): exactly the C calls made without it."""
-    rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
     if nav is not None:
+        _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)   # refused before the plan is linearised
         n0, _, Hm, rv = _nav_arg(nav, np.shape(x)[0])
         _, deriv = linearize_batch(cache, x, u, sigma, 1.0 / np.shape(x)[1])
         return track_mc_nav_batch(cache, x, u, sigma, deriv, gain, S0, n0, Hm, rv, samples, seed=seed, w=w, nsub=nsub, clamp=clamp,
                                   tol=tol, dense=dense, draws=draws, quantiles=quantiles, per_node=per_node, rng=rng,
                                   independent=independent, sample_lo=sample_lo, plan_lo=plan_lo, vehicle=vehicle)
-    vh = _McVeh(vehicle, dense)
-    mq = _McQ(quantiles, per_node, vh.rest)
-    dense = mq.rest
-    x = np.ascontiguousarray(x, np.float64)
-    u = np.ascontiguousarray(u, np.float64)
-    sigma = np.ascontiguousarray(sigma, np.float64)
-    gain = np.ascontiguousarray(gain, np.float64)
-    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], cache.nu) or sigma.shape != (x.shape[0],):
-        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % cache.nu)
-    B, K1, _ = x.shape
-    if gain.shape != (B, K1 - 1, cache.nu, 14 + cache.nu):
-        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (cache.nu, 14 + cache.nu))
-    c0, xi0, eta, sw = _mc_inputs(S0, B, K1 - 1, samples, seed, w, draws, sample_lo, rg is not None)
-    S = int(samples) if rg is not None else xi0.shape[0]
-    rep, xmean, xcov, flights, xland, dx0 = _mc_outputs(B, S, dense)
-    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    drw = (C.byref(rg), 1 if sw is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
-    args = (cache.handle, B, K1 - 1, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), *drw, opt(sw), None,
-            int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), _p(rep), _p(xmean), _p(xcov),
-            opt(flights), opt(xland), opt(dx0))
-    if vh.on:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_veh_f64_host(*args, *mq.args(B, K1 - 1, S),
-                                                                     *vh.args(B, S, rg, sw is not None, seed, sample_lo)),
-                   "scvx_track_mc_veh_f64_host")
-    elif rg is not None:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_rng_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_rng_f64_host")
-    elif mq.on:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_q_f64_host(*args, *mq.args(B, K1 - 1, S)), "scvx_track_mc_q_f64_host")
-    else:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_f64_host(*args), "scvx_track_mc_f64_host")
-    return McReport(rep, xmean, xcov, flights, xland, dx0)._with_q(mq)._with_veh(vh)
+    rg, vh, mq = _mc_keywords(rng, draws, independent, seed, sample_lo, plan_lo, vehicle, dense, quantiles, per_node)
+    f = _calls.plan_shapes(cache.nu, x, u, gain, sigma=sigma)
+    c0, xi0, eta, sw = _mc_inputs(S0, f["B"], f["K"], samples, seed, w, draws, sample_lo, rg is not None)
+    f.update(handle=cache.handle, C0=c0, xi0=xi0, eta=eta, sw14=sw, reserved=None, nsub=cache.npts if nsub is None else nsub,
+             flags=_lib.TRACK_CLAMP if clamp else 0, tol=tol)
+    return _mc_call(cache._L, cache.handle, f, f["B"], f["K"], samples, rg, vh, mq, seed, sample_lo)
 
 
 def vehicle_sensitivity_batch(cache: IntegratorCache, x, u, sigma, gain, h=2.0 ** -10, nsub=10, clamp=False):
@@ -846,17 +728,13 @@ def _nav_model(H, rm):
     return m, Hm, np.ascontiguousarray(np.broadcast_to(r, (m,)), np.float64)
 
 
-def _nav_dense(dense):
-    """dense: False / True (all four) / an iterable of names out of "sig", "navsig", "kf", "joint" -> the set of wanted outputs"""
-    names = {"sig", "navsig", "kf", "joint"}
-    if dense is True:
-        return names
-    if not dense:
-        return set()
-    want = {dense} if isinstance(dense, str) else set(dense)
-    if not want <= names:
-        raise ValueError("dense: True, False or names out of 'sig', 'navsig', 'kf', 'joint', not %r" % (dense,))
-    return want
+def _nav_record(cache, x, u, deriv, gain, S0, N0, H, rm, w):
+    """the checked plan and the inputs of the two navigation analyses as a record"""
+    f = _calls.plan_shapes(cache.nu, x, u, gain, deriv)
+    f.update(S0=_cov_s0(S0, f["B"]), N0=_cov_s0(N0, f["B"]))
+    f["m"], f["H"], f["rm"] = _nav_model(H, rm)
+    f["w14"] = _cov_noise(w)
+    return f
 
 
 def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None, dense=False, vehicle=None, vtile=None) -> NavReport:
@@ -869,40 +747,10 @@ def nav_cov_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=No
     vehicle, vtile: as cov_propagate_batch (scvx_nav_cov_vehicle_f64_host): J_k diag(sp^2) J_k' is added to the truth block wherever
     the report, sig and joint read it; the eps blocks, navsig, kf and NAV_* are untouched -- the filter does not know theta -- and
     EST_R / EST_V receive it in their truth term.  dense may then name "sens"."""
-    x = np.ascontiguousarray(x, np.float64)
-    u = np.ascontiguousarray(u, np.float64)
-    gain = np.ascontiguousarray(gain, np.float64)
-    deriv = np.ascontiguousarray(deriv, np.float64)
-    nu = cache.nu
-    n = 14 + nu
-    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
-        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
-    B, K1, _ = x.shape
-    K = K1 - 1
-    if gain.shape != (B, K, nu, n):
-        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
-    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
-        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
-    s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
-    m, Hm, rv = _nav_model(H, rm)
-    wv = _cov_noise(w)
-    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
-    want = _nav_dense(dense)
-    rep, navrep = np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.NAV_NREP))
-    sig = np.empty((B, K1, n)) if "sig" in want else None
-    navsig = np.empty((B, K1, 14)) if "navsig" in want else None
-    kf = np.empty((B, K, 14, m)) if "kf" in want else None
-    joint = np.empty((B, K1, n + 14, n + 14)) if "joint" in want else None
-    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    if sp is not None:
-        _lib.check(cache.handle, cache._L.scvx_nav_cov_vehicle_f64_host(
-            cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), None,
-            opt(sig), opt(navsig), opt(kf), opt(joint), opt(vt), _p(sp), opt(sens)), "scvx_nav_cov_vehicle_f64_host")
-        return NavReport(rep, navrep, sig, navsig, kf, joint, sens)
-    _lib.check(cache.handle, cache._L.scvx_nav_cov_f64_host(
-        cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), opt(sig),
-        opt(navsig), opt(kf), opt(joint)), "scvx_nav_cov_f64_host")
-    return NavReport(rep, navrep, sig, navsig, kf, joint)
+    f = _nav_record(cache, x, u, deriv, gain, S0, N0, H, rm, w)
+    f["sp6"], f["vtile"], f["sens"], dense = _cov_vehicle(cache, vehicle, vtile, dense, f["B"], f["K"])
+    _analysis(cache, f, _calls.dense_names(dense, _calls.NAV_DENSE) | {"report", "navrep"})
+    return NavReport(f["report"], f["navrep"], f["sig"], f["navsig"], f["kf"], f["joint"], f["sens"])
 
 
 def _nav_arg(nav, B):
@@ -940,21 +788,6 @@ class McNavReport(McReport):
             setattr(self, name, self.navraw[:, i])
 
 
-_MCNAV_DENSE = ("flights", "xland", "dx0", "navfed", "navK")
-
-
-def _mc_nav_dense(dense):
-    """dense: False / () / True (all five) / an iterable of names out of _MCNAV_DENSE -> the set of wanted outputs"""
-    if dense is True:
-        return set(_MCNAV_DENSE)
-    if not dense:
-        return set()
-    want = {dense} if isinstance(dense, str) else set(dense)
-    if not want <= set(_MCNAV_DENSE):
-        raise ValueError("dense: True, False or names out of %s, not %r" % (", ".join(repr(n) for n in _MCNAV_DENSE), dense))
-    return want
-
-
 def _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws, lo=0, device=False):
     """(C0, CN [B][14][14], xi0, eta or None, xin, nud or None, w [14] or None) of a sampled dispersion flown on an estimate: the factors
     of every plan's two handover covariances (montecarlo.handover_factor), the draws of montecarlo.mc_draws and mc_nav_draws -- or
@@ -985,13 +818,6 @@ def _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws, lo=0, device=False)
     return c0, cn, n0, xi0, eta, xin, (nud if m else None), wv
 
 
-def _mc_nav_outputs(B, S, K, dense):
-    want = _mc_nav_dense(dense)
-    shapes = {"flights": (B, S, _lib.FLIGHT_NREP), "xland": (B, S, 14), "dx0": (B, S, 14), "navfed": (B, S, K, 14), "navK": (B, S, 14)}
-    return ((np.empty((B, _lib.MC_NREP)), np.empty((B, 14)), np.empty((B, 14, 14)), np.empty((B, 28)), np.empty((B, 28, 28)),
-             np.empty((B, _lib.NAV_NREP))), tuple(np.empty(shapes[n]) if n in want else None for n in _MCNAV_DENSE))
-
-
 def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0, H, rm, samples, seed=0, w=None, kf=None, nsub=10,
                        clamp=False, tol=0.0, dense=(), draws=None, quantiles=None, per_node=False, rng="host", independent=False,
                        sample_lo=0, plan_lo=0, vehicle=None) -> McNavReport:
@@ -1006,51 +832,20 @@ def track_mc_nav_batch(cache: IntegratorCache, x, u, sigma, deriv, gain, S0, N0,
     and plan_lo as track_mc_batch (scvx_track_mc_nav_rng_f64_host): with "device" the lanes make all four draws.  vehicle and the
     dense name "theta" as track_mc_batch (scvx_track_mc_nav_veh_f64_host): the truth is flown with the vehicle errors, the recursion
     of the estimate's error is the analysis's, unchanged."""
-    rg = _mc_rng(rng, draws, independent, seed, sample_lo, plan_lo)
-    vh = _McVeh(vehicle, dense)
-    mq = _McQ(quantiles, per_node, vh.rest)
-    dense = mq.rest
-    x = np.ascontiguousarray(x, np.float64)
-    u = np.ascontiguousarray(u, np.float64)
-    sigma = np.ascontiguousarray(sigma, np.float64)
-    gain = np.ascontiguousarray(gain, np.float64)
-    deriv = np.ascontiguousarray(deriv, np.float64)
-    nu = cache.nu
-    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu) or sigma.shape != (x.shape[0],):
-        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % nu)
-    B, K1, _ = x.shape
-    K = K1 - 1
-    if gain.shape != (B, K, nu, 14 + nu):
-        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, 14 + nu))
-    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
-        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
+    rg, vh, mq = _mc_keywords(rng, draws, independent, seed, sample_lo, plan_lo, vehicle, dense, quantiles, per_node)
+    f = _calls.plan_shapes(cache.nu, x, u, gain, deriv, sigma)
+    B, K = f["B"], f["K"]
     m, Hm, rv = _nav_model(H, rm)
     c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(S0, N0, B, K, m, samples, seed, w, draws, sample_lo, rg is not None)
     if m and kf is None:
-        kf = nav_cov_batch(cache, x, u, deriv, gain, np.zeros((B, 14, 14)), n0, Hm, rv, wv, dense=("kf",)).kf
+        kf = nav_cov_batch(cache, f["x"], f["u"], f["deriv"], f["gain"], np.zeros((B, 14, 14)), n0, Hm, rv, wv, dense=("kf",)).kf
     if m:
         kf = np.ascontiguousarray(kf, np.float64)
         if kf.shape != (B, K, 14, m):
             raise ValueError("shape mismatch: kf [B][K][14][%d]" % m)
-    S = int(samples) if rg is not None else xi0.shape[0]
-    red, dn = _mc_nav_outputs(B, S, K, dense)
-    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    drw = (C.byref(rg), 1 if wv is not None else 0) if rg is not None and not vh.on else (opt(xi0), opt(eta))
-    args = (cache.handle, B, K, S, _p(x), _p(u), _p(sigma), _p(gain), _p(c0), *drw, opt(wv), _p(deriv),
-            opt(kf if m else None), _p(cn), *(() if rg is not None and not vh.on else (opt(xin), opt(nud))), m, opt(Hm), opt(rv),
-            int(cache.npts if nsub is None else nsub), _lib.TRACK_CLAMP if clamp else 0, float(tol), *[_p(a) for a in red],
-            *[opt(a) for a in dn])
-    if vh.on:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_veh_f64_host(*args, *mq.args(B, K, S),
-                                                                         *vh.args(B, S, rg, wv is not None, seed, sample_lo)),
-                   "scvx_track_mc_nav_veh_f64_host")
-    elif rg is not None:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_rng_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_rng_f64_host")
-    elif mq.on:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_q_f64_host(*args, *mq.args(B, K, S)), "scvx_track_mc_nav_q_f64_host")
-    else:
-        _lib.check(cache.handle, cache._L.scvx_track_mc_nav_f64_host(*args), "scvx_track_mc_nav_f64_host")
-    return McNavReport(*red, *dn)._with_q(mq)._with_veh(vh)
+    f.update(handle=cache.handle, C0=c0, xi0=xi0, eta=eta, w14=wv, kf=kf if m else None, CN=cn, xin=xin, nud=nud, m=m, H=Hm, rm=rv,
+             nsub=cache.npts if nsub is None else nsub, flags=_lib.TRACK_CLAMP if clamp else 0, tol=tol)
+    return _mc_call(cache._L, cache.handle, f, B, K, samples, rg, vh, mq, seed, sample_lo)
 
 
 def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, rm, w=None, vehicle=None, vtile=None, dense=()):
@@ -1059,38 +854,12 @@ def nav_path_sigma_batch(cache: IntegratorCache, x, u, deriv, gain, S0, N0, H, r
     constraints bind the vehicle, not its estimate.  Node 0 and a node its margin skips are 0; a non-finite tile, gain, S0 or N0 entry
     makes the rows of its own trajectory NaN.  With N0 = 0 this is cov_path_sigma_batch's psig to rounding.
     vehicle, vtile: as nav_cov_batch (psig and the report are then read off the truth block + J_k diag(sp^2) J_k'); dense: () or ("sens",)."""
-    x = np.ascontiguousarray(x, np.float64)
-    u = np.ascontiguousarray(u, np.float64)
-    gain = np.ascontiguousarray(gain, np.float64)
-    deriv = np.ascontiguousarray(deriv, np.float64)
-    nu = cache.nu
-    n = 14 + nu
-    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], nu):
-        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d]" % nu)
-    B, K1, _ = x.shape
-    K = K1 - 1
-    if gain.shape != (B, K, nu, n):
-        raise ValueError("shape mismatch: gain [B][K][%d][%d]" % (nu, n))
-    if deriv.size != B * K * 14 * (15 + 2 * nu) or deriv.shape[-2:] != (15 + 2 * nu, 14):
-        raise ValueError("shape mismatch: deriv [B][K][%d][14]" % (15 + 2 * nu))
-    s0, n0 = _cov_s0(S0, B), _cov_s0(N0, B)
-    m, Hm, rv = _nav_model(H, rm)
-    wv = _cov_noise(w)
-    sp, vt, sens, dense = _cov_vehicle(cache, vehicle, vtile, dense, B, K)
+    f = _nav_record(cache, x, u, deriv, gain, S0, N0, H, rm, w)
+    f["sp6"], f["vtile"], f["sens"], dense = _cov_vehicle(cache, vehicle, vtile, dense, f["B"], f["K"])
     if dense:
         raise ValueError('dense: () or ("sens",), not %r' % (dense,))
-    rep, navrep = np.empty((B, _lib.COV_NREP)), np.empty((B, _lib.NAV_NREP))
-    psig = np.empty((B, K1, _lib.PSIG_N))
-    opt = lambda a: _p(a) if a is not None else None   # noqa: E731
-    if sp is not None:
-        _lib.check(cache.handle, cache._L.scvx_nav_cov_vehicle_f64_host(
-            cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep),
-            _p(psig), None, None, None, None, opt(vt), _p(sp), opt(sens)), "scvx_nav_cov_vehicle_f64_host")
-        return NavReport(rep, navrep, sens=sens), psig
-    _lib.check(cache.handle, cache._L.scvx_nav_path_sigma_f64_host(
-        cache.handle, B, K, _p(x), _p(u), _p(deriv), _p(gain), _p(s0), _p(n0), m, opt(Hm), opt(rv), opt(wv), _p(rep), _p(navrep), _p(psig)),
-        "scvx_nav_path_sigma_f64_host")
-    return NavReport(rep, navrep), psig
+    _analysis(cache, f, {"report", "navrep", "psig"})
+    return NavReport(f["report"], f["navrep"], sens=f["sens"]), f["psig"]
 
 
 def _pf(a):

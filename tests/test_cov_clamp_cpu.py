@@ -144,7 +144,8 @@ def test_header_binding_and_julia_carry_the_same_symbols():
 
 def test_sat_cov_report_clamp_summary_and_the_argument_helpers():
     from successiveconvexification_amd import _lib
-    from successiveconvexification_amd.dynamics import CovReport, SatCovReport, _cov_band, _cov_clamp_dense
+    from successiveconvexification_amd._calls import CLAMP_DENSE, dense_names
+    from successiveconvexification_amd.dynamics import CovReport, SatCovReport, _cov_band
     from successiveconvexification_amd.montecarlo import clamp_summary
     raw, sat = np.arange(5 * 16, dtype=float).reshape(5, 16), 100.0 + np.arange(5 * 16, dtype=float).reshape(5, 16)
     r = SatCovReport(raw, sat, mean=np.zeros((5, 4, 17)))
@@ -167,9 +168,9 @@ def test_sat_cov_report_clamp_summary_and_the_argument_helpers():
     for bad in ((-0.1, 1.0), (np.inf, np.inf), (0.5, 0.4), (0.1, np.nan), (np.nan, 1.0), (0.1, 0.2, 0.3)):
         with pytest.raises(ValueError):
             _cov_band(bad)
-    assert _cov_clamp_dense(True) == {"mean", "sig", "covK", "cov", "satk"} and _cov_clamp_dense("satk") == {"satk"}
+    assert dense_names(True, CLAMP_DENSE) == {"mean", "sig", "covK", "cov", "satk"} and dense_names("satk", CLAMP_DENSE) == {"satk"}
     with pytest.raises(ValueError):
-        _cov_clamp_dense(["sens"])
+        dense_names(["sens"], CLAMP_DENSE)
 
 
 def test_anchor_against_sampled_clamped_flights_of_the_oracle():

@@ -241,7 +241,8 @@ def test_gaussian_handover():
 
 def test_dispersion_summary_and_cov_report():
     from successiveconvexification_amd import _lib
-    from successiveconvexification_amd.dynamics import CovReport, _cov_dense, _cov_noise, _cov_s0
+    from successiveconvexification_amd._calls import COV_DENSE, dense_names
+    from successiveconvexification_amd.dynamics import CovReport, _cov_noise, _cov_s0
     from successiveconvexification_amd.montecarlo import dispersion_summary
     raw = np.arange(5 * 16, dtype=float).reshape(5, 16)
     raw[:, _lib.COV_INDEX["N_RATE"]] = np.inf
@@ -272,6 +273,7 @@ def test_dispersion_summary_and_cov_report():
     assert _cov_noise(None) is None and _cov_noise(2.0).tolist() == [2.0] * 14
     with pytest.raises(ValueError):
         _cov_noise(np.ones(3))
-    assert _cov_dense(True) == {"sig", "covK", "cov"} and _cov_dense(False) == set() and _cov_dense("sig") == {"sig"}
+    assert dense_names(True, COV_DENSE) == {"sig", "covK", "cov"} and dense_names(False, COV_DENSE) == set()
+    assert dense_names("sig", COV_DENSE) == {"sig"}
     with pytest.raises(ValueError):
-        _cov_dense(["sigma"])
+        dense_names(["sigma"], COV_DENSE)

@@ -324,15 +324,15 @@ def test_statistics_on_the_device_within_six_standard_errors():
 
 def _raw_call(c, x, u, s, d, L, c0, cn, xi0, xin, nud, m, H, rm, kf):
     """scvx_track_mc_nav_f64_host on explicit factors, every dense output: a McNavReport"""
-    from successiveconvexification_amd import _lib
-    from successiveconvexification_amd.dynamics import McNavReport, _mc_nav_outputs, _p
+    from successiveconvexification_amd import _calls
+    from successiveconvexification_amd.dynamics import McNavReport
     B, K, S = x.shape[0], x.shape[1] - 1, xi0.shape[0]
-    red, dn = _mc_nav_outputs(B, S, K, True)
-    a = [np.ascontiguousarray(v, np.float64) for v in (x, u, s, L, c0, xi0, d, kf, cn, xin, nud, H, rm)]
-    _lib.check(c.handle, c._L.scvx_track_mc_nav_f64_host(c.handle, B, K, S, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), _p(a[4]), _p(a[5]), None, None,
-                                                         _p(a[6]), _p(a[7]), _p(a[8]), _p(a[9]), _p(a[10]), m, _p(a[11]), _p(a[12]), 10, 0, 0.0,
-                                                         *[_p(v) for v in red], *[_p(v) for v in dn]), "scvx_track_mc_nav_f64_host")
-    return McNavReport(*red, *dn)
+    f = dict(x=x, u=u, sigma=s, gain=L, C0=c0, xi0=xi0, deriv=d, kf=kf, CN=cn, xin=xin, nud=nud, H=H, rm=rm)
+    f = {k: np.ascontiguousarray(v, np.float64) for k, v in f.items()}
+    f.update(_calls.mc_outputs(B, K, S, _calls.MC_NAV_REDUCED + _calls.MC_NAV_DENSE), handle=c.handle, B=B, K=K, S=S, eta=None, w14=None,
+             m=m, nsub=10, flags=0, tol=0.0)
+    _calls.call(c._L, c.handle, "scvx_track_mc_nav_f64_host", f)
+    return McNavReport(*[f[k] for k in _calls.MC_NAV_REDUCED + _calls.MC_NAV_DENSE])
 
 
 def test_a_nan_poisons_only_its_plan():

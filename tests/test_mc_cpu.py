@@ -68,7 +68,8 @@ def test_header_binding_and_julia_carry_the_new_symbols():
 
 
 def test_mc_report_and_summary():
-    from successiveconvexification_amd.dynamics import FlightReport, McReport, _mc_dense
+    from successiveconvexification_amd._calls import MC_DENSE, dense_names
+    from successiveconvexification_amd.dynamics import FlightReport, McReport
     from successiveconvexification_amd.montecarlo import mc_summary
     rng = np.random.default_rng(0)
     raw = rng.uniform(0.0, 1.0, (6, 48))
@@ -84,8 +85,9 @@ def test_mc_report_and_summary():
     with pytest.raises(ValueError):
         McReport(raw, None, None).flight(0)
     with pytest.raises(ValueError):
-        _mc_dense(("flights", "ufly"))
-    assert _mc_dense(True) == {"flights", "xland", "dx0"} and _mc_dense(()) == set() and _mc_dense("xland") == {"xland"}
+        dense_names(("flights", "ufly"), MC_DENSE)
+    assert dense_names(True, MC_DENSE) == {"flights", "xland", "dx0"} and dense_names((), MC_DENSE) == set()
+    assert dense_names("xland", MC_DENSE) == {"xland"}
     status = np.array([0, 0, 0, 1, 3, 0])
     s = mc_summary(rep, status)
     assert s["n"] == 6 and s["converged"] == 4 and s["samples"] == 64 and s["plans_with_bad_flights"] == 1

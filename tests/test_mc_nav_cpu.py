@@ -80,7 +80,8 @@ def test_mc_nav_draws_rows_are_shard_independent_and_their_own():
 
 def test_mc_nav_report_and_summary():
     from successiveconvexification_amd import _lib
-    from successiveconvexification_amd.dynamics import McNavReport, McReport, _mc_nav_dense, _mc_nav_inputs, _mc_nav_outputs
+    from successiveconvexification_amd._calls import MC_NAV_DENSE, MC_NAV_REDUCED, dense_names, mc_outputs
+    from successiveconvexification_amd.dynamics import McNavReport, McReport, _mc_nav_inputs
     from successiveconvexification_amd.montecarlo import mc_summary
     rng = np.random.default_rng(0)
     raw = rng.uniform(0.0, 1.0, (3, 48))
@@ -95,10 +96,12 @@ def test_mc_nav_report_and_summary():
     assert np.array_equal(rep.MAX_FED, nav[:, 5]) and not hasattr(rep, "NAV_PEAK")
     s = mc_summary(rep, np.zeros(3, int))                                                   # reads it unchanged
     assert s["converged"] == 3 and s["samples"] == 64 and s["plans_with_bad_flights"] == 1 and s["stats"]["P_ANY"]["max"] == raw[:, 41].max()
-    assert _mc_nav_dense(True) == {"flights", "xland", "dx0", "navfed", "navK"} and _mc_nav_dense(()) == set() and _mc_nav_dense("navK") == {"navK"}
+    assert dense_names(True, MC_NAV_DENSE) == {"flights", "xland", "dx0", "navfed", "navK"} and dense_names((), MC_NAV_DENSE) == set()
+    assert dense_names("navK", MC_NAV_DENSE) == {"navK"}
     with pytest.raises(ValueError):
-        _mc_nav_dense(("navfed", "ufly"))
-    red, dn = _mc_nav_outputs(2, 5, 3, ("navfed",))
+        dense_names(("navfed", "ufly"), MC_NAV_DENSE)
+    out = mc_outputs(2, 3, 5, dense_names(("navfed",), MC_NAV_DENSE) | set(MC_NAV_REDUCED))
+    red, dn = [out[k] for k in MC_NAV_REDUCED], [out[k] for k in MC_NAV_DENSE]
     assert [a.shape for a in red] == [(2, 48), (2, 14), (2, 14, 14), (2, 28), (2, 28, 28), (2, 8)]
     assert [None if a is None else a.shape for a in dn] == [None, None, None, (2, 5, 3, 14), None]
     c0, cn, n0, xi0, eta, xin, nud, wv = _mc_nav_inputs(np.full(14, 2.0), np.full(14, 0.5), 2, 3, 6, 5, 1, 1e-8, None)

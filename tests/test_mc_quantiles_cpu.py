@@ -188,9 +188,11 @@ def test_report_carries_the_quantiles_by_name():
     from successiveconvexification_amd.dynamics import McNavReport, McReport, _McQ
     mq = _McQ([0.5, 0.99], True, ("flights", "pathv"))
     assert mq.on and set(mq.rest) == {"flights"} and mq.want_pv
-    nq, rk, fq, pq, pv = mq.args(2, 3, 70)
-    assert nq == 2 and mq.ranks.tolist() == [34, 69] and mq.flightq.shape == (2, 16, 2) and mq.pathq.shape == (2, 4, 5, 2)
-    assert mq.pathv.shape == (2, 4, 5, 70) and fq and pq and pv
+    f = mq.fields(2, 3, 70)
+    assert list(f) == ["nq", "ranks", "flightq", "pathq", "pathv"]
+    assert f["nq"] == 2 and mq.ranks.tolist() == [34, 69] and mq.flightq.shape == (2, 16, 2) and mq.pathq.shape == (2, 4, 5, 2)
+    assert mq.pathv.shape == (2, 4, 5, 70) and f["ranks"] is mq.ranks and f["flightq"] is mq.flightq and f["pathq"] is mq.pathq
+    assert f["pathv"] is mq.pathv
     mq.flightq[:] = np.arange(64.0).reshape(2, 16, 2)
     mq.pathq[:] = np.arange(80.0).reshape(2, 4, 5, 2)
     rep = McReport(np.zeros((2, 48)), None, None)._with_q(mq)
@@ -205,7 +207,7 @@ def test_report_carries_the_quantiles_by_name():
     with pytest.raises(ValueError):
         plain.quantile("MISS_R", 0.5)
     lean = _McQ([0.5], False, ())
-    assert lean.args(2, 3, 5)[3] is None and lean.args(2, 3, 5)[4] is None
+    assert lean.fields(2, 3, 5)["pathq"] is None and lean.fields(2, 3, 5)["pathv"] is None
     with pytest.raises(ValueError):
         _McQ(None, True, ())
     with pytest.raises(ValueError):

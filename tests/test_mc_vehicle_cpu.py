@@ -160,15 +160,28 @@ def test_host_helpers_and_keyword_checks_before_any_library_call():
         _McVeh((np.zeros(5), np.zeros(6)), ())
     on = _McVeh(mc.vehicle_errors(thrust=1e-3), ("theta", "xland"))
     assert on.on and on.rest == ("xland",) and on.veh.sp[0] == 1e-3 and list(on.veh.reserved) == [0, 0]
-    rg, noise, veh, zeta, theta = on.args(3, 7, None, True, 5, 64)
-    assert rg is None and noise == 0 and on.theta.shape == (3, 7, 6) and np.array_equal(on.zeta, mc.mc_vehicle_draws(7, 5, lo=64))
+    f = on.fields(3, 7, None, 5, 64)
+    assert list(f) == ["veh", "zeta", "theta"] and f["veh"] is on.veh and f["zeta"] is on.zeta and f["theta"] is on.theta
+    assert on.theta.shape == (3, 7, 6) and np.array_equal(on.zeta, mc.mc_vehicle_draws(7, 5, lo=64))
     dev = _McVeh((np.zeros(6), np.zeros(6), np.zeros((7, 6))), ())
     with pytest.raises(ValueError):
-        dev.args(3, 7, _mc_rng("device", None, False, 0, 0, 0), False, 0, 0)
+        dev.fields(3, 7, _mc_rng("device", None, False, 0, 0, 0), 0, 0)
     with pytest.raises(ValueError):
-        _McVeh((np.zeros(6), np.zeros(6), np.zeros((8, 6))), ()).args(3, 7, None, False, 0, 0)
-    rg, noise, _, zeta, theta = _McVeh(mc.vehicle_errors(isp=1e-3), ()).args(3, 7, _mc_rng("device", None, False, 0, 0, 0), True, 0, 0)
-    assert rg is not None and noise == 1 and zeta is None and theta is None
+        _McVeh((np.zeros(6), np.zeros(6), np.zeros((8, 6))), ()).fields(3, 7, None, 0, 0)
+    f = _McVeh(mc.vehicle_errors(isp=1e-3), ()).fields(3, 7, _mc_rng("device", None, False, 0, 0, 0), 0, 0)
+    assert f["veh"] is not None and f["zeta"] is None and f["theta"] is None
+    # (rng, noise) of the _veh tail, on the recorded call: NULL and 0 with host draws whatever w is, the stream and 1 with the device's
+    from py_call_recorder import Recorder, make_cache, pattern
+    from successiveconvexification_amd.dynamics import track_mc_batch
+    rec = Recorder()
+    plan = (pattern((2, 4, 14)), pattern((2, 4, 3)), pattern((2,)), pattern((2, 3, 3, 17)), np.full(14, 0.5), 7)
+    track_mc_batch(make_cache(rec, 3, False), *plan, seed=5, w=0.25, vehicle=mc.vehicle_errors(thrust=1e-3), sample_lo=64)
+    track_mc_batch(make_cache(rec, 3, False), *plan, w=0.25, vehicle=mc.vehicle_errors(isp=1e-3), rng="device")
+    track_mc_batch(make_cache(rec, 3, False), *plan, vehicle=mc.vehicle_errors(isp=1e-3), rng="device")
+    assert [ln.split("(")[0] for ln in rec.lines] == ["scvx_track_mc_veh_f64_host"] * 3
+    assert ", rng=NULL, noise=0, veh=&ScvxMcVehicle{" in rec.lines[0] and ", zeta=<f8[7, 6] crc=" in rec.lines[0]
+    assert ", rng=&ScvxMcRng{" in rec.lines[1] and ", noise=1, veh=&ScvxMcVehicle{" in rec.lines[1] and rec.lines[1].endswith("zeta=NULL, theta=NULL)")
+    assert ", rng=&ScvxMcRng{" in rec.lines[2] and ", noise=0, veh=&ScvxMcVehicle{" in rec.lines[2]
 
 
 def anchor_case():

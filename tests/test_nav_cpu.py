@@ -182,7 +182,8 @@ def test_header_binding_and_julia_carry_the_same_symbols():
 
 def test_nav_report_and_argument_helpers():
     from successiveconvexification_amd import _lib
-    from successiveconvexification_amd.dynamics import CovReport, NavReport, _nav_dense, _nav_model
+    from successiveconvexification_amd._calls import NAV_DENSE, dense_names
+    from successiveconvexification_amd.dynamics import CovReport, NavReport, _nav_model
     from successiveconvexification_amd.montecarlo import dispersion_summary
     raw = np.arange(3 * 16, dtype=float).reshape(3, 16)
     nav = 100.0 + np.arange(3 * 8, dtype=float).reshape(3, 8)
@@ -200,9 +201,10 @@ def test_nav_report_and_argument_helpers():
     for bad in ((np.eye(3), 1.0), (np.eye(14)[1:4], np.ones(2)), (np.eye(14)[1:4], None)):
         with pytest.raises(ValueError):
             _nav_model(*bad)
-    assert _nav_dense(True) == {"sig", "navsig", "kf", "joint"} and _nav_dense(False) == set() and _nav_dense("kf") == {"kf"}
+    assert dense_names(True, NAV_DENSE) == {"sig", "navsig", "kf", "joint"} and dense_names(False, NAV_DENSE) == set()
+    assert dense_names("kf", NAV_DENSE) == {"kf"}
     with pytest.raises(ValueError):
-        _nav_dense(["cov"])
+        dense_names(["cov"], NAV_DENSE)
 
 
 def test_measurement_rows_and_nav_error_samples():
