@@ -1176,6 +1176,57 @@ int scvx_batch_cov_clamp(scvx_batch *b, const double *q14, const double *rNU, co
                          const double *band2, double *report, double *satrep, double *mean, double *sig, double *covK, double *cov,
                          double *satk);
 
+/* ---- segment audit: the plan's path constraints segment by segment, and back-offs from it (no counterpart in the reference) ------
+ * The flight check keeps ONE maximum per column over the whole flight.  In SCVX_FLIGHT_PLAN mode the state restarts at every planned
+ * node, so the K segments of a plan are independent: this call audits each on a lane of its own (one lane per (b, k), the integrator,
+ * the hold, the nsub + 1 sample points and the path functions of scvx_flight_check_f64) and says WHERE a constraint fails between
+ * the nodes.  seg [B][K][SCVX_SEG_N], per segment k (from node k to node k + 1):
+ *   DEFECT   |x_end - x[k+1]|_inf, the scvx_propagate_f64 defect of the segment;
+ *   G_MASS .. G_FIN   the maxima of the flight report's path functions over the segment's nsub + 1 samples, in the report's order
+ *            (G_DP / G_FIN: -inf where the model has no such constraint);
+ *   QNORM    max of | |q| - 1 |.
+ * A non-finite sampled state makes the DEFECT, the state G_* and the QNORM of THAT segment NaN and cannot disturb another segment (a
+ * non-finite node k is also what segment k - 1 ends against: that one shows it in its DEFECT alone).
+ * report [B][SCVX_FLIGHT_NREP] or NULL: the SCVX_FLIGHT_PLAN report, reduced on the device from seg in a fixed order (two launches
+ * agree bit for bit): GAP and every G_* / QNORM are bitwise the maxima over k of seg's columns, the MISS_* and MASS_END are those of the
+ * last segment's end (MISS_* NaN when GAP is).  nsub = 0 takes the context's (scvx_set_nsub).  dt = 1 / (K + 1); asynchronous on the
+ * context's stream.  SCVX_ERR_ARG for nsub outside [1, 1000], B < 1, K != the problem's K, a null x / u / sigma / seg.
+ * Limits: the samples are the substep boundaries only (RK stage points and the stretch between two samples are not looked at; on the
+ * golden plans nsub = 40 moves the figures of nsub = 10 in the third digit). */
+#define SCVX_SEG_N 11
+#define SCVX_SEG_DEFECT 0
+#define SCVX_SEG_G_MASS 1
+#define SCVX_SEG_G_GLIDE 2
+#define SCVX_SEG_G_TILT 3
+#define SCVX_SEG_G_RATE 4
+#define SCVX_SEG_G_TMAX 5
+#define SCVX_SEG_G_TMIN 6
+#define SCVX_SEG_G_GIMBAL 7
+#define SCVX_SEG_G_DP 8
+#define SCVX_SEG_G_FIN 9
+#define SCVX_SEG_QNORM 10
+int scvx_segment_audit_f64(scvx_ctx *ctx, int B, int K, const double *x_dev, const double *u_dev, const double *sigma_dev, int nsub,
+                           double *seg_dev, double *report_dev);
+int scvx_segment_audit_f64_host(scvx_ctx *ctx, int B, int K, const double *x, const double *u, const double *sigma, int nsub,
+                                double *seg, double *report);
+/* The same on the batch's current accepted iterate; seg and report are host arrays (report may be NULL).  The batch is left untouched. */
+int scvx_batch_segment_audit(scvx_batch *b, int nsub, double *seg, double *report);
+/* Back-offs from the audit, on the device: the segment audit of the batch's current accepted iterate, then one small kernel on the
+ * batch's own back-off buffers.  Per node k and constraint selected in `which` (SCVX_MARGIN_*), with G the constraint's seg column,
+ *     e_k = max(excess(k - 1), excess(k)),  excess = G where G > tol, else 0       (node 0: segment 0 alone, node K: segment K - 1)
+ *     new = min(old + gain e_k, cap width_k)
+ * with the widths and the forced zeros of scvx_batch_margins_from_cov (glide, tilt and rate 0 at node K, glide and rate 0 at node 0,
+ * the glide width from the current iterate).  SCVX_MARGIN_THRUST reads G_TMIN and raises lo alone (|u| is convex along a hold, so hi
+ * needs nothing between the nodes); GLIDE, TILT and RATE act on pm.  SCVX_MARGIN_MASS is refused: mass is monotone, a bound held at
+ * the nodes holds between them.  The back-offs ACCUMULATE: the audit is against the true constants, so back-offs that are already
+ * there (scvx_batch_margins_from_cov, a previous round) show as negative G and nothing is added on top of them; a batch without
+ * back-offs starts from zeros.  A trajectory with a NaN in a selected seg column is left as it is.  The warm-start state is dropped,
+ * as by the other setters.  seg [B][K][SCVX_SEG_N] (host, or NULL: then nothing returns to the host and the call is asynchronous).
+ * SCVX_ERR_ARG for gain not finite or < 1, tol < 0, cap outside (0, 0.5), which = 0, an unknown bit or SCVX_MARGIN_MASS, a bad nsub.
+ * Limits: gain is a starting point (the violation can move to a neighbouring segment of the next plan: repeat the round); the
+ * dynamic-pressure, gimbal and fin cones are audited but have no back-off. */
+int scvx_batch_audit_margins(scvx_batch *b, int nsub, unsigned which, double gain, double tol, double cap, double *seg);
+
 /* Running totals over every solve_step enqueued since the last call with reset != 0 (what a timed region really executed):
  * out8 = {trajectory-steps, conic solves run, interior-point iterations summed over them, solves that were warm-started,
  * solves skipped by reuse_inactive_tr, steps REJECTED, steps that failed (SOLVER / NONFINITE / INFEASIBLE), steps that ended

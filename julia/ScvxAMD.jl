@@ -315,6 +315,49 @@ flight_check_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{
         (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
         cache.ctx, B, K, x_dev, u_dev, sigma_dev, nsub, mode, report_dev, xfly_dev), "scvx_flight_check_f64")
 
+# ---- segment audit (new): the PLAN-mode flight check per segment, and back-offs from it ---------------------------------------
+# include/scvx.h, "segment audit".  seg is SEG_N x K x B (column-major == [B][K][SEG_N]); the rows, 0-based as in the header:
+const SEG_N = 11
+const SEG_DEFECT = 0; const SEG_G_MASS = 1; const SEG_G_GLIDE = 2; const SEG_G_TILT = 3; const SEG_G_RATE = 4; const SEG_G_TMAX = 5
+const SEG_G_TMIN = 6; const SEG_G_GIMBAL = 7; const SEG_G_DP = 8; const SEG_G_FIN = 9; const SEG_QNORM = 10
+
+# any plans: (seg SEG_N x K x B, the PLAN-mode report 16 x B); nsub = 0 takes the context's
+function segment_audit(cache::Cache, x::Array{Float64,3}, u::Array{Float64,3}, sigma::Vector{Float64}; nsub::Int=0)
+    K = size(x, 2) - 1; B = size(x, 3)
+    seg = Array{Float64,3}(undef, SEG_N, K, B)
+    report = Matrix{Float64}(undef, FLIGHT_NREP, B)
+    check(cache.ctx, ccall((:scvx_segment_audit_f64_host, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x, u, sigma, nsub, seg, report), "scvx_segment_audit_f64_host")
+    return seg, report
+end
+
+# the current accepted iterate of a batch
+function segment_audit(b::Batch; nsub::Int=0)
+    seg = Array{Float64,3}(undef, SEG_N, b.cache.problem.K, b.B)
+    report = Matrix{Float64}(undef, FLIGHT_NREP, b.B)
+    check(b.cache.ctx, ccall((:scvx_batch_segment_audit, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+        b.h, nsub, seg, report), "scvx_batch_segment_audit")
+    return seg, report
+end
+
+# the same on device pointers, asynchronous on the context's stream; report_dev may be C_NULL
+segment_audit_dev!(cache::Cache, B::Int, K::Int, x_dev::Ptr{Cdouble}, u_dev::Ptr{Cdouble}, sigma_dev::Ptr{Cdouble}, nsub::Int,
+                   seg_dev::Ptr{Cdouble}, report_dev::Ptr{Cdouble}) =
+    check(cache.ctx, ccall((:scvx_segment_audit_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+        cache.ctx, B, K, x_dev, u_dev, sigma_dev, nsub, seg_dev, report_dev), "scvx_segment_audit_f64")
+
+# back-offs from the audit of the batch's current accepted iterate, accumulated on what it carries: new = min(old + gain e_k, cap width_k);
+# which: MARGIN_THRUST (lo alone) | MARGIN_GLIDE | MARGIN_TILT | MARGIN_RATE (the constants further down; the default is thrust + tilt).  Returns seg, or nothing with seg = false
+function margins_from_audit!(b::Batch; which::Integer=0x09, gain::Float64=1.5, tol::Float64=1e-7,
+                             cap::Float64=0.25, nsub::Int=0, seg::Bool=true)
+    out = seg ? Array{Float64,3}(undef, SEG_N, b.cache.problem.K, b.B) : nothing
+    check(b.cache.ctx, ccall((:scvx_batch_audit_margins, LIB), Cint, (Ptr{Cvoid}, Cint, Cuint, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}),
+        b.h, nsub, which, gain, tol, cap, seg ? pointer(out) : Ptr{Cdouble}(C_NULL)), "scvx_batch_audit_margins")
+    return out
+end
+
 # ---- plan tracking (new): time-varying LQR gains about a plan and the closed-loop flight under them ---------------------------
 # include/scvx.h, "plan tracking".  gain is n x NU x K x B (column-major == [B][K][NU][n], n = 14 + NU): du_{k+1} = gain[:, :, k, b]' * [dx_k; du_k].
 # q, r, qf: diagonal weights (scalars broadcast); 1, 1, 100 is a starting point, not tuning advice.

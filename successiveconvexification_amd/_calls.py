@@ -70,7 +70,16 @@ def _converter(kind):
     return lambda v: None if v is None else v.ctypes.data_as(kind)
 
 
-_LAYOUT = {name: tuple(zip(fields, [_converter(k) for k in _lib.SIGNATURES[name][1][1:]])) for name, fields in TABLE.items()}
+# The segment audit and the back-offs taken from it go through the same dispatcher.  They are a family of their own, so they stand beside
+# TABLE, which holds exactly the two wide families.
+AUDIT_TABLE = {
+    "scvx_segment_audit_f64_host": ("B", "K", "x", "u", "sigma", "nsub", "seg", "report"),
+    "scvx_batch_segment_audit": ("nsub", "seg", "report"),
+    "scvx_batch_audit_margins": ("nsub", "which", "gain", "tol", "cap", "seg"),
+}
+
+_LAYOUT = {name: tuple(zip(fields, [_converter(k) for k in _lib.SIGNATURES[name][1][1:]]))
+           for name, fields in {**TABLE, **AUDIT_TABLE}.items()}
 
 
 def call(L, err_handle, name, fields):

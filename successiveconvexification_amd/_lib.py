@@ -72,6 +72,10 @@ FLIGHT_NREP = 16
 FLIGHT_COLUMNS = ("GAP", "MISS_R", "MISS_V", "MISS_Q", "MISS_W", "MASS_END", "G_MASS", "G_GLIDE", "G_TILT", "G_RATE", "G_TMAX",
                   "G_TMIN", "G_GIMBAL", "G_DP", "G_FIN", "QNORM")
 FLIGHT_INDEX = {n: i for i, n in enumerate(FLIGHT_COLUMNS)}
+# scvx_segment_audit_*: the columns of seg [B][K][SEG_N] (the SCVX_SEG_* macros of include/scvx.h)
+SEG_N = 11
+SEG_COLUMNS = ("DEFECT", "G_MASS", "G_GLIDE", "G_TILT", "G_RATE", "G_TMAX", "G_TMIN", "G_GIMBAL", "G_DP", "G_FIN", "QNORM")
+SEG_INDEX = {n: i for i, n in enumerate(SEG_COLUMNS)}
 TRACK_CLAMP = 1   # SCVX_TRACK_CLAMP: scvx_track_fly_* rescales the commanded thrust / fin norms into their bounds
 # scvx_cov_propagate_*: the columns of the dispersion report [B][COV_NREP] (the SCVX_COV_* macros of include/scvx.h)
 COV_NREP = 16
@@ -225,6 +229,11 @@ SIGNATURES = {
     "scvx_batch_margins_from_cov_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint, _dp, _dp]),
     "scvx_batch_margins_from_nav_veh": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_uint,
                                                   _dp, _dp]),
+    # the segment audit and the back-offs taken from it
+    "scvx_segment_audit_f64": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "scvx_segment_audit_f64_host": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
+    "scvx_batch_segment_audit": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+    "scvx_batch_audit_margins": (C.c_int, [_vp, C.c_int, C.c_uint, C.c_double, C.c_double, C.c_double, _dp]),
     "scvx_linearize_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "scvx_linearize_f32_host": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]),
     "scvx_propagate_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, _vp]),

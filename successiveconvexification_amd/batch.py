@@ -516,6 +516,57 @@ class ScvxBatch:
             out = self.solve()
         return out + self.thrust_margins()
 
+    AUDIT_COLUMN = {"thrust": "G_TMIN", "glide": "G_GLIDE", "tilt": "G_TILT", "rate": "G_RATE"}   # the seg column a back-off answers
+
+    def audit(self, nsub=None):
+        """The segment audit of the batch's current accepted iterate (scvx_batch_segment_audit): a dynamics.SegmentReport, the path
+        functions of the PLAN-mode flight check per segment.  The batch is left untouched."""
+        from .dynamics import SegmentReport
+        f = dict(handle=self.handle, nsub=nsub or 0, seg=np.empty((self.B, self.K, _lib.SEG_N)), report=np.empty((self.B, _lib.FLIGHT_NREP)))
+        _calls.call(self._L, self.cache.handle, "scvx_batch_segment_audit", f)
+        return SegmentReport(f["seg"], f["report"])
+
+    def _audit_mask(self, constraints):
+        mask = self._margin_mask(constraints)
+        if mask & _lib.MARGIN_BITS["mass"]:
+            raise ValueError("the audit has no mass back-off: mass is monotone, a bound held at the nodes holds between them")
+        return mask
+
+    def margins_from_audit(self, constraints=("thrust", "tilt"), gain=1.5, tol=1e-7, cap=0.25, nsub=None, want_seg=True):
+        """Back-offs from the segment audit of the current accepted iterate, on the device (scvx_batch_audit_margins): per node,
+        new = min(old + gain e_k, cap width_k) with e_k the larger excess over tol of the two segments that meet at the node.  They
+        ACCUMULATE on what the batch carries; "thrust" raises lo alone.  constraints: a subset of ("thrust", "glide", "tilt", "rate").
+        Returns seg [B][K][11] of the audit the back-offs were taken from (None with want_seg=False: nothing returns to the host)."""
+        f = dict(handle=self.handle, nsub=nsub or 0, which=self._audit_mask(constraints), gain=gain, tol=tol, cap=cap,
+                 seg=np.empty((self.B, self.K, _lib.SEG_N)) if want_seg else None)
+        _calls.call(self._L, self.cache.handle, "scvx_batch_audit_margins", f)
+        return f["seg"]
+
+    def harden(self, constraints=("thrust", "glide", "tilt", "rate"), rounds=3, gain=1.5, tol=1e-7, restart="replan", nsub=None, cap=0.25):
+        """Make the converged plans hold their own constraints BETWEEN the nodes.  Per round: margins_from_audit, then replan() (or,
+        with restart="guess", reset(): the straight-line guess again, the back-offs kept), then solve().  It stops as soon as no
+        converged plan has a selected G > tol in its audit, and after `rounds` at the latest.  Returns (status, iters, nu_norm, dJ) of
+        the last solve() (iters 0 and NaN norms when the first audit was already clean), the SegmentReport of the final plans and the
+        rounds used.  Limits: the samples are the substep boundaries; gain is a starting point (a violation can move to a
+        neighbouring segment); a replan may land in another local optimum than a solve from the guess."""
+        if restart not in ("replan", "guess"):
+            raise ValueError('harden: restart must be "replan" or "guess", not %r' % (restart,))
+        if int(rounds) < 1:
+            raise ValueError("harden: rounds >= 1")
+        mask = self._audit_mask(constraints)
+        cols = [c for n, c in self.AUDIT_COLUMN.items() if mask & _lib.MARGIN_BITS[n]]
+        rep, st = self.audit(nsub), self.flags()[0]
+        out, used = (st, np.zeros(self.B, np.int32), np.full(self.B, np.nan), np.full(self.B, np.nan)), 0
+        for _ in range(int(rounds)):
+            conv = st == 0
+            if not any((getattr(rep, c)[conv] > tol).any() for c in cols):
+                break
+            self.margins_from_audit(constraints, gain, tol, cap, nsub, want_seg=False)
+            self.replan() if restart == "replan" else self.reset()
+            out = self.solve()
+            st, rep, used = out[0], self.audit(nsub), used + 1
+        return out + (rep, used)
+
     def navigation(self, S0, N0, H, rm, w=None, q=None, r=None, qf=None, dense=False, vehicle=None, clamp=False):
         """Navigation-error covariance analysis of the batch's current accepted iterate flown on an estimate under its LQR gains
         (scvx_batch_nav_cov; S0, N0, H, rm, w and dense as dynamics.nav_cov_batch, weights as track_gains): a dynamics.NavReport.

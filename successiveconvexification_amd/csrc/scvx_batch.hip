@@ -289,6 +289,7 @@ struct scvx_batch {
     bool pmarg_on = false;    // scvx_batch_set_path_margins / scvx_batch_margins_from_cov set it, NULL and scvx_batch_init clear it
     double *cov_s0 = nullptr, *cov_rep = nullptr, *cov_psig = nullptr;   // scratch of scvx_batch_thrust_margins_from_cov: allocated on first use
     double *nav_n0 = nullptr, *nav_rep = nullptr;   // scratch of scvx_batch_margins_from_nav on top of the three above: allocated on first use
+    double* audit_seg = nullptr;   // seg of scvx_batch_audit_margins [B][K][SCVX_SEG_N]: allocated on first use
     double* vtile = nullptr;   // the vehicle tiles of the _veh analyses [B][K][SCVX_VTILE_N][14]: allocated on first use
     double *track_gain = nullptr, *track_p0 = nullptr;   // scratch of scvx_batch_track_*: allocated on first use, freed with the batch
     int *k1skip = nullptr;   // per trajectory: >= SCVX_ST_REJECTED = the reference point did not change in the last step (K1 skips it)
@@ -669,7 +670,7 @@ void scvx_batch_destroy(scvx_batch* b) {
     if (b->h_nlive) (void)hipHostFree(b->h_nlive);
     void* ptrs[] = {b->traj0, b->traj, b->cand, b->sol, b->x, b->u, b->sigma, b->cx, b->cu, b->csigma, b->endpoint, b->deriv, b->xprop,
                     b->nu, b->rk, b->cost, b->ic, b->info, b->out, b->work, b->iter, b->status, b->active, b->live, b->ttr, b->deriv_f, b->acc, b->d_nlive, b->k1skip,
-                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig, b->nav_n0, b->nav_rep, b->vtile};
+                    b->track_gain, b->track_p0, b->marg, b->pmarg, b->cov_s0, b->cov_rep, b->cov_psig, b->nav_n0, b->nav_rep, b->vtile, b->audit_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -1344,6 +1345,55 @@ int scvx_batch_thrust_margins_from_cov(scvx_batch* b, const double* q14, const d
     scvx::CovCall c;
     c.S0 = S0, c.w = w14;
     return margins_from_cov(b, c, margins_own(q14, rNU, qf14, nsigma, cap, SCVX_MARGIN_THRUST, true), psig);
+}
+
+int scvx_batch_segment_audit(scvx_batch* b, int nsub, double* seg, double* report) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    if (nsub == 0) nsub = ctx->nsub;
+    // b->x / u / sigma are the split views of the accepted iterate (kept current by every step); only read here
+    rc = scvx::check_segment_audit(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, seg);
+    if (rc) return rc;
+    const scvx::Dims d(b->B, b->K, b->NU);
+    scvx::Staging s(ctx);
+    double *dg = s.out(seg, d.aud), *dr = s.out(report, d.frep);
+    s.launch([&] { return scvx::launch_segment_audit(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, dg, dr, s.st); });
+    return s.finish("scvx_batch_segment_audit");
+}
+
+int scvx_batch_audit_margins(scvx_batch* b, int nsub, unsigned which, double gain, double tol, double cap, double* seg) {
+    int rc = check_batch(b, true);
+    if (rc) return rc;
+    scvx_ctx* ctx = b->ctx;
+    // every check before anything is enqueued
+    if (nsub == 0) nsub = ctx->nsub;
+    if (!(gain >= 1.0) || !std::isfinite(gain)) return fail(ctx, SCVX_ERR_ARG, "margins from audit: gain must be finite and >= 1");
+    if (!(tol >= 0.0)) return fail(ctx, SCVX_ERR_ARG, "margins from audit: tol must be >= 0");
+    if (!(cap > 0.0 && cap < 0.5)) return fail(ctx, SCVX_ERR_ARG, "margins from audit: cap must lie in (0, 0.5), a fraction of the constraint's width");
+    if (which == 0u || (which & ~(unsigned)SCVX_MARGIN_ALL))
+        return fail(ctx, SCVX_ERR_ARG, "margins from audit: which must be a non-empty mask of SCVX_MARGIN_*");
+    if (which & SCVX_MARGIN_MASS)
+        return fail(ctx, SCVX_ERR_ARG, "margins from audit: mass is monotone, a bound held at the nodes holds between them (no SCVX_MARGIN_MASS)");
+    const size_t ns = (size_t)b->B * b->K * SCVX_SEG_N;
+    if (!b->audit_seg) SCVX_HIP(ctx, hipMalloc((void**)&b->audit_seg, ns * 8));
+    if ((rc = scvx::check_segment_audit(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, b->audit_seg))) return rc;
+    hipStream_t st = ctx->stream;
+    SCVX_HIP(ctx, scvx::launch_segment_audit(ctx, b->B, b->K, b->x, b->u, b->sigma, nsub, b->audit_seg, nullptr, st));
+    const bool path = (which & ~(unsigned)SCVX_MARGIN_THRUST) != 0u;
+    // the back-offs accumulate: a batch that has none starts from zeros
+    if ((which & SCVX_MARGIN_THRUST) && !b->marg_on) SCVX_HIP(ctx, hipMemsetAsync(b->marg, 0, (size_t)b->B * (b->K + 1) * 2 * 8, st));
+    if (path && !b->pmarg_on) SCVX_HIP(ctx, hipMemsetAsync(b->pmarg, 0, (size_t)b->B * (b->K + 1) * SCVX_PMARG_N * 8, st));
+    const scvx::AuditCaps capw{cap * (b->C.Tmax - b->C.Tmin), cap * b->C.sqcm, cap * b->C.omMax, cap, b->C.itan};
+    SCVX_HIP(ctx, scvx::launch_audit_margins(b->B, b->K, b->audit_seg, b->x, gain, tol, capw, which, b->marg, b->pmarg, st));
+    if (which & SCVX_MARGIN_THRUST) b->marg_on = true;
+    if (path) b->pmarg_on = true;
+    SCVX_HIP(ctx, hipMemsetAsync(b->ttr, 0x7f, (size_t)b->B * 8, st));   // see scvx_batch_set_thrust_margins
+    if (seg) {
+        SCVX_HIP(ctx, hipMemcpyAsync(seg, b->audit_seg, ns * 8, hipMemcpyDeviceToHost, st));
+        SCVX_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return SCVX_OK;
 }
 
 int scvx_batch_replan(scvx_batch* b) {

@@ -83,6 +83,17 @@ hipError_t launch_flight(const scvx_ctx* ctx, int B, int K, const double* x, con
 // argument checks shared by scvx_flight_check_f64[_host] and scvx_batch_flight_check (scvx_api.hip)
 int check_flight(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, int nsub, int mode, const void* report);
 
+// Segment audit (scvx_audit.hip): seg[B][K][SCVX_SEG_N], report[B][SCVX_FLIGHT_NREP] (the PLAN-mode report, reduced from seg) or
+// nullptr; one lane per (b, k), dt = 1 / (K + 1).
+hipError_t launch_segment_audit(const scvx_ctx* ctx, int B, int K, const double* x, const double* u, const double* sigma, int nsub,
+                                double* seg, double* report, hipStream_t st);
+int check_segment_audit(scvx_ctx* ctx, int B, int K, const void* x, const void* u, const void* sigma, int nsub, const void* seg);
+// scvx_batch_audit_margins: new = min(old + gain e_k, cap width_k) into marg [B][K+1][2] (lo alone) and pmarg [B][K+1][SCVX_PMARG_N];
+// capw = cap times the constant widths, the glide width is that of x [B][K+1][14]
+struct AuditCaps { double thrust, tilt, rate, cap, itan; };
+hipError_t launch_audit_margins(int B, int K, const double* seg, const double* x, double gain, double tol, const AuditCaps& capw,
+                                unsigned which, double* marg, double* pmarg, hipStream_t st);
+
 // Plan tracking (scvx_track.hip).  Gains: one wavefront per trajectory over the derivative tiles; gain[B][K][NU][14+NU],
 // p0[B][14+NU][14+NU] or nullptr; q / r / qf are host arrays.
 // Closed-loop flight (the flight check's kernel with TRACK set, scvx_flight.hip): dx0[B][14], xfly[B][K+1][14], ufly[B][K+1][NU] or nullptr.

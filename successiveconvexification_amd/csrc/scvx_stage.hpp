@@ -91,6 +91,7 @@ struct Dims {
     size_t xi, eta, nud, flights, s14, fed, jmean, jcov, flightq, pathq, pathv, zeta, theta;                           // sampled
     size_t vtile, sens;                                                                                                // vehicle errors
     size_t srep, satk;                                                                                                 // clamp-aware covariance
+    size_t aud;                                                                                                        // segment audit
     Dims(int B_, int K_, int NU, int S_ = 0, int m_ = 0, int nq_ = 0) {
         const size_t B = (size_t)B_, K = (size_t)K_, S = (size_t)S_, m = (size_t)m_, nq = (size_t)nq_, n = 14 + (size_t)NU, N = n + 14;
         x = B * (K + 1) * 14, u = B * (K + 1) * NU, b = B, seg = B * K * 14, deriv = B * K * 14 * (14 + 2 * NU + 1);
@@ -103,6 +104,7 @@ struct Dims {
         zeta = S * SCVX_VEH_N, theta = B * S * SCVX_VEH_N;
         vtile = B * K * SCVX_VTILE_N * 14, sens = B * (K + 1) * n * SCVX_VEH_N;
         srep = B * SCVX_SAT_NREP, satk = B * K * 4;
+        aud = B * K * SCVX_SEG_N;
     }
 };
 

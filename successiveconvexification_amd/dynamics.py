@@ -171,6 +171,42 @@ def flight_check_batch(cache: IntegratorCache, x, u, sigma, nsub=None, mode="sho
     return FlightReport(rep, xfly, mode)
 
 
+class SegmentReport:
+    """The segment audit of a batch of plans (scvx_segment_audit_f64, include/scvx.h): `seg` [B][K][11], one named [B][K] numpy view per
+    column (rep.DEFECT, rep.G_TMIN, ... -- _lib.SEG_COLUMNS), and `flight`, the PLAN-mode FlightReport reduced from seg on the device.
+    g <= 0 means satisfied, in the problem's own units; segment k runs from node k to node k + 1."""
+
+    def __init__(self, seg, flight_raw):
+        self.seg = np.asarray(seg, np.float64)
+        self.flight = FlightReport(flight_raw, None, "plan")
+        for name, i in _lib.SEG_INDEX.items():
+            setattr(self, name, self.seg[:, :, i])
+
+    def __len__(self):
+        return self.seg.shape[0]
+
+    def worst(self, name):
+        """(value [B], segment [B]) of the largest entry of column `name` in every plan; a NaN entry wins."""
+        g = getattr(self, name)
+        k = np.where(np.isnan(g).any(axis=1), np.isnan(g).argmax(axis=1), np.nan_to_num(g, nan=-np.inf).argmax(axis=1))
+        return g[np.arange(g.shape[0]), k], k
+
+
+def segment_audit_batch(cache: IntegratorCache, x, u, sigma, nsub=None) -> SegmentReport:
+    """Audit the plans x [B][K+1][14], u [B][K+1][nu], sigma [B] segment by segment on the device (scvx_segment_audit_f64_host): the
+    path functions of the PLAN-mode flight check, one row per segment.  nsub: RK4 substeps per segment (None = the cache's)."""
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    if x.ndim != 3 or x.shape[2] != 14 or u.shape != (x.shape[0], x.shape[1], cache.nu) or sigma.shape != (x.shape[0],):
+        raise ValueError("shape mismatch: x [B][K+1][14], u [B][K+1][%d], sigma [B]" % cache.nu)
+    B, K = x.shape[0], x.shape[1] - 1
+    f = dict(handle=cache.handle, B=B, K=K, x=x, u=u, sigma=sigma, nsub=cache.npts if nsub is None else nsub,
+             seg=np.empty((B, K, _lib.SEG_N)), report=np.empty((B, _lib.FLIGHT_NREP)))
+    _calls.call(cache._L, cache.handle, "scvx_segment_audit_f64_host", f)
+    return SegmentReport(f["seg"], f["report"])
+
+
 TRACK_DEFAULT_WEIGHTS = (1.0, 1.0, 100.0)   # q, r, qf on every component: a starting point, not tuning advice
 
 

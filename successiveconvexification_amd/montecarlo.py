@@ -515,6 +515,31 @@ def flight_summary(report, status, tol=0.0):
     return out
 
 
+def audit_summary(rep, status, tol=1e-7):
+    """What a Monte-Carlo batch has to say once its plans are audited segment by segment.  rep: a dynamics.SegmentReport or its seg
+    [N][K][11] array; status [N]: the SCvx statuses of scvx_solve.  Returns a plain dict: the number of converged plans and, per G_*
+    column over the converged plans, the share of plans and the share of segments with G > tol and the largest G (None where there is
+    no converged plan; a NaN entry counts as a violation).  Pure numpy."""
+    from ._lib import SEG_COLUMNS, SEG_INDEX, SEG_N
+    seg = np.asarray(getattr(rep, "seg", rep), np.float64)
+    if seg.ndim != 3 or seg.shape[2] != SEG_N:
+        raise ValueError("seg must be [N][K][%d]" % SEG_N)
+    status = np.asarray(status).reshape(-1)
+    if status.shape[0] != seg.shape[0]:
+        raise ValueError("seg has %d rows, status %d" % (seg.shape[0], status.shape[0]))
+    conv = seg[status == 0]
+    out = {"n": int(seg.shape[0]), "converged": int(conv.shape[0]), "tol": float(tol), "stats": {}}
+    for n in (c for c in SEG_COLUMNS if c.startswith("G_")):
+        g = conv[:, :, SEG_INDEX[n]]
+        if g.shape[0] == 0:
+            out["stats"][n] = None
+            continue
+        bad = ~(g <= tol)
+        out["stats"][n] = {"plans": float(np.mean(bad.any(axis=1))), "segments": float(np.mean(bad)),
+                           "max": float("nan") if np.isnan(g).any() else float(np.max(g))}
+    return out
+
+
 def dispersion_summary(covreport, status):
     """What a Monte-Carlo batch of plans has to say once its covariance analysis is done.  covreport: a dynamics.CovReport or its raw
     [N][16] array; status [N]: the SCvx statuses of scvx_solve.  Returns a plain dict: counts by SCvx status, the number of converged

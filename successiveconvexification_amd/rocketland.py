@@ -158,6 +158,19 @@ def robustify(iteration: ProblemIteration, cache: IntegratorCache = None, S0=Non
     return _snapshot(iteration.problem, cache, batch), lo[0], hi[0]
 
 
+def harden(iteration: ProblemIteration, cache: IntegratorCache = None, constraints=("thrust", "glide", "tilt", "rate"), rounds=3, gain=1.5,
+           tol=1e-7, restart="replan", nsub=None):
+    """Replan an iterate under back-offs taken from its own segment audit until it holds its constraints between the nodes
+    (ScvxBatch.harden on the iterate's device batch).  Returns (the new ProblemIteration, the dynamics.SegmentReport of its plan, the
+    rounds used); raises like solve_step when the conic solve fails.  The limits are those of ScvxBatch.harden."""
+    cache = cache if cache is not None else iteration.cache
+    batch = iteration.model
+    st, it, nu, dj, rep, used = batch.harden(constraints=constraints, rounds=rounds, gain=gain, tol=tol, restart=restart, nsub=nsub)
+    if st[0] in (3, 4, 5):  # rocketland.jl:273-276
+        raise RuntimeError("Non-optimal result %s exiting" % {3: "SLOW_PROGRESS", 4: "NUMERICAL_ERROR", 5: "INFEASIBLE"}[int(st[0])])
+    return _snapshot(iteration.problem, cache, batch), rep, used
+
+
 def navigation(iteration: ProblemIteration, cache: IntegratorCache = None, S0=None, N0=None, H=None, rm=None, w=None, q=None, r=None,
                qf=None, dense=False, vehicle=None, clamp=False):
     """Navigation-error covariance analysis of an iterate's plan flown on an estimate under the time-varying LQR gains about it: S0 the
